@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """Headline benchmark: end-to-end saliency+crop frames/s on synthetic 640x360 frame batches.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times ONE region of K steps, writes the outputs of its last step if --dump-outputs is
+given, and prints the result line (metric, value, unit, higher_is_better, dtype, ms_per_step; roofline, cpu_baseline and
+the extra config.* measurements are null).  --full adds everything else this file measures: the check of the streaming
+schedule against the plain call, the un-pipelined per-class profile and the roofline, --repeats timed regions (default
+15, the median reported), the one-batch-for-every-slot and matrix-pipe variants, config 3 and the CPU / PyTorch-ROCm
+baselines.
+
+--dump-outputs DIR: after the timed region, what the timed path computed in its last step -- the centres of that step's
+batch (centres.npy, float64 [B, 2], NaN = no centre), the crop windows computed from them (boxes.npy, float64 [B, 4])
+and the filtered saliency maps (maps.npy, float32 [B, 140, 250]) -- written as DIR/<name>.npy by rank 0.  Frames and
+weights are functions of fixed seeds, so two builds run with the same arguments can be compared output for output.
 
 N > 1 without WORLD_SIZE in the environment: this process starts `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ...` on this same file as a CHILD (before anything here has touched the
@@ -26,7 +38,7 @@ flight.  The synthetic frames are sized so that a thresholded map holds ~2 k poi
 config.points_per_map reports what the run saw.  The K-step timed region is repeated --repeats times; ms_per_step / value
 are the median region, config.repeats lists all of them.
 
-Rank 0 prints ONE JSON line.  `roofline` describes the kernel class that takes the most device time
+Rank 0 prints ONE JSON line.  (--full) `roofline` describes the kernel class that takes the most device time
 (HIP events recorded by the library around each launch of that class, on the stream it is launched on):
   achieved / frac          algorithmic FLOPs (or bytes) of the class per step / the summed durations of its launches
                            in an UN-PIPELINED step (one batch in flight: launch durations that do not overlap anything,
@@ -69,10 +81,20 @@ def parse_args(argv=None):
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--pipeline', type=int, default=4, help='batches in flight per GPU (engines / HIP streams)')
-    ap.add_argument('--cpu-sample', type=int, default=160, help='frames of the CPU baseline sample (0 = skip)')
-    ap.add_argument('--iso-steps', type=int, default=3, help='un-pipelined profiling steps per kernel class')
-    ap.add_argument('--repeats', type=int, default=15, help='timed regions of --steps steps each; the median is reported')
-    return ap.parse_args(argv)
+    ap.add_argument('--cpu-sample', type=int, default=160, help='frames of the CPU baseline sample (0 = skip; --full)')
+    ap.add_argument('--iso-steps', type=int, default=3, help='un-pipelined profiling steps per kernel class (--full)')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed regions of --steps steps each; the median is reported (default: 1, with --full 15)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement and check beyond the headline figure (profiles, variants, config 3, baselines)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/<name>.npy')
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 15 if args.full else 1
+    if args.dump_outputs and args.steps < 1:
+        ap.error('--dump-outputs needs --steps >= 1')
+    return args
 
 
 def self_launch(args):
@@ -156,6 +178,19 @@ def host_boxes(xy, ratio='1:3'):
         ys.append(last[1])
     VD['dxs'], VD['dys'] = xs, ys
     return S.sc_compute_bb(VD, {})['bbs']
+
+
+def dump_outputs(out_dir, last, slots, B):
+    """--dump-outputs: the last timed step's centres, crop windows and filtered maps -> out_dir/<name>.npy."""
+    if 'xy' not in last:
+        raise SystemExit('bench.py: the outputs of the last timed step were not recorded')
+    sl = slots[last['slot']]
+    maps = sl.pipe.final_rows(last['first'], B) if 'first' in last else sl.maps
+    arrays = dict(centres=np.asarray(last['xy'], np.float64), boxes=np.asarray(last['boxes'], np.float64),
+                  maps=maps.cpu().numpy().astype(np.float32))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def cpu_baseline(sd, frames_u8, CP, flags):
@@ -339,6 +374,7 @@ def config3_job(world, rank, dist_on, dev, sd, lanes, rccl_init_s, mode='residen
 
 def main():
     args = parse_args()
+    full = args.full
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -402,6 +438,7 @@ def main():
             self.start = torch.cuda.Event(enable_timing=True)
             self.done = torch.cuda.Event(enable_timing=True)
             self.pending = False
+            self.step = None                                # the step of run() this slot's pending batch belongs to
             # every slot works on its OWN batch (same generator, another seed): the maps of the batches in flight then hold
             # different numbers of points (round-4 verdict: one batch fed every step of every slot, so every map had the same N);
             # slot 0 keeps the batch of rounds 1-4 (the un-pipelined measurements and the CPU baseline use it)
@@ -446,6 +483,7 @@ def main():
         batch inside the timed region."""
         boxes = None
         pend = {}                                             # (slot, batch number on its stream) -> [centres, count]
+        last_key = ((steps - 1) % P, (steps - 1) // P)        # the batch of the last step
         for sl in slots:
             sl.pipe.reset()
 
@@ -458,6 +496,8 @@ def main():
                 ent[1] += 1
                 if ent[1] == B:
                     boxes = host_boxes(ent[0])
+                    if (k, g // B) == last_key:
+                        last.update(slot=k, first=(g // B) * B, xy=ent[0], boxes=boxes)
                     del pend[(k, g // B)]
             host_t['boxes'] += time.perf_counter() - t1
 
@@ -485,20 +525,31 @@ def main():
             spans['net'] += net; spans['tail'] += tail; spans['n'] += 1
         return boxes
 
+    last = {}                                                  # the outputs of the last step of the latest run (--dump-outputs)
+
     def run(steps):
+        last.clear()
         if STREAMED:
             return run_streamed(steps)
         boxes = None
+
+        def finish(sl):
+            b = sl.finish()
+            if sl.step == steps - 1:
+                last.update(slot=slots.index(sl), xy=sl.xy_host.numpy().copy(), boxes=b)
+            return b
+
         for s in range(steps):
             sl = slots[s % P]
             if sl.pending:
-                boxes = sl.finish()
+                boxes = finish(sl)
             t0 = time.perf_counter()
+            sl.step = s
             sl.enqueue()
             host_t['enqueue'] += time.perf_counter() - t0
         for sl in slots:
             if sl.pending:
-                boxes = sl.finish()
+                boxes = finish(sl)
         return boxes
 
     def barrier():
@@ -506,10 +557,13 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    boxes = run(max(args.warmup, P))
+    plain = os.environ.get('BENCH_PLAIN', '0') == '1'            # counter passes (tools/refresh_profiles.sh): only warm-up + timed steps run
+    # at least 48 warm-up steps (~65 ms of pipelined work) before the clock starts: after 5 or 12 the first timed region of 20
+    # steps ran 1 - 3 % slower than the regions after it, after 24 or 60 it did not (counter passes keep their exact step count)
+    boxes = run(max(args.warmup, P) if plain else max(args.warmup, P, 48))
     # the timed path against the plain call on one batch (cheap; the full statement is tests/test_gpu_pipeline.py): the
     # streaming scheduler must give the centres of the call that runs every blend chain out in rounds
-    if STREAMED:
+    if STREAMED and full:
         slots[0].enqueue()
         slots[0].finish()
         xy_plain = slots[0].xy_host.numpy().copy()
@@ -525,8 +579,7 @@ def main():
     eng = slots[0].eng
     iso = max(1, args.iso_steps)
     per_class, raw_class = {}, {}
-    plain = os.environ.get('BENCH_PLAIN', '0') == '1'            # counter passes (tools/refresh_profiles.sh): only warm-up + timed steps run
-    for k in eng.KERNEL_CLASSES:
+    for k in (eng.KERNEL_CLASSES if full else ()):
         if plain:
             per_class[k] = (1.0 if k == 'pw' else 0.0, 1.0)
             raw_class[k] = (per_class[k][0], 0.0)
@@ -541,12 +594,14 @@ def main():
     eng.profile_enable(None)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
-    for _ in range(0 if plain else 10):
+    for _ in range(0 if plain or not full else 10):
         slots[0].enqueue()
         slots[0].finish()
-    latency_ms = None if plain else (time.perf_counter() - t1) / 10 * 1e3
+    latency_ms = None if plain or not full else (time.perf_counter() - t1) / 10 * 1e3
     # points per map of this workload (what the clustering kernels see)
-    if plain:
+    if not full:
+        npts = None
+    elif plain:
         npts = np.zeros(B, np.int64)                              # (counter passes: nothing but warm-up + timed steps may run)
     else:
         with torch.cuda.stream(slots[0].stream):
@@ -557,11 +612,11 @@ def main():
                 _, st_ = eng.cluster_center_(m_, flags, CP, want_stats=True)
                 npl.append(st_[:, 0].cpu().numpy())
         npts = np.concatenate(npl)
-    dominant = max(per_class, key=lambda k: per_class[k][0])
+    dominant = max(per_class, key=lambda k: per_class[k][0]) if full else None
     # BENCH_LIVE_PROFILE=1 also records the dominant class's events INSIDE the timed region (roofline.*_in_flight).  Off by
     # default: 76 event records per step on every stream cost 2-3 % of the step with four batches in flight (1.49 -> 1.45 ms)
     # and more with deeper pipelines; roofline.frac comes from the un-pipelined passes above either way.
-    live = os.environ.get('BENCH_LIVE_PROFILE', '0') == '1' and not plain
+    live = os.environ.get('BENCH_LIVE_PROFILE', '0') == '1' and not plain and full
     for sl in slots:
         sl.eng.profile_enable(dominant if live else None)
         sl.eng.profile_read()
@@ -582,6 +637,8 @@ def main():
     order_r = sorted(range(len(regions)), key=lambda i: regions[i][0])
     dt_local, host_ms, span_ms = regions[order_r[len(order_r) // 2]]
     dt = dt_local
+    if args.dump_outputs and rank == 0:                       # the last region's last step (the slots are untouched since)
+        dump_outputs(args.dump_outputs, last, slots, B)
     fl_ms, fl_launches = 0.0, 0
     for sl in slots:
         ms, cnt = sl.eng.profile_read()
@@ -603,7 +660,7 @@ def main():
     # rounds 1-4 fed ONE batch to every slot (every map of a step then held the same number of points): the same timed region that
     # way, three repeats, for comparison across rounds (config.one_batch_for_every_slot)
     same_batch = None
-    if not plain and P > 1:
+    if full and not plain and P > 1:
         own = [sl.frames for sl in slots]
         for sl in slots:
             sl.frames = frames
@@ -622,7 +679,7 @@ def main():
     # the OTHER matrix pipe (SVC_MX=f32 | bf16x6), timed beside the default in the same run: the same timed region on engines created
     # with it, five repeats, median.  Reported under config.matrix_pipe_variant, never as `value`.
     variant = None
-    if os.environ.get('BENCH_VARIANT', '1') != '0' and not plain:
+    if full and os.environ.get('BENCH_VARIANT', '1') != '0' and not plain:
         other_pipe = 'f32' if eng.matrix_pipe() == 'bf16x6' else 'bf16x6'
         old_mx = os.environ.get('SVC_MX')
         try:
@@ -658,7 +715,7 @@ def main():
                 os.environ['SVC_MX'] = old_mx
             variant = dict(error=repr(e))
     c3 = c3_host = c3_shot = c3_shot3 = None
-    if os.environ.get('BENCH_CONFIG3', '1') != '0' and not plain:
+    if full and os.environ.get('BENCH_CONFIG3', '1') != '0' and not plain:
         c3_lanes = int(os.environ.get('BENCH_CONFIG3_LANES', 12))
         try:
             c3 = config3_job(world, rank, dist_on, dev, sd, c3_lanes, rccl_init_s)
@@ -684,106 +741,107 @@ def main():
                     c3_shot3 = r_
             torch.cuda.empty_cache()
     if rank == 0:
-        front_fused = eng.front_fused()
-        work = layer_work(B, front_fused=front_fused)
-        steps = max(args.steps, 1)
-        iso_ms, iso_n = per_class[dominant]
-        byte_work = {'pw': work['pw_bytes'], 'dw': work['dw_bytes'], 'lanczos': B * (140 * 250 * 3 + 256 * 416 * 12.0),
-                     'stem': B * (256 * 416 * 12.0 + 128 * 208 * 128.0), 'resize': B * (360 * 640 * 3 + 140 * 250 * 3.0),
-                     'smooth': B * (32 * 52 * 4 + 140 * 250 * 9.0)}.get(dominant, work['map_bytes'])
-        if dominant == 'pw':
-            unit_work, peak, unit, bound, scale = work['pw_flops'], MFMA_F32_PEAK_TFLOPS, 'TFLOP/s', 'mfma', 1e12
-        else:
-            unit_work, peak, unit, bound, scale = byte_work, HBM_PEAK_GBS, 'GB/s', 'hbm', 1e9
-        rate = lambda ms_per_step: unit_work / (ms_per_step * 1e-3) / scale if ms_per_step > 0 else 0.0
-        ach = rate(iso_ms)
-        roof = dict(bound=bound, kernel=dominant, achieved=round(ach, 3), peak=peak, unit=unit, frac=round(ach / peak, 5),
-                    measured='HIP events around every launch of the class in %d un-pipelined steps (one batch in flight) '
-                             'before the timed region' % iso,
-                    launches_per_step=round(iso_n, 2), class_ms_per_step=round(iso_ms, 4),
-                    class_ms_per_step_event_corrected=round(raw_class[dominant][0], 4), empty_event_pair_ms=round(raw_class[dominant][1], 5),
-                    frac_event_corrected=round(rate(raw_class[dominant][0]) / peak, 5) if raw_class[dominant][0] > 0 else None,
-                    event_correction='frac / achieved / class_ms_per_step are the RAW event-pair durations (they include the events\' own '
-                                     'cost, so they read a few percent below a profiler\'s kernel durations); *_event_corrected takes 0.75 x '
-                                     'an empty event pair off every launch',
-                    avg_launch_ms=round(iso_ms / max(iso_n, 1), 5),
-                    algorithmic_per_step=unit_work, algorithmic_unit='FLOP' if dominant == 'pw' else 'B',
-                    frac_wall=round(rate(dt / steps * 1e3) / peak, 5))
-        if live and fl_launches:
-            fl = rate(fl_ms / steps)
-            roof.update(achieved_in_flight=round(fl, 3), frac_in_flight=round(fl / peak, 5),
-                        avg_launch_ms_in_flight=round(fl_ms / fl_launches, 5),
-                        in_flight_note='timed region, %d batches in flight: launch durations overlap other streams\' kernels, '
-                                       'their sum (%.3f ms per step) exceeds the wall clock' % (P, fl_ms / steps))
-        if dominant == 'pw':
-            gbs = work['pw_bytes'] / (iso_ms * 1e-3) / 1e9
-            roof.update(hbm_achieved_GBs=round(gbs, 1), hbm_frac=round(gbs / HBM_PEAK_GBS, 5),
-                        hbm_note='un-fused layer-wise fp32 traffic of the class (in + out + weights) / class time')
-        roof['traffic'] = None
-        try:
-            src = next(os.path.join('profiles', f) for f in ('r06_pmc_traffic.json', 'r05_pmc_traffic.json', 'r04_pmc_traffic.json', 'r03_pmc_traffic.json')
-                       if os.path.isfile(os.path.join(ROOT, 'profiles', f)))
-            with open(os.path.join(ROOT, src)) as fp:
-                c = json.load(fp)['classes'][dominant]
-            roof.update(traffic=c['hbm_bytes_per_launch'], traffic_per_step=c.get('hbm_bytes_per_step'),
-                        traffic_source='%s (stored rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over bench.py --pipeline 1, '
-                                       'reduced by tools/pmc_traffic.py; not re-measured in this run)' % src)
-        except Exception:
-            pass
-        roof['class_ms_per_step_all'] = {k: round(v[0], 4) for k, v in per_class.items()}
-        net_classes = [k for k in per_class if k not in ('compact', 'core', 'prim', 'finish')]
-        roof['device_ms_per_unpipelined_step'] = dict(
-            network=round(sum(per_class[k][0] for k in net_classes), 4), tail=round(sum(per_class[k][0] for k in ('compact', 'core', 'prim', 'finish')), 4),
-            note='summed launch durations of one un-pipelined step: the tail (one 1024-thread workgroup per map: 32 of 256 CUs) is the '
-                 'larger DEVICE time and the smaller share of the chip; `kernel` above is the largest single class')
-        # which matrix pipe the class ran on (svc_matrix_pipe): with split-bf16 operands every f32 operand is three bf16 planes
-        # (24 significant bits) and six plane pairs per product are accumulated in f32 -- `frac` stays the ALGORITHMIC f32 FLOPs
-        # against the fp32-MFMA roof (it may now exceed what that pipe could do), the bf16 roof is quoted beside it
-        mp = eng.matrix_pipe()
-        roof['matrix_pipe'] = mp
-        if dominant == 'pw':
-            roof['peak_bf16_TFLOPs'] = MFMA_BF16_PEAK_TFLOPS
-            roof['frac_vs_bf16_roof'] = round(ach / MFMA_BF16_PEAK_TFLOPS, 5)
-            if mp == 'bf16x6':
-                roof['frac_vs_bf16_roof_executed'] = round(6.0 * ach / MFMA_BF16_PEAK_TFLOPS, 5)
-                roof['matrix_pipe_note'] = ('bf16x6 (the default since round 5): v_mfma_f32_32x32x16_bf16 on operands split into three bf16 planes (8 + 8 + 8 = 24 '
-                                            'significant bits), six plane pairs per product, f32 accumulation; the expand GEMM of fused blocks 2, 3, '
-                                            '5-7 and every un-fused 1x1 convolution run this way, block 4 and the project GEMMs of blocks 2-6 on the '
-                                            'fp32 MFMA; executed = 6 x algorithmic FLOPs')
-            else:
-                roof['matrix_pipe_note'] = ('f32 (SVC_MX=f32): v_mfma_f32_32x32x2_f32 / 16x16x4 (exact f32 products); the split-bf16 form is measured '
-                                            'beside it as config.matrix_pipe_variant')
-        if front_fused:
-            roof['class_note'] = ("'stem' = k_front: LANCZOS + features.0 + features.1 in one kernel; features.1's project is not in "
-                                  "the 'pw' FLOPs")
-        cpu = None
-        if world == 1 and args.cpu_sample > 0:
-            torch.set_num_threads(min(16, os.cpu_count() or 1))    # batch-1 convs stop scaling (and collapse) beyond this
-            nb = max(1, args.cpu_sample // B)
-            secs, nfr = 0.0, 0
-            for b in range(nb):                                    # whole steps of the same workload, new frames each
-                fh = frames_host if b == 0 else synth.blob_frames(B, 360, 640, seed=200 + b, **BENCH_BLOBS)
-                fps_b, s_b = cpu_baseline(sd, fh, CP, flags)
-                secs += s_b
-                nfr += B
-            cpu = dict(value=round(nfr / secs, 3), unit='frames/s', cores=torch.get_num_threads(), host_cpu_count=os.cpu_count(), kind='port',
-                       sample='%d steps of the same workload (%d frames), oracle/ (PyTorch-CPU fp32 forward at batch 1, '
-                              'NumPy tail), %.1f s' % (nb, nfr, secs))
-            if os.environ.get('BENCH_TORCH_BASELINE', '1') != '0':  # the reference's own way of running the network, on this GPU
-                try:
-                    cpu['network_under_pytorch_rocm'] = reference_formulation_on_gpu(sd, dev, B)
-                except Exception as e:                              # (MIOpen needs a writable cache directory: a baseline must not fail the bench)
-                    cpu['network_under_pytorch_rocm'] = dict(error='%s: %s' % (type(e).__name__, str(e)[:200]))
         value = world * B * args.steps / dt
-        tail_classes = {k: round(per_class[k][0], 4) for k in ('compact', 'core', 'prim', 'finish')}
-        roof['tail'] = dict(total_ms=round(sum(tail_classes.values()), 4), prim_ms=tail_classes['prim'], finish_ms=tail_classes['finish'], core_ms=tail_classes['core'],
-                            compact_ms=tail_classes['compact'],
-                            points_per_map=dict(min=int(npts.min()), mean=round(float(npts.mean()), 1), max=int(npts.max())),
-                            us_per_frame=round(sum(tail_classes.values()) / B * 1e3, 2),
-                            note='class ms per un-pipelined step of %d maps (three tail rounds: the batch starts a shot).  Default: a '
-                                 'round is two fused launches -- prim = k_tail_front (compact + core + Prim), finish = k_tail_back '
-                                 '(sort + hierarchy + finish), compact / core then read 0; SVC_TAIL_MERGE=0: one launch per stage, '
-                                 'finish = k_sort + k_tree_par + k_finish' % B)
+        roof = cpu = None
+        if full:
+            front_fused = eng.front_fused()
+            work = layer_work(B, front_fused=front_fused)
+            steps = max(args.steps, 1)
+            iso_ms, iso_n = per_class[dominant]
+            byte_work = {'pw': work['pw_bytes'], 'dw': work['dw_bytes'], 'lanczos': B * (140 * 250 * 3 + 256 * 416 * 12.0),
+                         'stem': B * (256 * 416 * 12.0 + 128 * 208 * 128.0), 'resize': B * (360 * 640 * 3 + 140 * 250 * 3.0),
+                         'smooth': B * (32 * 52 * 4 + 140 * 250 * 9.0)}.get(dominant, work['map_bytes'])
+            if dominant == 'pw':
+                unit_work, peak, unit, bound, scale = work['pw_flops'], MFMA_F32_PEAK_TFLOPS, 'TFLOP/s', 'mfma', 1e12
+            else:
+                unit_work, peak, unit, bound, scale = byte_work, HBM_PEAK_GBS, 'GB/s', 'hbm', 1e9
+            rate = lambda ms_per_step: unit_work / (ms_per_step * 1e-3) / scale if ms_per_step > 0 else 0.0
+            ach = rate(iso_ms)
+            roof = dict(bound=bound, kernel=dominant, achieved=round(ach, 3), peak=peak, unit=unit, frac=round(ach / peak, 5),
+                        measured='HIP events around every launch of the class in %d un-pipelined steps (one batch in flight) '
+                                 'before the timed region' % iso,
+                        launches_per_step=round(iso_n, 2), class_ms_per_step=round(iso_ms, 4),
+                        class_ms_per_step_event_corrected=round(raw_class[dominant][0], 4), empty_event_pair_ms=round(raw_class[dominant][1], 5),
+                        frac_event_corrected=round(rate(raw_class[dominant][0]) / peak, 5) if raw_class[dominant][0] > 0 else None,
+                        event_correction='frac / achieved / class_ms_per_step are the RAW event-pair durations (they include the events\' own '
+                                         'cost, so they read a few percent below a profiler\'s kernel durations); *_event_corrected takes 0.75 x '
+                                         'an empty event pair off every launch',
+                        avg_launch_ms=round(iso_ms / max(iso_n, 1), 5),
+                        algorithmic_per_step=unit_work, algorithmic_unit='FLOP' if dominant == 'pw' else 'B',
+                        frac_wall=round(rate(dt / steps * 1e3) / peak, 5))
+            if live and fl_launches:
+                fl = rate(fl_ms / steps)
+                roof.update(achieved_in_flight=round(fl, 3), frac_in_flight=round(fl / peak, 5),
+                            avg_launch_ms_in_flight=round(fl_ms / fl_launches, 5),
+                            in_flight_note='timed region, %d batches in flight: launch durations overlap other streams\' kernels, '
+                                           'their sum (%.3f ms per step) exceeds the wall clock' % (P, fl_ms / steps))
+            if dominant == 'pw':
+                gbs = work['pw_bytes'] / (iso_ms * 1e-3) / 1e9
+                roof.update(hbm_achieved_GBs=round(gbs, 1), hbm_frac=round(gbs / HBM_PEAK_GBS, 5),
+                            hbm_note='un-fused layer-wise fp32 traffic of the class (in + out + weights) / class time')
+            roof['traffic'] = None
+            try:
+                src = next(os.path.join('profiles', f) for f in ('r06_pmc_traffic.json', 'r05_pmc_traffic.json', 'r04_pmc_traffic.json', 'r03_pmc_traffic.json')
+                           if os.path.isfile(os.path.join(ROOT, 'profiles', f)))
+                with open(os.path.join(ROOT, src)) as fp:
+                    c = json.load(fp)['classes'][dominant]
+                roof.update(traffic=c['hbm_bytes_per_launch'], traffic_per_step=c.get('hbm_bytes_per_step'),
+                            traffic_source='%s (stored rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over bench.py --pipeline 1, '
+                                           'reduced by tools/pmc_traffic.py; not re-measured in this run)' % src)
+            except Exception:
+                pass
+            roof['class_ms_per_step_all'] = {k: round(v[0], 4) for k, v in per_class.items()}
+            net_classes = [k for k in per_class if k not in ('compact', 'core', 'prim', 'finish')]
+            roof['device_ms_per_unpipelined_step'] = dict(
+                network=round(sum(per_class[k][0] for k in net_classes), 4), tail=round(sum(per_class[k][0] for k in ('compact', 'core', 'prim', 'finish')), 4),
+                note='summed launch durations of one un-pipelined step: the tail (one 1024-thread workgroup per map: 32 of 256 CUs) is the '
+                     'larger DEVICE time and the smaller share of the chip; `kernel` above is the largest single class')
+            # which matrix pipe the class ran on (svc_matrix_pipe): with split-bf16 operands every f32 operand is three bf16 planes
+            # (24 significant bits) and six plane pairs per product are accumulated in f32 -- `frac` stays the ALGORITHMIC f32 FLOPs
+            # against the fp32-MFMA roof (it may now exceed what that pipe could do), the bf16 roof is quoted beside it
+            mp = eng.matrix_pipe()
+            roof['matrix_pipe'] = mp
+            if dominant == 'pw':
+                roof['peak_bf16_TFLOPs'] = MFMA_BF16_PEAK_TFLOPS
+                roof['frac_vs_bf16_roof'] = round(ach / MFMA_BF16_PEAK_TFLOPS, 5)
+                if mp == 'bf16x6':
+                    roof['frac_vs_bf16_roof_executed'] = round(6.0 * ach / MFMA_BF16_PEAK_TFLOPS, 5)
+                    roof['matrix_pipe_note'] = ('bf16x6 (the default since round 5): v_mfma_f32_32x32x16_bf16 on operands split into three bf16 planes (8 + 8 + 8 = 24 '
+                                                'significant bits), six plane pairs per product, f32 accumulation; the expand GEMM of fused blocks 2, 3, '
+                                                '5-7 and every un-fused 1x1 convolution run this way, block 4 and the project GEMMs of blocks 2-6 on the '
+                                                'fp32 MFMA; executed = 6 x algorithmic FLOPs')
+                else:
+                    roof['matrix_pipe_note'] = ('f32 (SVC_MX=f32): v_mfma_f32_32x32x2_f32 / 16x16x4 (exact f32 products); the split-bf16 form is measured '
+                                                'beside it as config.matrix_pipe_variant')
+            if front_fused:
+                roof['class_note'] = ("'stem' = k_front: LANCZOS + features.0 + features.1 in one kernel; features.1's project is not in "
+                                      "the 'pw' FLOPs")
+            if world == 1 and args.cpu_sample > 0:
+                torch.set_num_threads(min(16, os.cpu_count() or 1))    # batch-1 convs stop scaling (and collapse) beyond this
+                nb = max(1, args.cpu_sample // B)
+                secs, nfr = 0.0, 0
+                for b in range(nb):                                    # whole steps of the same workload, new frames each
+                    fh = frames_host if b == 0 else synth.blob_frames(B, 360, 640, seed=200 + b, **BENCH_BLOBS)
+                    fps_b, s_b = cpu_baseline(sd, fh, CP, flags)
+                    secs += s_b
+                    nfr += B
+                cpu = dict(value=round(nfr / secs, 3), unit='frames/s', cores=torch.get_num_threads(), host_cpu_count=os.cpu_count(), kind='port',
+                           sample='%d steps of the same workload (%d frames), oracle/ (PyTorch-CPU fp32 forward at batch 1, '
+                                  'NumPy tail), %.1f s' % (nb, nfr, secs))
+                if os.environ.get('BENCH_TORCH_BASELINE', '1') != '0':  # the reference's own way of running the network, on this GPU
+                    try:
+                        cpu['network_under_pytorch_rocm'] = reference_formulation_on_gpu(sd, dev, B)
+                    except Exception as e:                              # (MIOpen needs a writable cache directory: a baseline must not fail the bench)
+                        cpu['network_under_pytorch_rocm'] = dict(error='%s: %s' % (type(e).__name__, str(e)[:200]))
+            tail_classes = {k: round(per_class[k][0], 4) for k in ('compact', 'core', 'prim', 'finish')}
+            roof['tail'] = dict(total_ms=round(sum(tail_classes.values()), 4), prim_ms=tail_classes['prim'], finish_ms=tail_classes['finish'], core_ms=tail_classes['core'],
+                                compact_ms=tail_classes['compact'],
+                                points_per_map=dict(min=int(npts.min()), mean=round(float(npts.mean()), 1), max=int(npts.max())),
+                                us_per_frame=round(sum(tail_classes.values()) / B * 1e3, 2),
+                                note='class ms per un-pipelined step of %d maps (three tail rounds: the batch starts a shot).  Default: a '
+                                     'round is two fused launches -- prim = k_tail_front (compact + core + Prim), finish = k_tail_back '
+                                     '(sort + hierarchy + finish), compact / core then read 0; SVC_TAIL_MERGE=0: one launch per stage, '
+                                     'finish = k_sort + k_tree_par + k_finish' % B)
         out = dict(metric='frames/sec end-to-end saliency+crop on 640x360', value=round(value, 2), unit='frames/s',
                    n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=round(dt / max(args.steps, 1) * 1e3, 4),
                    higher_is_better=True, scaling='weak', vs_baseline=None, dtype='f32', data='synthetic',
@@ -801,7 +859,8 @@ def main():
                                ranks_share_gpus=('BENCH_SHARE_GPU=1: %d ranks on %d visible GPU(s) over gloo -- a functional run of the multi-rank '
                                                  'path, NOT a measurement' % (world, torch.cuda.device_count())) if share_gpu else None,
                                per_rank_frames_per_s=[round(v, 1) for v in rank_fps],
-                               points_per_map=dict(min=int(npts.min()), mean=round(float(npts.mean()), 1), max=int(npts.max())),
+                               points_per_map=(None if npts is None else
+                                               dict(min=int(npts.min()), mean=round(float(npts.mean()), 1), max=int(npts.max()))),
                                repeats=dict(regions=len(regions), ms_per_step=[round(r[0] / max(args.steps, 1) * 1e3, 4) for r in regions],
                                             reported='median'),
                                one_batch_in_flight=(None if latency_ms is None else

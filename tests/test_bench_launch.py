@@ -27,3 +27,12 @@ def test_bench_rejects_mismatched_world():
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '4'], capture_output=True, text=True,
                        env=env, timeout=600)
     assert p.returncode != 0 and 'WORLD_SIZE=2' in (p.stdout + p.stderr)
+
+
+def test_bench_dump_outputs_needs_a_timed_step():
+    env = dict(os.environ)
+    env.pop('WORLD_SIZE', None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '0', '--dump-outputs',
+                        os.path.join(ROOT, 'unused')], capture_output=True, text=True, env=env, timeout=600)
+    assert p.returncode == 2 and '--dump-outputs needs --steps >= 1' in p.stderr
+    assert not os.path.exists(os.path.join(ROOT, 'unused'))

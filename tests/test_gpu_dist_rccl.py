@@ -1,5 +1,5 @@
 """-m gpu: the multi-rank code path of bench.py on RCCL with the one GPU a test box has: a child
-`python -m torch.distributed.run --nproc-per-node 1 bench.py --gpus 1` with BENCH_FORCE_DIST=1 takes
+`python -m torch.distributed.run --nproc-per-node 1 bench.py --gpus 1 --full` with BENCH_FORCE_DIST=1 takes
 init_process_group('nccl'), the barriers, the MAX all-reduce of the timings and the box gather (dist.gather_boxes)
 on the device -- and runs the sharded 200-video job (config.config3: dist.crop_job over RCCL), whose gathered windows must be
 those of a single process without torch.distributed.  This module touches no GPU before the child has finished (no `engine`
@@ -25,7 +25,7 @@ def test_bench_under_torchrun_takes_the_rccl_path_at_world_1():
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-           '--cpu-sample', '0', '--repeats', '1', '--iso-steps', '1']
+           '--cpu-sample', '0', '--repeats', '1', '--iso-steps', '1', '--full']
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith('{')][-1]
@@ -57,7 +57,7 @@ def test_bench_self_launch_at_world_2_with_the_ranks_sharing_the_gpu():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--cpu-sample', '0',
-           '--repeats', '1', '--iso-steps', '1']
+           '--repeats', '1', '--iso-steps', '1', '--full']
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]

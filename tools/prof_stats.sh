@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_stats
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw -- python3 $R/bench.py --cpu-sample 0 "$@" > $O/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw -- python3 $R/bench.py --cpu-sample 0 --full "$@" > $O/bench.log 2>&1
 cp $(ls $O/raw/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv
 rm -rf $O/raw
 python3 - <<PY
