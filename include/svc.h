@@ -16,6 +16,7 @@
  *                               3rd_party_libs/unisal/unisal_handler.py:68-71 and
  *                               Trainer.model / init_unisal_weights, unisal/train.py:1449-1456, :1200-1209
  *   svc_resize_frames_u8        cv2.resize(frame,(SAL_W,SAL_H),INTER_LINEAR), smartVidCrop.py:333-335, :633-635
+ *   svc_render_crops_u8         the crop loop of sc_renderer(), smartVidCrop.py:1801-1921 (frame[by1:by2, bx1:bx2, :], :1910)
  *   svc_saliency_u8             unisal_handler.predictions_from_memory_nuint8_np(),
  *                               3rd_party_libs/unisal/unisal_handler.py:85-86 ->
  *                               Trainer.generate_predictions_from_image_memory_nuint8_np, unisal/train.py:1255-1279
@@ -72,8 +73,11 @@ const char *svc_last_error(void);
  * checks it once after dlopen.  2 = SvcParams starts with struct_size and carries resize_factor.
  * 3 = SvcParams ends with com_km; SVC_MAP_HELD is honoured by svc_cluster_center (a v2 library ignores the bit), svc_debug_cluster_state
  *     returns 32 header words, svc_debug_round_plan / svc_debug_argsort_u32 / svc_transnet_* exist.
- * 4 = the host stages svc_host_* (SvcTemporalParams) and svc_saliency_thresholded_u8 exist. */
-#define SVC_ABI_VERSION 5
+ * 4 = the host stages svc_host_* (SvcTemporalParams) and svc_saliency_thresholded_u8 exist.
+ * 5 = svc_saliency_census_u8, svc_transnet_predict_rows and svc_transnet_config_get / _set exist; svc_create rejects an
+ *     unknown spelling of SVC_MX / SVC_SHOT_MX with SVC_E_INVALID.
+ * 6 = svc_render_crops_u8 (SVC_RENDER_BGR) and the profile class SVC_K_RENDER exist. */
+#define SVC_ABI_VERSION 6
 int svc_abi_version(void);
 
 /* weights_blob_host: the packed, BN-folded static SALICON slice of a UNISAL
@@ -84,6 +88,17 @@ int svc_destroy(SvcHandle *h);
 /* frames[n][h][w][3] u8 RGB -> out[n][sh][sw][3] u8, OpenCV INTER_LINEAR semantics. */
 int svc_resize_frames_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
                          uint8_t *out, int sh, int sw, void *stream);
+
+/* frames[n][height][width][3] u8 and boxes[n][4] int32 (x1,y1,x2,y2; x2-x1 == bw, y2-y1 == bh for every frame), both on the
+ * device -> out[n][oh][ow][3] u8: each frame's window resampled to oh x ow with OpenCV INTER_LINEAR semantics, i.e.
+ * cv2.resize(frame[y1:y2, x1:x2], (ow, oh)); oh == bh && ow == bw is an exact copy (sc_renderer's crop, smartVidCrop.py:1910).
+ * flags: SVC_RENDER_BGR swaps R and B (smartVidCrop.py:1894).  Source reads are clamped into the frame (x1 to
+ * [0, width - bw], y1 to [0, height - bh]; x2 / y2 are not read), so a bad box never reads outside `frames`.
+ * SVC_E_INVALID: bw > width, bh > height, a size < 1, an unknown flag, or a resampled window / output row that needs
+ * more than 64 KiB of LDS (2 * (3 bw + 32) + 3 ow + 16 bytes). */
+#define SVC_RENDER_BGR 1
+int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                        int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
 
 /* frames_nhwc[n][h][w][3] u8 RGB (saliency size, e.g. 140x250) -> maps_nhw[n][h][w] u8.
  * Frame-major output; the reference's [h][w][n] view is a transpose done by the
@@ -201,7 +216,8 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
 #define SVC_K_CORE 9
 #define SVC_K_PRIM 10
 #define SVC_K_FINISH 11
-#define SVC_K_COUNT 12
+#define SVC_K_RENDER 12    /* svc_render_crops_u8 */
+#define SVC_K_COUNT 13
 int svc_profile_enable(SvcHandle *h, int kernel_class);
 int svc_profile_read(SvcHandle *h, double *total_ms, int *launches);
 /* The same log without the correction: raw_total_ms = sum of the event-pair durations, pair_ms = cost of an empty event pair

@@ -5,6 +5,7 @@
 //
 // Reference semantics restated per kernel (paths relative to the reference tree):
 //   k_cv_resize      cv2.resize(INTER_LINEAR)         smartVidCrop.py:333-335, :633-635
+//   k_render_*       frame[by1:by2, bx1:bx2, :] (+ cv2.resize INTER_LINEAR, + RGB2BGR)  smartVidCrop.py:1801-1921
 //   k_lanczos_norm   PIL LANCZOS + ToTensor + Normalize 3rd_party_libs/unisal/unisal/data.py:1281-1294
 //   k_stem           conv_bn(3,32,stride 2)+ReLU6      unisal/models/MobileNetV2.py:10-15,124
 //   k_pw<TN>         1x1 conv (+BN)(+ReLU6)(+residual) MobileNetV2.py:18-23,26-83; unisal/model.py:388-409
@@ -136,14 +137,9 @@ static void cv_linear_tab(int src, int dst, bool horizontal, int *ofs, int *a, i
     if (xmax_out) *xmax_out = xmax;
 }
 
-extern "C" int svc_resize_frames_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
-                                    uint8_t *out, int sh, int sw, void *stream) {
-    if (!h || n < 0 || (n > 0 && (!frames || !out)) || height < 1 || width < 1 || sh < 1 || sw < 1) {     // n = 0: a no-op, null buffers allowed
-        svc_set_error("svc_resize_frames_u8: invalid argument");
-        return SVC_E_INVALID;
-    }
-    if (n == 0) return SVC_OK;
-    SVC_HIP(hipSetDevice(h->device));
+// the INTER_LINEAR table of (height, width) -> (sh, sw), built once per handle and size pair (the ingest's and the
+// renderer's tables are the same thing: a window of bh x bw is resampled exactly like a frame of that size)
+static int cv_tab(SvcHandle *h, int height, int width, int sh, int sw, const int **out) {
     auto key = std::make_tuple(height, width, sh, sw);
     auto it = h->cvtabs.find(key);
     if (it == h->cvtabs.end()) {
@@ -158,11 +154,264 @@ extern "C" int svc_resize_frames_u8(SvcHandle *h, const uint8_t *frames, int n, 
         SVC_HIP(hipMemcpy(buf.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         it = h->cvtabs.emplace(key, buf).first;
     }
+    *out = (const int *)it->second.p;
+    return SVC_OK;
+}
+
+extern "C" int svc_resize_frames_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
+                                    uint8_t *out, int sh, int sw, void *stream) {
+    if (!h || n < 0 || (n > 0 && (!frames || !out)) || height < 1 || width < 1 || sh < 1 || sw < 1) {     // n = 0: a no-op, null buffers allowed
+        svc_set_error("svc_resize_frames_u8: invalid argument");
+        return SVC_E_INVALID;
+    }
+    if (n == 0) return SVC_OK;
+    SVC_HIP(hipSetDevice(h->device));
+    const int *tab = nullptr;
+    int rc = cv_tab(h, height, width, sh, sw, &tab);
+    if (rc) return rc;
     size_t total = (size_t)n * sh * sw;
     ProfScope ps(h, SVC_K_RESIZE, (hipStream_t)stream);
     k_cv_resize<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
-        frames, out, (const int *)it->second.p, n, height, width, sh, sw);
+        frames, out, tab, n, height, width, sh, sw);
     SVC_CHECK_LAUNCH();
+    return SVC_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// render: every frame's window (x1, y1, bw, bh) of the full frames, copied or resampled to oh x ow
+// (sc_renderer, smartVidCrop.py:1801-1921: frame[by1:by2, bx1:bx2, :] at :1910, the BGR conversion of the pickle mode :1894)
+// --------------------------------------------------------------------------------------
+// The window origin of frame f, clamped so that every source read lies inside that frame (the host checked bw <= width,
+// bh <= height); x2 / y2 of the box are not read.
+__device__ __forceinline__ void render_origin(const int32_t *__restrict__ boxes, int f, int height, int width, int bh, int bw,
+                                              int &x0, int &y0) {
+    x0 = min(max(boxes[4 * f], 0), width - bw);
+    y0 = min(max(boxes[4 * f + 1], 0), height - bh);
+}
+
+// 16 bytes at a 16-aligned address; the word that runs past `end` (the end of the frames buffer) is read bytewise
+__device__ __forceinline__ uint4 ld16_guard(const uint8_t *p, const uint8_t *end) {
+    if (p + 16 <= end) return *(const uint4 *)p;
+    uint32_t d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if (p + i < end) d[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
+    return make_uint4(d[0], d[1], d[2], d[3]);
+}
+
+// the 48 bytes at an arbitrary address a of a 16-aligned buffer ending at `end` -> o[12] (little-endian dwords): four
+// aligned 16-byte loads, then a funnel shift by (a & 15) bytes (two dword-select stages and v_alignbyte_b32)
+__device__ __forceinline__ void ld48(const uint8_t *a, const uint8_t *end, uint32_t (&o)[12]) {
+    const uint8_t *p = (const uint8_t *)((uintptr_t)a & ~(uintptr_t)15);
+    const int s = (int)(a - p), q = s >> 2, b = s & 3;
+    uint32_t w[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint4 v = ld16_guard(p + 16 * i, end);
+        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    uint32_t u[14];
+#pragma unroll
+    for (int j = 0; j < 14; ++j) u[j] = (q & 2) ? w[j + 2] : w[j];
+#pragma unroll
+    for (int j = 0; j < 13; ++j) u[j] = (q & 1) ? u[j + 1] : u[j];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) o[i] = __builtin_amdgcn_alignbyte(u[i + 1], u[i], b);
+}
+
+// Copy path (output size == window size), bw >= 16, frames and out 16-aligned.  The output is one packed run of pixels;
+// thread g owns output pixels [16 g, 16 g + 16) = bytes [48 g, 48 g + 48), written as three aligned 16-byte stores.  The
+// group's source is one 48-byte run of the window row it starts in (ld48), and when the group runs over the end of that
+// row, the rest comes from the next window row (of this frame or the next one) through a second ld48 merged in by byte
+// mask.  BGR: a fixed byte permutation inside the group (it starts on a pixel boundary).
+template <bool BGR>
+__global__ __launch_bounds__(256) void k_render_copy(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                     const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
+                                                     long long total_px, const uint8_t *in_end) {
+    const long long p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (p0 >= total_px) return;
+    const long long R = p0 / bw;
+    const int col = (int)(p0 - R * bw);
+    int f = (int)(R / bh), r = (int)(R - (long long)f * bh);
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    uint32_t o[12];
+    ld48(in + (((size_t)f * height + y0 + r) * width + x0 + col) * 3, in_end, o);
+    const int k = bw - col;                                     // pixels of the group in row R
+    if (k < 16 && p0 + k < total_px) {
+        if (++r == bh) { r = 0; ++f; }
+        render_origin(boxes, f, height, width, bh, bw, x0, y0);
+        uint32_t o2[12];                                         // bytes [3k, 48) = the first pixels of the next row
+        ld48(in + (((size_t)f * height + y0 + r) * width + x0) * 3 - 3 * k, in_end, o2);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            const int lim = 3 * k - 4 * i;                       // bytes of dword i that stay with row R
+            const uint32_t m = lim >= 4 ? 0xffffffffu : lim <= 0 ? 0u : (1u << (8 * lim)) - 1u;
+            o[i] = (o[i] & m) | (o2[i] & ~m);
+        }
+    }
+    if (BGR) {
+        uint32_t t[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int d = 4 * i + j, c = d % 3, sb = d - c + 2 - c;      // R <-> B inside the pixel
+                v |= ((o[sb >> 2] >> (8 * (sb & 3))) & 0xffu) << (8 * j);
+            }
+            t[i] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < 12; ++i) o[i] = t[i];
+    }
+    uint8_t *dst = out + p0 * 3;
+    if (p0 + 16 <= total_px) {
+        uint4 *d4 = (uint4 *)dst;
+        d4[0] = make_uint4(o[0], o[1], o[2], o[3]);
+        d4[1] = make_uint4(o[4], o[5], o[6], o[7]);
+        d4[2] = make_uint4(o[8], o[9], o[10], o[11]);
+    } else {
+        const int nb = (int)(total_px - p0) * 3;
+#pragma unroll
+        for (int i = 0; i < 48; ++i)
+            if (i < nb) dst[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
+    }
+}
+
+// Copy path for narrow windows (bw < 16) or unaligned buffers: one thread per output pixel, byte loads.
+template <bool BGR>
+__global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                        const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
+                                                        long long total_px) {
+    const long long px = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (px >= total_px) return;
+    const long long R = px / bw;
+    const int col = (int)(px - R * bw), f = (int)(R / bh), r = (int)(R - (long long)f * bh);
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    const uint8_t *s = in + (((size_t)f * height + y0 + r) * width + x0 + col) * 3;
+    const uint8_t c0 = s[0], c1 = s[1], c2 = s[2];
+    uint8_t *d = out + px * 3;
+    d[0] = BGR ? c2 : c0;
+    d[1] = c1;
+    d[2] = BGR ? c0 : c2;
+}
+
+// Resize path: k_cv_resize's arithmetic on a window of the full frame.  One workgroup = one output row of one frame: the
+// two window rows it reads are staged in LDS with aligned 16-byte loads (vec: frames 16-aligned; else bytewise), the
+// output row is assembled in LDS at the output's own 16-byte phase and written with aligned 16-byte stores (the partial
+// words at both ends bytewise).  LDS: two source rows of span_cap bytes, then the output row (ow * 3 + 16 bytes).
+template <bool BGR>
+__global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                       const int *__restrict__ tab, const int32_t *__restrict__ boxes, int f0,
+                                                       int height, int width, int bh, int bw, int oh, int ow, int span_cap,
+                                                       const uint8_t *in_end, int vec) {
+    extern __shared__ __align__(16) uint8_t sm_rr[];
+    const int *xofs = tab, *xa = tab + ow, *yofs = tab + 3 * ow, *ya = tab + 3 * ow + oh;
+    const int xmax = tab[3 * ow + 3 * oh];
+    const int oy = blockIdx.x, f = f0 + blockIdx.y;
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    const int sy = yofs[oy];
+    const int ry[2] = {min(max(sy, 0), bh - 1), min(max(sy + 1, 0), bh - 1)};
+    const int span = bw * 3;
+    int sh[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const uint8_t *a = in + (((size_t)f * height + y0 + ry[k]) * width + x0) * 3;
+        uint8_t *row = sm_rr + k * span_cap;
+        if (vec) {
+            const uint8_t *p = (const uint8_t *)((uintptr_t)a & ~(uintptr_t)15);
+            sh[k] = (int)(a - p);
+            const int nw = (sh[k] + span + 15) >> 4;
+            for (int i = threadIdx.x; i < nw; i += 256) ((uint4 *)row)[i] = ld16_guard(p + 16 * i, in_end);
+        } else {
+            sh[k] = 0;
+            for (int i = threadIdx.x; i < span; i += 256) row[i] = a[i];
+        }
+    }
+    uint8_t *dst = out + ((size_t)blockIdx.y * oh + oy) * ow * 3;
+    const int ph = (int)((uintptr_t)dst & 15);
+    uint8_t *orow = sm_rr + 2 * span_cap + ph;
+    __syncthreads();
+    const uint8_t *r0 = sm_rr + sh[0], *r1 = sm_rr + span_cap + sh[1];
+    const int b0 = ya[2 * oy], b1 = ya[2 * oy + 1];
+    for (int ox = threadIdx.x; ox < ow; ox += 256) {
+        const int sx = xofs[ox], sx1 = min(sx + 1, bw - 1);
+        const int a0 = xa[2 * ox], a1 = xa[2 * ox + 1];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            int h0, h1;
+            if (ox < xmax) {
+                h0 = r0[sx * 3 + c] * a0 + r0[sx1 * 3 + c] * a1;
+                h1 = r1[sx * 3 + c] * a0 + r1[sx1 * 3 + c] * a1;
+            } else {
+                h0 = r0[sx * 3 + c] * 2048;
+                h1 = r1[sx * 3 + c] * 2048;
+            }
+            int v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+            orow[ox * 3 + (BGR ? 2 - c : c)] = (uint8_t)min(max(v, 0), 255);
+        }
+    }
+    __syncthreads();
+    // bytes [0, head) and [head + 16 * nw, ow * 3) of the row are partial 16-byte words of the output: bytewise
+    const int nb = ow * 3, head = min(nb, (16 - ph) & 15), nw = (nb - head) >> 4;
+    const uint4 *src4 = (const uint4 *)(orow + head);
+    uint4 *dst4 = (uint4 *)(dst + head);
+    for (int i = threadIdx.x; i < nw; i += 256) dst4[i] = src4[i];
+    for (int i = threadIdx.x; i < head; i += 256) dst[i] = orow[i];
+    for (int i = head + 16 * nw + threadIdx.x; i < nb; i += 256) dst[i] = orow[i];
+}
+
+extern "C" int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                                   int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    if (!h || n < 0 || (n > 0 && (!frames || !boxes || !out)) || height < 1 || width < 1 || bw < 1 || bh < 1 ||
+        bw > width || bh > height || oh < 1 || ow < 1 || (flags & ~SVC_RENDER_BGR)) {       // n = 0: a no-op, null buffers allowed
+        svc_set_error("svc_render_crops_u8: invalid argument");
+        return SVC_E_INVALID;
+    }
+    const int span_cap = (bw * 3 + 32 + 15) / 16 * 16;
+    const size_t lds = 2 * (size_t)span_cap + (size_t)ow * 3 + 16;
+    const bool copy = oh == bh && ow == bw;
+    if (!copy && lds > 65536) {
+        svc_set_error("svc_render_crops_u8: window %dx%d -> %dx%d needs %zu bytes of LDS per output row (> 64 KiB)", bw, bh, ow, oh, lds);
+        return SVC_E_INVALID;
+    }
+    if (n == 0) return SVC_OK;
+    SVC_HIP(hipSetDevice(h->device));
+    const bool bgr = (flags & SVC_RENDER_BGR) != 0;
+    const uint8_t *in_end = frames + (size_t)n * height * width * 3;
+    const bool aligned_in = ((uintptr_t)frames & 15) == 0, aligned_out = ((uintptr_t)out & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int *tab = nullptr;
+    if (!copy) {
+        int rc = cv_tab(h, bh, bw, oh, ow, &tab);
+        if (rc) return rc;
+    }
+    ProfScope ps(h, SVC_K_RENDER, s);
+    if (copy) {
+        const long long total_px = (long long)n * bh * bw;
+        if (bw >= 16 && aligned_in && aligned_out) {
+            const unsigned grid = (unsigned)((total_px + 16 * 256 - 1) / (16 * 256));
+            if (bgr) k_render_copy<true><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px, in_end);
+            else k_render_copy<false><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px, in_end);
+        } else {
+            const unsigned grid = (unsigned)((total_px + 255) / 256);
+            if (bgr) k_render_copy_px<true><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px);
+            else k_render_copy_px<false><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px);
+        }
+        SVC_CHECK_LAUNCH();
+        return SVC_OK;
+    }
+    for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
+        const int nf = std::min(n - f0, 65535);
+        uint8_t *o = out + (size_t)f0 * oh * ow * 3;
+        const dim3 grid((unsigned)oh, (unsigned)nf);
+        if (bgr) k_render_resize<true><<<grid, 256, lds, s>>>(frames, o, tab, boxes, f0, height, width, bh, bw, oh, ow, span_cap, in_end, aligned_in);
+        else k_render_resize<false><<<grid, 256, lds, s>>>(frames, o, tab, boxes, f0, height, width, bh, bw, oh, ow, span_cap, in_end, aligned_in);
+        SVC_CHECK_LAUNCH();
+    }
     return SVC_OK;
 }
 

@@ -19,6 +19,12 @@ one multi-frame image file (GIF, APNG, WebP, TIFF).  ``shots=None`` leaves ``tra
 
     S.set_video_reader(lambda path, CP: ingest.read_frames_pillow(path, fr=25.0, shots=None))
     VD, res = S.smart_vid_crop('frames_of_clip_017/', CP, save_vid=False, shot_net=net)
+
+The way out mirrors the way in: ``write_frames_pillow`` is a writer for smartVidCrop.set_video_writer that stores the
+rendered frames as a lossless PNG frame folder, which ``read_frames_pillow`` reads back bit for bit:
+
+    S.set_video_writer(ingest.write_frames_pillow)
+    VD, res = S.smart_vid_crop('frames_of_clip_017/', CP, final_vid_fn='clip_017_9x16/')
 """
 import os
 
@@ -67,6 +73,31 @@ def read_frames_pillow(path, fr=None, shot_detector=None, max_frames=None, shots
     frames = np.ascontiguousarray(np.stack(out))
     trans = list(shot_detector(frames)) if shot_detector is not None else []
     return video_dict(frames, 25.0 if rate is None else rate, trans, shots=shots)
+
+
+class _PillowFrameWriter:
+    def __init__(self, path, fr, size):
+        os.makedirs(path, exist_ok=True)
+        self.path, self.fr, self.size, self.n = path, float(fr), (int(size[0]), int(size[1])), 0
+
+    def write(self, frame_rgb_u8):
+        from PIL import Image
+        f = np.ascontiguousarray(frame_rgb_u8, np.uint8)
+        if f.shape != (self.size[1], self.size[0], 3):
+            raise ValueError('frame of shape %s, the writer was opened for %d x %d' % (f.shape, self.size[0], self.size[1]))
+        Image.fromarray(f, 'RGB').save(os.path.join(self.path, '%06d.png' % self.n), compress_level=1)
+        self.n += 1
+
+    def release(self):
+        pass
+
+
+def write_frames_pillow(path, fr, size):
+    """The encode side of read_frames_pillow, in the shape of cv2.VideoWriter (smartVidCrop.set_video_writer):
+    ``write(frame)`` stores RGB [h,w,3] u8 frames of ``size`` = (w, h) as ``path/000000.png``, ``000001.png``, ... (lossless;
+    the directory is created), ``release()`` ends it.  ``fr`` is accepted for the writer signature; a PNG folder keeps no
+    frame rate (read_frames_pillow(path, fr=...) gives it back)."""
+    return _PillowFrameWriter(path, fr, size)
 
 
 def read_video_cv2(path, shot_detector=None, max_frames=None):

@@ -27,6 +27,7 @@ def _need_cuda(t, dtype, name):
         raise TypeError('%s must be a contiguous CUDA tensor of dtype %s' % (name, dtype))
 
 
+RENDER_BGR = 1                       # svc_render_crops_u8 flag (include/svc.h: SVC_RENDER_BGR)
 BLEND_NEXT, MAP_HELD = 1, 2          # bits of cluster_center_'s per-map flags (include/svc.h: SVC_BLEND_NEXT, SVC_MAP_HELD)
 
 
@@ -67,6 +68,35 @@ class Engine:
         assert c == 3
         out = torch.empty((n, sh, sw, 3), dtype=torch.uint8, device=frames.device)
         _lib.check(self.lib.svc_resize_frames_u8(self._h, _ptr(frames), n, h, w, _ptr(out), sh, sw, _stream()))
+        return out
+
+    # -- rendering ------------------------------------------------------------------------
+    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None):
+        """uint8 [n,h,w,3] frames on the device and int32 [n,4] boxes (x1,y1,x2,y2, one window size for all; a CUDA tensor, or
+        host values that are copied over) -> uint8
+        [n,oh,ow,3]: frame[y1:y2, x1:x2] copied (out_hw None or the window size) or resampled to out_hw = (oh, ow) with
+        cv2.resize(INTER_LINEAR) semantics; bgr: R and B swapped.  Runs on the current stream (svc_render_crops_u8)."""
+        _need_cuda(frames, torch.uint8, 'frames')
+        n = int(frames.shape[0])
+        if torch.is_tensor(boxes) and boxes.is_cuda:
+            b0 = boxes[0].tolist() if n else [0, 0, 1, 1]        # the window size (a host read of 16 bytes)
+        else:
+            b0 = np.asarray(boxes)[0].tolist() if n else [0, 0, 1, 1]
+            boxes = torch.from_numpy(np.ascontiguousarray(boxes, np.int32)).to(frames.device)
+        bw, bh = int(b0[2] - b0[0]), int(b0[3] - b0[1])
+        oh, ow = (bh, bw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        if out is None:
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
+        return self._render(frames, boxes, bw, bh, out, bgr)
+
+    def _render(self, frames, boxes, bw, bh, out, bgr):
+        _need_cuda(frames, torch.uint8, 'frames')
+        _need_cuda(boxes, torch.int32, 'boxes')
+        _need_cuda(out, torch.uint8, 'out')
+        n, h, w, c = frames.shape
+        assert c == 3 and tuple(boxes.shape) == (n, 4) and out.shape[0] == n and out.shape[3] == 3
+        _lib.check(self.lib.svc_render_crops_u8(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out),
+                                                int(out.shape[1]), int(out.shape[2]), RENDER_BGR if bgr else 0, _stream()))
         return out
 
     # -- saliency ------------------------------------------------------------------------
@@ -126,10 +156,11 @@ class Engine:
     # -- measurement door (bench.py) -------------------------------------------------------
     KERNEL_CLASSES = ('resize', 'lanczos', 'stem', 'pw', 'dw', 'resample', 'smooth', 'threshold', 'compact',
                       'core', 'prim', 'finish')
+    PROFILE_CLASSES = KERNEL_CLASSES + ('render',)   # 'render' (svc_render_crops_u8) is behind the saliency-to-crop path
 
     def profile_enable(self, kernel_class):
-        """kernel_class: name from KERNEL_CLASSES, or None to switch event recording off."""
-        k = -1 if kernel_class is None else self.KERNEL_CLASSES.index(kernel_class)
+        """kernel_class: name from PROFILE_CLASSES, or None to switch event recording off."""
+        k = -1 if kernel_class is None else self.PROFILE_CLASSES.index(kernel_class)
         _lib.check(self.lib.svc_profile_enable(self._h, k))
 
     def profile_read(self):

@@ -1,0 +1,157 @@
+"""The retargeted frames: every frame's crop window cut out of the full frame on the device (sc_renderer,
+smartVidCrop.py:1801-1921; the crop itself is frame[by1:by2, bx1:bx2, :] at :1910), optionally resampled to a fixed
+output size with cv2.resize(INTER_LINEAR) semantics (svc_render_crops_u8, include/svc.h).
+
+    VD, res = S.smart_vid_crop(video, CP, save_vid=False)
+    crops = render.render_video(video, VD)                            # uint8 [fc, fbb_h, fbb_w, 3] RGB
+    render.render_video(video, VD, out_size=(1080, 1920), sink=enc)   # enc(chunk [m,1920,1080,3]) in frame order
+
+The frames come from any container the ingest accepts: a host numpy array (gathered into pinned double buffers, H2D on a
+side stream: smartVidCrop._HostFeed), a pinned torch tensor (copied from where it lies), a CUDA tensor (no copy) or an
+on-device generator (synth.LazyBlobVideo: select on the device).  The crops come back through pinned double buffers on a
+second side stream, so that the sink consumes chunk c while the device renders chunk c + 1."""
+import numpy as np
+
+_MAX_CHUNK = 32
+_RING_BYTES = 96 << 20         # one output slot (device and pinned, two of each per engine): at most this many bytes
+
+
+def _container(video):
+    frames = video['frames'] if isinstance(video, dict) else video
+    if hasattr(frames, 'pinned') and hasattr(frames, 'rows'):
+        raise ValueError('render_video needs every frame of the video; %s holds only the frames the ingest selected'
+                         % type(frames).__name__)
+    if hasattr(frames, 'select') and not hasattr(frames, 'shape'):              # an on-device generator (synth.LazyBlobVideo)
+        return frames, len(frames), int(frames.h), int(frames.w)
+    import torch
+    if not torch.is_tensor(frames):
+        frames = np.asarray(frames)
+    if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype not in (np.uint8, torch.uint8):
+        raise TypeError('frames must be uint8 [n,h,w,3] RGB')
+    return frames, int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+
+
+def check_boxes(bbs, fc, h, w):
+    """bbs [fc,4] (x1,y1,x2,y2) -> (bw, bh); ValueError unless every window has the same size and lies inside the frame."""
+    b = np.asarray(bbs, np.int64)
+    if b.ndim != 2 or b.shape != (fc, 4):
+        raise ValueError('expected %d boxes [x1,y1,x2,y2], got shape %s' % (fc, b.shape))
+    bw, bh = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
+    if fc and (np.any(bw != bw[0]) or np.any(bh != bh[0])):
+        raise ValueError('crop windows differ in size (%s x %s ... %s x %s)' % (bw.min(), bh.min(), bw.max(), bh.max()))
+    if fc and (bw[0] < 1 or bh[0] < 1):
+        raise ValueError('empty crop window %d x %d' % (bw[0], bh[0]))
+    bad = np.flatnonzero((b[:, 0] < 0) | (b[:, 1] < 0) | (b[:, 2] > w) | (b[:, 3] > h))
+    if bad.size:
+        raise ValueError('crop window of frame %d %s lies outside the %d x %d frame' % (bad[0], b[bad[0]].tolist(), w, h))
+    return (int(bw[0]), int(bh[0])) if fc else (0, 0)
+
+
+def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, chunk=32):
+    """Render VD['fc'] frames of `video` (the ingest_pickle dict, or its 'frames' container) at VD['bbs_np'].
+    out_size: (w, h) of the output frames (None = the window size, an exact copy); bgr: R and B swapped (the reference's
+    pickle mode); sink: called with every chunk uint8 [m, oh, ow, 3] (m <= chunk) in frame order -- a view of a pinned
+    buffer that is refilled after the call returns, so copy what you keep.  -> numpy uint8 [fc, oh, ow, 3] without a sink,
+    else None.  Boxes of unequal size or outside the frame raise ValueError before any device work."""
+    frames, n, h, w = _container(video)
+    fc = int(VD['fc'])
+    if n < fc:
+        raise ValueError('the container holds %d frames, the video has %d' % (n, fc))
+    bw, bh = check_boxes(VD['bbs_np'][:fc] if fc else np.zeros((0, 4)), fc, h, w)
+    ow, oh = (bw, bh) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    if oh < 1 or ow < 1:
+        raise ValueError('output size %s' % (out_size,))
+    chunk = max(1, min(int(chunk), _MAX_CHUNK, _RING_BYTES // (oh * ow * 3)))
+    result = None
+    if sink is None:
+        result = np.empty((fc, oh, ow, 3), np.uint8)
+
+        def sink(c, _pos=[0]):
+            result[_pos[0]:_pos[0] + c.shape[0]] = c
+            _pos[0] += c.shape[0]
+    if fc == 0:
+        return result
+    import torch
+    from . import smartVidCrop as S
+    engine = engine or S.get_engine()
+    dev = engine.device
+    boxes = torch.from_numpy(np.ascontiguousarray(VD['bbs_np'][:fc], np.int32)).to(dev)
+    out = _OutRing(engine, chunk, oh, ow, sink)
+
+    def emit(staged, s):
+        out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr)
+
+    if hasattr(frames, 'select') and not hasattr(frames, 'shape'):             # on-device generator
+        for s in range(0, fc, chunk):
+            emit(frames.select(range(s, min(fc, s + chunk))).to(dev).contiguous(), s)
+    elif torch.is_tensor(frames) and frames.is_cuda:
+        src = frames if frames.device == dev else frames[:fc].to(dev)
+        src = src.contiguous()
+        for s in range(0, fc, chunk):
+            emit(src[s:min(fc, s + chunk)], s)
+    else:
+        feed = engine.__dict__.get('_render_feed')
+        if feed is None:
+            feed = engine._render_feed = S._HostFeed(engine)                   # its own staging (the ingest's keeps its size)
+        feed.feed(frames, list(range(fc)), emit)
+    out.flush()
+    return result
+
+
+class _OutRing:
+    """Two device output slots and two pinned host slots: chunk c is rendered on the caller's stream into device slot c & 1,
+    copied D2H on a side stream into pinned slot c & 1, and handed to the sink once the copy of chunk c + 1 is enqueued."""
+
+    def __init__(self, engine, cap, oh, ow, sink):
+        import torch
+        self.engine, self.sink, self.dev = engine, sink, engine.device
+        key = (cap, oh, ow)
+        ring = engine.__dict__.get('_render_ring')
+        if ring is None or ring['key'] != key:
+            ring = engine._render_ring = dict(
+                key=key, dev=[torch.empty((cap, oh, ow, 3), dtype=torch.uint8, device=self.dev) for _ in range(2)],
+                host=[torch.empty((cap, oh, ow, 3), dtype=torch.uint8).pin_memory() for _ in range(2)],
+                stream=torch.cuda.Stream(device=self.dev))
+        self.ring = ring
+        self.rendered = [torch.cuda.Event(), torch.cuda.Event()]
+        self.copied = [torch.cuda.Event(), torch.cuda.Event()]
+        self.used = [False, False]
+        self.c = 0
+        self.pending = None                 # (slot, frames) of the chunk whose D2H is in flight
+
+    def push(self, staged, boxes, bw, bh, bgr):
+        m = int(staged.shape[0])
+        cap = self.ring['key'][0]
+        for s in range(0, m, cap):          # (a host feed stages at most 32 frames, the ring holds `chunk`)
+            self._one(staged[s:s + cap], boxes[s:s + cap], bw, bh, bgr)
+
+    def _one(self, staged, boxes, bw, bh, bgr):
+        import torch
+        m = int(staged.shape[0])
+        slot = self.c & 1
+        compute = torch.cuda.current_stream(self.dev)
+        side = self.ring['stream']
+        if self.used[slot]:
+            compute.wait_event(self.copied[slot])           # the device slot's previous D2H has read it
+        dst = self.ring['dev'][slot][:m]
+        self.engine._render(staged, boxes, bw, bh, dst, bgr)
+        self.rendered[slot].record(compute)
+        with torch.cuda.stream(side):
+            side.wait_event(self.rendered[slot])
+            self.ring['host'][slot][:m].copy_(dst, non_blocking=True)
+            self.copied[slot].record(side)
+        self.used[slot] = True
+        prev, self.pending = self.pending, (slot, m)
+        if prev is not None:
+            self._deliver(prev)
+        self.c += 1
+
+    def _deliver(self, what):
+        slot, m = what
+        self.copied[slot].synchronize()
+        self.sink(self.ring['host'][slot][:m].numpy())
+
+    def flush(self):
+        if self.pending is not None:
+            self._deliver(self.pending)
+            self.pending = None

@@ -54,6 +54,7 @@ _tls = threading.local()       # per-thread stage timers (the reference keeps on
 
 
 _video_reader = None
+_video_writer = None
 
 
 def set_video_reader(fn):
@@ -61,6 +62,15 @@ def set_video_reader(fn):
     retargetvid_amd/ingest.py).  None removes it.  Decoding and shot detection are not part of the path."""
     global _video_reader
     _video_reader = fn
+
+
+def set_video_writer(fn):
+    """Install the encode hand-off of smart_vid_crop(..., save_vid=True, final_vid_fn=...), the mirror of set_video_reader:
+    ``fn(path, fr, (w, h))`` returns an object with ``write(frame_rgb_u8)`` and ``release()`` -- the shape of
+    cv2.VideoWriter.  Frames are handed over RGB [h,w,3] u8; a writer that wants BGR flips them itself.
+    ingest.write_frames_pillow writes a PNG frame folder.  None removes it."""
+    global _video_writer
+    _video_writer = fn
 
 
 def sc_init_time():
@@ -232,9 +242,20 @@ class _HostFeed:
         threads) or a PINNED torch tensor (copied from where it lies, frame by frame); idx: selected frame numbers.
         -> uint8 CUDA tensor [len(idx), sal_h, sal_w, 3], produced on the caller's current stream."""
         import torch
+        out = torch.empty((len(idx), sal_h, sal_w, 3), dtype=torch.uint8, device=self.dev)
+
+        def put(staged, s):
+            out[s:s + staged.shape[0]] = self.engine.resize_frames(staged, sal_h, sal_w)
+        self.feed(frames, idx, put)
+        return out
+
+    def feed(self, frames, idx, consume):
+        """The staging loop behind downscale (and render.render_video): frames idx of a host container reach the device in
+        chunks of at most k frames; consume(staged_chunk, s) enqueues the chunk's device work on the caller's current
+        stream (staged_chunk: uint8 CUDA [m,h,w,3], valid until that work has run; s: position of its first frame in idx)."""
+        import torch
         h, w = int(frames.shape[1]), int(frames.shape[2])
         k = self._buffers(h, w)
-        out = torch.empty((len(idx), sal_h, sal_w, 3), dtype=torch.uint8, device=self.dev)
         compute = torch.cuda.current_stream(self.dev)
         direct = torch.is_tensor(frames) and frames.is_pinned()
         src = frames if direct else (frames.numpy() if torch.is_tensor(frames) else frames)
@@ -262,10 +283,9 @@ class _HostFeed:
                     self.staged[slot][:len(part)].copy_(self.pinned[slot][:len(part)], non_blocking=True)
                 self.copied[slot].record(self.copy_stream)
             compute.wait_event(self.copied[slot])
-            out[s:s + len(part)] = self.engine.resize_frames(self.staged[slot][:len(part)], sal_h, sal_w)
+            consume(self.staged[slot][:len(part)], s)
             self.consumed[slot].record(compute)
             self.used[slot] = True
-        return out
 
     def _pool(self):
         if getattr(self, '_tp', None) is None:
@@ -581,10 +601,22 @@ class _LazySmaps(dict):
 
 def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn='', frames_dir='',
                    temp_path=None, verbose=False, save_vid=True, callback_progress=None,
-                   callback_session=None, callback_status=None, copy_sound=False, engine=None, shot_net=None, stream_batch=0):
+                   callback_session=None, callback_status=None, copy_sound=False, engine=None, shot_net=None, stream_batch=0,
+                   out_size=None):
     """Saliency -> crop windows for one video.  Returns (VD, smart_crop_results) like the
     reference; VD['bbs'] holds one [x1,y1,x2,y2] per decoded frame.  A video dict without ``trans_inds`` takes the
-    reference's video path: ``shot_net`` (transnetv1_handler.ShotTransNet) detects the shots inside the ingest."""
+    reference's video path: ``shot_net`` (transnetv1_handler.ShotTransNet) detects the shots inside the ingest.
+
+    Rendering (sc_renderer, smartVidCrop.py:1801-1921) happens when save_vid is set AND final_vid_fn is not empty, on the
+    device (render.render_video), after the windows are known; results['t_render'] is its time:
+      * a ``<name>.pkl`` input writes ``<name>_sc.pkl`` (the reference's vid_path.replace('.pkl', '_sc.pkl')): a list of
+        fc BGR crops [fbb_h, fbb_w, 3] u8, as the reference's pickle mode does.  Unlike the reference, which renders it on
+        every pkl call with save_vid=True, this happens only when final_vid_fn is given, so calls without one stay free of
+        side effects;
+      * any other input goes through the writer installed with set_video_writer(): fn(final_vid_fn, VD['fr'], size) with
+        size = out_size (w, h) if given (every crop resampled to it, cv2.resize INTER_LINEAR) else (fbb_w, fbb_h); RGB
+        frames.  No writer installed: NotImplementedError, before any work.
+    demo_fn (the five-panel demo) and copy_sound (ffmpeg) with a render raise NotImplementedError."""
     import torch
     sc_init_time()
     results = {}
@@ -593,8 +625,19 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
     if CP['exit_on_spread_sal'] or CP['exit_on_low_cvrg'] or CP['t_border'] != -1:
         raise NotImplementedError('mean-saliency / coverage gates and border detection are disabled in both '
                                   'published parameter sets and are not part of this path')
-    if save_vid and (final_vid_fn or demo_fn):
-        raise NotImplementedError('video rendering is outside the saliency-to-crop path; pass save_vid=False')
+    if save_vid and demo_fn:
+        raise NotImplementedError('the five-panel demo video (cv2 drawing and text) is not rendered by this package; '
+                                  'pass demo_fn=\'\'')
+    render_pkl = render_writer = False
+    if save_vid and final_vid_fn:
+        if copy_sound:
+            raise NotImplementedError('copy_sound needs ffmpeg, which is not part of this package; pass copy_sound=False')
+        render_pkl = isinstance(video_path, str) and video_path.endswith('.pkl')
+        render_writer = not render_pkl
+        if render_writer and _video_writer is None:
+            raise NotImplementedError('rendering to %r needs a video writer: install one with set_video_writer() (for '
+                                      'example ingest.write_frames_pillow, a PNG frame folder), or pass save_vid=False'
+                                      % (final_vid_fn,))
     engine = engine or get_engine()
     if callback_status is not None and callback_session is not None:
         callback_status(callback_session, 'sc', 'SC VIDEO ANALYSIS', 'smart-cropping video analysis')
@@ -652,6 +695,22 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
     VD, results = after_ingest(VD, CP, engine, verbose=verbose)
     if callback_status is not None and callback_session is not None:
         callback_status(callback_session, 'sc', 'SC RENDERING', 'smart-cropping rendering')
+    if render_pkl or render_writer:
+        from . import render
+        t = time.perf_counter()
+        if render_pkl:                  # the reference's pickle mode (:1821-1825, :1890-1896, :2151-2154): BGR crops, native size
+            crops = render.render_video(video, VD, engine=engine, bgr=True)
+            with open(video_path.replace('.pkl', '_sc.pkl'), 'wb') as fp:
+                pickle.dump(list(crops), fp)
+        else:
+            size = tuple(int(v) for v in out_size) if out_size is not None else (int(VD['fbb_w']), int(VD['fbb_h']))
+            writer = _video_writer(final_vid_fn, VD['fr'], size)
+            try:
+                render.render_video(video, VD, engine=engine, out_size=size, sink=lambda chunk: [writer.write(f) for f in chunk])
+            finally:
+                writer.release()
+        sc_register_time(t, 'render')
+        results['t_render'] = sc_all_times(VD['fc'] / VD['fr'])['render']
     return VD, results
 
 

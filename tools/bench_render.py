@@ -1,0 +1,118 @@
+"""Rendering on the device (svc_render_crops_u8, render.render_video): one JSON line.
+
+  * per geometry: kernel time of a 32-frame batch resident in HBM (device events over --launches launches after a
+    warm-up), and the effective bandwidth = (bytes of the source windows read + bytes written) / kernel time, against the
+    6.3 TB/s achievable HBM bandwidth of the MI355X;
+  * render_video from host memory: frames/s for a --frames-frame 1080p numpy video (native 9:16 windows), beside the bare
+    H2D of the frames and D2H of the crops (same bytes, same pinned-buffer sizes) timed in the same run.
+
+usage: python tools/bench_render.py [--launches 200] [--frames 300]
+A rocprofv3 --kernel-trace --stats run of its own gives the per-kernel durations without the event overhead."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from retargetvid_amd import ops, render  # noqa: E402
+
+HBM_TBS = 6.3
+
+GEOMETRIES = (  # name, (h, w) frame, (bw, bh) window, (ow, oh) output or None
+    ('640x360_1x3_copy', (360, 640), (120, 360), None),
+    ('1920x1080_9x16_copy', (1080, 1920), (608, 1080), None),
+    ('1920x1080_9x16_to_1080x1920', (1080, 1920), (608, 1080), (1080, 1920)),
+    ('3840x2160_9x16_to_1080x1920', (2160, 3840), (1215, 2160), (1080, 1920)),
+)
+
+
+def boxes_for(n, h, w, bw, bh, seed=0):
+    rng = np.random.RandomState(seed)
+    x = rng.randint(0, w - bw + 1, n)
+    y = rng.randint(0, h - bh + 1, n)
+    return np.stack([x, y, x + bw, y + bh], 1).astype(np.int32)
+
+
+def kernel_times(eng, launches):
+    out = {}
+    n = 32
+    for name, (h, w), (bw, bh), osz in GEOMETRIES:
+        frames = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device=eng.device)
+        boxes = torch.from_numpy(boxes_for(n, h, w, bw, bh)).to(eng.device)
+        ow, oh = osz or (bw, bh)
+        dst = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=eng.device)
+        for _ in range(10):
+            eng._render(frames, boxes, bw, bh, dst, False)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(launches):
+            eng._render(frames, boxes, bw, bh, dst, False)
+        b.record()
+        torch.cuda.synchronize()
+        ms = a.elapsed_time(b) / launches
+        moved = n * (bw * bh * 3 + ow * oh * 3)
+        out[name] = dict(ms_per_32=round(ms, 4), us_per_frame=round(ms * 1e3 / n, 2), bytes_per_frame=moved // n,
+                         eff_tbs=round(moved / (ms * 1e-3) / 1e12, 3), frac_of_hbm=round(moved / (ms * 1e-3) / 1e12 / HBM_TBS, 3))
+        del frames, dst
+        torch.cuda.empty_cache()
+    return out
+
+
+def host_fed(eng, nf):
+    h, w, bw, bh = 1080, 1920, 608, 1080
+    frames = np.random.RandomState(1).randint(0, 256, (nf, h, w, 3), dtype=np.uint8)
+    VD = dict(fc=nf, bbs_np=boxes_for(nf, h, w, bw, bh, seed=2).astype(np.int64))
+    sink = lambda c: None
+    render.render_video(frames[:40], dict(fc=40, bbs_np=VD['bbs_np'][:40]), engine=eng, sink=sink)       # warm-up (buffers)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    render.render_video(frames, VD, engine=eng, sink=sink)
+    torch.cuda.synchronize()
+    t_render = time.perf_counter() - t0
+    # the bare copies of the same bytes through pinned buffers of the same sizes (15 frames in, 32 crops out), serial
+    k_in, k_out = 15, 32
+    pin_in = torch.empty((k_in, h, w, 3), dtype=torch.uint8).pin_memory()
+    dev_in = torch.empty((k_in, h, w, 3), dtype=torch.uint8, device=eng.device)
+    pin_out = torch.empty((k_out, bh, bw, 3), dtype=torch.uint8).pin_memory()
+    dev_out = torch.empty((k_out, bh, bw, 3), dtype=torch.uint8, device=eng.device)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for s in range(0, nf, k_in):
+        m = min(k_in, nf - s)
+        pin_in[:m].numpy()[...] = frames[s:s + m]
+        dev_in[:m].copy_(pin_in[:m], non_blocking=True)
+        torch.cuda.synchronize()
+    t_h2d = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    for s in range(0, nf, k_out):
+        m = min(k_out, nf - s)
+        pin_out[:m].copy_(dev_out[:m], non_blocking=True)
+        torch.cuda.synchronize()
+    t_d2h = time.perf_counter() - t0
+    return dict(frames=nf, render_s=round(t_render, 4), fps=round(nf / t_render, 1), bare_h2d_s=round(t_h2d, 4),
+                bare_d2h_s=round(t_d2h, 4), render_over_bare=round(t_render / (t_h2d + t_d2h), 3),
+                render_over_h2d=round(t_render / t_h2d, 3))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--launches', type=int, default=200)
+    ap.add_argument('--frames', type=int, default=300)
+    ap.add_argument('--skip-host', action='store_true')
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    eng = ops.Engine(device=0)
+    res = dict(kernels=kernel_times(eng, args.launches))
+    if not args.skip_host:
+        res['host_fed_1080p_9x16'] = host_fed(eng, args.frames)
+    print(json.dumps(res))
+    eng.close()
+
+
+if __name__ == '__main__':
+    main()
