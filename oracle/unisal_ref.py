@@ -67,26 +67,28 @@ def get_optimal_out_size(img_size):
     return best_size[0] * 32, best_size[1] * 32
 
 
-def preprocess(img_u8, out_size=None):
-    """data.py:1281-1294: HWC u8 RGB -> LANCZOS resize -> /255 -> normalise -> CHW fp32."""
+def preprocess(img_u8, out_size=None, dtype=torch.float32):
+    """data.py:1281-1294: HWC u8 RGB -> LANCZOS resize -> /255 -> normalise -> CHW fp32.
+    dtype=torch.float64 evaluates the same operations in double precision (a reference for the fp32 rounding)."""
     if out_size is None:
         out_size = get_optimal_out_size(img_u8.shape[:2])
     r = lanczos_ref.resize_lanczos_u8(img_u8, out_size[0], out_size[1])
     t = torch.from_numpy(r).permute(2, 0, 1).contiguous()
     # torchvision ToTensor: byte -> float32 then div(255); Normalize: sub mean, div std
-    t = t.to(torch.float32).div(255)
-    mean = torch.tensor(RGB_MEAN, dtype=torch.float32).view(3, 1, 1)
-    std = torch.tensor(RGB_STD, dtype=torch.float32).view(3, 1, 1)
+    t = t.to(dtype).div(255)
+    mean = torch.tensor(RGB_MEAN, dtype=dtype).view(3, 1, 1)
+    std = torch.tensor(RGB_STD, dtype=dtype).view(3, 1, 1)
     return (t - mean) / std
 
 
 class _SD:
-    def __init__(self, sd):
+    def __init__(self, sd, dtype=torch.float32):
         self.sd = {k: (v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v)))
                    for k, v in sd.items()}
+        self.dtype = dtype
 
     def __call__(self, key):
-        return self.sd[key].to(torch.float32)
+        return self.sd[key].to(self.dtype)
 
     def bn(self, x, prefix):
         """Eval-mode BatchNorm2d; resolves the SALICON branch of a DSBN module."""
@@ -141,14 +143,14 @@ def backbone(P, x):
     return x, feat_2x, feat_4x
 
 
-def gaussian_maps(gaussians, h, w, scaling=6.0):
+def gaussian_maps(gaussians, h, w, scaling=6.0, dtype=torch.float32):
     """model.py:348-378: 16 separable Gaussian priors on a linspace(0,1) grid -> [16,h,w]."""
-    ys = torch.linspace(0, 1, h, dtype=torch.float32)
-    xs = torch.linspace(0, 1, w, dtype=torch.float32)
+    ys = torch.linspace(0, 1, h, dtype=dtype)
+    xs = torch.linspace(0, 1, w, dtype=dtype)
     gy, gx = torch.meshgrid(ys, xs, indexing='ij')
     maps = []
-    for g in torch.unbind(gaussians.to(torch.float32)):
-        m = torch.ones(h, w, dtype=torch.float32)
+    for g in torch.unbind(gaussians.to(dtype)):
+        m = torch.ones(h, w, dtype=dtype)
         for mu_logstd, grid in zip(g, (gy, gx)):
             mu = mu_logstd[0]
             std = torch.exp(mu_logstd[1])
@@ -172,16 +174,16 @@ def _up2(x):
 def forward_logits(sd, x, target_size, taps=None):
     """model.py:411-497 for T=1, static=True, source='SALICON'.
 
-    x: [B,3,H,W] fp32 normalised.  Returns the bilinear-resized pre-softmax map
-    [B, th, tw] (log_softmax is applied by the caller).  ``taps`` (dict) receives
-    intermediate tensors for golden comparison.
+    x: [B,3,H,W] fp32 normalised (or fp64: every weight and intermediate then follows x's dtype).
+    Returns the bilinear-resized pre-softmax map [B, th, tw] (log_softmax is applied by the
+    caller).  ``taps`` (dict) receives intermediate tensors for golden comparison.
     """
-    P = _SD(sd)
+    P = _SD(sd, x.dtype)
     with torch.no_grad():
         f1, f2, f4 = backbone(P, x)
         s2 = _skip(P, f2, 'skip_2x')
         s4 = _skip(P, f4, 'skip_4x')
-        g = gaussian_maps(P('coarse_gaussians_salicon'), f1.shape[-2], f1.shape[-1])
+        g = gaussian_maps(P('coarse_gaussians_salicon'), f1.shape[-2], f1.shape[-1], dtype=x.dtype)
         f = torch.cat((f1, g.unsqueeze(0).expand(f1.shape[0], -1, -1, -1)), dim=1)
         f = _inverted_residual(P, f, 'post_cnn.inv_res.conv', 1296, 256, 1, 1, False)
         post_cnn = f
@@ -204,7 +206,9 @@ def forward_logits(sd, x, target_size, taps=None):
 
 def quantise_u8(pre):
     """utils.py:132-136 + train.py:1267-1274: log-softmax over all pixels, exp,
-    divide by the max, *255.0, truncate to u8.  pre: [B,h,w] fp32 -> [B,h,w] u8."""
+    divide by the max, *255.0, truncate to u8.  pre: [B,h,w] fp32 -> [B,h,w] u8.
+    Always in fp32, the reference's semantics, whatever the dtype of ``pre``."""
+    pre = pre.to(torch.float32)
     b = pre.shape[0]
     ls = F.log_softmax(pre.reshape(b, -1), dim=1).reshape(pre.shape)
     p = ls.exp().numpy()
@@ -215,14 +219,15 @@ def quantise_u8(pre):
     return out
 
 
-def saliency_u8(sd, images_u8, taps=None):
+def saliency_u8(sd, images_u8, taps=None, dtype=torch.float32):
     """Oracle of predictions_from_memory_nuint8_np (unisal_handler.py:85-86,
     train.py:1255-1279).  images_u8: [n,H,W,3] u8 RGB -> [H,W,n] u8.
-    Frames are processed one at a time like the reference."""
+    Frames are processed one at a time like the reference.  dtype=torch.float64 runs the
+    network in double precision (taps in fp64); the u8 quantisation stays fp32."""
     n, h, w = images_u8.shape[:3]
     out = np.zeros((h, w, n), np.uint8)
     for i in range(n):
-        x = preprocess(images_u8[i]).unsqueeze(0)
+        x = preprocess(images_u8[i], dtype=dtype).unsqueeze(0)
         t = {} if taps is not None else None
         pre = forward_logits(sd, x, (h, w), t)
         out[:, :, i] = quantise_u8(pre)[0]

@@ -51,6 +51,38 @@ def test_ingest_resize_bit_exact(engine):
         assert np.array_equal(got, ref)
 
 
+def test_ingest_resize_bit_exact_common_sources_and_random_sizes(engine):
+    """k_cv_resize against the INTER_LINEAR oracle at the frame -> saliency-map sizes of common sources (square, 4:5, 2:3, 4K; both
+    orientations: maps 249x249, 249x200, 249x166, 250x140 and their transposes) and at 30 seeded random size pairs: up- and
+    down-scaling, 1-pixel inputs and outputs, pixel totals that are not multiples of the 256-thread workgroup."""
+    cases = []
+    for (h, w) in ((1080, 1080), (1080, 1350), (1080, 1620), (2160, 3840)):
+        for (fh, fw) in ((h, w), (w, h)):
+            cases.append((fh, fw) + P.sal_size(fw, fh, 250))
+    assert {c[2:] for c in cases} == {(249, 249), (200, 249), (249, 200), (166, 249), (249, 166), (140, 250), (250, 140)}
+    rng = np.random.RandomState(2026)
+    for k in range(30):
+        h, w = int(rng.randint(1, 600)), int(rng.randint(1, 600))
+        if k % 3 == 0:                                               # up-scaling
+            sh, sw = int(rng.randint(h, 2 * h + 2)), int(rng.randint(w, 2 * w + 2))
+        else:
+            sh, sw = int(rng.randint(1, h + 1)), int(rng.randint(1, w + 1))
+        if k % 7 == 1:
+            sh = 1
+        if k % 7 == 3:
+            sw = 1
+        if k == 5:
+            h, w = 1, 1
+        cases.append((h, w, sh, sw))
+    assert any(sh * sw % 256 for (_, _, sh, sw) in cases) and any(sh > h and sw > w for (h, w, sh, sw) in cases)
+    for (h, w, sh, sw) in cases:
+        n = 1 + (h + w) % 3
+        fr = np.random.RandomState(h * 7919 + w).randint(0, 256, (n, h, w, 3)).astype(np.uint8)
+        got = engine.resize_frames(torch.from_numpy(fr).cuda(), sh, sw).cpu().numpy()
+        ref = np.stack([cv_ref.resize_linear_u8(f, sh, sw) for f in fr])
+        assert np.array_equal(got, ref), (h, w, sh, sw)
+
+
 def test_saliency_against_oracle_and_reference_golden(engine, synthetic_sd, golden_dir):
     g = np.load(os.path.join(golden_dir, 'unisal_golden.npz'))
     frames = g['frames']
@@ -91,10 +123,15 @@ def test_fused_threshold_entry_gives_the_bytes_of_the_two_calls(engine):
     assert torch.equal(engine.saliency(fr, threshold=0), engine.saliency(fr))
 
 
-@pytest.mark.parametrize('shape', [(140, 250), (187, 250), (250, 140)])
+# one saliency-map shape for each of the other eight network input sizes get_optimal_out_size can select (288x416, 320x384,
+# 320x352, 320x320, 352x320, 384x320, 384x288, 416x288): lowest levels 9 - 13 wide or tall
+_OTHER_MAPS = [(166, 250), (200, 250), (230, 250), (249, 249), (250, 230), (250, 200), (250, 187), (250, 166)]
+
+
+@pytest.mark.parametrize('shape', [(140, 250), (187, 250), (250, 140)] + _OTHER_MAPS)
 def test_saliency_batch_and_chunk_independence(engine, shape):
     """A frame's map does not depend on its batch or its place in it -- also where a level's pixel count is not a multiple of
-    32, so that the 32-pixel workgroups of k_pwpw / k_pw_sk straddle frames (the 4:3 and portrait geometries)."""
+    32, so that the 32-pixel workgroups of k_pwpw / k_pw_sk straddle frames (the 4:3 and portrait geometries and the eight others)."""
     h, w = shape
     fr = torch.from_numpy(synth.blob_frames(40, h, w, seed=9)).cuda()           # 40 > default chunk of 32
     full = engine.saliency(fr)
@@ -153,11 +190,11 @@ def test_saliency_kernel_families_agree(engine, synthetic_sd, knobs):
     assert d.max() <= 1 and (d > 0).mean() < 1e-3
 
 
-@pytest.mark.parametrize('shape', [(140, 250), (187, 250), (250, 140)])
+@pytest.mark.parametrize('shape', [(140, 250), (187, 250), (250, 140)] + _OTHER_MAPS)
 def test_lane_order_weight_copies_are_bit_identical(engine, synthetic_sd, shape):
     """Round 4 (default on): k_pw_sk, k_dwpw, k_pwpw and k_front read their weights from lane-order copies of the matrices (a wave's
     load = 8 whole cache lines instead of 32 quarter-used ones).  Same values in the same order: the maps and the decoder tap equal
-    those of the [N][K] reads (SVC_SK_LANE=0) bit for bit, at the three geometries."""
+    those of the [N][K] reads (SVC_SK_LANE=0) bit for bit, at all eleven network input sizes."""
     h, w = shape
     NH, NW = U.get_optimal_out_size((h, w))
     fr = torch.from_numpy(synth.blob_frames(5, h, w, seed=3 * h + w)).cuda()
@@ -179,7 +216,7 @@ def test_lane_order_weight_copies_are_bit_identical(engine, synthetic_sd, shape)
         other.close()
 
 
-@pytest.mark.parametrize('shape', [(140, 250), (187, 250), (250, 140), (360, 640), (97, 131)])
+@pytest.mark.parametrize('shape', [(140, 250), (187, 250), (250, 140), (360, 640), (97, 131)] + _OTHER_MAPS)
 def test_front_kernel_bit_identical_to_three_kernels(engine, synthetic_sd, shape):
     """k_front (LANCZOS + features.0 + features.1 in one kernel) keeps the operation order of the three kernels it
     replaces: network input, feature taps and maps are bit-identical, at up-scaling, down-scaling and odd source sizes."""

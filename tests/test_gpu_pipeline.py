@@ -44,10 +44,12 @@ def test_smart_vid_crop_matches_oracle_boxes(engine, synthetic_sd, tmp_path):
 
 
 def test_other_frame_shapes_match_oracle_boxes(engine, synthetic_sd):
-    """Portrait and 4:3 sources: other saliency sizes (250x140, 187x250), other network inputs (416x256, 288x384),
-    other tile / patch edge cases in every kernel."""
+    """Portrait, 4:3, square, 3:2 and 4:5 sources: other saliency sizes (250x140, 187x250, 250x250, 166x249, 250x200), other network
+    inputs (416x256, 288x384, 320x320, 288x416, 384x320), other tile / patch edge cases in every kernel.  The crop ratios of the
+    last three make the window move (19 - 23 distinct positions in the oracle's 36)."""
     torch.set_num_threads(8)
-    for (h, w, ratio, seed) in ((640, 360, '1:1', 11), (480, 640, '9:16', 12)):
+    for (h, w, ratio, seed) in ((640, 360, '1:1', 11), (480, 640, '9:16', 12), (360, 360, '16:9', 13), (360, 540, '1:1', 14),
+                                (400, 320, '16:9', 15)):
         video = dict(fr=25.0, frame_count=36, w=w, h=h, frames=synth.blob_frames(36, h, w, seed=seed), trans_inds=[0, 14, 36])
         CP = S.sc_init_crop_params()
         CP['out_ratio'] = ratio
