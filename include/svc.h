@@ -76,8 +76,9 @@ const char *svc_last_error(void);
  * 4 = the host stages svc_host_* (SvcTemporalParams) and svc_saliency_thresholded_u8 exist.
  * 5 = svc_saliency_census_u8, svc_transnet_predict_rows and svc_transnet_config_get / _set exist; svc_create rejects an
  *     unknown spelling of SVC_MX / SVC_SHOT_MX with SVC_E_INVALID.
- * 6 = svc_render_crops_u8 (SVC_RENDER_BGR) and the profile class SVC_K_RENDER exist. */
-#define SVC_ABI_VERSION 6
+ * 6 = svc_render_crops_u8 (SVC_RENDER_BGR) and the profile class SVC_K_RENDER exist.
+ * 7 = svc_debug_transnet_tap (SVC_SHOT_TAP_*) exists; svc_create rejects SVC_SHOT_M16 outside 2..4 with SVC_E_INVALID. */
+#define SVC_ABI_VERSION 7
 int svc_abi_version(void);
 
 /* weights_blob_host: the packed, BN-folded static SALICON slice of a UNISAL
@@ -269,6 +270,18 @@ int svc_transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_windows
  * going through the process environment.  _set rejects values that are not a configuration with SVC_E_INVALID. */
 int svc_transnet_config_get(const SvcHandle *h, int32_t *cfg3);
 int svc_transnet_config_set(SvcHandle *h, const int32_t *cfg3);
+/* Test/diagnostic door: run svc_transnet_predict_rows on DEVICE frames [n_windows][frames_per_window][27][48][3], stop after
+ * `layer` (one of SVC_SHOT_TAP_*), synchronise, and write that layer to the HOST buffer out_host as fp32 NDHWC
+ * [n_windows][frames_per_window][H][W][C] without channel padding (split-bf16 planes added as the kernels add them; Dense(256)'s K
+ * parts summed in the head's order, then its bias and ReLU).  Frames a layer does not compute (rows outside what row0 .. row1 - 1
+ * depend on) are unspecified.  Runs on the null stream.  SVC_E_INVALID: an unknown layer, no weights, more windows than one pass
+ * holds, cap_floats below the layer's size. */
+#define SVC_SHOT_TAP_INPUT 0   /* [27][48][3]   v / 255                                            */
+#define SVC_SHOT_TAP_CELL1 1   /* cells 1..6 (after the ReLU) = 1..6: [27][48][64] x 2, [13][24][128] x 2, [6][12][256] x 2 */
+#define SVC_SHOT_TAP_POOL1 7   /* pools 1..3 = 7..9: [13][24][64], [6][12][128], [3][6][256]          */
+#define SVC_SHOT_TAP_DENSE 10  /* [256]         Dense(256) after bias and ReLU                       */
+int svc_debug_transnet_tap(SvcHandle *h, const uint8_t *frames, int n_windows, int frames_per_window, int row0, int row1, int layer,
+                           float *out_host, size_t cap_floats);
 
 /* Test/diagnostic door: copy an intermediate activation of the LAST svc_saliency_u8
  * call (NHWC fp32, frame 0..n-1) to a HOST buffer.  `which` is one of the SVC_TAP_*

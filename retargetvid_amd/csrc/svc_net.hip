@@ -3714,7 +3714,12 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
         else { svc_set_error("svc_create: SVC_SHOT_MX=%s (expected f32, bf16x6 or bf16x3)", env); delete h; return SVC_E_INVALID; }
     }
     env = getenv("SVC_SHOT_M16");
-    if (env) { const int v = atoi(env); if (v >= 2 && v <= 4) h->shot_m16 = v; }
+    if (env) {
+        char *end = nullptr;
+        const long v = strtol(env, &end, 10);
+        if (end == env || *end || v < 2 || v > 4) { svc_set_error("svc_create: SVC_SHOT_M16=%s (expected 2, 3 or 4)", env); delete h; return SVC_E_INVALID; }
+        h->shot_m16 = (int)v;
+    }
     env = getenv("SVC_SHOT_XCD");
     if (env) h->shot_xcd = atoi(env) != 0;
     env = getenv("SVC_PRIM_PT");

@@ -20,6 +20,8 @@
 // (SVC_SHOT_FORM 0 / 1: 19.5 / 17.0 ms per 8 windows against 10.9) and the split-bf16 cells on the 32x32x16 shape (k_shot_conv_x3,
 // SVC_SHOT_M16=0: 89.4 k against 94.1 k video frames/s); DESIGN_HISTORY.md keeps their measurements.
 #include <algorithm>
+#include <cstring>
+#include <vector>
 
 #include "svc_internal.h"
 #include "svc_x3.h"
@@ -90,6 +92,25 @@ __device__ __forceinline__ void shot_store_x3(uint4 *Y3, long long Mp, long long
 // the zero positions in front of the planes q0 .. q0 + nq - 1 (called by the first workgroup of the producing launch)
 __device__ __forceinline__ void shot_zero_pads(uint4 *Y3, long long Mp, int q0, int nq, int tid) {
     for (int i = tid; i < nq * 3 * SHOT_PAD * 2; i += 256) Y3[(size_t)(q0 * 3 + i / (SHOT_PAD * 2)) * Mp * 2 + i % (SHOT_PAD * 2)] = make_uint4(0, 0, 0, 0);
+}
+
+// host (svc_debug_transnet_tap): channel c of position m of a split activation copied back as bf16 words, its planes added the way
+// k_shot_pool_x3 adds them, (hi + mid) + lo in f32.  nq = C / 16 planes of 16 channels (the input: nq = 0, [3][Mp][4 channels]).
+static inline float shot_bf16(uint16_t b) {
+    const uint32_t u = (uint32_t)b << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+static float shot_x3_value(const uint16_t *X3, long long Mp, long long m, int c, bool input) {
+    size_t e, ps;
+    if (input) { e = (size_t)(SHOT_PAD + m) * 4 + c; ps = (size_t)Mp * 4; }
+    else {                                                   // the uint4 (q, plane 0, position, hh = bit 2 of c), element 4 (bit 3 of c) + (c & 3)
+        const int q = c >> 4, r = c & 15;
+        e = (((size_t)(q * 3) * Mp + SHOT_PAD + m) * 2 + ((r >> 2) & 1)) * 8 + ((r >> 3) << 2) + (r & 3);
+        ps = (size_t)Mp * 16;
+    }
+    return (shot_bf16(X3[e]) + shot_bf16(X3[e + ps])) + shot_bf16(X3[e + 2 * ps]);
 }
 
 __global__ __launch_bounds__(256) void k_shot_conv(const ShotConv A) {
@@ -897,7 +918,7 @@ extern "C" int svc_transnet_config_set(SvcHandle *h, const int32_t *cfg3) {
 }
 
 static int transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_windows, int frames_per_window, int row0, int row1, float *probs,
-                                 void *stream);
+                                 void *stream, int tap = -1, float *tap_out = nullptr);
 
 extern "C" int svc_transnet_predict(SvcHandle *h, const uint8_t *frames, int n_windows, int frames_per_window, float *probs,
                                     void *stream) {
@@ -909,9 +930,64 @@ extern "C" int svc_transnet_predict_rows(SvcHandle *h, const uint8_t *frames, in
     return transnet_predict_rows(h, frames, n_windows, frames_per_window, row0, row1, probs, stream);
 }
 
+
+// ---- test door (svc_debug_transnet_tap) -------------------------------------------------------------------------------------
+// The layer a pass has just written, as fp32 [frames][H][W][C] on the host.  Buffer kinds: fp32 rows of `ld` floats (the fp32 pipe;
+// the last pool of the split-bf16 pipe), split-bf16 planes (shot_x3_value), Dense(256)'s K parts (added in k_shot_head's order, then its
+// bias and ReLU).  Synchronises the stream.
+enum { SHOT_BUF_F32, SHOT_BUF_X3, SHOT_BUF_X3IN, SHOT_BUF_DENSE };
+static const int shot_tap_dims[SVC_SHOT_TAP_DENSE + 1][3] = {{SHOT_H, SHOT_W, 3}, {27, 48, 64}, {27, 48, 64}, {13, 24, 128}, {13, 24, 128},
+                                                             {6, 12, 256}, {6, 12, 256}, {13, 24, 64}, {6, 12, 128}, {3, 6, 256}, {1, 1, SHOT_D}};
+
+static int shot_tap_emit(hipStream_t s, const void *buf, int kind, long long nfr, int H, int W, int C, int ld, long long Mp, int ksplit,
+                         const float *bias_dev, float *out) {
+    SVC_HIP(hipStreamSynchronize(s));
+    const size_t npos = (size_t)nfr * H * W;
+    if (kind == SHOT_BUF_F32) {
+        std::vector<float> v(npos * ld);
+        SVC_HIP(hipMemcpy(v.data(), buf, v.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < npos; ++p)
+            for (int c = 0; c < C; ++c) out[p * C + c] = v[p * ld + c];
+    } else if (kind == SHOT_BUF_DENSE) {                     // [ksplit][nfr][256] raw sums
+        std::vector<float> v((size_t)ksplit * npos * SHOT_D), b(SHOT_D);
+        SVC_HIP(hipMemcpy(v.data(), buf, v.size() * sizeof(float), hipMemcpyDeviceToHost));
+        SVC_HIP(hipMemcpy(b.data(), bias_dev, SHOT_D * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < npos; ++p)
+            for (int c = 0; c < SHOT_D; ++c) {
+                float x = v[p * SHOT_D + c];
+                for (int z = 1; z < ksplit; ++z) x += v[((size_t)z * npos + p) * SHOT_D + c];
+                out[p * SHOT_D + c] = std::max(x + b[c], 0.f);
+            }
+    } else {
+        const bool in = kind == SHOT_BUF_X3IN;
+        std::vector<uint16_t> v(in ? (size_t)3 * Mp * 4 : (size_t)(C / 16) * 3 * Mp * 16);
+        SVC_HIP(hipMemcpy(v.data(), buf, v.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < npos; ++p)
+            for (int c = 0; c < C; ++c) out[p * C + c] = shot_x3_value(v.data(), Mp, (long long)p, c, in);
+    }
+    return SVC_OK;
+}
+
+extern "C" int svc_debug_transnet_tap(SvcHandle *h, const uint8_t *frames, int n_windows, int frames_per_window, int row0, int row1, int layer,
+                                      float *out_host, size_t cap_floats) {
+    if (!h || !frames || !out_host || n_windows < 1 || frames_per_window < 1 || layer < SVC_SHOT_TAP_INPUT || layer > SVC_SHOT_TAP_DENSE) {
+        svc_set_error("svc_debug_transnet_tap: invalid argument (layer %d)", layer);
+        return SVC_E_INVALID;
+    }
+    const int *d = shot_tap_dims[layer];
+    const size_t need = (size_t)n_windows * frames_per_window * d[0] * d[1] * d[2];
+    if (cap_floats < need) {
+        svc_set_error("svc_debug_transnet_tap: layer %d needs %zu floats, the buffer holds %zu", layer, need, cap_floats);
+        return SVC_E_INVALID;
+    }
+    return transnet_predict_rows(h, frames, n_windows, frames_per_window, row0, row1, nullptr, nullptr, layer, out_host);
+}
+
+// tap >= 0 (svc_debug_transnet_tap): stop after that layer and write it to tap_out; the device work up to it is the normal pass's
 static int transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_windows, int frames_per_window, int row0, int row1, float *probs,
-                                 void *stream) {
-    if (!h || n_windows < 0 || frames_per_window < 1 || (n_windows > 0 && (!frames || !probs)) || row0 < 0 || row1 > frames_per_window || row0 >= row1) {
+                                 void *stream, int tap, float *tap_out) {
+    if (!h || n_windows < 0 || frames_per_window < 1 || (n_windows > 0 && (!frames || (!probs && tap < 0))) || row0 < 0 || row1 > frames_per_window ||
+        row0 >= row1) {
         svc_set_error("svc_transnet_predict: invalid argument");
         return SVC_E_INVALID;
     }
@@ -964,6 +1040,10 @@ static int transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_wind
     const size_t per_win = (size_t)T * SHOT_H * SHOT_W * 64;
     const size_t val_bytes = mx ? 6 : 4, cap = (size_t)(mx ? 1536 : 768) << 20;
     const int chunk = std::max(1, std::min(n_windows, (int)(cap / (2 * per_win * val_bytes))));
+    if (tap >= 0 && chunk < n_windows) {
+        svc_set_error("svc_debug_transnet_tap: %d windows of %d frames, one pass holds %d", n_windows, T, chunk);
+        return SVC_E_INVALID;
+    }
     const size_t buf_bytes = per_win * chunk * val_bytes + (mx ? (size_t)64 * 3 * (SHOT_PAD + 4) * 32 : 0);
     int rc = h->shot_ws.ensure(2 * buf_bytes);
     if (rc) return rc;
@@ -981,6 +1061,9 @@ static int transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_wind
             else
                 k_shot_in<<<(unsigned)((npix + 255) / 256), 256, 0, s>>>(frames + (size_t)w0 * T * H * W * 3, P[0], npix);
             SVC_CHECK_LAUNCH();
+            if (tap == SVC_SHOT_TAP_INPUT)
+                return shot_tap_emit(s, P[0], first_x3 ? SHOT_BUF_X3IN : SHOT_BUF_F32, (long long)nfr, H, W, 3, 4,
+                                     (long long)((npix + SHOT_PAD + 3) / 4 * 4), 0, nullptr, tap_out);
         }
         for (int b = 0; b < SHOT_L; ++b) {
             const long long Mc = (long long)nfr * H * W, Mp = (Mc + SHOT_PAD + 3) / 4 * 4;       // plane stride of this resolution
@@ -998,6 +1081,7 @@ static int transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_wind
                     else k_shot_first_x3<2, 6><<<grid, 256, 0, s>>>(X);
                     SVC_CHECK_LAUNCH();
                     cur ^= 1;
+                    if (tap == SVC_SHOT_TAP_CELL1) return shot_tap_emit(s, P[cur], SHOT_BUF_X3, (long long)nfr, H, W, 4 * k.f, 0, Mp, 0, nullptr, tap_out);
                     continue;
                 }
                 if (mx && k.cpad >= 64) {
@@ -1023,6 +1107,8 @@ static int transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_wind
 #undef SHOT_X3M
                     SVC_CHECK_LAUNCH();
                     cur ^= 1;
+                    if (tap == SVC_SHOT_TAP_CELL1 + b * SHOT_S + c)
+                        return shot_tap_emit(s, P[cur], SHOT_BUF_X3, (long long)nfr, H, W, 4 * k.f, 0, Mp, 0, nullptr, tap_out);
                     continue;
                 }
                 ShotConv A;
@@ -1048,6 +1134,8 @@ static int transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_wind
                 }
                 SVC_CHECK_LAUNCH();
                 cur ^= 1;
+                if (tap == SVC_SHOT_TAP_CELL1 + b * SHOT_S + c)
+                    return shot_tap_emit(s, P[cur], SHOT_BUF_F32, (long long)nfr, H, W, 4 * k.f, 4 * k.f, 0, 0, nullptr, tap_out);
             }
             const int C = 4 * (SHOT_F << b);
             if (mx) {
@@ -1064,6 +1152,12 @@ static int transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_wind
             SVC_CHECK_LAUNCH();
             cur ^= 1;
             H /= 2; W /= 2;
+            if (tap == SVC_SHOT_TAP_POOL1 + b) {
+                const bool planes = mx && b < SHOT_L - 1;
+                const long long Mo = (long long)nfr * H * W;
+                return shot_tap_emit(s, P[cur], planes ? SHOT_BUF_X3 : SHOT_BUF_F32, (long long)nfr, H, W, C, C, (Mo + SHOT_PAD + 3) / 4 * 4, 0, nullptr,
+                                     tap_out);
+            }
         }
         {
             ShotConv A;
@@ -1078,6 +1172,9 @@ static int transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_wind
             k_shot_conv<<<grid, 256, 0, s>>>(A);
             SVC_CHECK_LAUNCH();
             cur ^= 1;
+            if (tap == SVC_SHOT_TAP_DENSE)
+                return shot_tap_emit(s, P[cur], A.ksplit > 1 ? SHOT_BUF_DENSE : SHOT_BUF_F32, (long long)nfr, 1, 1, SHOT_D, SHOT_D, 0, A.ksplit,
+                                     blob + d1b, tap_out);
             k_shot_head<<<(unsigned)(nw * kn), 64, 0, s>>>(P[cur], blob + d2w, blob + d2b, probs + (size_t)w0 * T, (int)nfr,
                                                            A.ksplit > 1 ? A.ksplit : 0, blob + d1b, T, ka, kn);
             SVC_CHECK_LAUNCH();

@@ -100,8 +100,31 @@ class ShotTransNet:
                                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out
 
-    def predict_raw(self, frames):
+    TAP_INPUT, TAP_CELL1, TAP_POOL1, TAP_DENSE = 0, 1, 7, 10           # include/svc.h SVC_SHOT_TAP_*
+    TAP_SHAPES = ((27, 48, 3), (27, 48, 64), (27, 48, 64), (13, 24, 128), (13, 24, 128), (6, 12, 256), (6, 12, 256),
+                  (13, 24, 64), (6, 12, 128), (3, 6, 256), (256,))
+
+    def debug_tap(self, frames, layer, rows=None):
+        """Test door (svc_debug_transnet_tap): the pass of predict_raw_device(frames, rows) stopped after `layer` (TAP_INPUT = v / 255,
+        cells 1..6 after the ReLU, TAP_POOL1 + 0..2, TAP_DENSE = Dense(256) after bias and ReLU) -> NumPy float32 NDHWC
+        [batch, frames, H, W, C] ([batch, frames, 256] for TAP_DENSE).  Frames the layer does not compute for `rows` are
+        unspecified.  At most one pass of windows (15 of 100 frames on the split-bf16 pipes)."""
         dev = torch.device('cuda', torch.cuda.current_device())
+        t = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, np.uint8))
+        t = t.to(dev).contiguous()
+        nb, nt = int(t.shape[0]), int(t.shape[1])
+        a, b = (0, nt) if rows is None else (int(rows[0]), int(rows[1]))
+        out = np.empty((nb, nt) + self.TAP_SHAPES[layer], np.float32)
+        torch.cuda.current_stream().synchronize()                     # the door runs on the null stream
+        _lib.check(self.eng.lib.svc_debug_transnet_tap(self.eng._h, ctypes.c_void_p(t.data_ptr()), nb, nt, a, b, int(layer),
+                                                        out.ctypes.data_as(ctypes.c_void_p), out.size))
+        return out
+
+    def _device(self):
+        return torch.device('cuda', torch.cuda.current_device())
+
+    def predict_raw(self, frames):
+        dev =torch.device('cuda', torch.cuda.current_device())
         t = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, np.uint8))
         return self.predict_raw_device(t.to(dev).contiguous()).cpu().numpy()
 
@@ -116,7 +139,7 @@ class ShotTransNet:
         outputs fall into [a, b) are computed -- the kept rows are bit for bit those of the full computation, the others read 0."""
         assert len(frames.shape) == 4 and tuple(frames.shape[1:]) == (self.params.INPUT_HEIGHT, self.params.INPUT_WIDTH, 3), \
             ' [ShotTransNet] Input shape must be [frames, height, width, 3].'
-        dev = torch.device('cuda', torch.cuda.current_device())
+        dev = self._device()
         t = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, np.uint8))
         t = t.to(dev).contiguous()
         n = int(t.shape[0])

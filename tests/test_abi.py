@@ -80,3 +80,15 @@ def test_host_stage_entries_check_their_arguments():
     assert lib.svc_host_savgol(y.ctypes.data_as(vp), 8, 4, 2, o.ctypes.data_as(vp)) == -1          # even window: savgol_filter raises
     assert lib.svc_host_focus_stability(None, None, 0, None, 140, 250, 30.0, 6, 1.0, 60.0, 1.5, None, None) == 0
     assert lib.svc_host_focus_stability(None, None, 3, None, 140, 250, 30.0, 6, 1.0, 60.0, 1.5, None, None) == -1
+
+
+def test_transnet_tap_door_constants_and_argument_checks():
+    """svc_debug_transnet_tap (ABI 7): the layer ids of include/svc.h are the binding's, and a call without a handle is refused."""
+    from retargetvid_amd import transnetv1_handler as Hd
+    text = open(os.path.join(ROOT, 'include', 'svc.h')).read()
+    ids = {k: int(v) for k, v in re.findall(r'#define SVC_SHOT_TAP_([A-Z0-9]+) (\d+)', text)}
+    assert ids == {'INPUT': Hd.ShotTransNet.TAP_INPUT, 'CELL1': Hd.ShotTransNet.TAP_CELL1, 'POOL1': Hd.ShotTransNet.TAP_POOL1,
+                   'DENSE': Hd.ShotTransNet.TAP_DENSE}
+    assert len(Hd.ShotTransNet.TAP_SHAPES) == ids['DENSE'] + 1
+    out = (ctypes.c_float * 4)()
+    assert _lib.load().svc_debug_transnet_tap(None, None, 1, 4, 0, 4, 0, out, 4) == -1

@@ -152,7 +152,8 @@ def test_kept_rows_only_every_layer_on_the_frames_they_depend_on(net):
 def test_clone_copies_the_knobs_handle_to_handle_and_unknown_pipes_are_rejected(net):
     """ShotTransNet.clone(): same weights, matrix pipe and kernel knobs on an engine of its own, copied with svc_transnet_config_get /
     _set -- the process environment is neither read nor written; svc_create rejects a misspelt SVC_MX / SVC_SHOT_MX (it used to select
-    the fp32 pipe silently) and svc_transnet_config_set a configuration that does not exist."""
+    the fp32 pipe silently) or an SVC_SHOT_M16 outside 2..4 (ignored silently before ABI 7), and svc_transnet_config_set a
+    configuration that does not exist."""
     import ctypes, os
     n, sd = net
     env = {k: os.environ.get(k) for k in ('SVC_SHOT_MX', 'SVC_SHOT_M16', 'SVC_SHOT_XCD')}
@@ -182,7 +183,8 @@ def test_clone_copies_the_knobs_handle_to_handle_and_unknown_pipes_are_rejected(
             assert a.eng.lib.svc_transnet_config_set(a.eng._h, (ctypes.c_int32 * 3)(*cfg)) < 0 and a.config() == [3, 4, 0]
     finally:
         a.close()
-    for var, val in (('SVC_MX', 'bf16'), ('SVC_MX', 'bf16x9'), ('SVC_SHOT_MX', '1'), ('SVC_SHOT_MX', 'fp32')):
+    for var, val in (('SVC_MX', 'bf16'), ('SVC_MX', 'bf16x9'), ('SVC_SHOT_MX', '1'), ('SVC_SHOT_MX', 'fp32'),
+                     ('SVC_SHOT_M16', '5'), ('SVC_SHOT_M16', '1'), ('SVC_SHOT_M16', '3x'), ('SVC_SHOT_M16', '')):
         old = os.environ.get(var)
         os.environ[var] = val
         try:

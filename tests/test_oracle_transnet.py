@@ -82,3 +82,75 @@ def test_scene_walks():
     # assert_segmentation: shots shorter than 12 frames dropped, neighbours made adjacent, the last one reaches the end
     shots = Hd.shots_from_predictions(np.array([0] * 30 + [1] + [0] * 5 + [1] + [0] * 40, np.float32), 0.1)
     assert shots.tolist() == [[0, 36], [37, 76]]
+
+
+@pytest.mark.parametrize('variant', ['seed0', 'loud'])
+def test_fp32_oracle_is_within_a_stated_bound_of_the_float64_one_on_every_tap(variant):
+    """The gates of tests/test_gpu_transnet_layers.py are set against the float64 restatement; the fp32 oracle (tests/test_gpu_transnet.py's
+    reference) stays within 5e-6 of max|ref| of it on every tap (measured here: 3e-8 on the input, 4e-7 .. 1.3e-6 from the first cell to
+    the logits, at both scales).  The taps are consistent with forward's P and with each other."""
+    import torch
+    torch.set_num_threads(8)
+    sd = R.variant_state_dict(variant)
+    fr = np.stack([R.frames('video', 17, 5), R.frames('noise', 17, 6)])
+    p32, t32 = R.forward(sd, fr, taps=True)
+    p64, t64 = R.forward(sd, fr, torch.float64, taps=True)
+    assert np.array_equal(p32, R.forward(sd, fr)) and t64['P'].dtype == np.float64
+    names = ['input'] + ['pre%d' % i for i in range(1, 7)] + ['cell%d' % i for i in range(1, 7)] + ['pool1', 'pool2', 'pool3', 'dense', 'logits']
+    assert sorted(t64) == sorted(names + ['P'])
+    for k in names:
+        assert t32[k].shape == t64[k].shape and t32[k].dtype == np.float32
+        assert np.abs(t32[k] - t64[k]).max() <= 5e-6 * np.abs(t64[k]).max(), k
+    for tp in (t32, t64):
+        assert np.array_equal(tp['input'], fr / np.array(255.0, tp['input'].dtype))
+        for i, shape in enumerate([(27, 48, 64)] * 2 + [(13, 24, 128)] * 2 + [(6, 12, 256)] * 2):
+            assert tp['cell%d' % (i + 1)].shape == (2, 17) + shape
+            assert np.array_equal(tp['cell%d' % (i + 1)], np.maximum(tp['pre%d' % (i + 1)], 0))
+        for b, (c, hh, ww) in enumerate(((2, 13, 24), (4, 6, 12), (6, 3, 6))):
+            x = tp['cell%d' % c][:, :, :2 * hh, :2 * ww]
+            assert np.array_equal(tp['pool%d' % (b + 1)], x.reshape(2, 17, hh, 2, ww, 2, -1).max((3, 5)))
+        ld = tp['logits'][..., 1] - tp['logits'][..., 0]
+        assert np.allclose(tp['P'], 0.5 * (1 + np.tanh(ld / 2)), rtol=1e-5, atol=1e-7)      # softmax, class 1
+    if variant == 'loud':
+        assert np.abs(t64['cell6']).max() > 500                        # the scale the variant is there for
+
+
+def test_windows_are_the_reference_predict_videos():
+    """tests/golden/transnet_windows.npz (tools/make_golden_transnet_windows.py): the windows the reference's predict_video
+    (transnetv1_handler.py:102-130) feeds to predict_raw, and its output, for 18 lengths around the window and stride edges.
+    R.window_indices and Hd.window_indices are those windows; Hd.ShotTransNet.predict_video, its raw predictor replaced by one that
+    returns window * 1000 + slot, returns the reference's output (so it keeps the same slot of the same window for every frame),
+    and with keep=(a, b) the same rows."""
+    import os
+    import torch
+    from retargetvid_amd import transnetv1_handler as Hd
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'transnet_windows.npz'))
+    lengths = [int(n) for n in z['lengths']]
+    assert lengths == [1, 2, 24, 25, 26, 49, 50, 51, 74, 75, 76, 99, 100, 101, 149, 150, 151, 2037]
+
+    class Mock(Hd.ShotTransNet):
+        def __init__(self):
+            self.params, self.windows_per_call, self.seen = Hd.ShotTransNetParams(), 3, []
+
+        def _device(self):
+            return torch.device('cpu')
+
+        def predict_raw_device(self, frames, rows=None):
+            assert rows == (25, 75) and frames.shape[1:] == (100, 27, 48, 3)
+            idx = frames[:, :, 0, 0, 0].long() + 256 * frames[:, :, 0, 0, 1].long()
+            self.seen.extend(idx.numpy())
+            k = idx[:, 25] // 50                                        # window k's slot 25 holds frame 50 k
+            return (k[:, None] * 1000 + torch.arange(100)[None]).float()
+
+    for n in lengths:
+        win, out = z['win_%d' % n], z['out_%d' % n]
+        assert np.array_equal(R.window_indices(n), win) and np.array_equal(Hd.window_indices(n), win), n
+        fr = np.zeros((n, 27, 48, 3), np.uint8)
+        fr[:, 0, 0, 0], fr[:, 0, 0, 1] = np.arange(n) % 256, np.arange(n) // 256
+        m = Mock()
+        got = m.predict_video(fr)
+        assert got.shape == (n,) and np.array_equal(got, out) and np.array_equal(np.stack(m.seen), win), n
+        for a, b in ((0, 1), (n // 3, n - n // 4), (n - 1, n)):
+            if b > a:
+                part = Mock().predict_video(fr, keep=(a, b))
+                assert np.array_equal(part[a:b], out[a:b]), (n, a, b)
