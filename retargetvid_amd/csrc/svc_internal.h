@@ -133,36 +133,14 @@ struct SvcHandle {
     std::map<std::tuple<const void *, int, int, int>, DevBuf> lane_w;   // split-K layers' weights in lane order (svc_net.hip: lane_weights), keyed by (matrix, row stride, K, padded N)
     std::map<std::tuple<const void *, int, int, int>, DevBuf> x3_w;     // split-bf16 copies of weight matrices (svc_net.hip: x3_weights), keyed by (matrix, row stride, K, 2 * padded N + order)
     int mx = 6;                        // matrix pipe of the 1x1-convolution GEMMs: 6 = split-bf16 operands, six plane pairs on v_mfma_f32_32x32x16_bf16 (round 5, the default: a pass 1.42 -> 1.24 ms alone, 1.01 -> 0.87 ms with four passes sharing the chip, every parity gate unchanged); 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32, rounds 1-4: SVC_MX=f32).  The one kernel found to miscompute beside bf16 workgroups, the smoothing kernel, lost a product in a packed-instruction sequence of its bilinear stage: written with scalar instructions since (sd_bilinear)
-    unsigned irb_mx = 0x1b;            // ... which of k_irb's five fixed-shape instances take that form for their expand GEMM (bit = block 2, 3, 4, 5-6, 7; SVC_IRB_MX).  Measured per instance against the fp32 form, us per pass alone / shared: -17 / -11, -12 / -7, +11 / +11 (block 4: Cin = 24 pads its second step, two halo tiles per wave: 36 spilled registers), -11 / -4, -10 / -6: block 4 stays fp32
-    unsigned mx_mask = 0xff;           // ... and which kernel families: bit 0 k_pwr, 1 k_irb, 2 k_dwpw, 3 k_pw_sk, 4 k_pwpw (SVC_MX_MASK; for A/B timing)
     bool sk_lane = true;               // k_pw_sk reads its weights from the lane-order copy: a wave's load is 1 KB contiguous instead of 32 rows x 32 B (SVC_SK_LANE=0: from the [N][K] matrix)
     std::set<const void *> lds_attr_done;   // kernels whose dynamic-LDS limit has been raised on this handle's device
     int chunk = 32;                    // frames per network pass
     DevBuf census;                     // threshold census (svc_threshold_census): [4] u64 totals, then [chunk][4] u32 per-frame counts of the last pass
     unsigned long long census_maps = 0;
-    int pw_min_wg = 1024;              // k_pw narrows its column tile until the grid has this many workgroups (SVC_PW_MIN_WG)
-    bool pw_sk = true;                 // split-K pointwise kernel for long-K small-M layers (SVC_PW_SK=0 disables)
-    int pw_tr = 2;                     // k_pw with swapped MFMA operands (a lane owns one pixel, float4 epilogue): 0 never, 1 always, 2 for wave tiles of 2+ column tiles and up-sample-add launches (single-tile launches store whole 128 B lines with the scalar form)
-    int pw_sk_max = 2048;              // ... when row blocks x column tiles (at the nominal batch) do not exceed this (SVC_PW_SK_MAX)
-    int pw_small = 0;                  // small-M pointwise layers on 16-row wave tiles (SVC_PW_SMALL: 0 off, 1: 16x32, 2: 16x64, 3: 32x32)
-    bool pwr = true;                   // short-K pointwise layers with the activations resident in registers and the weight chunk in LDS (SVC_PWR=0: k_pw)
-    int pwr_nt = 2;                    // ... column tiles (of 32) per workgroup (measured at B = 32: 1 / 2 / 3 / 4 -> 1.735 / 1.692 / 1.726 / 1.767 ms per pass); 0 = as many as leave pwr_min_wg workgroups (SVC_PWR_NT)
-    int pwr_min_wg = 512;              // (SVC_PWR_MIN_WG)
-    bool pw16 = true;                  // 16x16x4 MFMA pointwise kernel for narrow short-K layers (SVC_PW16=0: always 32x32x2)
-    int fuse_max = 7;                  // backbone blocks 1..fuse_max run as the fused inverted-residual kernel (SVC_FUSE_MAX, 0..13)
-    bool split_up = true;              // decoder expansions as conv(skip) + up-sample(conv(low-res part)) (SVC_SPLIT_UP=0: up-sample, concatenate, one GEMM)
-    bool irb_fixed = true;             // fused blocks of the six MobileNetV2 shapes run compile-time-shaped instances (SVC_IRB_FIXED=0: generic)
     DevBuf stem_wt;                    // stem weights transposed to [32 out][32 taps, 27 used] for the MFMA stem
-    int smooth_mfma = 1;               // 41x41 smoothing phases as a GEMM on the matrix cores (SVC_SMOOTH_MFMA=0: the FMA kernel)
     bool front = true;                 // LANCZOS + features.0 + features.1 as one kernel, k_front (SVC_FRONT=0: three kernels)
     bool keep_input = false;           // ... which then also writes the normalised network input for svc_debug_tap(SVC_TAP_INPUT) (SVC_KEEP_INPUT=1)
-    bool dwpw = true;                  // depthwise 3x3 fused into the following 1x1 project (SVC_DWPW=0: two kernels)
-    bool pwpw = true;                  // the skip branches' two 1x1 convolutions (ReLU6 between) as one launch, k_pwpw: the intermediate tensor stays in registers (SVC_PWPW=0: two launches)
-    unsigned seg_off = 0;              // MEASUREMENT AID (SVC_SEG_OFF=bitmask): stages of the network pass whose launches are skipped -- the maps are then garbage; tools/time_segments.py prices a stage by leaving it out.  Stages: 0 front, 1 blocks 2-3, 2 blocks 4-7, 3 blocks 8-14, 4 blocks 15-17, 5 features.18 + skips + post_cnn, 6 upsampling block 1, 7 upsampling block 2, 8 adaptation / smoothing / quantisation
-    int seg_cur = 0;                   // stage forward_chunk is in
-    int dwpw_max_nt = 5;               // output-channel tiles (32 columns each) per k_dwpw workgroup: fewer = more workgroups, the depthwise part redone per group (SVC_DWPW_NT)
-    int dwpw_min_px = 400;             // ... on levels with at least this many pixels per frame (SVC_DWPW_MIN_PX); svc_create sets 100 with the split-bf16 pipe (the fused kernel then wins on the 8x13 level too: -18 us per shared pass), 400 is the fp32 pipe's optimum
-    int dw_tile = 42;                  // stride-1 depthwise: outputs per thread as TX*10+TY (SVC_DW_TILE: 21, 22, 41, 42, 44; 0 = one output per thread)
     int prim_pt = 2;                   // legacy Prim (k_prim_pt): smallest points-per-thread variant (SVC_PRIM_PT: 2, 4, 8, 16)
     int tail_merge = 1;                // a round's kernels as two fused launches, k_tail_front / k_tail_back (SVC_TAIL_MERGE=0: one launch per stage, for per-kernel profiles)
     int tree_par = 1;                  // data-parallel hierarchy k_tree_par for maps of up to 4352 points (SVC_TREE_PAR=0: the serial builder k_tree)

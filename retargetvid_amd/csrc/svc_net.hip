@@ -8,13 +8,13 @@
 //   k_render_*       frame[by1:by2, bx1:bx2, :] (+ cv2.resize INTER_LINEAR, + RGB2BGR)  smartVidCrop.py:1801-1921
 //   k_lanczos_norm   PIL LANCZOS + ToTensor + Normalize 3rd_party_libs/unisal/unisal/data.py:1281-1294
 //   k_stem           conv_bn(3,32,stride 2)+ReLU6      unisal/models/MobileNetV2.py:10-15,124
-//   k_pw<TN>         1x1 conv (+BN)(+ReLU6)(+residual) MobileNetV2.py:18-23,26-83; unisal/model.py:388-409
-//   k_dw<S>          3x3 depthwise (+BN+ReLU6)         MobileNetV2.py:48-51,66-69
+//   k_pwr, k_pw_sk   1x1 conv (+BN)(+ReLU6)(+residual) MobileNetV2.py:18-23,26-83; unisal/model.py:388-409
+//   k_dw_tile        3x3 depthwise (+BN+ReLU6)         MobileNetV2.py:48-51,66-69
 //   k_subsample      x[..., ::2, ::2] (omit-stride)    MobileNetV2.py:170-171
 //   k_gauss_fill     Gaussian prior maps + concat      unisal/model.py:348-385,446-448
-//   k_upsample2x     bilinear x2, align_corners=False  unisal/model.py:304-309,475-478
+//   UpsAdd (k_pwr)   bilinear x2, align_corners=False  unisal/model.py:304-309,475-478
 //   k_adapt          adaptation 1x1 64->1 (+bias)      unisal/model.py:481-483
-//   k_smooth_down    nearest x8 + replicate pad 20 + 41x41 smoothing + bilinear to (h,w)
+//   k_smooth_down_mfma nearest x8 + replicate pad 20 + 41x41 smoothing + bilinear to (h,w)
 //                                                      unisal/model.py:485-495
 //   k_quantise       log-softmax/exp/max/x255/u8 cast  unisal/utils.py:132-136, unisal/train.py:1267-1274
 #include <math.h>
@@ -867,14 +867,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 }
 
 // --------------------------------------------------------------------------------------
-// pointwise conv as a GEMM on the f32 MFMA:  Y[M,N] = act(X[M,K] * W[N,K]^T + b) (+ R)
-// Block = 4 waves; wave v owns rows m0+32v..+31 and TN column tiles of 32.
-// Lane l (r = l&31, hh = l>>5) feeds A[r][k] and B[k][r] with k = kk + 4*hh + s for the
-// s-th MFMA of an 8-deep K chunk: both operands come from one float4 per lane, read
-// straight from global memory (the k order inside a chunk is a consistent permutation).
-// --------------------------------------------------------------------------------------
-// Optional epilogue term of k_pw: a low-resolution tensor U [n][UH][UW][ldu] added after 2x bilinear
-// up-sampling (align_corners = False, the arithmetic of k_upsample2x).  A 1x1 convolution commutes with the
+// Optional epilogue term of k_pwr: a low-resolution tensor U [n][UH][UW][ldu] added after 2x bilinear up-sampling
+// (align_corners = False, model.py:304-309: source coordinate max(0.5 (o + 0.5) - 0.5, 0), the upper neighbour clamped to the
+// last row / column, ly0 (lx0 v00 + lx1 v01) + ly1 (lx0 v10 + lx1 v11)).  A 1x1 convolution commutes with the
 // up-sampling, so the decoder's "up-sample, concatenate with the skip, expand" (model.py:463-483) is evaluated
 // as conv(skip part) + up-sample(conv(low-resolution part)): the up-sampled half of the concatenation is
 // contracted at a quarter of the pixels and never materialised.
@@ -884,171 +879,16 @@ struct UpsAdd {
     FDiv dOW, dOH;
 };
 
-// TR = true: the MFMA operands are swapped (weights as A, activations as B), so a lane ends up with ONE pixel and
-// 16 output channels in runs of four -- the epilogue then moves float4 (4 stores per tile instead of 16).
-template <int TN, int PF, bool TR = false>
-__global__ __launch_bounds__(256) SVC_NO_PK void k_pw(const float *__restrict__ X, int ldx, const float *__restrict__ Wt, int ldw,
-                                            const float *__restrict__ bias, const float *__restrict__ R, int ldr,
-                                            float *__restrict__ Y, int ldy, int M, int N, int Npad, int K,
-                                            int relu6, UpsAdd ups) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, hh = lane >> 5;
-    const int m0 = xcd_bx() * 128 + wave * 32;
-    const int n0 = blockIdx.y * (32 * TN);
-    if (m0 >= M) return;
-    const int row = min(m0 + r, M - 1);
-    const float *xp = X + (size_t)row * ldx + 4 * hh;
-    const float *wp[TN];
-#pragma unroll
-    for (int t = 0; t < TN; ++t) {
-        int col = min(n0 + t * 32 + r, Npad - 1);
-        wp[t] = Wt + (size_t)col * ldw + 4 * hh;
-    }
-    f32x16 acc[TN];
-#pragma unroll
-    for (int t = 0; t < TN; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-    // the operands of PF k-steps (8 deep each) are in flight ahead of the MFMAs (PF = 1 measured
-    // fastest on MI355X: these layers are bound by the L1 line rate, not by load latency)
-    const int nsteps = K >> 3;
-    float4 A[PF], B[PF][TN];
-#pragma unroll
-    for (int p = 0; p < PF; ++p)
-        if (p < nsteps) {
-            A[p] = *(const float4 *)(xp + 8 * p);
-#pragma unroll
-            for (int t = 0; t < TN; ++t) B[p][t] = *(const float4 *)(wp[t] + 8 * p);
-        }
-    for (int s0 = 0; s0 < nsteps; s0 += PF) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int st = s0 + p;
-            if (st < nsteps) {
-                const float4 a = A[p];
-                float4 b[TN];
-#pragma unroll
-                for (int t = 0; t < TN; ++t) b[t] = B[p][t];
-                if (st + PF < nsteps) {
-                    A[p] = *(const float4 *)(xp + 8 * (st + PF));
-#pragma unroll
-                    for (int t = 0; t < TN; ++t) B[p][t] = *(const float4 *)(wp[t] + 8 * (st + PF));
-                }
-#pragma unroll
-                for (int t = 0; t < TN; ++t) {
-                    if (TR) {
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[t].x, a.x, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[t].y, a.y, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[t].z, a.z, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[t].w, a.w, acc[t], 0, 0, 0);
-                    } else {
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b[t].x, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b[t].y, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[t].z, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[t].w, acc[t], 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-    if (TR) {
-        // lane = pixel m0 + r; accumulator i = channel n0 + 32t + 8(i>>2) + 4hh + (i&3)
-        const int rr = m0 + r;
-        if (rr >= M) return;
-        const float *u00 = nullptr, *u01 = nullptr, *u10 = nullptr, *u11 = nullptr;
-        float w00 = 0.f, w01 = 0.f, w10 = 0.f, w11 = 0.f;
-        if (ups.U) {
-            uint32_t ox, oy;
-            const uint32_t f = fdivmod(fdivmod((uint32_t)rr, ups.dOW, ox), ups.dOH, oy);
-            const float sy = fmaxf(0.5f * (oy + 0.5f) - 0.5f, 0.f), sx = fmaxf(0.5f * (ox + 0.5f) - 0.5f, 0.f);
-            const int y0 = (int)sy, x0 = (int)sx;
-            const int y1 = y0 + (y0 < ups.UH - 1 ? 1 : 0), x1 = x0 + (x0 < ups.UW - 1 ? 1 : 0);
-            const float ly1 = sy - y0, lx1 = sx - x0, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
-            const float *uf = ups.U + (size_t)f * ups.UH * ups.UW * ups.ldu;
-            u00 = uf + ((size_t)y0 * ups.UW + x0) * ups.ldu; u01 = uf + ((size_t)y0 * ups.UW + x1) * ups.ldu;
-            u10 = uf + ((size_t)y1 * ups.UW + x0) * ups.ldu; u11 = uf + ((size_t)y1 * ups.UW + x1) * ups.ldu;
-            w00 = lx0; w01 = lx1; w10 = ly0; w11 = ly1;
-        }
-#pragma unroll
-        for (int t = 0; t < TN; ++t)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int col = n0 + t * 32 + 8 * g + 4 * hh;
-                if (col >= N) continue;
-                float4 v = make_float4(acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]);
-                if (bias) { const float4 bv = *(const float4 *)(bias + col); v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w; }
-                if (ups.U) {
-                    const float4 a0 = *(const float4 *)(u00 + col), a1 = *(const float4 *)(u01 + col);
-                    const float4 c0 = *(const float4 *)(u10 + col), c1 = *(const float4 *)(u11 + col);
-                    v.x += w10 * (w00 * a0.x + w01 * a1.x) + w11 * (w00 * c0.x + w01 * c1.x);
-                    v.y += w10 * (w00 * a0.y + w01 * a1.y) + w11 * (w00 * c0.y + w01 * c1.y);
-                    v.z += w10 * (w00 * a0.z + w01 * a1.z) + w11 * (w00 * c0.z + w01 * c1.z);
-                    v.w += w10 * (w00 * a0.w + w01 * a1.w) + w11 * (w00 * c0.w + w01 * c1.w);
-                }
-                if (R) { const float4 rv = *(const float4 *)(R + (size_t)rr * ldr + col); v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w; }
-                if (relu6) {
-                    v.x = fminf(fmaxf(v.x, 0.f), 6.f); v.y = fminf(fmaxf(v.y, 0.f), 6.f);
-                    v.z = fminf(fmaxf(v.z, 0.f), 6.f); v.w = fminf(fmaxf(v.w, 0.f), 6.f);
-                }
-                *(float4 *)(Y + (size_t)rr * ldy + col) = v;
-            }
-        return;
-    }
-    if (ups.U) {
-        // rows first: the four taps and weights of an output pixel are shared by all of the wave's column tiles
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int rr = m0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-            if (rr >= M) continue;
-            uint32_t ox, oy;
-            const uint32_t f = fdivmod(fdivmod((uint32_t)rr, ups.dOW, ox), ups.dOH, oy);
-            const float sy = fmaxf(0.5f * (oy + 0.5f) - 0.5f, 0.f), sx = fmaxf(0.5f * (ox + 0.5f) - 0.5f, 0.f);
-            const int y0 = (int)sy, x0 = (int)sx;
-            const int y1 = y0 + (y0 < ups.UH - 1 ? 1 : 0), x1 = x0 + (x0 < ups.UW - 1 ? 1 : 0);
-            const float ly1 = sy - y0, lx1 = sx - x0, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
-            const float *uf = ups.U + (size_t)f * ups.UH * ups.UW * ups.ldu;
-            const float *u00 = uf + ((size_t)y0 * ups.UW + x0) * ups.ldu, *u01 = uf + ((size_t)y0 * ups.UW + x1) * ups.ldu;
-            const float *u10 = uf + ((size_t)y1 * ups.UW + x0) * ups.ldu, *u11 = uf + ((size_t)y1 * ups.UW + x1) * ups.ldu;
-#pragma unroll
-            for (int t = 0; t < TN; ++t) {
-                const int col = n0 + t * 32 + r;
-                if (col >= N) continue;
-                float v = acc[t][i] + (bias ? bias[col] : 0.f);
-                v += ly0 * (lx0 * u00[col] + lx1 * u01[col]) + ly1 * (lx0 * u10[col] + lx1 * u11[col]);
-                if (relu6) v = fminf(fmaxf(v, 0.f), 6.f);
-                Y[(size_t)rr * ldy + col] = v;
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int t = 0; t < TN; ++t) {
-        const int col = n0 + t * 32 + r;
-        if (col >= N) continue;
-        const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int rr = m0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-            if (rr < M) {
-                float v = acc[t][i] + bv;
-                if (R) v += R[(size_t)rr * ldr + col];
-                if (relu6) v = fminf(fmaxf(v, 0.f), 6.f);
-                Y[(size_t)rr * ldy + col] = v;
-            }
-        }
-    }
-}
-
 // --------------------------------------------------------------------------------------
 // Short-K pointwise layers (K <= 160: the 6x expansions of blocks 8-17, the skips, the decoder expansions) with the
-// activations RESIDENT IN REGISTERS.  k_pw feeds both MFMA operands from global memory per k-step: every column tile
+// activations RESIDENT IN REGISTERS.  Feeding both MFMA operands from global memory per k-step, every column tile
 // re-reads the activation rows, the four waves of a workgroup each re-read the same weight rows, one load pair is in
 // flight per wave, and a load instruction touches 32 cache lines for 1 KB -- the CU's vector-memory path is as busy as
 // its matrix pipes and the waves sit in s_waitcnt (SQ_WAIT_ANY 59 %).  Here a wave loads its 32 rows x K ONCE, all
 // k-steps in flight together (KS float4 per lane), the workgroup's weight chunk (NTW column tiles x K) is staged once
 // in LDS and shared by the four waves, and the wave then walks the NTW column tiles with the activations in registers:
 // per tile K/2 MFMAs fed by one ds_read_b128 per four MFMAs, and a float4 epilogue (operands swapped: a lane owns one
-// pixel).  Global loads per MFMA drop by 2 NTW x; the k order of every sum is k_pw's, so results are bit-identical.
+// pixel).  Global loads per MFMA drop by 2 NTW x.
 // --------------------------------------------------------------------------------------
 // The epilogue goes through a per-wave LDS slab: the accumulator layout gives a lane 16 B pieces of ONE pixel's row, so a
 // direct float4 store instruction touches 32 cache lines for 1 KB and the CU's store path, not HBM, limits the kernel
@@ -1216,72 +1056,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
 }
 
 // --------------------------------------------------------------------------------------
-// Pointwise conv on v_mfma_f32_16x16x4_f32 (K % 16 == 0): the four 16-lane groups of a wave
-// carry four k slots, so one float4 load instruction covers 16 rows x 64 contiguous bytes
-// (16 cache lines) instead of 32 rows x 32 bytes (32 lines) — these layers are bound by the
-// L1 line rate (SQ_WAIT_ANY ~ 68 % in k_pw).  Wave tile 32 x (32*TN) = 2 x 2TN accumulators
-// of 16x16; lane l (r16 = l&15, q = l>>4) feeds A[r16][k0+4q+j], B[k0+4q+j][r16] in MFMA j.
-// --------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-template <int MT, int NT>     // wave tile = (16*MT) rows x (16*NT) columns; workgroup = 4 waves stacked along M
-__global__ __launch_bounds__(256) void k_pw16(const float *__restrict__ X, int ldx, const float *__restrict__ Wt, int ldw,
-                                              const float *__restrict__ bias, const float *__restrict__ R, int ldr,
-                                              float *__restrict__ Y, int ldy, int M, int N, int Npad, int K,
-                                              int relu6) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r16 = lane & 15, q = lane >> 4;
-    const int m0 = xcd_bx() * (64 * MT) + wave * (16 * MT);
-    const int n0 = blockIdx.y * (16 * NT);
-    if (m0 >= M) return;
-    const float *xa[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) xa[i] = X + (size_t)min(m0 + 16 * i + r16, M - 1) * ldx + 4 * q;
-    const float *wb[NT];
-#pragma unroll
-    for (int c = 0; c < NT; ++c) wb[c] = Wt + (size_t)min(n0 + 16 * c + r16, Npad - 1) * ldw + 4 * q;
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int c = 0; c < NT; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][c][e] = 0.f;
-#pragma unroll 2
-    for (int k = 0; k < K; k += 16) {
-        float4 a[MT], b[NT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) a[i] = *(const float4 *)(xa[i] + k);
-#pragma unroll
-        for (int c = 0; c < NT; ++c) b[c] = *(const float4 *)(wb[c] + k);
-#define PW16_STEP(EL)                                                                                       \
-    _Pragma("unroll") for (int c = 0; c < NT; ++c) _Pragma("unroll") for (int i = 0; i < MT; ++i)           \
-        acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].EL, b[c].EL, acc[i][c], 0, 0, 0);
-        PW16_STEP(x) PW16_STEP(y) PW16_STEP(z) PW16_STEP(w)
-#undef PW16_STEP
-    }
-#pragma unroll
-    for (int c = 0; c < NT; ++c) {
-        const int col = n0 + 16 * c + r16;
-        if (col >= N) continue;
-        const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int rr = m0 + 16 * i + 4 * q + e;
-                if (rr < M) {
-                    float v = acc[i][c][e] + bv;
-                    if (R) v += R[(size_t)rr * ldr + col];
-                    if (relu6) v = fminf(fmaxf(v, 0.f), 6.f);
-                    Y[(size_t)rr * ldy + col] = v;
-                }
-            }
-    }
-}
-
-// --------------------------------------------------------------------------------------
-// Split-K variant for the long-K, small-M layers (8x13 / 16x26 levels at B = 32), where k_pw runs
-// one wave per SIMD through a serial K loop: the workgroup owns 32 rows x (32*TN) columns and its
+// Split-K pointwise GEMM for the long-K, small-M layers (8x13 / 16x26 levels at B = 32), where one wave per 32-row tile
+// would leave one wave per SIMD in a serial K loop: the workgroup owns 32 rows x (32*TN) columns and its
 // four waves each take a quarter of K; the partial tiles meet in LDS and are summed in a fixed
 // order (deterministic), every wave finishing four of the sixteen accumulator rows.
 // --------------------------------------------------------------------------------------
@@ -1434,53 +1210,12 @@ __global__ __launch_bounds__(256) void k_pw_sk(const float *__restrict__ X, int 
 }
 
 // --------------------------------------------------------------------------------------
-// depthwise 3x3 pad 1, stride S, + bias, ReLU6.  NHWC, one thread = one pixel x 4 channels.
-// w layout [9][C]
+// Depthwise 3x3 pad 1, stride 1, + bias, ReLU6.  NHWC, w layout [9][C].  A thread owns a TX x TY register tile of outputs
+// (x 4 channels): it walks its TY+2 input rows once, keeps one row of TX+2 taps in registers and feeds every output row that
+// uses it: (TY+2)(TX+2)+9 loads for TX*TY outputs (4.1 per output at 4x2; one output per thread would issue 18 vector loads
+// and be bound by the CU's vector-memory issue rate, not by HBM).  Per output the taps are accumulated in the order ky, kx
+// with out-of-image taps contributing nothing.
 // --------------------------------------------------------------------------------------
-template <int S>
-__global__ __launch_bounds__(256) void k_dw(const float *__restrict__ X, const float *__restrict__ Wt,
-                                            const float *__restrict__ bias, float *__restrict__ Y, int n, int H,
-                                            int W, int C, int OH, int OW, FDiv dC4, FDiv dOW, FDiv dOH) {
-    const int C4 = C >> 2;
-    const uint32_t gid = xcd_bx() * 256u + threadIdx.x;
-    const uint32_t total = (uint32_t)n * OH * OW * C4;
-    if (gid >= total) return;
-    uint32_t c4, ox, oy;
-    const uint32_t pix = fdivmod(gid, dC4, c4);
-    const uint32_t f = fdivmod(fdivmod(pix, dOW, ox), dOH, oy);
-    const float *xf = X + (size_t)f * H * W * C + c4 * 4;
-    const float *wf = Wt + c4 * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-        int iy = oy * S - 1 + ky;
-        if (iy < 0 || iy >= H) continue;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            int ix = ox * S - 1 + kx;
-            if (ix < 0 || ix >= W) continue;
-            const float4 x = *(const float4 *)(xf + ((size_t)iy * W + ix) * C);
-            const float4 w = *(const float4 *)(wf + (ky * 3 + kx) * C);
-            acc.x = fmaf(x.x, w.x, acc.x);
-            acc.y = fmaf(x.y, w.y, acc.y);
-            acc.z = fmaf(x.z, w.z, acc.z);
-            acc.w = fmaf(x.w, w.w, acc.w);
-        }
-    }
-    const float4 b = *(const float4 *)(bias + c4 * 4);
-    acc.x = fminf(fmaxf(acc.x + b.x, 0.f), 6.f);
-    acc.y = fminf(fmaxf(acc.y + b.y, 0.f), 6.f);
-    acc.z = fminf(fmaxf(acc.z + b.z, 0.f), 6.f);
-    acc.w = fminf(fmaxf(acc.w + b.w, 0.f), 6.f);
-    *(float4 *)(Y + (size_t)gid * 4) = acc;
-}
-
-// Stride-1 depthwise with a TX x TY register tile of outputs per thread (x 4 channels).  k_dw issues 18
-// vector loads per output (9 taps + 9 weights) and is bound by the CU's vector-memory issue rate, not by
-// HBM; here a thread walks its TY+2 input rows once, keeps one row of TX+2 taps in registers and feeds
-// every output row that uses it: (TY+2)(TX+2)+9 loads for TX*TY outputs (4.1 per output at 4x2).  Per
-// output the taps are still accumulated in the order ky, kx with out-of-image taps contributing nothing,
-// so the result equals k_dw<1>'s.
 template <int TX, int TY>
 __global__ __launch_bounds__(256) void k_dw_tile(const float *__restrict__ X, const float *__restrict__ Wt,
                                                  const float *__restrict__ bias, float *__restrict__ Y, int n,
@@ -1565,33 +1300,6 @@ __global__ __launch_bounds__(256) void k_gauss_fill(const float *__restrict__ G,
     size_t fp = gid >> 4;
     int pos = fp % npos;
     Y[fp * ldy + c_off + j] = G[pos * 16 + j];
-}
-
-// bilinear x2 (align_corners=False): X[n][H][W][C] -> Y[n][2H][2W][ldy] channels 0..C-1
-__global__ __launch_bounds__(256) SVC_NO_PK void k_upsample2x(const float *__restrict__ X, float *__restrict__ Y, int n,
-                                                    int H, int W, int C, int ldy, FDiv dC4, FDiv dOW, FDiv dOH) {
-    const int C4 = C >> 2, OH = 2 * H, OW = 2 * W;
-    const uint32_t gid = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t total = (uint32_t)n * OH * OW * C4;
-    if (gid >= total) return;
-    uint32_t c4, ox, oy;
-    const uint32_t pix = fdivmod(gid, dC4, c4);
-    const uint32_t f = fdivmod(fdivmod(pix, dOW, ox), dOH, oy);
-    float sy = fmaxf(0.5f * (oy + 0.5f) - 0.5f, 0.f), sx = fmaxf(0.5f * (ox + 0.5f) - 0.5f, 0.f);
-    int y0 = (int)sy, x0 = (int)sx;
-    int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    float ly1 = sy - y0, lx1 = sx - x0, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
-    const float *xf = X + (size_t)f * H * W * C + c4 * 4;
-    const float4 v00 = *(const float4 *)(xf + ((size_t)y0 * W + x0) * C);
-    const float4 v01 = *(const float4 *)(xf + ((size_t)y0 * W + x1) * C);
-    const float4 v10 = *(const float4 *)(xf + ((size_t)y1 * W + x0) * C);
-    const float4 v11 = *(const float4 *)(xf + ((size_t)y1 * W + x1) * C);
-    float4 o;
-    o.x = ly0 * (lx0 * v00.x + lx1 * v01.x) + ly1 * (lx0 * v10.x + lx1 * v11.x);
-    o.y = ly0 * (lx0 * v00.y + lx1 * v01.y) + ly1 * (lx0 * v10.y + lx1 * v11.y);
-    o.z = ly0 * (lx0 * v00.z + lx1 * v01.z) + ly1 * (lx0 * v10.z + lx1 * v11.z);
-    o.w = ly0 * (lx0 * v00.w + lx1 * v01.w) + ly1 * (lx0 * v10.w + lx1 * v11.w);
-    *(float4 *)(Y + (size_t)pix * ldy + c4 * 4) = o;
 }
 
 // adaptation: logit[p] = sum_c X[p][c] * w[c] + b, C = 64
@@ -1793,64 +1501,12 @@ __global__ __launch_bounds__(256) SD_NO_PK void k_smooth_down_mfma(const float *
         }
     }
 #endif
-    for (int o = 32; o > 0; o >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, o));
+    // (written out: the compiler does not unroll the loop form here)
+    lmax = fmaxf(lmax, __shfl_xor(lmax, 32)); lmax = fmaxf(lmax, __shfl_xor(lmax, 16)); lmax = fmaxf(lmax, __shfl_xor(lmax, 8));
+    lmax = fmaxf(lmax, __shfl_xor(lmax, 4)); lmax = fmaxf(lmax, __shfl_xor(lmax, 2)); lmax = fmaxf(lmax, __shfl_xor(lmax, 1));
     if ((tid & 63) == 0) wmax[tid >> 6] = enc_f32(lmax);
     __syncthreads();
     if (tid == 0) atomicMax(fmax + f, max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
-}
-
-__global__ __launch_bounds__(256) SD_NO_PK void k_smooth_down(const float *__restrict__ logit, const float *__restrict__ phase,
-                                                     float *__restrict__ pre, unsigned *__restrict__ fmax, int LH,
-                                                     int LW, int NH, int NW, int h, int w, int rows_per_block,
-                                                     int tile_cap, FDiv dNW, FDiv dw) {
-    extern __shared__ float sm[];
-    float *L = sm, *ph = sm + LH * LW, *tile = ph + 64 * 49;
-    __shared__ unsigned wmax[4];
-    const int f = blockIdx.y;
-    const int oy0 = blockIdx.x * rows_per_block, oy1 = min(h, oy0 + rows_per_block);
-    const float scy = (float)NH / (float)h, scx = (float)NW / (float)w;
-    const int ylo = (int)fmaxf(scy * (oy0 + 0.5f) - 0.5f, 0.f);
-    const int yhi = min((int)fmaxf(scy * ((oy1 - 1) + 0.5f) - 0.5f, 0.f) + 1, NH - 1);
-    const int nrows = min(yhi - ylo + 1, tile_cap);
-    for (int i = threadIdx.x; i < LH * LW; i += 256) L[i] = logit[(size_t)f * LH * LW + i];
-    for (int i = threadIdx.x; i < 64 * 49; i += 256) ph[i] = phase[i];
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < nrows * NW; idx += 256) {
-        uint32_t x;
-        const int ry = (int)fdivmod((uint32_t)idx, dNW, x);
-        int y = ylo + ry;
-        int cy = y >> 3, py = y & 7, cx = x >> 3, px = x & 7;
-        const float *p = ph + (py * 8 + px) * 49;
-        float s = 0.f;
-#pragma unroll
-        for (int a = 0; a < 7; ++a) {
-            int yy = min(max(cy + a - 3, 0), LH - 1);
-#pragma unroll
-            for (int b = 0; b < 7; ++b) {
-                int xx = min(max(cx + b - 3, 0), LW - 1);
-                s = fmaf(p[a * 7 + b], L[yy * LW + xx], s);
-            }
-        }
-        tile[idx] = s;
-    }
-    __syncthreads();
-    float lmax = -INFINITY;
-    for (int idx = threadIdx.x; idx < (oy1 - oy0) * w; idx += 256) {
-        uint32_t ox;
-        const int oy = oy0 + (int)fdivmod((uint32_t)idx, dw, ox);
-        float sy = fmaxf(scy * (oy + 0.5f) - 0.5f, 0.f), sx = fmaxf(scx * (ox + 0.5f) - 0.5f, 0.f);
-        int y0 = (int)sy, x0 = (int)sx;
-        int y1 = y0 + (y0 < NH - 1 ? 1 : 0), x1 = x0 + (x0 < NW - 1 ? 1 : 0);
-        float ly1 = sy - y0, lx1 = sx - x0, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
-        const float *t0 = tile + (y0 - ylo) * NW, *t1 = tile + (y1 - ylo) * NW;
-        const float v = sd_bilinear(lx0, lx1, ly0, ly1, t0[x0], t0[x1], t1[x0], t1[x1]);
-        pre[((size_t)f * h + oy) * w + ox] = v;
-        lmax = fmaxf(lmax, v);
-    }
-    for (int o = 32; o > 0; o >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, o));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = enc_f32(lmax);
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(fmax + f, max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
 }
 
 // u8 = trunc(255 * exp(x - max x)): the softmax normaliser cancels in p / max p.
@@ -1880,19 +1536,22 @@ __global__ __launch_bounds__(256) void k_quantise(const float *__restrict__ pre,
 // --------------------------------------------------------------------------------------
 // plan / workspace
 // --------------------------------------------------------------------------------------
-enum Buf { B_IN, B_P0, B_P1, B_E0, B_E1, B_F4X, B_F2X, B_S4E, B_S2E, B_CAT1, B_PCD, B_PC, B_CAT2, B_U2E, B_U2D,
-           B_U2, B_CAT3, B_P3E, B_P3D, B_DEC, B_LOGIT, B_PRE, B_T1, B_T2, B_COUNT };
+enum Buf { B_IN, B_P0, B_P1, B_E0, B_E1, B_F4X, B_F2X, B_CAT1, B_PCD, B_PC, B_CAT2, B_U2E, B_U2, B_CAT3, B_P3E, B_DEC,
+           B_LOGIT, B_PRE, B_T1, B_T2, B_COUNT };
+
+#define LZ_ROWS 8       // output rows per workgroup of k_lanczos_norm
+#define SD_ROWS 7       // output rows per workgroup of k_smooth_down_mfma
 
 struct NetPlan {
     int h = 0, w = 0, NH = 0, NW = 0, nb = 0;
     size_t off[B_COUNT + 1];      // per-frame float offsets
     DevBuf ws, fmax, lut, gauss;
     DevBuf hb, hk, vb, vk;
-    int hks = 0, vks = 0, lz_rows = 8, lz_tile_cap = 0;       // output rows per workgroup of k_lanczos_norm (SVC_LZ_ROWS)
+    int hks = 0, vks = 0, lz_tile_cap = 0;                    // k_lanczos_norm: source rows one workgroup needs at most
     int fr_nr = 0, fr_nc = 0;                                 // source rows / columns one tile of k_front needs at most
     bool fr_ok = false;                                       // the geometry can run k_front
     short fr_row_lo[32], fr_row_n[32], fr_col_lo[32], fr_col_n[32];
-    int sd_rows = 7, sd_tile_cap = 0;                         // output rows per workgroup of k_smooth_down (SVC_SD_ROWS)
+    int sd_tile_cap = 0;                                      // k_smooth_down_mfma: network-size rows one workgroup needs at most
     int last_n = 0;
     bool last_front = false;       // the last pass ran k_front (the network input is then kept only under SVC_KEEP_INPUT=1)
     int gauss_filled = 0;          // frames of the workspace whose Gaussian-prior channels of CAT1 are already written
@@ -1931,8 +1590,6 @@ static int build_plan(SvcHandle *h, int height, int width, int nb) {
     int NH, NW;
     optimal_out_size(height, width, NH, NW);
     const bool same_size = (p->h == height && p->w == width);
-    if (const char *e = getenv("SVC_LZ_ROWS")) if (atoi(e) > 0) p->lz_rows = atoi(e);
-    if (const char *e = getenv("SVC_SD_ROWS")) if (atoi(e) > 0) p->sd_rows = atoi(e);
     p->h = height; p->w = width; p->NH = NH; p->NW = NW; p->nb = nb;
     const size_t H1 = NH / 2, W1 = NW / 2, H2 = NH / 4, W2 = NW / 4, H3 = NH / 8, W3 = NW / 8, H4 = NH / 16,
                  W4 = NW / 16, H5 = NH / 32, W5 = NW / 32;
@@ -1943,10 +1600,9 @@ static int build_plan(SvcHandle *h, int height, int width, int nb) {
     sz[B_E0] = std::max(std::max(H1 * W1 * 96, H2 * W2 * 144), std::max(H3 * W3 * 192, std::max(H4 * W4 * 576, H5 * W5 * 960)));
     sz[B_E1] = std::max(std::max(H1 * W1 * 32, H2 * W2 * 144), std::max(H3 * W3 * 192, std::max(H4 * W4 * 576, H5 * W5 * 960)));
     sz[B_F4X] = H3 * W3 * 64;  sz[B_F2X] = H4 * W4 * 160;
-    sz[B_S4E] = H3 * W3 * 128; sz[B_S2E] = H4 * W4 * 320;
     sz[B_CAT1] = H5 * W5 * 1296; sz[B_PCD] = H5 * W5 * 1296; sz[B_PC] = H5 * W5 * 256;
-    sz[B_CAT2] = H4 * W4 * 384; sz[B_U2E] = H4 * W4 * 768; sz[B_U2D] = H4 * W4 * 768; sz[B_U2] = H4 * W4 * 128;
-    sz[B_CAT3] = H3 * W3 * 192; sz[B_P3E] = H3 * W3 * 384; sz[B_P3D] = H3 * W3 * 384; sz[B_DEC] = H3 * W3 * 64;
+    sz[B_CAT2] = H4 * W4 * 384; sz[B_U2E] = H4 * W4 * 768; sz[B_U2] = H4 * W4 * 128;
+    sz[B_CAT3] = H3 * W3 * 192; sz[B_P3E] = H3 * W3 * 384; sz[B_DEC] = H3 * W3 * 64;
     sz[B_T1] = H5 * W5 * 768; sz[B_T2] = H4 * W4 * 384;   // low-resolution halves of the two decoder expansions
     sz[B_LOGIT] = (H3 * W3 + 3) / 4 * 4;
     sz[B_PRE] = ((size_t)height * width + 3) / 4 * 4;
@@ -1962,8 +1618,8 @@ static int build_plan(SvcHandle *h, int height, int width, int nb) {
     lanczos_tab(width, NW, hb, hk, p->hks);
     lanczos_tab(height, NH, vb, vk, p->vks);
     int cap = 0;
-    for (int y0 = 0; y0 < NH; y0 += p->lz_rows) {
-        int y1 = std::min(NH, y0 + p->lz_rows);
+    for (int y0 = 0; y0 < NH; y0 += LZ_ROWS) {
+        int y1 = std::min(NH, y0 + LZ_ROWS);
         cap = std::max(cap, vb[2 * (y1 - 1)] + vb[2 * (y1 - 1) + 1] - vb[2 * y0]);
     }
     p->lz_tile_cap = cap;
@@ -2023,11 +1679,11 @@ static int build_plan(SvcHandle *h, int height, int width, int nb) {
     }
     if ((rc = p->gauss.ensure(g.size() * 4))) return rc;
     SVC_HIP(hipMemcpy(p->gauss.p, g.data(), g.size() * 4, hipMemcpyHostToDevice));
-    // tile rows for k_smooth_down
+    // tile rows for k_smooth_down_mfma
     float scy = (float)NH / (float)height;
     cap = 0;
-    for (int oy0 = 0; oy0 < height; oy0 += p->sd_rows) {
-        int oy1 = std::min(height, oy0 + p->sd_rows);
+    for (int oy0 = 0; oy0 < height; oy0 += SD_ROWS) {
+        int oy1 = std::min(height, oy0 + SD_ROWS);
         int ylo = (int)std::max(scy * (oy0 + 0.5f) - 0.5f, 0.f);
         int yhi = std::min((int)std::max(scy * ((oy1 - 1) + 0.5f) - 0.5f, 0.f) + 1, NH - 1);
         cap = std::max(cap, yhi - ylo + 1);
@@ -2129,36 +1785,31 @@ static int x3_weights(SvcHandle *h, hipStream_t s, const float *Wt, int ldw, int
     return SVC_OK;
 }
 
+// k_pwr: column tiles (of 32) per workgroup.  Measured at B = 32: 1 / 2 / 3 / 4 -> 1.735 / 1.692 / 1.726 / 1.767 ms per pass.
+#define PWR_NT 2
+// k_pw_sk serves a long-K layer (K >= 256) when its row blocks x column tiles, at the nominal batch, do not exceed this.
+#define PW_SK_MAX_WG 2048
+
 // One pointwise layer, or a column slice of one: K of the ldw input channels of the weight rows, starting at Wt
 // (bias may be null).  ups != null adds the up-sampled low-resolution product (see UpsAdd).
 static int launch_pw_ex(SvcHandle *h, hipStream_t s, const float *X, int ldx, const float *Wt, int ldw, int K,
                         const float *bias, int relu6v, int N, const float *R, int ldr, float *Y, int ldy, int M, int n,
                         const UpsAdd *ups) {
-    if (h->seg_off >> h->seg_cur & 1u) return SVC_OK;
     ProfScope ps(h, SVC_K_PW, s);
     const int Npad = (N + 31) / 32 * 32, tiles = Npad / 32;
     UpsAdd ua = ups ? *ups : UpsAdd{nullptr, 0, 0, 0, make_fdiv(1), make_fdiv(1)};
     const int rb = ceil_div(M, 128);
-    int TN = 4;
-    while (TN > 1 && (TN > tiles || rb * ceil_div(tiles, TN) < h->pw_min_wg)) --TN;
-    dim3 grid(rb, ceil_div(tiles, TN));
     // Which kernel FAMILY runs (and with it the order of the K sum) depends only on the layer shape,
     // judged at a nominal batch of 32 frames, never on the batch actually passed: a frame's map
-    // must not depend on its batch.  The tile shape (TN) may follow the real M, it does not change
-    // any sum order.
+    // must not depend on its batch.
     const int rb_nom = ceil_div((M / n) * 32, 128);
-#define PW16_ARGS X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v
-    // short K, no residual: activations resident in registers, weight chunk shared through LDS (k_pwr)
-    if (h->pwr && !R && (K == 64 || K == 96 || K == 128 || K == 160) && (N % 4) == 0) {
-        // column tiles per workgroup: enough workgroups (at the nominal batch) to put two or three on every CU
-        int ntw = h->pwr_nt;
-        if (ntw <= 0) {
-            ntw = 4;
-            while (ntw > 1 && rb_nom * ceil_div(tiles, ntw) < h->pwr_min_wg) --ntw;
-        }
-        ntw = std::min(ntw, tiles);
+    // short K, no residual: activations resident in registers, weight chunk shared through LDS (k_pwr).  The layers that come
+    // here: K = 64 (the expansions of blocks 8-11; the skip half of the second decoder expansion, with ups), 96 (blocks 12-14),
+    // 128 (the second decoder expansion's low-resolution half; the skip half of the first, with ups), 160 (blocks 15-17)
+    if (!R && (K == 64 || K == 96 || K == 128 || K == 160) && (N % 4) == 0) {
+        const int ntw = std::min(PWR_NT, tiles);
         const dim3 g(rb, ceil_div(tiles, ntw));
-        const bool mx = h->mx != 0 && (h->mx_mask & 1);
+        const bool mx = h->mx != 0;
         const float *Wk = Wt;                                // MX: the split-bf16 copy of the slice, rows of (K / 16) * 6 uint4
         if (mx) {
             const uint4 *W3 = nullptr;
@@ -2168,86 +1819,53 @@ static int launch_pw_ex(SvcHandle *h, hipStream_t s, const float *X, int ldx, co
         }
         const size_t lds = mx ? (size_t)ntw * 32 * ((K / 16) * 6 + 1) * sizeof(uint4) + ((size_t)4 * 32 * PWR_SLAB + 128) * sizeof(float)
                               : ((size_t)ntw * 32 * (K + 4) + 4 * 32 * PWR_SLAB + 128) * sizeof(float);
-#define PWR_ARGS X, ldx, Wk, ldw, bias, Y, ldy, M, N, Npad, ntw, relu6v, ua
-#define PWR_CASE(KSv)                                                                                                   \
-    {                                                                                                                   \
-        auto kfn = mx ? (ups ? k_pwr<KSv, true, true> : k_pwr<KSv, false, true>)                                        \
-                      : (ups ? k_pwr<KSv, true> : k_pwr<KSv, false>);                                                   \
-        if (h->lds_attr_done.insert((const void *)kfn).second)                                                          \
-            SVC_HIP(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));    \
-        kfn<<<g, 256, lds, s>>>(PWR_ARGS);                                                                              \
-    }
+#define PWR_KFN(KSv, UPSv) (mx ? k_pwr<KSv, UPSv, true> : k_pwr<KSv, UPSv>)
+        decltype(&k_pwr<8, false>) kfn = nullptr;
         switch (K) {
-            case 64: PWR_CASE(8) break;
-            case 96: PWR_CASE(12) break;
-            case 128: PWR_CASE(16) break;
-            default: PWR_CASE(20) break;
+            case 64: kfn = ups ? PWR_KFN(8, true) : PWR_KFN(8, false); break;
+            case 96: if (!ups) kfn = PWR_KFN(12, false); break;
+            case 128: kfn = ups ? PWR_KFN(16, true) : PWR_KFN(16, false); break;
+            default: if (!ups) kfn = PWR_KFN(20, false); break;
         }
-#undef PWR_CASE
-#undef PWR_ARGS
+#undef PWR_KFN
+        if (!kfn) {
+            svc_set_error("no k_pwr instance for K = %d with an up-sampled term", K);
+            return SVC_E_INVALID;
+        }
+        if (h->lds_attr_done.insert((const void *)kfn).second)
+            SVC_HIP(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        kfn<<<g, 256, lds, s>>>(X, ldx, Wk, ldw, bias, Y, ldy, M, N, Npad, ntw, relu6v, ua);
         SVC_CHECK_LAUNCH();
         return SVC_OK;
     }
-    if (!ups && h->pw_sk && K >= 256 && rb_nom * tiles <= h->pw_sk_max) {   // long K, few workgroups: split K over the four waves
+    // long K, few workgroups: split K over the four waves (k_pw_sk).  The layers that come here: features.18 and the first
+    // decoder expansion's low-resolution half on both pipes; on the fp32 pipe also post_cnn's and blocks 15-17's projections
+    // (unfused there: see dwpw_min_px), where 160 outputs give an odd number of column tiles
+    if (!ups && K >= 256 && rb_nom * tiles <= PW_SK_MAX_WG) {
         const int tn = (tiles % 2 == 0) ? 2 : 1;
         dim3 g(ceil_div(M, 32), ceil_div(tiles, tn));
-        if (h->mx && (h->mx_mask & 8) && (K & 15) == 0) {
+        if (h->mx && (K & 15) == 0) {
+            if (tn != 2) {
+                svc_set_error("no split-bf16 k_pw_sk instance for %d column tiles", tiles);
+                return SVC_E_INVALID;
+            }
             const uint4 *W3 = nullptr;
             int rc = x3_weights(h, s, Wt, ldw, K, Npad, X3_LANES, &W3);
             if (rc) return rc;
-            if (tn == 2) k_pw_sk<2, true, true><<<g, 256, 0, s>>>(X, ldx, (const float *)W3, tiles, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
-            else k_pw_sk<1, true, true><<<g, 256, 0, s>>>(X, ldx, (const float *)W3, tiles, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
+            k_pw_sk<2, true, true><<<g, 256, 0, s>>>(X, ldx, (const float *)W3, tiles, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
         } else if (h->sk_lane && (K & 7) == 0) {
             const float *Wl = nullptr;
             int rc = lane_weights(h, s, Wt, ldw, K, Npad, &Wl);
             if (rc) return rc;
             if (tn == 2) k_pw_sk<2, true><<<g, 256, 0, s>>>(X, ldx, Wl, tiles, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
             else k_pw_sk<1, true><<<g, 256, 0, s>>>(X, ldx, Wl, tiles, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
-        } else if (tn == 2) k_pw_sk<2><<<g, 256, 0, s>>>(PW16_ARGS);
-        else k_pw_sk<1><<<g, 256, 0, s>>>(PW16_ARGS);
+        } else if (tn == 2) k_pw_sk<2><<<g, 256, 0, s>>>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
+        else k_pw_sk<1><<<g, 256, 0, s>>>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
         SVC_CHECK_LAUNCH();
         return SVC_OK;
     }
-    // small-M layers (8x13 and 16x26 levels at B = 32) leave most SIMDs idle with 32x32 wave tiles:
-    // 16x32 wave tiles (SVC_PW_SMALL selects the shape) give 2-4x more waves
-    if (!ups && h->pw_small && K % 16 == 0 && K >= 64 && rb_nom * tiles < 1024) {
-        if (h->pw_small == 1) {
-            k_pw16<1, 2><<<dim3(ceil_div(M, 64), tiles), 256, 0, s>>>(PW16_ARGS);
-        } else if (h->pw_small == 2) {
-            k_pw16<1, 4><<<dim3(ceil_div(M, 64), ceil_div(tiles, 2)), 256, 0, s>>>(PW16_ARGS);
-        } else {
-            k_pw16<2, 2><<<dim3(ceil_div(M, 128), tiles), 256, 0, s>>>(PW16_ARGS);
-        }
-        SVC_CHECK_LAUNCH();
-        return SVC_OK;
-    }
-    // measured on MI355X: the 16x16x4 form wins for single-N-tile layers with a short K (the
-    // high-resolution project layers), the 32x32x2 form everywhere else
-    if (!ups && h->pw16 && tiles == 1 && K % 16 == 0 && K >= 64 && K <= 192) {
-        k_pw16<2, 2><<<dim3(rb, 1), 256, 0, s>>>(PW16_ARGS);
-        SVC_CHECK_LAUNCH();
-        return SVC_OK;
-    }
-#undef PW16_ARGS
-#define PW_ARGS X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v, ua
-    if (h->pw_tr == 1 || (h->pw_tr == 2 && (TN >= 2 || ups))) {
-        switch (TN) {
-            case 4: k_pw<4, 1, true><<<grid, 256, 0, s>>>(PW_ARGS); break;
-            case 3: k_pw<3, 1, true><<<grid, 256, 0, s>>>(PW_ARGS); break;
-            case 2: k_pw<2, 1, true><<<grid, 256, 0, s>>>(PW_ARGS); break;
-            default: k_pw<1, 1, true><<<grid, 256, 0, s>>>(PW_ARGS); break;
-        }
-    } else {
-        switch (TN) {
-            case 4: k_pw<4, 1><<<grid, 256, 0, s>>>(PW_ARGS); break;
-            case 3: k_pw<3, 1><<<grid, 256, 0, s>>>(PW_ARGS); break;
-            case 2: k_pw<2, 1><<<grid, 256, 0, s>>>(PW_ARGS); break;
-            default: k_pw<1, 1><<<grid, 256, 0, s>>>(PW_ARGS); break;
-        }
-    }
-#undef PW_ARGS
-    SVC_CHECK_LAUNCH();
-    return SVC_OK;
+    svc_set_error("no pointwise kernel for K = %d, N = %d%s", K, N, R ? " with a residual" : ups ? " with an up-sampled term" : "");
+    return SVC_E_INVALID;
 }
 
 static int launch_pw(SvcHandle *h, hipStream_t s, const float *X, int ldx, const SvcLayer &L, const float *R, int ldr,
@@ -2255,33 +1873,13 @@ static int launch_pw(SvcHandle *h, hipStream_t s, const float *X, int ldx, const
     return launch_pw_ex(h, s, X, ldx, L.w.dev, L.cin, L.cin, L.b.dev, L.relu6, L.cout, R, ldr, Y, ldy, M, n, nullptr);
 }
 
-static int launch_dw(SvcHandle *h, hipStream_t s, const float *X, const SvcLayer &L, float *Y, int n, int H, int W,
-                     int stride) {
-    if (h->seg_off >> h->seg_cur & 1u) return SVC_OK;
+// stride-1 depthwise layer on k_dw_tile's 4 x 2 output tiles
+static int launch_dw(SvcHandle *h, hipStream_t s, const float *X, const SvcLayer &L, float *Y, int n, int H, int W) {
     ProfScope ps(h, SVC_K_DW, s);
-    const int C = L.cout, OH = stride == 2 ? H / 2 : H, OW = stride == 2 ? W / 2 : W;
-    size_t total = (size_t)n * OH * OW * (C / 4);
-    if (stride == 2)
-        k_dw<2><<<blocks256(total), 256, 0, s>>>(X, L.w.dev, L.b.dev, Y, n, H, W, C, OH, OW, make_fdiv(C / 4), make_fdiv(OW),
-                                                 make_fdiv(OH));
-    else if (h->dw_tile) {
-        const int tx = h->dw_tile / 10, ty = h->dw_tile % 10;
-        const int GX = (W + tx - 1) / tx, GY = (H + ty - 1) / ty;
-        const size_t cells = (size_t)n * GY * GX * (C / 4);
-#define DW_TILE(TXv, TYv)                                                                                             \
-    k_dw_tile<TXv, TYv><<<blocks256(cells), 256, 0, s>>>(X, L.w.dev, L.b.dev, Y, n, H, W, C, make_fdiv(C / 4),        \
-                                                         make_fdiv(GX), make_fdiv(GY), (uint32_t)cells)
-        switch (h->dw_tile) {
-            case 21: DW_TILE(2, 1); break;
-            case 22: DW_TILE(2, 2); break;
-            case 41: DW_TILE(4, 1); break;
-            case 44: DW_TILE(4, 4); break;
-            default: DW_TILE(4, 2); break;
-        }
-#undef DW_TILE
-    } else
-        k_dw<1><<<blocks256(total), 256, 0, s>>>(X, L.w.dev, L.b.dev, Y, n, H, W, C, OH, OW, make_fdiv(C / 4), make_fdiv(OW),
-                                                 make_fdiv(OH));
+    const int C = L.cout, GX = (W + 3) / 4, GY = (H + 1) / 2;
+    const size_t cells = (size_t)n * GY * GX * (C / 4);
+    k_dw_tile<4, 2><<<blocks256(cells), 256, 0, s>>>(X, L.w.dev, L.b.dev, Y, n, H, W, C, make_fdiv(C / 4), make_fdiv(GX),
+                                                     make_fdiv(GY), (uint32_t)cells);
     SVC_CHECK_LAUNCH();
     return SVC_OK;
 }
@@ -2682,20 +2280,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
     }
 }
 
-// the pair qualifies: K1 = 64 or 160, intermediate channels a multiple of 32, 64 or 128 outputs, ReLU6 between, none after
-static bool pwpw_takes(const SvcHandle *h, const SvcLayer &L1, const SvcLayer &L2) {
-    return h->pwpw && (L1.cin == 64 || L1.cin == 160) && (L1.cout % 32) == 0 && L2.cin == L1.cout && (L2.cout == 64 || L2.cout == 128) &&
-           L1.relu6 && !L2.relu6;
-}
-
+// The two skip branches (model.py:443-444): 64 -> 128 -> 64 channels (features.7) and 160 -> 320 -> 128 (features.14),
+// ReLU6 between, none after.
 static int launch_pwpw(SvcHandle *h, hipStream_t s, const float *X, int ldx, const SvcLayer &L1, const SvcLayer &L2, float *Y, int ldy,
                        int M) {
-    if (h->seg_off >> h->seg_cur & 1u) return SVC_OK;
     ProfScope ps(h, SVC_K_PW, s);
+    const bool k8 = L1.cin == 64 && L2.cout == 64, k20 = L1.cin == 160 && L2.cout == 128;
+    if (!(k8 || k20) || (L1.cout % 32) != 0 || L2.cin != L1.cout || !L1.relu6 || L2.relu6) {
+        svc_set_error("no k_pwpw instance for a %d -> %d -> %d skip branch", L1.cin, L1.cout, L2.cout);
+        return SVC_E_INVALID;
+    }
     const dim3 grid((unsigned)ceil_div(M, 32));
     const float *W1 = L1.w.dev, *W2 = L2.w.dev;
     int lw = 0;
-    const bool mx = h->mx && (h->mx_mask & 16);
+    const bool mx = h->mx != 0;
     if (mx) {
         const uint4 *a = nullptr, *b = nullptr;
         int rc = x3_weights(h, s, L1.w.dev, L1.cin, L1.cin, L1.cout, X3_ROWS, &a);
@@ -2710,40 +2308,34 @@ static int launch_pwpw(SvcHandle *h, hipStream_t s, const float *X, int ldx, con
         if (rc) return rc;
         lw = 1;
     }
-#define PWPW_ARGS X, ldx, W1, L1.b.dev, L1.cout, W2, L2.b.dev, Y, ldy, M, lw
-    if (mx) {
-        if (L1.cin == 64) {
-            if (L2.cout == 64) k_pwpw<8, 2, true><<<grid, 256, 0, s>>>(PWPW_ARGS);
-            else k_pwpw<8, 4, true><<<grid, 256, 0, s>>>(PWPW_ARGS);
-        } else {
-            if (L2.cout == 64) k_pwpw<20, 2, true><<<grid, 256, 0, s>>>(PWPW_ARGS);
-            else k_pwpw<20, 4, true><<<grid, 256, 0, s>>>(PWPW_ARGS);
-        }
-    } else if (L1.cin == 64) {
-        if (L2.cout == 64) k_pwpw<8, 2><<<grid, 256, 0, s>>>(PWPW_ARGS);
-        else k_pwpw<8, 4><<<grid, 256, 0, s>>>(PWPW_ARGS);
-    } else {
-        if (L2.cout == 64) k_pwpw<20, 2><<<grid, 256, 0, s>>>(PWPW_ARGS);
-        else k_pwpw<20, 4><<<grid, 256, 0, s>>>(PWPW_ARGS);
-    }
-#undef PWPW_ARGS
+    const auto kfn = k8 ? (mx ? k_pwpw<8, 2, true> : k_pwpw<8, 2>) : (mx ? k_pwpw<20, 4, true> : k_pwpw<20, 4>);
+    kfn<<<grid, 256, 0, s>>>(X, ldx, W1, L1.b.dev, L1.cout, W2, L2.b.dev, Y, ldy, M, lw);
     SVC_CHECK_LAUNCH();
     return SVC_OK;
 }
 
+// k_dwpw: output-channel tiles (32 columns each) per workgroup at most; fewer = more workgroups, the depthwise part redone
+// per group
+#define DWPW_MAX_NT 5
+
+// A depthwise + project pair is fused (launch_dwpw) on the levels of at least this many pixels per frame, and runs as
+// launch_dw + launch_pw below.  Split-bf16 pipe: 100, so the fused kernel serves every level, the lowest (8x13 to 12x9
+// cells: 100 - 120 px) included -- there it wins by 18 us per shared pass.  fp32 pipe: 400, its optimum, which leaves
+// post_cnn and blocks 15-17 unfused.
+static int dwpw_min_px(const SvcHandle *h) { return h->mx ? 100 : 400; }
+
 static int launch_dwpw(SvcHandle *h, hipStream_t s, const float *X, const SvcLayer &Ld, const SvcLayer &Lp, const float *R,
                        int ldr, float *Y, int ldy, int n, int H, int W) {
-    if (h->seg_off >> h->seg_cur & 1u) return SVC_OK;
     ProfScope ps(h, SVC_K_PW, s);
     const int C = Ld.cout, N = Lp.cout, Npad = (N + 31) / 32 * 32, tiles = Npad / 32;
-    // output-channel groups of at most 5 tiles, as even as possible (the depthwise part is redone per group)
-    const int groups = ceil_div(tiles, std::min(5, std::max(1, h->dwpw_max_nt))), nt = ceil_div(tiles, groups);
+    // output-channel groups of at most DWPW_MAX_NT tiles, as even as possible (the depthwise part is redone per group)
+    const int groups = ceil_div(tiles, DWPW_MAX_NT), nt = ceil_div(tiles, groups);
     const int pw = (W % 8 == 0 || W > 16) ? 8 : 16;          // 8x4 patches; 16x2 on the narrow 13-wide level
     const int tx = ceil_div(W, pw), ty = ceil_div(H, 32 / pw);
     dim3 grid((unsigned)(n * tx * ty), groups);
     const float *Wpl = Lp.w.dev;                             // the project weights: lane-order copy where the knob allows
     int lw_tiles = 0;
-    const bool mx = h->mx && (h->mx_mask & 4) && (C & 15) == 0;
+    const bool mx = h->mx && (C & 15) == 0;
     if (mx) {
         const uint4 *W3 = nullptr;
         int rc = x3_weights(h, s, Lp.w.dev, C, C, Npad, X3_LANES, &W3);
@@ -2755,21 +2347,23 @@ static int launch_dwpw(SvcHandle *h, hipStream_t s, const float *X, const SvcLay
         if (rc) return rc;
         lw_tiles = tiles;
     }
-#define DWPW_ARGS X, H, W, C, Ld.w.dev, Ld.b.dev, Wpl, Lp.b.dev, N, Npad, R, ldr, Y, ldy, Lp.relu6, tx, ty, lw_tiles
-#define DWPW_CASE(NTv)                                                                    \
-    case NTv:                                                                             \
-        if (mx) {                                                                         \
-            if (pw == 8) k_dwpw<NTv, 8, 4, true><<<grid, 256, 0, s>>>(DWPW_ARGS);         \
-            else k_dwpw<NTv, 16, 4, true><<<grid, 256, 0, s>>>(DWPW_ARGS);                \
-        } else if (pw == 8) k_dwpw<NTv, 8, 4><<<grid, 256, 0, s>>>(DWPW_ARGS);            \
-        else k_dwpw<NTv, 16, 4><<<grid, 256, 0, s>>>(DWPW_ARGS);                          \
-        break
-    switch (nt) {
-        DWPW_CASE(1); DWPW_CASE(2); DWPW_CASE(3); DWPW_CASE(4);
-        default: DWPW_CASE(5);
+    // The layers' shapes give nt = 2 .. 5.  Every level but the lowest is at least 16 columns wide (8-wide patches); the lowest
+    // level is fused on the split-bf16 pipe only, by layers of 4 and 5 tiles.
+    decltype(&k_dwpw<2, 8, 4>) kfn = nullptr;
+    if (pw == 8) {
+        switch (nt) {
+            case 2: kfn = mx ? k_dwpw<2, 8, 4, true> : k_dwpw<2, 8, 4>; break;
+            case 3: kfn = mx ? k_dwpw<3, 8, 4, true> : k_dwpw<3, 8, 4>; break;
+            case 4: kfn = mx ? k_dwpw<4, 8, 4, true> : k_dwpw<4, 8, 4>; break;
+            case 5: kfn = mx ? k_dwpw<5, 8, 4, true> : k_dwpw<5, 8, 4>; break;
+        }
+    } else if (mx && nt == 4) kfn = k_dwpw<4, 16, 4, true>;
+    else if (mx && nt == 5) kfn = k_dwpw<5, 16, 4, true>;
+    if (!kfn) {
+        svc_set_error("no k_dwpw instance for %d column tiles on a %d-wide level (%s pipe)", tiles, W, mx ? "split-bf16" : "fp32");
+        return SVC_E_INVALID;
     }
-#undef DWPW_CASE
-#undef DWPW_ARGS
+    kfn<<<grid, 256, 0, s>>>(X, H, W, C, Ld.w.dev, Ld.b.dev, Wpl, Lp.b.dev, N, Npad, R, ldr, Y, ldy, Lp.relu6, tx, ty, lw_tiles);
     SVC_CHECK_LAUNCH();
     return SVC_OK;
 }
@@ -2782,8 +2376,8 @@ static int launch_dwpw(SvcHandle *h, hipStream_t s, const float *X, const SvcLay
 //   E  = relu6(Xs . We^T + be)   for the (TOH-1)S+3 x (TOW-1)S+3 input halo   (f32 MFMA, A and B from LDS)
 //   D  = relu6(dw3x3(E) + bd)                                                 (VALU, float4 over channels)
 //   acc += D . Wp^T                                                           (f32 MFMA, A and B from LDS)
-// with the same k order and tap order as k_pw / k_dw, so results are bit-identical to the
-// un-fused kernels.  Out-of-image halo pixels hold E = 0 (the depthwise conv pads E, not X).
+// with the same k order and tap order as the un-fused kernels (k_pwr, k_dw_tile), so results are bit-identical to
+// theirs.  Out-of-image halo pixels hold E = 0 (the depthwise conv pads E, not X).
 // EXPAND = false is the t=1 block (features.1): E is the input itself.
 //
 // Weights: the three weight slices of a chunk are a few KB.  They are fetched from global memory (L2)
@@ -3220,12 +2814,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IRB_MX3(S, 
 
 static int launch_irb(SvcHandle *h, hipStream_t s, const float *X, int n, int H, int W, int Cin, const SvcLayer *Le,
                       const SvcLayer &Ld, const SvcLayer &Lp, int stride, const float *R, float *Y) {
-    if (h->seg_off >> h->seg_cur & 1u) return SVC_OK;
     ProfScope ps(h, SVC_K_PW, s);
     const int Ce = Ld.cout, Cout = Lp.cout, CoutP = (Cout + 31) / 32 * 32;
     const int OH = H / stride, OW = W / stride;
-    // split-bf16 form (h->mx; the fixed-shape expanding instances; h->irb_mx: one bit per instance, in the order below): We and Wp
-    // as X3_ROWS copies
+    // split-bf16 form of an expanding block (IRB_LAUNCH_MX on the split-bf16 pipe): We and Wp as X3_ROWS copies
     const float *We_ = Le ? Le->w.dev : nullptr, *Wp_ = Lp.w.dev;
     auto mx_weights = [&]() -> int {
         const uint4 *a = nullptr, *b = nullptr;
@@ -3237,16 +2829,15 @@ static int launch_irb(SvcHandle *h, hipStream_t s, const float *X, int n, int H,
         }
         return rc;
     };
-#define IRB_LAUNCH(S_, TOH_, TOW_, EXP_) IRB_LAUNCH4(S_, TOH_, TOW_, EXP_, 0, 0, 0, false)
-#define IRB_LAUNCH3(S_, TOH_, TOW_, EXP_, CI_, CE_, CO_, BIT_)                                                       \
+#define IRB_LAUNCH_MX(S_, TOH_, TOW_, CI_, CE_, CO_)                                                                 \
     do {                                                                                                             \
-        if (h->mx && (h->mx_mask & 2) && (h->irb_mx >> (BIT_) & 1)) {                                                                   \
+        if (h->mx) {                                                                                                 \
             int rc = mx_weights();                                                                                   \
             if (rc) return rc;                                                                                       \
-            IRB_LAUNCH4(S_, TOH_, TOW_, EXP_, CI_, CE_, CO_, true);                                                  \
-        } else IRB_LAUNCH4(S_, TOH_, TOW_, EXP_, CI_, CE_, CO_, false);                                              \
+            IRB_LAUNCH(S_, TOH_, TOW_, true, CI_, CE_, CO_, true);                                                   \
+        } else IRB_LAUNCH(S_, TOH_, TOW_, true, CI_, CE_, CO_, false);                                               \
     } while (0)
-#define IRB_LAUNCH4(S_, TOH_, TOW_, EXP_, CI_, CE_, CO_, MX_)                                                        \
+#define IRB_LAUNCH(S_, TOH_, TOW_, EXP_, CI_, CE_, CO_, MX_)                                                         \
     do {                                                                                                             \
         const int tx = ceil_div(OW, TOW_), ty = ceil_div(OH, TOH_);                                                  \
         const size_t lds = IrbGeom<S_, TOH_, TOW_>::lds_floats(Cin, CoutP, EXP_, Ce, IRB_XREG && EXP_ && (CI_) > 0 && (CI_) <= 32 && ((CI_) % 8) == 0, MX_) * 4; \
@@ -3259,19 +2850,24 @@ static int launch_irb(SvcHandle *h, hipStream_t s, const float *X, int n, int H,
             X, H, W, Cin, EXP_ ? We_ : nullptr, EXP_ ? Le->b.dev : nullptr, Ce, Ld.w.dev, Ld.b.dev, Wp_,              \
             Lp.b.dev, Cout, CoutP, R, Y, Cout, OH, OW, tx, ty);                                                       \
     } while (0)
-    const bool fixed = h->irb_fixed;
-    if (!Le && fixed && Cin == 32 && Ce == 32 && Cout == 16) IRB_LAUNCH4(1, 8, 8, false, 32, 32, 16, false);
-    else if (!Le) IRB_LAUNCH(1, 8, 8, false);
-    else if (stride == 2 && fixed && Cin == 16 && Ce == 96 && Cout == 24) IRB_LAUNCH3(2, 4, 8, true, 16, 96, 24, 0);
-    else if (stride == 2 && fixed && Cin == 24 && Ce == 144 && Cout == 32) IRB_LAUNCH3(2, 4, 8, true, 24, 144, 32, 2);
-    else if (stride == 2) IRB_LAUNCH(2, 4, 8, true);
-    else if (fixed && Cin == 24 && Ce == 144 && Cout == 24) IRB_LAUNCH3(1, 8, 8, true, 24, 144, 24, 1);
-    else if (fixed && Cin == 32 && Ce == 192 && Cout == 32) IRB_LAUNCH3(1, 8, 8, true, 32, 192, 32, 3);
-    else if (fixed && Cin == 32 && Ce == 192 && Cout == 64) IRB_LAUNCH3(1, 8, 8, true, 32, 192, 64, 4);
-    else IRB_LAUNCH(1, 8, 8, true);
+    // One compile-time-shaped instance per block shape.  The expand GEMM takes the split-bf16 form where it is faster than the
+    // fp32 form.  Measured per instance, us per pass alone / shared: blocks 2, 3, 5-6, 7: -17 / -11, -12 / -7, -11 / -4,
+    // -10 / -6; block 4: +11 / +11 (Cin = 24 pads its second step, two halo tiles per wave: 36 spilled registers), so it stays fp32.
+    if (!Le && Cin == 32 && Ce == 32 && Cout == 16) IRB_LAUNCH(1, 8, 8, false, 32, 32, 16, false);             // block 1
+    else if (!Le) {
+        svc_set_error("no k_irb instance for a %d -> %d -> %d block without expansion", Cin, Ce, Cout);
+        return SVC_E_INVALID;
+    } else if (stride == 2 && Cin == 16 && Ce == 96 && Cout == 24) IRB_LAUNCH_MX(2, 4, 8, 16, 96, 24);          // block 2
+    else if (stride == 2 && Cin == 24 && Ce == 144 && Cout == 32) IRB_LAUNCH(2, 4, 8, true, 24, 144, 32, false); // block 4
+    else if (stride == 1 && Cin == 24 && Ce == 144 && Cout == 24) IRB_LAUNCH_MX(1, 8, 8, 24, 144, 24);          // block 3
+    else if (stride == 1 && Cin == 32 && Ce == 192 && Cout == 32) IRB_LAUNCH_MX(1, 8, 8, 32, 192, 32);          // blocks 5-6
+    else if (stride == 1 && Cin == 32 && Ce == 192 && Cout == 64) IRB_LAUNCH_MX(1, 8, 8, 32, 192, 64);          // block 7
+    else {
+        svc_set_error("no k_irb instance for a stride-%d %d -> %d -> %d block", stride, Cin, Ce, Cout);
+        return SVC_E_INVALID;
+    }
+#undef IRB_LAUNCH_MX
 #undef IRB_LAUNCH
-#undef IRB_LAUNCH3
-#undef IRB_LAUNCH4
     SVC_CHECK_LAUNCH();
     return SVC_OK;
 }
@@ -3288,23 +2884,21 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
     float *IN = p->buf(B_IN), *P[2] = {p->buf(B_P0), p->buf(B_P1)}, *E0 = p->buf(B_E0), *E1 = p->buf(B_E1);
     // the front of the network (LANCZOS, features.0, features.1) as one kernel where a tile's resampling arrays fit in LDS
     const int fr_lds = front_lds_bytes();
-    const bool front = h->front && h->fuse_max >= 1 && p->fr_ok;
+    const bool front = h->front && p->fr_ok;
     p->last_front = front;
-    h->seg_cur = 0;
-    auto seg_on = [&]() { return !(h->seg_off >> h->seg_cur & 1u); };   // SVC_SEG_OFF (measurement aid): see svc_internal.h
     // K0
-    if (!front && seg_on()) {
+    if (!front) {
         ProfScope ps(h, SVC_K_LANCZOS, s);
-        dim3 grid(ceil_div(NH, p->lz_rows), n);
+        dim3 grid(ceil_div(NH, LZ_ROWS), n);
         size_t lds = ((size_t)p->lz_tile_cap * p->w * 3 + 15) / 16 * 16 + ((size_t)p->lz_tile_cap * NW * 3 + 15) / 16 * 16 +
                      (size_t)NW * p->hks * 4 + 768 * 4;
         k_lanczos_norm<<<grid, 256, lds, s>>>(frames, IN, p->h, p->w, NH, NW, (const int *)p->hb.p, (const int *)p->hk.p,
                                              p->hks, (const int *)p->vb.p, (const int *)p->vk.p, p->vks,
-                                             (const float *)p->lut.p, p->lz_rows, p->lz_tile_cap);
+                                             (const float *)p->lut.p, LZ_ROWS, p->lz_tile_cap);
         SVC_CHECK_LAUNCH();
     }
     const SvcLayer &Lstem = next();
-    if (!front && seg_on()) {
+    if (!front) {
         ProfScope ps(h, SVC_K_STEM, s);
         const int tx = ceil_div(W, STEM_TW), ty = ceil_div(H, STEM_TH);
         k_stem_mfma<<<dim3((unsigned)(n * tx * ty)), 256, 0, s>>>(IN, (const float *)h->stem_wt.p, Lstem.b.dev, P[0], NH, NW,
@@ -3321,12 +2915,11 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
             const int oup = Cc[st], stride = (i == 0) ? Ss[st] : 1, t = T[st];
             const bool res = (stride == 1 && inp == oup);
             const bool tap = (idx == 7 || idx == 14);             // full-resolution output feeds a skip
-            h->seg_cur = idx <= 1 ? 0 : idx <= 3 ? 1 : idx <= 7 ? 2 : idx <= 14 ? 3 : 4;
             const int dws = (stride == 2 && !tap) ? 2 : 1;        // stride-2 dw == stride-1 dw + ::2 sub-sampling
             const float *x = P[cur];
             int OH = H / dws, OW = W / dws;
             float *y = tap ? p->buf(idx == 7 ? B_F4X : B_F2X) : P[cur ^ 1];
-            // the first fuse_max blocks (of 1..13: Cin <= 96, Cout <= 128) run as one fused kernel; the rest un-fused
+            // blocks 1-7 run as one fused kernel each; the rest un-fused
             if (front && idx == 1) {
                 ProfScope ps(h, SVC_K_STEM, s);
                 const SvcLayer &Ld = next();
@@ -3346,9 +2939,9 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
                     A.row_lo[i] = p->fr_row_lo[i]; A.row_n[i] = p->fr_row_n[i];
                     A.col_lo[i] = p->fr_col_lo[i]; A.col_n[i] = p->fr_col_n[i];
                 }
-                if (seg_on()) k_front<<<dim3((unsigned)(n * A.tiles_x * A.tiles_y)), 256, fr_lds, s>>>(A);
+                k_front<<<dim3((unsigned)(n * A.tiles_x * A.tiles_y)), 256, fr_lds, s>>>(A);
                 SVC_CHECK_LAUNCH();
-            } else if (idx <= h->fuse_max && (t != 1 || inp == 32)) {
+            } else if (idx <= 7) {
                 const SvcLayer *Le = (t != 1) ? &next() : nullptr;
                 const SvcLayer &Ld = next();
                 const SvcLayer &Lp = next();
@@ -3360,17 +2953,17 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
                     dwin = E0;
                 }
                 const SvcLayer &Ld = next();
-                if (h->dwpw && dws == 1 && H * W >= h->dwpw_min_px) {
+                if (H * W >= dwpw_min_px(h)) {
                     const SvcLayer &Lp = next();
                     RC(launch_dwpw(h, s, dwin, Ld, Lp, res ? x : nullptr, oup, y, oup, n, H, W));
                 } else {
-                    RC(launch_dw(h, s, dwin, Ld, E1, n, H, W, dws));
+                    RC(launch_dw(h, s, dwin, Ld, E1, n, H, W));
                     RC(launch_pw(h, s, E1, inp * t, next(), res ? x : nullptr, oup, y, oup, n * OH * OW, n));
                 }
             }
             if (tap) {
                 ProfScope ps(h, SVC_K_RESAMPLE, s);
-                if (seg_on()) k_subsample<<<blocks256((size_t)n * (OH / 2) * (OW / 2) * (oup / 4)), 256, 0, s>>>(y, P[cur ^ 1], n, OH,
+                k_subsample<<<blocks256((size_t)n * (OH / 2) * (OW / 2) * (oup / 4)), 256, 0, s>>>(y, P[cur ^ 1], n, OH,
                                                                                                   OW, oup);
                 SVC_CHECK_LAUNCH();
                 OH /= 2; OW /= 2;
@@ -3382,25 +2975,16 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
     // features.18 -> CAT1[:, 0:1280], Gaussian maps -> CAT1[:, 1280:1296]
     const int H5 = H, W5 = W, H4 = 2 * H5, W4 = 2 * W5, H3 = 4 * H5, W3 = 4 * W5;
     float *CAT1 = p->buf(B_CAT1);
-    h->seg_cur = 5;
     RC(launch_pw(h, s, P[cur], 320, next(), nullptr, 0, CAT1, 1296, n * H5 * W5, n));
     // skips (model.py:443-444)
     float *CAT2 = p->buf(B_CAT2), *CAT3 = p->buf(B_CAT3);
     {
         const SvcLayer &Le2 = next();
         const SvcLayer &Lr2 = next();
-        if (pwpw_takes(h, Le2, Lr2)) RC(launch_pwpw(h, s, p->buf(B_F2X), 160, Le2, Lr2, CAT2 + 256, 384, n * H4 * W4));
-        else {
-            RC(launch_pw(h, s, p->buf(B_F2X), 160, Le2, nullptr, 0, p->buf(B_S2E), 320, n * H4 * W4, n));
-            RC(launch_pw(h, s, p->buf(B_S2E), 320, Lr2, nullptr, 0, CAT2 + 256, 384, n * H4 * W4, n));
-        }
+        RC(launch_pwpw(h, s, p->buf(B_F2X), 160, Le2, Lr2, CAT2 + 256, 384, n * H4 * W4));
         const SvcLayer &Le4 = next();
         const SvcLayer &Lr4 = next();
-        if (pwpw_takes(h, Le4, Lr4)) RC(launch_pwpw(h, s, p->buf(B_F4X), 64, Le4, Lr4, CAT3 + 128, 192, n * H3 * W3));
-        else {
-            RC(launch_pw(h, s, p->buf(B_F4X), 64, Le4, nullptr, 0, p->buf(B_S4E), 128, n * H3 * W3, n));
-            RC(launch_pw(h, s, p->buf(B_S4E), 128, Lr4, nullptr, 0, CAT3 + 128, 192, n * H3 * W3, n));
-        }
+        RC(launch_pwpw(h, s, p->buf(B_F4X), 64, Le4, Lr4, CAT3 + 128, 192, n * H3 * W3));
     }
     next();   // GAUSS placeholder layer (raw parameters; maps live in plan->gauss)
     if (p->gauss_filled < n) {       // the prior maps are constants: nothing else writes channels 1280..1295 of CAT1
@@ -3411,90 +2995,55 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
         p->gauss_filled = n;
     }
     // post_cnn
-    if (h->dwpw && H5 * W5 >= h->dwpw_min_px) {
+    if (H5 * W5 >= dwpw_min_px(h)) {
         const SvcLayer &Ld = next();
         RC(launch_dwpw(h, s, CAT1, Ld, next(), nullptr, 0, p->buf(B_PC), 256, n, H5, W5));
     } else {
-        RC(launch_dw(h, s, CAT1, next(), p->buf(B_PCD), n, H5, W5, 1));
+        RC(launch_dw(h, s, CAT1, next(), p->buf(B_PCD), n, H5, W5));
         RC(launch_pw(h, s, p->buf(B_PCD), 1296, next(), nullptr, 0, p->buf(B_PC), 256, n * H5 * W5, n));
     }
-    // US1 + concat, US2 block
-    h->seg_cur = 6;
-    if (h->split_up) {
-        // expand(concat(up(PC), skip)) = relu6(up(W[:, :256] . PC) + W[:, 256:] . skip + b)
+    // US1 + concat, US2 block: expand(concat(up(PC), skip)) = relu6(up(W[:, :256] . PC) + W[:, 256:] . skip + b)
+    {
         const SvcLayer &Le = next();
         RC(launch_pw_ex(h, s, p->buf(B_PC), 256, Le.w.dev, 384, 256, nullptr, 0, 768, nullptr, 0, p->buf(B_T1), 768,
                         n * H5 * W5, n, nullptr));
         const UpsAdd ua{p->buf(B_T1), H5, W5, 768, make_fdiv(W4), make_fdiv(H4)};
         RC(launch_pw_ex(h, s, CAT2 + 256, 384, Le.w.dev + 256, 384, 128, Le.b.dev, Le.relu6, 768, nullptr, 0,
                         p->buf(B_U2E), 768, n * H4 * W4, n, &ua));
-    } else {
-        {
-            ProfScope ps(h, SVC_K_RESAMPLE, s);
-            if (seg_on()) k_upsample2x<<<blocks256((size_t)n * H4 * W4 * 64), 256, 0, s>>>(p->buf(B_PC), CAT2, n, H5, W5, 256, 384,
-                                                                             make_fdiv(64), make_fdiv(W4), make_fdiv(H4));
-            SVC_CHECK_LAUNCH();
-        }
-        RC(launch_pw(h, s, CAT2, 384, next(), nullptr, 0, p->buf(B_U2E), 768, n * H4 * W4, n));
-    }
-    if (h->dwpw) {
         const SvcLayer &Ld = next();
         RC(launch_dwpw(h, s, p->buf(B_U2E), Ld, next(), nullptr, 0, p->buf(B_U2), 128, n, H4, W4));
-    } else {
-        RC(launch_dw(h, s, p->buf(B_U2E), next(), p->buf(B_U2D), n, H4, W4, 1));
-        RC(launch_pw(h, s, p->buf(B_U2D), 768, next(), nullptr, 0, p->buf(B_U2), 128, n * H4 * W4, n));
     }
-    h->seg_cur = 7;
-    if (h->split_up) {
+    {
         const SvcLayer &Le = next();
         RC(launch_pw_ex(h, s, p->buf(B_U2), 128, Le.w.dev, 192, 128, nullptr, 0, 384, nullptr, 0, p->buf(B_T2), 384,
                         n * H4 * W4, n, nullptr));
         const UpsAdd ua{p->buf(B_T2), H4, W4, 384, make_fdiv(W3), make_fdiv(H3)};
         RC(launch_pw_ex(h, s, CAT3 + 128, 192, Le.w.dev + 128, 192, 64, Le.b.dev, Le.relu6, 384, nullptr, 0,
                         p->buf(B_P3E), 384, n * H3 * W3, n, &ua));
-    } else {
-        {
-            ProfScope ps(h, SVC_K_RESAMPLE, s);
-            if (seg_on()) k_upsample2x<<<blocks256((size_t)n * H3 * W3 * 32), 256, 0, s>>>(p->buf(B_U2), CAT3, n, H4, W4, 128, 192,
-                                                                             make_fdiv(32), make_fdiv(W3), make_fdiv(H3));
-            SVC_CHECK_LAUNCH();
-        }
-        RC(launch_pw(h, s, CAT3, 192, next(), nullptr, 0, p->buf(B_P3E), 384, n * H3 * W3, n));
-    }
-    if (h->dwpw) {
         const SvcLayer &Ld = next();
         RC(launch_dwpw(h, s, p->buf(B_P3E), Ld, next(), nullptr, 0, p->buf(B_DEC), 64, n, H3, W3));
-    } else {
-        RC(launch_dw(h, s, p->buf(B_P3E), next(), p->buf(B_P3D), n, H3, W3, 1));
-        RC(launch_pw(h, s, p->buf(B_P3D), 384, next(), nullptr, 0, p->buf(B_DEC), 64, n * H3 * W3, n));
     }
     // adaptation, smoothing, resize, quantise
-    h->seg_cur = 8;
     const SvcLayer &La = next();
     {
         ProfScope ps(h, SVC_K_RESAMPLE, s);
-        if (seg_on()) k_adapt<<<blocks256((size_t)n * H3 * W3), 256, 0, s>>>(p->buf(B_DEC), La.w.dev, La.b.dev, p->buf(B_LOGIT),
+        k_adapt<<<blocks256((size_t)n * H3 * W3), 256, 0, s>>>(p->buf(B_DEC), La.w.dev, La.b.dev, p->buf(B_LOGIT),
                                                               (size_t)n * H3 * W3, (unsigned *)p->fmax.p, n,
                                                               (unsigned long long *)h->census.p, h->chunk);
         SVC_CHECK_LAUNCH();
     }
-    // B_LOGIT per-frame stride may exceed H3*W3 (rounded to 4): compact layout is used instead
+    // B_LOGIT per-frame stride may exceed H3*W3 (rounded to 4): compact layout is used instead.  NH, NW = 8 H3, 8 W3 (the
+    // network input sizes are multiples of 32)
     const SvcLayer &Ls = next();
     ProfScope ps_smooth(h, SVC_K_SMOOTH, s);
     {
-        dim3 grid(ceil_div(p->h, p->sd_rows), n);
-        if (h->smooth_mfma && NW % 8 == 0 && NW == 8 * W3 && NH == 8 * H3) {
-            const size_t lds = ((size_t)H3 * W3 + 64 * SD_KP + (size_t)p->sd_tile_cap * NW) * sizeof(float);
-            if (seg_on()) k_smooth_down_mfma<<<grid, 256, lds, s>>>(p->buf(B_LOGIT), Ls.w.dev, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3,
-                                                      NH, NW, p->h, p->w, p->sd_rows, p->sd_tile_cap, make_fdiv(p->w));
-        } else {
-            size_t lds = ((size_t)H3 * W3 + 64 * 49 + (size_t)p->sd_tile_cap * NW) * sizeof(float);
-            if (seg_on()) k_smooth_down<<<grid, 256, lds, s>>>(p->buf(B_LOGIT), Ls.w.dev, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3, NH,
-                                                 NW, p->h, p->w, p->sd_rows, p->sd_tile_cap, make_fdiv(NW), make_fdiv(p->w));
-        }
+        dim3 grid(ceil_div(p->h, SD_ROWS), n);
+        const size_t lds = ((size_t)H3 * W3 + 64 * SD_KP + (size_t)p->sd_tile_cap * NW) * sizeof(float);
+        k_smooth_down_mfma<<<grid, 256, lds, s>>>(p->buf(B_LOGIT), Ls.w.dev, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3,
+                                                  NH, NW, p->h, p->w, SD_ROWS, p->sd_tile_cap, make_fdiv(p->w));
         SVC_CHECK_LAUNCH();
     }
-    if (seg_on()) k_quantise<<<blocks256((size_t)n * p->h * p->w), 256, 0, s>>>(p->buf(B_PRE), (const unsigned *)p->fmax.p, maps, n,
+    k_quantise<<<blocks256((size_t)n * p->h * p->w), 256, 0, s>>>(p->buf(B_PRE), (const unsigned *)p->fmax.p, maps, n,
                                                                  p->h * p->w, make_fdiv(p->h * p->w), thr,
                                                                  (unsigned long long *)h->census.p, census_rows);
     SVC_CHECK_LAUNCH();
@@ -3651,61 +3200,18 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
     h->device = device;
     const char *env = getenv("SVC_CHUNK");
     if (env && atoi(env) > 0) h->chunk = atoi(env);
-    env = getenv("SVC_PW_MIN_WG");
-    if (env && atoi(env) > 0) h->pw_min_wg = atoi(env);
-    env = getenv("SVC_PW_SK");
-    if (env) h->pw_sk = atoi(env) != 0;
-    env = getenv("SVC_PW_TR");
-    if (env) h->pw_tr = atoi(env);
-    env = getenv("SVC_PW_SK_MAX");
-    if (env && atoi(env) > 0) h->pw_sk_max = atoi(env);
-    env = getenv("SVC_PW_SMALL");
-    if (env) h->pw_small = atoi(env);
-    env = getenv("SVC_PW16");
-    if (env) h->pw16 = atoi(env) != 0;
-    env = getenv("SVC_PWR");
-    if (env) h->pwr = atoi(env) != 0;
-    env = getenv("SVC_PWR_NT");
-    if (env) h->pwr_nt = atoi(env);
-    env = getenv("SVC_PWR_MIN_WG");
-    if (env && atoi(env) > 0) h->pwr_min_wg = atoi(env);
-    env = getenv("SVC_FUSE_MAX");
-    if (env) h->fuse_max = std::min(13, std::max(0, atoi(env)));
-    env = getenv("SVC_SPLIT_UP");
-    if (env) h->split_up = atoi(env) != 0;
-    env = getenv("SVC_IRB_FIXED");
-    if (env) h->irb_fixed = atoi(env) != 0;
-    env = getenv("SVC_SMOOTH_MFMA");
-    if (env) h->smooth_mfma = atoi(env);
     env = getenv("SVC_FRONT");
     if (env) h->front = atoi(env) != 0;
     env = getenv("SVC_KEEP_INPUT");
     if (env) h->keep_input = atoi(env) != 0;
-    env = getenv("SVC_DWPW");
-    if (env) h->dwpw = atoi(env) != 0;
-    env = getenv("SVC_DWPW_MIN_PX");
-    if (env) h->dwpw_min_px = atoi(env);
     env = getenv("SVC_MX");
     if (env) {                                               // a typo must not silently select another pipe
         if (!strcmp(env, "bf16x6") || !strcmp(env, "6")) h->mx = 6;
         else if (!strcmp(env, "f32") || !strcmp(env, "0")) h->mx = 0;
         else { svc_set_error("svc_create: SVC_MX=%s (expected f32 or bf16x6)", env); delete h; return SVC_E_INVALID; }
     }
-    if (h->mx && !getenv("SVC_DWPW_MIN_PX")) h->dwpw_min_px = 100;
-    env = getenv("SVC_IRB_MX");
-    if (env) h->irb_mx = (unsigned)strtoul(env, nullptr, 0);
-    env = getenv("SVC_MX_MASK");
-    if (env) h->mx_mask = (unsigned)strtoul(env, nullptr, 0);
     env = getenv("SVC_SK_LANE");
     if (env) h->sk_lane = atoi(env) != 0;
-    env = getenv("SVC_PWPW");
-    if (env) h->pwpw = atoi(env) != 0;
-    env = getenv("SVC_SEG_OFF");
-    if (env) h->seg_off = (unsigned)strtoul(env, nullptr, 0);
-    env = getenv("SVC_DWPW_NT");
-    if (env) h->dwpw_max_nt = atoi(env);
-    env = getenv("SVC_DW_TILE");
-    if (env) h->dw_tile = atoi(env);
     env = getenv("SVC_SHOT_MX");
     if (env) {
         if (!strcmp(env, "bf16x6") || !strcmp(env, "6")) h->shot_mx = 6;

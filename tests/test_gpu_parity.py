@@ -141,30 +141,31 @@ def test_saliency_batch_and_chunk_independence(engine, shape):
 
 
 @pytest.mark.parametrize('knobs', [
-    {'SVC_FUSE_MAX': '0'},                                  # no fused inverted-residual blocks: k_pw / k_dw* / k_pw only
-    {'SVC_DWPW': '0'},                                      # depthwise and project as two kernels
-    {'SVC_DWPW': '0', 'SVC_DW_TILE': '0'},                  # ... with the one-output-per-thread depthwise
-    {'SVC_DWPW_MIN_PX': '1'},                               # fused depthwise+project on the 8x13 level too
-    {'SVC_PWR': '0'},                                       # short-K layers through k_pw (operands from global memory) instead of k_pwr
-    {'SVC_PWR_NT': '1'},                                    # k_pwr with one column tile per workgroup
-    {'SVC_PWR_NT': '4', 'SVC_PW_SK': '0'},                  # ... with four; long-K layers without split-K
-    {'SVC_PWR': '0', 'SVC_PW_SK': '0', 'SVC_PW16': '0'},    # no k_pwr, no split-K, no 16x16x4 pointwise form
-    {'SVC_PW_SMALL': '1'},                                  # 16x16x4 wave tiles for the small-M levels (three shapes)
-    {'SVC_PW_SMALL': '2'},
-    {'SVC_PW_SMALL': '3', 'SVC_PW_TR': '1'},               # ... and the float4 epilogue for every k_pw launch
-    {'SVC_PW_TR': '0'},                                     # pointwise kernel with a lane per channel (scalar epilogue)
-    {'SVC_FUSE_MAX': '13'},                                 # every block that can be fused is
-    {'SVC_SPLIT_UP': '0'},                                  # decoder: up-sample + concatenate + one GEMM (the reference's order)
-    {'SVC_IRB_FIXED': '0'},                                 # generic (run-time shaped) fused block instead of the fixed-shape instances
-    {'SVC_SMOOTH_MFMA': '0'},                               # the 41x41 smoothing as the FMA kernel (the fall-back for geometries whose maps are not 8 x the low-resolution grid)
+    {'SVC_MX': 'f32'},                                      # fp32 matrix pipe: k_pwr / k_irb / k_dwpw / k_pwpw / k_pw_sk in fp32 form, post_cnn and blocks 15-17 unfused
+    {'SVC_MX': 'f32', 'SVC_SK_LANE': '0'},                  # ... with the split-K layers reading the [N][K] weight matrix
+    {'SVC_MX': 'f32', 'SVC_FRONT': '0'},                    # ... with LANCZOS, features.0 and features.1 as three kernels
+    {'SVC_MX': 'f32', 'SVC_CHUNK': '5'},                    # ... in ragged chunks of the batch
+    {'SVC_MX': 'f32', 'SVC_KEEP_INPUT': '1'},               # ... with k_front also writing the network input
+    {'SVC_KEEP_INPUT': '1'},                                # k_front also writing the network input
+    {'SVC_FRONT': '0', 'SVC_SK_LANE': '0'},                 # three front kernels and [N][K] weight reads together
+    {'SVC_FRONT': '0', 'SVC_CHUNK': '5'},                   # three front kernels in ragged chunks
+    {'SVC_CHUNK': '1'},                                     # one frame per pass
+    {'SVC_CHUNK': '2'},
+    {'SVC_CHUNK': '3'},
+    {'SVC_CHUNK': '6'},                                     # a full chunk and a single-frame one
+    {'SVC_CHUNK': '7'},                                     # the batch as exactly one chunk
+    {'SVC_CHUNK': '4', 'SVC_SK_LANE': '0'},                 # ragged chunks with [N][K] weight reads
+    {'SVC_MX': 'f32', 'SVC_FRONT': '0', 'SVC_SK_LANE': '0'},    # fp32 pipe, three front kernels, [N][K] weight reads
+    {'SVC_MX': 'f32', 'SVC_CHUNK': '1'},                    # fp32 pipe, one frame per pass
     {'SVC_FRONT': '0'},                                     # LANCZOS, features.0 and features.1 as three kernels instead of k_front
     {'SVC_CHUNK': '5'},                                     # ragged chunks of the batch
     {'SVC_SK_LANE': '0'},                                   # split-K layers read the [N][K] weight matrix instead of its lane-order copy
-    {'SVC_PWPW': '0'},                                      # the skip branches' two 1x1 convolutions as two launches instead of k_pwpw
+    {'SVC_MX': 'f32', 'SVC_SK_LANE': '0', 'SVC_CHUNK': '5'},    # fp32 pipe, [N][K] weight reads, ragged chunks
+    {'SVC_MX': 'f32', 'SVC_FRONT': '0', 'SVC_CHUNK': '3'},  # fp32 pipe, three front kernels, ragged chunks
 ])
 def test_saliency_kernel_families_agree(engine, synthetic_sd, knobs):
-    """Every kernel family that can serve a layer (selected by shape at run time, forced here through
-    the tuning knobs) must produce the same network output within the fp32 tolerance."""
+    """Every configuration a handle can be created with (matrix pipe, front kernels, weight order, chunking; read from the
+    environment) must produce the same network output as the default within the fp32 tolerance."""
     fr = torch.from_numpy(synth.blob_frames(7, 140, 250, seed=21)).cuda()
     ref_maps = engine.saliency(fr).cpu().numpy()
     ref_dec = engine.tap(ops.TAP_DEC, 3, (32, 52, 64))

@@ -58,7 +58,7 @@ def test_no_half_swapping_packed_f32_instruction_in_the_library():
     """Build check (hipcc -S on this box, ~35 s): round 5 found a product LOST in a `v_pk_mul_f32 x2 ; v_pk_add_f32 op_sel:[0,1]
     op_sel_hi:[1,0]` sequence of the smoothing kernel when bf16-MFMA workgroups shared its CU (profiles/r05_mx_reproducibility.txt).
     The trigger is not fully understood, so the form is kept out of the library: no kernel may contain a packed f32 instruction that
-    routes the halves of an operand crosswise, and the two smoothing kernels none at all (tools/packed_f32_census.py; kernels whose C
+    routes the halves of an operand crosswise, and the smoothing kernel none at all (tools/packed_f32_census.py; kernels whose C
     code the compiler packs that way carry SVC_NO_PK).  The detector itself is checked on a two-line kernel that compiles to the form."""
     import subprocess
     import tempfile

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of tuning knobs on the benchmark: per knob set, the pipelined step and the un-pipelined 'pw' class time.
-#   tools/ab_knobs.sh "SVC_DWPW_NT=5" "SVC_DWPW_NT=3" ...     (a set may hold several assignments separated by spaces)
+#   tools/ab_knobs.sh "SVC_MX=bf16x6" "SVC_MX=f32" ...     (a set may hold several assignments separated by spaces)
 for set in "$@"; do
   env $set BENCH_CONFIG3=0 python bench.py --steps 60 --cpu-sample 0 --repeats 5 --iso-steps 3 --full 2>/dev/null | tail -1 | python -c "
 import json,sys

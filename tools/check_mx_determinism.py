@@ -1,15 +1,12 @@
 """Which kernel family makes a frame's map depend on its batch / engine / run?  (GPU box helper, round 5.)
-For every SVC_MX_MASK bit (one family on the split-bf16 pipe at a time), SVC_MX=f32 and the default: the maps and taps of the
-same frames (a) twice on one engine, (b) on a second engine, (c) as a sub-batch, at three geometries."""
+For SVC_MX=f32 and the default: the maps and taps of the same frames (a) twice on one engine, (b) on a second engine, (c) as a sub-batch, at three geometries."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from retargetvid_amd import ops, synth
 from oracle import unisal_ref as U
 
-SETS = [('f32', {'SVC_MX': 'f32'}), ('default', {})] + [('mask %d' % m, {'SVC_MX_MASK': str(m)}) for m in (1, 2, 4, 8, 16)] + \
-       [('irb bit %d' % b, {'SVC_MX_MASK': '2', 'SVC_IRB_MX': str(1 << b)}) for b in (0, 1, 3, 4)] + \
-       [('default minpx400', {'SVC_DWPW_MIN_PX': '400'})]
+SETS = [('f32', {'SVC_MX': 'f32'}), ('default', {})]
 
 
 def engine(env):

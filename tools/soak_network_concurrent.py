@@ -1,6 +1,6 @@
 """Run-to-run reproducibility of the NETWORK with several passes sharing the chip: N engines on N streams push the same 32 frames
 ITERS times; every pass's maps (and, on a mismatch, the taps of the differing frame) are compared with a single-stream reference.
-python tools/soak_network_concurrent.py [N] [ITERS]    (GPU box; SVC_MX / SVC_MX_MASK select the matrix pipe)
+python tools/soak_network_concurrent.py [N] [ITERS]    (GPU box; SVC_MX selects the matrix pipe)
 GEOM=HxW: maps of another geometry (187x250 = 4:3 sources, 250x140 = portrait; default 140x250) -- the taps of a differing frame are
 then not printed (their shapes belong to the 16:9 network input), the count of differing passes is."""
 import os, sys
