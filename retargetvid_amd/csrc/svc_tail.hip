@@ -3202,15 +3202,22 @@ static int cluster_center_impl(SvcHandle *h, uint8_t *maps, int n, int height, i
     hipStream_t s = (hipStream_t)stream;
     int rc = ensure_ring(h);
     if (rc) return rc;
-    // best settings: the cluster filter runs on maps shrunk by resize_factor (cvRound sizes, scale = factor)
-    const int factor = params->clust_filt ? params->resize_factor : 1;
+    // best settings: the cluster filter runs on maps shrunk by resize_factor and the centre is taken on the nearest-shrunk map,
+    // both of the size cv2.resize gives fx = fy = 1 / factor (cvRound, half to even).  cv2.resize refuses an empty size, so a
+    // map that shrinks to nothing is an error whenever one of the two would shrink it (smartVidCrop.py:1080, :1184).
     const int full_h = height, full_w = width;
+    const int rs_h = (int)lrint((double)full_h * (1.0 / params->resize_factor));
+    const int rs_w = (int)lrint((double)full_w * (1.0 / params->resize_factor));
+    if (params->resize_factor > 1 && (params->clust_filt || params->com_km) && (rs_h < 1 || rs_w < 1)) {
+        svc_set_error("svc_cluster_center: map %dx%d too small for resize_factor %d", full_h, full_w, params->resize_factor);
+        return SVC_E_INVALID;
+    }
+    const int factor = params->clust_filt ? params->resize_factor : 1;
     uint8_t *full_maps = maps;
     const int *rs_down = nullptr, *rs_up = nullptr;
     if (factor > 1) {
-        height = (int)lrint((double)full_h * (1.0 / factor));
-        width = (int)lrint((double)full_w * (1.0 / factor));
-        if (height < 1 || width < 1) { svc_set_error("svc_cluster_center: map too small for resize_factor"); return SVC_E_INVALID; }
+        height = rs_h;
+        width = rs_w;
         auto key = std::make_tuple(full_h, full_w, factor);
         auto it = h->rs_tabs.find(key);
         if (it == h->rs_tabs.end()) {       // tables are keyed by shape and never rewritten (earlier calls may still read theirs)
@@ -3391,9 +3398,7 @@ static int cluster_center_impl(SvcHandle *h, uint8_t *maps, int n, int height, i
         k_centre_argmax<<<n, 256, 0, s>>>(full_maps, full_h, full_w, make_fdiv(full_w), xy);
         SVC_CHECK_LAUNCH();
     } else if (params->resize_factor > 1) {       // centre of the nearest-neighbour shrunk final map (also when clust_filt is off)
-        const int f2 = params->resize_factor;
-        k_centre_nearest<<<n, 256, 0, s>>>(full_maps, full_h, full_w, (int)lrint((double)full_h * (1.0 / f2)),
-                                           (int)lrint((double)full_w * (1.0 / f2)), f2, xy);
+        k_centre_nearest<<<n, 256, 0, s>>>(full_maps, full_h, full_w, rs_h, rs_w, params->resize_factor, xy);
         SVC_CHECK_LAUNCH();
     }
     return SVC_OK;

@@ -28,8 +28,9 @@ def _ref_tail(maps, flags, CP):
     return np.transpose(hwn, (2, 0, 1)), dx, dy, npts
 
 
-def _check_tail(engine, maps, flags, CP):
-    ref_maps, dx, dy, _ = _ref_tail(maps, flags, CP)
+def _check_tail(engine, maps, flags, CP, ref=None):
+    """Device tail on maps (raw u8 [n,h,w]) against the oracle's (ref: _ref_tail's result, when the caller has it already)."""
+    ref_maps, dx, dy, _ = _ref_tail(maps, flags, CP) if ref is None else ref
     dm = torch.from_numpy(maps.copy()).cuda()
     engine.threshold_(dm, CP['t_threshold'])
     xy, stats = engine.cluster_center_(dm, flags, CP, want_stats=True)
@@ -309,22 +310,28 @@ def _prim_and_labels(engine, maps, CP):
     """Per map: the device's Prim edge list and labels against the oracle's (the rare paths of k_prim_lvl / k_tree_par)."""
     dm = torch.from_numpy(maps.copy()).cuda()
     engine.cluster_center_(dm, None, CP)
-    mcs, ms = CP['hdbscan_min'], CP['hdbscan_min_samples']
     for i in range(maps.shape[0]):
-        st = engine.cluster_state(i, maps.shape[1] * maps.shape[2])
-        X = np.stack([st['pts'] & 255, (st['pts'] >> 8) & 255], 1).astype(np.int64)
-        assert np.array_equal(X, np.argwhere(maps[i] > 0))
-        if len(X) <= mcs + 1:
-            continue
-        core = H.core_distances(X, H.effective_min_samples(len(X), mcs, ms))
-        assert np.array_equal(core, st['core']), i
-        u, v, w = H.prim_mst(X, core)
-        assert np.array_equal(np.stack([u, v, w], 1), st['mst']), 'Prim sequence of map %d (N = %d)' % (i, len(X))
-        ref = H.hdbscan_labels(X, mcs, ms)
-        got = st['labels']
-        assert np.array_equal(ref < 0, got < 0), i
-        pairs = {(a, b) for a, b in zip(ref[ref >= 0], got[got >= 0])}
-        assert len(pairs) == len({a for a, _ in pairs}) == len({b for _, b in pairs}), 'labels of map %d' % i
+        _state_is_the_oracles(engine, i, maps[i], CP)
+
+
+def _state_is_the_oracles(engine, i, clustered, CP):
+    """The last call's state of map i (point list, core distances, Prim edge list, labels up to renaming) against the
+    oracle's HDBSCAN on the map the cluster filter saw (clustered: thresholded, blended and, with resize_factor > 1, shrunk)."""
+    mcs, ms = CP['hdbscan_min'], CP['hdbscan_min_samples']
+    st = engine.cluster_state(i, clustered.shape[0] * clustered.shape[1])
+    X = np.stack([st['pts'] & 255, (st['pts'] >> 8) & 255], 1).astype(np.int64)
+    assert np.array_equal(X, np.argwhere(clustered > 0)), i
+    if len(X) <= mcs + 1:
+        return
+    core = H.core_distances(X, H.effective_min_samples(len(X), mcs, ms))
+    assert np.array_equal(core, st['core']), i
+    u, v, w = H.prim_mst(X, core)
+    assert np.array_equal(np.stack([u, v, w], 1), st['mst']), 'Prim sequence of map %d (N = %d)' % (i, len(X))
+    ref = H.hdbscan_labels(X, mcs, ms)
+    got = st['labels']
+    assert np.array_equal(ref < 0, got < 0), i
+    pairs = {(a, b) for a, b in zip(ref[ref >= 0], got[got >= 0])}
+    assert len(pairs) == len({a for a, _ in pairs}) == len({b for _, b in pairs}), 'labels of map %d' % i
 
 
 def test_prim_rounds_and_parallel_hierarchy_on_adversarial_maps(engine):

@@ -145,12 +145,16 @@ def test_focus_stability_is_the_oracles_to_the_last_bit():
     """svc_host_focus_stability against oracle/temporal_ref.focus_stability (get_points_on_line + sc_check_for_extra_cuts + the
     hold loop, smartVidCrop.py:1337-1455, :2425-2473): the float32 buffer / float32 slope arithmetic, NumPy's arange lengths,
     the sample-count mismatch that makes NumPy raise (-> no statistic), moves along one axis, integer-valued centres, centres
-    outside the image.  Jump statistics, held centres and the list of low-saliency jumps: equal, not close."""
+    outside the image; landscape, shrunk, portrait and square maps.  Jump statistics, held centres and the list of
+    low-saliency jumps: equal, not close."""
     rng = np.random.RandomState(0)
     n_stats = 0
-    for trial in range(120):
+    for trial in range(184):
         n = rng.randint(7, 40)
-        h, w = (35, 62) if trial % 2 else (140, 250)
+        if trial < 120:
+            h, w = (35, 62) if trial % 2 else (140, 250)
+        else:
+            h, w = (250, 140) if (trial // 4) % 2 else (249, 249)          # every kind below at both shapes
         maps = np.zeros((n, h, w), np.uint8)
         for i in range(n):
             maps[i] = np.where(rng.rand(h, w) < rng.choice([0.02, 0.2, 0.6]), rng.randint(90, 256, (h, w)), 0)
