@@ -77,8 +77,9 @@ const char *svc_last_error(void);
  * 5 = svc_saliency_census_u8, svc_transnet_predict_rows and svc_transnet_config_get / _set exist; svc_create rejects an
  *     unknown spelling of SVC_MX / SVC_SHOT_MX with SVC_E_INVALID.
  * 6 = svc_render_crops_u8 (SVC_RENDER_BGR) and the profile class SVC_K_RENDER exist.
- * 7 = svc_debug_transnet_tap (SVC_SHOT_TAP_*) exists; svc_create rejects SVC_SHOT_M16 outside 2..4 with SVC_E_INVALID. */
-#define SVC_ABI_VERSION 7
+ * 7 = svc_debug_transnet_tap (SVC_SHOT_TAP_*) exists; svc_create rejects SVC_SHOT_M16 outside 2..4 with SVC_E_INVALID.
+ * 8 = svc_border_profile_u8, svc_saliency_profile_u8 and the profile class SVC_K_BORDER exist. */
+#define SVC_ABI_VERSION 8
 int svc_abi_version(void);
 
 /* weights_blob_host: the packed, BN-folded static SALICON slice of a UNISAL
@@ -119,6 +120,24 @@ int svc_saliency_thresholded_u8(SvcHandle *h, const uint8_t *frames_nhwc, int n,
  * diagnostic per video from these rows).  census_n4 may be NULL (= svc_saliency_thresholded_u8).  No counterpart in the reference. */
 int svc_saliency_census_u8(SvcHandle *h, const uint8_t *frames_nhwc, int n, int height, int width,
                            uint8_t *maps_nhw, int t, uint32_t *census_n4, void *stream);
+
+/* The device half of sc_border_detection (smartVidCrop.py:842-924).  The reference takes the maximum of a video's RAW
+ * (un-thresholded) maps over time, then per row (f_col) and per column (f_row), and counts the leading / trailing entries
+ * that do not exceed t_border.  Here every map i of maps_nhw[n][height][width] is max-combined into the caller's DEVICE row
+ * profile_n[i][height + width] (uint32): the first `height` entries are the row maxima (max over x), the next `width` the
+ * column maxima (max over y).  The caller zeroes the rows and reduces a video's rows with one maximum over i; counting, the
+ * 0.45 cap and the scaling to the original frame (:880-913) are four numbers per video and stay on the host
+ * (retargetvid_amd.smartVidCrop.sc_border_detection).  Maximum is order-independent: the rows do not depend on the schedule. */
+int svc_border_profile_u8(SvcHandle *h, const uint8_t *maps_nhw, int n, int height, int width,
+                          uint32_t *profile_n, void *stream);
+
+/* svc_saliency_census_u8 that also fills profile_n (as svc_border_profile_u8 would from the UN-thresholded maps) inside the
+ * network's last kernel, for callers that never hold the raw maps (retargetvid_amd/scheduler.py: the frames of several
+ * videos share a pass and come out thresholded).  maps_nhw and census_n4 are byte for byte those of svc_saliency_census_u8.
+ * t in 0..255 (0 = the plain map); census_n4 may be NULL (required NULL with t = 0); profile_n == NULL takes exactly the
+ * launches of svc_saliency_census_u8 / svc_saliency_thresholded_u8. */
+int svc_saliency_profile_u8(SvcHandle *h, const uint8_t *frames_nhwc, int n, int height, int width,
+                            uint8_t *maps_nhw, int t, uint32_t *census_n4, uint32_t *profile_n, void *stream);
 
 /* maps[i] = maps[i] < t ? 0 : maps[i], in place. */
 int svc_threshold_u8(SvcHandle *h, uint8_t *maps, size_t n_bytes, int t, void *stream);
@@ -218,7 +237,8 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
 #define SVC_K_PRIM 10
 #define SVC_K_FINISH 11
 #define SVC_K_RENDER 12    /* svc_render_crops_u8 */
-#define SVC_K_COUNT 13
+#define SVC_K_BORDER 13    /* svc_border_profile_u8 (the fused form, svc_saliency_profile_u8, counts under SVC_K_SMOOTH) */
+#define SVC_K_COUNT 14
 int svc_profile_enable(SvcHandle *h, int kernel_class);
 int svc_profile_read(SvcHandle *h, double *total_ms, int *launches);
 /* The same log without the correction: raw_total_ms = sum of the event-pair durations, pair_ms = cost of an empty event pair

@@ -1533,6 +1533,86 @@ __global__ __launch_bounds__(256) void k_quantise(const float *__restrict__ pre,
     }
 }
 
+// Border profile (sc_border_detection, smartVidCrop.py:842-924): the reference takes the maximum of the RAW maps over time, then per
+// row (f_col) and per column (f_row).  The device keeps one u32 row per map, profile[i][h + w] = { max over x of map i's row y,
+// y < h; max over y of its column x, x < w }, max-combined into what the caller holds; the caller reduces a video's rows with one
+// amax(0).  Grid = (bands of BP_ROWS rows, maps): thread tid owns columns tid, tid + 256, .. and walks down its band with the
+// column maxima in registers; a row's maximum is one wave reduction and one LDS atomic per wave; the band ends in one global
+// atomicMax per column and per row (no return value; maximum is order-independent, so the rows are the same under any schedule).
+// A zero never changes a row, so it is not sent.  Byte loads, coalesced along x: map sides are not multiples of 4 and the whole
+// read is n * h * w bytes.
+#define BP_ROWS 20      // rows per workgroup: 7 bands x 32 maps = 224 workgroups for a chunk of 140 x 250 maps
+#define BP_COLS 4       // columns per thread at most (widths up to 1024; wider maps loop over column groups)
+
+template <class Load>
+__device__ __forceinline__ void border_band(Load load, int h, int w, unsigned *__restrict__ prof) {
+    __shared__ unsigned rmax[BP_ROWS];
+    const int tid = threadIdx.x;
+    const int y0 = blockIdx.x * BP_ROWS, y1 = min(h, y0 + BP_ROWS);
+    if (tid < BP_ROWS) rmax[tid] = 0u;
+    __syncthreads();
+    for (int c0 = 0; c0 < w; c0 += 256 * BP_COLS) {
+        unsigned cmax[BP_COLS];
+#pragma unroll
+        for (int j = 0; j < BP_COLS; ++j) cmax[j] = 0u;
+        for (int y = y0; y < y1; ++y) {
+            unsigned r = 0u;
+#pragma unroll
+            for (int j = 0; j < BP_COLS; ++j) {
+                const int c = c0 + j * 256 + tid;
+                if (c < w) {
+                    const unsigned v = load(y, c);
+                    cmax[j] = max(cmax[j], v);
+                    r = max(r, v);
+                }
+            }
+            r = max(r, (unsigned)__shfl_xor((int)r, 32)); r = max(r, (unsigned)__shfl_xor((int)r, 16));
+            r = max(r, (unsigned)__shfl_xor((int)r, 8)); r = max(r, (unsigned)__shfl_xor((int)r, 4));
+            r = max(r, (unsigned)__shfl_xor((int)r, 2)); r = max(r, (unsigned)__shfl_xor((int)r, 1));
+            if ((tid & 63) == 0 && r) atomicMax(&rmax[y - y0], r);
+        }
+#pragma unroll
+        for (int j = 0; j < BP_COLS; ++j) {
+            const int c = c0 + j * 256 + tid;
+            if (c < w && cmax[j]) atomicMax(prof + h + c, cmax[j]);
+        }
+    }
+    __syncthreads();
+    if (tid < y1 - y0 && rmax[tid]) atomicMax(prof + y0 + tid, rmax[tid]);
+}
+
+// svc_border_profile_u8: maps already in memory
+__global__ __launch_bounds__(256) void k_border_profile(const uint8_t *__restrict__ maps, int h, int w, unsigned *__restrict__ profile) {
+    const size_t f = blockIdx.y;
+    const uint8_t *m = maps + f * (size_t)h * w;
+    border_band([&](int y, int c) { return (unsigned)m[(size_t)y * w + c]; }, h, w, profile + f * (size_t)(h + w));
+}
+
+// k_quantise with the profile of the UN-thresholded value (svc_saliency_profile_u8): the same expression per pixel, the same map
+// and census; grid = (bands, frames) instead of flat, because the profile needs the row structure.
+__global__ __launch_bounds__(256) void k_quantise_profile(const float *__restrict__ pre, const unsigned *__restrict__ fmax,
+                                                          uint8_t *__restrict__ out, int h, int w, int thr,
+                                                          unsigned long long *__restrict__ census, unsigned *__restrict__ rows,
+                                                          unsigned *__restrict__ profile) {
+    const uint32_t f = blockIdx.y;
+    const size_t base = (size_t)f * h * w;
+    const float m = dec_f32(fmax[f]);
+    border_band([&](int y, int c) {
+        const size_t gid = base + (size_t)y * w + c;
+        const float e = expf(pre[gid] - m);
+        const uint8_t v = (uint8_t)(e * 255.0f);
+        out[gid] = (int)v < thr ? (uint8_t)0 : v;
+        if (census && thr > 0) {
+            const int d = (int)v - (thr - 1);
+            if (d >= 0 && d <= 2) {
+                atomicAdd((unsigned *)(census + 4) + f * 4 + d, 1u);
+                if (rows) atomicAdd(rows + f * 4 + d, 1u);
+            }
+        }
+        return (unsigned)v;
+    }, h, w, profile + (size_t)f * (h + w));
+}
+
 // --------------------------------------------------------------------------------------
 // plan / workspace
 // --------------------------------------------------------------------------------------
@@ -2875,7 +2955,8 @@ static int launch_irb(SvcHandle *h, hipStream_t s, const float *X, int n, int H,
 #define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 // One pass of the network over n <= plan->nb frames.
-static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *maps, hipStream_t s, int thr = 0, unsigned *census_rows = nullptr) {
+static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *maps, hipStream_t s, int thr = 0, unsigned *census_rows = nullptr,
+                         unsigned *profile_rows = nullptr) {
     NetPlan *p = h->plan;
     const int NH = p->NH, NW = p->NW;
     int H = NH / 2, W = NW / 2;
@@ -3043,9 +3124,15 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
                                                   NH, NW, p->h, p->w, SD_ROWS, p->sd_tile_cap, make_fdiv(p->w));
         SVC_CHECK_LAUNCH();
     }
-    k_quantise<<<blocks256((size_t)n * p->h * p->w), 256, 0, s>>>(p->buf(B_PRE), (const unsigned *)p->fmax.p, maps, n,
-                                                                 p->h * p->w, make_fdiv(p->h * p->w), thr,
-                                                                 (unsigned long long *)h->census.p, census_rows);
+    if (profile_rows) {         // svc_saliency_profile_u8: the banded variant also fills the caller's border-profile rows
+        k_quantise_profile<<<dim3(ceil_div(p->h, BP_ROWS), n), 256, 0, s>>>(p->buf(B_PRE), (const unsigned *)p->fmax.p, maps, p->h, p->w,
+                                                                            thr, (unsigned long long *)h->census.p, census_rows,
+                                                                            profile_rows);
+    } else {
+        k_quantise<<<blocks256((size_t)n * p->h * p->w), 256, 0, s>>>(p->buf(B_PRE), (const unsigned *)p->fmax.p, maps, n,
+                                                                     p->h * p->w, make_fdiv(p->h * p->w), thr,
+                                                                     (unsigned long long *)h->census.p, census_rows);
+    }
     SVC_CHECK_LAUNCH();
     if (thr > 0) h->census_maps += (unsigned long long)n;
     p->last_n = n;
@@ -3053,7 +3140,7 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
 }
 
 static int saliency_impl(SvcHandle *h, const uint8_t *frames, int n, int height, int width, uint8_t *maps, int thr, void *stream,
-                         uint32_t *census_rows = nullptr);
+                         uint32_t *census_rows = nullptr, uint32_t *profile_rows = nullptr);
 
 extern "C" int svc_saliency_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, uint8_t *maps,
                                void *stream) {
@@ -3075,8 +3162,40 @@ extern "C" int svc_saliency_census_u8(SvcHandle *h, const uint8_t *frames, int n
     return saliency_impl(h, frames, n, height, width, maps, t, stream, census_n4);
 }
 
+// svc_saliency_census_u8 that also max-combines, per frame, the row and column maxima of the UN-thresholded map into the caller's
+// device rows profile_n[n][height + width] (u32; the caller zeroes them): the input of sc_border_detection (smartVidCrop.py:842-924)
+// for callers that never hold the raw maps.  profile_n == NULL: the launches of svc_saliency_census_u8 / _thresholded_u8 / _u8.
+extern "C" int svc_saliency_profile_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, uint8_t *maps,
+                                       int t, uint32_t *census_n4, uint32_t *profile_n, void *stream) {
+    if (t < 0 || t > 255 || (census_n4 && t < 1)) {
+        svc_set_error("svc_saliency_profile_u8: threshold outside 0..255 (1..255 with census rows)");
+        return SVC_E_INVALID;
+    }
+    return saliency_impl(h, frames, n, height, width, maps, t, stream, census_n4, profile_n);
+}
+
+// maps_nhw[n][height][width] u8 (raw maps) -> profile_n[n][height + width] u32, max-combined (see k_border_profile)
+extern "C" int svc_border_profile_u8(SvcHandle *h, const uint8_t *maps, int n, int height, int width, uint32_t *profile_n,
+                                     void *stream) {
+    if (!h || n < 0 || height < 1 || width < 1 || (n > 0 && (!maps || !profile_n))) {
+        svc_set_error("svc_border_profile_u8: invalid argument");
+        return SVC_E_INVALID;
+    }
+    if (n == 0) return SVC_OK;
+    SVC_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(h, SVC_K_BORDER, s);
+    const size_t fmap = (size_t)height * width, frow = (size_t)height + width;
+    for (int i = 0; i < n; i += 65535) {                      // grid.y limit
+        const int m = std::min(65535, n - i);
+        k_border_profile<<<dim3(ceil_div(height, BP_ROWS), m), 256, 0, s>>>(maps + i * fmap, height, width, profile_n + i * frow);
+        SVC_CHECK_LAUNCH();
+    }
+    return SVC_OK;
+}
+
 static int saliency_impl(SvcHandle *h, const uint8_t *frames, int n, int height, int width, uint8_t *maps, int thr, void *stream,
-                         uint32_t *census_rows) {
+                         uint32_t *census_rows, uint32_t *profile_rows) {
     if (!h || n < 0 || (n > 0 && (!frames || !maps)) || height < 8 || width < 8) {     // n = 0: a no-op, null buffers allowed
         svc_set_error("svc_saliency_u8: invalid argument");
         return SVC_E_INVALID;
@@ -3091,7 +3210,8 @@ static int saliency_impl(SvcHandle *h, const uint8_t *frames, int n, int height,
         int m = std::min(h->plan->nb, n - i);
         const uint8_t *fr = frames + i * fin;
         uint8_t *mp = maps + i * fout;
-        RC(forward_chunk(h, fr, m, mp, s, thr, census_rows ? census_rows + (size_t)i * 4 : nullptr));
+        RC(forward_chunk(h, fr, m, mp, s, thr, census_rows ? census_rows + (size_t)i * 4 : nullptr,
+                         profile_rows ? profile_rows + (size_t)i * (height + width) : nullptr));
     }
     return SVC_OK;
 }

@@ -100,11 +100,14 @@ class Engine:
         return out
 
     # -- saliency ------------------------------------------------------------------------
-    def saliency(self, frames, out=None, threshold=0, census=None):
+    def saliency(self, frames, out=None, threshold=0, census=None, profile=None):
         """uint8 [n,h,w,3] RGB at saliency size -> uint8 [n,h,w] maps (frame-major); `out`: write into this tensor.
         threshold > 0: the maps come out thresholded (sc_threshold fused into the network's last kernel: the bytes of
         saliency() + threshold_(), one launch less).  census (with a threshold): int32 CUDA rows [n,4] to which the pixels
-        of every frame's raw map at t - 1, t, t + 1 are ADDED (svc_saliency_census_u8; the caller zeroes the rows)."""
+        of every frame's raw map at t - 1, t, t + 1 are ADDED (svc_saliency_census_u8; the caller zeroes the rows).
+        profile: int32 CUDA rows [n,h+w] into which the row and column maxima of every frame's RAW map are max-combined
+        (what border_profile() gives on the un-thresholded maps, from inside the network's last kernel:
+        svc_saliency_profile_u8; the caller zeroes the rows).  Maps and census are the same bytes with and without it."""
         _need_cuda(frames, torch.uint8, 'frames')
         n, h, w, c = frames.shape
         assert c == 3
@@ -116,11 +119,31 @@ class Engine:
         if census is not None:
             _need_cuda(census, torch.int32, 'census')
             assert threshold and tuple(census.shape) == (n, 4)
+        if profile is not None:
+            _need_cuda(profile, torch.int32, 'profile')
+            assert tuple(profile.shape) == (n, h + w)
+            _lib.check(self.lib.svc_saliency_profile_u8(self._h, _ptr(frames), n, h, w, _ptr(out), int(threshold),
+                                                        _ptr(census) if census is not None else None, _ptr(profile), _stream()))
+        elif census is not None:
             _lib.check(self.lib.svc_saliency_census_u8(self._h, _ptr(frames), n, h, w, _ptr(out), int(threshold), _ptr(census), _stream()))
         elif threshold:
             _lib.check(self.lib.svc_saliency_thresholded_u8(self._h, _ptr(frames), n, h, w, _ptr(out), int(threshold), _stream()))
         else:
             _lib.check(self.lib.svc_saliency_u8(self._h, _ptr(frames), n, h, w, _ptr(out), _stream()))
+        return out
+
+    def border_profile(self, maps, out=None):
+        """RAW uint8 [n,h,w] maps -> int32 [n,h+w] rows: [i,:h] the maxima of map i's rows (max over x), [i,h:] of its columns
+        (max over y): the device half of sc_border_detection (svc_border_profile_u8).  `out`: rows to max-combine into
+        (not overwritten); without it a zeroed tensor is made.  A video's profile is out.amax(0)."""
+        _need_cuda(maps, torch.uint8, 'maps')
+        n, h, w = maps.shape
+        if out is None:
+            out = torch.zeros((n, h + w), dtype=torch.int32, device=maps.device)
+        else:
+            _need_cuda(out, torch.int32, 'out')
+            assert tuple(out.shape) == (n, h + w)
+        _lib.check(self.lib.svc_border_profile_u8(self._h, _ptr(maps), n, h, w, _ptr(out), _stream()))
         return out
 
     def tap(self, which, frame, shape):
@@ -156,7 +179,8 @@ class Engine:
     # -- measurement door (bench.py) -------------------------------------------------------
     KERNEL_CLASSES = ('resize', 'lanczos', 'stem', 'pw', 'dw', 'resample', 'smooth', 'threshold', 'compact',
                       'core', 'prim', 'finish')
-    PROFILE_CLASSES = KERNEL_CLASSES + ('render',)   # 'render' (svc_render_crops_u8) is behind the saliency-to-crop path
+    PROFILE_CLASSES = KERNEL_CLASSES + ('render', 'border')   # 'render' (svc_render_crops_u8) is behind the saliency-to-crop path;
+    #                                                        'border' = svc_border_profile_u8 (the fused form counts under 'smooth')
 
     def profile_enable(self, kernel_class):
         """kernel_class: name from PROFILE_CLASSES, or None to switch event recording off."""

@@ -111,7 +111,7 @@ class LookAhead:
 
 
 class _Video:
-    __slots__ = ('idx', 'video', 'plan', 'lane', 'row0', 'xy', 'remaining', 'maps', 'pos', 'done', 'sink', 'ready', 'census')
+    __slots__ = ('idx', 'video', 'plan', 'lane', 'row0', 'xy', 'remaining', 'maps', 'pos', 'done', 'sink', 'ready', 'census', 'profile')
 
     def __init__(self, idx, video, plan, sink):
         self.idx, self.video, self.plan = idx, video, plan
@@ -153,6 +153,13 @@ class _Lane:
             # last kernel (svc_saliency_census_u8); rows without a network pass stay 0
             self.census = torch.zeros((rows, 4), dtype=torch.int32, device=dev)
             self.census_tmp = torch.zeros((sc.chunk, 4), dtype=torch.int32, device=dev)
+            # border profile (sc_border_detection with t_border set): row and column maxima of a row's RAW map, max-combined by the
+            # network's last kernel (svc_saliency_profile_u8) -- the maps themselves come out thresholded; rows without a
+            # network pass stay 0, which no maximum notices
+            self.profile = self.profile_tmp = None
+            if sc.CP['t_border'] != -1:
+                self.profile = torch.zeros((rows, sal_h + sal_w), dtype=torch.int32, device=dev)
+                self.profile_tmp = torch.zeros((sc.chunk, sal_h + sal_w), dtype=torch.int32, device=dev)
         self.cap = rows
         self.row_of_frame = np.empty(rows, np.int64)
         self.flags = np.zeros(rows, np.uint8)
@@ -256,14 +263,19 @@ class _Lane:
                 rows = self.row_of_frame[f0:f0 + k]
                 r0 = int(rows[0])
                 cen = 2 <= int(sc.CP['t_threshold']) <= 254              # (t = 1: level t - 1 is the value of the rows without a network pass)
+                bor = self.profile is not None
                 if int(rows[-1]) - r0 + 1 == k:                       # no zero row inside: the network writes in place
                     self.eng.saliency(self.small[f0:f0 + k], out=self.maps[r0:r0 + k], threshold=sc.CP['t_threshold'],
-                                      census=self.census[r0:r0 + k] if cen else None)
+                                      census=self.census[r0:r0 + k] if cen else None,
+                                      profile=self.profile[r0:r0 + k] if bor else None)
                 else:
                     if cen:
                         self.census_tmp[:k].zero_()
+                    if bor:
+                        self.profile_tmp[:k].zero_()
                     self.eng.saliency(self.small[f0:f0 + k], out=self.tmp[:k], threshold=sc.CP['t_threshold'],
-                                      census=self.census_tmp[:k] if cen else None)
+                                      census=self.census_tmp[:k] if cen else None,
+                                      profile=self.profile_tmp[:k] if bor else None)
                     brk = np.flatnonzero(np.diff(rows) != 1) + 1
                     a = 0
                     for b in list(brk) + [k]:                         # runs of consecutive rows
@@ -271,6 +283,8 @@ class _Lane:
                         self.maps[ra:ra + (b - a)].copy_(self.tmp[a:b])
                         if cen:
                             self.census[ra:ra + (b - a)].copy_(self.census_tmp[a:b])
+                        if bor:
+                            self.profile[ra:ra + (b - a)].copy_(self.profile_tmp[a:b])
                         a = int(b)
         t1 = time.perf_counter()
         self.pipe.submit_rows(n_rows, self.flags[self.rows_called:R])
@@ -318,9 +332,8 @@ class JobScheduler:
                  host_threads=3, depth=2, lane_rows=4096, piece_frames=256, piece_bytes=256 << 20, plan_ahead=None):
         import torch
         from . import ops as _ops
-        if CP['exit_on_spread_sal'] or CP['exit_on_low_cvrg'] or CP['t_border'] != -1:
-            raise NotImplementedError('mean-saliency / coverage gates and border detection are disabled in both '
-                                      'published parameter sets and are not part of this path')
+        if CP['exit_on_spread_sal'] or CP['exit_on_low_cvrg']:
+            raise NotImplementedError(S.GATES_REFUSED)
         self.CP = CP
         self.ratios = tuple(ratios) if ratios else (CP['out_ratio'],)
         self.chunk, self.depth, self.lane_rows = int(chunk), int(depth), int(lane_rows)
@@ -529,6 +542,10 @@ class JobScheduler:
                     v.maps = v.maps.clone()
                     n_sel = v.plan['n_sel']
                     v.census = lane.census[v.row0:v.row0 + n_sel].sum(0)      # the video's own rows (read on the host by _finish_video)
+                    v.profile = None
+                    if lane.profile is not None:              # maximum over time of the video's raw maps, per row and per column
+                        v.profile = (lane.profile[v.row0:v.row0 + n_sel].amax(0) if n_sel else
+                                     torch.zeros(lane.profile.shape[1], dtype=torch.int32, device=lane.profile.device))
                     v.ready = torch.cuda.Event()
                     v.ready.record(lane.stream)               # _finish_video waits for the copy before anything reads it
                 self.futures.append(self.pool.submit(self._finish_video, v))
@@ -538,7 +555,8 @@ class JobScheduler:
         """Host stages of one video (pool thread)."""
         S.sc_init_time()
         v.ready.synchronize()              # the video's own copy of its maps is complete (made on the lane's stream; read on any)
-        VD = S._LazySmaps(S._ingest_dict(v.plan, v.maps, xy_stream=v.xy))
+        VD = S._LazySmaps(S._ingest_dict(v.plan, v.maps, xy_stream=v.xy,
+                                         border_profile=None if v.profile is None else v.profile.cpu().numpy()))
         # the regime diagnostic of THIS video (smartVidCrop.after_ingest reports it): its maps' pixels at t - 1, t, t + 1 per map and level
         n_net = int((~v.plan['zero_map']).sum())
         tt = int(self.CP['t_threshold'])

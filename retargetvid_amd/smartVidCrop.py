@@ -146,6 +146,58 @@ def sc_calc_dest_size(vid_data, crop_params, verbose=False):
     return vid_data
 
 
+GATES_REFUSED = ('the mean-saliency gate (exit_on_spread_sal) and the coverage gate (exit_on_low_cvrg) are disabled in both '
+                 'published parameter sets and are not part of this path')
+
+
+def sc_border_detection(crop_params, vid_data, verbose=False, engine=None):
+    """Blank borders (letterbox / pillarbox bars) of one video, in pixels of the original frame (smartVidCrop.py:842-924):
+    vid_data['border_t' / '_b' / '_l' / '_r'].  t_border == -1 (the default): four zeros, nothing else is touched.
+    Otherwise the video's profile -- the maximum of its RAW saliency maps over time, then per row (h_process values) and per
+    column (w_process values) -- is taken from vid_data['border_profile'] (put there by the ingest that ran: the streaming
+    ingest and the multi-video scheduler threshold the maps before anybody could look) or, if absent, computed on the device
+    from vid_data['smaps_dev'] (Engine.border_profile), which must then still hold the raw maps.  From the top, the bottom,
+    the left and the right the entries that do not exceed t_border are counted up to the first that does, capped at 45 % of
+    the side and scaled to the original frame with the reference's float order, int((ho / h) * t).  Also stores what was
+    measured: vid_data['border_f_col'] (row maxima, uint8 [h_process]) and ['border_f_row'] (column maxima, [w_process])."""
+    if crop_params['t_border'] == -1:
+        vid_data['border_t'] = vid_data['border_b'] = vid_data['border_l'] = vid_data['border_r'] = 0
+        return vid_data
+    h, w = int(vid_data['h_process']), int(vid_data['w_process'])
+    ho, wo = int(vid_data['h_orig']), int(vid_data['w_orig'])
+    prof = vid_data.get('border_profile')
+    if prof is None:
+        if 'xy_stream' in vid_data or not dict.__contains__(vid_data, 'smaps_dev'):
+            raise ValueError('sc_border_detection: no border_profile and no raw maps (the ingest that thresholds the maps '
+                             'records the profile only when t_border is set)')
+        maps = vid_data['smaps_dev']
+        if maps.shape[0]:
+            prof = (engine or get_engine()).border_profile(maps).amax(0).cpu().numpy()
+        else:
+            prof = np.zeros(h + w, np.int32)
+        vid_data['border_profile'] = prof
+    prof = np.asarray(prof).reshape(-1)
+    if prof.size != h + w:
+        raise ValueError('sc_border_detection: border_profile has %d entries, h_process + w_process = %d' % (prof.size, h + w))
+    f_col, f_row = prof[:h].astype(np.uint8), prof[h:].astype(np.uint8)
+    tb = crop_params['t_border']
+
+    def blank(f):                       # (:880-904) entries up to the first above t_border
+        above = np.flatnonzero(f > tb)
+        return int(above[0]) if above.size else int(f.size)
+
+    t, b, l, r = blank(f_col), blank(f_col[::-1]), blank(f_row), blank(f_row[::-1])
+    t, b = min(t, int(h * 0.45)), min(b, int(h * 0.45))
+    l, r = min(l, int(w * 0.45)), min(r, int(w * 0.45))
+    vid_data['border_t'], vid_data['border_b'] = int((ho / h) * t), int((ho / h) * b)
+    vid_data['border_l'], vid_data['border_r'] = int((wo / w) * l), int((wo / w) * r)
+    vid_data['border_f_col'], vid_data['border_f_row'] = f_col, f_row
+    if verbose:
+        print(' %-24s: (%dx%d) t=%d,b=%d,l=%d,r=%d' % ('border detection', ho, wo, vid_data['border_t'], vid_data['border_b'],
+                                                         vid_data['border_l'], vid_data['border_r']))
+    return vid_data
+
+
 def sc_compute_bb(vid_data, crop_params, verbose=False):
     """smartVidCrop.py:979-1048: centres (saliency-map pixels) -> [x1,y1,x2,y2] per frame (native: svc_host_boxes)."""
     fc = vid_data['fc']
@@ -403,7 +455,7 @@ def plan_video(video, crop_params, engine=None, shot_net=None, shots=None):
                 zero_map=zero_map, flags=blend_flags(n_sel, seg_sel) if crop_params['clust_filt'] else None)
 
 
-def _ingest_dict(plan, smaps, xy_stream=None):
+def _ingest_dict(plan, smaps, xy_stream=None, border_profile=None):
     """The dict the ingest hands on (the reference's vid_data after ingest_pickle, smartVidCrop.py:826-836)."""
     vd = dict(smaps_dev=smaps, segmentation=plan['seg'], segmentation_sel=plan['seg_sel'], true_inds=plan['true_inds'],
               inds_to_orig=plan['map2orig'], fr=plan['fr'], fc=plan['n_frames'], fc_sel=plan['n_sel'], h_orig=plan['h'],
@@ -413,6 +465,8 @@ def _ingest_dict(plan, smaps, xy_stream=None):
         vd['trans_probs'] = plan['trans_probs']
     if xy_stream is not None:
         vd['xy_stream'] = xy_stream
+    if border_profile is not None:                    # sc_border_detection's input when the maps are no longer raw
+        vd['border_profile'] = border_profile
     return vd
 
 
@@ -442,7 +496,7 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
     n_sel = len(true_inds)
     dev = engine.device
     smaps = torch.zeros((n_sel, sal_h, sal_w), dtype=torch.uint8, device=dev)
-    pipe, xy_stream, flags_all = None, None, None
+    pipe, xy_stream, flags_all, prof = None, None, None, None
     if stream_batch and crop_params['clust_filt']:
         from . import pipeline as _pl
         flags_all = plan['flags']
@@ -455,6 +509,8 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
         pipe.CP, pipe.maps_out = crop_params, smaps
         xy_stream = np.full((n_sel, 2), np.nan)
         fed = 0
+        if crop_params['t_border'] != -1:             # the maps leave this ingest thresholded: their border profile is taken here
+            prof = torch.zeros((n_sel, sal_h + sal_w), dtype=torch.int32, device=dev)
 
         def feed_tail(upto):
             """threshold + one clustering round for the maps [fed, upto) that are complete (in stream order)."""
@@ -465,6 +521,8 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
                     for g, x, y in pipe.collect():
                         xy_stream[g] = (x, y)
                 chunk = smaps[fed:fed + k]
+                if prof is not None:
+                    engine.border_profile(chunk, out=prof[fed:fed + k])
                 engine.threshold_(chunk, crop_params['t_threshold'])
                 pipe.submit_maps(chunk, flags_all[fed:fed + k])
                 fed += k
@@ -486,9 +544,12 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
     if pipe is not None:
         for g, x, y in pipe.finish():
             xy_stream[g] = (x, y)
+    border_profile = None
+    if prof is not None:
+        border_profile = prof.amax(0).cpu().numpy() if n_sel else np.zeros(sal_h + sal_w, np.int32)
     torch.cuda.current_stream(dev).synchronize()      # the caller's stream only: other videos may be in flight on theirs
     sc_register_time(t, '_read_sal_det')
-    return _ingest_dict(plan, smaps, xy_stream)
+    return _ingest_dict(plan, smaps, xy_stream, border_profile)
 
 
 def detect_shots(frames, fr, crop_params=None, net=None, engine=None, trans_threshold=0.1):
@@ -622,9 +683,8 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
     results = {}
     if CP is None:
         CP = sc_init_crop_params()
-    if CP['exit_on_spread_sal'] or CP['exit_on_low_cvrg'] or CP['t_border'] != -1:
-        raise NotImplementedError('mean-saliency / coverage gates and border detection are disabled in both '
-                                  'published parameter sets and are not part of this path')
+    if CP['exit_on_spread_sal'] or CP['exit_on_low_cvrg']:
+        raise NotImplementedError(GATES_REFUSED)
     if save_vid and demo_fn:
         raise NotImplementedError('the five-panel demo video (cv2 drawing and text) is not rendered by this package; '
                                   'pass demo_fn=\'\'')
@@ -727,7 +787,7 @@ def after_ingest(VD, CP, engine, verbose=False):
     VD = sc_calc_dest_size(VD, CP, verbose=verbose)
     sc_register_time(t, '_calc_dest_size')
     t = time.perf_counter()
-    VD['border_t'] = VD['border_b'] = VD['border_l'] = VD['border_r'] = 0
+    VD = sc_border_detection(CP, VD, verbose=verbose, engine=engine)      # (the maps are still raw here unless the ingest ran the tail)
     sc_register_time(t, '_border_det')
     VD['mean_sal_score'] = None
     VD['mean_cvrg_score'] = None

@@ -34,6 +34,7 @@ def main():
     ap.add_argument('--resident', type=int, default=1, help='1: the frames the job selects are generated before the timed run and lie in HBM (synth.ResidentBlobVideo), as bench.py\'s batch does; 0: generated on the fly inside the run (40 element-wise passes per frame on the GPU: the generator, not the path)')
     ap.add_argument('--repeat', type=int, default=1, help='run the job this many times in the process (the first pays one-time costs)')
     ap.add_argument('--ranks-per-gpu', type=int, default=1, help='processes that share one GPU (launch nproc-per-node = GPUs x this)')
+    ap.add_argument('--t-border', type=int, default=-1, help='CP[\'t_border\']: -1 = border detection off (the published settings); 0..255: measure blank borders and crop inside them')
     ap.add_argument('--annotations', default=os.path.join(ROOT, 'tests', 'golden', 'retargetvid'))
     args = ap.parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (('WORLD_SIZE', '1'), ('RANK', '0'), ('LOCAL_RANK', '0')))
@@ -51,6 +52,7 @@ def main():
     if args.max_frames:
         counts = [min(c, args.max_frames) for c in counts]
     CP = S.sc_init_crop_params()
+    CP['t_border'] = args.t_border
     ratios = ('1:3', '3:1')
 
     def make(i):
@@ -90,7 +92,7 @@ def main():
             rows, _ = E.evaluate(args.out, args.annotations, out_path=os.path.join(args.out, 'eval_current.txt'))
             score = {ar: [round(x, 3) for x in s] for ar, s in rows[0][1].items()}
         dt = st['seconds_rank']
-        print(json.dumps(dict(config='RetargetVid-shaped synthetic set', packed=bool(args.packed), seconds_rank0_runs=runs, scheduler={k: (round(v, 4) if isinstance(v, float) else v) for k, v in sched_stats.items()}, resident=bool(args.resident), stream_batch=args.stream_batch, videos=len(vids), world=world,
+        print(json.dumps(dict(config='RetargetVid-shaped synthetic set', t_border=args.t_border, packed=bool(args.packed), seconds_rank0_runs=runs, scheduler={k: (round(v, 4) if isinstance(v, float) else v) for k, v in sched_stats.items()}, resident=bool(args.resident), stream_batch=args.stream_batch, videos=len(vids), world=world,
                               video_frames=sum(counts), saliency_frames_rank0=st['saliency_frames_rank'],
                               seconds_rank0=round(dt, 2), seconds_slowest_rank=round(dt_max, 2), video_frames_per_s_job=round(sum(counts) / dt_max, 1), video_frames_per_s_rank0=round(st['video_frames_rank'] / dt, 1),
                               saliency_frames_per_s_rank0=round(st['saliency_frames_rank'] / dt, 1), eval=score)))
