@@ -78,8 +78,9 @@ const char *svc_last_error(void);
  *     unknown spelling of SVC_MX / SVC_SHOT_MX with SVC_E_INVALID.
  * 6 = svc_render_crops_u8 (SVC_RENDER_BGR) and the profile class SVC_K_RENDER exist.
  * 7 = svc_debug_transnet_tap (SVC_SHOT_TAP_*) exists; svc_create rejects SVC_SHOT_M16 outside 2..4 with SVC_E_INVALID.
- * 8 = svc_border_profile_u8, svc_saliency_profile_u8 and the profile class SVC_K_BORDER exist. */
-#define SVC_ABI_VERSION 8
+ * 8 = svc_border_profile_u8, svc_saliency_profile_u8 and the profile class SVC_K_BORDER exist.
+ * 9 = svc_resize_frames_nv12 and svc_render_crops_nv12 exist (NV12 input). */
+#define SVC_ABI_VERSION 9
 int svc_abi_version(void);
 
 /* weights_blob_host: the packed, BN-folded static SALICON slice of a UNISAL
@@ -101,6 +102,22 @@ int svc_resize_frames_u8(SvcHandle *h, const uint8_t *frames, int n, int height,
 #define SVC_RENDER_BGR 1
 int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                         int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
+
+/* NV12 input: the two entries above on frames[n][height * 3 / 2][width] u8 -- `height` rows of luma Y, then height / 2 rows of
+ * interleaved chroma pairs U V, one pair per 2 x 2 pixels; `height` and `width` are the PICTURE's, even and >= 2 (else
+ * SVC_E_INVALID).  Pixel (y, x) takes Y[y][x] and the pair (y >> 1, x >> 1) (chroma replicated, not interpolated) and is
+ * converted with BT.601 limited range in 20-bit fixed point, int32, arithmetic shifts (OpenCV's COLOR_YUV2RGB_NV12 constants):
+ *   yy = max(0, Y - 16) * 1220542, u = U - 128, v = V - 128
+ *   R = clamp((yy + (1 << 19) + 1673527 v) >> 20), G = clamp((yy + (1 << 19) - 852492 v - 409993 u) >> 20),
+ *   B = clamp((yy + (1 << 19) + 2116026 u) >> 20), clamp to 0..255
+ * fused into the resampling / the copy: out is bit for bit what the _u8 entry gives on the converted frames -- same output
+ * layout, flags, clamping of the window origins (which may be odd in x and y: the chroma index comes from frame coordinates)
+ * and LDS limit.  They count under SVC_K_RESIZE / SVC_K_RENDER.  No counterpart in the reference (OpenCV decodes to RGB before
+ * it sees a frame); the output is always RGB / BGR. */
+int svc_resize_frames_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
+                           uint8_t *out, int sh, int sw, void *stream);
+int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                          int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
 
 /* frames_nhwc[n][h][w][3] u8 RGB (saliency size, e.g. 140x250) -> maps_nhw[n][h][w] u8.
  * Frame-major output; the reference's [h][w][n] view is a transpose done by the
@@ -224,7 +241,7 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
  * the same stream, measured at read time, is taken off every launch: calibrated against rocprofv3 kernel durations) and the number of launches recorded since the last
  * read, and resets the log.  Nothing like it exists in the
  * reference (its timers are host wall-clock accumulators, smartVidCrop.py:98-127). */
-#define SVC_K_RESIZE 0
+#define SVC_K_RESIZE 0     /* svc_resize_frames_u8 / _nv12 */
 #define SVC_K_LANCZOS 1
 #define SVC_K_STEM 2
 #define SVC_K_PW 3
@@ -236,7 +253,7 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
 #define SVC_K_CORE 9
 #define SVC_K_PRIM 10
 #define SVC_K_FINISH 11
-#define SVC_K_RENDER 12    /* svc_render_crops_u8 */
+#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 */
 #define SVC_K_BORDER 13    /* svc_border_profile_u8 (the fused form, svc_saliency_profile_u8, counts under SVC_K_SMOOTH) */
 #define SVC_K_COUNT 14
 int svc_profile_enable(SvcHandle *h, int kernel_class);

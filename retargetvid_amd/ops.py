@@ -28,6 +28,35 @@ def _need_cuda(t, dtype, name):
 
 
 RENDER_BGR = 1                       # svc_render_crops_u8 flag (include/svc.h: SVC_RENDER_BGR)
+PIX_FMTS = ('rgb24', 'nv12')         # input pixel formats: uint8 [n,h,w,3] RGB | uint8 [n,h*3/2,w] (include/svc.h: the _nv12 entries)
+
+
+def frame_shape(pix_fmt, h, w):
+    """Shape of one frame of a h x w picture in `pix_fmt`; ValueError for an unknown format or an NV12 picture of odd size."""
+    h, w = int(h), int(w)
+    if pix_fmt == 'rgb24':
+        return (h, w, 3)
+    if pix_fmt == 'nv12':
+        if h < 2 or w < 2 or h % 2 or w % 2:
+            raise ValueError('an nv12 picture has even width and height (>= 2), not %d x %d' % (w, h))
+        return (h * 3 // 2, w)
+    raise ValueError('unknown pix_fmt %r (one of %s)' % (pix_fmt, ', '.join(PIX_FMTS)))
+
+
+def picture_size(frames, pix_fmt):
+    """(n, h, w) of the PICTURES in a frames tensor / array of `pix_fmt`; the shape is checked."""
+    shape = tuple(int(v) for v in frames.shape)
+    if pix_fmt == 'nv12':
+        if len(shape) != 3 or shape[1] % 3 or shape[1] < 3:
+            raise ValueError('nv12 frames are uint8 [n, h * 3 / 2, w], not %s' % (shape,))
+        n, h, w = shape[0], shape[1] * 2 // 3, shape[2]
+    else:
+        if len(shape) != 4 or shape[3] != 3:
+            raise ValueError('%s frames are uint8 [n, h, w, 3], not %s' % (pix_fmt, shape))
+        n, h, w = shape[:3]
+    if shape[1:] != frame_shape(pix_fmt, h, w):
+        raise ValueError('frames of shape %s are not %s frames' % (shape, pix_fmt))
+    return n, h, w
 BLEND_NEXT, MAP_HELD = 1, 2          # bits of cluster_center_'s per-map flags (include/svc.h: SVC_BLEND_NEXT, SVC_MAP_HELD)
 
 
@@ -61,18 +90,20 @@ class Engine:
             pass
 
     # -- ingest down-scale -------------------------------------------------------------
-    def resize_frames(self, frames, sh, sw):
-        """uint8 [n,h,w,3] -> uint8 [n,sh,sw,3], cv2.resize(INTER_LINEAR) semantics."""
+    def resize_frames(self, frames, sh, sw, pix_fmt='rgb24'):
+        """uint8 [n,h,w,3] -> uint8 [n,sh,sw,3], cv2.resize(INTER_LINEAR) semantics.  pix_fmt='nv12': frames uint8
+        [n,h*3/2,w], converted to RGB inside the kernel (svc_resize_frames_nv12): the bytes of the RGB call on the converted frames."""
         _need_cuda(frames, torch.uint8, 'frames')
-        n, h, w, c = frames.shape
-        assert c == 3
+        n, h, w = picture_size(frames, pix_fmt)
         out = torch.empty((n, sh, sw, 3), dtype=torch.uint8, device=frames.device)
-        _lib.check(self.lib.svc_resize_frames_u8(self._h, _ptr(frames), n, h, w, _ptr(out), sh, sw, _stream()))
+        fn = self.lib.svc_resize_frames_nv12 if pix_fmt == 'nv12' else self.lib.svc_resize_frames_u8
+        _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(out), sh, sw, _stream()))
         return out
 
     # -- rendering ------------------------------------------------------------------------
-    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None):
-        """uint8 [n,h,w,3] frames on the device and int32 [n,4] boxes (x1,y1,x2,y2, one window size for all; a CUDA tensor, or
+    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None, pix_fmt='rgb24'):
+        """uint8 [n,h,w,3] frames on the device (pix_fmt='nv12': uint8 [n,h*3/2,w], svc_render_crops_nv12; the crops are RGB / BGR
+        either way) and int32 [n,4] boxes (x1,y1,x2,y2, one window size for all; a CUDA tensor, or
         host values that are copied over) -> uint8
         [n,oh,ow,3]: frame[y1:y2, x1:x2] copied (out_hw None or the window size) or resampled to out_hw = (oh, ow) with
         cv2.resize(INTER_LINEAR) semantics; bgr: R and B swapped.  Runs on the current stream (svc_render_crops_u8)."""
@@ -87,16 +118,17 @@ class Engine:
         oh, ow = (bh, bw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
         if out is None:
             out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
-        return self._render(frames, boxes, bw, bh, out, bgr)
+        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt)
 
-    def _render(self, frames, boxes, bw, bh, out, bgr):
+    def _render(self, frames, boxes, bw, bh, out, bgr, pix_fmt='rgb24'):
         _need_cuda(frames, torch.uint8, 'frames')
         _need_cuda(boxes, torch.int32, 'boxes')
         _need_cuda(out, torch.uint8, 'out')
-        n, h, w, c = frames.shape
-        assert c == 3 and tuple(boxes.shape) == (n, 4) and out.shape[0] == n and out.shape[3] == 3
-        _lib.check(self.lib.svc_render_crops_u8(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out),
-                                                int(out.shape[1]), int(out.shape[2]), RENDER_BGR if bgr else 0, _stream()))
+        n, h, w = picture_size(frames, pix_fmt)
+        assert tuple(boxes.shape) == (n, 4) and out.shape[0] == n and out.shape[3] == 3
+        fn = self.lib.svc_render_crops_nv12 if pix_fmt == 'nv12' else self.lib.svc_render_crops_u8
+        _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out),
+                      int(out.shape[1]), int(out.shape[2]), RENDER_BGR if bgr else 0, _stream()))
         return out
 
     # -- saliency ------------------------------------------------------------------------

@@ -8,7 +8,9 @@ output size with cv2.resize(INTER_LINEAR) semantics (svc_render_crops_u8, includ
 
 The frames come from any container the ingest accepts: a host numpy array (gathered into pinned double buffers, H2D on a
 side stream: smartVidCrop._HostFeed), a pinned torch tensor (copied from where it lies), a CUDA tensor (no copy) or an
-on-device generator (synth.LazyBlobVideo: select on the device).  The crops come back through pinned double buffers on a
+on-device generator (synth.LazyBlobVideo: select on the device).  A video dict with pix_fmt='nv12' holds NV12 frames
+(uint8 [n, h * 3 / 2, w]): they are converted inside the render kernels (svc_render_crops_nv12); the crops are RGB / BGR
+either way.  The crops come back through pinned double buffers on a
 second side stream, so that the sink consumes chunk c while the device renders chunk c + 1."""
 import numpy as np
 
@@ -16,19 +18,28 @@ _MAX_CHUNK = 32
 _RING_BYTES = 96 << 20         # one output slot (device and pinned, two of each per engine): at most this many bytes
 
 
-def _container(video):
+def _container(video, pix_fmt=None):
+    """-> frames, n, h, w (the PICTURE's size), pix_fmt.  The format is the video dict's ('rgb24' when it does not say), or
+    `pix_fmt` for a bare container; a dict's NV12 container is checked against its w, h (smartVidCrop.video_pix_fmt)."""
     frames = video['frames'] if isinstance(video, dict) else video
+    if isinstance(video, dict) and (pix_fmt is not None or video.get('pix_fmt')):
+        from .smartVidCrop import video_pix_fmt
+        pix_fmt = video_pix_fmt(video if pix_fmt is None else dict(video, pix_fmt=pix_fmt))
+    pix_fmt = pix_fmt or 'rgb24'
     if hasattr(frames, 'pinned') and hasattr(frames, 'rows'):
         raise ValueError('render_video needs every frame of the video; %s holds only the frames the ingest selected'
                          % type(frames).__name__)
     if hasattr(frames, 'select') and not hasattr(frames, 'shape'):              # an on-device generator (synth.LazyBlobVideo)
-        return frames, len(frames), int(frames.h), int(frames.w)
+        return frames, len(frames), int(frames.h), int(frames.w), pix_fmt
     import torch
+    from .ops import picture_size
     if not torch.is_tensor(frames):
         frames = np.asarray(frames)
-    if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype not in (np.uint8, torch.uint8):
+    if pix_fmt == 'rgb24' and (frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype not in (np.uint8, torch.uint8)):
         raise TypeError('frames must be uint8 [n,h,w,3] RGB')
-    return frames, int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    if pix_fmt == 'nv12' and frames.dtype not in (np.uint8, torch.uint8):
+        raise TypeError('nv12 frames must be uint8 [n,h*3/2,w]')
+    return (frames,) + picture_size(frames, pix_fmt) + (pix_fmt,)
 
 
 def check_boxes(bbs, fc, h, w):
@@ -47,13 +58,15 @@ def check_boxes(bbs, fc, h, w):
     return (int(bw[0]), int(bh[0])) if fc else (0, 0)
 
 
-def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, chunk=32):
+def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, chunk=32, pix_fmt=None):
     """Render VD['fc'] frames of `video` (the ingest_pickle dict, or its 'frames' container) at VD['bbs_np'].
+    pix_fmt: the frames' format when `video` is a bare container (a dict brings its own 'pix_fmt'; default 'rgb24'); an
+    unknown format, an NV12 picture of odd size or a container of another shape raise ValueError before any device work.
     out_size: (w, h) of the output frames (None = the window size, an exact copy); bgr: R and B swapped (the reference's
     pickle mode); sink: called with every chunk uint8 [m, oh, ow, 3] (m <= chunk) in frame order -- a view of a pinned
     buffer that is refilled after the call returns, so copy what you keep.  -> numpy uint8 [fc, oh, ow, 3] without a sink,
     else None.  Boxes of unequal size or outside the frame raise ValueError before any device work."""
-    frames, n, h, w = _container(video)
+    frames, n, h, w, pix_fmt = _container(video, pix_fmt)
     fc = int(VD['fc'])
     if n < fc:
         raise ValueError('the container holds %d frames, the video has %d' % (n, fc))
@@ -79,7 +92,7 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     out = _OutRing(engine, chunk, oh, ow, sink)
 
     def emit(staged, s):
-        out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr)
+        out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr, pix_fmt)
 
     if hasattr(frames, 'select') and not hasattr(frames, 'shape'):             # on-device generator
         for s in range(0, fc, chunk):
@@ -119,13 +132,13 @@ class _OutRing:
         self.c = 0
         self.pending = None                 # (slot, frames) of the chunk whose D2H is in flight
 
-    def push(self, staged, boxes, bw, bh, bgr):
+    def push(self, staged, boxes, bw, bh, bgr, pix_fmt='rgb24'):
         m = int(staged.shape[0])
         cap = self.ring['key'][0]
         for s in range(0, m, cap):          # (a host feed stages at most 32 frames, the ring holds `chunk`)
-            self._one(staged[s:s + cap], boxes[s:s + cap], bw, bh, bgr)
+            self._one(staged[s:s + cap], boxes[s:s + cap], bw, bh, bgr, pix_fmt)
 
-    def _one(self, staged, boxes, bw, bh, bgr):
+    def _one(self, staged, boxes, bw, bh, bgr, pix_fmt='rgb24'):
         import torch
         m = int(staged.shape[0])
         slot = self.c & 1
@@ -134,7 +147,7 @@ class _OutRing:
         if self.used[slot]:
             compute.wait_event(self.copied[slot])           # the device slot's previous D2H has read it
         dst = self.ring['dev'][slot][:m]
-        self.engine._render(staged, boxes, bw, bh, dst, bgr)
+        self.engine._render(staged, boxes, bw, bh, dst, bgr, pix_fmt)
         self.rendered[slot].record(compute)
         with torch.cuda.stream(side):
             side.wait_event(self.rendered[slot])

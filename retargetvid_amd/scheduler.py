@@ -196,14 +196,14 @@ class _Lane:
         v, plan, sc = self.cur, self.cur.plan, self.sched
         frames = v.video['frames']
         n = plan['n_sel']
-        per = max(sc.chunk, min(sc.piece_frames, sc.piece_bytes // max(1, plan['h'] * plan['w'] * 3)))
+        per = max(sc.chunk, min(sc.piece_frames, sc.piece_bytes // max(1, plan['h'] * plan['w'] * 3)))     # (half the bytes as NV12: the same count)
         m = min(per, n - v.pos)
         loc = np.arange(v.pos, v.pos + m)
         net = loc[~plan['zero_map'][v.pos:v.pos + m]]
         if len(net):
             idx = [plan['true_inds'][j] for j in net]
             with torch.cuda.stream(self.stream):
-                small = S._small_frames(self.eng, frames, idx, plan['sal_h'], plan['sal_w'], self.eng.device)
+                small = S._small_frames(self.eng, frames, idx, plan['sal_h'], plan['sal_w'], self.eng.device, plan['pix_fmt'])
                 self.small[self.frames_in:self.frames_in + len(net)].copy_(small)
             self.row_of_frame[self.frames_in:self.frames_in + len(net)] = v.row0 + net
             self.frames_in += len(net)
@@ -498,7 +498,8 @@ class JobScheduler:
                         v = self.videos[i]() if callable(self.videos[i]) else self.videos[i]
                         shots = None
                         if v.get('trans_inds') is None:
-                            shots = S.detect_shots(v['frames'], v['fr'], self.CP, net=net, engine=net.eng, trans_threshold=S.TRANS_THRESHOLD)
+                            shots = S.detect_shots(v['frames'], v['fr'], self.CP, net=net, engine=net.eng, trans_threshold=S.TRANS_THRESHOLD,
+                                                   pix_fmt=S.video_pix_fmt(v))
                         else:
                             st.synchronize()                  # whatever the callable enqueued is done before a lane reads the frames
                         self._planned[i] = (v, shots)
