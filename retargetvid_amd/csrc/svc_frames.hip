@@ -1,0 +1,486 @@
+// svc_frames.hip — frame I/O for gfx950: the ingest down-scale and the renderer, on packed RGB and on NV12 frames.
+// Every kernel is written once and takes its pixels from a source (SrcRgb, SrcNv12 below); the INTER_LINEAR rule is
+// svc_cvlinear.h's.
+//
+// Reference semantics restated per kernel (paths relative to the reference tree):
+//   k_cv_resize      cv2.resize(INTER_LINEAR)         smartVidCrop.py:333-335, :633-635
+//   k_render_*       frame[by1:by2, bx1:bx2, :] (+ cv2.resize INTER_LINEAR, + RGB2BGR)  smartVidCrop.py:1801-1921
+//   SrcNv12          BT.601 conversion fused into both (no counterpart: the reference is handed RGB)
+#include <algorithm>
+
+#include "svc_cvlinear.h"
+#include "svc_internal.h"
+
+// --------------------------------------------------------------------------------------
+// loads at arbitrary addresses of a 16-aligned buffer ending at `end`, through aligned 16-byte loads
+// --------------------------------------------------------------------------------------
+// 16 bytes at a 16-aligned address; the word that runs past `end` is read bytewise, bytes at or past `end` as zero (no
+// array: every value stays in a register)
+__device__ __forceinline__ uint32_t ld4_end(const uint8_t *p, const uint8_t *end) {
+    uint32_t v = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v |= (p + i < end ? (uint32_t)p[i] : 0u) << (8 * i);
+    return v;
+}
+__device__ __forceinline__ uint4 ld16_end(const uint8_t *p, const uint8_t *end) {
+    if (p + 16 <= end) return *(const uint4 *)p;
+    return make_uint4(ld4_end(p, end), ld4_end(p + 4, end), ld4_end(p + 8, end), ld4_end(p + 12, end));
+}
+
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+
+// the 48 bytes at an arbitrary address a -> o[12] (little-endian dwords): four aligned 16-byte loads, then a funnel shift
+// by (a & 15) bytes (two dword-select stages and v_alignbyte_b32)
+__device__ __forceinline__ void ld48(const uint8_t *a, const uint8_t *end, uint32_t (&o)[12]) {
+    const uint8_t *p = (const uint8_t *)((uintptr_t)a & ~(uintptr_t)15);
+    const int s = (int)(a - p), q = s >> 2, b = s & 3;
+    // (w, u: vector values, not arrays.  hipcc turns a select between two array elements into one load at a selected
+    // address, and the array then lives in scratch -- or, promoted, in LDS -- instead of registers)
+    u32x16 w, u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint4 v = ld16_end(p + 16 * i, end);
+        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 14; ++j) u[j] = (q & 2) ? w[j + 2] : w[j];
+#pragma unroll
+    for (int j = 0; j < 13; ++j) u[j] = (q & 1) ? u[j + 1] : u[j];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) o[i] = __builtin_amdgcn_alignbyte(u[i + 1], u[i], b);
+}
+
+// The 24 bytes at an arbitrary address a -> o0, o1, o2 (little-endian qwords): two aligned 16-byte loads, one qword select
+// and a 64-bit funnel shift by (a & 7) bytes.  Bytes past the second word (the last (a & 15) - 8 of o2 when a & 15 > 8)
+// read as zero: the callers use 16 bytes (luma) or 18 from an even address (chroma).
+__device__ __forceinline__ void ld24(const uint8_t *a, const uint8_t *end, uint64_t &o0, uint64_t &o1, uint64_t &o2) {
+    const uint8_t *p = (const uint8_t *)((uintptr_t)a & ~(uintptr_t)15);
+    const int s = (int)(a - p), sh = 8 * (s & 7);
+    const uint4 v0 = ld16_end(p, end), v1 = ld16_end(p + 16, end);
+    const uint64_t a0 = v0.x | ((uint64_t)v0.y << 32), a1 = v0.z | ((uint64_t)v0.w << 32);
+    const uint64_t a2 = v1.x | ((uint64_t)v1.y << 32), a3 = v1.z | ((uint64_t)v1.w << 32);
+    const bool hi = s & 8;
+    const uint64_t b0 = hi ? a1 : a0, b1 = hi ? a2 : a1, b2 = hi ? a3 : a2, b3 = hi ? 0ull : a3;
+    o0 = sh ? (b0 >> sh) | (b1 << (64 - sh)) : b0;
+    o1 = sh ? (b1 >> sh) | (b2 << (64 - sh)) : b1;
+    o2 = sh ? (b2 >> sh) | (b3 << (64 - sh)) : b2;
+}
+
+// --------------------------------------------------------------------------------------
+// Pixel sources: what the kernels below ask of a frame format.
+//   size_ok, size_rule   the pictures the format can hold, and the words the error text says it with
+//   frame_bytes          bytes of one frame
+//   px<BGR>              pixel (y, x) of the frame at `fr` as r | g << 8 | b << 16 (BGR: b | g << 8 | r << 16), byte loads
+//   px16<BGR>            pixels x .. x + 15 of row y as 48 bytes (o[12], little-endian dwords) through aligned 16-byte loads
+//                        (the buffer is 16-aligned and ends at `end`).  x may be below 0 by less than 16 (the copy kernel's
+//                        second run): then the pixels left of the row are whatever lies there -- inside the buffer, since
+//                        row y is not its first -- and the caller masks them out.
+//   order16<BGR>         what is left to do to such 48 bytes once two runs are merged: px16 then order16 is the output's
+//                        channel order
+//   stage_row            pixels x .. x + bw - 1 of row y as RGB bytes into the LDS row `row` (span_cap bytes) by the whole
+//                        workgroup (vec: frames 16-aligned, 16-byte loads; else bytewise); returns the byte of `row` at which
+//                        they start
+// --------------------------------------------------------------------------------------
+struct SrcRgb {                                 // u8 [h][w][3]
+    static bool size_ok(int h, int w) { return h >= 1 && w >= 1; }
+    static const char *size_rule() { return ""; }
+    __host__ __device__ static size_t frame_bytes(int h, int w) { return (size_t)h * w * 3; }
+
+    template <bool BGR>
+    __device__ __forceinline__ static uint32_t px(const uint8_t *__restrict__ fr, int h, int w, int y, int x) {
+        const uint8_t *s = fr + ((size_t)y * w + x) * 3;
+        const uint32_t c0 = s[0], c1 = s[1], c2 = s[2];
+        return BGR ? c2 | (c1 << 8) | (c0 << 16) : c0 | (c1 << 8) | (c2 << 16);
+    }
+
+    // one 48-byte run of the row, as it lies there
+    template <bool BGR>
+    __device__ __forceinline__ static void px16(const uint8_t *__restrict__ fr, int h, int w, int y, int x, const uint8_t *end,
+                                                uint32_t (&o)[12]) {
+        ld48(fr + ((ptrdiff_t)y * w + x) * 3, end, o);
+    }
+
+    // BGR: a fixed byte permutation inside the group (it starts on a pixel boundary)
+    template <bool BGR>
+    __device__ __forceinline__ static void order16(uint32_t (&o)[12]) {
+        if (!BGR) return;
+        uint32_t t[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int d = 4 * i + j, c = d % 3, sb = d - c + 2 - c;      // R <-> B inside the pixel
+                v |= ((o[sb >> 2] >> (8 * (sb & 3))) & 0xffu) << (8 * j);
+            }
+            t[i] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < 12; ++i) o[i] = t[i];
+    }
+
+    // vec: the aligned 16-byte words that hold the span, so the row starts at the span's own 16-byte phase
+    __device__ __forceinline__ static int stage_row(const uint8_t *__restrict__ fr, int h, int w, int y, int x, int bw,
+                                                    uint8_t *row, int span_cap, const uint8_t *end, int vec) {
+        const uint8_t *a = fr + ((size_t)y * w + x) * 3;
+        const int span = bw * 3;
+        if (vec) {
+            const uint8_t *p = (const uint8_t *)((uintptr_t)a & ~(uintptr_t)15);
+            const int sh = (int)(a - p), nw = (sh + span + 15) >> 4;
+            for (int i = threadIdx.x; i < nw; i += 256) ((uint4 *)row)[i] = ld16_end(p + 16 * i, end);
+            return sh;
+        }
+        for (int i = threadIdx.x; i < span; i += 256) row[i] = a[i];
+        return 0;
+    }
+};
+
+// NV12 (no counterpart in the reference: its frames are decoded to RGB by OpenCV before it sees them).  A frame of a
+// height x width picture is u8 [height * 3 / 2][width]: `height` luma rows, then height / 2 rows of interleaved U V pairs;
+// pixel (y, x) takes Y[y][x] and the pair (y >> 1, x >> 1).  The conversion is BT.601 limited range in 20-bit fixed point
+// (the constants OpenCV publishes for COLOR_YUV2RGB_NV12); everything behind it -- the INTER_LINEAR arithmetic, the
+// window rules, the output layouts -- is shared with the RGB source, so the results are the RGB source's on the converted
+// frames.  Another matrix or range changes these constants and nothing else.
+#define NV12_SHIFT 20
+#define NV12_Y0 16
+#define NV12_C0 128
+#define NV12_CY 1220542
+#define NV12_CVR 1673527
+#define NV12_CVG (-852492)
+#define NV12_CUG (-409993)
+#define NV12_CUB 2116026
+
+// one pixel -> r | g << 8 | b << 16 (BGR: b | g << 8 | r << 16); int32 throughout (largest magnitude 5.7e8)
+template <bool BGR>
+__device__ __forceinline__ uint32_t nv12_rgb(int Y, int U, int V) {
+    // (__mul24: both factors fit 24 bits and the products 32, so the full-rate 24-bit multiply is exact)
+    const int yy = __mul24(max(0, Y - NV12_Y0), NV12_CY) + (1 << (NV12_SHIFT - 1)), u = U - NV12_C0, v = V - NV12_C0;
+    // clamp(x >> 20, 0, 255) taken as clamp(x, 0, 2^28 - 1) >> 20 (the same value).  Written the first way, hipcc turns two
+    // clamped shifts that are packed next to each other into one v_ashr_pk_u8_i32 and then relies on the upper half of its
+    // result being zero, which it is not on gfx950 (seen as stray bits in bytes 2 and 3 of every third output dword).
+    const int top = (256 << NV12_SHIFT) - 1;
+    const int r = min(max(yy + __mul24(NV12_CVR, v), 0), top) >> NV12_SHIFT;
+    const int g = min(max(yy + __mul24(NV12_CVG, v) + __mul24(NV12_CUG, u), 0), top) >> NV12_SHIFT;
+    const int b = min(max(yy + __mul24(NV12_CUB, u), 0), top) >> NV12_SHIFT;
+    return BGR ? (uint32_t)(b | (g << 8) | (r << 16)) : (uint32_t)(r | (g << 8) | (b << 16));
+}
+
+struct SrcNv12 {                                // u8 [h * 3 / 2][w]
+    static bool size_ok(int h, int w) { return h >= 2 && w >= 2 && !(h & 1) && !(w & 1); }       // even, >= 2
+    static const char *size_rule() { return " (height and width of an NV12 picture are even)"; }
+    __host__ __device__ static size_t frame_bytes(int h, int w) { return (size_t)(h + h / 2) * w; }
+
+    template <bool BGR>
+    __device__ __forceinline__ static uint32_t px(const uint8_t *__restrict__ fr, int h, int w, int y, int x) {
+        const uint8_t *c = fr + ((size_t)(h + (y >> 1)) * w + (x & ~1));
+        return nv12_rgb<BGR>(fr[(size_t)y * w + x], c[0], c[1]);
+    }
+
+    // the 16 luma bytes and the 18 bytes that hold their (at most nine) chroma pairs, each through two aligned 16-byte
+    // loads; the chroma index is taken from frame coordinates, so x and y may be odd
+    template <bool BGR>
+    __device__ __forceinline__ static void px16(const uint8_t *__restrict__ fr, int h, int w, int y, int x, const uint8_t *end,
+                                                uint32_t (&o)[12]) {
+        uint64_t L[3], C[3];
+        ld24(fr + ((ptrdiff_t)y * w + x), end, L[0], L[1], L[2]);
+        ld24(fr + ((ptrdiff_t)(h + (y >> 1)) * w + (x & ~1)), end, C[0], C[1], C[2]);     // (x & ~1 = 2 * (x >> 1), also for x < 0)
+        const bool odd = x & 1;
+        uint32_t p[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            // pair of pixel i = (i + odd) >> 1: i / 2 for even i, (i - 1) / 2 + odd for odd i; pair p = bytes 2 p, 2 p + 1 of C
+            const int p0 = i >> 1, p1 = (i + 1) >> 1;
+            const uint32_t h0 = (uint32_t)(C[p0 >> 2] >> (16 * (p0 & 3))) & 0xffffu, h1 = (uint32_t)(C[p1 >> 2] >> (16 * (p1 & 3))) & 0xffffu;
+            const uint32_t uv = (i & 1) && odd ? h1 : h0;
+            p[i] = nv12_rgb<BGR>((int)((L[i >> 3] >> (8 * (i & 7))) & 0xffu), (int)(uv & 0xffu), (int)(uv >> 8));
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                     // four pixels = three dwords
+            o[3 * i] = p[4 * i] | (p[4 * i + 1] << 24);
+            o[3 * i + 1] = (p[4 * i + 1] >> 8) | (p[4 * i + 2] << 16);
+            o[3 * i + 2] = (p[4 * i + 2] >> 16) | (p[4 * i + 3] << 8);
+        }
+    }
+
+    template <bool BGR>
+    __device__ __forceinline__ static void order16(uint32_t (&)[12]) {}      // converted straight to the order asked for
+
+    // the row is converted while it is staged; vec: 16 pixels per thread through px16
+    __device__ __forceinline__ static int stage_row(const uint8_t *__restrict__ fr, int h, int w, int y, int x, int bw,
+                                                    uint8_t *row, int span_cap, const uint8_t *end, int vec) {
+        if (vec) {
+            for (int g = threadIdx.x; 16 * g < bw; g += 256) {
+                uint32_t o[12];
+                px16<false>(fr, h, w, y, x + 16 * g, end, o);
+#pragma unroll
+                for (int j = 0; j < 3; ++j)                     // (the last group's words past the row's capacity are never read)
+                    if (48 * g + 16 * j + 16 <= span_cap) ((uint4 *)(row + 48 * g))[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
+            }
+        } else {
+            for (int i = threadIdx.x; i < bw; i += 256) {
+                const uint32_t v = px<false>(fr, h, w, y, x + i);
+                row[3 * i] = (uint8_t)v;
+                row[3 * i + 1] = (uint8_t)(v >> 8);
+                row[3 * i + 2] = (uint8_t)(v >> 16);
+            }
+        }
+        return 0;
+    }
+};
+
+// --------------------------------------------------------------------------------------
+// ingest down-scale: OpenCV INTER_LINEAR on u8, one thread per output pixel, the four tapped source pixels by byte loads
+// (at 4K -> 140x250 a frame is tapped at 140 000 of its 8.3 M pixels)
+// --------------------------------------------------------------------------------------
+template <class Src>
+__global__ __launch_bounds__(256) void k_cv_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                   const int *__restrict__ tab, int n, int h, int w, int oh, int ow) {
+    const CvLinear T(tab, oh, ow);
+    size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+    size_t total = (size_t)n * oh * ow;
+    if (gid >= total) return;
+    int ox = gid % ow;
+    int oy = (gid / ow) % oh;
+    int f = gid / ((size_t)ow * oh);
+    int y0, y1, b0, b1, sx, sx1, a0, a1;
+    bool inner;
+    T.row(oy, h, y0, y1, b0, b1);
+    T.col(ox, w, sx, sx1, a0, a1, inner);
+    const uint8_t *fr = in + f * Src::frame_bytes(h, w);
+    const uint32_t p00 = Src::template px<false>(fr, h, w, y0, sx), p01 = Src::template px<false>(fr, h, w, y0, sx1);
+    const uint32_t p10 = Src::template px<false>(fr, h, w, y1, sx), p11 = Src::template px<false>(fr, h, w, y1, sx1);
+    uint8_t *o = out + gid * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        o[c] = CvLinear::blend((p00 >> (8 * c)) & 0xffu, (p01 >> (8 * c)) & 0xffu, (p10 >> (8 * c)) & 0xffu, (p11 >> (8 * c)) & 0xffu,
+                               a0, a1, b0, b1, inner);
+}
+
+// the INTER_LINEAR table of (height, width) -> (sh, sw), built once per handle and size pair (the ingest's and the
+// renderer's tables are the same thing: a window of bh x bw is resampled exactly like a frame of that size)
+static int cv_tab(SvcHandle *h, int height, int width, int sh, int sw, const int **out) {
+    auto key = std::make_tuple(height, width, sh, sw);
+    auto it = h->cvtabs.find(key);
+    if (it == h->cvtabs.end()) {
+        const std::vector<int> tab = cv_linear_tab(height, width, sh, sw, (double)height / sh, (double)width / sw);
+        DevBuf buf;
+        int rc = buf.ensure(tab.size() * 4);
+        if (rc) return rc;
+        SVC_HIP(hipMemcpy(buf.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        it = h->cvtabs.emplace(key, buf).first;
+    }
+    *out = (const int *)it->second.p;
+    return SVC_OK;
+}
+
+template <class Src>
+static int resize_frames(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width, uint8_t *out,
+                         int sh, int sw, void *stream) {
+    if (!h || n < 0 || (n > 0 && (!frames || !out)) || !Src::size_ok(height, width) || sh < 1 || sw < 1) {     // n = 0: a no-op, null buffers allowed
+        svc_set_error("%s: invalid argument%s", name, Src::size_rule());
+        return SVC_E_INVALID;
+    }
+    if (n == 0) return SVC_OK;
+    SVC_HIP(hipSetDevice(h->device));
+    const int *tab = nullptr;
+    int rc = cv_tab(h, height, width, sh, sw, &tab);
+    if (rc) return rc;
+    size_t total = (size_t)n * sh * sw;
+    ProfScope ps(h, SVC_K_RESIZE, (hipStream_t)stream);
+    k_cv_resize<Src><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
+        frames, out, tab, n, height, width, sh, sw);
+    SVC_CHECK_LAUNCH();
+    return SVC_OK;
+}
+
+extern "C" int svc_resize_frames_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
+                                    uint8_t *out, int sh, int sw, void *stream) {
+    return resize_frames<SrcRgb>("svc_resize_frames_u8", h, frames, n, height, width, out, sh, sw, stream);
+}
+extern "C" int svc_resize_frames_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
+                                      uint8_t *out, int sh, int sw, void *stream) {
+    return resize_frames<SrcNv12>("svc_resize_frames_nv12", h, frames, n, height, width, out, sh, sw, stream);
+}
+
+// --------------------------------------------------------------------------------------
+// render: every frame's window (x1, y1, bw, bh) of the full frames, copied or resampled to oh x ow
+// (sc_renderer, smartVidCrop.py:1801-1921: frame[by1:by2, bx1:bx2, :] at :1910, the BGR conversion of the pickle mode :1894)
+// --------------------------------------------------------------------------------------
+// The window origin of frame f, clamped so that every source read lies inside that frame (the host checked bw <= width,
+// bh <= height); x2 / y2 of the box are not read.
+__device__ __forceinline__ void render_origin(const int32_t *__restrict__ boxes, int f, int height, int width, int bh, int bw,
+                                              int &x0, int &y0) {
+    x0 = min(max(boxes[4 * f], 0), width - bw);
+    y0 = min(max(boxes[4 * f + 1], 0), height - bh);
+}
+
+// Copy path (output size == window size), bw >= 16, frames and out 16-aligned.  The output is one packed run of pixels;
+// thread g owns output pixels [16 g, 16 g + 16) = bytes [48 g, 48 g + 48), written as three aligned 16-byte stores.  The
+// group's source is one run of 16 pixels of the window row it starts in (Src::px16), and when the group runs over the end
+// of that row, the rest comes from the next window row (of this frame or the next one) through a second run, placed so
+// that its pixel k is the first of that row, merged in by byte mask.
+template <class Src, bool BGR>
+__global__ __launch_bounds__(256) void k_render_copy(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                     const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
+                                                     long long total_px, const uint8_t *in_end) {
+    const long long p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (p0 >= total_px) return;
+    const size_t fstride = Src::frame_bytes(height, width);
+    const long long R = p0 / bw;
+    const int col = (int)(p0 - R * bw);
+    int f = (int)(R / bh), r = (int)(R - (long long)f * bh);
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    uint32_t o[12];
+    Src::template px16<BGR>(in + f * fstride, height, width, y0 + r, x0 + col, in_end, o);
+    const int k = bw - col;                                     // pixels of the group in row R
+    if (k < 16 && p0 + k < total_px) {
+        if (++r == bh) { r = 0; ++f; }
+        render_origin(boxes, f, height, width, bh, bw, x0, y0);
+        uint32_t o2[12];                                         // bytes [3k, 48) = the first pixels of the next row
+        Src::template px16<BGR>(in + f * fstride, height, width, y0 + r, x0 - k, in_end, o2);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            const int lim = 3 * k - 4 * i;                       // bytes of dword i that stay with row R
+            const uint32_t m = lim >= 4 ? 0xffffffffu : lim <= 0 ? 0u : (1u << (8 * lim)) - 1u;
+            o[i] = (o[i] & m) | (o2[i] & ~m);
+        }
+    }
+    Src::template order16<BGR>(o);
+    uint8_t *dst = out + p0 * 3;
+    if (p0 + 16 <= total_px) {
+        uint4 *d4 = (uint4 *)dst;
+        d4[0] = make_uint4(o[0], o[1], o[2], o[3]);
+        d4[1] = make_uint4(o[4], o[5], o[6], o[7]);
+        d4[2] = make_uint4(o[8], o[9], o[10], o[11]);
+    } else {
+        const int nb = (int)(total_px - p0) * 3;
+#pragma unroll
+        for (int i = 0; i < 48; ++i)
+            if (i < nb) dst[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
+    }
+}
+
+// Copy path for narrow windows (bw < 16) or unaligned buffers: one thread per output pixel, byte loads.
+template <class Src, bool BGR>
+__global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                        const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
+                                                        long long total_px) {
+    const long long px = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (px >= total_px) return;
+    const long long R = px / bw;
+    const int col = (int)(px - R * bw), f = (int)(R / bh), r = (int)(R - (long long)f * bh);
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    const uint32_t v = Src::template px<BGR>(in + f * Src::frame_bytes(height, width), height, width, y0 + r, x0 + col);
+    uint8_t *d = out + px * 3;
+    d[0] = (uint8_t)v;
+    d[1] = (uint8_t)(v >> 8);
+    d[2] = (uint8_t)(v >> 16);
+}
+
+// Resize path: k_cv_resize's arithmetic on a window of the full frame.  One workgroup = one output row of one frame: the
+// two window rows it reads are staged in LDS as RGB (Src::stage_row; R and B are never swapped before the store), the
+// output row is assembled in LDS at the output's own 16-byte phase and written with aligned 16-byte stores (the partial
+// words at both ends bytewise).  LDS: two source rows of span_cap bytes, then the output row (ow * 3 + 16 bytes).
+template <class Src, bool BGR>
+__global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                       const int *__restrict__ tab, const int32_t *__restrict__ boxes, int f0,
+                                                       int height, int width, int bh, int bw, int oh, int ow, int span_cap,
+                                                       const uint8_t *in_end, int vec) {
+    extern __shared__ __align__(16) uint8_t sm_rr[];
+    const CvLinear T(tab, oh, ow);
+    const int oy = blockIdx.x, f = f0 + blockIdx.y;
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    int ry[2], b0, b1;
+    T.row(oy, bh, ry[0], ry[1], b0, b1);
+    const uint8_t *fr = in + f * Src::frame_bytes(height, width);
+    int sh[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        sh[k] = Src::stage_row(fr, height, width, y0 + ry[k], x0, bw, sm_rr + k * span_cap, span_cap, in_end, vec);
+    uint8_t *dst = out + ((size_t)blockIdx.y * oh + oy) * ow * 3;
+    const int ph = (int)((uintptr_t)dst & 15);
+    uint8_t *orow = sm_rr + 2 * span_cap + ph;
+    __syncthreads();
+    const uint8_t *r0 = sm_rr + sh[0], *r1 = sm_rr + span_cap + sh[1];
+    for (int ox = threadIdx.x; ox < ow; ox += 256) {
+        int sx, sx1, a0, a1;
+        bool inner;
+        T.col(ox, bw, sx, sx1, a0, a1, inner);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            orow[ox * 3 + (BGR ? 2 - c : c)] = CvLinear::blend(r0[sx * 3 + c], r0[sx1 * 3 + c], r1[sx * 3 + c], r1[sx1 * 3 + c],
+                                                               a0, a1, b0, b1, inner);
+    }
+    __syncthreads();
+    // bytes [0, head) and [head + 16 * nw, ow * 3) of the row are partial 16-byte words of the output: bytewise
+    const int nb = ow * 3, head = min(nb, (16 - ph) & 15), nw = (nb - head) >> 4;
+    const uint4 *src4 = (const uint4 *)(orow + head);
+    uint4 *dst4 = (uint4 *)(dst + head);
+    for (int i = threadIdx.x; i < nw; i += 256) dst4[i] = src4[i];
+    for (int i = threadIdx.x; i < head; i += 256) dst[i] = orow[i];
+    for (int i = head + 16 * nw + threadIdx.x; i < nb; i += 256) dst[i] = orow[i];
+}
+
+template <class Src>
+static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                        int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    if (!h || n < 0 || (n > 0 && (!frames || !boxes || !out)) || !Src::size_ok(height, width) || bw < 1 || bh < 1 ||
+        bw > width || bh > height || oh < 1 || ow < 1 || (flags & ~SVC_RENDER_BGR)) {       // n = 0: a no-op, null buffers allowed
+        svc_set_error("%s: invalid argument%s", name, Src::size_rule());
+        return SVC_E_INVALID;
+    }
+    const int span_cap = (bw * 3 + 32 + 15) / 16 * 16;
+    const size_t lds = 2 * (size_t)span_cap + (size_t)ow * 3 + 16;
+    const bool copy = oh == bh && ow == bw;
+    if (!copy && lds > 65536) {
+        svc_set_error("%s: window %dx%d -> %dx%d needs %zu bytes of LDS per output row (> 64 KiB)", name, bw, bh, ow, oh, lds);
+        return SVC_E_INVALID;
+    }
+    if (n == 0) return SVC_OK;
+    SVC_HIP(hipSetDevice(h->device));
+    const bool bgr = (flags & SVC_RENDER_BGR) != 0;
+    const uint8_t *in_end = frames + n * Src::frame_bytes(height, width);
+    const bool aligned_in = ((uintptr_t)frames & 15) == 0, aligned_out = ((uintptr_t)out & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int *tab = nullptr;
+    if (!copy) {
+        int rc = cv_tab(h, bh, bw, oh, ow, &tab);
+        if (rc) return rc;
+    }
+    ProfScope ps(h, SVC_K_RENDER, s);
+    if (copy) {
+        const long long total_px = (long long)n * bh * bw;
+        if (bw >= 16 && aligned_in && aligned_out) {
+            const unsigned grid = (unsigned)((total_px + 16 * 256 - 1) / (16 * 256));
+            if (bgr) k_render_copy<Src, true><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px, in_end);
+            else k_render_copy<Src, false><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px, in_end);
+        } else {
+            const unsigned grid = (unsigned)((total_px + 255) / 256);
+            if (bgr) k_render_copy_px<Src, true><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px);
+            else k_render_copy_px<Src, false><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px);
+        }
+        SVC_CHECK_LAUNCH();
+        return SVC_OK;
+    }
+    for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
+        const int nf = std::min(n - f0, 65535);
+        uint8_t *o = out + (size_t)f0 * oh * ow * 3;
+        const dim3 grid((unsigned)oh, (unsigned)nf);
+        if (bgr) k_render_resize<Src, true><<<grid, 256, lds, s>>>(frames, o, tab, boxes, f0, height, width, bh, bw, oh, ow, span_cap, in_end, aligned_in);
+        else k_render_resize<Src, false><<<grid, 256, lds, s>>>(frames, o, tab, boxes, f0, height, width, bh, bw, oh, ow, span_cap, in_end, aligned_in);
+        SVC_CHECK_LAUNCH();
+    }
+    return SVC_OK;
+}
+
+extern "C" int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                                   int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    return render_crops<SrcRgb>("svc_render_crops_u8", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+}
+extern "C" int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                                     int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    return render_crops<SrcNv12>("svc_render_crops_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+}

@@ -1,4 +1,4 @@
-// svc_internal.h — handle layout and helpers shared by svc_net.hip / svc_tail.hip.
+// svc_internal.h — handle layout and helpers shared by svc_net.hip / svc_frames.hip / svc_tail.hip / svc_shot.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>

@@ -26,6 +26,7 @@
 #include <chrono>
 
 #include "hdb_tree.h"
+#include "svc_cvlinear.h"
 #include "svc_internal.h"
 
 #ifndef TB
@@ -205,32 +206,23 @@ __global__ __launch_bounds__(256) void k_iou(const int4 *__restrict__ a, const i
 
 // --------------------------------------------------------------------------------------
 // resize_factor != 1 (best settings): OpenCV INTER_LINEAR on single-channel u8 maps for the maps of
-// the current round, and the centre of the INTER_NEAREST-shrunk map.
-// tab (int32): xofs[ow] | xa[ow][2] | yofs[oh] | ya[oh][2] | xmax
+// the current round (svc_cvlinear.h), and the centre of the INTER_NEAREST-shrunk map.
 // --------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_map_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                     const int *__restrict__ tab, const uint16_t *__restrict__ order,
                                                     int h, int w, int oh, int ow) {
     const int f = order[blockIdx.y];
-    const int *xofs = tab, *xa = tab + ow, *yofs = tab + 3 * ow, *ya = tab + 3 * ow + oh;
-    const int xmax = tab[3 * ow + 3 * oh];
+    const CvLinear T(tab, oh, ow);
     const uint8_t *src = in + (size_t)f * h * w;
     uint8_t *dst = out + (size_t)f * oh * ow;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < oh * ow; i += gridDim.x * 256) {
         const int oy = i / ow, ox = i - oy * ow;
-        const int sy = yofs[oy];
-        const uint8_t *r0 = src + (size_t)min(max(sy, 0), h - 1) * w, *r1 = src + (size_t)min(max(sy + 1, 0), h - 1) * w;
-        const int sx = xofs[ox], sx1 = min(sx + 1, w - 1);
-        int h0, h1;
-        if (ox < xmax) {
-            h0 = r0[sx] * xa[2 * ox] + r0[sx1] * xa[2 * ox + 1];
-            h1 = r1[sx] * xa[2 * ox] + r1[sx1] * xa[2 * ox + 1];
-        } else {
-            h0 = r0[sx] * 2048;
-            h1 = r1[sx] * 2048;
-        }
-        const int v = (((ya[2 * oy] * (h0 >> 4)) >> 16) + ((ya[2 * oy + 1] * (h1 >> 4)) >> 16) + 2) >> 2;
-        dst[i] = (uint8_t)min(max(v, 0), 255);
+        int y0, y1, b0, b1, sx, sx1, a0, a1;
+        bool inner;
+        T.row(oy, h, y0, y1, b0, b1);
+        T.col(ox, w, sx, sx1, a0, a1, inner);
+        const uint8_t *r0 = src + (size_t)y0 * w, *r1 = src + (size_t)y1 * w;
+        dst[i] = CvLinear::blend(r0[sx], r0[sx1], r1[sx], r1[sx1], a0, a1, b0, b1, inner);
     }
 }
 
@@ -3043,33 +3035,8 @@ extern "C" int svc_iou_i32(const int32_t *a, const int32_t *b, size_t n, double 
     return SVC_OK;
 }
 
-// OpenCV INTER_LINEAR tables for one axis with an explicit scale (see svc_net.hip for the frame version)
-static void cv_tab_axis(int src, int dst, double scale, bool horizontal, int *ofs, int *a, int *xmax_out) {
-    int xmax = dst;
-    for (int d = 0; d < dst; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)floorf(f);
-        f -= (float)s;
-        if (horizontal) {
-            if (s < 0) { f = 0.f; s = 0; }
-            if (s + 1 >= src) {
-                xmax = std::min(xmax, d);
-                if (s >= src - 1) { f = 0.f; s = src - 1; }
-            }
-        }
-        ofs[d] = s;
-        a[2 * d] = (int)std::min(std::max(lrintf((1.f - f) * 2048.f), -32768L), 32767L);
-        a[2 * d + 1] = (int)std::min(std::max(lrintf(f * 2048.f), -32768L), 32767L);
-    }
-    if (xmax_out) *xmax_out = xmax;
-}
-
 static int upload_map_tab(DevBuf &buf, int h, int w, int oh, int ow, double sy, double sx) {
-    std::vector<int> tab(3 * ow + 3 * oh + 1);
-    int xmax = ow;
-    cv_tab_axis(w, ow, sx, true, tab.data(), tab.data() + ow, &xmax);
-    cv_tab_axis(h, oh, sy, false, tab.data() + 3 * ow, tab.data() + 3 * ow + oh, nullptr);
-    tab[3 * ow + 3 * oh] = xmax;
+    const std::vector<int> tab = cv_linear_tab(h, w, oh, ow, sy, sx);
     int rc = buf.ensure(tab.size() * 4);
     if (rc) return rc;
     SVC_HIP(hipMemcpy(buf.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));

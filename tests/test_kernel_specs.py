@@ -65,7 +65,7 @@ def test_no_half_swapping_packed_f32_instruction_in_the_library():
     tool = os.path.join(ROOT, 'tools', 'packed_f32_census.py')
     r = subprocess.run([sys.executable, tool], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert 'svc_net.hip' in r.stdout and 'svc_shot.hip' in r.stdout and 'FAIL' not in r.stdout
+    assert 'svc_net.hip' in r.stdout and 'svc_frames.hip' in r.stdout and 'svc_shot.hip' in r.stdout and 'FAIL' not in r.stdout
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, 'swap.hip')
         with open(src, 'w') as f:

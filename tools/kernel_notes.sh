@@ -1,9 +1,9 @@
 #!/bin/bash
-# Private segment / spill table of every kernel of the three device code objects (compiled from the sources with the
+# Private segment / spill table of every kernel of the four device code objects (compiled from the sources with the
 # Makefile's flags, device side only): tools/kernel_notes.sh > profiles/rNN_kernel_resources.txt
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
-for src in svc_tail svc_net svc_shot; do
+for src in svc_tail svc_net svc_frames svc_shot; do
   echo "# $src.hip: hipcc -Rpass-analysis=kernel-resource-usage (tools/kernel_resources.py)"
   python3 $R/tools/kernel_resources.py $R/retargetvid_amd/csrc/$src.hip
   echo

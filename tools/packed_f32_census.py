@@ -12,7 +12,7 @@ understood, so this tool keeps the pattern out of the build:
     packs that way carry SVC_NO_PK, svc_internal.h).  `--no-packed` compiles with -target-feature -packed-fp32-ops (the whole
     library without packed f32: 1 - 3 % slower, measured in round 6) and expects zero everywhere.
 
-usage: python tools/packed_f32_census.py [--no-packed] [--all] [file.hip ...]      (default: the three library sources)
+usage: python tools/packed_f32_census.py [--no-packed] [--all] [file.hip ...]      (default: the four library sources)
 tests/test_kernel_specs.py runs it on the library sources (about 40 s of hipcc)."""
 import os
 import re
@@ -21,7 +21,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'retargetvid_amd', 'csrc')
-DEFAULT = [os.path.join(CSRC, f) for f in ('svc_net.hip', 'svc_tail.hip', 'svc_shot.hip')]
+DEFAULT = [os.path.join(CSRC, f) for f in ('svc_net.hip', 'svc_frames.hip', 'svc_tail.hip', 'svc_shot.hip')]
 MUST_BE_SCALAR = ('k_smooth_down_mfma',)
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-ffp-contract=off', '-S', '--cuda-device-only', '-Wno-pass-failed']
 NO_PACKED = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
