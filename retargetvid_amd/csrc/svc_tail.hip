@@ -576,6 +576,14 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
     v = dpp_min_u32<0x143, 0xC>(v);      // row_bcast:31 into rows 2 and 3 -> lane 63 holds the minimum
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
+// second level of a block minimum: lanes 0..15 of every row hold one wavefront's value each; row minimum by DPP
+__device__ __forceinline__ uint32_t row16_min_u32(uint32_t v) {
+    v = dpp_min_u32<0x111, 0xF>(v);
+    v = dpp_min_u32<0x112, 0xF>(v);
+    v = dpp_min_u32<0x114, 0xF>(v);
+    v = dpp_min_u32<0x118, 0xF>(v);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 15);
+}
 
 template <int PT>
 __device__ __forceinline__ void prim_regs32(const uint32_t *__restrict__ core_g, hdb::Edge *__restrict__ mst, int N,
@@ -621,12 +629,7 @@ __device__ __forceinline__ void prim_regs32(const uint32_t *__restrict__ core_g,
         // second level: lanes 0..15 of every row hold one slot each; row minimum by DPP, the winner's
         // payload by readlane
         const uint4 t = sl[lane & (NW16 - 1)];
-        uint32_t k2 = t.x;
-        k2 = dpp_min_u32<0x111, 0xF>(k2);
-        k2 = dpp_min_u32<0x112, 0xF>(k2);
-        k2 = dpp_min_u32<0x114, 0xF>(k2);
-        k2 = dpp_min_u32<0x118, 0xF>(k2);
-        const uint32_t kmin = (uint32_t)__builtin_amdgcn_readlane((int)k2, 15);
+        const uint32_t kmin = row16_min_u32(t.x);
         const int src = __ffsll((unsigned long long)__ballot(t.x == kmin)) - 1;
         const uint32_t nidx = kmin & 0x7FFFu;
         if (tid == 0) mst[step] = hdb::Edge{(uint16_t)cur, (uint16_t)nidx, kmin >> 15};
@@ -784,6 +787,7 @@ static_assert(LVL_CAP % TB == 0, "k_prim_lvl keeps LVL_CAP / TB points per threa
 #define LVL_RING2 (RING_R * RING_R)
 #define LVL_PAD RING_R                 // the occupancy grid carries a border of empty cells: discs need no bounds tests
 #define LVL_NB 256                     // batches of tree nodes a map can have pending (then everything is settled at once)
+#define LVL_NBB 576                    // ... a big map (k_prim_lvl_big) can have pending: 36 864 nodes >= a whole 140 x 250 map (18 flag words per chunk)
 #define LVL_NEAR 64u                   // a rise whose bound exceeds this is a jump between blobs: the bound is tightened first
 
 #ifndef LVL_WORKERS
@@ -925,9 +929,10 @@ struct LvlLds {
     uint2 *slot;            // [workers][64] (drop: smallest mr below the level or NONE, lowest entrant or NONE) per candidate, per worker's share of the disc
     uint32_t *red;          // [2][NW16] block reductions (alternating halves)
     int *ctl;               // outcome of a round for the wavefronts that do not work in it: accepted, dropped, level, last node
-    uint4 *btab;            // [LVL_NB] batches of tree nodes: (start | len << 16, box, smallest core distance, -)
-    uint32_t *proc;         // [chunks][LVL_NB / 32] batch already relaxed against the chunk
+    uint4 *btab;            // [LVL_NB or LVL_NBB] batches of tree nodes: (start | len << 16, box, smallest core distance, -)
+    uint32_t *proc;         // [chunks][table size / 32] batch already relaxed against the chunk
     uint16_t *rcnt;         // [RING_R^2 + 1] ring offsets with d2 <= index
+    uint2 *stage;           // k_prim_lvl_big: [64] this wavefront's slab for a batch's tree nodes
     int gw;                 // padded grid width
 };
 
@@ -997,114 +1002,43 @@ __device__ __forceinline__ void lvl_walk(const LvlLds &S, int wave, int nk, uint
     }
 }
 
-// One batch of <= 64 tree nodes (positions start .. start + len in tnode) against one chunk of 64 points (one per
-// lane): r = min(r, max(d2, core_j, core_t)).  Every lane reads the node from LDS itself (one address for the whole
-// wavefront: a broadcast read on the LDS pipe, two nodes per ds_read_b128) -- the earlier form, nodes read once by the
-// lanes and handed round with v_readlane, spent 2 of its 6.5 VALU slots per node (+ the SGPR hazard nops) on that.
-__device__ __forceinline__ uint32_t lvl_relax_block(const LvlLds &S, int start, int len, uint32_t rcv, uint32_t cj, uint32_t r) {
-    const uint2 *tn = S.tnode + start;
-    if (len == 64) {
-#pragma unroll 4          // (8 and 16 cost the kernel its last registers: 2-3 spills)
-        for (int j = 0; j < 64; ++j) {
-            const uint2 t = tn[j];
-            const lvl_s2 d = __builtin_bit_cast(lvl_s2, rcv) - __builtin_bit_cast(lvl_s2, t.x);
-            r = min(r, max(max((uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false), cj), t.y));
-        }
-        return r;
-    }
-#pragma unroll 4
-    for (int j = 0; j < len; ++j) {
-        const uint2 t = tn[j];
-        const lvl_s2 d = __builtin_bit_cast(lvl_s2, rcv) - __builtin_bit_cast(lvl_s2, t.x);
-        r = min(r, max(max((uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false), cj), t.y));
-    }
-    return r;
+// What differs between k_prim_lvl and k_prim_lvl_big, at compile time.  Everything below that is not a body's own storage
+// set-up or rise is written once and takes one of these.
+constexpr int lvl_key_bits(int nb) { int b = 0; while ((1 << b) < nb) ++b; return b; }
+struct LvlSmall {                                  // <= LVL_CAP points: tnode / corei / rc carved from LDS, R in registers
+    static constexpr int NB = LVL_NB;              // pending-batch table
+    static constexpr bool STAGED = false;          // a batch is relaxed straight from S.tnode (LDS)
+    static constexpr bool SHORTCUTS = true;        // round 6: F words kept in registers (fkeep), the commit re-uses the probe's reads, entrants from j4
+    static constexpr bool STAMPS = true;           // SVC_PRIM_LVL=3: phase stamps -> hdr[18..22]
+};
+struct LvlBig {                                    // > LVL_CAP points: tnode / corei / rc in the frame's workspace, R in L.absw + cmin / cbx
+    static constexpr int NB = LVL_NBB;
+    static constexpr bool STAGED = true;           // a batch's nodes are staged into the wavefront's LDS slab first
+    static constexpr bool SHORTCUTS = false;       // (not ported: that is a change of behaviour and speed of its own)
+    static constexpr bool STAMPS = false;
+};
+
+// What a map's rounds carry from one to the next (registers; the rise reads and writes it too)
+struct LvlRun {
+    int cnt = 1;                                   // tree nodes so far
+    uint32_t m = 0, cur = 0;                       // level, last node added
+    bool need_rise = true;
+    int n_rounds = 0;
+    unsigned long long fkeep = 0ull;               // word `lane` of F as the F-empty test read it (maps of <= 4 096 points)
+    bool fkeep_ok = false;
+    long long ph[5] = {0, 0, 0, 0, 0}, tp = 0;     // phase stamps (10 ns units): rise, extract, probe, accept + commit, mark
+    bool stamps = false;                           // SVC_PRIM_LVL=3: phase stamps (each costs a scalar memory round trip)
+};
+template <class P>
+__device__ __forceinline__ void lvl_phase(LvlRun &st, int i) {
+    if (P::STAMPS && st.stamps) { const long long tn_ = wall_clock64(); st.ph[i] += tn_ - st.tp; st.tp = tn_; }
 }
 
-// box = rmin | rmax << 8 | cmin << 16 | cmax << 24: squared distance between two boxes (0 when they overlap)
-__device__ __forceinline__ uint32_t lvl_box_d2(uint32_t a, uint32_t b) {
-    const int ar0 = a & 255, ar1 = (a >> 8) & 255, ac0 = (a >> 16) & 255, ac1 = a >> 24;
-    const int br0 = b & 255, br1 = (b >> 8) & 255, bc0 = (b >> 16) & 255, bc1 = b >> 24;
-    const int dr = max(0, max(br0 - ar1, ar0 - br1)), dc = max(0, max(bc0 - ac1, ac0 - bc1));
-    return (uint32_t)(dr * dr + dc * dc);
-}
-
-// One sweep of a rise over one chunk: relax the pending batches whose lower bound max(box distance^2, smallest core
-// distances) is <= limit (NEAREST: only the one with the smallest bound).  proc = the chunk's "already relaxed" bits.
-template <bool NEAREST>
-__device__ __forceinline__ uint32_t lvl_sweep_chunk(const LvlLds &S, const uint4 *btab, uint32_t *proc, int nb, uint32_t limit, bool all,
-                                                    uint4 cb, uint32_t rcv, uint32_t cj, uint32_t r) {
-    const int lane = threadIdx.x & 63;
-    uint32_t bestkey = LVL_NONE;
-    for (int bb = 0; bb < nb; bb += 64) {
-        const int b = bb + lane;
-        uint32_t lb = LVL_NONE;
-        if (b < nb && !((proc[b >> 5] >> (b & 31)) & 1u)) {
-            const uint4 e = btab[b];
-            lb = all ? 0u : max(max(lvl_box_d2(e.y, cb.x), e.z), cb.y);
-        }
-        if (NEAREST) {
-            if (lb <= limit) bestkey = min(bestkey, (min(lb, 0xFFFFFFu) << 8) | (uint32_t)b);
-            continue;
-        }
-        unsigned long long todo = __ballot(lb <= limit && lb != LVL_NONE);
-        if (lane == 0 && todo) {
-            proc[bb >> 5] |= (uint32_t)todo;
-            if (bb + 32 < LVL_NB) proc[(bb >> 5) + 1] |= (uint32_t)(todo >> 32);
-        }
-        while (todo) {
-            const int b0 = bb + __builtin_ctzll(todo);
-            todo &= todo - 1ull;
-            const uint32_t sl = btab[b0].x;
-            r = lvl_relax_block(S, (int)(sl & 0xFFFFu), (int)(sl >> 16), rcv, cj, r);
-        }
-    }
-    if (NEAREST) {
-        bestkey = wave_min_u32(bestkey);
-        if (bestkey != LVL_NONE) {
-            const int b0 = (int)(bestkey & 255u);
-            if (lane == 0) proc[b0 >> 5] |= 1u << (b0 & 31);
-            const uint32_t sl = btab[b0].x;
-            r = lvl_relax_block(S, (int)(sl & 0xFFFFu), (int)(sl >> 16), rcv, cj, r);
-        }
-    }
-    return r;
-}
-
-__device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
-    uint8_t *ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
-    int32_t *hdr = (int32_t *)(ws + A.L.hdr);
-    if (!hdr[3]) return;
-    const int N = hdr[0];
-    if (N > LVL_CAP) return;                                          // k_prim_big takes it
-    extern __shared__ uint8_t sm_lvl[];
-    __shared__ int lds16[NW16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int gw = A.w + 2 * LVL_PAD, gcells = (A.h + 2 * LVL_PAD) * gw, nocc = (gcells + 31) >> 5;
-    const int NF64 = (N + 63) >> 6;
-    const int cap = min(A.h * A.w, LVL_CAP);
-    LvlLds S;
-    {
-        uint8_t *p = sm_lvl;
-        S.occ = carve<OccW>(p, nocc);
-        S.tnode = carve<uint2>(p, cap);
-        S.corei = carve<uint32_t>(p, cap);
-        S.F = carve<uint32_t>(p, (size_t)((cap + 63) / 64) * 2);
-        S.ring = carve<uint2>(p, A.n_ring);
-        S.rc = carve<uint16_t>(p, cap);
-        S.cand = carve<uint32_t>(p, 64 * LVL_WORKERS);
-        S.slot = carve<uint2>(p, 64 * LVL_WORKERS);
-        S.red = carve<uint32_t>(p, 2 * NW16);
-        S.ctl = carve<int>(p, 4);
-        S.btab = carve<uint4>(p, LVL_NB);
-        S.proc = carve<uint32_t>(p, (size_t)((cap + 63) / 64) * (LVL_NB / 32));
-        S.rcnt = carve<uint16_t>(p, LVL_RING2 + 1);
-        S.gw = gw;
-    }
-    const long long t0 = wall_clock64();
-    const uint32_t *pts = (const uint32_t *)(ws + A.L.pts);
-    const uint32_t *core_g = (const uint32_t *)(ws + A.L.core);
-    hdb::Edge *mst = (hdb::Edge *)(ws + A.L.mst);
+// The LDS set-up both kernels start with: empty occupancy grid, the ring table rewritten to grid deltas, rcnt, the points
+// scattered into the grid (and their row / col and core distance into wherever S.rc / S.corei live), points before every
+// occupancy word, point 0 as the first tree node.  Ends with a barrier.
+__device__ __forceinline__ void lvl_setup(const TailArgs &A, const LvlLds &S, int N, int nocc, const uint32_t *pts, const uint32_t *core_g, int *lds16) {
+    const int tid = threadIdx.x, gw = S.gw;
     for (int i = tid; i < nocc; i += TB) S.occ[i] = OccW{0u, 0u};
     for (int i = tid; i <= LVL_RING2; i += TB) S.rcnt[i] = A.ring_cnt[i];
     for (int i = tid; i < A.n_ring; i += TB) {
@@ -1135,6 +1069,310 @@ __device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
         S.corei[0] |= LVL_TREE;
     }
     __syncthreads();
+}
+
+// Batches of <= 64 of the tree nodes [first, cnt) -> table entries from position `at` on: (start | len << 16, box, smallest
+// core distance, -).  One wavefront per batch.
+__device__ __forceinline__ void lvl_add_batches(const LvlLds &S, int first, int cnt, int nbat, int at) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int g = wave; g < nbat; g += NW16) {
+        const int s0 = first + 64 * g, len = min(64, cnt - s0);
+        const uint2 tn = S.tnode[s0 + min(lane, len - 1)];
+        const uint32_t r = tn.x & 0xFFFFu, cc = tn.x >> 16;
+        const uint32_t rmin = wave_min_u32(r), rmax = 255u - wave_min_u32(255u - r);
+        const uint32_t cmin = wave_min_u32(cc), cmax = 255u - wave_min_u32(255u - cc);
+        const uint32_t kmin = wave_min_u32(tn.y);
+        if (lane == 0) S.btab[at + g] = make_uint4((uint32_t)s0 | ((uint32_t)len << 16), rmin | (rmax << 8) | (cmin << 16) | (cmax << 24), kmin, 0u);
+    }
+}
+
+// (box, smallest core distance) of a chunk's points that are still OUTSIDE the tree (live; not all lanes dead): tighter lower
+// bounds than the whole chunk's (a jump between blobs otherwise relaxes the finished blob's blocks again).
+// rcv = row | col << 16, cj = core word of the lane's point.
+__device__ __forceinline__ uint2 lvl_chunk_box(bool live, uint32_t rcv, uint32_t cj) {
+    const uint32_t r_ = rcv & 0xFFFFu, c_ = rcv >> 16;
+    const uint32_t rmin = wave_min_u32(live ? r_ : 255u), rmax = 255u - wave_min_u32(live ? 255u - r_ : 255u);
+    const uint32_t cmin = wave_min_u32(live ? c_ : 255u), cmax = 255u - wave_min_u32(live ? 255u - c_ : 255u);
+    const uint32_t kmin = wave_min_u32(live ? cj : LVL_RINF);
+    return make_uint2(rmin | (rmax << 8) | (cmin << 16) | (cmax << 24), kmin);
+}
+
+// Minimum over the block of every wavefront's `best` (all wavefronts get it); one barrier.  red = [2][NW16], alternating halves.
+__device__ __forceinline__ uint32_t lvl_block_min(uint32_t best, uint32_t *red2, int &parity) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    best = wave_min_u32(best);
+    uint32_t *red = red2 + parity * NW16;
+    parity ^= 1;
+    if (lane == 0) red[wave] = best;
+    __syncthreads();
+    return row16_min_u32(red[lane & (NW16 - 1)]);
+}
+
+// One batch of <= 64 tree nodes (tn[0 .. len)) against one chunk of 64 points (one per
+// lane): r = min(r, max(d2, core_j, core_t)).  Every lane reads the node from LDS itself (one address for the whole
+// wavefront: a broadcast read on the LDS pipe, two nodes per ds_read_b128) -- the earlier form, nodes read once by the
+// lanes and handed round with v_readlane, spent 2 of its 6.5 VALU slots per node (+ the SGPR hazard nops) on that.
+__device__ __forceinline__ uint32_t lvl_relax_block(const uint2 *tn, int len, uint32_t rcv, uint32_t cj, uint32_t r) {
+    if (len == 64) {
+#pragma unroll 4          // (8 and 16 cost the kernel its last registers: 2-3 spills)
+        for (int j = 0; j < 64; ++j) {
+            const uint2 t = tn[j];
+            const lvl_s2 d = __builtin_bit_cast(lvl_s2, rcv) - __builtin_bit_cast(lvl_s2, t.x);
+            r = min(r, max(max((uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false), cj), t.y));
+        }
+        return r;
+    }
+#pragma unroll 4
+    for (int j = 0; j < len; ++j) {
+        const uint2 t = tn[j];
+        const lvl_s2 d = __builtin_bit_cast(lvl_s2, rcv) - __builtin_bit_cast(lvl_s2, t.x);
+        r = min(r, max(max((uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false), cj), t.y));
+    }
+    return r;
+}
+// ... the batch of table entry word sl = start | len << 16: straight from S.tnode, or (STAGED: tnode is in global memory) after one
+// coalesced load into the wavefront's LDS slab
+template <class P>
+__device__ __forceinline__ uint32_t lvl_relax_batch(const LvlLds &S, uint32_t sl, uint32_t rcv, uint32_t cj, uint32_t r) {
+    const int start = (int)(sl & 0xFFFFu), len = (int)(sl >> 16);
+    if constexpr (P::STAGED) {
+        const int lane = threadIdx.x & 63;
+        __builtin_amdgcn_wave_barrier();                                // the slab's previous readers are done
+        S.stage[lane] = S.tnode[start + min(lane, len - 1)];
+        __builtin_amdgcn_wave_barrier();
+        return lvl_relax_block(S.stage, len, rcv, cj, r);
+    }
+    return lvl_relax_block(S.tnode + start, len, rcv, cj, r);
+}
+
+// box = rmin | rmax << 8 | cmin << 16 | cmax << 24: squared distance between two boxes (0 when they overlap)
+__device__ __forceinline__ uint32_t lvl_box_d2(uint32_t a, uint32_t b) {
+    const int ar0 = a & 255, ar1 = (a >> 8) & 255, ac0 = (a >> 16) & 255, ac1 = a >> 24;
+    const int br0 = b & 255, br1 = (b >> 8) & 255, bc0 = (b >> 16) & 255, bc1 = b >> 24;
+    const int dr = max(0, max(br0 - ar1, ar0 - br1)), dc = max(0, max(bc0 - ac1, ac0 - bc1));
+    return (uint32_t)(dr * dr + dc * dc);
+}
+
+// One sweep of a rise over one chunk: relax the pending batches whose lower bound max(box distance^2, smallest core
+// distances) is <= limit (NEAREST: only the one with the smallest bound).  proc = the chunk's "already relaxed" bits;
+// cb = lvl_chunk_box of the chunk.
+template <class P, bool NEAREST>
+__device__ __forceinline__ uint32_t lvl_sweep_chunk(const LvlLds &S, uint32_t *proc, int nb, uint32_t limit, bool all,
+                                                    uint2 cb, uint32_t rcv, uint32_t cj, uint32_t r) {
+    constexpr int KB = lvl_key_bits(P::NB);                             // index bits of the nearest-batch key
+    const int lane = threadIdx.x & 63;
+    const uint4 *btab = S.btab;
+    uint32_t bestkey = LVL_NONE;
+    for (int bb = 0; bb < nb; bb += 64) {
+        const int b = bb + lane;
+        uint32_t lb = LVL_NONE;
+        if (b < nb && !((proc[b >> 5] >> (b & 31)) & 1u)) {
+            const uint4 e = btab[b];
+            lb = all ? 0u : max(max(lvl_box_d2(e.y, cb.x), e.z), cb.y);
+        }
+        if (NEAREST) {
+            if (lb <= limit) bestkey = min(bestkey, (min(lb, 0xFFFFFFFFu >> KB) << KB) | (uint32_t)b);
+            continue;
+        }
+        unsigned long long todo = __ballot(lb <= limit && lb != LVL_NONE);
+        if (lane == 0 && todo) {
+            proc[bb >> 5] |= (uint32_t)todo;
+            if (bb + 32 < P::NB) proc[(bb >> 5) + 1] |= (uint32_t)(todo >> 32);
+        }
+        while (todo) {
+            const int b0 = bb + __builtin_ctzll(todo);
+            todo &= todo - 1ull;
+            r = lvl_relax_batch<P>(S, btab[b0].x, rcv, cj, r);
+        }
+    }
+    if (NEAREST) {
+        bestkey = wave_min_u32(bestkey);
+        if (bestkey != LVL_NONE) {
+            const int b0 = (int)(bestkey & ((1u << KB) - 1u));
+            if (lane == 0) proc[b0 >> 5] |= 1u << (b0 & 31);
+            r = lvl_relax_batch<P>(S, btab[b0].x, rcv, cj, r);
+        }
+    }
+    return r;
+}
+
+// One round at level st.m: extract the candidates, probe their discs, find the accepted prefix, commit it (edges, tree
+// membership, F, entrants), publish the outcome to the wavefronts that did not work, rebuild F after a drop, and test whether
+// F ran empty (-> st.need_rise).  Wavefronts 0 .. LVL_WORKERS - 1 work, lane i = the i-th candidate; the others only meet
+// the barriers and read the outcome (they are needed again at the next rise).  Returns false once the tree is complete: the
+// caller leaves its loop there (with the loop's own test in its place k_prim_lvl, which sits on the register ceiling, spills).
+template <class P>
+__device__ __forceinline__ bool lvl_round(const LvlLds &S, LvlRun &st, hdb::Edge *mst, int N, int NF64) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int gw = S.gw;
+    const uint32_t m = st.m;
+    const bool worker = wave < LVL_WORKERS;
+    const bool slow = m > (uint32_t)LVL_RING2;
+    const int nk = slow ? 0 : (int)S.rcnt[m];
+    const bool fast = nk <= 32 * LVL_WORKERS;                       // every worker's share of the disc fits a 32-bit entrant mask
+    int ncand = 0, a = 1;
+    uint32_t mycand = LVL_NONE, m2 = LVL_NONE, entmask = 0;
+    uint32_t rcv = 0, corev = 0, j4[4] = {0u, 0u, 0u, 0u};         // from the probe: the candidate's own row | col << 8 and core word, the points of its first four cells
+    bool dropped = false;
+    if (worker) {
+        // the first 64 members of F in index order (each worker for itself: no barrier; lvl_extract).  Round 6 (SHORTCUTS): a dependent LDS
+        // round trip costs this chain 0.2 - 0.4 us, so three of a round's were taken out: F's words come from the registers the F-empty test
+        // of the previous round read them into (fkeep: nothing writes F in between unless the level rose), the commit re-uses what the
+        // probe read of the candidate, and the entrants of the first four cells are marked from the indices the probe found.
+        uint32_t *cw = S.cand + wave * 64;
+        ncand = lvl_extract((const unsigned long long *)S.F, NF64, cw, (uint32_t *)(S.slot + wave * 64), mycand,
+                            P::SHORTCUTS && st.fkeep_ok, st.fkeep);     // (the slot rows are scratch until the probe writes them)
+        lvl_phase<P>(st, 1);
+        if (!slow) {
+            uint32_t dmin, nmin;
+            lvl_walk<false>(S, wave, nk, m, lane < ncand, mycand, gw, dmin, nmin, entmask, rcv, corev, j4);
+            S.slot[wave * 64 + lane] = make_uint2(dmin, nmin);
+        }
+    }
+    if (!slow) {
+        __syncthreads();
+        lvl_phase<P>(st, 2);
+    }
+    ++st.n_rounds;
+    if (worker) {
+        if (!slow) {
+            // ---- accepted prefix (every worker computes the same)
+            uint2 sl = S.slot[lane];
+#pragma unroll
+            for (int w2 = 1; w2 < LVL_WORKERS; ++w2) {
+                const uint2 t = S.slot[w2 * 64 + lane];
+                sl.x = min(sl.x, t.x); sl.y = min(sl.y, t.y);
+            }
+            if (lane >= ncand) sl = make_uint2(LVL_NONE, LVL_NONE);
+            const uint32_t pend = wave_prefix_min_u32(sl.y);
+            const uint32_t nextf = (uint32_t)__builtin_amdgcn_update_dpp((int)mycand, (int)mycand, 0x130, 0xF, 0xF, false);   // wave_shl:1 = the next lane's candidate
+            const bool stop = lane < ncand && (sl.x != LVL_NONE || (lane + 1 < ncand && pend < nextf));
+            const unsigned long long bal = __ballot(stop);
+            a = bal ? __builtin_ctzll(bal) + 1 : ncand;
+            m2 = (uint32_t)__builtin_amdgcn_readlane((int)sl.x, a - 1);
+            dropped = m2 != LVL_NONE;
+        }
+        // ---- commit: edges, tree membership, F
+        const uint32_t prevc = (uint32_t)__builtin_amdgcn_update_dpp((int)mycand, (int)mycand, 0x138, 0xF, 0xF, false);       // wave_shr:1 = the previous lane's
+        const bool reread = !P::SHORTCUTS || slow;                      // (a slow round has no probe)
+        if (wave == 0 && lane < a) {
+            const uint32_t from = lane == 0 ? st.cur : prevc;
+            mst[st.cnt - 1 + lane] = hdb::Edge{(uint16_t)from, (uint16_t)mycand, m};
+            const uint32_t v = reread ? (uint32_t)S.rc[mycand] : rcv;
+            const uint32_t cj = reread ? S.corei[mycand] : corev;
+            S.tnode[st.cnt + lane] = make_uint2((v & 255) | ((v >> 8) << 16), cj);
+            S.corei[mycand] = cj | LVL_TREE;
+            if (!dropped) atomicAnd(&S.F[mycand >> 5], ~(1u << (mycand & 31u)));
+        }
+        if (!slow && !dropped && fast && lane < a && entmask) {
+            // entrants of the accepted candidates: from the cells the probe remembered (SHORTCUTS: those of the first four cells from the
+            // indices it kept)
+            uint32_t em = entmask;
+            if (P::SHORTCUTS) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if ((entmask >> u) & 1u) atomicOr(&S.F[j4[u] >> 5], 1u << (j4[u] & 31u));
+                em &= ~15u;
+            }
+            const uint32_t v = P::SHORTCUTS ? rcv : (uint32_t)S.rc[mycand];
+            const uint32_t cell0 = ((v & 255) + LVL_PAD) * (uint32_t)gw + (v >> 8) + LVL_PAD;
+            while (em) {
+                const int it = __builtin_ctz(em);
+                em &= em - 1u;
+                const uint32_t cell = cell0 + S.ring[LVL_WORKERS * it + wave].y;
+                const OccW ow = S.occ[cell >> 5];
+                const uint32_t j = ow.base + (uint32_t)__popc(ow.bits & ((1u << (cell & 31u)) - 1u));
+                atomicOr(&S.F[j >> 5], 1u << (j & 31u));
+            }
+        }
+        if (dropped) for (int i = tid; i < 2 * NF64; i += 64 * LVL_WORKERS) S.F[i] = 0u;
+        if (wave == 0) {
+            const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)mycand, a - 1);
+            if (lane == 0) {
+                S.ctl[0] = a;
+                S.ctl[1] = dropped ? 1 : 0;
+                S.ctl[2] = (int)(dropped ? m2 : m);
+                S.ctl[3] = (int)last;
+            }
+        }
+    }
+    __syncthreads();
+    lvl_phase<P>(st, 3);
+    a = S.ctl[0];
+    dropped = S.ctl[1] != 0;
+    const uint32_t mnew = (uint32_t)S.ctl[2];
+    st.cur = (uint32_t)S.ctl[3];
+    st.cnt += a;
+    if (st.cnt >= N) return false;
+    if (slow) { st.need_rise = true; return true; }                      // beyond the ring table: one node, then a rise
+    if (dropped || !fast) {
+        // a drop (F is rebuilt from the last node's disc at the new, lower level) or a disc too large for the
+        // entrant masks: a second walk, now that this round's nodes carry their tree bit
+        if (worker) {
+            const bool on = dropped ? lane == a - 1 : lane < a;
+            uint32_t d_, n_, e_;
+            uint32_t r_, c_, j_[4];
+            lvl_walk<true>(S, wave, (int)S.rcnt[mnew], mnew, on, mycand, gw, d_, n_, e_, r_, c_, j_);
+        }
+        st.m = mnew;
+        __syncthreads();
+        lvl_phase<P>(st, 4);
+    }
+    // F empty -> the level rises (every wavefront reads the same words).  SHORTCUTS, maps of up to 4 096 points: the words stay in registers for
+    // the next round's extraction (no write to F lies between this read and that one unless the level rises, which clears fkeep_ok).
+    {
+        bool any = false;
+        if (P::SHORTCUTS && NF64 <= 64) {
+            st.fkeep = lane < NF64 ? ((const unsigned long long *)S.F)[lane] : 0ull;
+            any = __ballot(st.fkeep != 0ull) != 0ull;
+            st.fkeep_ok = true;
+        } else {
+            for (int wb = 0; wb < NF64; wb += 64) {
+                const int k = wb + lane;
+                any = any || (__ballot(k < NF64 && ((const unsigned long long *)S.F)[k] != 0ull) != 0ull);
+            }
+        }
+        st.need_rise = !any;
+    }
+    return true;
+}
+
+// k_prim_lvl's own part: LDS storage for the per-point state, R in LVL_PT registers per thread, the rise unrolled over them.
+__device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
+    typedef LvlSmall P;
+    uint8_t *ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
+    int32_t *hdr = (int32_t *)(ws + A.L.hdr);
+    if (!hdr[3]) return;
+    const int N = hdr[0];
+    if (N > LVL_CAP) return;                                          // k_prim_lvl_big, launched after this kernel, takes it
+    extern __shared__ uint8_t sm_lvl[];
+    __shared__ int lds16[NW16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int gw = A.w + 2 * LVL_PAD, gcells = (A.h + 2 * LVL_PAD) * gw, nocc = (gcells + 31) >> 5;
+    const int NF64 = (N + 63) >> 6;
+    const int cap = min(A.h * A.w, LVL_CAP);
+    LvlLds S;
+    {
+        uint8_t *p = sm_lvl;
+        S.occ = carve<OccW>(p, nocc);
+        S.tnode = carve<uint2>(p, cap);
+        S.corei = carve<uint32_t>(p, cap);
+        S.F = carve<uint32_t>(p, (size_t)((cap + 63) / 64) * 2);
+        S.ring = carve<uint2>(p, A.n_ring);
+        S.rc = carve<uint16_t>(p, cap);
+        S.cand = carve<uint32_t>(p, 64 * LVL_WORKERS);
+        S.slot = carve<uint2>(p, 64 * LVL_WORKERS);
+        S.red = carve<uint32_t>(p, 2 * NW16);
+        S.ctl = carve<int>(p, 4);
+        S.btab = carve<uint4>(p, LVL_NB);
+        S.proc = carve<uint32_t>(p, (size_t)((cap + 63) / 64) * (LVL_NB / 32));
+        S.rcnt = carve<uint16_t>(p, LVL_RING2 + 1);
+        S.stage = nullptr;
+        S.gw = gw;
+    }
+    const long long t0 = wall_clock64();
+    hdb::Edge *mst = (hdb::Edge *)(ws + A.L.mst);
+    lvl_setup(A, S, N, nocc, (const uint32_t *)(ws + A.L.pts), (const uint32_t *)(ws + A.L.core), lds16);
     // chunk c = 64 consecutive points; wavefront w owns chunks w, w + 16, ... (neighbouring chunks -- the ones a rise has
     // work for -- on different SIMDs); lane = point
     uint32_t R[LVL_PT];
@@ -1145,42 +1383,30 @@ __device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
         if (c < NF64)
             for (int i = lane; i < LVL_NB / 32; i += 64) S.proc[c * (LVL_NB / 32) + i] = 0u;
     }
-    int cnt = 1, done = 0, nb = 0, parity = 0;
-    uint32_t m = 0, cur = 0, swept = 0;
-    bool need_rise = true;
-    unsigned long long fkeep = 0ull;                                // word `lane` of F as the F-empty test read it (maps of <= 4 096 points)
-    bool fkeep_ok = false;
-    int n_rounds = 0, n_rises = 0;
-    long long ph[5] = {0, 0, 0, 0, 0}, tp = wall_clock64();        // phase stamps (10 ns units): rise, extract, probe, accept + commit, mark
-    const bool stamps = (A.prim_lvl & 2) != 0;                      // SVC_PRIM_LVL=3: phase stamps (each costs a scalar memory round trip)
-#define LVL_PHASE(i) do { if (stamps) { const long long tn_ = wall_clock64(); ph[i] += tn_ - tp; tp = tn_; } } while (0)
-    if (tid == 0) hdr[24] = (int)(tp - t0);
+    LvlRun st;
+    int done = 0, nb = 0, parity = 0;
+    uint32_t swept = 0;
+    int n_rises = 0;
+    st.tp = wall_clock64();
+    st.stamps = (A.prim_lvl & 2) != 0;
+    if (tid == 0) hdr[24] = (int)(st.tp - t0);
     __syncthreads();
     // minimum of R over the block (all wavefronts get it); one barrier
     auto block_min_R = [&]() -> uint32_t {
         uint32_t best = LVL_RINF;
 #pragma unroll
         for (int q = 0; q < LVL_PT; ++q) best = min(best, R[q]);
-        best = wave_min_u32(best);
-        uint32_t *red = S.red + parity * NW16;
-        parity ^= 1;
-        if (lane == 0) red[wave] = best;
-        __syncthreads();
-        uint32_t k2 = red[lane & (NW16 - 1)];
-        k2 = dpp_min_u32<0x111, 0xF>(k2);
-        k2 = dpp_min_u32<0x112, 0xF>(k2);
-        k2 = dpp_min_u32<0x114, 0xF>(k2);
-        k2 = dpp_min_u32<0x118, 0xF>(k2);
-        return (uint32_t)__builtin_amdgcn_readlane((int)k2, 15);
+        return lvl_block_min(best, S.red, parity);
     };
-    while (cnt < N) {
-        if (need_rise) {
+    while (st.cnt < N) {
+        if (st.need_rise) {
             // ---- rise: the nodes added since the last one become batches; R is caught up block by block (a batch
             // against a chunk) where the block's lower bound allows a value <= the bound; new level, new F
+            const int cnt = st.cnt;
             ++n_rises;
-            fkeep_ok = false;                                        // F is rewritten below
+            st.fkeep_ok = false;                                     // F is rewritten below
             uint32_t cjq[LVL_PT], rcq[LVL_PT];
-            uint4 cbq[LVL_PT];
+            uint2 cbq[LVL_PT];
             uint32_t qmask = 0;
 #pragma unroll
             for (int q = 0; q < LVL_PT; ++q) {
@@ -1196,14 +1422,7 @@ __device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
                     if (cjq[q] & LVL_TREE) R[q] = LVL_RINF;
                     if (__ballot(!(cjq[q] & LVL_TREE))) {
                         qmask |= 1u << q;
-                        // the box and the smallest core distance of the chunk's points that are still OUTSIDE the tree: tighter lower
-                        // bounds than the whole chunk's (a jump between blobs otherwise relaxes the finished blob's blocks again)
-                        const bool live = !(cjq[q] & LVL_TREE);
-                        const uint32_t r_ = rcq[q] & 0xFFFFu, c_ = rcq[q] >> 16;
-                        const uint32_t rmin = wave_min_u32(live ? r_ : 255u), rmax = 255u - wave_min_u32(live ? 255u - r_ : 255u);
-                        const uint32_t cmin = wave_min_u32(live ? c_ : 255u), cmax = 255u - wave_min_u32(live ? 255u - c_ : 255u);
-                        const uint32_t kmin = wave_min_u32(live ? cjq[q] : LVL_RINF);
-                        cbq[q] = make_uint4(rmin | (rmax << 8) | (cmin << 16) | (cmax << 24), kmin, 0u, 0u);
+                        cbq[q] = lvl_chunk_box(!(cjq[q] & LVL_TREE), rcq[q], cjq[q]);
                     }
                 }
             }
@@ -1214,7 +1433,7 @@ __device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
                 for (int q = 0; q < LVL_PT; ++q)
                     if (qmask & (1u << q)) {
                         const int c = q * NW16 + wave;
-                        R[q] = lvl_sweep_chunk<false>(S, S.btab, S.proc + c * (LVL_NB / 32), nb, 0u, true, cbq[q], rcq[q], cjq[q], R[q]);
+                        R[q] = lvl_sweep_chunk<P, false>(S, S.proc + c * (LVL_NB / 32), nb, 0u, true, cbq[q], rcq[q], cjq[q], R[q]);
                     }
 #pragma unroll
                 for (int q = 0; q < LVL_PT; ++q) {
@@ -1225,15 +1444,7 @@ __device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
                 swept = 0;
                 __syncthreads();                                       // every wavefront is done with the old table
             }
-            for (int g = wave; g < nnew; g += NW16) {
-                const int s0 = done + 64 * g, len = min(64, cnt - s0);
-                const uint2 tn = S.tnode[s0 + min(lane, len - 1)];
-                const uint32_t r = tn.x & 0xFFFFu, cc = tn.x >> 16;
-                const uint32_t rmin = wave_min_u32(r), rmax = 255u - wave_min_u32(255u - r);
-                const uint32_t cmin = wave_min_u32(cc), cmax = 255u - wave_min_u32(255u - cc);
-                const uint32_t kmin = wave_min_u32(tn.y);
-                if (lane == 0) S.btab[nb + g] = make_uint4((uint32_t)s0 | ((uint32_t)len << 16), rmin | (rmax << 8) | (cmin << 16) | (cmax << 24), kmin, 0u);
-            }
+            lvl_add_batches(S, done, cnt, nnew, nb);
             const bool single = cnt - done == 1;                       // one new node (the start, a jump beyond the ring table)
             if (single) {
                 // ... is relaxed against every chunk right away: the bound below is then tight and one sweep is enough
@@ -1257,7 +1468,7 @@ __device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
                 for (int q = 0; q < LVL_PT; ++q)
                     if (qmask & (1u << q)) {
                         const int c = q * NW16 + wave;
-                        R[q] = lvl_sweep_chunk<false>(S, S.btab, S.proc + c * (LVL_NB / 32), nb, single ? ub0 : min(ub0, LVL_NEAR), false, cbq[q], rcq[q], cjq[q], R[q]);
+                        R[q] = lvl_sweep_chunk<P, false>(S, S.proc + c * (LVL_NB / 32), nb, single ? ub0 : min(ub0, LVL_NEAR), false, cbq[q], rcq[q], cjq[q], R[q]);
                     }
                 swept = single ? ub0 : min(ub0, LVL_NEAR);
             }
@@ -1268,160 +1479,35 @@ __device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
                 for (int q = 0; q < LVL_PT; ++q)
                     if (qmask & (1u << q)) {
                         const int c = q * NW16 + wave;
-                        R[q] = lvl_sweep_chunk<true>(S, S.btab, S.proc + c * (LVL_NB / 32), nb, ub1, false, cbq[q], rcq[q], cjq[q], R[q]);
+                        R[q] = lvl_sweep_chunk<P, true>(S, S.proc + c * (LVL_NB / 32), nb, ub1, false, cbq[q], rcq[q], cjq[q], R[q]);
                     }
                 const uint32_t ub2 = block_min_R();
 #pragma unroll
                 for (int q = 0; q < LVL_PT; ++q)
                     if (qmask & (1u << q)) {
                         const int c = q * NW16 + wave;
-                        R[q] = lvl_sweep_chunk<false>(S, S.btab, S.proc + c * (LVL_NB / 32), nb, ub2, false, cbq[q], rcq[q], cjq[q], R[q]);
+                        R[q] = lvl_sweep_chunk<P, false>(S, S.proc + c * (LVL_NB / 32), nb, ub2, false, cbq[q], rcq[q], cjq[q], R[q]);
                     }
                 swept = max(swept, ub2);
             }
-            m = need_sweep ? block_min_R() : ub0;                      // (no sweep: nothing changed since ub0)
+            st.m = need_sweep ? block_min_R() : ub0;                   // (no sweep: nothing changed since ub0)
 #pragma unroll
             for (int q = 0; q < LVL_PT; ++q) {
                 const int c = q * NW16 + wave;
                 if (c < NF64) {
-                    const unsigned long long bal = __ballot(R[q] == m);
+                    const unsigned long long bal = __ballot(R[q] == st.m);
                     if (lane == 0) ((unsigned long long *)S.F)[c] = bal;
                 }
             }
             __syncthreads();
-            need_rise = false;
-            LVL_PHASE(0);
+            st.need_rise = false;
+            lvl_phase<P>(st, 0);
         }
-        // ---- a round.  Wavefronts 0..3 (one per SIMD) work, lane i = the i-th candidate; the others only meet the
-        // barriers and read the outcome (they are needed again at the next rise).
-        const bool worker = wave < LVL_WORKERS;
-        const bool slow = m > (uint32_t)LVL_RING2;
-        const int nk = slow ? 0 : (int)S.rcnt[m];
-        const bool fast = nk <= 32 * LVL_WORKERS;                       // every worker's share of the disc fits a 32-bit entrant mask
-        int ncand = 0, a = 1;
-        uint32_t mycand = LVL_NONE, m2 = LVL_NONE, entmask = 0;
-        uint32_t rcv = 0, corev = 0, j4[4] = {0u, 0u, 0u, 0u};         // from the probe: the candidate's own row | col << 8 and core word, the points of its first four cells
-        bool dropped = false;
-        if (worker) {
-            // the first 64 members of F in index order (each worker for itself: no barrier; lvl_extract).  Round 6: a dependent LDS round
-            // trip costs this chain 0.2 - 0.4 us, so three of a round's were taken out: F's words come from the registers the F-empty test
-            // of the previous round read them into (fkeep: nothing writes F in between unless the level rose), the commit re-uses what the
-            // probe read of the candidate, and the entrants of the first four cells are marked from the indices the probe found.
-            uint32_t *cw = S.cand + wave * 64;
-            ncand = lvl_extract((const unsigned long long *)S.F, NF64, cw, (uint32_t *)(S.slot + wave * 64), mycand, fkeep_ok, fkeep);     // (the slot rows are scratch until the probe writes them)
-            LVL_PHASE(1);
-            if (!slow) {
-                uint32_t dmin, nmin;
-                lvl_walk<false>(S, wave, nk, m, lane < ncand, mycand, gw, dmin, nmin, entmask, rcv, corev, j4);
-                S.slot[wave * 64 + lane] = make_uint2(dmin, nmin);
-            }
-        }
-        if (!slow) {
-            __syncthreads();
-            LVL_PHASE(2);
-        }
-        ++n_rounds;
-        if (worker) {
-            if (!slow) {
-                // ---- accepted prefix (every worker computes the same)
-                uint2 sl = S.slot[lane];
-#pragma unroll
-                for (int w2 = 1; w2 < LVL_WORKERS; ++w2) {
-                    const uint2 t = S.slot[w2 * 64 + lane];
-                    sl.x = min(sl.x, t.x); sl.y = min(sl.y, t.y);
-                }
-                if (lane >= ncand) sl = make_uint2(LVL_NONE, LVL_NONE);
-                const uint32_t pend = wave_prefix_min_u32(sl.y);
-                const uint32_t nextf = (uint32_t)__builtin_amdgcn_update_dpp((int)mycand, (int)mycand, 0x130, 0xF, 0xF, false);   // wave_shl:1 = the next lane's candidate
-                const bool stop = lane < ncand && (sl.x != LVL_NONE || (lane + 1 < ncand && pend < nextf));
-                const unsigned long long bal = __ballot(stop);
-                a = bal ? __builtin_ctzll(bal) + 1 : ncand;
-                m2 = (uint32_t)__builtin_amdgcn_readlane((int)sl.x, a - 1);
-                dropped = m2 != LVL_NONE;
-            }
-            // ---- commit: edges, tree membership, F
-            const uint32_t prevc = (uint32_t)__builtin_amdgcn_update_dpp((int)mycand, (int)mycand, 0x138, 0xF, 0xF, false);       // wave_shr:1 = the previous lane's
-            if (wave == 0 && lane < a) {
-                const uint32_t from = lane == 0 ? cur : prevc;
-                mst[cnt - 1 + lane] = hdb::Edge{(uint16_t)from, (uint16_t)mycand, m};
-                const uint32_t v = slow ? (uint32_t)S.rc[mycand] : rcv;           // (a slow round has no probe)
-                const uint32_t cj = slow ? S.corei[mycand] : corev;
-                S.tnode[cnt + lane] = make_uint2((v & 255) | ((v >> 8) << 16), cj);
-                S.corei[mycand] = cj | LVL_TREE;
-                if (!dropped) atomicAnd(&S.F[mycand >> 5], ~(1u << (mycand & 31u)));
-            }
-            if (!slow && !dropped && fast && lane < a && entmask) {
-                // entrants of the accepted candidates: those of the first four cells from the indices the probe kept, the others from the
-                // cells it remembered
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if ((entmask >> u) & 1u) atomicOr(&S.F[j4[u] >> 5], 1u << (j4[u] & 31u));
-                const uint32_t v = rcv;
-                const uint32_t cell0 = ((v & 255) + LVL_PAD) * (uint32_t)gw + (v >> 8) + LVL_PAD;
-                uint32_t em = entmask & ~15u;
-                while (em) {
-                    const int it = __builtin_ctz(em);
-                    em &= em - 1u;
-                    const uint32_t cell = cell0 + S.ring[LVL_WORKERS * it + wave].y;
-                    const OccW ow = S.occ[cell >> 5];
-                    const uint32_t j = ow.base + (uint32_t)__popc(ow.bits & ((1u << (cell & 31u)) - 1u));
-                    atomicOr(&S.F[j >> 5], 1u << (j & 31u));
-                }
-            }
-            if (dropped) for (int i = tid; i < 2 * NF64; i += 64 * LVL_WORKERS) S.F[i] = 0u;
-            if (wave == 0 && lane == 0) {
-                S.ctl[0] = a;
-                S.ctl[1] = dropped ? 1 : 0;
-                S.ctl[2] = (int)(dropped ? m2 : m);
-                S.ctl[3] = (int)(uint32_t)__builtin_amdgcn_readlane((int)mycand, 0);      // (placeholder, overwritten below)
-            }
-            if (wave == 0) {
-                const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)mycand, a - 1);
-                if (lane == 0) S.ctl[3] = (int)last;
-            }
-        }
-        __syncthreads();
-        LVL_PHASE(3);
-        a = S.ctl[0];
-        dropped = S.ctl[1] != 0;
-        const uint32_t mnew = (uint32_t)S.ctl[2];
-        cur = (uint32_t)S.ctl[3];
-        cnt += a;
-        if (cnt >= N) break;
-        if (slow) { need_rise = true; continue; }                       // beyond the ring table: one node, then a rise
-        if (dropped || !fast) {
-            // a drop (F is rebuilt from the last node's disc at the new, lower level) or a disc too large for the
-            // entrant masks: a second walk, now that this round's nodes carry their tree bit
-            if (worker) {
-                const bool on = dropped ? lane == a - 1 : lane < a;
-                uint32_t d_, n_, e_;
-                uint32_t r_, c_, j_[4];
-                lvl_walk<true>(S, wave, (int)S.rcnt[mnew], mnew, on, mycand, gw, d_, n_, e_, r_, c_, j_);
-            }
-            m = mnew;
-            __syncthreads();
-            LVL_PHASE(4);
-        }
-        // F empty -> the level rises (every wavefront reads the same words).  Maps of up to 4 096 points: the words stay in registers for the
-        // next round's extraction (no write to F lies between this read and that one unless the level rises, which clears fkeep_ok).
-        {
-            bool any = false;
-            if (NF64 <= 64) {
-                fkeep = lane < NF64 ? ((const unsigned long long *)S.F)[lane] : 0ull;
-                any = __ballot(fkeep != 0ull) != 0ull;
-                fkeep_ok = true;
-            } else {
-                for (int wb = 0; wb < NF64; wb += 64) {
-                    const int k = wb + lane;
-                    any = any || (__ballot(k < NF64 && ((const unsigned long long *)S.F)[k] != 0ull) != 0ull);
-                }
-            }
-            need_rise = !any;
-        }
+        if (!lvl_round<P>(S, st, mst, N, NF64)) break;
     }
     if (tid == 0) {
-        hdr[12] = (int)(wall_clock64() - t0); hdr[16] = n_rounds; hdr[17] = n_rises;
-        for (int i = 0; i < 5; ++i) hdr[18 + i] = (int)ph[i];
+        hdr[12] = (int)(wall_clock64() - t0); hdr[16] = st.n_rounds; hdr[17] = n_rises;
+        for (int i = 0; i < 5; ++i) hdr[18 + i] = (int)st.ph[i];
     }
 }
 __global__ __launch_bounds__(TB) void k_prim_lvl(TailArgs A) { prim_lvl_body(A); }
@@ -1430,14 +1516,17 @@ __global__ __launch_bounds__(TB) void k_prim_lvl(TailArgs A) { prim_lvl_body(A);
 // k_prim_lvl_big: the same rounds for maps of MORE than LVL_CAP points (up to the whole 255 x 255 grid).  Per-point state
 // does not fit in LDS there (35 000 points x (tree node 8 + core 4 + row/col 2 + reach 4 + block flags 0.5) B = 650 KB),
 // so it lives in the frame's workspace -- L2-resident, read with gathers -- and LDS keeps what every probe touches: the
-// occupancy grid, F, the ring table, the batch table, one box + minimum per chunk of 64 points.  The reach R of a chunk is
-// loaded, relaxed and stored per sweep instead of sitting in registers; a batch's 64 tree nodes are staged into a per-wave
-// LDS slab (one coalesced load) before they are broadcast to the lanes.  Same (last node, new node, weight) sequence as
-// k_prim_lvl and the library (tests: test_tail_maximum_size_all_pixels_set, the 288-map comparison with the one-node-per-step
-// kernels, tools/soak_tail.py).  Replaces the one-node-per-step k_prim_big (3 171 spilled VGPRs; 12 ms per map at N = 10 k,
-// 3.3 s at 25 k: profiles/r04_tail_vs_N.txt) on the default path.
+// occupancy grid, F, the ring table, the batch table, one box + minimum per chunk of 64 points.
+//   shared with k_prim_lvl (one implementation, policy LvlBig): the set-up, the batch-table entries, the chunk boxes, the block
+//           minimum, lvl_sweep_chunk and the whole round (lvl_round: extract, probe, accepted prefix, commit, rebuild, F-empty test).
+//   its own: where the state lives (below), and the rise -- the reach R of a chunk is loaded, relaxed and stored per sweep (sweep_all)
+//           instead of sitting in registers, a batch's 64 tree nodes are staged into a per-wave LDS slab (one coalesced load) before
+//           they are broadcast to the lanes, and more new nodes than the batch table holds are entered a table at a time.
+// Same (last node, new node, weight) sequence as k_prim_lvl and the library (tests: test_tail_maximum_size_all_pixels_set, the
+// 288-map comparison with the one-node-per-step kernels, the four maps around LVL_CAP, tools/soak_tail.py).  Replaces the
+// one-node-per-step k_prim_big (3 171 spilled VGPRs; 12 ms per map at N = 10 k, 3.3 s at 25 k: profiles/r04_tail_vs_N.txt) on
+// the default path.
 // --------------------------------------------------------------------------------------
-#define LVL_NBB 576                    // batches of tree nodes a big map can have pending: 36 864 nodes >= a whole 140 x 250 map (18 flag words per chunk)
 static size_t lvl_big_lds_bytes(int h, int w, int n_ring) {
     const size_t cap = (size_t)h * w;
     const size_t cells = (size_t)(h + 2 * LVL_PAD) * (w + 2 * LVL_PAD);
@@ -1448,56 +1537,8 @@ static size_t lvl_big_lds_bytes(int h, int w, int n_ring) {
            up(nf * (LVL_NBB / 32) * 4) + 64;
 }
 
-// lvl_sweep_chunk with the batch staged through the wave's LDS slab (tnode is in global memory here)
-template <bool NEAREST>
-__device__ __forceinline__ uint32_t lvl_sweep_chunk_big(const LvlLds &S, uint2 *stage, const uint4 *btab, uint32_t *proc, int nb, uint32_t limit,
-                                                        bool all, uint2 cb, uint32_t rcv, uint32_t cj, uint32_t r) {
-    const int lane = threadIdx.x & 63;
-    LvlLds T = S;
-    T.tnode = stage;
-    auto relax = [&](int b0) {
-        const uint32_t sl = btab[b0].x;
-        const int start = (int)(sl & 0xFFFFu), len = (int)(sl >> 16);
-        __builtin_amdgcn_wave_barrier();                                // the slab's previous readers are done
-        stage[lane] = S.tnode[start + min(lane, len - 1)];
-        __builtin_amdgcn_wave_barrier();
-        r = lvl_relax_block(T, 0, len, rcv, cj, r);
-    };
-    uint32_t bestkey = LVL_NONE;
-    for (int bb = 0; bb < nb; bb += 64) {
-        const int b = bb + lane;
-        uint32_t lb = LVL_NONE;
-        if (b < nb && !((proc[b >> 5] >> (b & 31)) & 1u)) {
-            const uint4 e = btab[b];
-            lb = all ? 0u : max(max(lvl_box_d2(e.y, cb.x), e.z), cb.y);
-        }
-        if (NEAREST) {
-            if (lb <= limit) bestkey = min(bestkey, (min(lb, 0x3FFFFFu) << 10) | (uint32_t)b);
-            continue;
-        }
-        unsigned long long todo = __ballot(lb <= limit && lb != LVL_NONE);
-        if (lane == 0 && todo) {
-            proc[bb >> 5] |= (uint32_t)todo;
-            if (bb + 32 < LVL_NBB) proc[(bb >> 5) + 1] |= (uint32_t)(todo >> 32);
-        }
-        while (todo) {
-            const int b0 = bb + __builtin_ctzll(todo);
-            todo &= todo - 1ull;
-            relax(b0);
-        }
-    }
-    if (NEAREST) {
-        bestkey = wave_min_u32(bestkey);
-        if (bestkey != LVL_NONE) {
-            const int b0 = (int)(bestkey & 1023u);
-            if (lane == 0) proc[b0 >> 5] |= 1u << (b0 & 31);
-            relax(b0);
-        }
-    }
-    return r;
-}
-
 __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
+    typedef LvlBig P;
     uint8_t *ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
     int32_t *hdr = (int32_t *)(ws + A.L.hdr);
     if (!hdr[3]) return;
@@ -1512,7 +1553,6 @@ __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
     LvlLds S;
     uint2 *cbx;                 // per chunk: box of its points outside the tree, their smallest core distance (LVL_NONE: none left)
     uint32_t *cmin;             // per chunk: minimum of R
-    uint2 *stage;               // [NW16][64] a batch's tree nodes, per wavefront
     {
         uint8_t *p = sm_lvl;
         S.occ = carve<OccW>(p, nocc);
@@ -1526,7 +1566,7 @@ __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
         S.rcnt = carve<uint16_t>(p, LVL_RING2 + 1);
         cbx = carve<uint2>(p, capf);
         cmin = carve<uint32_t>(p, capf);
-        stage = carve<uint2>(p, NW16 * 64);
+        S.stage = carve<uint2>(p, NW16 * 64) + wave * 64;                // [NW16][64] a batch's tree nodes, per wavefront
         S.proc = carve<uint32_t>(p, (size_t)capf * (LVL_NBB / 32));     // [chunks][LVL_NBB / 32] batch already relaxed against the chunk
         S.gw = gw;
     }
@@ -1535,63 +1575,26 @@ __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
     S.corei = (uint32_t *)(ws + A.L.reach);
     S.rc = (uint16_t *)(ws + A.L.sp);
     uint32_t *Rg = (uint32_t *)(ws + A.L.absw);
-    uint2 *mystage = stage + wave * 64;
     const long long t0 = wall_clock64();
-    const uint32_t *pts = (const uint32_t *)(ws + A.L.pts);
-    const uint32_t *core_g = (const uint32_t *)(ws + A.L.core);
     hdb::Edge *mst = (hdb::Edge *)(ws + A.L.mst);
-    for (int i = tid; i < nocc; i += TB) S.occ[i] = OccW{0u, 0u};
-    for (int i = tid; i <= LVL_RING2; i += TB) S.rcnt[i] = A.ring_cnt[i];
-    for (int i = tid; i < A.n_ring; i += TB) {
-        const uint32_t o = A.ring[i];
-        S.ring[i] = make_uint2(o >> 16, (uint32_t)(((int)(o & 255) - 128) * gw + ((int)((o >> 8) & 255) - 128)));
-    }
-    __syncthreads();
-    for (int p = tid; p < N; p += TB) {
-        const uint32_t v = pts[p];
-        S.rc[p] = (uint16_t)(v & 0xFFFFu);
-        S.corei[p] = core_g[p];
-        Rg[p] = LVL_RINF;
-        const int cell = ((int)(v & 255) + LVL_PAD) * gw + (int)((v >> 8) & 255) + LVL_PAD;
-        atomicOr(&S.occ[cell >> 5].bits, 1u << (cell & 31));
-    }
+    for (int p = tid; p < N; p += TB) Rg[p] = LVL_RINF;
     for (int c = tid; c < NF64; c += TB) cmin[c] = LVL_RINF;
     for (int i = tid; i < NF64 * (LVL_NBB / 32); i += TB) S.proc[i] = 0u;
-    __syncthreads();
-    {
-        const int per = (nocc + TB - 1) / TB, lo = min(nocc, tid * per), hi = min(nocc, lo + per);
-        int mine = 0;
-        for (int i = lo; i < hi; ++i) mine += __popc(S.occ[i].bits);
-        int tot;
-        int ex = block_excl_scan(mine, lds16, &tot);
-        for (int i = lo; i < hi; ++i) { S.occ[i].base = (uint32_t)ex; ex += __popc(S.occ[i].bits); }
-    }
-    if (tid == 0) {
-        const uint32_t v = S.rc[0];
-        S.tnode[0] = make_uint2((v & 255) | ((v >> 8) << 16), S.corei[0]);
-        S.corei[0] |= LVL_TREE;
-    }
-    __syncthreads();
-    int cnt = 1, done = 0, nb = 0, parity = 0;
-    uint32_t m = 0, cur = 0, swept = 0;
-    bool need_rise = true;
-    int n_rounds = 0, n_rises = 0;
+    lvl_setup(A, S, N, nocc, (const uint32_t *)(ws + A.L.pts), (const uint32_t *)(ws + A.L.core), lds16);
+    // Placement pad.  This kernel's time moves by up to 1.6 % with the position of the code below modulo 32 bytes (measured by padding
+    // the SAME source 8 .. 48 bytes here: profiles/tail_prim_refactor_resources.txt); 16 bytes puts it where the set-up's present length
+    // would otherwise not.  Re-measure when the set-up above changes length.
+    asm volatile(".rept 4\n s_nop 0\n .endr");
+    LvlRun st;
+    int done = 0, nb = 0, parity = 0;
+    uint32_t swept = 0;
+    int n_rises = 0;
     if (tid == 0) hdr[24] = (int)(wall_clock64() - t0);
     // minimum of cmin over the block (all wavefronts get it); one barrier
     auto block_min_R = [&]() -> uint32_t {
         uint32_t best = LVL_RINF;
         for (int c = wave + lane * NW16; c < NF64; c += 64 * NW16) best = min(best, cmin[c]);      // this wavefront's own chunks
-        best = wave_min_u32(best);
-        uint32_t *red = S.red + parity * NW16;
-        parity ^= 1;
-        if (lane == 0) red[wave] = best;
-        __syncthreads();
-        uint32_t k2 = red[lane & (NW16 - 1)];
-        k2 = dpp_min_u32<0x111, 0xF>(k2);
-        k2 = dpp_min_u32<0x112, 0xF>(k2);
-        k2 = dpp_min_u32<0x114, 0xF>(k2);
-        k2 = dpp_min_u32<0x118, 0xF>(k2);
-        return (uint32_t)__builtin_amdgcn_readlane((int)k2, 15);
+        return lvl_block_min(best, S.red, parity);
     };
     // one sweep over this wavefront's chunks that still hold points outside the tree: R is loaded, relaxed, stored
     auto sweep_all = [&](int mode, uint32_t limit, bool all) {      // mode 0: every batch within the limit, 1: the nearest one
@@ -1608,16 +1611,17 @@ __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
             }
             uint32_t *proc = S.proc + c * (LVL_NBB / 32);
             const uint32_t r0 = r;
-            if (mode == 0) r = lvl_sweep_chunk_big<false>(S, mystage, S.btab, proc, nb, limit, all, cb, rcv, cj, r);
-            else r = lvl_sweep_chunk_big<true>(S, mystage, S.btab, proc, nb, limit, all, cb, rcv, cj, r);
+            if (mode == 0) r = lvl_sweep_chunk<P, false>(S, proc, nb, limit, all, cb, rcv, cj, r);
+            else r = lvl_sweep_chunk<P, true>(S, proc, nb, limit, all, cb, rcv, cj, r);
             if (cj & LVL_TREE) r = LVL_RINF;
             if (p < N && r != r0) Rg[p] = r;
             const uint32_t mn = wave_min_u32(r);
             if (lane == 0) cmin[c] = mn;
         }
     };
-    while (cnt < N) {
-        if (need_rise) {
+    while (st.cnt < N) {
+        if (st.need_rise) {
+            const int cnt = st.cnt;
             ++n_rises;
             // per chunk: tree members get an infinite reach; box and smallest core distance of the points still outside
             for (int c = wave; c < NF64; c += NW16) {
@@ -1636,28 +1640,10 @@ __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
                 }
                 const uint32_t mn = wave_min_u32(r);
                 uint2 cb = make_uint2(0u, LVL_NONE);
-                if (__ballot(live)) {
-                    const uint32_t r_ = rcv & 0xFFFFu, c_ = rcv >> 16;
-                    const uint32_t rmin = wave_min_u32(live ? r_ : 255u), rmax = 255u - wave_min_u32(live ? 255u - r_ : 255u);
-                    const uint32_t cmn = wave_min_u32(live ? c_ : 255u), cmx = 255u - wave_min_u32(live ? 255u - c_ : 255u);
-                    const uint32_t kmin = wave_min_u32(live ? cj : LVL_RINF);
-                    cb = make_uint2(rmin | (rmax << 8) | (cmn << 16) | (cmx << 24), kmin);
-                }
+                if (__ballot(live)) cb = lvl_chunk_box(live, rcv, cj);
                 if (lane == 0) { cbx[c] = cb; cmin[c] = mn; }
             }
             __builtin_amdgcn_wave_barrier();
-            // batches of <= 64 of the nodes [first, cnt) -> table entries from position `at` on
-            auto add_batches = [&](int first, int nbat, int at) {
-                for (int g = wave; g < nbat; g += NW16) {
-                    const int s0 = first + 64 * g, len = min(64, cnt - s0);
-                    const uint2 tn = S.tnode[s0 + min(lane, len - 1)];
-                    const uint32_t r = tn.x & 0xFFFFu, cc = tn.x >> 16;
-                    const uint32_t rmin = wave_min_u32(r), rmax = 255u - wave_min_u32(255u - r);
-                    const uint32_t cmn = wave_min_u32(cc), cmx = 255u - wave_min_u32(255u - cc);
-                    const uint32_t kmin = wave_min_u32(tn.y);
-                    if (lane == 0) S.btab[at + g] = make_uint4((uint32_t)s0 | ((uint32_t)len << 16), rmin | (rmax << 8) | (cmn << 16) | (cmx << 24), kmin, 0u);
-                }
-            };
             int nnew = (cnt - done + 63) >> 6;
             while (nb + nnew > LVL_NBB) {
                 // table full: settle every pending block, start afresh (N^2 work: the table is sized so that a 140 x 250 map never
@@ -1671,14 +1657,14 @@ __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
                     __syncthreads();                                   // every wavefront is done with the old table
                 }
                 if (nnew > LVL_NBB) {
-                    add_batches(done, LVL_NBB, 0);
+                    lvl_add_batches(S, done, cnt, LVL_NBB, 0);
                     nb = LVL_NBB;
                     done += 64 * LVL_NBB;
                     nnew -= LVL_NBB;
                     __syncthreads();                                   // the table is published
                 }
             }
-            add_batches(done, nnew, nb);
+            lvl_add_batches(S, done, cnt, nnew, nb);
             const bool single = cnt - done == 1;                       // one new node (the start, a jump beyond the ring table)
             if (single) {
                 const uint2 tn = S.tnode[done];
@@ -1719,117 +1705,21 @@ __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
                 sweep_all(0, ub2, false);
                 swept = max(swept, ub2);
             }
-            m = need_sweep ? block_min_R() : ub0;
+            st.m = need_sweep ? block_min_R() : ub0;
             for (int c = wave; c < NF64; c += NW16) {
                 unsigned long long bal = 0ull;
-                if (cmin[c] == m) {
+                if (cmin[c] == st.m) {
                     const int p = c * 64 + lane;
-                    bal = __ballot(p < N && Rg[p] == m);
+                    bal = __ballot(p < N && Rg[p] == st.m);
                 }
                 if (lane == 0) ((unsigned long long *)S.F)[c] = bal;
             }
             __syncthreads();
-            need_rise = false;
+            st.need_rise = false;
         }
-        // ---- a round (as in prim_lvl_body)
-        const bool worker = wave < LVL_WORKERS;
-        const bool slow = m > (uint32_t)LVL_RING2;
-        const int nk = slow ? 0 : (int)S.rcnt[m];
-        const bool fast = nk <= 32 * LVL_WORKERS;
-        int ncand = 0, a = 1;
-        uint32_t mycand = LVL_NONE, m2 = LVL_NONE, entmask = 0;
-        bool dropped = false;
-        if (worker) {
-            uint32_t *cw = S.cand + wave * 64;
-            ncand = lvl_extract((const unsigned long long *)S.F, NF64, cw, (uint32_t *)(S.slot + wave * 64), mycand);     // (the slot rows are scratch until the probe writes them)
-            if (!slow) {
-                uint32_t dmin, nmin;
-                uint32_t r_, c_, j_[4];
-                lvl_walk<false>(S, wave, nk, m, lane < ncand, mycand, gw, dmin, nmin, entmask, r_, c_, j_);
-                S.slot[wave * 64 + lane] = make_uint2(dmin, nmin);
-            }
-        }
-        if (!slow) __syncthreads();
-        ++n_rounds;
-        if (worker) {
-            if (!slow) {
-                uint2 sl = S.slot[lane];
-#pragma unroll
-                for (int w2 = 1; w2 < LVL_WORKERS; ++w2) {
-                    const uint2 t = S.slot[w2 * 64 + lane];
-                    sl.x = min(sl.x, t.x); sl.y = min(sl.y, t.y);
-                }
-                if (lane >= ncand) sl = make_uint2(LVL_NONE, LVL_NONE);
-                const uint32_t pend = wave_prefix_min_u32(sl.y);
-                const uint32_t nextf = (uint32_t)__builtin_amdgcn_update_dpp((int)mycand, (int)mycand, 0x130, 0xF, 0xF, false);
-                const bool stop = lane < ncand && (sl.x != LVL_NONE || (lane + 1 < ncand && pend < nextf));
-                const unsigned long long bal = __ballot(stop);
-                a = bal ? __builtin_ctzll(bal) + 1 : ncand;
-                m2 = (uint32_t)__builtin_amdgcn_readlane((int)sl.x, a - 1);
-                dropped = m2 != LVL_NONE;
-            }
-            const uint32_t prevc = (uint32_t)__builtin_amdgcn_update_dpp((int)mycand, (int)mycand, 0x138, 0xF, 0xF, false);
-            if (wave == 0 && lane < a) {
-                const uint32_t from = lane == 0 ? cur : prevc;
-                mst[cnt - 1 + lane] = hdb::Edge{(uint16_t)from, (uint16_t)mycand, m};
-                const uint32_t v = S.rc[mycand];
-                const uint32_t cj = S.corei[mycand];
-                S.tnode[cnt + lane] = make_uint2((v & 255) | ((v >> 8) << 16), cj);
-                S.corei[mycand] = cj | LVL_TREE;
-                if (!dropped) atomicAnd(&S.F[mycand >> 5], ~(1u << (mycand & 31u)));
-            }
-            if (!slow && !dropped && fast && lane < a && entmask) {
-                const uint32_t v = S.rc[mycand];
-                const uint32_t cell0 = ((v & 255) + LVL_PAD) * (uint32_t)gw + (v >> 8) + LVL_PAD;
-                uint32_t em = entmask;
-                while (em) {
-                    const int it = __builtin_ctz(em);
-                    em &= em - 1u;
-                    const uint32_t cell = cell0 + S.ring[LVL_WORKERS * it + wave].y;
-                    const OccW ow = S.occ[cell >> 5];
-                    const uint32_t j = ow.base + (uint32_t)__popc(ow.bits & ((1u << (cell & 31u)) - 1u));
-                    atomicOr(&S.F[j >> 5], 1u << (j & 31u));
-                }
-            }
-            if (dropped) for (int i = tid; i < 2 * NF64; i += 64 * LVL_WORKERS) S.F[i] = 0u;
-            if (wave == 0) {
-                const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)mycand, a - 1);
-                if (lane == 0) {
-                    S.ctl[0] = a;
-                    S.ctl[1] = dropped ? 1 : 0;
-                    S.ctl[2] = (int)(dropped ? m2 : m);
-                    S.ctl[3] = (int)last;
-                }
-            }
-        }
-        __syncthreads();
-        a = S.ctl[0];
-        dropped = S.ctl[1] != 0;
-        const uint32_t mnew = (uint32_t)S.ctl[2];
-        cur = (uint32_t)S.ctl[3];
-        cnt += a;
-        if (cnt >= N) break;
-        if (slow) { need_rise = true; continue; }
-        if (dropped || !fast) {
-            if (worker) {
-                const bool on = dropped ? lane == a - 1 : lane < a;
-                uint32_t d_, n_, e_;
-                uint32_t r_, c_, j_[4];
-                lvl_walk<true>(S, wave, (int)S.rcnt[mnew], mnew, on, mycand, gw, d_, n_, e_, r_, c_, j_);
-            }
-            m = mnew;
-            __syncthreads();
-        }
-        {
-            bool any = false;
-            for (int wb = 0; wb < NF64; wb += 64) {
-                const int k = wb + lane;
-                any = any || (__ballot(k < NF64 && ((const unsigned long long *)S.F)[k] != 0ull) != 0ull);
-            }
-            need_rise = !any;
-        }
+        if (!lvl_round<P>(S, st, mst, N, NF64)) break;
     }
-    if (tid == 0) { hdr[12] = (int)(wall_clock64() - t0); hdr[16] = n_rounds; hdr[17] = n_rises; }
+    if (tid == 0) { hdr[12] = (int)(wall_clock64() - t0); hdr[16] = st.n_rounds; hdr[17] = n_rises; }
 }
 __global__ __launch_bounds__(TB) void k_prim_lvl_big(TailArgs A) { prim_lvl_big_body(A); }
 

@@ -492,6 +492,63 @@ def test_maps_beyond_8192_points_new_kernels_equal_the_round2_kernels_and_the_or
         old.close()
 
 
+def _round2_engine():
+    """An engine on the one-node-per-step Prim and the serial hierarchy, one kernel per stage (the second device reference)."""
+    import os
+    saved = {k: os.environ.get(k) for k in ('SVC_PRIM_LVL', 'SVC_TREE_PAR', 'SVC_TAIL_MERGE')}
+    try:
+        os.environ.update(SVC_PRIM_LVL='0', SVC_TREE_PAR='0', SVC_TAIL_MERGE='0')
+        return ops.Engine(seed=0)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _noise_map_with_n_points(rng, h, w, dens, n):
+    """Dense noise with random pixels cleared or set until exactly n are set."""
+    m = rng.rand(h, w) < dens
+    while int(m.sum()) != n:
+        want = int(m.sum()) < n                                            # set a cleared pixel, or clear a set one
+        ys, xs = np.nonzero(m != want)
+        k = rng.randint(len(ys))
+        m[ys[k], xs[k]] = want
+    return (m * 200).astype(np.uint8)
+
+
+def test_the_seam_between_k_prim_lvl_and_k_prim_lvl_big_at_8192_points(engine):
+    """The two Prim-in-rounds kernels share their round and differ in where the state lives; a map picks its kernel by N.  Four
+    96 x 96 maps of dense noise with exactly LVL_CAP - 1, LVL_CAP, LVL_CAP + 1 and LVL_CAP + 64 points in ONE call (9 216 cells:
+    k_prim_lvl_big is launched, the first two maps are k_prim_lvl's), with and without cut-blend flags, both parameter sets,
+    against the round-2 kernels: maps, stats, centres, Prim edge list, labels identical; the 8 193-point map also against the
+    oracle (~10 s of host time)."""
+    rng = np.random.RandomState(8192)
+    counts = (8191, 8192, 8193, 8256)
+    maps = np.stack([_noise_map_with_n_points(rng, 96, 96, 0.9, n) for n in counts])
+    old = _round2_engine()
+    try:
+        for CP in (P.init_crop_params(), dict(P.init_crop_params(), hdbscan_min=5, hdbscan_min_samples=3, select_sum=1)):
+            for flags in (np.array([1, 0, 1, 0], np.uint8), None):
+                a, b = torch.from_numpy(maps).cuda(), torch.from_numpy(maps).cuda()
+                xa, sa = old.cluster_center_(a, flags, CP, want_stats=True)
+                xb, sb = engine.cluster_center_(b, flags, CP, want_stats=True)
+                assert torch.equal(a, b) and torch.equal(sa, sb)
+                assert np.array_equal(xa.cpu().numpy(), xb.cpu().numpy(), equal_nan=True)
+                if flags is None:
+                    assert tuple(int(n) for n in sb[:, 0]) == counts
+                for i in range(4):
+                    s_old, s_new = old.cluster_state(i, 96 * 96), engine.cluster_state(i, 96 * 96)
+                    assert np.array_equal(s_old['mst'], s_new['mst']), 'Prim sequence of map %d (N = %d)' % (i, s_old['n'])
+                    assert np.array_equal(s_old['labels'], s_new['labels']), 'labels of map %d' % i
+                    assert s_new['hdr'][16] > 0                                # Prim in rounds, either kernel
+            if CP['hdbscan_min'] == 26:
+                _state_is_the_oracles(engine, 2, maps[2], CP)                  # (the last call had no flags: map 2 is the 8 193-point one)
+    finally:
+        old.close()
+
+
 def test_largest_geometries_up_to_65025_points_equal_the_round2_kernels(engine):
     """What a 140 x 250 map cannot reach: more new tree nodes than k_prim_lvl_big's batch table holds (> 36 864 since the last
     rise), the fourth level of the hierarchy's nearest-greater search (> 8 192 x 4 edges), a 255 x 255 map with every pixel set

@@ -17,6 +17,6 @@ for src in sys.argv[1:]:
             rows[cur][k] = v
     for name, r in rows.items():
         dem = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
-        print('%-64s vgpr %-4s agpr %-3s spill %-3s sgpr %-4s lds %-6s occ %s' % (
-            re.sub(r'^void ', '', dem.split('(')[0])[:64], r.get('VGPRs'), r.get('AGPRs'), r.get('VGPRs Spill'), r.get('SGPRs'),
+        print('%-64s vgpr %-4s agpr %-3s spill %-3s scratch %-4s sgpr %-4s lds %-6s occ %s' % (
+            re.sub(r'^void ', '', dem.split('(')[0])[:64], r.get('VGPRs'), r.get('AGPRs'), r.get('VGPRs Spill'), r.get('ScratchSize [bytes/lane]'), r.get('SGPRs'),
             r.get('LDS Size [bytes/block]'), r.get('Occupancy [waves/SIMD]')))
