@@ -79,8 +79,9 @@ const char *svc_last_error(void);
  * 6 = svc_render_crops_u8 (SVC_RENDER_BGR) and the profile class SVC_K_RENDER exist.
  * 7 = svc_debug_transnet_tap (SVC_SHOT_TAP_*) exists; svc_create rejects SVC_SHOT_M16 outside 2..4 with SVC_E_INVALID.
  * 8 = svc_border_profile_u8, svc_saliency_profile_u8 and the profile class SVC_K_BORDER exist.
- * 9 = svc_resize_frames_nv12 and svc_render_crops_nv12 exist (NV12 input). */
-#define SVC_ABI_VERSION 9
+ * 9 = svc_resize_frames_nv12 and svc_render_crops_nv12 exist (NV12 input).
+ * 10 = svc_render_crops_u8_to_nv12 and svc_render_crops_nv12_to_nv12 exist (NV12 output). */
+#define SVC_ABI_VERSION 10
 int svc_abi_version(void);
 
 /* weights_blob_host: the packed, BN-folded static SALICON slice of a UNISAL
@@ -113,11 +114,32 @@ int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, 
  * fused into the resampling / the copy: out is bit for bit what the _u8 entry gives on the converted frames -- same output
  * layout, flags, clamping of the window origins (which may be odd in x and y: the chroma index comes from frame coordinates)
  * and LDS limit.  They count under SVC_K_RESIZE / SVC_K_RENDER.  No counterpart in the reference (OpenCV decodes to RGB before
- * it sees a frame); the output is always RGB / BGR. */
+ * it sees a frame); the output of these two is RGB / BGR (NV12 output: the _to_nv12 entries below). */
 int svc_resize_frames_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
                            uint8_t *out, int sh, int sw, void *stream);
 int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                           int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
+
+/* NV12 output: svc_render_crops_u8 / svc_render_crops_nv12 with out[n][oh * 3 / 2][ow] u8 -- oh rows of luma Y, then oh / 2 rows
+ * of interleaved pairs U V (row oh + j holds U[j][0] V[j][0] U[j][1] V[j][1] ...: the layout the NV12-input entries read).
+ * With C the RGB crop [oh][ow][3] that the entry without _to_nv12 writes (same windows, same clamping of the origins, the
+ * exact copy or the INTER_LINEAR resampling), the frame is BT.601 limited range of C in 20-bit fixed point, int32, arithmetic
+ * shifts, chroma taken from the SUM of each 2 x 2 block:
+ *   Y[y][x] = (269484 r + 528482 g + 102760 b + (16 << 20) + (1 << 19)) >> 20                    r, g, b = C[y][x]
+ *   U[j][i] = (-155188 sr - 305135 sg + 460324 sb + (128 << 22) + (1 << 21)) >> 22               sr, sg, sb = sums of r, g, b
+ *   V[j][i] = ( 460324 sr - 385875 sg -  74448 sb + (128 << 22) + (1 << 21)) >> 22               over C[2j .. 2j+1][2i .. 2i+1]
+ * Y lands in 16..235, U and V in 16..240 (black 16 128 128, white 235 128 128, red 82 90 240): nothing is clamped; decoding
+ * a flat colour again with the NV12-input formula gives it back within 2 grey levels.  The transform is fused into the copy / the
+ * resampling: no RGB crop is written.  NV12 in, NV12 out is the same definition on the converted crop (every result is
+ * that of the converted RGB frames); a plane copy of a native-size window at an even origin would give other bytes and is
+ * not done.  SVC_E_INVALID: whatever the RGB entries reject; oh or ow odd or below 2 (a native-size render of a window with
+ * an odd bw or bh does not exist: pass an even output size); flags != 0 (SVC_RENDER_BGR has no meaning here); a resampled
+ * window that needs more than 64 KiB of LDS per pair of output rows: 2 * (3 bw + 32) + 2 * 3 ow + 3 * (ow + 16) bytes, every
+ * term rounded up to 16.  They count under SVC_K_RENDER.  No counterpart in the reference. */
+int svc_render_crops_u8_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                                int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
+int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                                  int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
 
 /* frames_nhwc[n][h][w][3] u8 RGB (saliency size, e.g. 140x250) -> maps_nhw[n][h][w] u8.
  * Frame-major output; the reference's [h][w][n] view is a transpose done by the
@@ -253,7 +275,7 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
 #define SVC_K_CORE 9
 #define SVC_K_PRIM 10
 #define SVC_K_FINISH 11
-#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 */
+#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 / _u8_to_nv12 / _nv12_to_nv12 */
 #define SVC_K_BORDER 13    /* svc_border_profile_u8 (the fused form, svc_saliency_profile_u8, counts under SVC_K_SMOOTH) */
 #define SVC_K_COUNT 14
 int svc_profile_enable(SvcHandle *h, int kernel_class);

@@ -6,6 +6,7 @@
 //   k_cv_resize      cv2.resize(INTER_LINEAR)         smartVidCrop.py:333-335, :633-635
 //   k_render_*       frame[by1:by2, bx1:bx2, :] (+ cv2.resize INTER_LINEAR, + RGB2BGR)  smartVidCrop.py:1801-1921
 //   SrcNv12          BT.601 conversion fused into both (no counterpart: the reference is handed RGB)
+//   k_render_*_yuv   the same crops written as NV12, the forward BT.601 transform fused in (no counterpart: the reference hands RGB to its writer)
 #include <algorithm>
 
 #include "svc_cvlinear.h"
@@ -379,6 +380,17 @@ __global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restric
     d[2] = (uint8_t)(v >> 16);
 }
 
+// nb bytes of an output row from LDS (orow, at the phase of dst: orow & 15 == dst & 15) to dst by the whole workgroup: aligned
+// 16-byte stores; bytes [0, head) and [head + 16 * nw, nb) are partial 16-byte words of the output: bytewise
+__device__ __forceinline__ void row_out(uint8_t *__restrict__ dst, const uint8_t *orow, int nb) {
+    const int head = min(nb, (16 - (int)((uintptr_t)dst & 15)) & 15), nw = (nb - head) >> 4;
+    const uint4 *src4 = (const uint4 *)(orow + head);
+    uint4 *dst4 = (uint4 *)(dst + head);
+    for (int i = threadIdx.x; i < nw; i += 256) dst4[i] = src4[i];
+    for (int i = threadIdx.x; i < head; i += 256) dst[i] = orow[i];
+    for (int i = head + 16 * nw + threadIdx.x; i < nb; i += 256) dst[i] = orow[i];
+}
+
 // Resize path: k_cv_resize's arithmetic on a window of the full frame.  One workgroup = one output row of one frame: the
 // two window rows it reads are staged in LDS as RGB (Src::stage_row; R and B are never swapped before the store), the
 // output row is assembled in LDS at the output's own 16-byte phase and written with aligned 16-byte stores (the partial
@@ -415,13 +427,7 @@ __global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict
                                                                a0, a1, b0, b1, inner);
     }
     __syncthreads();
-    // bytes [0, head) and [head + 16 * nw, ow * 3) of the row are partial 16-byte words of the output: bytewise
-    const int nb = ow * 3, head = min(nb, (16 - ph) & 15), nw = (nb - head) >> 4;
-    const uint4 *src4 = (const uint4 *)(orow + head);
-    uint4 *dst4 = (uint4 *)(dst + head);
-    for (int i = threadIdx.x; i < nw; i += 256) dst4[i] = src4[i];
-    for (int i = threadIdx.x; i < head; i += 256) dst[i] = orow[i];
-    for (int i = head + 16 * nw + threadIdx.x; i < nb; i += 256) dst[i] = orow[i];
+    row_out(dst, orow, ow * 3);
 }
 
 template <class Src>
@@ -483,4 +489,242 @@ extern "C" int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, i
 extern "C" int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                      int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
     return render_crops<SrcNv12>("svc_render_crops_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+}
+
+// --------------------------------------------------------------------------------------
+// render to NV12 (no counterpart in the reference, whose renderer hands RGB / BGR to OpenCV's writer).  The RGB crop C of a
+// frame is exactly what the kernels above produce (same window rules, same clamping, the copy or the INTER_LINEAR
+// resampling); the output frame u8 [oh * 3 / 2][ow] (oh, ow even) is BT.601 limited range of C in 20-bit fixed point, int32:
+//   Y[y][x] = (269484 r + 528482 g + 102760 b + (16 << 20) + (1 << 19)) >> 20
+//   U[j][i] = (-155188 sr - 305135 sg + 460324 sb + (128 << 22) + (1 << 21)) >> 22      sr, sg, sb = sums over the 2 x 2 block
+//   V[j][i] = ( 460324 sr - 385875 sg -  74448 sb + (128 << 22) + (1 << 21)) >> 22      C[2j .. 2j+1][2i .. 2i+1]
+// Y lands in 16..235 and U, V in 16..240 for every input: no clamp.  Another matrix or range changes these constants only.
+// NV12 in, NV12 out is the same thing on the converted crop; copying the planes of a native-size window at an even origin
+// would give other bytes (and a picture that was never RGB) and is not done here.
+// --------------------------------------------------------------------------------------
+#define YUV_CRY 269484
+#define YUV_CGY 528482
+#define YUV_CBY 102760
+#define YUV_CRU (-155188)
+#define YUV_CGU (-305135)
+#define YUV_CBU 460324
+#define YUV_CRV 460324
+#define YUV_CGV (-385875)
+#define YUV_CBV (-74448)
+
+// (__mul24: the coefficients are below 2^23 in magnitude, the other factor at most 1020, the products fit 32 bits: exact.
+// Every sum is positive (largest 1.01e9), so the shift is taken on the unsigned value -- the same number as the arithmetic
+// one -- and the byte is masked before it is packed: nothing here has the shape of the clamped shifts of nv12_rgb.)
+__device__ __forceinline__ uint32_t rgb_luma(uint32_t p) {                 // p = r | g << 8 | b << 16
+    const int r = (int)(p & 0xffu), g = (int)((p >> 8) & 0xffu), b = (int)((p >> 16) & 0xffu);
+    const int v = __mul24(YUV_CRY, r) + __mul24(YUV_CGY, g) + __mul24(YUV_CBY, b) + ((16 << 20) + (1 << 19));
+    return ((uint32_t)v >> 20) & 0xffu;
+}
+// the four pixels of a 2 x 2 block -> U | V << 8
+__device__ __forceinline__ uint32_t rgb_chroma(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3) {
+    // r and b summed in place (10-bit fields at bits 0 and 16), g on its own
+    const uint32_t rb = (p0 & 0xff00ffu) + (p1 & 0xff00ffu) + (p2 & 0xff00ffu) + (p3 & 0xff00ffu);
+    const int sr = (int)(rb & 0xffffu), sb = (int)(rb >> 16);
+    const int sg = (int)(((p0 >> 8) & 0xffu) + ((p1 >> 8) & 0xffu) + ((p2 >> 8) & 0xffu) + ((p3 >> 8) & 0xffu));
+    const int off = (128 << 22) + (1 << 21);
+    const int u = __mul24(YUV_CRU, sr) + __mul24(YUV_CGU, sg) + __mul24(YUV_CBU, sb) + off;
+    const int v = __mul24(YUV_CRV, sr) + __mul24(YUV_CGV, sg) + __mul24(YUV_CBV, sb) + off;
+    return (((uint32_t)u >> 22) & 0xffu) | ((((uint32_t)v >> 22) & 0xffu) << 8);
+}
+
+// pixel i (a constant once unrolled) of the 48 bytes of a px16 run -> r | g << 8 | b << 16
+__device__ __forceinline__ uint32_t run_px(const uint32_t (&o)[12], int i) {
+    const int b = 3 * i, d = b >> 2;
+    return __builtin_amdgcn_alignbyte(d + 1 < 12 ? o[d + 1] : 0u, o[d], b & 3) & 0xffffffu;
+}
+
+// 16 (or, half: the first 8) bytes to an 8-aligned address: one 16-byte store where the address allows it
+__device__ __forceinline__ void st16_a8(uint8_t *d, const uint32_t (&v)[4], bool half) {
+    if (half) *(uint2 *)d = make_uint2(v[0], v[1]);
+    else if (((uintptr_t)d & 15) == 0) *(uint4 *)d = make_uint4(v[0], v[1], v[2], v[3]);
+    else { *(uint2 *)d = make_uint2(v[0], v[1]); *(uint2 *)(d + 8) = make_uint2(v[2], v[3]); }
+}
+
+// Copy path, bw % 8 == 0, bw >= 16, frames and out 16-aligned (every output row, luma or chroma, then starts on 8 bytes).
+// Thread t owns the strip of window rows 2j, 2j + 1 by pixels [16 g, 16 g + 16) (the last strip of a row is 8 wide when
+// bw % 16 == 8): two runs through Src::px16 (odd x, odd y and the frame's end are its business; the pixels past the window
+// are converted and dropped), 32 luma bytes and the strip's 8 interleaved chroma pairs, each row of it as one aligned store.
+template <class Src>
+__global__ __launch_bounds__(256) void k_render_copy_yuv(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                         const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
+                                                         long long total, const uint8_t *in_end) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int G = (bw + 15) >> 4, hb = bh >> 1;
+    const long long R = t / G;
+    const int g = (int)(t - R * G), f = (int)(R / hb), j = (int)(R - (long long)f * hb);
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    const uint8_t *fr = in + f * Src::frame_bytes(height, width);
+    uint32_t a[12], b[12];
+    Src::template px16<false>(fr, height, width, y0 + 2 * j, x0 + 16 * g, in_end, a);
+    Src::template px16<false>(fr, height, width, y0 + 2 * j + 1, x0 + 16 * g, in_end, b);
+    uint32_t ya[4] = {0u, 0u, 0u, 0u}, yb[4] = {0u, 0u, 0u, 0u}, uv[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {                               // block i of the strip: pixels 2 i, 2 i + 1 of both rows
+        const uint32_t p0 = run_px(a, 2 * i), p1 = run_px(a, 2 * i + 1), p2 = run_px(b, 2 * i), p3 = run_px(b, 2 * i + 1);
+        ya[i >> 1] |= (rgb_luma(p0) | (rgb_luma(p1) << 8)) << (16 * (i & 1));
+        yb[i >> 1] |= (rgb_luma(p2) | (rgb_luma(p3) << 8)) << (16 * (i & 1));
+        uv[i >> 1] |= rgb_chroma(p0, p1, p2, p3) << (16 * (i & 1));
+    }
+    uint8_t *o = out + (size_t)f * (bh + hb) * bw + 16 * g;
+    const bool half = 16 * g + 16 > bw;
+    st16_a8(o + (size_t)(2 * j) * bw, ya, half);
+    st16_a8(o + (size_t)(2 * j + 1) * bw, yb, half);
+    st16_a8(o + (size_t)(bh + j) * bw, uv, half);
+}
+
+// Copy path for everything else (narrow windows, other widths, unaligned buffers): one thread per 2 x 2 block, byte accesses.
+template <class Src>
+__global__ __launch_bounds__(256) void k_render_copy_yuv_px(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                            const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
+                                                            long long total) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int wb = bw >> 1, hb = bh >> 1;
+    const long long R = t / wb;
+    const int i = (int)(t - R * wb), f = (int)(R / hb), j = (int)(R - (long long)f * hb);
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    const uint8_t *fr = in + f * Src::frame_bytes(height, width);
+    const int x = x0 + 2 * i, y = y0 + 2 * j;
+    const uint32_t p0 = Src::template px<false>(fr, height, width, y, x), p1 = Src::template px<false>(fr, height, width, y, x + 1);
+    const uint32_t p2 = Src::template px<false>(fr, height, width, y + 1, x), p3 = Src::template px<false>(fr, height, width, y + 1, x + 1);
+    uint8_t *o = out + (size_t)f * (bh + hb) * bw + 2 * i;
+    uint8_t *d0 = o + (size_t)(2 * j) * bw, *d1 = d0 + bw, *dc = o + (size_t)(bh + j) * bw;
+    const uint32_t c = rgb_chroma(p0, p1, p2, p3);
+    d0[0] = (uint8_t)rgb_luma(p0);
+    d0[1] = (uint8_t)rgb_luma(p1);
+    d1[0] = (uint8_t)rgb_luma(p2);
+    d1[1] = (uint8_t)rgb_luma(p3);
+    dc[0] = (uint8_t)c;
+    dc[1] = (uint8_t)(c >> 8);
+}
+
+// Resize path.  One workgroup = output rows 2 j, 2 j + 1 of one frame: k_render_resize's staging and arithmetic once per
+// row, the two RGB rows kept in LDS; then every 2 x 2 block is converted into three LDS rows (two of luma, one of chroma),
+// each at the 16-byte phase of its place in the output, and row_out stores them.  LDS: two source rows of span_cap bytes,
+// two RGB rows of rgb_cap bytes, three output rows of row_cap bytes.
+template <class Src>
+__global__ __launch_bounds__(256) void k_render_resize_yuv(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                           const int *__restrict__ tab, const int32_t *__restrict__ boxes, int f0,
+                                                           int height, int width, int bh, int bw, int oh, int ow, int span_cap,
+                                                           int rgb_cap, int row_cap, const uint8_t *in_end, int vec) {
+    extern __shared__ __align__(16) uint8_t sm_ry[];
+    const CvLinear T(tab, oh, ow);
+    const int j = blockIdx.x, f = f0 + blockIdx.y;
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    const uint8_t *fr = in + f * Src::frame_bytes(height, width);
+    uint8_t *rgb = sm_ry + 2 * span_cap;
+    for (int r = 0; r < 2; ++r) {
+        int ry[2], b0, b1, sh[2];
+        T.row(2 * j + r, bh, ry[0], ry[1], b0, b1);
+        if (r) __syncthreads();                                 // row 0's resampling has read the staged rows
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            sh[k] = Src::stage_row(fr, height, width, y0 + ry[k], x0, bw, sm_ry + k * span_cap, span_cap, in_end, vec);
+        __syncthreads();
+        const uint8_t *r0 = sm_ry + sh[0], *r1 = sm_ry + span_cap + sh[1];
+        uint8_t *orow = rgb + r * rgb_cap;
+        for (int ox = threadIdx.x; ox < ow; ox += 256) {
+            int sx, sx1, a0, a1;
+            bool inner;
+            T.col(ox, bw, sx, sx1, a0, a1, inner);
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                orow[ox * 3 + c] = CvLinear::blend(r0[sx * 3 + c], r0[sx1 * 3 + c], r1[sx * 3 + c], r1[sx1 * 3 + c], a0, a1, b0, b1, inner);
+        }
+    }
+    __syncthreads();
+    uint8_t *frame_o = out + (size_t)blockIdx.y * (oh + (oh >> 1)) * ow;
+    uint8_t *dst[3] = {frame_o + (size_t)(2 * j) * ow, frame_o + (size_t)(2 * j + 1) * ow, frame_o + (size_t)(oh + j) * ow};
+    uint8_t *lrow[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) lrow[k] = rgb + 2 * rgb_cap + k * row_cap + (int)((uintptr_t)dst[k] & 15);
+    for (int i = threadIdx.x; 2 * i < ow; i += 256) {
+        const uint8_t *s0 = rgb + 6 * i, *s1 = s0 + rgb_cap;
+        const uint32_t p0 = s0[0] | (s0[1] << 8) | (s0[2] << 16), p1 = s0[3] | (s0[4] << 8) | (s0[5] << 16);
+        const uint32_t p2 = s1[0] | (s1[1] << 8) | (s1[2] << 16), p3 = s1[3] | (s1[4] << 8) | (s1[5] << 16);
+        const uint32_t c = rgb_chroma(p0, p1, p2, p3);
+        lrow[0][2 * i] = (uint8_t)rgb_luma(p0);
+        lrow[0][2 * i + 1] = (uint8_t)rgb_luma(p1);
+        lrow[1][2 * i] = (uint8_t)rgb_luma(p2);
+        lrow[1][2 * i + 1] = (uint8_t)rgb_luma(p3);
+        lrow[2][2 * i] = (uint8_t)c;
+        lrow[2][2 * i + 1] = (uint8_t)(c >> 8);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; ++k) row_out(dst[k], lrow[k], ow);
+}
+
+template <class Src>
+static int render_crops_yuv(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                            int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    if (!h || n < 0 || (n > 0 && (!frames || !boxes || !out)) || !Src::size_ok(height, width) || bw < 1 || bh < 1 ||
+        bw > width || bh > height) {                                                       // n = 0: a no-op, null buffers allowed
+        svc_set_error("%s: invalid argument%s", name, Src::size_rule());
+        return SVC_E_INVALID;
+    }
+    if (oh < 2 || ow < 2 || (oh & 1) || (ow & 1)) {
+        svc_set_error("%s: an NV12 output of %dx%d (width and height must be even and >= 2; a window of odd size needs an "
+                      "even output size)", name, ow, oh);
+        return SVC_E_INVALID;
+    }
+    if (flags) {
+        svc_set_error("%s: flags must be 0 (SVC_RENDER_BGR has no meaning for an NV12 output)", name);
+        return SVC_E_INVALID;
+    }
+    const int span_cap = (bw * 3 + 32 + 15) / 16 * 16, rgb_cap = (ow * 3 + 15) / 16 * 16, row_cap = (ow + 15) / 16 * 16 + 16;
+    const size_t lds = 2 * (size_t)span_cap + 2 * (size_t)rgb_cap + 3 * (size_t)row_cap;
+    const bool copy = oh == bh && ow == bw;
+    if (!copy && lds > 65536) {
+        svc_set_error("%s: window %dx%d -> %dx%d needs %zu bytes of LDS per pair of output rows (> 64 KiB)", name, bw, bh, ow, oh, lds);
+        return SVC_E_INVALID;
+    }
+    if (n == 0) return SVC_OK;
+    SVC_HIP(hipSetDevice(h->device));
+    const uint8_t *in_end = frames + n * Src::frame_bytes(height, width);
+    const bool aligned_in = ((uintptr_t)frames & 15) == 0, aligned_out = ((uintptr_t)out & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int *tab = nullptr;
+    if (!copy) {
+        int rc = cv_tab(h, bh, bw, oh, ow, &tab);
+        if (rc) return rc;
+    }
+    ProfScope ps(h, SVC_K_RENDER, s);
+    if (copy) {
+        if (bw >= 16 && bw % 8 == 0 && aligned_in && aligned_out) {
+            const long long total = (long long)n * (bh / 2) * ((bw + 15) / 16);
+            k_render_copy_yuv<Src><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total, in_end);
+        } else {
+            const long long total = (long long)n * (bh / 2) * (bw / 2);
+            k_render_copy_yuv_px<Src><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total);
+        }
+        SVC_CHECK_LAUNCH();
+        return SVC_OK;
+    }
+    for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
+        const int nf = std::min(n - f0, 65535);
+        uint8_t *o = out + (size_t)f0 * (oh + oh / 2) * ow;
+        k_render_resize_yuv<Src><<<dim3((unsigned)(oh / 2), (unsigned)nf), 256, lds, s>>>(
+            frames, o, tab, boxes, f0, height, width, bh, bw, oh, ow, span_cap, rgb_cap, row_cap, in_end, aligned_in);
+        SVC_CHECK_LAUNCH();
+    }
+    return SVC_OK;
+}
+
+extern "C" int svc_render_crops_u8_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                                           int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    return render_crops_yuv<SrcRgb>("svc_render_crops_u8_to_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+}
+extern "C" int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                                             int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    return render_crops_yuv<SrcNv12>("svc_render_crops_nv12_to_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }

@@ -25,6 +25,12 @@ rendered frames as a lossless PNG frame folder, which ``read_frames_pillow`` rea
 
     S.set_video_writer(ingest.write_frames_pillow)
     VD, res = S.smart_vid_crop('frames_of_clip_017/', CP, final_vid_fn='clip_017_9x16/')
+
+``write_frames_raw`` is the writer for an encoder: one file of raw frames, RGB or -- rendered as such on the device -- NV12,
+which ``ffmpeg -f rawvideo -pix_fmt nv12 -s 1080x1920 -r 25 -i clip_017.nv12 ...`` reads:
+
+    S.set_video_writer(ingest.write_frames_raw)
+    VD, res = S.smart_vid_crop(video, CP, final_vid_fn='clip_017.nv12', out_size=(1080, 1920), out_pix_fmt='nv12')
 """
 import os
 
@@ -92,12 +98,48 @@ class _PillowFrameWriter:
         pass
 
 
-def write_frames_pillow(path, fr, size):
+def write_frames_pillow(path, fr, size, pix_fmt='rgb24'):
     """The encode side of read_frames_pillow, in the shape of cv2.VideoWriter (smartVidCrop.set_video_writer):
     ``write(frame)`` stores RGB [h,w,3] u8 frames of ``size`` = (w, h) as ``path/000000.png``, ``000001.png``, ... (lossless;
     the directory is created), ``release()`` ends it.  ``fr`` is accepted for the writer signature; a PNG folder keeps no
-    frame rate (read_frames_pillow(path, fr=...) gives it back)."""
+    frame rate (read_frames_pillow(path, fr=...) gives it back).  A PNG holds RGB: any other ``pix_fmt`` (smart_vid_crop's
+    out_pix_fmt='nv12') is refused with ValueError; write_frames_raw takes NV12."""
+    if pix_fmt != 'rgb24':
+        raise ValueError('write_frames_pillow stores RGB frames as PNG files, not pix_fmt=%r: use write_frames_raw' % (pix_fmt,))
     return _PillowFrameWriter(path, fr, size)
+
+
+class _RawFrameWriter:
+    def __init__(self, path, fr, size, pix_fmt):
+        w, h = int(size[0]), int(size[1])
+        if pix_fmt == 'rgb24':
+            self.shape = (h, w, 3)
+        elif pix_fmt == 'nv12':
+            if w < 2 or h < 2 or w % 2 or h % 2:
+                raise ValueError('an nv12 picture has even width and height (>= 2), not %d x %d' % (w, h))
+            self.shape = (h * 3 // 2, w)
+        else:
+            raise ValueError('unknown pix_fmt %r (rgb24 or nv12)' % (pix_fmt,))
+        self.path, self.fr, self.size, self.pix_fmt, self.n = path, float(fr), (w, h), pix_fmt, 0
+        self.fp = open(path, 'wb')
+
+    def write(self, frame_u8):
+        f = np.ascontiguousarray(frame_u8, np.uint8)
+        if f.shape != self.shape:
+            raise ValueError('frame of shape %s, the writer was opened for %s frames of %d x %d' % ((f.shape, self.pix_fmt) + self.size))
+        self.fp.write(f.data)
+        self.n += 1
+
+    def release(self):
+        self.fp.close()
+
+
+def write_frames_raw(path, fr, size, pix_fmt='rgb24'):
+    """A writer for smartVidCrop.set_video_writer that appends every frame's bytes to the one file ``path``: a raw stream
+    as ``ffmpeg -f rawvideo -pix_fmt <pix_fmt> -s <w>x<h> -r <fr>`` reads it.  ``pix_fmt``: 'rgb24' (frames [h,w,3] u8) or
+    'nv12' (frames [h*3/2,w] u8, w and h even: smart_vid_crop(..., out_pix_fmt='nv12')); ``size`` = (w, h).  A raw file keeps
+    neither size nor rate: ``fr`` is accepted for the writer signature.  Needs nothing beyond numpy."""
+    return _RawFrameWriter(path, fr, size, pix_fmt)
 
 
 def read_video_cv2(path, shot_detector=None, max_frames=None):

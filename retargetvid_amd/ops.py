@@ -29,6 +29,7 @@ def _need_cuda(t, dtype, name):
 
 RENDER_BGR = 1                       # svc_render_crops_u8 flag (include/svc.h: SVC_RENDER_BGR)
 PIX_FMTS = ('rgb24', 'nv12')         # input pixel formats: uint8 [n,h,w,3] RGB | uint8 [n,h*3/2,w] (include/svc.h: the _nv12 entries)
+OUT_FMTS = ('rgb24', 'nv12')         # the renderer's output formats: the same two shapes (include/svc.h: the _to_nv12 entries)
 
 
 def frame_shape(pix_fmt, h, w):
@@ -41,6 +42,19 @@ def frame_shape(pix_fmt, h, w):
             raise ValueError('an nv12 picture has even width and height (>= 2), not %d x %d' % (w, h))
         return (h * 3 // 2, w)
     raise ValueError('unknown pix_fmt %r (one of %s)' % (pix_fmt, ', '.join(PIX_FMTS)))
+
+
+def out_frame_shape(out_fmt, oh, ow, bgr=False):
+    """Shape of one rendered frame of oh x ow in `out_fmt` (frame_shape's); ValueError for an unknown format, an NV12 output of
+    odd size, or bgr with NV12 -- what the renderer's doors check before any device work."""
+    if out_fmt not in OUT_FMTS:
+        raise ValueError('unknown out_fmt %r (one of %s)' % (out_fmt, ', '.join(OUT_FMTS)))
+    if out_fmt == 'nv12':
+        if bgr:
+            raise ValueError('bgr has no meaning for an nv12 output')
+        if oh < 2 or ow < 2 or oh % 2 or ow % 2:
+            raise ValueError('an nv12 output has even width and height (>= 2), not %d x %d: pass an even out_size' % (ow, oh))
+    return frame_shape(out_fmt, oh, ow)
 
 
 def picture_size(frames, pix_fmt):
@@ -101,30 +115,43 @@ class Engine:
         return out
 
     # -- rendering ------------------------------------------------------------------------
-    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None, pix_fmt='rgb24'):
+    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None, pix_fmt='rgb24', out_fmt='rgb24'):
         """uint8 [n,h,w,3] frames on the device (pix_fmt='nv12': uint8 [n,h*3/2,w], svc_render_crops_nv12; the crops are RGB / BGR
         either way) and int32 [n,4] boxes (x1,y1,x2,y2, one window size for all; a CUDA tensor, or
         host values that are copied over) -> uint8
         [n,oh,ow,3]: frame[y1:y2, x1:x2] copied (out_hw None or the window size) or resampled to out_hw = (oh, ow) with
-        cv2.resize(INTER_LINEAR) semantics; bgr: R and B swapped.  Runs on the current stream (svc_render_crops_u8)."""
-        _need_cuda(frames, torch.uint8, 'frames')
+        cv2.resize(INTER_LINEAR) semantics; bgr: R and B swapped.  Runs on the current stream (svc_render_crops_u8).
+        out_fmt='nv12': the crops come out as NV12 frames uint8 [n,oh*3/2,ow] (BT.601 limited range of the RGB crop, fused
+        into the kernels: svc_render_crops_u8_to_nv12 / _nv12_to_nv12); oh and ow must be even and bgr unset (ValueError)."""
         n = int(frames.shape[0])
-        if torch.is_tensor(boxes) and boxes.is_cuda:
-            b0 = boxes[0].tolist() if n else [0, 0, 1, 1]        # the window size (a host read of 16 bytes)
+        on_dev = torch.is_tensor(boxes) and boxes.is_cuda
+        if n:
+            b0 = boxes[0].tolist() if on_dev else np.asarray(boxes)[0].tolist()     # the window size (on_dev: a host read of 16 bytes)
         else:
-            b0 = np.asarray(boxes)[0].tolist() if n else [0, 0, 1, 1]
-            boxes = torch.from_numpy(np.ascontiguousarray(boxes, np.int32)).to(frames.device)
+            b0 = [0, 0, 2, 2] if out_fmt == 'nv12' else [0, 0, 1, 1]
         bw, bh = int(b0[2] - b0[0]), int(b0[3] - b0[1])
         oh, ow = (bh, bw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        shape = (n,) + out_frame_shape(out_fmt, oh, ow, bgr)      # (the ValueErrors come before anything touches the device)
+        _need_cuda(frames, torch.uint8, 'frames')
+        if not on_dev:
+            boxes = torch.from_numpy(np.ascontiguousarray(boxes, np.int32)).to(frames.device)
         if out is None:
-            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
-        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt)
+            out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt, out_fmt)
 
-    def _render(self, frames, boxes, bw, bh, out, bgr, pix_fmt='rgb24'):
+    def _render(self, frames, boxes, bw, bh, out, bgr, pix_fmt='rgb24', out_fmt='rgb24'):
         _need_cuda(frames, torch.uint8, 'frames')
         _need_cuda(boxes, torch.int32, 'boxes')
         _need_cuda(out, torch.uint8, 'out')
         n, h, w = picture_size(frames, pix_fmt)
+        if out_fmt == 'nv12':
+            on, oh, ow = picture_size(out, 'nv12')
+            out_frame_shape(out_fmt, oh, ow, bgr)
+            assert tuple(boxes.shape) == (n, 4) and on == n
+            fn = self.lib.svc_render_crops_nv12_to_nv12 if pix_fmt == 'nv12' else self.lib.svc_render_crops_u8_to_nv12
+            _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out), oh, ow, 0, _stream()))
+            return out
+        out_frame_shape(out_fmt, 1, 1)
         assert tuple(boxes.shape) == (n, 4) and out.shape[0] == n and out.shape[3] == 3
         fn = self.lib.svc_render_crops_nv12 if pix_fmt == 'nv12' else self.lib.svc_render_crops_u8
         _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out),

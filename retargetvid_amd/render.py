@@ -10,7 +10,9 @@ The frames come from any container the ingest accepts: a host numpy array (gathe
 side stream: smartVidCrop._HostFeed), a pinned torch tensor (copied from where it lies), a CUDA tensor (no copy) or an
 on-device generator (synth.LazyBlobVideo: select on the device).  A video dict with pix_fmt='nv12' holds NV12 frames
 (uint8 [n, h * 3 / 2, w]): they are converted inside the render kernels (svc_render_crops_nv12); the crops are RGB / BGR
-either way.  The crops come back through pinned double buffers on a
+either way -- unless out_fmt='nv12' asks for NV12 crops (uint8 [m, oh * 3 / 2, ow], what a hardware encoder takes: BT.601
+limited range, fused into the render kernels, svc_render_crops_u8_to_nv12 / _nv12_to_nv12; half the bytes to copy back).
+The crops come back through pinned double buffers on a
 second side stream, so that the sink consumes chunk c while the device renders chunk c + 1."""
 import numpy as np
 
@@ -58,14 +60,16 @@ def check_boxes(bbs, fc, h, w):
     return (int(bw[0]), int(bh[0])) if fc else (0, 0)
 
 
-def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, chunk=32, pix_fmt=None):
+def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, chunk=32, pix_fmt=None, out_fmt='rgb24'):
     """Render VD['fc'] frames of `video` (the ingest_pickle dict, or its 'frames' container) at VD['bbs_np'].
     pix_fmt: the frames' format when `video` is a bare container (a dict brings its own 'pix_fmt'; default 'rgb24'); an
     unknown format, an NV12 picture of odd size or a container of another shape raise ValueError before any device work.
     out_size: (w, h) of the output frames (None = the window size, an exact copy); bgr: R and B swapped (the reference's
     pickle mode); sink: called with every chunk uint8 [m, oh, ow, 3] (m <= chunk) in frame order -- a view of a pinned
     buffer that is refilled after the call returns, so copy what you keep.  -> numpy uint8 [fc, oh, ow, 3] without a sink,
-    else None.  Boxes of unequal size or outside the frame raise ValueError before any device work."""
+    else None.  Boxes of unequal size or outside the frame raise ValueError before any device work.
+    out_fmt='nv12': chunks and the returned array are NV12 frames uint8 [m, oh * 3 / 2, ow] (include/svc.h states the formula);
+    an odd output size (pass an even out_size), bgr with it, or an unknown format raise ValueError before any device work."""
     frames, n, h, w, pix_fmt = _container(video, pix_fmt)
     fc = int(VD['fc'])
     if n < fc:
@@ -74,10 +78,12 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     ow, oh = (bw, bh) if out_size is None else (int(out_size[0]), int(out_size[1]))
     if oh < 1 or ow < 1:
         raise ValueError('output size %s' % (out_size,))
-    chunk = max(1, min(int(chunk), _MAX_CHUNK, _RING_BYTES // (oh * ow * 3)))
+    from .ops import out_frame_shape
+    shape = out_frame_shape(out_fmt, oh, ow, bgr)
+    chunk = max(1, min(int(chunk), _MAX_CHUNK, _RING_BYTES // int(np.prod(shape))))       # (the real bytes per frame)
     result = None
     if sink is None:
-        result = np.empty((fc, oh, ow, 3), np.uint8)
+        result = np.empty((fc,) + shape, np.uint8)
 
         def sink(c, _pos=[0]):
             result[_pos[0]:_pos[0] + c.shape[0]] = c
@@ -89,7 +95,7 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     engine = engine or S.get_engine()
     dev = engine.device
     boxes = torch.from_numpy(np.ascontiguousarray(VD['bbs_np'][:fc], np.int32)).to(dev)
-    out = _OutRing(engine, chunk, oh, ow, sink)
+    out = _OutRing(engine, chunk, oh, ow, sink, out_fmt)
 
     def emit(staged, s):
         out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr, pix_fmt)
@@ -115,15 +121,17 @@ class _OutRing:
     """Two device output slots and two pinned host slots: chunk c is rendered on the caller's stream into device slot c & 1,
     copied D2H on a side stream into pinned slot c & 1, and handed to the sink once the copy of chunk c + 1 is enqueued."""
 
-    def __init__(self, engine, cap, oh, ow, sink):
+    def __init__(self, engine, cap, oh, ow, sink, out_fmt='rgb24'):
         import torch
-        self.engine, self.sink, self.dev = engine, sink, engine.device
-        key = (cap, oh, ow)
+        from .ops import frame_shape
+        self.engine, self.sink, self.dev, self.out_fmt = engine, sink, engine.device, out_fmt
+        key = (cap, oh, ow, out_fmt)
+        shape = (cap,) + frame_shape(out_fmt, oh, ow)           # slots shaped (and keyed) by the output format
         ring = engine.__dict__.get('_render_ring')
         if ring is None or ring['key'] != key:
             ring = engine._render_ring = dict(
-                key=key, dev=[torch.empty((cap, oh, ow, 3), dtype=torch.uint8, device=self.dev) for _ in range(2)],
-                host=[torch.empty((cap, oh, ow, 3), dtype=torch.uint8).pin_memory() for _ in range(2)],
+                key=key, dev=[torch.empty(shape, dtype=torch.uint8, device=self.dev) for _ in range(2)],
+                host=[torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(2)],
                 stream=torch.cuda.Stream(device=self.dev))
         self.ring = ring
         self.rendered = [torch.cuda.Event(), torch.cuda.Event()]
@@ -147,7 +155,7 @@ class _OutRing:
         if self.used[slot]:
             compute.wait_event(self.copied[slot])           # the device slot's previous D2H has read it
         dst = self.ring['dev'][slot][:m]
-        self.engine._render(staged, boxes, bw, bh, dst, bgr, pix_fmt)
+        self.engine._render(staged, boxes, bw, bh, dst, bgr, pix_fmt, self.out_fmt)
         self.rendered[slot].record(compute)
         with torch.cuda.stream(side):
             side.wait_event(self.rendered[slot])

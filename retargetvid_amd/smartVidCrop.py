@@ -70,7 +70,8 @@ def set_video_writer(fn):
     """Install the encode hand-off of smart_vid_crop(..., save_vid=True, final_vid_fn=...), the mirror of set_video_reader:
     ``fn(path, fr, (w, h))`` returns an object with ``write(frame_rgb_u8)`` and ``release()`` -- the shape of
     cv2.VideoWriter.  Frames are handed over RGB [h,w,3] u8; a writer that wants BGR flips them itself.
-    ingest.write_frames_pillow writes a PNG frame folder.  None removes it."""
+    ingest.write_frames_pillow writes a PNG frame folder.  With smart_vid_crop(out_pix_fmt='nv12') the call is
+    ``fn(path, fr, (w, h), pix_fmt='nv12')`` and the frames are NV12 [h*3/2,w] u8 (ingest.write_frames_raw).  None removes it."""
     global _video_writer
     _video_writer = fn
 
@@ -695,7 +696,7 @@ class _LazySmaps(dict):
 def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn='', frames_dir='',
                    temp_path=None, verbose=False, save_vid=True, callback_progress=None,
                    callback_session=None, callback_status=None, copy_sound=False, engine=None, shot_net=None, stream_batch=0,
-                   out_size=None):
+                   out_size=None, out_pix_fmt='rgb24'):
     """Saliency -> crop windows for one video.  Returns (VD, smart_crop_results) like the
     reference; VD['bbs'] holds one [x1,y1,x2,y2] per decoded frame.  A video dict without ``trans_inds`` takes the
     reference's video path: ``shot_net`` (transnetv1_handler.ShotTransNet) detects the shots inside the ingest.
@@ -708,7 +709,11 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         side effects;
       * any other input goes through the writer installed with set_video_writer(): fn(final_vid_fn, VD['fr'], size) with
         size = out_size (w, h) if given (every crop resampled to it, cv2.resize INTER_LINEAR) else (fbb_w, fbb_h); RGB
-        frames.  No writer installed: NotImplementedError, before any work.
+        frames.  No writer installed: NotImplementedError, before any work.  out_pix_fmt='nv12': the frames are rendered as
+        NV12 (uint8 [h * 3 / 2, w], render.render_video(out_fmt='nv12'); the size must be even) and the writer is opened as
+        fn(final_vid_fn, VD['fr'], size, pix_fmt='nv12') (ingest.write_frames_raw takes it); with the default 'rgb24' the
+        call is the three-argument one.  The pickle mode is defined as BGR crops: with 'nv12' it raises ValueError, as does
+        an unknown format, before any work.
     demo_fn (the five-panel demo) and copy_sound (ffmpeg) with a render raise NotImplementedError."""
     import torch
     sc_init_time()
@@ -721,10 +726,15 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         raise NotImplementedError('the five-panel demo video (cv2 drawing and text) is not rendered by this package; '
                                   'pass demo_fn=\'\'')
     render_pkl = render_writer = False
+    from .ops import out_frame_shape
+    out_frame_shape(out_pix_fmt, *((2, 2) if out_size is None else (out_size[1], out_size[0])))     # unknown format, odd out_size: ValueError
     if save_vid and final_vid_fn:
         if copy_sound:
             raise NotImplementedError('copy_sound needs ffmpeg, which is not part of this package; pass copy_sound=False')
         render_pkl = isinstance(video_path, str) and video_path.endswith('.pkl')
+        if render_pkl and out_pix_fmt != 'rgb24':
+            raise ValueError('the pickle mode writes BGR crops; out_pix_fmt=%r needs a writer (a video that is not a .pkl path)'
+                             % (out_pix_fmt,))
         render_writer = not render_pkl
         if render_writer and _video_writer is None:
             raise NotImplementedError('rendering to %r needs a video writer: install one with set_video_writer() (for '
@@ -797,9 +807,12 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
                 pickle.dump(list(crops), fp)
         else:
             size = tuple(int(v) for v in out_size) if out_size is not None else (int(VD['fbb_w']), int(VD['fbb_h']))
-            writer = _video_writer(final_vid_fn, VD['fr'], size)
+            out_frame_shape(out_pix_fmt, size[1], size[0])        # (an odd crop window as NV12: ValueError before the writer creates anything)
+            writer = _video_writer(final_vid_fn, VD['fr'], size) if out_pix_fmt == 'rgb24' else \
+                _video_writer(final_vid_fn, VD['fr'], size, pix_fmt=out_pix_fmt)
             try:
-                render.render_video(video, VD, engine=engine, out_size=size, sink=lambda chunk: [writer.write(f) for f in chunk])
+                render.render_video(video, VD, engine=engine, out_size=size, sink=lambda chunk: [writer.write(f) for f in chunk],
+                                    out_fmt=out_pix_fmt)
             finally:
                 writer.release()
         sc_register_time(t, 'render')

@@ -1,0 +1,233 @@
+"""-m gpu: NV12 output of the renderer (svc_render_crops_u8_to_nv12, svc_render_crops_nv12_to_nv12 and every door above them).
+Every expected value is nv12_out_ref.rgb_to_nv12_fixed(E) -- the formula of include/svc.h in numpy, int64 -- of the expected RGB
+crop E that the RGB-output tests use: the slice of the frame (of nv12_ref.nv12_to_rgb(frame) for NV12 input), or
+oracle.cv_ref.resize_linear_u8 of that slice on the resize path.  Nothing has a tolerance."""
+import numpy as np
+import pytest
+import torch
+
+import nv12_out_ref
+import nv12_ref
+from oracle import cv_ref
+from retargetvid_amd import ingest, ops, render, smartVidCrop as S, synth
+
+pytestmark = pytest.mark.gpu
+
+SOURCES = ('rgb24', 'nv12')
+forward = nv12_out_ref.rgb_to_nv12_fixed
+
+
+def _frames(pix_fmt, n, h, w, seed):
+    """-> (the frames as fed, uint8 of the format's shape; the same pictures as RGB)."""
+    rng = np.random.RandomState(seed)
+    if pix_fmt == 'nv12':
+        nv = rng.randint(0, 256, (n, h * 3 // 2, w)).astype(np.uint8)
+        return nv, nv12_ref.nv12_to_rgb(nv, h, w)
+    rgb = rng.randint(0, 256, (n, h, w, 3)).astype(np.uint8)
+    return rgb, rgb
+
+
+def _boxes(n, h, w, bw, bh, seed):
+    """The four corners of the frame first (every edge touched), then one origin of every (x, y) parity, then random ones."""
+    rng = np.random.RandomState(seed)
+    xs, ys = [0, w - bw, 0, w - bw], [0, 0, h - bh, h - bh]
+    for k in range(4, n):
+        x, y = int(rng.randint(0, w - bw + 1)), int(rng.randint(0, h - bh + 1))
+        if k < 8:                                               # parity (k & 1, k >> 1 & 1) where the frame leaves room for it
+            x, y = (max(x - 1, 0) & ~1) | (k & 1), (max(y - 1, 0) & ~1) | (k >> 1 & 1)
+        xs.append(min(x, w - bw))
+        ys.append(min(y, h - bh))
+    return np.array([[x, y, x + bw, y + bh] for x, y in zip(xs[:n], ys[:n])], np.int32)
+
+
+def _slices(rgb, boxes):
+    return np.stack([np.ascontiguousarray(f[y1:y2, x1:x2]) for f, (x1, y1, x2, y2) in zip(rgb, boxes)])
+
+
+def _offset_by_one(a):
+    """The array's bytes on the device one byte behind an aligned address."""
+    raw = torch.from_numpy(np.concatenate([np.zeros(1, np.uint8), a.ravel()])).cuda()
+    return raw[1:].view(a.shape)
+
+
+def test_every_rgb_triple(engine):
+    """One 4096 x 4096 RGB frame that holds every triple once, through the full-frame window: luma exhaustively, chroma on
+    4 M distinct blocks."""
+    f = nv12_out_ref.every_rgb_triple_frame()[None]
+    exp = forward(f)
+    got = engine.render_crops(torch.from_numpy(f).cuda(), np.array([[0, 0, 4096, 4096]], np.int32), out_fmt='nv12')
+    assert got.shape == (1, 6144, 4096) and got.dtype == torch.uint8
+    assert np.array_equal(got.cpu().numpy(), exp)
+
+
+@pytest.mark.parametrize('pix_fmt', SOURCES)
+def test_copy_path(engine, pix_fmt):
+    """The vector kernel (bw % 8 == 0, >= 16; (24, 6) ends its rows in a half strip) and the block kernel (the other widths),
+    in a picture whose width is no multiple of 16 and in a 640 x 360 one, windows at the corners and at every x / y parity."""
+    for h, w in ((38, 70), (360, 640)):
+        fed, rgb = _frames(pix_fmt, 8, h, w, seed=h)
+        d = torch.from_numpy(fed).cuda()
+        for bw, bh in ((2, 2), (16, 2), (18, 10), (24, 6), (32, 20), (34, 6), (70, 38), (608, 360)):
+            if bw > w or bh > h:
+                continue
+            boxes = _boxes(8, h, w, bw, bh, seed=bw)
+            if w - bw >= 1 and h - bh >= 1:
+                assert {(x & 1, y & 1) for x, y in boxes[:, :2]} == {(0, 0), (0, 1), (1, 0), (1, 1)}
+            exp = forward(_slices(rgb, boxes))
+            got = engine.render_crops(d, torch.from_numpy(boxes).cuda(), pix_fmt=pix_fmt, out_fmt='nv12')
+            assert got.shape == (8, bh * 3 // 2, bw)
+            assert np.array_equal(got.cpu().numpy(), exp), (h, w, bw, bh)
+            got = engine.render_crops(d, boxes, out_hw=(bh, bw), pix_fmt=pix_fmt, out_fmt='nv12')      # the size spelled out
+            assert np.array_equal(got.cpu().numpy(), exp), (h, w, bw, bh, 'out_hw')
+
+
+@pytest.mark.parametrize('pix_fmt', SOURCES)
+def test_unaligned_buffers(engine, pix_fmt):
+    """Frames / output that do not start on 16 bytes: the block kernel on a window the vector kernel would take, and the
+    resize path's bytewise staging with every output row at another phase."""
+    h, w = 36, 64
+    fed, rgb = _frames(pix_fmt, 3, h, w, seed=1)
+    d = _offset_by_one(fed)
+    boxes = _boxes(3, h, w, 32, 20, seed=2)
+    out = torch.zeros(1 + 3 * 30 * 32 + 1, dtype=torch.uint8, device='cuda')
+    got = engine.render_crops(d, boxes, out=out[1:-1].view(3, 30, 32), pix_fmt=pix_fmt, out_fmt='nv12')
+    assert np.array_equal(got.cpu().numpy(), forward(_slices(rgb, boxes)))
+    assert out[0].item() == 0 and out[-1].item() == 0                    # nothing written around the output
+    # aligned frames, unaligned output: still the block kernel
+    got = engine.render_crops(torch.from_numpy(fed).cuda(), boxes, out=out[1:-1].view(3, 30, 32), pix_fmt=pix_fmt, out_fmt='nv12')
+    assert np.array_equal(got.cpu().numpy(), forward(_slices(rgb, boxes)))
+    out = torch.zeros(1 + 3 * 60 * 50 + 1, dtype=torch.uint8, device='cuda')
+    got = engine.render_crops(d, boxes, out=out[1:-1].view(3, 60, 50), pix_fmt=pix_fmt, out_fmt='nv12').cpu().numpy()
+    exp = forward(np.stack([cv_ref.resize_linear_u8(c, 40, 50) for c in _slices(rgb, boxes)]))
+    assert np.array_equal(got, exp)
+    assert out[0].item() == 0 and out[-1].item() == 0
+
+
+@pytest.mark.parametrize('pix_fmt', SOURCES)
+@pytest.mark.parametrize('pic,win,osz', [((360, 640), (203, 360), (640, 360)),         # non-integer upscale of a 9:16 window
+                                         ((360, 640), (320, 180), (90, 160)),          # exact 2:1
+                                         ((360, 640), (301, 77), (50, 334)),           # anisotropic
+                                         ((2160, 3840), (1215, 2160), (1080, 608)),    # 4K 9:16 window, non-integer downscale
+                                         ((360, 640), (17, 9), (64, 96))])             # upscale of a tiny window
+def test_resize_path(engine, pix_fmt, pic, win, osz):
+    (h, w), (bw, bh), (oh, ow) = pic, win, osz
+    n = 2 if h >= 2160 else 3
+    fed, rgb = _frames(pix_fmt, n, h, w, seed=bw)
+    boxes = _boxes(n, h, w, bw, bh, seed=oh)
+    got = engine.render_crops(torch.from_numpy(fed).cuda(), boxes, out_hw=(oh, ow), pix_fmt=pix_fmt, out_fmt='nv12').cpu().numpy()
+    assert got.shape == (n, oh * 3 // 2, ow)
+    for i, c in enumerate(_slices(rgb, boxes)):
+        assert np.array_equal(got[i], forward(cv_ref.resize_linear_u8(c, oh, ow))), i
+
+
+def test_argument_checks(engine):
+    lib, vp = engine.lib, lambda t: t.data_ptr()
+    box = torch.zeros((1, 4), dtype=torch.int32, device='cuda')
+    out = torch.zeros(1 << 16, dtype=torch.uint8, device='cuda')
+
+    def refused(rc):
+        return rc == -1 and lib.svc_last_error().startswith(b'svc_render_crops_')
+
+    for fn, d in ((lib.svc_render_crops_u8_to_nv12, torch.zeros((1, 36, 64, 3), dtype=torch.uint8, device='cuda')),
+                  (lib.svc_render_crops_nv12_to_nv12, torch.zeros((1, 54, 64), dtype=torch.uint8, device='cuda'))):
+        assert fn(engine._h, None, 0, 36, 64, None, 24, 14, None, 14, 24, 0, None) == 0                  # n = 0: a no-op
+        assert fn(engine._h, vp(d), 1, 36, 64, vp(box), 24, 14, vp(out), 14, 24, 0, None) == 0
+        assert fn(engine._h, vp(d), 1, 36, 64, vp(box), 24, 14, vp(out), 20, 30, 0, None) == 0
+        assert refused(fn(engine._h, vp(d), 1, 36, 64, vp(box), 24, 14, vp(out), 15, 24, 0, None))       # odd oh
+        assert refused(fn(engine._h, vp(d), 1, 36, 64, vp(box), 24, 14, vp(out), 14, 25, 0, None))       # odd ow
+        assert refused(fn(engine._h, vp(d), 1, 36, 64, vp(box), 25, 14, vp(out), 14, 25, 0, None))       # native size, odd window
+        assert refused(fn(engine._h, vp(d), 1, 36, 64, vp(box), 24, 13, vp(out), 13, 24, 0, None))
+        assert refused(fn(engine._h, vp(d), 1, 36, 64, vp(box), 24, 14, vp(out), 0, 24, 0, None))
+        assert refused(fn(engine._h, vp(d), 1, 36, 64, vp(box), 24, 14, vp(out), 14, 24, ops.RENDER_BGR, None))
+        assert refused(fn(engine._h, vp(d), 1, 36, 64, vp(box), 24, 14, vp(out), 14, 24, 2, None))
+        assert refused(fn(engine._h, vp(d), 1, 36, 64, vp(box), 66, 14, vp(out), 14, 24, 0, None))       # what the RGB entries reject
+        assert refused(fn(engine._h, vp(d), 1, 36, 64, None, 24, 14, vp(out), 14, 24, 0, None))
+    assert refused(lib.svc_render_crops_nv12_to_nv12(engine._h, vp(out), 1, 35, 64, vp(box), 24, 14, vp(out), 14, 24, 0, None))
+    # a window over the LDS limit (2 (3 bw + 32) + 6 ow + 3 (ow + 16) > 64 KiB) is refused; as a copy it needs no LDS
+    wide = torch.zeros((1, 2, 8192, 3), dtype=torch.uint8, device='cuda')
+    big = torch.zeros(3 * 8192, dtype=torch.uint8, device='cuda')
+    assert refused(lib.svc_render_crops_u8_to_nv12(engine._h, vp(wide), 1, 2, 8192, vp(box), 8192, 2, vp(big), 2, 4000, 0, None))
+    assert b'LDS' in lib.svc_last_error()
+    assert lib.svc_render_crops_u8_to_nv12(engine._h, vp(wide), 1, 2, 8192, vp(box), 8192, 2, vp(big), 2, 1000, 0, None) == 0
+    assert lib.svc_render_crops_u8_to_nv12(engine._h, vp(wide), 1, 2, 8192, vp(box), 8192, 2, vp(big), 2, 8192, 0, None) == 0
+    torch.cuda.synchronize()
+    assert (big[:2 * 8192] == 16).all() and (big[2 * 8192:] == 128).all()          # black, the copy's bytes
+    d = torch.zeros((1, 36, 64, 3), dtype=torch.uint8, device='cuda')
+    with pytest.raises(ValueError):
+        engine.render_crops(d, np.array([[1, 1, 26, 15]], np.int32), out_fmt='nv12')
+    with pytest.raises(ValueError):
+        engine.render_crops(d, np.array([[1, 1, 25, 15]], np.int32), bgr=True, out_fmt='nv12')
+    for pix_fmt, src in (('rgb24', d), ('nv12', torch.zeros((1, 54, 64), dtype=torch.uint8, device='cuda'))):
+        engine.profile_enable('render')
+        engine.render_crops(src, np.array([[1, 1, 25, 15]], np.int32), pix_fmt=pix_fmt, out_fmt='nv12')
+        engine.render_crops(src, np.array([[1, 1, 25, 15]], np.int32), out_hw=(8, 10), pix_fmt=pix_fmt, out_fmt='nv12')
+        assert engine.profile_read()[1] == 2                         # counted under SVC_K_RENDER
+        engine.profile_enable(None)
+    assert engine.render_crops(d[:0], np.zeros((0, 4), np.int32), out_fmt='nv12').shape == (0, 3, 2)
+
+
+@pytest.mark.parametrize('pix_fmt', SOURCES)
+def test_render_video(engine, pix_fmt):
+    """13 frames in chunks of 5 (both ring slots are used twice), from host memory and from the device, with a sink and
+    without: every frame is the single call's."""
+    n, h, w = 13, 90, 160
+    fed, rgb = _frames(pix_fmt, n, h, w, seed=7)
+    for (bw, bh), out_size in (((48, 90), None), ((49, 89), (40, 72))):
+        VD = dict(fc=n, bbs_np=_boxes(n, h, w, bw, bh, seed=5).astype(np.int64))
+        ow, oh = out_size or (bw, bh)
+        want = engine.render_crops(torch.from_numpy(fed).cuda(), VD['bbs_np'].astype(np.int32), out_hw=(oh, ow), pix_fmt=pix_fmt,
+                                   out_fmt='nv12').cpu().numpy()
+        if out_size is None:
+            assert np.array_equal(want, forward(_slices(rgb, VD['bbs_np'])))
+        for cont in (fed, torch.from_numpy(fed).cuda()):
+            got = render.render_video(cont, VD, engine=engine, out_size=out_size, chunk=5, pix_fmt=pix_fmt, out_fmt='nv12')
+            assert got.shape == (n, oh * 3 // 2, ow) and np.array_equal(got, want)
+            chunks = []
+            assert render.render_video(cont, VD, engine=engine, out_size=out_size, chunk=5, pix_fmt=pix_fmt, out_fmt='nv12',
+                                       sink=lambda c: chunks.append(c.copy())) is None
+            assert [c.shape[0] for c in chunks] == [5, 5, 3] and np.array_equal(np.concatenate(chunks), want)
+        # the ring goes back to RGB slots (keyed by the format)
+        back = render.render_video(fed, VD, engine=engine, out_size=out_size, chunk=5, pix_fmt=pix_fmt)
+        assert back.shape == (n, oh, ow, 3)
+        if out_size is None:
+            assert np.array_equal(back, _slices(rgb, VD['bbs_np']))
+    with pytest.raises(ValueError):
+        render.render_video(fed, dict(fc=n, bbs_np=_boxes(n, h, w, 49, 89, seed=5)), engine=engine, pix_fmt=pix_fmt, out_fmt='nv12')
+
+
+@pytest.mark.parametrize('pix_fmt', SOURCES)
+def test_smart_vid_crop_writes_a_raw_nv12_stream(engine, tmp_path, pix_fmt):
+    torch.set_num_threads(8)
+    n, h, w = 40, 360, 640
+    frames = synth.blob_frames(n, h, w, seed=4)
+    video = dict(fr=30.0, frame_count=n, w=w, h=h, trans_inds=[0, n], frames=frames)
+    if pix_fmt == 'nv12':
+        video = dict(video, frames=nv12_ref.rgb_to_nv12(frames), pix_fmt='nv12')
+    CP = dict(S.sc_init_crop_params(), out_ratio='1:3')
+    path = str(tmp_path / 'clip.nv12')
+    calls = []
+
+    def factory(*a, **k):
+        calls.append((a, k))
+        return ingest.write_frames_raw(*a, **k)
+
+    S.set_video_writer(factory)
+    try:
+        VD, res = S.smart_vid_crop(video, CP, final_vid_fn=path, out_size=(100, 300), out_pix_fmt='nv12', engine=engine)
+        assert calls == [((path, VD['fr'], (100, 300)), dict(pix_fmt='nv12'))] and 't_render' in res
+        want = render.render_video(video, VD, engine=engine, out_size=(100, 300), out_fmt='nv12')
+        with open(path, 'rb') as fp:
+            data = fp.read()
+        assert len(data) == n * 100 * 300 * 3 // 2 and data == want.tobytes()
+        i = n // 2
+        x1, y1, x2, y2 = VD['bbs_np'][i]
+        rgb = frames if pix_fmt == 'rgb24' else nv12_ref.nv12_to_rgb(video['frames'], h, w)
+        assert np.array_equal(want[i], forward(cv_ref.resize_linear_u8(np.ascontiguousarray(rgb[i, y1:y2, x1:x2]), 300, 100)))
+        # the default format calls the factory exactly as before
+        del calls[:]
+        S.smart_vid_crop(video, CP, final_vid_fn=str(tmp_path / 'clip.rgb'), out_size=(100, 300), engine=engine)
+        assert calls == [((str(tmp_path / 'clip.rgb'), VD['fr'], (100, 300)), {})]
+        with open(str(tmp_path / 'clip.rgb'), 'rb') as fp:
+            assert fp.read() == render.render_video(video, VD, engine=engine, out_size=(100, 300)).tobytes()
+    finally:
+        S.set_video_writer(None)

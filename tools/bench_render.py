@@ -6,7 +6,12 @@
   * render_video from host memory: frames/s for a --frames-frame 1080p numpy video (native 9:16 windows), beside the bare
     H2D of the frames and D2H of the crops (same bytes, same pinned-buffer sizes) timed in the same run.
 
-usage: python tools/bench_render.py [--launches 200] [--frames 300]
+  * --nv12-out: the NV12-output entries (svc_render_crops_u8_to_nv12 / _nv12_to_nv12) beside the RGB-output ones, same
+    geometries, both sources, same method; and render_video end to end on the host-fed 1080p case with RGB and with NV12
+    output.  The two outputs alternate --rounds times in one process, so that the run-to-run spread is visible next to
+    their difference.
+
+usage: python tools/bench_render.py [--launches 200] [--frames 300] [--nv12-out [--rounds 3]] [--out file.json]
 A rocprofv3 --kernel-trace --stats run of its own gives the per-kernel durations without the event overhead."""
 import argparse
 import json
@@ -63,6 +68,70 @@ def kernel_times(eng, launches):
     return out
 
 
+def _event_ms(fn, launches):
+    for _ in range(10):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(launches):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / launches
+
+
+def nv12_out_kernel_times(eng, launches, rounds):
+    """Per geometry and source: ms per 32-frame launch with RGB output and with NV12 output, `rounds` values each, measured
+    alternately; bytes per frame = window bytes read (in the source's format) + bytes written."""
+    out = {}
+    n = 32
+    for name, (h, w), (bw, bh), osz in GEOMETRIES:
+        ow, oh = osz or (bw, bh)
+        boxes = torch.from_numpy(boxes_for(n, h, w, bw, bh)).to(eng.device)
+        for src in ops.PIX_FMTS:
+            frames = torch.randint(0, 256, (n,) + ops.frame_shape(src, h, w), dtype=torch.uint8, device=eng.device)
+            dst = {f: torch.empty((n,) + ops.frame_shape(f, oh, ow), dtype=torch.uint8, device=eng.device) for f in ops.OUT_FMTS}
+            ms = {f: [] for f in ops.OUT_FMTS}
+            for _ in range(rounds):
+                for f in ops.OUT_FMTS:
+                    ms[f].append(round(_event_ms(lambda: eng._render(frames, boxes, bw, bh, dst[f], False, src, f), launches), 4))
+            px_in = 3.0 if src == 'rgb24' else 1.5
+            row = dict(ms_per_32_rgb_out=ms['rgb24'], ms_per_32_nv12_out=ms['nv12'],
+                       nv12_over_rgb=round(float(np.median(ms['nv12']) / np.median(ms['rgb24'])), 3))
+            for f, px_out in (('rgb24', 3.0), ('nv12', 1.5)):
+                moved = n * (bw * bh * px_in + ow * oh * px_out)
+                row['bytes_per_frame_%s_out' % f.replace('24', '')] = int(moved // n)
+                row['eff_tbs_%s_out' % f.replace('24', '')] = round(moved / (float(np.median(ms[f])) * 1e-3) / 1e12, 3)
+            out['%s_from_%s' % (name, src)] = row
+            del frames, dst
+            torch.cuda.empty_cache()
+    return out
+
+
+def nv12_out_host_fed(eng, nf, rounds):
+    """render_video end to end, host-fed 1080p numpy at native 608 x 1080 windows: seconds with RGB and with NV12 output,
+    alternating."""
+    h, w, bw, bh = 1080, 1920, 608, 1080
+    frames = np.random.RandomState(1).randint(0, 256, (nf, h, w, 3), dtype=np.uint8)
+    VD = dict(fc=nf, bbs_np=boxes_for(nf, h, w, bw, bh, seed=2).astype(np.int64))
+    sink = lambda c: None
+    secs = {f: [] for f in ops.OUT_FMTS}
+    for f in ops.OUT_FMTS:                                        # warm-up (buffers of both formats' sizes)
+        render.render_video(frames[:40], dict(fc=40, bbs_np=VD['bbs_np'][:40]), engine=eng, sink=sink, out_fmt=f)
+    for _ in range(rounds):
+        for f in ops.OUT_FMTS:
+            render.render_video(frames[:40], dict(fc=40, bbs_np=VD['bbs_np'][:40]), engine=eng, sink=sink, out_fmt=f)   # (the ring is re-made per format)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            render.render_video(frames, VD, engine=eng, sink=sink, out_fmt=f)
+            torch.cuda.synchronize()
+            secs[f].append(round(time.perf_counter() - t0, 4))
+    return dict(frames=nf, render_s_rgb_out=secs['rgb24'], render_s_nv12_out=secs['nv12'],
+                fps_rgb_out=round(nf / float(np.median(secs['rgb24'])), 1), fps_nv12_out=round(nf / float(np.median(secs['nv12'])), 1),
+                d2h_bytes_per_frame=dict(rgb_out=bw * bh * 3, nv12_out=bw * bh * 3 // 2))
+
+
 def host_fed(eng, nf):
     h, w, bw, bh = 1080, 1920, 608, 1080
     frames = np.random.RandomState(1).randint(0, 256, (nf, h, w, 3), dtype=np.uint8)
@@ -104,13 +173,27 @@ def main():
     ap.add_argument('--launches', type=int, default=200)
     ap.add_argument('--frames', type=int, default=300)
     ap.add_argument('--skip-host', action='store_true')
+    ap.add_argument('--nv12-out', action='store_true', help='measure the NV12-output entries beside the RGB-output ones')
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--out', help='also write the JSON to this file')
     args = ap.parse_args()
     torch.cuda.set_device(0)
     eng = ops.Engine(device=0)
-    res = dict(kernels=kernel_times(eng, args.launches))
-    if not args.skip_host:
-        res['host_fed_1080p_9x16'] = host_fed(eng, args.frames)
+    if args.nv12_out:
+        res = dict(method='32-frame batch resident in HBM, 10 warm-up launches, device events over %d launches; RGB and NV12 output '
+                          'alternated %d times in one process' % (args.launches, args.rounds),
+                   kernels=nv12_out_kernel_times(eng, args.launches, args.rounds))
+        if not args.skip_host:
+            res['host_fed_1080p_9x16'] = nv12_out_host_fed(eng, args.frames, args.rounds)
+    else:
+        res = dict(kernels=kernel_times(eng, args.launches))
+        if not args.skip_host:
+            res['host_fed_1080p_9x16'] = host_fed(eng, args.frames)
     print(json.dumps(res))
+    if args.out:
+        with open(args.out, 'w') as fp:
+            json.dump(res, fp, indent=1)
+            fp.write('\n')
     eng.close()
 
 
