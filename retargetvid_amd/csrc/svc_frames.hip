@@ -1,12 +1,16 @@
-// svc_frames.hip — frame I/O for gfx950: the ingest down-scale and the renderer, on packed RGB and on NV12 frames.
-// Every kernel is written once and takes its pixels from a source (SrcRgb, SrcNv12 below); the INTER_LINEAR rule is
-// svc_cvlinear.h's.
+// svc_frames.hip — frame I/O for gfx950: the ingest down-scale and the renderer, from packed RGB and NV12 frames, the
+// renderer to packed RGB / BGR and to NV12.  Every kernel is written once: it takes its pixels from a source (SrcRgb, SrcNv12)
+// and the render kernels hand theirs to a sink (DstRgb<BGR>, DstNv12); the INTER_LINEAR rule is svc_cvlinear.h's.  The one
+// pair that is two bodies is the copy path's vector kernel, whose decomposition of the output is the sink's own.
 //
 // Reference semantics restated per kernel (paths relative to the reference tree):
 //   k_cv_resize      cv2.resize(INTER_LINEAR)         smartVidCrop.py:333-335, :633-635
 //   k_render_*       frame[by1:by2, bx1:bx2, :] (+ cv2.resize INTER_LINEAR, + RGB2BGR)  smartVidCrop.py:1801-1921
+//     k_render_copy_to_rgb, k_render_copy_to_nv12    the copy's vector kernels, one per sink
+//     k_render_copy_px<Src, Dst>                     the copy for everything they leave
+//     k_render_resize<Src, Dst>                      the resampled crop
 //   SrcNv12          BT.601 conversion fused into both (no counterpart: the reference is handed RGB)
-//   k_render_*_yuv   the same crops written as NV12, the forward BT.601 transform fused in (no counterpart: the reference hands RGB to its writer)
+//   DstNv12          the same crops written as NV12, the forward BT.601 transform fused in (no counterpart: the reference hands RGB to its writer)
 #include <algorithm>
 
 #include "svc_cvlinear.h"
@@ -315,16 +319,28 @@ __device__ __forceinline__ void render_origin(const int32_t *__restrict__ boxes,
     y0 = min(max(boxes[4 * f + 1], 0), height - bh);
 }
 
-// Copy path (output size == window size), bw >= 16, frames and out 16-aligned.  The output is one packed run of pixels;
+// nb bytes of an output row from LDS (orow, at the phase of dst: orow & 15 == dst & 15) to dst by the whole workgroup: aligned
+// 16-byte stores; bytes [0, head) and [head + 16 * nw, nb) are partial 16-byte words of the output: bytewise
+__device__ __forceinline__ void row_out(uint8_t *__restrict__ dst, const uint8_t *orow, int nb) {
+    const int head = min(nb, (16 - (int)((uintptr_t)dst & 15)) & 15), nw = (nb - head) >> 4;
+    const uint4 *src4 = (const uint4 *)(orow + head);
+    uint4 *dst4 = (uint4 *)(dst + head);
+    for (int i = threadIdx.x; i < nw; i += 256) dst4[i] = src4[i];
+    for (int i = threadIdx.x; i < head; i += 256) dst[i] = orow[i];
+    for (int i = head + 16 * nw + threadIdx.x; i < nb; i += 256) dst[i] = orow[i];
+}
+
+// The two vector kernels of the copy path (output size == window size), one per sink; frames and out are 16-aligned.
+// To RGB, bw >= 16.  The output is one packed run of pixels;
 // thread g owns output pixels [16 g, 16 g + 16) = bytes [48 g, 48 g + 48), written as three aligned 16-byte stores.  The
 // group's source is one run of 16 pixels of the window row it starts in (Src::px16), and when the group runs over the end
 // of that row, the rest comes from the next window row (of this frame or the next one) through a second run, placed so
 // that its pixel k is the first of that row, merged in by byte mask.
 template <class Src, bool BGR>
-__global__ __launch_bounds__(256) void k_render_copy(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
-                                                     const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
-                                                     long long total_px, const uint8_t *in_end) {
-    const long long p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 16;
+__global__ __launch_bounds__(256) void k_render_copy_to_rgb(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                            const int32_t *__restrict__ boxes, int n, int height, int width, int bh,
+                                                            int bw, const uint8_t *in_end) {
+    const long long total_px = (long long)n * bh * bw, p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 16;
     if (p0 >= total_px) return;
     const size_t fstride = Src::frame_bytes(height, width);
     const long long R = p0 / bw;
@@ -362,138 +378,9 @@ __global__ __launch_bounds__(256) void k_render_copy(const uint8_t *__restrict__
     }
 }
 
-// Copy path for narrow windows (bw < 16) or unaligned buffers: one thread per output pixel, byte loads.
-template <class Src, bool BGR>
-__global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
-                                                        const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
-                                                        long long total_px) {
-    const long long px = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (px >= total_px) return;
-    const long long R = px / bw;
-    const int col = (int)(px - R * bw), f = (int)(R / bh), r = (int)(R - (long long)f * bh);
-    int x0, y0;
-    render_origin(boxes, f, height, width, bh, bw, x0, y0);
-    const uint32_t v = Src::template px<BGR>(in + f * Src::frame_bytes(height, width), height, width, y0 + r, x0 + col);
-    uint8_t *d = out + px * 3;
-    d[0] = (uint8_t)v;
-    d[1] = (uint8_t)(v >> 8);
-    d[2] = (uint8_t)(v >> 16);
-}
-
-// nb bytes of an output row from LDS (orow, at the phase of dst: orow & 15 == dst & 15) to dst by the whole workgroup: aligned
-// 16-byte stores; bytes [0, head) and [head + 16 * nw, nb) are partial 16-byte words of the output: bytewise
-__device__ __forceinline__ void row_out(uint8_t *__restrict__ dst, const uint8_t *orow, int nb) {
-    const int head = min(nb, (16 - (int)((uintptr_t)dst & 15)) & 15), nw = (nb - head) >> 4;
-    const uint4 *src4 = (const uint4 *)(orow + head);
-    uint4 *dst4 = (uint4 *)(dst + head);
-    for (int i = threadIdx.x; i < nw; i += 256) dst4[i] = src4[i];
-    for (int i = threadIdx.x; i < head; i += 256) dst[i] = orow[i];
-    for (int i = head + 16 * nw + threadIdx.x; i < nb; i += 256) dst[i] = orow[i];
-}
-
-// Resize path: k_cv_resize's arithmetic on a window of the full frame.  One workgroup = one output row of one frame: the
-// two window rows it reads are staged in LDS as RGB (Src::stage_row; R and B are never swapped before the store), the
-// output row is assembled in LDS at the output's own 16-byte phase and written with aligned 16-byte stores (the partial
-// words at both ends bytewise).  LDS: two source rows of span_cap bytes, then the output row (ow * 3 + 16 bytes).
-template <class Src, bool BGR>
-__global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
-                                                       const int *__restrict__ tab, const int32_t *__restrict__ boxes, int f0,
-                                                       int height, int width, int bh, int bw, int oh, int ow, int span_cap,
-                                                       const uint8_t *in_end, int vec) {
-    extern __shared__ __align__(16) uint8_t sm_rr[];
-    const CvLinear T(tab, oh, ow);
-    const int oy = blockIdx.x, f = f0 + blockIdx.y;
-    int x0, y0;
-    render_origin(boxes, f, height, width, bh, bw, x0, y0);
-    int ry[2], b0, b1;
-    T.row(oy, bh, ry[0], ry[1], b0, b1);
-    const uint8_t *fr = in + f * Src::frame_bytes(height, width);
-    int sh[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-        sh[k] = Src::stage_row(fr, height, width, y0 + ry[k], x0, bw, sm_rr + k * span_cap, span_cap, in_end, vec);
-    uint8_t *dst = out + ((size_t)blockIdx.y * oh + oy) * ow * 3;
-    const int ph = (int)((uintptr_t)dst & 15);
-    uint8_t *orow = sm_rr + 2 * span_cap + ph;
-    __syncthreads();
-    const uint8_t *r0 = sm_rr + sh[0], *r1 = sm_rr + span_cap + sh[1];
-    for (int ox = threadIdx.x; ox < ow; ox += 256) {
-        int sx, sx1, a0, a1;
-        bool inner;
-        T.col(ox, bw, sx, sx1, a0, a1, inner);
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            orow[ox * 3 + (BGR ? 2 - c : c)] = CvLinear::blend(r0[sx * 3 + c], r0[sx1 * 3 + c], r1[sx * 3 + c], r1[sx1 * 3 + c],
-                                                               a0, a1, b0, b1, inner);
-    }
-    __syncthreads();
-    row_out(dst, orow, ow * 3);
-}
-
-template <class Src>
-static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
-                        int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    if (!h || n < 0 || (n > 0 && (!frames || !boxes || !out)) || !Src::size_ok(height, width) || bw < 1 || bh < 1 ||
-        bw > width || bh > height || oh < 1 || ow < 1 || (flags & ~SVC_RENDER_BGR)) {       // n = 0: a no-op, null buffers allowed
-        svc_set_error("%s: invalid argument%s", name, Src::size_rule());
-        return SVC_E_INVALID;
-    }
-    const int span_cap = (bw * 3 + 32 + 15) / 16 * 16;
-    const size_t lds = 2 * (size_t)span_cap + (size_t)ow * 3 + 16;
-    const bool copy = oh == bh && ow == bw;
-    if (!copy && lds > 65536) {
-        svc_set_error("%s: window %dx%d -> %dx%d needs %zu bytes of LDS per output row (> 64 KiB)", name, bw, bh, ow, oh, lds);
-        return SVC_E_INVALID;
-    }
-    if (n == 0) return SVC_OK;
-    SVC_HIP(hipSetDevice(h->device));
-    const bool bgr = (flags & SVC_RENDER_BGR) != 0;
-    const uint8_t *in_end = frames + n * Src::frame_bytes(height, width);
-    const bool aligned_in = ((uintptr_t)frames & 15) == 0, aligned_out = ((uintptr_t)out & 15) == 0;
-    hipStream_t s = (hipStream_t)stream;
-    const int *tab = nullptr;
-    if (!copy) {
-        int rc = cv_tab(h, bh, bw, oh, ow, &tab);
-        if (rc) return rc;
-    }
-    ProfScope ps(h, SVC_K_RENDER, s);
-    if (copy) {
-        const long long total_px = (long long)n * bh * bw;
-        if (bw >= 16 && aligned_in && aligned_out) {
-            const unsigned grid = (unsigned)((total_px + 16 * 256 - 1) / (16 * 256));
-            if (bgr) k_render_copy<Src, true><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px, in_end);
-            else k_render_copy<Src, false><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px, in_end);
-        } else {
-            const unsigned grid = (unsigned)((total_px + 255) / 256);
-            if (bgr) k_render_copy_px<Src, true><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px);
-            else k_render_copy_px<Src, false><<<grid, 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total_px);
-        }
-        SVC_CHECK_LAUNCH();
-        return SVC_OK;
-    }
-    for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
-        const int nf = std::min(n - f0, 65535);
-        uint8_t *o = out + (size_t)f0 * oh * ow * 3;
-        const dim3 grid((unsigned)oh, (unsigned)nf);
-        if (bgr) k_render_resize<Src, true><<<grid, 256, lds, s>>>(frames, o, tab, boxes, f0, height, width, bh, bw, oh, ow, span_cap, in_end, aligned_in);
-        else k_render_resize<Src, false><<<grid, 256, lds, s>>>(frames, o, tab, boxes, f0, height, width, bh, bw, oh, ow, span_cap, in_end, aligned_in);
-        SVC_CHECK_LAUNCH();
-    }
-    return SVC_OK;
-}
-
-extern "C" int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
-                                   int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops<SrcRgb>("svc_render_crops_u8", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
-}
-extern "C" int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
-                                     int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops<SrcNv12>("svc_render_crops_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
-}
-
 // --------------------------------------------------------------------------------------
 // render to NV12 (no counterpart in the reference, whose renderer hands RGB / BGR to OpenCV's writer).  The RGB crop C of a
-// frame is exactly what the kernels above produce (same window rules, same clamping, the copy or the INTER_LINEAR
+// frame is exactly what the RGB output is (same window rules, same clamping, the copy or the INTER_LINEAR
 // resampling); the output frame u8 [oh * 3 / 2][ow] (oh, ow even) is BT.601 limited range of C in 20-bit fixed point, int32:
 //   Y[y][x] = (269484 r + 528482 g + 102760 b + (16 << 20) + (1 << 19)) >> 20
 //   U[j][i] = (-155188 sr - 305135 sg + 460324 sb + (128 << 22) + (1 << 21)) >> 22      sr, sg, sb = sums over the 2 x 2 block
@@ -545,17 +432,17 @@ __device__ __forceinline__ void st16_a8(uint8_t *d, const uint32_t (&v)[4], bool
     else { *(uint2 *)d = make_uint2(v[0], v[1]); *(uint2 *)(d + 8) = make_uint2(v[2], v[3]); }
 }
 
-// Copy path, bw % 8 == 0, bw >= 16, frames and out 16-aligned (every output row, luma or chroma, then starts on 8 bytes).
+// To NV12, bw % 8 == 0, bw >= 16 (every output row, luma or chroma, then starts on 8 bytes).
 // Thread t owns the strip of window rows 2j, 2j + 1 by pixels [16 g, 16 g + 16) (the last strip of a row is 8 wide when
 // bw % 16 == 8): two runs through Src::px16 (odd x, odd y and the frame's end are its business; the pixels past the window
 // are converted and dropped), 32 luma bytes and the strip's 8 interleaved chroma pairs, each row of it as one aligned store.
 template <class Src>
-__global__ __launch_bounds__(256) void k_render_copy_yuv(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
-                                                         const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
-                                                         long long total, const uint8_t *in_end) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= total) return;
+__global__ __launch_bounds__(256) void k_render_copy_to_nv12(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                             const int32_t *__restrict__ boxes, int n, int height, int width, int bh,
+                                                             int bw, const uint8_t *in_end) {
     const int G = (bw + 15) >> 4, hb = bh >> 1;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)n * hb * G) return;
     const long long R = t / G;
     const int g = (int)(t - R * G), f = (int)(R / hb), j = (int)(R - (long long)f * hb);
     int x0, y0;
@@ -579,113 +466,203 @@ __global__ __launch_bounds__(256) void k_render_copy_yuv(const uint8_t *__restri
     st16_a8(o + (size_t)(bh + j) * bw, uv, half);
 }
 
-// Copy path for everything else (narrow windows, other widths, unaligned buffers): one thread per 2 x 2 block, byte accesses.
-template <class Src>
-__global__ __launch_bounds__(256) void k_render_copy_yuv_px(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
-                                                            const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
-                                                            long long total) {
+// --------------------------------------------------------------------------------------
+// Pixel sinks: what the render kernels ask of an output format.  The crop is RGB (in the sink's channel order `bgr`) until
+// a sink stores it.
+//   size_ok, size_rule       the pictures the format can hold, and the words the error text says it with
+//   flags_ok, flags_rule     the same for the SVC_RENDER_* flags
+//   frame_bytes              bytes of one frame
+//   rows                     B: a thread of the per-pixel copy owns a B x B block of the crop, a resize workgroup B output rows
+//   put_block                block (j, i) of the frame at `fo` from its pixels p[B * B] (row-major, as Src::px gives them)
+//   vec_ok, vec_threads,     the copy path's vector kernel: the window widths it takes when both buffers are 16-aligned, its
+//   vec_copy<Src>            threads, the kernel
+//   lds_bytes                LDS of the resize kernel behind the two staged window rows
+//   out_rows, dst_rows       the output rows that rows B j .. B j + B - 1 of the crop become (frame fy of `out`): how many, where
+//   rgb_row                  where in that LDS row r of the workgroup's B rows is resampled to
+//   rows_out                 the B resampled rows -> the output rows, by the whole workgroup (called behind a barrier)
+// --------------------------------------------------------------------------------------
+template <bool BGR>
+struct DstRgb {                                 // u8 [oh][ow][3]
+    static constexpr bool bgr = BGR;
+    static constexpr int rows = 1;
+    static bool size_ok(int oh, int ow) { return oh >= 1 && ow >= 1; }
+    static const char *size_rule() { return "an RGB output has width and height >= 1"; }
+    static bool flags_ok(int flags) { return !(flags & ~SVC_RENDER_BGR); }
+    static const char *flags_rule() { return "flags has bits other than SVC_RENDER_BGR"; }
+    __host__ __device__ static size_t frame_bytes(int oh, int ow) { return (size_t)oh * ow * 3; }
+    static bool vec_ok(int bw) { return bw >= 16; }
+    static long long vec_threads(int n, int bh, int bw) { return ((long long)n * bh * bw + 15) / 16; }
+    template <class Src>
+    static auto vec_copy() { return k_render_copy_to_rgb<Src, BGR>; }
+    static size_t lds_bytes(int ow) { return (size_t)ow * 3 + 16; }
+
+    __device__ __forceinline__ static void put_block(uint8_t *fo, int oh, int ow, int j, int i, const uint32_t (&p)[1]) {
+        uint8_t *d = fo + ((size_t)j * ow + i) * 3;
+        d[0] = (uint8_t)p[0];
+        d[1] = (uint8_t)(p[0] >> 8);
+        d[2] = (uint8_t)(p[0] >> 16);
+    }
+    // the row is resampled at the output row's own 16-byte phase and stored as it is
+    static constexpr int out_rows = 1;
+    __device__ __forceinline__ static void dst_rows(uint8_t *out, int fy, int oh, int ow, int j, uint8_t *(&dst)[1]) {
+        dst[0] = out + ((size_t)fy * oh + j) * ow * 3;
+    }
+    __device__ __forceinline__ static uint8_t *rgb_row(uint8_t *lds, uint8_t *const (&dst)[1], int ow, int r) {
+        return lds + (int)((uintptr_t)dst[0] & 15);
+    }
+    __device__ __forceinline__ static void rows_out(uint8_t *lds, uint8_t *const (&dst)[1], int ow) {
+        row_out(dst[0], rgb_row(lds, dst, ow, 0), ow * 3);
+    }
+};
+
+struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the formula above
+    static constexpr bool bgr = false;
+    static constexpr int rows = 2;
+    static bool size_ok(int oh, int ow) { return oh >= 2 && ow >= 2 && !(oh & 1) && !(ow & 1); }
+    static const char *size_rule() {
+        return "width and height of an NV12 output are even and >= 2; a window of odd size needs an even output size";
+    }
+    static bool flags_ok(int flags) { return flags == 0; }
+    static const char *flags_rule() { return "flags must be 0 (SVC_RENDER_BGR has no meaning for an NV12 output)"; }
+    __host__ __device__ static size_t frame_bytes(int oh, int ow) { return (size_t)(oh + oh / 2) * ow; }
+    static bool vec_ok(int bw) { return bw >= 16 && bw % 8 == 0; }
+    static long long vec_threads(int n, int bh, int bw) { return (long long)n * (bh / 2) * ((bw + 15) / 16); }
+    template <class Src>
+    static auto vec_copy() { return k_render_copy_to_nv12<Src>; }
+    // two RGB rows of rgb_cap bytes, then three output rows (two of luma, one of chroma) of row_cap bytes
+    __host__ __device__ static int rgb_cap(int ow) { return (ow * 3 + 15) / 16 * 16; }
+    __host__ __device__ static int row_cap(int ow) { return (ow + 15) / 16 * 16 + 16; }
+    static size_t lds_bytes(int ow) { return 2 * (size_t)rgb_cap(ow) + 3 * (size_t)row_cap(ow); }
+
+    __device__ __forceinline__ static void put_block(uint8_t *fo, int oh, int ow, int j, int i, const uint32_t (&p)[4]) {
+        uint8_t *d0 = fo + (size_t)(2 * j) * ow + 2 * i, *d1 = d0 + ow, *dc = fo + (size_t)(oh + j) * ow + 2 * i;
+        const uint32_t c = rgb_chroma(p[0], p[1], p[2], p[3]);
+        d0[0] = (uint8_t)rgb_luma(p[0]);
+        d0[1] = (uint8_t)rgb_luma(p[1]);
+        d1[0] = (uint8_t)rgb_luma(p[2]);
+        d1[1] = (uint8_t)rgb_luma(p[3]);
+        dc[0] = (uint8_t)c;
+        dc[1] = (uint8_t)(c >> 8);
+    }
+    static constexpr int out_rows = 3;
+    __device__ __forceinline__ static void dst_rows(uint8_t *out, int fy, int oh, int ow, int j, uint8_t *(&dst)[3]) {
+        uint8_t *fo = out + (size_t)fy * (oh + (oh >> 1)) * ow;
+        dst[0] = fo + (size_t)(2 * j) * ow;
+        dst[1] = fo + (size_t)(2 * j + 1) * ow;
+        dst[2] = fo + (size_t)(oh + j) * ow;
+    }
+    __device__ __forceinline__ static uint8_t *rgb_row(uint8_t *lds, uint8_t *const (&dst)[3], int ow, int r) {
+        return lds + r * rgb_cap(ow);
+    }
+    // every 2 x 2 block of the two RGB rows is converted into the three output rows, each at the 16-byte phase of its
+    // place in the output
+    __device__ __forceinline__ static void rows_out(uint8_t *lds, uint8_t *const (&dst)[3], int ow) {
+        const int cap = rgb_cap(ow);
+        uint8_t *lrow[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) lrow[k] = lds + 2 * cap + k * row_cap(ow) + (int)((uintptr_t)dst[k] & 15);
+        for (int i = threadIdx.x; 2 * i < ow; i += 256) {
+            const uint8_t *s0 = lds + 6 * i, *s1 = s0 + cap;
+            const uint32_t p0 = s0[0] | (s0[1] << 8) | (s0[2] << 16), p1 = s0[3] | (s0[4] << 8) | (s0[5] << 16);
+            const uint32_t p2 = s1[0] | (s1[1] << 8) | (s1[2] << 16), p3 = s1[3] | (s1[4] << 8) | (s1[5] << 16);
+            const uint32_t c = rgb_chroma(p0, p1, p2, p3);
+            lrow[0][2 * i] = (uint8_t)rgb_luma(p0);
+            lrow[0][2 * i + 1] = (uint8_t)rgb_luma(p1);
+            lrow[1][2 * i] = (uint8_t)rgb_luma(p2);
+            lrow[1][2 * i + 1] = (uint8_t)rgb_luma(p3);
+            lrow[2][2 * i] = (uint8_t)c;
+            lrow[2][2 * i + 1] = (uint8_t)(c >> 8);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) row_out(dst[k], lrow[k], ow);
+    }
+};
+
+// Copy path for everything the vector kernels leave (narrow windows, other widths, unaligned buffers): one thread per
+// B x B block of the crop (B = Dst::rows), byte accesses.
+template <class Src, class Dst>
+__global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                        const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
+                                                        long long total) {
+    constexpr int B = Dst::rows;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
-    const int wb = bw >> 1, hb = bh >> 1;
+    const int wb = bw / B, hb = bh / B;
     const long long R = t / wb;
     const int i = (int)(t - R * wb), f = (int)(R / hb), j = (int)(R - (long long)f * hb);
     int x0, y0;
     render_origin(boxes, f, height, width, bh, bw, x0, y0);
     const uint8_t *fr = in + f * Src::frame_bytes(height, width);
-    const int x = x0 + 2 * i, y = y0 + 2 * j;
-    const uint32_t p0 = Src::template px<false>(fr, height, width, y, x), p1 = Src::template px<false>(fr, height, width, y, x + 1);
-    const uint32_t p2 = Src::template px<false>(fr, height, width, y + 1, x), p3 = Src::template px<false>(fr, height, width, y + 1, x + 1);
-    uint8_t *o = out + (size_t)f * (bh + hb) * bw + 2 * i;
-    uint8_t *d0 = o + (size_t)(2 * j) * bw, *d1 = d0 + bw, *dc = o + (size_t)(bh + j) * bw;
-    const uint32_t c = rgb_chroma(p0, p1, p2, p3);
-    d0[0] = (uint8_t)rgb_luma(p0);
-    d0[1] = (uint8_t)rgb_luma(p1);
-    d1[0] = (uint8_t)rgb_luma(p2);
-    d1[1] = (uint8_t)rgb_luma(p3);
-    dc[0] = (uint8_t)c;
-    dc[1] = (uint8_t)(c >> 8);
+    uint32_t p[B * B];
+#pragma unroll
+    for (int k = 0; k < B * B; ++k) p[k] = Src::template px<Dst::bgr>(fr, height, width, y0 + B * j + k / B, x0 + B * i + k % B);
+    Dst::put_block(out + f * Dst::frame_bytes(bh, bw), bh, bw, j, i, p);
 }
 
-// Resize path.  One workgroup = output rows 2 j, 2 j + 1 of one frame: k_render_resize's staging and arithmetic once per
-// row, the two RGB rows kept in LDS; then every 2 x 2 block is converted into three LDS rows (two of luma, one of chroma),
-// each at the 16-byte phase of its place in the output, and row_out stores them.  LDS: two source rows of span_cap bytes,
-// two RGB rows of rgb_cap bytes, three output rows of row_cap bytes.
-template <class Src>
-__global__ __launch_bounds__(256) void k_render_resize_yuv(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
-                                                           const int *__restrict__ tab, const int32_t *__restrict__ boxes, int f0,
-                                                           int height, int width, int bh, int bw, int oh, int ow, int span_cap,
-                                                           int rgb_cap, int row_cap, const uint8_t *in_end, int vec) {
-    extern __shared__ __align__(16) uint8_t sm_ry[];
+// Resize path: k_cv_resize's arithmetic on a window of the full frame.  One workgroup = B output rows of one frame (B =
+// Dst::rows).  Per row, the two window rows it reads are staged in LDS as RGB (Src::stage_row; R and B are swapped only on
+// the way out of them) and resampled into the LDS row the sink names; then the sink stores its rows with aligned 16-byte
+// stores (row_out).  LDS: two source rows of span_cap bytes, then Dst::lds_bytes.
+template <class Src, class Dst>
+__global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                       const int *__restrict__ tab, const int32_t *__restrict__ boxes, int f0,
+                                                       int height, int width, int bh, int bw, int oh, int ow, int span_cap,
+                                                       const uint8_t *in_end, int vec) {
+    extern __shared__ __align__(16) uint8_t sm_rr[];
     const CvLinear T(tab, oh, ow);
     const int j = blockIdx.x, f = f0 + blockIdx.y;
     int x0, y0;
     render_origin(boxes, f, height, width, bh, bw, x0, y0);
     const uint8_t *fr = in + f * Src::frame_bytes(height, width);
-    uint8_t *rgb = sm_ry + 2 * span_cap;
-    for (int r = 0; r < 2; ++r) {
+    uint8_t *lds = sm_rr + 2 * span_cap, *dst[Dst::out_rows];
+    for (int r = 0; r < Dst::rows; ++r) {
         int ry[2], b0, b1, sh[2];
-        T.row(2 * j + r, bh, ry[0], ry[1], b0, b1);
+        T.row(Dst::rows * j + r, bh, ry[0], ry[1], b0, b1);
         if (r) __syncthreads();                                 // row 0's resampling has read the staged rows
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-            sh[k] = Src::stage_row(fr, height, width, y0 + ry[k], x0, bw, sm_ry + k * span_cap, span_cap, in_end, vec);
+            sh[k] = Src::stage_row(fr, height, width, y0 + ry[k], x0, bw, sm_rr + k * span_cap, span_cap, in_end, vec);
+        if (!r) Dst::dst_rows(out, blockIdx.y, oh, ow, j, dst);
+        uint8_t *orow = Dst::rgb_row(lds, dst, ow, r);
         __syncthreads();
-        const uint8_t *r0 = sm_ry + sh[0], *r1 = sm_ry + span_cap + sh[1];
-        uint8_t *orow = rgb + r * rgb_cap;
+        const uint8_t *r0 = sm_rr + sh[0], *r1 = sm_rr + span_cap + sh[1];
         for (int ox = threadIdx.x; ox < ow; ox += 256) {
             int sx, sx1, a0, a1;
             bool inner;
             T.col(ox, bw, sx, sx1, a0, a1, inner);
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                orow[ox * 3 + c] = CvLinear::blend(r0[sx * 3 + c], r0[sx1 * 3 + c], r1[sx * 3 + c], r1[sx1 * 3 + c], a0, a1, b0, b1, inner);
+                orow[ox * 3 + (Dst::bgr ? 2 - c : c)] = CvLinear::blend(r0[sx * 3 + c], r0[sx1 * 3 + c], r1[sx * 3 + c], r1[sx1 * 3 + c],
+                                                                        a0, a1, b0, b1, inner);
         }
     }
     __syncthreads();
-    uint8_t *frame_o = out + (size_t)blockIdx.y * (oh + (oh >> 1)) * ow;
-    uint8_t *dst[3] = {frame_o + (size_t)(2 * j) * ow, frame_o + (size_t)(2 * j + 1) * ow, frame_o + (size_t)(oh + j) * ow};
-    uint8_t *lrow[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) lrow[k] = rgb + 2 * rgb_cap + k * row_cap + (int)((uintptr_t)dst[k] & 15);
-    for (int i = threadIdx.x; 2 * i < ow; i += 256) {
-        const uint8_t *s0 = rgb + 6 * i, *s1 = s0 + rgb_cap;
-        const uint32_t p0 = s0[0] | (s0[1] << 8) | (s0[2] << 16), p1 = s0[3] | (s0[4] << 8) | (s0[5] << 16);
-        const uint32_t p2 = s1[0] | (s1[1] << 8) | (s1[2] << 16), p3 = s1[3] | (s1[4] << 8) | (s1[5] << 16);
-        const uint32_t c = rgb_chroma(p0, p1, p2, p3);
-        lrow[0][2 * i] = (uint8_t)rgb_luma(p0);
-        lrow[0][2 * i + 1] = (uint8_t)rgb_luma(p1);
-        lrow[1][2 * i] = (uint8_t)rgb_luma(p2);
-        lrow[1][2 * i + 1] = (uint8_t)rgb_luma(p3);
-        lrow[2][2 * i] = (uint8_t)c;
-        lrow[2][2 * i + 1] = (uint8_t)(c >> 8);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; ++k) row_out(dst[k], lrow[k], ow);
+    Dst::rows_out(lds, dst, ow);
 }
 
-template <class Src>
-static int render_crops_yuv(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
-                            int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+template <class Src, class Dst>
+static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                        int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
     if (!h || n < 0 || (n > 0 && (!frames || !boxes || !out)) || !Src::size_ok(height, width) || bw < 1 || bh < 1 ||
         bw > width || bh > height) {                                                       // n = 0: a no-op, null buffers allowed
         svc_set_error("%s: invalid argument%s", name, Src::size_rule());
         return SVC_E_INVALID;
     }
-    if (oh < 2 || ow < 2 || (oh & 1) || (ow & 1)) {
-        svc_set_error("%s: an NV12 output of %dx%d (width and height must be even and >= 2; a window of odd size needs an "
-                      "even output size)", name, ow, oh);
+    if (!Dst::size_ok(oh, ow)) {
+        svc_set_error("%s: an output of %dx%d (%s)", name, ow, oh, Dst::size_rule());
         return SVC_E_INVALID;
     }
-    if (flags) {
-        svc_set_error("%s: flags must be 0 (SVC_RENDER_BGR has no meaning for an NV12 output)", name);
+    if (!Dst::flags_ok(flags)) {
+        svc_set_error("%s: %s", name, Dst::flags_rule());
         return SVC_E_INVALID;
     }
-    const int span_cap = (bw * 3 + 32 + 15) / 16 * 16, rgb_cap = (ow * 3 + 15) / 16 * 16, row_cap = (ow + 15) / 16 * 16 + 16;
-    const size_t lds = 2 * (size_t)span_cap + 2 * (size_t)rgb_cap + 3 * (size_t)row_cap;
+    const int span_cap = (bw * 3 + 32 + 15) / 16 * 16;
+    const size_t lds = 2 * (size_t)span_cap + Dst::lds_bytes(ow);
     const bool copy = oh == bh && ow == bw;
     if (!copy && lds > 65536) {
-        svc_set_error("%s: window %dx%d -> %dx%d needs %zu bytes of LDS per pair of output rows (> 64 KiB)", name, bw, bh, ow, oh, lds);
+        svc_set_error("%s: window %dx%d -> %dx%d needs %zu bytes of LDS per %s (> 64 KiB)", name, bw, bh, ow, oh, lds,
+                      Dst::rows == 1 ? "output row" : "pair of output rows");
         return SVC_E_INVALID;
     }
     if (n == 0) return SVC_OK;
@@ -700,31 +677,40 @@ static int render_crops_yuv(const char *name, SvcHandle *h, const uint8_t *frame
     }
     ProfScope ps(h, SVC_K_RENDER, s);
     if (copy) {
-        if (bw >= 16 && bw % 8 == 0 && aligned_in && aligned_out) {
-            const long long total = (long long)n * (bh / 2) * ((bw + 15) / 16);
-            k_render_copy_yuv<Src><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total, in_end);
+        if (Dst::vec_ok(bw) && aligned_in && aligned_out) {
+            const unsigned grid = (unsigned)((Dst::vec_threads(n, bh, bw) + 255) / 256);
+            Dst::template vec_copy<Src>()<<<grid, 256, 0, s>>>(frames, out, boxes, n, height, width, bh, bw, in_end);
         } else {
-            const long long total = (long long)n * (bh / 2) * (bw / 2);
-            k_render_copy_yuv_px<Src><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total);
+            const long long total = (long long)n * (bh / Dst::rows) * (bw / Dst::rows);
+            k_render_copy_px<Src, Dst><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total);
         }
         SVC_CHECK_LAUNCH();
         return SVC_OK;
     }
     for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
-        const int nf = std::min(n - f0, 65535);
-        uint8_t *o = out + (size_t)f0 * (oh + oh / 2) * ow;
-        k_render_resize_yuv<Src><<<dim3((unsigned)(oh / 2), (unsigned)nf), 256, lds, s>>>(
-            frames, o, tab, boxes, f0, height, width, bh, bw, oh, ow, span_cap, rgb_cap, row_cap, in_end, aligned_in);
+        const dim3 grid((unsigned)(oh / Dst::rows), (unsigned)std::min(n - f0, 65535));
+        k_render_resize<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * Dst::frame_bytes(oh, ow), tab, boxes, f0, height, width,
+                                                         bh, bw, oh, ow, span_cap, in_end, aligned_in);
         SVC_CHECK_LAUNCH();
     }
     return SVC_OK;
 }
 
+extern "C" int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                                   int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    return (flags & SVC_RENDER_BGR ? render_crops<SrcRgb, DstRgb<true>> : render_crops<SrcRgb, DstRgb<false>>)(
+        "svc_render_crops_u8", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+}
+extern "C" int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
+                                     int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    return (flags & SVC_RENDER_BGR ? render_crops<SrcNv12, DstRgb<true>> : render_crops<SrcNv12, DstRgb<false>>)(
+        "svc_render_crops_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+}
 extern "C" int svc_render_crops_u8_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                            int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_yuv<SrcRgb>("svc_render_crops_u8_to_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops<SrcRgb, DstNv12>("svc_render_crops_u8_to_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }
 extern "C" int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                              int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_yuv<SrcNv12>("svc_render_crops_nv12_to_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops<SrcNv12, DstNv12>("svc_render_crops_nv12_to_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }

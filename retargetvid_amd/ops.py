@@ -30,6 +30,8 @@ def _need_cuda(t, dtype, name):
 RENDER_BGR = 1                       # svc_render_crops_u8 flag (include/svc.h: SVC_RENDER_BGR)
 PIX_FMTS = ('rgb24', 'nv12')         # input pixel formats: uint8 [n,h,w,3] RGB | uint8 [n,h*3/2,w] (include/svc.h: the _nv12 entries)
 OUT_FMTS = ('rgb24', 'nv12')         # the renderer's output formats: the same two shapes (include/svc.h: the _to_nv12 entries)
+RENDER_ENTRIES = {('rgb24', 'rgb24'): 'svc_render_crops_u8', ('nv12', 'rgb24'): 'svc_render_crops_nv12',        # (pix_fmt, out_fmt)
+                  ('rgb24', 'nv12'): 'svc_render_crops_u8_to_nv12', ('nv12', 'nv12'): 'svc_render_crops_nv12_to_nv12'}
 
 
 def frame_shape(pix_fmt, h, w):
@@ -147,15 +149,13 @@ class Engine:
         if out_fmt == 'nv12':
             on, oh, ow = picture_size(out, 'nv12')
             out_frame_shape(out_fmt, oh, ow, bgr)
-            assert tuple(boxes.shape) == (n, 4) and on == n
-            fn = self.lib.svc_render_crops_nv12_to_nv12 if pix_fmt == 'nv12' else self.lib.svc_render_crops_u8_to_nv12
-            _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out), oh, ow, 0, _stream()))
-            return out
-        out_frame_shape(out_fmt, 1, 1)
-        assert tuple(boxes.shape) == (n, 4) and out.shape[0] == n and out.shape[3] == 3
-        fn = self.lib.svc_render_crops_nv12 if pix_fmt == 'nv12' else self.lib.svc_render_crops_u8
-        _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out),
-                      int(out.shape[1]), int(out.shape[2]), RENDER_BGR if bgr else 0, _stream()))
+        else:
+            out_frame_shape(out_fmt, 1, 1)
+            assert out.shape[3] == 3
+            on, oh, ow = (int(v) for v in out.shape[:3])
+        assert tuple(boxes.shape) == (n, 4) and on == n
+        fn = getattr(self.lib, RENDER_ENTRIES[pix_fmt, out_fmt])
+        _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out), oh, ow, RENDER_BGR if bgr else 0, _stream()))
         return out
 
     # -- saliency ------------------------------------------------------------------------

@@ -231,3 +231,34 @@ def test_smart_vid_crop_writes_a_raw_nv12_stream(engine, tmp_path, pix_fmt):
             assert fp.read() == render.render_video(video, VD, engine=engine, out_size=(100, 300)).tobytes()
     finally:
         S.set_video_writer(None)
+
+
+@pytest.mark.parametrize('pix_fmt', SOURCES)
+@pytest.mark.parametrize('out_fmt', ops.OUT_FMTS)
+def test_resize_path_second_launch(engine, pix_fmt, out_fmt):
+    """65 537 frames of 4 x 4 through the resize path: one launch takes 65 535 frames, so frames 65 535 and 65 536 come from a
+    second one.  Frame i is a flat triple a_i in its left two columns and b_i in its right two (as RGB, or as Y U V); its
+    2 x 2 window sits at x = 0 (even i) or x = 2 (odd i), y = i % 3, and INTER_LINEAR of a flat window to 4 x 4 is flat, so a
+    wrong frame base, box index or output offset in the second launch is a wrong colour."""
+    n = 65537
+    i = np.arange(n)
+    a = np.stack([i & 255, (i >> 8) & 255, (37 + 101 * (i >> 16)) & 255], 1).astype(np.uint8)
+    b = a ^ np.uint8(0x5a)
+    px = np.repeat(np.stack([a, b], 1), 2, axis=1)[:, None]                    # [n, 1, 4, 3]: a a b b
+    if pix_fmt == 'nv12':
+        luma, chroma = px[..., 0], px[:, :, ::2, 1:].reshape(n, 1, 4)             # Y Y Y Y per row; U V U V per chroma row
+        fed = np.concatenate([np.broadcast_to(luma, (n, 4, 4)), np.broadcast_to(chroma, (n, 2, 4))], 1)
+        rgb = nv12_ref.nv12_to_rgb(fed, 4, 4)
+    else:
+        fed = rgb = np.ascontiguousarray(np.broadcast_to(px, (n, 4, 4, 3)))
+    x, y = 2 * (i & 1), i % 3
+    boxes = np.stack([x, y, x + 2, y + 2], 1).astype(np.int32)
+    exp = np.ascontiguousarray(np.broadcast_to(rgb[i, 0, x][:, None, None], (n, 4, 4, 3)))
+    if out_fmt == 'nv12':
+        exp = forward(exp)
+    flat = exp.reshape(n, -1)
+    assert (flat[1:] != flat[:-1]).any(1).all()                                # neighbouring frames differ
+    edge = flat[[0, 65534, 65535, 65536]]
+    assert all((edge[p] != edge[q]).any() for p in range(4) for q in range(p))
+    got = engine.render_crops(torch.from_numpy(np.ascontiguousarray(fed)).cuda(), boxes, out_hw=(4, 4), pix_fmt=pix_fmt, out_fmt=out_fmt)
+    assert np.array_equal(got.cpu().numpy(), exp)
