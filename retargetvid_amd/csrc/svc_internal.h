@@ -71,11 +71,27 @@ struct SvcTensor {
     size_t n;             // floats
 };
 
-// One folded layer of the static SALICON graph, in execution order (weights.fold_state_dict).
+// One folded layer of the static SALICON graph (weights.fold_state_dict): a 1x1 or a 3x3 depthwise convolution with its bias.
 struct SvcLayer {
-    enum Kind { STEM, PW, DW, GAUSS, ADAPT, SMOOTH } kind;
     int cin, cout, stride, relu6;
     SvcTensor w, b;
+};
+
+// An inverted-residual block (MobileNetV2.py:26-83): 1x1 expand (absent where t = 1) -> 3x3 depthwise -> 1x1 project.
+struct InvRes {
+    SvcLayer expand, dw, project;
+    bool has_expand;
+    int inp, oup, stride;
+};
+
+// The network by name, in the blob's tensor order; filled once by svc_create (svc_net.hip: fill_graph), read by forward_chunk.
+struct NetGraph {
+    SvcLayer stem;
+    InvRes block[17];                     // cnn.features.1 .. features.17: block[i] is features.(i + 1)
+    SvcLayer f18, skip2x_expand, skip2x_reduce, skip4x_expand, skip4x_reduce;
+    SvcTensor gauss;                      // raw parameters of the Gaussian priors (host copy: SvcHandle::gauss_params)
+    InvRes post_cnn, us2, post_us2;       // post_cnn, upsampling_2, post_upsampling_2
+    SvcLayer adapt, smooth;               // adaptation 64 -> 1; the smoothing kernel's phase table (w only)
 };
 
 struct DevBuf {
@@ -108,7 +124,7 @@ struct SvcHandle {
     int device = 0;
     DevBuf blob;
     std::vector<SvcTensor> tensors;
-    std::vector<SvcLayer> layers;
+    NetGraph net = {};                    // the layers by name (svc_net.hip: fill_graph)
     std::vector<float> gauss_params;      // coarse_gaussians_salicon [16][2][2]
     // network workspace + plan (svc_net.hip)
     NetPlan *plan = nullptr;
@@ -130,10 +146,9 @@ struct SvcHandle {
     uint8_t *depth_pinned = nullptr;   // pinned staging ring for the per-map round numbers
     unsigned depth_slot = 0;
     hipEvent_t depth_ev[8] = {};       // recorded behind the upload of a slot; waited on before the slot is rewritten
-    std::map<std::tuple<const void *, int, int, int>, DevBuf> lane_w;   // split-K layers' weights in lane order (svc_net.hip: lane_weights), keyed by (matrix, row stride, K, padded N)
-    std::map<std::tuple<const void *, int, int, int>, DevBuf> x3_w;     // split-bf16 copies of weight matrices (svc_net.hip: x3_weights), keyed by (matrix, row stride, K, 2 * padded N + order)
+    std::map<std::tuple<const void *, int, int, int, int>, DevBuf> w_copies;   // re-ordered copies of weight matrices, made on first use (svc_net.hip: weight_copy), keyed by (matrix, row stride, K, padded N, WForm)
     int mx = 6;                        // matrix pipe of the 1x1-convolution GEMMs: 6 = split-bf16 operands, six plane pairs on v_mfma_f32_32x32x16_bf16 (round 5, the default: a pass 1.42 -> 1.24 ms alone, 1.01 -> 0.87 ms with four passes sharing the chip, every parity gate unchanged); 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32, rounds 1-4: SVC_MX=f32).  The one kernel found to miscompute beside bf16 workgroups, the smoothing kernel, lost a product in a packed-instruction sequence of its bilinear stage: written with scalar instructions since (sd_bilinear)
-    bool sk_lane = true;               // k_pw_sk reads its weights from the lane-order copy: a wave's load is 1 KB contiguous instead of 32 rows x 32 B (SVC_SK_LANE=0: from the [N][K] matrix)
+    bool sk_lane = true;               // k_pw_sk / k_dwpw / k_pwpw read their fp32 weights from the lane-order copy (svc_net.hip: lane_form): a wave's load is 1 KB contiguous instead of 32 rows x 32 B (SVC_SK_LANE=0: from the [N][K] matrix)
     std::set<const void *> lds_attr_done;   // kernels whose dynamic-LDS limit has been raised on this handle's device
     int chunk = 32;                    // frames per network pass
     DevBuf census;                     // threshold census (svc_threshold_census): [4] u64 totals, then [chunk][4] u32 per-frame counts of the last pass

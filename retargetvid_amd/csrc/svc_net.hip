@@ -53,7 +53,7 @@ __device__ __forceinline__ void fma4(float4 &a, const float4 x, const float4 w) 
 // v_mfma_f32_32x32x2_f32; X3_NP = 9 keeps them).  Measured against float64 on the layers' shapes
 // (tools/micro/bf16x3_gemm.hip, profiles/r05_bf16x3_micro.txt): rms error 1.14e-7 (x6) / 1.14e-7 (x9) / 1.08e-7 (fp32
 // MFMA) of a unit-rms result on ReLU6-like inputs, 1.24 / 1.23 / 1.55e-7 on signed wide-range inputs.
-// Small pairs are accumulated first.  Weights are split ONCE per handle (round-to-nearest planes, x3_weights below);
+// Small pairs are accumulated first.  Weights are split ONCE per handle (round-to-nearest planes, k_x3_weights below);
 // activations are split in registers where a wave holds them anyway.
 // Operand convention: element j (0..7) of the fragment of lane (r, hh) in the 16-deep step q is
 //   k = 16 q + 8 (j >> 2) + 4 hh + (j & 3)
@@ -285,7 +285,7 @@ struct FrontArgs {
     int hks, vks;
     const float *lut;               // [3][256]
     const float *Wstem, *bstem;     // [32 out][32 taps], [32]
-    const float *Wstem_l, *Wp_l;    // lane-order copies of Wstem and Wp (lane_weights): a wave's weight load is one contiguous KB
+    const float *Wstem_l, *Wp_l;    // lane-order copies of Wstem and Wp (k_lane_weights): a wave's weight load is one contiguous KB
     const float *Wd, *bd;           // [9][32], [32]
     const float *Wp, *bp;           // [16][32], [16]
     float *Y;                       // [n][OH][OW][16]
@@ -724,7 +724,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
 #ifndef SK_DEPTH
 #define SK_DEPTH 2     // k-steps k_pw_sk keeps in flight per wave (round 4, [N][K] weights: 2 / 4 / 6 -> pw class 1.442 / 1.437 / 1.476 ms; lane-order weights: 2 / 3 / 4 -> the pass 1.383 / 1.385 / 1.388 ms alone, 1.020 / 1.026 / 1.028 shared)
 #endif
-// LW (round 4): the weights come from a LANE-ORDER copy of the matrix (lane_weights below): element ((k-step, column tile), lane)
+// LW (round 4): the weights come from a LANE-ORDER copy of the matrix (k_lane_weights below): element ((k-step, column tile), lane)
 // = the float4 that lane feeds into the tile's four MFMAs of the step, so a wave's load is one contiguous KB (8 cache lines,
 // each used whole) instead of 32 rows x 32 B (32 lines, a quarter of each) -- the texture-address units are busy 48 % of this
 // kernel and stalled by the L1 37 % of it (profiles/r04_pmc_mem_pipes.txt).  ldw then carries the number of column tiles.
@@ -1279,6 +1279,16 @@ __global__ __launch_bounds__(256) void k_quantise_profile(const float *__restric
 enum Buf { B_IN, B_P0, B_P1, B_E0, B_E1, B_F4X, B_F2X, B_CAT1, B_PCD, B_PC, B_CAT2, B_U2E, B_U2, B_CAT3, B_P3E, B_DEC,
            B_LOGIT, B_PRE, B_T1, B_T2, B_COUNT };
 
+// The workspace tensors that are a whole level of the network: the input size divided by `div`, times `ch` channels, in the
+// order of Buf.  div = 0: sized by build_plan itself.  build_plan and svc_debug_tap both take their element counts from here.
+static const struct { int div, ch; } BUF_SHAPE[B_COUNT] = {
+    {1, 3}, {2, 32}, {2, 32}, {0, 0}, {0, 0}, {8, 64}, {16, 160},        // IN, P0, P1, E0, E1, F4X, F2X
+    {32, 1296}, {32, 1296}, {32, 256},                                  // CAT1, PCD, PC
+    {16, 384}, {16, 768}, {16, 128},                                    // CAT2, U2E, U2
+    {8, 192}, {8, 384}, {8, 64},                                        // CAT3, P3E, DEC
+    {0, 0}, {0, 0}, {32, 768}, {16, 384}};                              // LOGIT, PRE; T1, T2: the low-resolution halves of the two decoder expansions
+static size_t buf_floats(int NH, int NW, int b) { return (size_t)(NH / BUF_SHAPE[b].div) * (NW / BUF_SHAPE[b].div) * BUF_SHAPE[b].ch; }
+
 #define LZ_ROWS 8       // output rows per workgroup of k_lanczos_norm
 #define SD_ROWS 7       // output rows per workgroup of k_smooth_down_mfma
 
@@ -1334,16 +1344,10 @@ static int build_plan(SvcHandle *h, int height, int width, int nb) {
     const size_t H1 = NH / 2, W1 = NW / 2, H2 = NH / 4, W2 = NW / 4, H3 = NH / 8, W3 = NW / 8, H4 = NH / 16,
                  W4 = NW / 16, H5 = NH / 32, W5 = NW / 32;
     size_t sz[B_COUNT];
-    sz[B_IN] = (size_t)NH * NW * 3;
-    sz[B_P0] = sz[B_P1] = H1 * W1 * 32;
+    for (int b = 0; b < B_COUNT; ++b) sz[b] = BUF_SHAPE[b].div ? buf_floats(NH, NW, b) : 0;
     // expanded tensors: f2 expand at H1 (96 ch) is the largest
     sz[B_E0] = std::max(std::max(H1 * W1 * 96, H2 * W2 * 144), std::max(H3 * W3 * 192, std::max(H4 * W4 * 576, H5 * W5 * 960)));
     sz[B_E1] = std::max(std::max(H1 * W1 * 32, H2 * W2 * 144), std::max(H3 * W3 * 192, std::max(H4 * W4 * 576, H5 * W5 * 960)));
-    sz[B_F4X] = H3 * W3 * 64;  sz[B_F2X] = H4 * W4 * 160;
-    sz[B_CAT1] = H5 * W5 * 1296; sz[B_PCD] = H5 * W5 * 1296; sz[B_PC] = H5 * W5 * 256;
-    sz[B_CAT2] = H4 * W4 * 384; sz[B_U2E] = H4 * W4 * 768; sz[B_U2] = H4 * W4 * 128;
-    sz[B_CAT3] = H3 * W3 * 192; sz[B_P3E] = H3 * W3 * 384; sz[B_DEC] = H3 * W3 * 64;
-    sz[B_T1] = H5 * W5 * 768; sz[B_T2] = H4 * W4 * 384;   // low-resolution halves of the two decoder expansions
     sz[B_LOGIT] = (H3 * W3 + 3) / 4 * 4;
     sz[B_PRE] = ((size_t)height * width + 3) / 4 * 4;
     p->off[0] = 0;
@@ -1448,35 +1452,24 @@ int svc_net_release(SvcHandle *h) {
 // --------------------------------------------------------------------------------------
 // launch helpers
 // --------------------------------------------------------------------------------------
+#define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+
 static inline unsigned blocks256(size_t total) { return (unsigned)((total + 255) / 256); }
 
-// Lane-order copy of a weight matrix for k_pw_sk<.., true>: out[((st * tiles + tile) * 64 + lane)] (float4) =
+// Raises a kernel's dynamic-LDS limit, once per kernel and handle: the attribute is per device, so the once-flag lives in the
+// handle (one handle = one device), not in the process.
+static int raise_lds_limit(SvcHandle *h, const void *kfn, int bytes) {
+    if (h->lds_attr_done.insert(kfn).second) SVC_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return SVC_OK;
+}
+
+// F32_LANES: lane-order copy of a weight matrix for k_pw_sk<.., true>: out[((st * tiles + tile) * 64 + lane)] (float4) =
 // W[tile * 32 + (lane & 31)][8 st + 4 (lane >> 5) .. + 3] -- what the lane loads in k-step st for column tile `tile`.
 __global__ void k_lane_weights(const float *__restrict__ Wt, int ldw, int nsteps, int tiles, int nrows, float4 *__restrict__ out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)nsteps * tiles * 64) return;
     const int lane = (int)(i & 63), tile = (int)((i >> 6) % tiles), st = (int)((i >> 6) / tiles);
     out[i] = *(const float4 *)(Wt + (size_t)min(tile * 32 + (lane & 31), nrows - 1) * ldw + 8 * st + 4 * (lane >> 5));     // rows beyond the matrix repeat its last one
-}
-
-// the copy is made on the stream of the first launch that needs it (ordered in front of that launch, and waited for) and kept with the handle
-static int lane_weights(SvcHandle *h, hipStream_t s, const float *Wt, int ldw, int K, int Npad, const float **out) {
-    const auto key = std::make_tuple((const void *)Wt, ldw, K, Npad);
-    auto it = h->lane_w.find(key);
-    if (it == h->lane_w.end()) {
-        DevBuf b;
-        const int nsteps = K >> 3, tiles = (Npad + 31) >> 5;
-        int rc = b.ensure((size_t)nsteps * tiles * 64 * sizeof(float4));
-        if (rc) return rc;
-        k_lane_weights<<<blocks256((size_t)nsteps * tiles * 64), 256, 0, s>>>(Wt, ldw, nsteps, tiles, Npad, (float4 *)b.p);
-        SVC_CHECK_LAUNCH();
-        // once per matrix and handle, on the first pass that needs it:
-        // finished before any other stream can be handed the copy
-        SVC_HIP(hipStreamSynchronize(s));
-        it = h->lane_w.emplace(key, b).first;
-    }
-    *out = (const float *)it->second.p;
-    return SVC_OK;
 }
 
 // Split-bf16 copies of a weight matrix (see x3_split): three round-to-nearest bf16 planes per element, 48 B per (row, 16-deep
@@ -1486,7 +1479,8 @@ static int lane_weights(SvcHandle *h, hipStream_t s, const float *Wt, int ldw, i
 //   X3_LANES  out[(((q * tiles + tile) * 64) + lane) * 3 + plane]     what lane (r, hh) of column tile `tile` feeds into step q:
 //                                                                     a wave's load is 3 KB contiguous (k_pw_sk, k_dwpw, k_pwpw)
 // k beyond K reads as zero (K = 24: the second step's upper half); rows beyond nrows repeat the last one (as k_lane_weights).
-enum { X3_ROWS = 0, X3_LANES = 1 };
+// The forms a weight matrix is read in.  W_MATRIX is the [N][K] matrix of the blob itself; the others are copies (weight_copy).
+enum WForm { X3_ROWS = 0, X3_LANES = 1, F32_LANES = 2, W_MATRIX = 3 };
 __global__ void k_x3_weights(const float *__restrict__ Wt, int ldw, int K, int Q, int tiles, int nrows, int order, uint4 *__restrict__ out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;          // one (row, step, half)
     if (i >= (size_t)tiles * 32 * Q * 2) return;
@@ -1506,29 +1500,45 @@ __global__ void k_x3_weights(const float *__restrict__ Wt, int ldw, int K, int Q
     out[i * 3] = H.q; out[i * 3 + 1] = Mi.q; out[i * 3 + 2] = L.q;
 }
 
-// made on the stream of the first launch that needs it, waited for, kept with the handle (like lane_weights)
-static int x3_weights(SvcHandle *h, hipStream_t s, const float *Wt, int ldw, int K, int Npad, int order, const uint4 **out) {
-    const auto key = std::make_tuple((const void *)Wt, ldw, K, Npad * 2 + order);
-    auto it = h->x3_w.find(key);
-    if (it == h->x3_w.end()) {
+// The copy of matrix Wt (K of the ldw columns of its rows, Npad rows wanted) in form `form`.  It is made on the stream of the first
+// launch that needs it (ordered in front of that launch, and waited for: finished before any other stream can be handed the
+// copy) and kept with the handle.
+static int weight_copy(SvcHandle *h, hipStream_t s, WForm form, const float *Wt, int ldw, int K, int Npad, const void **out) {
+    *out = Wt;
+    if (form == W_MATRIX) return SVC_OK;
+    const auto key = std::make_tuple((const void *)Wt, ldw, K, Npad, (int)form);
+    auto it = h->w_copies.find(key);
+    if (it == h->w_copies.end()) {
         DevBuf b;
-        const int Q = (K + 15) >> 4, tiles = (Npad + 31) >> 5;
-        const size_t cells = (size_t)tiles * 32 * Q * 2;
-        int rc = b.ensure(cells * 3 * sizeof(uint4));
-        if (rc) return rc;
-        k_x3_weights<<<blocks256(cells), 256, 0, s>>>(Wt, ldw, K, Q, tiles, Npad, order, (uint4 *)b.p);
+        const int tiles = (Npad + 31) >> 5, nsteps = K >> 3, Q = (K + 15) >> 4;
+        const size_t cells = form == F32_LANES ? (size_t)nsteps * tiles * 64 : (size_t)tiles * 32 * Q * 2;
+        RC(b.ensure(cells * (form == F32_LANES ? sizeof(float4) : 3 * sizeof(uint4))));
+        if (form == F32_LANES) k_lane_weights<<<blocks256(cells), 256, 0, s>>>(Wt, ldw, nsteps, tiles, Npad, (float4 *)b.p);
+        else k_x3_weights<<<blocks256(cells), 256, 0, s>>>(Wt, ldw, K, Q, tiles, Npad, form, (uint4 *)b.p);
         SVC_CHECK_LAUNCH();
         SVC_HIP(hipStreamSynchronize(s));
-        it = h->x3_w.emplace(key, b).first;
+        it = h->w_copies.emplace(key, b).first;
     }
-    *out = (const uint4 *)it->second.p;
+    *out = it->second.p;
     return SVC_OK;
+}
+
+// Which form the lane-order consumers (k_pw_sk, k_dwpw, k_pwpw's second GEMM) read a matrix of K input channels in: the
+// split-bf16 lanes on that pipe (whole 16-deep steps), else the fp32 lanes where the knob allows (whole 8-deep steps), else
+// the matrix itself.
+static WForm lane_form(const SvcHandle *h, int K) {
+    return h->mx && (K & 15) == 0 ? X3_LANES : h->sk_lane && (K & 7) == 0 ? F32_LANES : W_MATRIX;
 }
 
 // k_pwr: column tiles (of 32) per workgroup.  Measured at B = 32: 1 / 2 / 3 / 4 -> 1.735 / 1.692 / 1.726 / 1.767 ms per pass.
 #define PWR_NT 2
 // k_pw_sk serves a long-K layer (K >= 256) when its row blocks x column tiles, at the nominal batch, do not exceed this.
 #define PW_SK_MAX_WG 2048
+
+// k_pwr<KS, UPS> on the handle's matrix pipe
+using PwrFn = decltype(&k_pwr<8, false>);
+template <int KS, bool UPS>
+static PwrFn pwr_kfn(bool mx) { return mx ? k_pwr<KS, UPS, true> : k_pwr<KS, UPS>; }
 
 // One pointwise layer, or a column slice of one: K of the ldw input channels of the weight rows, starting at Wt
 // (bias may be null).  ups != null adds the up-sampled low-resolution product (see UpsAdd).
@@ -1550,31 +1560,23 @@ static int launch_pw_ex(SvcHandle *h, hipStream_t s, const float *X, int ldx, co
         const int ntw = std::min(PWR_NT, tiles);
         const dim3 g(rb, ceil_div(tiles, ntw));
         const bool mx = h->mx != 0;
-        const float *Wk = Wt;                                // MX: the split-bf16 copy of the slice, rows of (K / 16) * 6 uint4
-        if (mx) {
-            const uint4 *W3 = nullptr;
-            int rc = x3_weights(h, s, Wt, ldw, K, Npad, X3_ROWS, &W3);
-            if (rc) return rc;
-            Wk = (const float *)W3;
-        }
+        const void *Wk;                                      // MX: the split-bf16 copy of the slice, rows of (K / 16) * 6 uint4
+        RC(weight_copy(h, s, mx ? X3_ROWS : W_MATRIX, Wt, ldw, K, Npad, &Wk));
         const size_t lds = mx ? (size_t)ntw * 32 * ((K / 16) * 6 + 1) * sizeof(uint4) + ((size_t)4 * 32 * PWR_SLAB + 128) * sizeof(float)
                               : ((size_t)ntw * 32 * (K + 4) + 4 * 32 * PWR_SLAB + 128) * sizeof(float);
-#define PWR_KFN(KSv, UPSv) (mx ? k_pwr<KSv, UPSv, true> : k_pwr<KSv, UPSv>)
-        decltype(&k_pwr<8, false>) kfn = nullptr;
+        PwrFn kfn = nullptr;
         switch (K) {
-            case 64: kfn = ups ? PWR_KFN(8, true) : PWR_KFN(8, false); break;
-            case 96: if (!ups) kfn = PWR_KFN(12, false); break;
-            case 128: kfn = ups ? PWR_KFN(16, true) : PWR_KFN(16, false); break;
-            default: if (!ups) kfn = PWR_KFN(20, false); break;
+            case 64: kfn = ups ? pwr_kfn<8, true>(mx) : pwr_kfn<8, false>(mx); break;
+            case 96: if (!ups) kfn = pwr_kfn<12, false>(mx); break;
+            case 128: kfn = ups ? pwr_kfn<16, true>(mx) : pwr_kfn<16, false>(mx); break;
+            default: if (!ups) kfn = pwr_kfn<20, false>(mx); break;
         }
-#undef PWR_KFN
         if (!kfn) {
             svc_set_error("no k_pwr instance for K = %d with an up-sampled term", K);
             return SVC_E_INVALID;
         }
-        if (h->lds_attr_done.insert((const void *)kfn).second)
-            SVC_HIP(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        kfn<<<g, 256, lds, s>>>(X, ldx, Wk, ldw, bias, Y, ldy, M, N, Npad, ntw, relu6v, ua);
+        RC(raise_lds_limit(h, (const void *)kfn, 128 * 1024));
+        kfn<<<g, 256, lds, s>>>(X, ldx, (const float *)Wk, ldw, bias, Y, ldy, M, N, Npad, ntw, relu6v, ua);
         SVC_CHECK_LAUNCH();
         return SVC_OK;
     }
@@ -1584,23 +1586,16 @@ static int launch_pw_ex(SvcHandle *h, hipStream_t s, const float *X, int ldx, co
     if (!ups && K >= 256 && rb_nom * tiles <= PW_SK_MAX_WG) {
         const int tn = (tiles % 2 == 0) ? 2 : 1;
         dim3 g(ceil_div(M, 32), ceil_div(tiles, tn));
-        if (h->mx && (K & 15) == 0) {
-            if (tn != 2) {
-                svc_set_error("no split-bf16 k_pw_sk instance for %d column tiles", tiles);
-                return SVC_E_INVALID;
-            }
-            const uint4 *W3 = nullptr;
-            int rc = x3_weights(h, s, Wt, ldw, K, Npad, X3_LANES, &W3);
-            if (rc) return rc;
-            k_pw_sk<2, true, true><<<g, 256, 0, s>>>(X, ldx, (const float *)W3, tiles, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
-        } else if (h->sk_lane && (K & 7) == 0) {
-            const float *Wl = nullptr;
-            int rc = lane_weights(h, s, Wt, ldw, K, Npad, &Wl);
-            if (rc) return rc;
-            if (tn == 2) k_pw_sk<2, true><<<g, 256, 0, s>>>(X, ldx, Wl, tiles, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
-            else k_pw_sk<1, true><<<g, 256, 0, s>>>(X, ldx, Wl, tiles, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
-        } else if (tn == 2) k_pw_sk<2><<<g, 256, 0, s>>>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
-        else k_pw_sk<1><<<g, 256, 0, s>>>(X, ldx, Wt, ldw, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
+        const WForm form = lane_form(h, K);
+        if (form == X3_LANES && tn != 2) {
+            svc_set_error("no split-bf16 k_pw_sk instance for %d column tiles", tiles);
+            return SVC_E_INVALID;
+        }
+        const void *Wk;
+        RC(weight_copy(h, s, form, Wt, ldw, K, Npad, &Wk));
+        const auto kfn = form == X3_LANES ? k_pw_sk<2, true, true>
+                       : form == F32_LANES ? (tn == 2 ? k_pw_sk<2, true> : k_pw_sk<1, true>) : (tn == 2 ? k_pw_sk<2> : k_pw_sk<1>);
+        kfn<<<g, 256, 0, s>>>(X, ldx, (const float *)Wk, form == W_MATRIX ? ldw : tiles, bias, R, ldr, Y, ldy, M, N, Npad, K, relu6v);
         SVC_CHECK_LAUNCH();
         return SVC_OK;
     }
@@ -1656,7 +1651,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2, 8))
                                               const float *__restrict__ Wp, const float *__restrict__ bp, int N,
                                               int Npad, const float *__restrict__ R, int ldr, float *__restrict__ Y,
                                               int ldy, int relu6, int tiles_x, int tiles_y, int lw_tiles) {
-    // lw_tiles > 0: Wp is the LANE-ORDER copy of the project weights (lane_weights: one contiguous KB per wave load instead of
+    // lw_tiles > 0: Wp is the LANE-ORDER copy of the project weights (k_lane_weights: one contiguous KB per wave load instead of
     // 32 rows x 32 B; lw_tiles = its column tiles) -- the project-weight loads were more than half of the cache lines this
     // kernel touches
     constexpr int PH = 32 / PW;
@@ -1877,7 +1872,7 @@ template <int KS1, int NT2, bool MX = false>     // K1 = 8 KS1 input channels, N
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) void k_pwpw(const float *__restrict__ X, int ldx, const float *__restrict__ W1,
                                               const float *__restrict__ b1, int Cm, const float *__restrict__ W2,
                                               const float *__restrict__ b2, float *__restrict__ Y, int ldy, int M, int lw) {
-    // lw: W2 is a LANE-ORDER copy (lane_weights: a wave's weight load is one contiguous KB instead of 32 rows x 32 B)
+    // lw: W2 is a LANE-ORDER copy (k_lane_weights: a wave's weight load is one contiguous KB instead of 32 rows x 32 B)
     constexpr int K1 = 8 * KS1;
     __shared__ float red_pp[4][16][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
@@ -2031,25 +2026,16 @@ static int launch_pwpw(SvcHandle *h, hipStream_t s, const float *X, int ldx, con
         return SVC_E_INVALID;
     }
     const dim3 grid((unsigned)ceil_div(M, 32));
-    const float *W1 = L1.w.dev, *W2 = L2.w.dev;
-    int lw = 0;
     const bool mx = h->mx != 0;
-    if (mx) {
-        const uint4 *a = nullptr, *b = nullptr;
-        int rc = x3_weights(h, s, L1.w.dev, L1.cin, L1.cin, L1.cout, X3_ROWS, &a);
-        if (!rc) rc = x3_weights(h, s, L2.w.dev, L2.cin, L2.cin, L2.cout, X3_LANES, &b);
-        if (rc) return rc;
-        W1 = (const float *)a; W2 = (const float *)b;
-        lw = 1;
-    } else if (h->sk_lane) {
-        // (the SECOND matrix only: the first one's loads run one step ahead of their MFMAs, and in [Cm][K1] order three of
-        // four hit the line the one before them fetched -- in lane order every one is an L2 round trip: 44 -> 57 us at K1 = 160)
-        int rc = lane_weights(h, s, L2.w.dev, L2.cin, L2.cin, L2.cout, &W2);
-        if (rc) return rc;
-        lw = 1;
-    }
+    // The first matrix is read as X3_ROWS on the split-bf16 pipe and stays [N][K] on the fp32 pipe: its loads run one step ahead
+    // of their MFMAs, and in [Cm][K1] order three of four hit the line the one before them fetched -- in lane order every one is
+    // an L2 round trip: 44 -> 57 us at K1 = 160.  The second one is a lane-order consumer (L2.cin is a multiple of 32).
+    const WForm f2 = lane_form(h, L2.cin);
+    const void *W1, *W2;
+    RC(weight_copy(h, s, mx ? X3_ROWS : W_MATRIX, L1.w.dev, L1.cin, L1.cin, L1.cout, &W1));
+    RC(weight_copy(h, s, f2, L2.w.dev, L2.cin, L2.cin, L2.cout, &W2));
     const auto kfn = k8 ? (mx ? k_pwpw<8, 2, true> : k_pwpw<8, 2>) : (mx ? k_pwpw<20, 4, true> : k_pwpw<20, 4>);
-    kfn<<<grid, 256, 0, s>>>(X, ldx, W1, L1.b.dev, L1.cout, W2, L2.b.dev, Y, ldy, M, lw);
+    kfn<<<grid, 256, 0, s>>>(X, ldx, (const float *)W1, L1.b.dev, L1.cout, (const float *)W2, L2.b.dev, Y, ldy, M, f2 != W_MATRIX);
     SVC_CHECK_LAUNCH();
     return SVC_OK;
 }
@@ -2073,20 +2059,11 @@ static int launch_dwpw(SvcHandle *h, hipStream_t s, const float *X, const SvcLay
     const int pw = (W % 8 == 0 || W > 16) ? 8 : 16;          // 8x4 patches; 16x2 on the narrow 13-wide level
     const int tx = ceil_div(W, pw), ty = ceil_div(H, 32 / pw);
     dim3 grid((unsigned)(n * tx * ty), groups);
-    const float *Wpl = Lp.w.dev;                             // the project weights: lane-order copy where the knob allows
-    int lw_tiles = 0;
-    const bool mx = h->mx && (C & 15) == 0;
-    if (mx) {
-        const uint4 *W3 = nullptr;
-        int rc = x3_weights(h, s, Lp.w.dev, C, C, Npad, X3_LANES, &W3);
-        if (rc) return rc;
-        Wpl = (const float *)W3;
-        lw_tiles = tiles;
-    } else if (h->sk_lane && (C & 7) == 0) {
-        int rc = lane_weights(h, s, Lp.w.dev, C, C, Npad, &Wpl);
-        if (rc) return rc;
-        lw_tiles = tiles;
-    }
+    const WForm form = lane_form(h, C);                      // the project weights: a lane-order copy where the pipe / the knob allow
+    const bool mx = form == X3_LANES;
+    const void *Wpl;
+    RC(weight_copy(h, s, form, Lp.w.dev, C, C, Npad, &Wpl));
+    const int lw_tiles = form == W_MATRIX ? 0 : tiles;
     // The layers' shapes give nt = 2 .. 5.  Every level but the lowest is at least 16 columns wide (8-wide patches); the lowest
     // level is fused on the split-bf16 pipe only, by layers of 4 and 5 tiles.
     decltype(&k_dwpw<2, 8, 4>) kfn = nullptr;
@@ -2103,7 +2080,7 @@ static int launch_dwpw(SvcHandle *h, hipStream_t s, const float *X, const SvcLay
         svc_set_error("no k_dwpw instance for %d column tiles on a %d-wide level (%s pipe)", tiles, W, mx ? "split-bf16" : "fp32");
         return SVC_E_INVALID;
     }
-    kfn<<<grid, 256, 0, s>>>(X, H, W, C, Ld.w.dev, Ld.b.dev, Wpl, Lp.b.dev, N, Npad, R, ldr, Y, ldy, Lp.relu6, tx, ty, lw_tiles);
+    kfn<<<grid, 256, 0, s>>>(X, H, W, C, Ld.w.dev, Ld.b.dev, (const float *)Wpl, Lp.b.dev, N, Npad, R, ldr, Y, ldy, Lp.relu6, tx, ty, lw_tiles);
     SVC_CHECK_LAUNCH();
     return SVC_OK;
 }
@@ -2552,83 +2529,95 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IRB_MX3(S, 
     }
 }
 
-static int launch_irb(SvcHandle *h, hipStream_t s, const float *X, int n, int H, int W, int Cin, const SvcLayer *Le,
-                      const SvcLayer &Ld, const SvcLayer &Lp, int stride, const float *R, float *Y) {
+// Block B on one k_irb instance.  MX: the split-bf16 form of an expanding block -- We as an X3_ROWS copy, and Wp too where
+// the project GEMM is split (MXP: Cout = 64, block 7).
+template <int S, int TOH, int TOW, bool EXP, int CI, int CE, int CO, bool MX>
+static int launch_irb_as(SvcHandle *h, hipStream_t s, const float *X, int n, int H, int W, const InvRes &B, const float *R, float *Y) {
+    const int Cin = B.inp, Ce = B.dw.cout, Cout = B.oup, CoutP = (Cout + 31) / 32 * 32, OH = H / S, OW = W / S;
+    const void *We = EXP ? B.expand.w.dev : nullptr, *Wp = B.project.w.dev;
+    if (MX) {
+        RC(weight_copy(h, s, X3_ROWS, B.expand.w.dev, Cin, Cin, (Ce + 31) / 32 * 32, &We));
+        if (Cout == 64) RC(weight_copy(h, s, X3_ROWS, B.project.w.dev, Ce, Ce, CoutP, &Wp));
+    }
+    const int tx = ceil_div(OW, TOW), ty = ceil_div(OH, TOH);
+    const size_t lds = IrbGeom<S, TOH, TOW>::lds_floats(Cin, CoutP, EXP, Ce, IRB_XREG && EXP && CI > 0 && CI <= 32 && (CI % 8) == 0, MX) * 4;
+    const auto kfn = k_irb<S, TOH, TOW, EXP, CI, CE, CO, MX>;
+    RC(raise_lds_limit(h, (const void *)kfn, 120 * 1024));       // tiles of the 96-channel blocks need more than the default 64 KB of dynamic LDS
+    kfn<<<dim3((unsigned)(n * tx * ty)), 256, lds, s>>>(X, H, W, Cin, (const float *)We, EXP ? B.expand.b.dev : nullptr, Ce, B.dw.w.dev, B.dw.b.dev,
+                                                        (const float *)Wp, B.project.b.dev, Cout, CoutP, R, Y, Cout, OH, OW, tx, ty);
+    SVC_CHECK_LAUNCH();
+    return SVC_OK;
+}
+using IrbFn = decltype(&launch_irb_as<1, 8, 8, false, 32, 32, 16, false>);
+// an expanding block's instance on the handle's matrix pipe
+template <int S, int TOH, int TOW, int CI, int CE, int CO>
+static IrbFn irb_on_pipe(bool mx) { return mx ? launch_irb_as<S, TOH, TOW, true, CI, CE, CO, true> : launch_irb_as<S, TOH, TOW, true, CI, CE, CO, false>; }
+
+// Block B as one fused kernel, run at `stride` (a tap block runs at stride 1: see backbone_block).
+static int launch_irb(SvcHandle *h, hipStream_t s, const float *X, int n, int H, int W, const InvRes &B, int stride, const float *R, float *Y) {
     ProfScope ps(h, SVC_K_PW, s);
-    const int Ce = Ld.cout, Cout = Lp.cout, CoutP = (Cout + 31) / 32 * 32;
-    const int OH = H / stride, OW = W / stride;
-    // split-bf16 form of an expanding block (IRB_LAUNCH_MX on the split-bf16 pipe): We and Wp as X3_ROWS copies
-    const float *We_ = Le ? Le->w.dev : nullptr, *Wp_ = Lp.w.dev;
-    auto mx_weights = [&]() -> int {
-        const uint4 *a = nullptr, *b = nullptr;
-        int rc = x3_weights(h, s, Le->w.dev, Cin, Cin, (Ce + 31) / 32 * 32, X3_ROWS, &a);
-        We_ = (const float *)a;
-        if (!rc && Cout == 64) {                             // (MXP: block 7)
-            rc = x3_weights(h, s, Lp.w.dev, Ce, Ce, CoutP, X3_ROWS, &b);
-            Wp_ = (const float *)b;
-        }
-        return rc;
-    };
-#define IRB_LAUNCH_MX(S_, TOH_, TOW_, CI_, CE_, CO_)                                                                 \
-    do {                                                                                                             \
-        if (h->mx) {                                                                                                 \
-            int rc = mx_weights();                                                                                   \
-            if (rc) return rc;                                                                                       \
-            IRB_LAUNCH(S_, TOH_, TOW_, true, CI_, CE_, CO_, true);                                                   \
-        } else IRB_LAUNCH(S_, TOH_, TOW_, true, CI_, CE_, CO_, false);                                               \
-    } while (0)
-#define IRB_LAUNCH(S_, TOH_, TOW_, EXP_, CI_, CE_, CO_, MX_)                                                         \
-    do {                                                                                                             \
-        const int tx = ceil_div(OW, TOW_), ty = ceil_div(OH, TOH_);                                                  \
-        const size_t lds = IrbGeom<S_, TOH_, TOW_>::lds_floats(Cin, CoutP, EXP_, Ce, IRB_XREG && EXP_ && (CI_) > 0 && (CI_) <= 32 && ((CI_) % 8) == 0, MX_) * 4; \
-        auto kfn = k_irb<S_, TOH_, TOW_, EXP_, CI_, CE_, CO_, MX_>;                                                  \
-        /* tiles of the 96-channel blocks need more than the default 64 KB of dynamic LDS; the attribute is per  */  \
-        /* device, so the once-flag lives in the handle (one handle = one device), not in the process            */  \
-        if (h->lds_attr_done.insert((const void *)kfn).second)                                                       \
-            SVC_HIP(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024)); \
-        kfn<<<dim3((unsigned)(n * tx * ty)), 256, lds, s>>>(                                                          \
-            X, H, W, Cin, EXP_ ? We_ : nullptr, EXP_ ? Le->b.dev : nullptr, Ce, Ld.w.dev, Ld.b.dev, Wp_,              \
-            Lp.b.dev, Cout, CoutP, R, Y, Cout, OH, OW, tx, ty);                                                       \
-    } while (0)
+    const int Cin = B.inp, Ce = B.dw.cout, Cout = B.oup;
+    const bool mx = h->mx != 0;
     // One compile-time-shaped instance per block shape.  The expand GEMM takes the split-bf16 form where it is faster than the
     // fp32 form.  Measured per instance, us per pass alone / shared: blocks 2, 3, 5-6, 7: -17 / -11, -12 / -7, -11 / -4,
     // -10 / -6; block 4: +11 / +11 (Cin = 24 pads its second step, two halo tiles per wave: 36 spilled registers), so it stays fp32.
-    if (!Le && Cin == 32 && Ce == 32 && Cout == 16) IRB_LAUNCH(1, 8, 8, false, 32, 32, 16, false);             // block 1
-    else if (!Le) {
-        svc_set_error("no k_irb instance for a %d -> %d -> %d block without expansion", Cin, Ce, Cout);
-        return SVC_E_INVALID;
-    } else if (stride == 2 && Cin == 16 && Ce == 96 && Cout == 24) IRB_LAUNCH_MX(2, 4, 8, 16, 96, 24);          // block 2
-    else if (stride == 2 && Cin == 24 && Ce == 144 && Cout == 32) IRB_LAUNCH(2, 4, 8, true, 24, 144, 32, false); // block 4
-    else if (stride == 1 && Cin == 24 && Ce == 144 && Cout == 24) IRB_LAUNCH_MX(1, 8, 8, 24, 144, 24);          // block 3
-    else if (stride == 1 && Cin == 32 && Ce == 192 && Cout == 32) IRB_LAUNCH_MX(1, 8, 8, 32, 192, 32);          // blocks 5-6
-    else if (stride == 1 && Cin == 32 && Ce == 192 && Cout == 64) IRB_LAUNCH_MX(1, 8, 8, 32, 192, 64);          // block 7
+    IrbFn fn = nullptr;
+    if (!B.has_expand) {
+        if (Cin == 32 && Ce == 32 && Cout == 16) fn = launch_irb_as<1, 8, 8, false, 32, 32, 16, false>;              // block 1
+        else {
+            svc_set_error("no k_irb instance for a %d -> %d -> %d block without expansion", Cin, Ce, Cout);
+            return SVC_E_INVALID;
+        }
+    } else if (stride == 2 && Cin == 16 && Ce == 96 && Cout == 24) fn = irb_on_pipe<2, 4, 8, 16, 96, 24>(mx);       // block 2
+    else if (stride == 2 && Cin == 24 && Ce == 144 && Cout == 32) fn = launch_irb_as<2, 4, 8, true, 24, 144, 32, false>;   // block 4
+    else if (stride == 1 && Cin == 24 && Ce == 144 && Cout == 24) fn = irb_on_pipe<1, 8, 8, 24, 144, 24>(mx);       // block 3
+    else if (stride == 1 && Cin == 32 && Ce == 192 && Cout == 32) fn = irb_on_pipe<1, 8, 8, 32, 192, 32>(mx);       // blocks 5-6
+    else if (stride == 1 && Cin == 32 && Ce == 192 && Cout == 64) fn = irb_on_pipe<1, 8, 8, 32, 192, 64>(mx);       // block 7
     else {
         svc_set_error("no k_irb instance for a stride-%d %d -> %d -> %d block", stride, Cin, Ce, Cout);
         return SVC_E_INVALID;
     }
-#undef IRB_LAUNCH_MX
-#undef IRB_LAUNCH
-    SVC_CHECK_LAUNCH();
-    return SVC_OK;
+    return fn(h, s, X, n, H, W, B, R, Y);
 }
 
-#define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+// --------------------------------------------------------------------------------------
+// The pass, stage by stage.  Every stage launches on stream s, for the n frames of the pass.
+// --------------------------------------------------------------------------------------
 
-// One pass of the network over n <= plan->nb frames.
-static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *maps, hipStream_t s, int thr = 0, unsigned *census_rows = nullptr,
-                         unsigned *profile_rows = nullptr) {
+// The front of the network: LANCZOS, features.0 (stem), features.1 -> y at half the input size.  One kernel (k_front) where a
+// tile's resampling arrays fit in LDS, else the three kernels (the stem's output in `stem_out`).
+static int net_front(SvcHandle *h, hipStream_t s, const uint8_t *frames, int n, float *stem_out, float *y) {
     NetPlan *p = h->plan;
-    const int NH = p->NH, NW = p->NW;
-    int H = NH / 2, W = NW / 2;
-    size_t li = 0;
-    auto next = [&]() -> const SvcLayer & { return h->layers[li++]; };
-    float *IN = p->buf(B_IN), *P[2] = {p->buf(B_P0), p->buf(B_P1)}, *E0 = p->buf(B_E0), *E1 = p->buf(B_E1);
-    // the front of the network (LANCZOS, features.0, features.1) as one kernel where a tile's resampling arrays fit in LDS
-    const int fr_lds = front_lds_bytes();
-    const bool front = h->front && p->fr_ok;
-    p->last_front = front;
-    // K0
-    if (!front) {
+    const NetGraph &g = h->net;
+    const InvRes &B = g.block[0];
+    const int NH = p->NH, NW = p->NW, H = NH / 2, W = NW / 2;
+    float *IN = p->buf(B_IN);
+    p->last_front = h->front && p->fr_ok;
+    if (p->last_front) {
+        ProfScope ps(h, SVC_K_STEM, s);
+        FrontArgs A;
+        A.frames = frames; A.h = p->h; A.w = p->w; A.NH = NH; A.NW = NW; A.OH = H; A.OW = W;
+        A.tiles_x = ceil_div(W, FR_TW); A.tiles_y = ceil_div(H, FR_TH);
+        A.hb = (const int *)p->hb.p; A.hk = (const int *)p->hk.p; A.vb = (const int *)p->vb.p; A.vk = (const int *)p->vk.p;
+        A.hks = p->hks; A.vks = p->vks; A.lut = (const float *)p->lut.p;
+        A.Wstem = (const float *)h->stem_wt.p; A.bstem = g.stem.b.dev;
+        const void *wl;
+        RC(weight_copy(h, s, F32_LANES, (const float *)h->stem_wt.p, 32, 32, 32, &wl));
+        A.Wstem_l = (const float *)wl;
+        RC(weight_copy(h, s, F32_LANES, B.project.w.dev, 32, 32, 16, &wl));
+        A.Wp_l = (const float *)wl;
+        A.Wd = B.dw.w.dev; A.bd = B.dw.b.dev; A.Wp = B.project.w.dev; A.bp = B.project.b.dev;
+        A.Y = y; A.in_dbg = h->keep_input ? IN : nullptr;
+        A.nr_cap = p->fr_nr; A.nc_cap = p->fr_nc;
+        for (int i = 0; i < FR_MAXT; ++i) {
+            A.row_lo[i] = p->fr_row_lo[i]; A.row_n[i] = p->fr_row_n[i];
+            A.col_lo[i] = p->fr_col_lo[i]; A.col_n[i] = p->fr_col_n[i];
+        }
+        k_front<<<dim3((unsigned)(n * A.tiles_x * A.tiles_y)), 256, front_lds_bytes(), s>>>(A);
+        SVC_CHECK_LAUNCH();
+        return SVC_OK;
+    }
+    {   // K0
         ProfScope ps(h, SVC_K_LANCZOS, s);
         dim3 grid(ceil_div(NH, LZ_ROWS), n);
         size_t lds = ((size_t)p->lz_tile_cap * p->w * 3 + 15) / 16 * 16 + ((size_t)p->lz_tile_cap * NW * 3 + 15) / 16 * 16 +
@@ -2638,96 +2627,63 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
                                              (const float *)p->lut.p, LZ_ROWS, p->lz_tile_cap);
         SVC_CHECK_LAUNCH();
     }
-    const SvcLayer &Lstem = next();
-    if (!front) {
+    {
         ProfScope ps(h, SVC_K_STEM, s);
         const int tx = ceil_div(W, STEM_TW), ty = ceil_div(H, STEM_TH);
-        k_stem_mfma<<<dim3((unsigned)(n * tx * ty)), 256, 0, s>>>(IN, (const float *)h->stem_wt.p, Lstem.b.dev, P[0], NH, NW,
+        k_stem_mfma<<<dim3((unsigned)(n * tx * ty)), 256, 0, s>>>(IN, (const float *)h->stem_wt.p, g.stem.b.dev, stem_out, NH, NW,
                                                                  H, W, tx, ty);
         SVC_CHECK_LAUNCH();
     }
-    int cur = 0;
-    // backbone blocks 1..17  (MobileNetV2.py:111-136)
-    static const int T[7] = {1, 6, 6, 6, 6, 6, 6}, Cc[7] = {16, 24, 32, 64, 96, 160, 320}, Nn[7] = {1, 2, 3, 4, 3, 3, 1},
-                     Ss[7] = {1, 2, 2, 2, 1, 2, 1};
-    int idx = 1, inp = 32;
-    for (int st = 0; st < 7; ++st)
-        for (int i = 0; i < Nn[st]; ++i, ++idx) {
-            const int oup = Cc[st], stride = (i == 0) ? Ss[st] : 1, t = T[st];
-            const bool res = (stride == 1 && inp == oup);
-            const bool tap = (idx == 7 || idx == 14);             // full-resolution output feeds a skip
-            const int dws = (stride == 2 && !tap) ? 2 : 1;        // stride-2 dw == stride-1 dw + ::2 sub-sampling
-            const float *x = P[cur];
-            int OH = H / dws, OW = W / dws;
-            float *y = tap ? p->buf(idx == 7 ? B_F4X : B_F2X) : P[cur ^ 1];
-            // blocks 1-7 run as one fused kernel each; the rest un-fused
-            if (front && idx == 1) {
-                ProfScope ps(h, SVC_K_STEM, s);
-                const SvcLayer &Ld = next();
-                const SvcLayer &Lp = next();
-                FrontArgs A;
-                A.frames = frames; A.h = p->h; A.w = p->w; A.NH = NH; A.NW = NW; A.OH = H; A.OW = W;
-                A.tiles_x = ceil_div(W, FR_TW); A.tiles_y = ceil_div(H, FR_TH);
-                A.hb = (const int *)p->hb.p; A.hk = (const int *)p->hk.p; A.vb = (const int *)p->vb.p; A.vk = (const int *)p->vk.p;
-                A.hks = p->hks; A.vks = p->vks; A.lut = (const float *)p->lut.p;
-                A.Wstem = (const float *)h->stem_wt.p; A.bstem = Lstem.b.dev;
-                RC(lane_weights(h, s, (const float *)h->stem_wt.p, 32, 32, 32, &A.Wstem_l));
-                RC(lane_weights(h, s, Lp.w.dev, 32, 32, 16, &A.Wp_l));
-                A.Wd = Ld.w.dev; A.bd = Ld.b.dev; A.Wp = Lp.w.dev; A.bp = Lp.b.dev;
-                A.Y = y; A.in_dbg = h->keep_input ? IN : nullptr;
-                A.nr_cap = p->fr_nr; A.nc_cap = p->fr_nc;
-                for (int i = 0; i < FR_MAXT; ++i) {
-                    A.row_lo[i] = p->fr_row_lo[i]; A.row_n[i] = p->fr_row_n[i];
-                    A.col_lo[i] = p->fr_col_lo[i]; A.col_n[i] = p->fr_col_n[i];
-                }
-                k_front<<<dim3((unsigned)(n * A.tiles_x * A.tiles_y)), 256, fr_lds, s>>>(A);
-                SVC_CHECK_LAUNCH();
-            } else if (idx <= 7) {
-                const SvcLayer *Le = (t != 1) ? &next() : nullptr;
-                const SvcLayer &Ld = next();
-                const SvcLayer &Lp = next();
-                RC(launch_irb(h, s, x, n, H, W, inp, Le, Ld, Lp, dws, res ? x : nullptr, y));
-            } else {
-                const float *dwin = x;
-                if (t != 1) {
-                    RC(launch_pw(h, s, x, inp, next(), nullptr, 0, E0, inp * t, n * H * W, n));
-                    dwin = E0;
-                }
-                const SvcLayer &Ld = next();
-                if (H * W >= dwpw_min_px(h)) {
-                    const SvcLayer &Lp = next();
-                    RC(launch_dwpw(h, s, dwin, Ld, Lp, res ? x : nullptr, oup, y, oup, n, H, W));
-                } else {
-                    RC(launch_dw(h, s, dwin, Ld, E1, n, H, W));
-                    RC(launch_pw(h, s, E1, inp * t, next(), res ? x : nullptr, oup, y, oup, n * OH * OW, n));
-                }
-            }
-            if (tap) {
-                ProfScope ps(h, SVC_K_RESAMPLE, s);
-                k_subsample<<<blocks256((size_t)n * (OH / 2) * (OW / 2) * (oup / 4)), 256, 0, s>>>(y, P[cur ^ 1], n, OH,
-                                                                                                  OW, oup);
-                SVC_CHECK_LAUNCH();
-                OH /= 2; OW /= 2;
-            }
-            H = OH; W = OW;
-            cur ^= 1;
-            inp = oup;
+    return launch_irb(h, s, stem_out, n, H, W, B, 1, nullptr, y);
+}
+
+// A block's depthwise + project pair (+ residual R): fused on the levels of at least dwpw_min_px pixels, else two kernels
+// through `dw_out`.
+static int dw_project(SvcHandle *h, hipStream_t s, const float *X, const InvRes &B, const float *R, int ldr, float *dw_out, float *Y,
+                      int n, int H, int W) {
+    if (H * W >= dwpw_min_px(h)) return launch_dwpw(h, s, X, B.dw, B.project, R, ldr, Y, B.oup, n, H, W);
+    RC(launch_dw(h, s, X, B.dw, dw_out, n, H, W));
+    return launch_pw(h, s, dw_out, B.dw.cout, B.project, R, ldr, Y, B.oup, n * H * W, n);
+}
+
+// Backbone block idx = 2 .. 17 (features.idx) on the H x W level: x -> out, H and W updated to the block's output level.
+static int backbone_block(SvcHandle *h, hipStream_t s, int idx, const float *x, float *out, int n, int &H, int &W) {
+    NetPlan *p = h->plan;
+    const InvRes &B = h->net.block[idx - 1];
+    const float *res = (B.stride == 1 && B.inp == B.oup) ? x : nullptr;
+    const bool tap = (idx == 7 || idx == 14);               // full-resolution output feeds a skip
+    const int dws = (B.stride == 2 && !tap) ? 2 : 1;        // stride-2 dw == stride-1 dw + ::2 sub-sampling
+    int OH = H / dws, OW = W / dws;
+    float *y = tap ? p->buf(idx == 7 ? B_F4X : B_F2X) : out;
+    // blocks 1-7 run as one fused kernel each; the rest un-fused
+    if (idx <= 7) RC(launch_irb(h, s, x, n, H, W, B, dws, res, y));
+    else {
+        const float *dwin = x;               // (blocks 8-17 all expand, and none strides: block 14, the one stride-2 block, is a tap)
+        if (B.has_expand) {
+            dwin = p->buf(B_E0);
+            RC(launch_pw(h, s, x, B.inp, B.expand, nullptr, 0, p->buf(B_E0), B.dw.cin, n * H * W, n));
         }
-    // features.18 -> CAT1[:, 0:1280], Gaussian maps -> CAT1[:, 1280:1296]
-    const int H5 = H, W5 = W, H4 = 2 * H5, W4 = 2 * W5, H3 = 4 * H5, W3 = 4 * W5;
-    float *CAT1 = p->buf(B_CAT1);
-    RC(launch_pw(h, s, P[cur], 320, next(), nullptr, 0, CAT1, 1296, n * H5 * W5, n));
-    // skips (model.py:443-444)
-    float *CAT2 = p->buf(B_CAT2), *CAT3 = p->buf(B_CAT3);
-    {
-        const SvcLayer &Le2 = next();
-        const SvcLayer &Lr2 = next();
-        RC(launch_pwpw(h, s, p->buf(B_F2X), 160, Le2, Lr2, CAT2 + 256, 384, n * H4 * W4));
-        const SvcLayer &Le4 = next();
-        const SvcLayer &Lr4 = next();
-        RC(launch_pwpw(h, s, p->buf(B_F4X), 64, Le4, Lr4, CAT3 + 128, 192, n * H3 * W3));
+        RC(dw_project(h, s, dwin, B, res, B.oup, p->buf(B_E1), y, n, H, W));
     }
-    next();   // GAUSS placeholder layer (raw parameters; maps live in plan->gauss)
+    if (tap) {
+        ProfScope ps(h, SVC_K_RESAMPLE, s);
+        k_subsample<<<blocks256((size_t)n * (OH / 2) * (OW / 2) * (B.oup / 4)), 256, 0, s>>>(y, out, n, OH, OW, B.oup);
+        SVC_CHECK_LAUNCH();
+        OH /= 2; OW /= 2;
+    }
+    H = OH; W = OW;
+    return SVC_OK;
+}
+
+// The head on the lowest level (H5 x W5): features.18 -> CAT1[:, 0:1280], the two skip branches (model.py:443-444) into their
+// halves of CAT2 / CAT3, the Gaussian maps -> CAT1[:, 1280:1296], post_cnn -> PC.
+static int net_head(SvcHandle *h, hipStream_t s, const float *x, int n, int H5, int W5) {
+    NetPlan *p = h->plan;
+    const NetGraph &g = h->net;
+    float *CAT1 = p->buf(B_CAT1);
+    RC(launch_pw(h, s, x, 320, g.f18, nullptr, 0, CAT1, 1296, n * H5 * W5, n));
+    RC(launch_pwpw(h, s, p->buf(B_F2X), 160, g.skip2x_expand, g.skip2x_reduce, p->buf(B_CAT2) + 256, 384, n * 4 * H5 * W5));
+    RC(launch_pwpw(h, s, p->buf(B_F4X), 64, g.skip4x_expand, g.skip4x_reduce, p->buf(B_CAT3) + 128, 192, n * 16 * H5 * W5));
     if (p->gauss_filled < n) {       // the prior maps are constants: nothing else writes channels 1280..1295 of CAT1
         ProfScope ps(h, SVC_K_RESAMPLE, s);
         k_gauss_fill<<<blocks256((size_t)n * H5 * W5 * 16), 256, 0, s>>>((const float *)p->gauss.p, CAT1, n, H5 * W5,
@@ -2735,56 +2691,45 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
         SVC_CHECK_LAUNCH();
         p->gauss_filled = n;
     }
-    // post_cnn
-    if (H5 * W5 >= dwpw_min_px(h)) {
-        const SvcLayer &Ld = next();
-        RC(launch_dwpw(h, s, CAT1, Ld, next(), nullptr, 0, p->buf(B_PC), 256, n, H5, W5));
-    } else {
-        RC(launch_dw(h, s, CAT1, next(), p->buf(B_PCD), n, H5, W5));
-        RC(launch_pw(h, s, p->buf(B_PCD), 1296, next(), nullptr, 0, p->buf(B_PC), 256, n * H5 * W5, n));
-    }
-    // US1 + concat, US2 block: expand(concat(up(PC), skip)) = relu6(up(W[:, :256] . PC) + W[:, 256:] . skip + b)
-    {
-        const SvcLayer &Le = next();
-        RC(launch_pw_ex(h, s, p->buf(B_PC), 256, Le.w.dev, 384, 256, nullptr, 0, 768, nullptr, 0, p->buf(B_T1), 768,
-                        n * H5 * W5, n, nullptr));
-        const UpsAdd ua{p->buf(B_T1), H5, W5, 768, make_fdiv(W4), make_fdiv(H4)};
-        RC(launch_pw_ex(h, s, CAT2 + 256, 384, Le.w.dev + 256, 384, 128, Le.b.dev, Le.relu6, 768, nullptr, 0,
-                        p->buf(B_U2E), 768, n * H4 * W4, n, &ua));
-        const SvcLayer &Ld = next();
-        RC(launch_dwpw(h, s, p->buf(B_U2E), Ld, next(), nullptr, 0, p->buf(B_U2), 128, n, H4, W4));
-    }
-    {
-        const SvcLayer &Le = next();
-        RC(launch_pw_ex(h, s, p->buf(B_U2), 128, Le.w.dev, 192, 128, nullptr, 0, 384, nullptr, 0, p->buf(B_T2), 384,
-                        n * H4 * W4, n, nullptr));
-        const UpsAdd ua{p->buf(B_T2), H4, W4, 384, make_fdiv(W3), make_fdiv(H3)};
-        RC(launch_pw_ex(h, s, CAT3 + 128, 192, Le.w.dev + 128, 192, 64, Le.b.dev, Le.relu6, 384, nullptr, 0,
-                        p->buf(B_P3E), 384, n * H3 * W3, n, &ua));
-        const SvcLayer &Ld = next();
-        RC(launch_dwpw(h, s, p->buf(B_P3E), Ld, next(), nullptr, 0, p->buf(B_DEC), 64, n, H3, W3));
-    }
-    // adaptation, smoothing, resize, quantise
-    const SvcLayer &La = next();
+    return dw_project(h, s, CAT1, g.post_cnn, nullptr, 0, p->buf(B_PCD), p->buf(B_PC), n, H5, W5);
+}
+
+// One decoder block (upsampling_2, post_upsampling_2): up-sample `lo` (Hl x Wl, Cl channels) x2, concatenate the skip half of
+// `cat` (row stride B.inp, behind the Cl channels `lo` would take), then the block.  The expansion is split instead:
+// expand(concat(up(lo), skip)) = relu6(up(W[:, :Cl] . lo) + W[:, Cl:] . skip + b), the first product in T at the low level.
+static int decoder_block(SvcHandle *h, hipStream_t s, const InvRes &B, const float *lo, int Cl, int Hl, int Wl, const float *cat,
+                         float *T, float *E, float *Y, int n) {
+    const SvcLayer &Le = B.expand;
+    const int Ce = Le.cout, H = 2 * Hl, W = 2 * Wl;
+    RC(launch_pw_ex(h, s, lo, Cl, Le.w.dev, B.inp, Cl, nullptr, 0, Ce, nullptr, 0, T, Ce, n * Hl * Wl, n, nullptr));
+    const UpsAdd ua{T, Hl, Wl, Ce, make_fdiv(W), make_fdiv(H)};
+    RC(launch_pw_ex(h, s, cat + Cl, B.inp, Le.w.dev + Cl, B.inp, B.inp - Cl, Le.b.dev, Le.relu6, Ce, nullptr, 0, E, Ce, n * H * W, n, &ua));
+    return launch_dwpw(h, s, E, B.dw, B.project, nullptr, 0, Y, B.oup, n, H, W);
+}
+
+// Adaptation, smoothing + resize to the saliency size, quantise (profile_rows: the banded variant, which also fills the
+// caller's border-profile rows for svc_saliency_profile_u8).
+static int net_tail(SvcHandle *h, hipStream_t s, int n, int H3, int W3, uint8_t *maps, int thr, unsigned *census_rows, unsigned *profile_rows) {
+    NetPlan *p = h->plan;
+    const int NH = p->NH, NW = p->NW;
     {
         ProfScope ps(h, SVC_K_RESAMPLE, s);
-        k_adapt<<<blocks256((size_t)n * H3 * W3), 256, 0, s>>>(p->buf(B_DEC), La.w.dev, La.b.dev, p->buf(B_LOGIT),
+        k_adapt<<<blocks256((size_t)n * H3 * W3), 256, 0, s>>>(p->buf(B_DEC), h->net.adapt.w.dev, h->net.adapt.b.dev, p->buf(B_LOGIT),
                                                               (size_t)n * H3 * W3, (unsigned *)p->fmax.p, n,
                                                               (unsigned long long *)h->census.p, h->chunk);
         SVC_CHECK_LAUNCH();
     }
     // B_LOGIT per-frame stride may exceed H3*W3 (rounded to 4): compact layout is used instead.  NH, NW = 8 H3, 8 W3 (the
     // network input sizes are multiples of 32)
-    const SvcLayer &Ls = next();
     ProfScope ps_smooth(h, SVC_K_SMOOTH, s);
     {
         dim3 grid(ceil_div(p->h, SD_ROWS), n);
         const size_t lds = ((size_t)H3 * W3 + 64 * SD_KP + (size_t)p->sd_tile_cap * NW) * sizeof(float);
-        k_smooth_down_mfma<<<grid, 256, lds, s>>>(p->buf(B_LOGIT), Ls.w.dev, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3,
+        k_smooth_down_mfma<<<grid, 256, lds, s>>>(p->buf(B_LOGIT), h->net.smooth.w.dev, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3,
                                                   NH, NW, p->h, p->w, SD_ROWS, p->sd_tile_cap, make_fdiv(p->w));
         SVC_CHECK_LAUNCH();
     }
-    if (profile_rows) {         // svc_saliency_profile_u8: the banded variant also fills the caller's border-profile rows
+    if (profile_rows) {
         k_quantise_profile<<<dim3(ceil_div(p->h, BP_ROWS), n), 256, 0, s>>>(p->buf(B_PRE), (const unsigned *)p->fmax.p, maps, p->h, p->w,
                                                                             thr, (unsigned long long *)h->census.p, census_rows,
                                                                             profile_rows);
@@ -2794,6 +2739,23 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
                                                                      (unsigned long long *)h->census.p, census_rows);
     }
     SVC_CHECK_LAUNCH();
+    return SVC_OK;
+}
+
+// One pass of the network over n <= plan->nb frames.
+static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *maps, hipStream_t s, int thr = 0, unsigned *census_rows = nullptr,
+                         unsigned *profile_rows = nullptr) {
+    NetPlan *p = h->plan;
+    const NetGraph &g = h->net;
+    float *P[2] = {p->buf(B_P0), p->buf(B_P1)};
+    int H = p->NH / 2, W = p->NW / 2, cur = 1;
+    RC(net_front(h, s, frames, n, P[0], P[1]));
+    for (int idx = 2; idx <= 17; ++idx, cur ^= 1) RC(backbone_block(h, s, idx, P[cur], P[cur ^ 1], n, H, W));
+    const int H5 = H, W5 = W;                               // the levels: /32, /16 (H4 = 2 H5), /8 (H3 = 4 H5)
+    RC(net_head(h, s, P[cur], n, H5, W5));
+    RC(decoder_block(h, s, g.us2, p->buf(B_PC), 256, H5, W5, p->buf(B_CAT2), p->buf(B_T1), p->buf(B_U2E), p->buf(B_U2), n));
+    RC(decoder_block(h, s, g.post_us2, p->buf(B_U2), 128, 2 * H5, 2 * W5, p->buf(B_CAT3), p->buf(B_T2), p->buf(B_P3E), p->buf(B_DEC), n));
+    RC(net_tail(h, s, n, 4 * H5, 4 * W5, maps, thr, census_rows, profile_rows));
     if (thr > 0) h->census_maps += (unsigned long long)n;
     p->last_n = n;
     return SVC_OK;
@@ -2881,17 +2843,7 @@ extern "C" int svc_debug_tap(SvcHandle *h, int which, int frame, float *out_host
     NetPlan *p = h->plan;
     static const int map[7] = {B_IN, B_F4X, B_F2X, B_CAT1, B_PC, B_DEC, B_PRE};
     if (which < 0 || which > 6 || frame < 0 || frame >= p->last_n) { svc_set_error("svc_debug_tap: bad tap/frame"); return SVC_E_INVALID; }
-    const int NH = p->NH, NW = p->NW;
-    size_t count;
-    switch (which) {
-        case SVC_TAP_INPUT: count = (size_t)NH * NW * 3; break;
-        case SVC_TAP_FEAT4X: count = (size_t)(NH / 8) * (NW / 8) * 64; break;
-        case SVC_TAP_FEAT2X: count = (size_t)(NH / 16) * (NW / 16) * 160; break;
-        case SVC_TAP_FEAT1X: count = (size_t)(NH / 32) * (NW / 32) * 1296; break;
-        case SVC_TAP_POSTCNN: count = (size_t)(NH / 32) * (NW / 32) * 256; break;
-        case SVC_TAP_DEC: count = (size_t)(NH / 8) * (NW / 8) * 64; break;
-        default: count = (size_t)p->h * p->w; break;
-    }
+    const size_t count = which == SVC_TAP_PRE ? (size_t)p->h * p->w : buf_floats(p->NH, p->NW, map[which]);     // PRE: at the saliency size
     if (count > cap_floats) { svc_set_error("svc_debug_tap: buffer too small (%zu needed)", count); return SVC_E_INVALID; }
     if (which == SVC_TAP_INPUT && p->last_front && !h->keep_input) {
         svc_set_error("svc_debug_tap: the fused front kernel keeps the network input on chip; create the handle with SVC_KEEP_INPUT=1 (or SVC_FRONT=0)");
@@ -2944,25 +2896,52 @@ static int take(SvcHandle *h, size_t &ti, size_t expect, SvcTensor &out, const c
     return SVC_OK;
 }
 
-static int add_pw(SvcHandle *h, size_t &ti, int cin, int cout, int relu6, const char *what) {
-    SvcLayer L{SvcLayer::PW, cin, cout, 1, relu6, {}, {}};
-    const size_t npad = (cout + 31) / 32 * 32;
-    RC(take(h, ti, npad * cin, L.w, what));
-    RC(take(h, ti, (size_t)cout, L.b, what));
-    h->layers.push_back(L);
-    return SVC_OK;
+static int add_pw(SvcHandle *h, size_t &ti, int cin, int cout, int relu6, const char *what, SvcLayer &L) {
+    L = SvcLayer{cin, cout, 1, relu6, {}, {}};
+    RC(take(h, ti, (size_t)((cout + 31) / 32 * 32) * cin, L.w, what));
+    return take(h, ti, (size_t)cout, L.b, what);
 }
-static int add_dw(SvcHandle *h, size_t &ti, int c, int stride, const char *what) {
-    SvcLayer L{SvcLayer::DW, c, c, stride, 1, {}, {}};
+static int add_dw(SvcHandle *h, size_t &ti, int c, int stride, const char *what, SvcLayer &L) {
+    L = SvcLayer{c, c, stride, 1, {}, {}};
     RC(take(h, ti, (size_t)9 * c, L.w, what));
-    RC(take(h, ti, (size_t)c, L.b, what));
-    h->layers.push_back(L);
-    return SVC_OK;
+    return take(h, ti, (size_t)c, L.b, what);
 }
-static int add_inv_res(SvcHandle *h, size_t &ti, int inp, int oup, int t, int stride, const char *what) {
-    if (t != 1) RC(add_pw(h, ti, inp, inp * t, 1, what));
-    RC(add_dw(h, ti, inp * t, stride, what));
-    RC(add_pw(h, ti, inp * t, oup, 0, what));
+static int add_inv_res(SvcHandle *h, size_t &ti, int inp, int oup, int t, int stride, const char *what, InvRes &B) {
+    B = InvRes{{}, {}, {}, t != 1, inp, oup, stride};
+    if (t != 1) RC(add_pw(h, ti, inp, inp * t, 1, what, B.expand));
+    RC(add_dw(h, ti, inp * t, stride, what, B.dw));
+    return add_pw(h, ti, inp * t, oup, 0, what, B.project);
+}
+
+// The MobileNetV2 stages (MobileNetV2.py:111-136): expansion factor, output channels, blocks, stride of the first block.
+static const struct { int t, c, n, s; } MBV2_STAGES[7] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2},
+                                                          {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
+
+// Names the blob's tensors: h->tensors -> h->net, in the order of retargetvid_amd.weights.fold_state_dict.
+static int fill_graph(SvcHandle *h) {
+    NetGraph &g = h->net;
+    size_t ti = 0;
+    g.stem = SvcLayer{3, 32, 2, 1, {}, {}};
+    RC(take(h, ti, 27 * 32, g.stem.w, "stem.w"));
+    RC(take(h, ti, 32, g.stem.b, "stem.b"));
+    int inp = 32, idx = 0;
+    for (const auto &st : MBV2_STAGES)
+        for (int i = 0; i < st.n; ++i, inp = st.c) RC(add_inv_res(h, ti, inp, st.c, st.t, i == 0 ? st.s : 1, "backbone", g.block[idx++]));
+    RC(add_pw(h, ti, 320, 1280, 1, "features.18", g.f18));
+    RC(add_pw(h, ti, 160, 320, 1, "skip_2x.expansion", g.skip2x_expand));
+    RC(add_pw(h, ti, 320, 128, 0, "skip_2x.reduction", g.skip2x_reduce));
+    RC(add_pw(h, ti, 64, 128, 1, "skip_4x.expansion", g.skip4x_expand));
+    RC(add_pw(h, ti, 128, 64, 0, "skip_4x.reduction", g.skip4x_reduce));
+    RC(take(h, ti, 64, g.gauss, "gaussians"));
+    RC(add_inv_res(h, ti, 1296, 256, 1, 1, "post_cnn", g.post_cnn));
+    RC(add_inv_res(h, ti, 384, 128, 2, 1, "upsampling_2", g.us2));
+    RC(add_inv_res(h, ti, 192, 64, 2, 1, "post_upsampling_2", g.post_us2));
+    g.adapt = SvcLayer{64, 1, 1, 0, {}, {}};
+    RC(take(h, ti, 64, g.adapt.w, "adaptation.w"));
+    RC(take(h, ti, 1, g.adapt.b, "adaptation.b"));
+    g.smooth = SvcLayer{1, 1, 1, 0, {}, {}};
+    RC(take(h, ti, 64 * 49, g.smooth.w, "smoothing phase table"));
+    if (ti != h->tensors.size()) { svc_set_error("svc_create: %zu unused tensors in blob", h->tensors.size() - ti); return SVC_E_BLOB; }
     return SVC_OK;
 }
 
@@ -3033,56 +3012,21 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
         if ((off + cnt) * 4 > n_bytes) { svc_set_error("svc_create: tensor %zu out of range", i); svc_destroy(h); return SVC_E_BLOB; }
         h->tensors.push_back(SvcTensor{(const float *)h->blob.p + off, (size_t)cnt});
     }
-    // walk the fixed graph (same order as retargetvid_amd.weights.fold_state_dict)
-    size_t ti = 0;
     auto fail = [&](int code) { svc_destroy(h); return code; };
-    {
-        SvcLayer L{SvcLayer::STEM, 3, 32, 2, 1, {}, {}};
-        if ((rc = take(h, ti, 27 * 32, L.w, "stem.w")) || (rc = take(h, ti, 32, L.b, "stem.b"))) return fail(rc);
-        h->layers.push_back(L);
-        // [27 taps][32 out] -> [32 out][32 taps] for k_stem_mfma
-        const float *w_host = (const float *)blob_host + (L.w.dev - (const float *)h->blob.p);
-        std::vector<float> wt(32 * 32, 0.f);
-        for (int k = 0; k < 27; ++k)
-            for (int co = 0; co < 32; ++co) wt[co * 32 + k] = w_host[k * 32 + co];
-        if ((rc = h->stem_wt.ensure(wt.size() * 4))) return fail(rc);
-        if (hipMemcpy(h->stem_wt.p, wt.data(), wt.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            svc_set_error("svc_create: stem weight upload failed");
-            return fail(SVC_E_HIP);
-        }
+    if ((rc = fill_graph(h))) return fail(rc);
+    // host copies of what the host computes with (the blob's device image is at the same offsets)
+    const float *host = (const float *)blob_host, *dev = (const float *)h->blob.p;
+    h->gauss_params.assign(host + (h->net.gauss.dev - dev), host + (h->net.gauss.dev - dev) + 64);
+    // the stem's weights [27 taps][32 out] -> [32 out][32 taps] for k_stem_mfma
+    const float *w_host = host + (h->net.stem.w.dev - dev);
+    std::vector<float> wt(32 * 32, 0.f);
+    for (int k = 0; k < 27; ++k)
+        for (int co = 0; co < 32; ++co) wt[co * 32 + k] = w_host[k * 32 + co];
+    if ((rc = h->stem_wt.ensure(wt.size() * 4))) return fail(rc);
+    if (hipMemcpy(h->stem_wt.p, wt.data(), wt.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        svc_set_error("svc_create: stem weight upload failed");
+        return fail(SVC_E_HIP);
     }
-    static const int T[7] = {1, 6, 6, 6, 6, 6, 6}, Cc[7] = {16, 24, 32, 64, 96, 160, 320}, Nn[7] = {1, 2, 3, 4, 3, 3, 1},
-                     Ss[7] = {1, 2, 2, 2, 1, 2, 1};
-    int inp = 32;
-    for (int st = 0; st < 7; ++st)
-        for (int i = 0; i < Nn[st]; ++i) {
-            if ((rc = add_inv_res(h, ti, inp, Cc[st], T[st], i == 0 ? Ss[st] : 1, "backbone"))) return fail(rc);
-            inp = Cc[st];
-        }
-    if ((rc = add_pw(h, ti, 320, 1280, 1, "features.18"))) return fail(rc);
-    if ((rc = add_pw(h, ti, 160, 320, 1, "skip_2x.expansion")) || (rc = add_pw(h, ti, 320, 128, 0, "skip_2x.reduction")) ||
-        (rc = add_pw(h, ti, 64, 128, 1, "skip_4x.expansion")) || (rc = add_pw(h, ti, 128, 64, 0, "skip_4x.reduction")))
-        return fail(rc);
-    {
-        SvcLayer L{SvcLayer::GAUSS, 16, 16, 1, 0, {}, {}};
-        if ((rc = take(h, ti, 64, L.w, "gaussians"))) return fail(rc);
-        h->layers.push_back(L);
-        h->gauss_params.resize(64);
-        const uint8_t *base = (const uint8_t *)blob_host;
-        memcpy(h->gauss_params.data(), base + ((const uint8_t *)L.w.dev - (const uint8_t *)h->blob.p), 64 * 4);
-    }
-    if ((rc = add_inv_res(h, ti, 1296, 256, 1, 1, "post_cnn")) || (rc = add_inv_res(h, ti, 384, 128, 2, 1, "upsampling_2")) ||
-        (rc = add_inv_res(h, ti, 192, 64, 2, 1, "post_upsampling_2")))
-        return fail(rc);
-    {
-        SvcLayer L{SvcLayer::ADAPT, 64, 1, 1, 0, {}, {}};
-        if ((rc = take(h, ti, 64, L.w, "adaptation.w")) || (rc = take(h, ti, 1, L.b, "adaptation.b"))) return fail(rc);
-        h->layers.push_back(L);
-        SvcLayer S{SvcLayer::SMOOTH, 1, 1, 1, 0, {}, {}};
-        if ((rc = take(h, ti, 64 * 49, S.w, "smoothing phase table"))) return fail(rc);
-        h->layers.push_back(S);
-    }
-    if (ti != h->tensors.size()) { svc_set_error("svc_create: %zu unused tensors in blob", h->tensors.size() - ti); return fail(SVC_E_BLOB); }
     *out = h;
     return SVC_OK;
 }
@@ -3153,8 +3097,7 @@ extern "C" int svc_destroy(SvcHandle *h) {
     h->tail_ws.release();
     h->tail_offsets.release();
     h->tail_ring_cnt.release();
-    for (auto &kv : h->lane_w) kv.second.release();
-    for (auto &kv : h->x3_w) kv.second.release();
+    for (auto &kv : h->w_copies) kv.second.release();
     h->census.release();
     for (auto &kv : h->tail_delta) kv.second.release();
     h->stem_wt.release();

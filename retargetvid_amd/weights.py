@@ -351,7 +351,7 @@ def smoothing_phase_table(k41):
 
 
 def fold_state_dict(sd):
-    """-> ordered list of layer dicts in execution order (see csrc/svc_net.cpp)."""
+    """-> ordered list of layer dicts in execution order (see fill_graph in csrc/svc_net.hip)."""
     sd = to_numpy_state_dict(sd)
     L = []
     wf, bf = _fold(sd, 'cnn.features.0.0.weight', 'cnn.features.0.1')
@@ -389,7 +389,7 @@ def pack_blob(layers):
     """Serialise folded layers: header {magic, n_tensors}, then per tensor
     {offset_floats, n_floats} (u64 each), then the fp32 payload (each tensor 64-B
     aligned).  Tensor order is fixed: for every layer its ``w`` then (if any) ``b``;
-    csrc/svc_net.cpp walks the same order."""
+    fill_graph in csrc/svc_net.hip walks the same order."""
     tensors = []
     for l in layers:
         w = np.ascontiguousarray(l['w'], np.float32)

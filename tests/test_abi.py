@@ -3,7 +3,9 @@ declares; without a GPU svc_create reports an error instead of crashing."""
 import ctypes
 import os
 import re
+import struct
 
+import pytest
 import torch
 
 from retargetvid_amd import _lib, weights
@@ -46,6 +48,53 @@ def test_create_reports_errors():
         assert lib.svc_create(buf, len(blob), 0, ctypes.byref(h)) < 0
         assert len(lib.svc_last_error()) > 0
     assert lib.svc_destroy(None) == 0
+
+
+def _blob_with_table(blob, table, magic=None, count=None):
+    """The blob with another tensor table [(offset_floats, n_floats)] in front of the same payload (the offsets move with the header's
+    size); magic / count: what the first two header words say instead of the blob's magic and len(table)."""
+    m, nt = struct.unpack_from('<QQ', blob, 0)
+    head = (16 + 16 * nt + 63) // 64 * 64
+    new_head = (16 + 16 * len(table) + 63) // 64 * 64
+    out = bytearray(new_head) + blob[head:]
+    struct.pack_into('<QQ', out, 0, m if magic is None else magic, len(table) if count is None else count)
+    for i, (off, n) in enumerate(table):
+        struct.pack_into('<QQ', out, 16 + 16 * i, off + (new_head - head) // 4, n)
+    return bytes(out)
+
+
+@pytest.mark.gpu
+def test_create_rejects_malformed_blobs(synthetic_sd):
+    """svc_create names the blob's tensors in the order of weights.fold_state_dict: a blob with a tensor too few, one too many, a
+    tensor of the wrong size, a wrong magic or a tensor count beyond its bytes is refused with SVC_E_BLOB and a message that says
+    which; the blob as packed creates a handle.  No kernel is launched."""
+    lib = _lib.load()
+    layers = weights.fold_state_dict(synthetic_sd)
+    blob = weights.pack_blob(layers)
+    nt = struct.unpack_from('<QQ', blob, 0)[1]
+    table = [struct.unpack_from('<QQ', blob, 16 + 16 * i) for i in range(nt)]
+    assert _blob_with_table(blob, table) == blob
+    names = [l['name'] for l in layers for _ in range(2 if 'b' in l else 1)]              # one per tensor: w, then b where there is one
+    mid = names.index('skip_4x.reduce')                                                  # its weight: [64][128]
+    assert table[mid][1] == 64 * 128
+    wrong = list(table)
+    wrong[mid] = (table[mid][0], table[mid][1] - 1)
+    E_BLOB = -3
+    cases = [('good', blob, 0, None),
+             ('last tensor dropped', _blob_with_table(blob, table[:-1]), E_BLOB, b'blob: ran out of tensors at smoothing phase table'),
+             ('one tensor appended', _blob_with_table(blob, table + [(table[0][0], 1)]), E_BLOB, b'1 unused tensors in blob'),
+             ('wrong float count', _blob_with_table(blob, wrong), E_BLOB,
+              b'blob: tensor %d (skip_4x.reduction) has 8191 floats, expected 8192' % mid),
+             ('wrong magic', _blob_with_table(blob, table, magic=weights.BLOB_MAGIC + 1), E_BLOB, b'bad blob magic'),
+             ('count past the bytes', _blob_with_table(blob, table, count=len(blob)), E_BLOB, b'truncated blob header')]
+    for label, data, want, text in cases:
+        h = ctypes.c_void_p()
+        rc = lib.svc_create(ctypes.create_string_buffer(data, len(data)), len(data), 0, ctypes.byref(h))
+        assert rc == want, (label, rc, lib.svc_last_error())
+        if want:
+            assert text in lib.svc_last_error() and not h.value, (label, lib.svc_last_error())
+        else:
+            assert h.value and lib.svc_destroy(h) == 0, label
 
 
 def test_host_stage_entries_check_their_arguments():

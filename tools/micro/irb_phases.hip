@@ -29,15 +29,15 @@ static void study(const char *name, int n, int H, int W) {
     unsigned long long *st;
     hipMalloc(&st, (size_t)wgs * 8 * 8);
     hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), &st, sizeof st);
-    auto kfn = k_irb<S, TOH, TOW, true, false, CI, CE, CO>;
+    auto kfn = k_irb<S, TOH, TOW, true, CI, CE, CO>;
     hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
     const size_t lds = IrbGeom<S, TOH, TOW>::lds_floats(CI, CoutP, true, CE) * 4;
     hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
-    for (int it = 0; it < 3; ++it) kfn<<<wgs, 256, lds, 0>>>(X, H, W, CI, We, be, CE, Wd, bd, Wp, bp, CO, CoutP, nullptr, Y, CO, OH, OW, tx, ty, nullptr, nullptr);
+    for (int it = 0; it < 3; ++it) kfn<<<wgs, 256, lds, 0>>>(X, H, W, CI, We, be, CE, Wd, bd, Wp, bp, CO, CoutP, nullptr, Y, CO, OH, OW, tx, ty);
     hipDeviceSynchronize();
     hipMemset(st, 0, (size_t)wgs * 8 * 8);
     hipEventRecord(a, 0);
-    kfn<<<wgs, 256, lds, 0>>>(X, H, W, CI, We, be, CE, Wd, bd, Wp, bp, CO, CoutP, nullptr, Y, CO, OH, OW, tx, ty, nullptr, nullptr);
+    kfn<<<wgs, 256, lds, 0>>>(X, H, W, CI, We, be, CE, Wd, bd, Wp, bp, CO, CoutP, nullptr, Y, CO, OH, OW, tx, ty);
     hipEventRecord(b, 0); hipEventSynchronize(b);
     float ms; hipEventElapsedTime(&ms, a, b);
     std::vector<unsigned long long> h((size_t)wgs * 8);

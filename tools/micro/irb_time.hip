@@ -21,17 +21,17 @@ static double study(const char *name, int n, int H, int W) {
     hipMemcpy(We, hw.data(), (size_t)(CE + 32) * CI * 4, hipMemcpyHostToDevice); hipMemset(be, 0, (CE + 32) * 4);
     hipMemcpy(Wd, hw.data(), 9 * (CE + 32) * 4, hipMemcpyHostToDevice); hipMemset(bd, 0, (CE + 32) * 4);
     hipMemcpy(Wp, hw.data(), (size_t)CoutP * (CE + 32) * 4, hipMemcpyHostToDevice); hipMemset(bp, 0, CoutP * 4);
-    auto kfn = k_irb<S, TOH, TOW, true, false, CI, CE, CO>;
+    auto kfn = k_irb<S, TOH, TOW, true, CI, CE, CO>;
     hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
     const bool xreg = IRB_XREG && CI <= 32 && CI % 8 == 0;
     const size_t lds = IrbGeom<S, TOH, TOW>::lds_floats(CI, CoutP, true, CE, xreg) * 4;
     hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
-    for (int it = 0; it < 5; ++it) kfn<<<wgs, 256, lds, 0>>>(X, H, W, CI, We, be, CE, Wd, bd, Wp, bp, CO, CoutP, nullptr, Y, CO, OH, OW, tx, ty, nullptr, nullptr);
+    for (int it = 0; it < 5; ++it) kfn<<<wgs, 256, lds, 0>>>(X, H, W, CI, We, be, CE, Wd, bd, Wp, bp, CO, CoutP, nullptr, Y, CO, OH, OW, tx, ty);
     hipDeviceSynchronize();
     std::vector<float> t;
     for (int it = 0; it < 9; ++it) {
         hipEventRecord(a, 0);
-        kfn<<<wgs, 256, lds, 0>>>(X, H, W, CI, We, be, CE, Wd, bd, Wp, bp, CO, CoutP, nullptr, Y, CO, OH, OW, tx, ty, nullptr, nullptr);
+        kfn<<<wgs, 256, lds, 0>>>(X, H, W, CI, We, be, CE, Wd, bd, Wp, bp, CO, CoutP, nullptr, Y, CO, OH, OW, tx, ty);
         hipEventRecord(b, 0); hipEventSynchronize(b);
         float ms; hipEventElapsedTime(&ms, a, b); t.push_back(ms * 1e3f);
     }
