@@ -80,8 +80,9 @@ const char *svc_last_error(void);
  * 7 = svc_debug_transnet_tap (SVC_SHOT_TAP_*) exists; svc_create rejects SVC_SHOT_M16 outside 2..4 with SVC_E_INVALID.
  * 8 = svc_border_profile_u8, svc_saliency_profile_u8 and the profile class SVC_K_BORDER exist.
  * 9 = svc_resize_frames_nv12 and svc_render_crops_nv12 exist (NV12 input).
- * 10 = svc_render_crops_u8_to_nv12 and svc_render_crops_nv12_to_nv12 exist (NV12 output). */
-#define SVC_ABI_VERSION 10
+ * 10 = svc_render_crops_u8_to_nv12 and svc_render_crops_nv12_to_nv12 exist (NV12 output).
+ * 11 = svc_debug_run_node (SVC_NODE_*) exists. */
+#define SVC_ABI_VERSION 11
 int svc_abi_version(void);
 
 /* weights_blob_host: the packed, BN-folded static SALICON slice of a UNISAL
@@ -353,6 +354,43 @@ int svc_debug_transnet_tap(SvcHandle *h, const uint8_t *frames, int n_windows, i
 #define SVC_TAP_DEC 5       /* [32][52][64]   post_upsampling_2 output          */
 #define SVC_TAP_PRE 6       /* [h][w]         pre-softmax map at saliency size  */
 int svc_debug_tap(SvcHandle *h, int which, int frame, float *out_host, size_t cap_floats);
+/* Debug/test entry point: runs ONE node of the saliency network on the caller's input, through the stage function the
+ * pass itself calls, on the null stream, and copies the node's output buffer to the host.  Plans (height, width, n) like
+ * svc_saliency_u8; n is at most one pass (SVC_CHUNK).  Inputs and outputs are fp32 NHWC host arrays of n frames at the
+ * node's level of the network size (NH, NW) that (height, width) selects:
+ *   2 .. 17 (SVC_NODE_BLOCK)   cnn.features.<node>: in0 = the block's input, out = what the next block reads (blocks 7 and
+ *                              14: behind the ::2 sub-sampling; SVC_NODE_F4X / SVC_NODE_F2X return their full-resolution
+ *                              output, the skip branches' input)
+ *   SVC_NODE_FRONT             LANCZOS + features.0 + features.1: in0 = uint8 [n][height][width][3], out [NH/2][NW/2][16]
+ *   SVC_NODE_F18               in0 [NH/32][NW/32][320] -> the whole row [..][1296]: channels 0..1279 written
+ *   SVC_NODE_SKIP_2X / _4X     in0 = F2X [NH/16][NW/16][160] / F4X [NH/8][NW/8][64] -> the whole row of 384 / 192 channels:
+ *                              the branch's half (from channel 256 / 128) written
+ *   SVC_NODE_POST_CNN          in0 = the whole 1296-channel row -> [NH/32][NW/32][256]
+ *   SVC_NODE_US2 / _POST_US2   in0 = the low-resolution tensor ([NH/32][NW/32][256] / [NH/16][NW/16][128]), in1 = the skip half
+ *                              ([NH/16][NW/16][128] / [NH/8][NW/8][64]) -> [NH/16][NW/16][128] / [NH/8][NW/8][64]
+ *   SVC_NODE_ADAPT             in0 [NH/8][NW/8][64] -> logits [NH/8][NW/8]
+ *   SVC_NODE_SMOOTH            in0 = logits -> the pre-softmax map [height][width]
+ * Before the node runs, its output buffer and the scratch buffers of the pass are filled with a NaN bit pattern (all ones):
+ * whatever the node's kernels do not write -- the other half of a row included -- comes back as that.  Returns the floats
+ * per frame of the output.  SVC_E_INVALID, with nothing launched: an unknown node, n outside 1..SVC_CHUNK, in0 (or a
+ * decoder node's in1) or out_host NULL, height or width below 8 (as svc_saliency_u8), cap_floats below n frames of output.
+ * svc_debug_tap has no pass to read after this call.  Where the call changes the geometry the plan is rebuilt for n frames,
+ * so the next pass of more frames re-allocates the workspace. */
+#define SVC_NODE_FRONT 1
+#define SVC_NODE_BLOCK(idx) (idx)        /* idx = 2 .. 17 */
+#define SVC_NODE_F18 18
+#define SVC_NODE_SKIP_2X 19
+#define SVC_NODE_SKIP_4X 20
+#define SVC_NODE_POST_CNN 21
+#define SVC_NODE_US2 22
+#define SVC_NODE_POST_US2 23
+#define SVC_NODE_ADAPT 24
+#define SVC_NODE_SMOOTH 25
+#define SVC_NODE_FULL 100                /* + 7 / 14: the full-resolution output of that block */
+#define SVC_NODE_F4X (SVC_NODE_FULL + 7)
+#define SVC_NODE_F2X (SVC_NODE_FULL + 14)
+int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int width, const void *in0_host, const void *in1_host,
+                       float *out_host, size_t cap_floats);
 /* SVC_TAP_INPUT with the fused front kernel (the default): the input is written to memory only by handles created
  * with SVC_KEEP_INPUT=1 in the environment; otherwise the call fails with SVC_E_INVALID.
  * svc_front_fused: 1 when the last svc_saliency_u8 call ran LANCZOS + features.0 + features.1 as one kernel

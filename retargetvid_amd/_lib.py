@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SVC_LIB') or os.path.join(_HERE, 'libsvc_hip.so')      # SVC_LIB: another build of the same ABI (A/B runs)
 
-ABI_VERSION = 10         # include/svc.h SVC_ABI_VERSION this binding was written against
+ABI_VERSION = 11         # include/svc.h SVC_ABI_VERSION this binding was written against
 
 EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'svc_resize_frames_u8', 'svc_saliency_u8',
            'svc_threshold_u8', 'svc_cluster_center', 'svc_iou_i32', 'svc_debug_cluster_state', 'svc_debug_tap', 'svc_front_fused', 'svc_matrix_pipe', 'svc_threshold_census', 'svc_debug_round_plan', 'svc_transnet_load', 'svc_transnet_predict', 'svc_transnet_matrix_pipe',
@@ -19,7 +19,7 @@ EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'sv
            'svc_host_temporal', 'svc_host_boxes', 'svc_host_focus_stability', 'svc_saliency_thresholded_u8',
            'svc_saliency_census_u8', 'svc_transnet_predict_rows', 'svc_transnet_config_get', 'svc_transnet_config_set',
            'svc_render_crops_u8', 'svc_debug_transnet_tap', 'svc_border_profile_u8', 'svc_saliency_profile_u8',
-           'svc_resize_frames_nv12', 'svc_render_crops_nv12', 'svc_render_crops_u8_to_nv12', 'svc_render_crops_nv12_to_nv12')
+           'svc_resize_frames_nv12', 'svc_render_crops_nv12', 'svc_render_crops_u8_to_nv12', 'svc_render_crops_nv12_to_nv12', 'svc_debug_run_node')
 
 
 class SvcParams(ctypes.Structure):
@@ -88,6 +88,7 @@ def load():
     lib.svc_iou_i32.argtypes = [vp, vp, sz, vp, vp]
     lib.svc_debug_cluster_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     lib.svc_debug_tap.argtypes = [vp, i32, i32, vp, sz]
+    lib.svc_debug_run_node.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, sz]
     lib.svc_front_fused.argtypes = [vp]
     lib.svc_matrix_pipe.argtypes = [vp]
     lib.svc_transnet_matrix_pipe.argtypes = [vp]

@@ -2675,23 +2675,46 @@ static int backbone_block(SvcHandle *h, hipStream_t s, int idx, const float *x, 
     return SVC_OK;
 }
 
-// The head on the lowest level (H5 x W5): features.18 -> CAT1[:, 0:1280], the two skip branches (model.py:443-444) into their
-// halves of CAT2 / CAT3, the Gaussian maps -> CAT1[:, 1280:1296], post_cnn -> PC.
-static int net_head(SvcHandle *h, hipStream_t s, const float *x, int n, int H5, int W5) {
+// The head on the lowest level (H5 x W5), piece by piece (each is also a node of svc_debug_run_node): features.18 ->
+// CAT1[:, 0:1280]; the two skip branches (model.py:443-444) into their halves of CAT2 / CAT3; the Gaussian maps ->
+// CAT1[:, 1280:1296]; post_cnn -> PC.
+static int head_f18(SvcHandle *h, hipStream_t s, const float *x, int n, int H5, int W5) {
+    return launch_pw(h, s, x, 320, h->net.f18, nullptr, 0, h->plan->buf(B_CAT1), 1296, n * H5 * W5, n);
+}
+
+static int head_skip_2x(SvcHandle *h, hipStream_t s, int n, int H5, int W5) {
     NetPlan *p = h->plan;
-    const NetGraph &g = h->net;
-    float *CAT1 = p->buf(B_CAT1);
-    RC(launch_pw(h, s, x, 320, g.f18, nullptr, 0, CAT1, 1296, n * H5 * W5, n));
-    RC(launch_pwpw(h, s, p->buf(B_F2X), 160, g.skip2x_expand, g.skip2x_reduce, p->buf(B_CAT2) + 256, 384, n * 4 * H5 * W5));
-    RC(launch_pwpw(h, s, p->buf(B_F4X), 64, g.skip4x_expand, g.skip4x_reduce, p->buf(B_CAT3) + 128, 192, n * 16 * H5 * W5));
+    return launch_pwpw(h, s, p->buf(B_F2X), 160, h->net.skip2x_expand, h->net.skip2x_reduce, p->buf(B_CAT2) + 256, 384, n * 4 * H5 * W5);
+}
+
+static int head_skip_4x(SvcHandle *h, hipStream_t s, int n, int H5, int W5) {
+    NetPlan *p = h->plan;
+    return launch_pwpw(h, s, p->buf(B_F4X), 64, h->net.skip4x_expand, h->net.skip4x_reduce, p->buf(B_CAT3) + 128, 192, n * 16 * H5 * W5);
+}
+
+static int head_priors(SvcHandle *h, hipStream_t s, int n, int H5, int W5) {
+    NetPlan *p = h->plan;
     if (p->gauss_filled < n) {       // the prior maps are constants: nothing else writes channels 1280..1295 of CAT1
         ProfScope ps(h, SVC_K_RESAMPLE, s);
-        k_gauss_fill<<<blocks256((size_t)n * H5 * W5 * 16), 256, 0, s>>>((const float *)p->gauss.p, CAT1, n, H5 * W5,
+        k_gauss_fill<<<blocks256((size_t)n * H5 * W5 * 16), 256, 0, s>>>((const float *)p->gauss.p, p->buf(B_CAT1), n, H5 * W5,
                                                                          1296, 1280);
         SVC_CHECK_LAUNCH();
         p->gauss_filled = n;
     }
-    return dw_project(h, s, CAT1, g.post_cnn, nullptr, 0, p->buf(B_PCD), p->buf(B_PC), n, H5, W5);
+    return SVC_OK;
+}
+
+static int head_post_cnn(SvcHandle *h, hipStream_t s, int n, int H5, int W5) {
+    NetPlan *p = h->plan;
+    return dw_project(h, s, p->buf(B_CAT1), h->net.post_cnn, nullptr, 0, p->buf(B_PCD), p->buf(B_PC), n, H5, W5);
+}
+
+static int net_head(SvcHandle *h, hipStream_t s, const float *x, int n, int H5, int W5) {
+    RC(head_f18(h, s, x, n, H5, W5));
+    RC(head_skip_2x(h, s, n, H5, W5));
+    RC(head_skip_4x(h, s, n, H5, W5));
+    RC(head_priors(h, s, n, H5, W5));
+    return head_post_cnn(h, s, n, H5, W5);
 }
 
 // One decoder block (upsampling_2, post_upsampling_2): up-sample `lo` (Hl x Wl, Cl channels) x2, concatenate the skip half of
@@ -2707,28 +2730,34 @@ static int decoder_block(SvcHandle *h, hipStream_t s, const InvRes &B, const flo
     return launch_dwpw(h, s, E, B.dw, B.project, nullptr, 0, Y, B.oup, n, H, W);
 }
 
-// Adaptation, smoothing + resize to the saliency size, quantise (profile_rows: the banded variant, which also fills the
-// caller's border-profile rows for svc_saliency_profile_u8).
-static int net_tail(SvcHandle *h, hipStream_t s, int n, int H3, int W3, uint8_t *maps, int thr, unsigned *census_rows, unsigned *profile_rows) {
+// The tail, piece by piece (the first two are also nodes of svc_debug_run_node): adaptation DEC -> LOGIT (which also clears
+// the per-frame maxima and folds the census), smoothing + resize to the saliency size LOGIT -> PRE, quantise (profile_rows:
+// the banded variant, which also fills the caller's border-profile rows for svc_saliency_profile_u8).
+static int tail_adapt(SvcHandle *h, hipStream_t s, int n, int H3, int W3) {
+    NetPlan *p = h->plan;
+    ProfScope ps(h, SVC_K_RESAMPLE, s);
+    k_adapt<<<blocks256((size_t)n * H3 * W3), 256, 0, s>>>(p->buf(B_DEC), h->net.adapt.w.dev, h->net.adapt.b.dev, p->buf(B_LOGIT),
+                                                          (size_t)n * H3 * W3, (unsigned *)p->fmax.p, n,
+                                                          (unsigned long long *)h->census.p, h->chunk);
+    SVC_CHECK_LAUNCH();
+    return SVC_OK;
+}
+
+// B_LOGIT per-frame stride may exceed H3*W3 (rounded to 4): compact layout is used instead.  NH, NW = 8 H3, 8 W3 (the
+// network input sizes are multiples of 32)
+static int tail_smooth(SvcHandle *h, hipStream_t s, int n, int H3, int W3) {
     NetPlan *p = h->plan;
     const int NH = p->NH, NW = p->NW;
-    {
-        ProfScope ps(h, SVC_K_RESAMPLE, s);
-        k_adapt<<<blocks256((size_t)n * H3 * W3), 256, 0, s>>>(p->buf(B_DEC), h->net.adapt.w.dev, h->net.adapt.b.dev, p->buf(B_LOGIT),
-                                                              (size_t)n * H3 * W3, (unsigned *)p->fmax.p, n,
-                                                              (unsigned long long *)h->census.p, h->chunk);
-        SVC_CHECK_LAUNCH();
-    }
-    // B_LOGIT per-frame stride may exceed H3*W3 (rounded to 4): compact layout is used instead.  NH, NW = 8 H3, 8 W3 (the
-    // network input sizes are multiples of 32)
-    ProfScope ps_smooth(h, SVC_K_SMOOTH, s);
-    {
-        dim3 grid(ceil_div(p->h, SD_ROWS), n);
-        const size_t lds = ((size_t)H3 * W3 + 64 * SD_KP + (size_t)p->sd_tile_cap * NW) * sizeof(float);
-        k_smooth_down_mfma<<<grid, 256, lds, s>>>(p->buf(B_LOGIT), h->net.smooth.w.dev, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3,
-                                                  NH, NW, p->h, p->w, SD_ROWS, p->sd_tile_cap, make_fdiv(p->w));
-        SVC_CHECK_LAUNCH();
-    }
+    dim3 grid(ceil_div(p->h, SD_ROWS), n);
+    const size_t lds = ((size_t)H3 * W3 + 64 * SD_KP + (size_t)p->sd_tile_cap * NW) * sizeof(float);
+    k_smooth_down_mfma<<<grid, 256, lds, s>>>(p->buf(B_LOGIT), h->net.smooth.w.dev, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3,
+                                              NH, NW, p->h, p->w, SD_ROWS, p->sd_tile_cap, make_fdiv(p->w));
+    SVC_CHECK_LAUNCH();
+    return SVC_OK;
+}
+
+static int tail_quantise(SvcHandle *h, hipStream_t s, int n, uint8_t *maps, int thr, unsigned *census_rows, unsigned *profile_rows) {
+    NetPlan *p = h->plan;
     if (profile_rows) {
         k_quantise_profile<<<dim3(ceil_div(p->h, BP_ROWS), n), 256, 0, s>>>(p->buf(B_PRE), (const unsigned *)p->fmax.p, maps, p->h, p->w,
                                                                             thr, (unsigned long long *)h->census.p, census_rows,
@@ -2740,6 +2769,13 @@ static int net_tail(SvcHandle *h, hipStream_t s, int n, int H3, int W3, uint8_t 
     }
     SVC_CHECK_LAUNCH();
     return SVC_OK;
+}
+
+static int net_tail(SvcHandle *h, hipStream_t s, int n, int H3, int W3, uint8_t *maps, int thr, unsigned *census_rows, unsigned *profile_rows) {
+    RC(tail_adapt(h, s, n, H3, W3));
+    ProfScope ps_smooth(h, SVC_K_SMOOTH, s);
+    RC(tail_smooth(h, s, n, H3, W3));
+    return tail_quantise(h, s, n, maps, thr, census_rows, profile_rows);
 }
 
 // One pass of the network over n <= plan->nb frames.
@@ -2853,6 +2889,98 @@ extern "C" int svc_debug_tap(SvcHandle *h, int which, int frame, float *out_host
     SVC_HIP(hipDeviceSynchronize());
     SVC_HIP(hipMemcpy(out_host, p->buf(map[which]) + (size_t)frame * count, count * sizeof(float), hipMemcpyDeviceToHost));
     return (int)count;
+}
+
+// The test door of the network's nodes: one stage of forward_chunk on the caller's input (include/svc.h).  Host code only:
+// the stage functions above are what forward_chunk calls.
+extern "C" int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int width, const void *in0_host, const void *in1_host,
+                                  float *out_host, size_t cap_floats) {
+    if (!h || !in0_host || !out_host || height < 8 || width < 8) { svc_set_error("svc_debug_run_node: invalid argument"); return SVC_E_INVALID; }
+    if (n < 1 || n > h->chunk) { svc_set_error("svc_debug_run_node: %d frames (1..%d)", n, h->chunk); return SVC_E_INVALID; }
+    int NH, NW;
+    optimal_out_size(height, width, NH, NW);
+    const size_t H5 = NH / 32, W5 = NW / 32, px5 = H5 * W5;
+    const bool full = node == SVC_NODE_F4X || node == SVC_NODE_F2X;
+    const int idx = full ? node - SVC_NODE_FULL : node;          // the backbone block of a block node
+    // what the node reads (in0 -> buffer ib, in1 -> the skip half of a concatenation row) and writes (buffer ob), per frame
+    int ib = -1, ob = -1, cat = -1, bH = NH / 2, bW = NW / 2;
+    size_t ipx = 0, ich = 0, opx = 0, och = 0, i1px = 0, i1ch = 0;
+    if (full || (node >= 2 && node <= 17)) {
+        for (int i = 2; i < idx; ++i)
+            if (h->net.block[i - 1].stride == 2) { bH /= 2; bW /= 2; }
+        const InvRes &B = h->net.block[idx - 1];
+        const int d = (B.stride == 2 && !full) ? 2 : 1;
+        ib = (idx & 1) ? B_P0 : B_P1;                            // forward_chunk: net_front writes P1, block 2 reads it, ...
+        ob = full ? (idx == 7 ? B_F4X : B_F2X) : ((idx & 1) ? B_P1 : B_P0);
+        ipx = (size_t)bH * bW; ich = B.inp; opx = (size_t)(bH / d) * (bW / d); och = B.oup;
+    } else switch (node) {
+        case SVC_NODE_FRONT: ob = B_P1; opx = (size_t)bH * bW; och = 16; break;
+        case SVC_NODE_F18: ib = B_P1; ipx = px5; ich = 320; ob = B_CAT1; opx = px5; och = 1296; break;
+        case SVC_NODE_SKIP_2X: ib = B_F2X; ipx = 4 * px5; ich = 160; ob = B_CAT2; opx = 4 * px5; och = 384; break;
+        case SVC_NODE_SKIP_4X: ib = B_F4X; ipx = 16 * px5; ich = 64; ob = B_CAT3; opx = 16 * px5; och = 192; break;
+        case SVC_NODE_POST_CNN: ib = B_CAT1; ipx = px5; ich = 1296; ob = B_PC; opx = px5; och = 256; break;
+        case SVC_NODE_US2: ib = B_PC; ipx = px5; ich = 256; cat = B_CAT2; i1px = 4 * px5; i1ch = 128; ob = B_U2; opx = 4 * px5; och = 128; break;
+        case SVC_NODE_POST_US2: ib = B_U2; ipx = 4 * px5; ich = 128; cat = B_CAT3; i1px = 16 * px5; i1ch = 64; ob = B_DEC; opx = 16 * px5; och = 64; break;
+        case SVC_NODE_ADAPT: ib = B_DEC; ipx = 16 * px5; ich = 64; ob = B_LOGIT; opx = 16 * px5; och = 1; break;
+        case SVC_NODE_SMOOTH: ib = B_LOGIT; ipx = 16 * px5; ich = 1; ob = B_PRE; opx = (size_t)height * width; och = 1; break;
+        default: svc_set_error("svc_debug_run_node: unknown node %d", node); return SVC_E_INVALID;
+    }
+    if (cat >= 0 && !in1_host) { svc_set_error("svc_debug_run_node: node %d needs its skip input", node); return SVC_E_INVALID; }
+    const size_t count = opx * och;
+    if (count * n > cap_floats) { svc_set_error("svc_debug_run_node: buffer too small (%zu needed)", count * n); return SVC_E_INVALID; }
+    SVC_HIP(hipSetDevice(h->device));
+    RC(build_plan(h, height, width, n));
+    NetPlan *p = h->plan;
+    hipStream_t s = nullptr;
+    // a NaN bit pattern (all ones) in everything the node may write: what its kernels skip comes back as NaN
+    auto fill = [&](int b) { return hipMemsetAsync(p->buf(b), 0xFF, p->per_frame(b) * (size_t)n * sizeof(float), s); };
+    for (int b : {ob, (int)B_E0, (int)B_E1, (int)B_T1, (int)B_T2, (int)B_PCD, (int)B_U2E, (int)B_P3E}) SVC_HIP(fill(b));
+    if (cat >= 0) SVC_HIP(fill(cat));
+    if (idx == 7 || idx == 14) SVC_HIP(fill(idx == 7 ? B_F4X : B_F2X));
+    p->gauss_filled = 0;                    // the prior channels of CAT1 may hold the fill or the caller's values now
+    p->last_n = 0;                          // the workspace is no pass's any more (svc_debug_tap)
+    struct Owned : DevBuf { ~Owned() { release(); } } frames;      // the front's uint8 input: freed on every way out
+    int rc = SVC_OK;
+    if (node == SVC_NODE_FRONT) {
+        SVC_HIP(fill(B_P0));
+        const size_t bytes = (size_t)n * height * width * 3;
+        RC(frames.ensure(bytes));
+        if (hipMemcpy(frames.p, in0_host, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = SVC_E_HIP;
+        if (!rc) rc = net_front(h, s, (const uint8_t *)frames.p, n, p->buf(B_P0), p->buf(B_P1));
+    } else {
+        SVC_HIP(hipMemcpy(p->buf(ib), in0_host, (size_t)n * ipx * ich * sizeof(float), hipMemcpyHostToDevice));
+        if (cat >= 0) {                     // the skip half of the row, behind the channels the low-resolution tensor would take
+            const size_t row = BUF_SHAPE[cat].ch * sizeof(float);
+            SVC_HIP(hipMemcpy2D(p->buf(cat) + (BUF_SHAPE[cat].ch - i1ch), row, in1_host, i1ch * sizeof(float), i1ch * sizeof(float),
+                                (size_t)n * i1px, hipMemcpyHostToDevice));
+        }
+        const int h5 = (int)H5, w5 = (int)W5;
+        if (full || node <= 17) rc = backbone_block(h, s, idx, p->buf(ib), p->buf((idx & 1) ? B_P1 : B_P0), n, bH, bW);
+        else switch (node) {
+            case SVC_NODE_F18: rc = head_f18(h, s, p->buf(B_P1), n, h5, w5); break;
+            case SVC_NODE_SKIP_2X: rc = head_skip_2x(h, s, n, h5, w5); break;
+            case SVC_NODE_SKIP_4X: rc = head_skip_4x(h, s, n, h5, w5); break;
+            case SVC_NODE_POST_CNN: rc = head_post_cnn(h, s, n, h5, w5); break;
+            case SVC_NODE_US2:
+                rc = decoder_block(h, s, h->net.us2, p->buf(B_PC), 256, h5, w5, p->buf(B_CAT2), p->buf(B_T1), p->buf(B_U2E), p->buf(B_U2), n);
+                break;
+            case SVC_NODE_POST_US2:
+                rc = decoder_block(h, s, h->net.post_us2, p->buf(B_U2), 128, 2 * h5, 2 * w5, p->buf(B_CAT3), p->buf(B_T2), p->buf(B_P3E),
+                                   p->buf(B_DEC), n);
+                break;
+            case SVC_NODE_ADAPT: rc = tail_adapt(h, s, n, 4 * h5, 4 * w5); break;
+            default:                        // SVC_NODE_SMOOTH: the per-frame maxima k_adapt clears in a pass
+                SVC_HIP(hipMemsetAsync(p->fmax.p, 0, (size_t)n * sizeof(unsigned), s));
+                rc = tail_smooth(h, s, n, 4 * h5, 4 * w5);
+                break;
+        }
+    }
+    if (!rc && hipDeviceSynchronize() != hipSuccess) { svc_set_error("svc_debug_run_node: node %d failed on the device", node); rc = SVC_E_HIP; }
+    if (!rc && hipMemcpy(out_host, p->buf(ob), count * n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+        svc_set_error("svc_debug_run_node: copying the output failed");
+        rc = SVC_E_HIP;
+    }
+    return rc ? rc : (int)count;
 }
 
 extern "C" int svc_front_fused(const SvcHandle *h) { return h && h->plan && h->plan->last_front ? 1 : 0; }

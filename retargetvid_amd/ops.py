@@ -12,6 +12,9 @@ from . import _lib, weights as _weights
 from ._lib import SvcParams
 
 TAP_INPUT, TAP_FEAT4X, TAP_FEAT2X, TAP_FEAT1X, TAP_POSTCNN, TAP_DEC, TAP_PRE = range(7)
+# nodes of svc_debug_run_node (include/svc.h: SVC_NODE_*); backbone block idx = 2 .. 17 is node idx
+NODE_FRONT, NODE_F18, NODE_SKIP_2X, NODE_SKIP_4X, NODE_POST_CNN, NODE_US2, NODE_POST_US2, NODE_ADAPT, NODE_SMOOTH = 1, 18, 19, 20, 21, 22, 23, 24, 25
+NODE_F4X, NODE_F2X = 107, 114
 
 
 def _stream():
@@ -87,7 +90,21 @@ class Engine:
         self.device = torch.device('cuda', torch.cuda.current_device() if device is None else device)
         if state_dict is None:
             state_dict = _weights.make_synthetic_state_dict(seed)
-        blob = _weights.pack_blob(_weights.fold_state_dict(state_dict))
+        self._create(_weights.pack_blob(_weights.fold_state_dict(state_dict)))
+
+    @classmethod
+    def from_layers(cls, layers, device=None):
+        """A handle from a folded layer list (weights.fold_state_dict's; serialised by weights.pack_blob): the caller chooses the
+        numbers the device computes with, without a checkpoint whose BatchNorm folding would have to produce them."""
+        if not torch.cuda.is_available():
+            raise _lib.SvcError('no GPU visible: the SmartVidCrop hot path runs on the MI355X only')
+        self = cls.__new__(cls)
+        self.lib = _lib.load()
+        self.device = torch.device('cuda', torch.cuda.current_device() if device is None else device)
+        self._create(_weights.pack_blob(layers))
+        return self
+
+    def _create(self, blob):
         import zlib
         self.weights_id = zlib.crc32(blob) & 0xffffffff        # identifies the checkpoint (smartVidCrop's feature cache keys on it)
         self._h = ctypes.c_void_p()
@@ -209,6 +226,20 @@ class Engine:
         out = np.empty(int(np.prod(shape)), np.float32)
         _lib.check(self.lib.svc_debug_tap(self._h, which, frame, out.ctypes.data_as(ctypes.c_void_p), out.size))
         return out.reshape(shape)
+
+    def run_node(self, node, n, height, width, in0, in1=None, out_shape=None):
+        """Test door (svc_debug_run_node): one node of the network on the caller's host arrays -- fp32 NHWC of n frames (uint8
+        frames for NODE_FRONT) -- for saliency maps of height x width.  -> fp32 [n, *out_shape] (out_shape: the per-frame shape
+        of the node's output buffer; include/svc.h lists them).  What the node did not write comes back as NaN."""
+        vp = ctypes.c_void_p
+        in0 = np.ascontiguousarray(in0, np.uint8 if node == NODE_FRONT else np.float32)
+        in1 = None if in1 is None else np.ascontiguousarray(in1, np.float32)
+        out = np.empty((n,) + tuple(int(v) for v in out_shape), np.float32)
+        per = _lib.check(self.lib.svc_debug_run_node(self._h, int(node), int(n), int(height), int(width), in0.ctypes.data_as(vp),
+                                                     None if in1 is None else in1.ctypes.data_as(vp), out.ctypes.data_as(vp), out.size))
+        if per * n != out.size:
+            raise ValueError('node %d writes %d floats per frame, not %s' % (node, per, out.shape[1:]))
+        return out
 
     # -- tail ----------------------------------------------------------------------------
     def threshold_(self, maps, t):
