@@ -81,8 +81,9 @@ const char *svc_last_error(void);
  * 8 = svc_border_profile_u8, svc_saliency_profile_u8 and the profile class SVC_K_BORDER exist.
  * 9 = svc_resize_frames_nv12 and svc_render_crops_nv12 exist (NV12 input).
  * 10 = svc_render_crops_u8_to_nv12 and svc_render_crops_nv12_to_nv12 exist (NV12 output).
- * 11 = svc_debug_run_node (SVC_NODE_*) exists. */
-#define SVC_ABI_VERSION 11
+ * 11 = svc_debug_run_node (SVC_NODE_*) exists.
+ * 12 = SvcFrameLayout, svc_resize_frames_layout and svc_render_crops_layout exist (pitched frames). */
+#define SVC_ABI_VERSION 12
 int svc_abi_version(void);
 
 /* weights_blob_host: the packed, BN-folded static SALICON slice of a UNISAL
@@ -141,6 +142,45 @@ int svc_render_crops_u8_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int 
                                 int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
 int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                   int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
+
+/* Frames in a decoder's layout: the six entries above on frames that are not packed -- a row pitch above the row's bytes, an
+ * NV12 chroma plane that starts behind a coded height, frames further apart than their bytes (a hardware decoder's 1920 x 1080
+ * surface: pitch 2048, chroma_offset 2048 * 1088; libavcodec's linesize).  `height` and `width` stay the PICTURE's.  Pixel
+ * (y, x) of frame f lies at
+ *   RGB   frames + f * frame_stride + y * pitch + 3 x
+ *   NV12  Y at frames + f * frame_stride + y * pitch + x,  its U V pair at ... + chroma_offset + (y >> 1) * chroma_pitch + (x & ~1)
+ * and everything behind the fetched pixel -- conversion, INTER_LINEAR, window rules, the (packed) outputs, the LDS limits -- is
+ * that of the packed entries: the result is bit for bit theirs on a packed copy of the same pictures.  out_fmt: SVC_FMT_RGB24
+ * (flags: SVC_RENDER_BGR) or SVC_FMT_NV12 (flags 0), the outputs of svc_render_crops_u8 and of the _to_nv12 entries.  The six
+ * entries above are these launchers with the packed layout (pitch 3 w | w, chroma_offset w * h, chroma_pitch w, frame_stride
+ * 3 w h | w h 3 / 2).
+ * Rules, checked before any device work (SVC_E_INVALID, the rule in svc_last_error()): struct_size is this header's; pix_fmt is
+ * one of SVC_FMT_*; every value is non-negative; pitch >= the row's bytes (3 w | w); RGB: chroma_offset = chroma_pitch = 0;
+ * NV12: chroma_pitch >= w and chroma_offset >= pitch * (h - 1) + w (the chroma plane begins behind the last luma row);
+ * frame_stride >= extent, the bytes from a frame's start to the end of its last plane row: pitch * (h - 1) + 3 w for RGB,
+ * chroma_offset + chroma_pitch * (h / 2 - 1) + w for NV12; (n - 1) * frame_stride + extent <= PTRDIFF_MAX (the range below is
+ * addressed in 64 bits).  No alignment is demanded: an odd pitch is legal.
+ * What is read: the kernels load only bytes of [frames, frames + (n - 1) * frame_stride + extent) -- nothing below `frames`,
+ * nothing behind the last frame's last plane row, so that range is all that has to be mapped.  Padding bytes inside the range
+ * may be loaded (the 16-byte loads are aligned down and guarded by the range's end) and never reach a result.
+ * The layout only decides which path runs: the 16-byte paths need `frames` (and, for the copy, `out`) 16-aligned, as for the
+ * packed entries, and for NV12 an even frame_stride, chroma_offset and chroma_pitch (a U V pair on an odd address is read
+ * by the byte paths).  They count under SVC_K_RESIZE / SVC_K_RENDER.  No counterpart in the reference. */
+#define SVC_FMT_RGB24 0
+#define SVC_FMT_NV12  1
+typedef struct SvcFrameLayout {
+    uint32_t struct_size;     /* sizeof(SvcFrameLayout), as SvcParams: a stale binding is refused */
+    int32_t  pix_fmt;         /* SVC_FMT_* */
+    int64_t  frame_stride;    /* bytes from frame f to frame f + 1 */
+    int64_t  pitch;           /* bytes from row y to row y + 1 (RGB rows; NV12 luma rows) */
+    int64_t  chroma_offset;   /* NV12: bytes from the frame's start to its first U V row; RGB: 0 */
+    int64_t  chroma_pitch;    /* NV12: bytes between U V rows; RGB: 0 */
+} SvcFrameLayout;
+int svc_resize_frames_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height, int width,
+                             uint8_t *out, int sh, int sw, void *stream);
+int svc_render_crops_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height, int width,
+                            const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
+                            int flags, void *stream);
 
 /* frames_nhwc[n][h][w][3] u8 RGB (saliency size, e.g. 140x250) -> maps_nhw[n][h][w] u8.
  * Frame-major output; the reference's [h][w][n] view is a transpose done by the
@@ -264,7 +304,7 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
  * the same stream, measured at read time, is taken off every launch: calibrated against rocprofv3 kernel durations) and the number of launches recorded since the last
  * read, and resets the log.  Nothing like it exists in the
  * reference (its timers are host wall-clock accumulators, smartVidCrop.py:98-127). */
-#define SVC_K_RESIZE 0     /* svc_resize_frames_u8 / _nv12 */
+#define SVC_K_RESIZE 0     /* svc_resize_frames_u8 / _nv12 / _layout */
 #define SVC_K_LANCZOS 1
 #define SVC_K_STEM 2
 #define SVC_K_PW 3
@@ -276,7 +316,7 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
 #define SVC_K_CORE 9
 #define SVC_K_PRIM 10
 #define SVC_K_FINISH 11
-#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 / _u8_to_nv12 / _nv12_to_nv12 */
+#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 / _u8_to_nv12 / _nv12_to_nv12 / _layout */
 #define SVC_K_BORDER 13    /* svc_border_profile_u8 (the fused form, svc_saliency_profile_u8, counts under SVC_K_SMOOTH) */
 #define SVC_K_COUNT 14
 int svc_profile_enable(SvcHandle *h, int kernel_class);

@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SVC_LIB') or os.path.join(_HERE, 'libsvc_hip.so')      # SVC_LIB: another build of the same ABI (A/B runs)
 
-ABI_VERSION = 11         # include/svc.h SVC_ABI_VERSION this binding was written against
+ABI_VERSION = 12         # include/svc.h SVC_ABI_VERSION this binding was written against
 
 EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'svc_resize_frames_u8', 'svc_saliency_u8',
            'svc_threshold_u8', 'svc_cluster_center', 'svc_iou_i32', 'svc_debug_cluster_state', 'svc_debug_tap', 'svc_front_fused', 'svc_matrix_pipe', 'svc_threshold_census', 'svc_debug_round_plan', 'svc_transnet_load', 'svc_transnet_predict', 'svc_transnet_matrix_pipe',
@@ -19,7 +19,8 @@ EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'sv
            'svc_host_temporal', 'svc_host_boxes', 'svc_host_focus_stability', 'svc_saliency_thresholded_u8',
            'svc_saliency_census_u8', 'svc_transnet_predict_rows', 'svc_transnet_config_get', 'svc_transnet_config_set',
            'svc_render_crops_u8', 'svc_debug_transnet_tap', 'svc_border_profile_u8', 'svc_saliency_profile_u8',
-           'svc_resize_frames_nv12', 'svc_render_crops_nv12', 'svc_render_crops_u8_to_nv12', 'svc_render_crops_nv12_to_nv12', 'svc_debug_run_node')
+           'svc_resize_frames_nv12', 'svc_render_crops_nv12', 'svc_render_crops_u8_to_nv12', 'svc_render_crops_nv12_to_nv12', 'svc_debug_run_node',
+           'svc_resize_frames_layout', 'svc_render_crops_layout')
 
 
 class SvcParams(ctypes.Structure):
@@ -32,6 +33,14 @@ class SvcTemporalParams(ctypes.Structure):
     _fields_ = [('struct_size', ctypes.c_uint32), ('lp_filt', ctypes.c_int32), ('lp_taps', ctypes.c_int32),
                 ('loess_filt', ctypes.c_int32), ('loess_degree', ctypes.c_int32), ('reserved', ctypes.c_int32),
                 ('loess_w_secs', ctypes.c_double), ('fr', ctypes.c_double)]
+
+
+FMT_RGB24, FMT_NV12 = 0, 1          # include/svc.h: SVC_FMT_*
+
+
+class SvcFrameLayout(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_uint32), ('pix_fmt', ctypes.c_int32), ('frame_stride', ctypes.c_int64),
+                ('pitch', ctypes.c_int64), ('chroma_offset', ctypes.c_int64), ('chroma_pitch', ctypes.c_int64)]
 
 
 def make_params(CP):
@@ -81,6 +90,8 @@ def load():
     lib.svc_render_crops_nv12.argtypes = lib.svc_render_crops_u8.argtypes
     lib.svc_render_crops_u8_to_nv12.argtypes = lib.svc_render_crops_u8.argtypes
     lib.svc_render_crops_nv12_to_nv12.argtypes = lib.svc_render_crops_u8.argtypes
+    lib.svc_resize_frames_layout.argtypes = [vp, vp, ctypes.POINTER(SvcFrameLayout), i32, i32, i32, vp, i32, i32, vp]
+    lib.svc_render_crops_layout.argtypes = [vp, vp, ctypes.POINTER(SvcFrameLayout), i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     lib.svc_saliency_u8.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.svc_saliency_thresholded_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp]
     lib.svc_threshold_u8.argtypes = [vp, vp, sz, i32, vp]

@@ -1,6 +1,6 @@
-// svc_frames.hip — frame I/O for gfx950: the ingest down-scale and the renderer, from packed RGB and NV12 frames, the
-// renderer to packed RGB / BGR and to NV12.  Every kernel is written once: it takes its pixels from a source (SrcRgb, SrcNv12)
-// and the render kernels hand theirs to a sink (DstRgb<BGR>, DstNv12); the INTER_LINEAR rule is svc_cvlinear.h's.  The one
+// svc_frames.hip — frame I/O for gfx950: the ingest down-scale and the renderer, from RGB and NV12 frames (packed, or in a
+// decoder's layout: Packed / Pitched below), the renderer to packed RGB / BGR and to NV12.  Every kernel is written once: it
+// takes its pixels from a source (SrcRgb<Lay>, SrcNv12<Lay>) and the render kernels hand theirs to a sink (DstRgb<BGR>, DstNv12); the INTER_LINEAR rule is svc_cvlinear.h's.  The one
 // pair that is two bodies is the copy path's vector kernel, whose decomposition of the output is the sink's own.
 //
 // Reference semantics restated per kernel (paths relative to the reference tree):
@@ -72,37 +72,75 @@ __device__ __forceinline__ void ld24(const uint8_t *a, const uint8_t *end, uint6
 }
 
 // --------------------------------------------------------------------------------------
-// Pixel sources: what the kernels below ask of a frame format.
+// Frame layouts: where the bytes of a source frame lie (SvcFrameLayout, include/svc.h).  A layout is a compile-time policy of
+// the pixel source and travels as the kernels' last argument.  Packed is an empty struct whose offsets are the expressions
+// in w that these kernels have always used, so the packed instances are the kernels they were; Pitched carries the four
+// strides.  T: the integer type the caller's expression is formed in (size_t for byte loads, ptrdiff_t where x may be < 0).
+//   frame<Src>   bytes from frame f to frame f + 1
+//   rgb          offset of byte 0 of pixel (y, x) of an RGB frame
+//   luma, chroma offsets of Y[y][x] and of the U V pair of pixel (y, x) of an NV12 frame
+// --------------------------------------------------------------------------------------
+struct Packed {
+    template <class Src> __host__ __device__ __forceinline__ size_t frame(int h, int w) const { return Src::frame_bytes(h, w); }
+    template <class T> __device__ __forceinline__ T rgb(int w, int y, int x) const { return ((T)y * w + x) * 3; }
+    template <class T> __device__ __forceinline__ T luma(int w, int y, int x) const { return (T)y * w + x; }
+    template <class T> __device__ __forceinline__ T chroma(int h, int w, int y, int x) const { return (T)(h + (y >> 1)) * w + (x & ~1); }
+};
+struct Pitched {
+    long long frame_stride, pitch, chroma_offset, chroma_pitch;
+    template <class Src> __host__ __device__ __forceinline__ size_t frame(int, int) const { return (size_t)frame_stride; }
+    template <class T> __device__ __forceinline__ T rgb(int, int y, int x) const { return (T)y * (T)pitch + x * 3; }
+    template <class T> __device__ __forceinline__ T luma(int, int y, int x) const { return (T)y * (T)pitch + x; }
+    template <class T> __device__ __forceinline__ T chroma(int, int, int y, int x) const {
+        return (T)chroma_offset + (T)(y >> 1) * (T)chroma_pitch + (x & ~1);
+    }
+};
+
+// --------------------------------------------------------------------------------------
+// Pixel sources: what the kernels below ask of a frame format, in the layout Lay (`L`: the kernel's layout argument).
 //   size_ok, size_rule   the pictures the format can hold, and the words the error text says it with
-//   frame_bytes          bytes of one frame
+//   frame_bytes          bytes of one packed frame
+//   extent               bytes from a frame's start to the end of its last plane row: the kernels read inside
+//                        [frames, frames + (n - 1) * L.frame + extent) and nowhere else
+//   vec_ok               whether the 16-byte paths (px16, stage_row's vec) may run on this layout
 //   px<BGR>              pixel (y, x) of the frame at `fr` as r | g << 8 | b << 16 (BGR: b | g << 8 | r << 16), byte loads
 //   px16<BGR>            pixels x .. x + 15 of row y as 48 bytes (o[12], little-endian dwords) through aligned 16-byte loads
 //                        (the buffer is 16-aligned and ends at `end`).  x may be below 0 by less than 16 (the copy kernel's
-//                        second run): then the pixels left of the row are whatever lies there -- inside the buffer, since
-//                        row y is not its first -- and the caller masks them out.
+//                        second run): then the pixels left of the row are whatever lies there and the caller masks them
+//                        out.  They lie inside the buffer, also with padding and for row 0: that run is never the first
+//                        window row of frame 0, so its row starts at least one pitch (a row further down the same frame) or
+//                        one frame stride (row 0 of the next frame) behind `frames`, and it reaches back by k < 16 pixels
+//                        with k <= bw <= w, i.e. by at most 3 w <= pitch <= extent <= frame stride bytes (NV12: k <= w <=
+//                        pitch for luma; at most 16 <= w <= chroma_offset bytes for chroma, bw >= 16 on that path).  The
+//                        16-byte words are aligned down from there and `frames` is 16-aligned, so no load starts below it.
 //   order16<BGR>         what is left to do to such 48 bytes once two runs are merged: px16 then order16 is the output's
 //                        channel order
 //   stage_row            pixels x .. x + bw - 1 of row y as RGB bytes into the LDS row `row` (span_cap bytes) by the whole
 //                        workgroup (vec: frames 16-aligned, 16-byte loads; else bytewise); returns the byte of `row` at which
 //                        they start
 // --------------------------------------------------------------------------------------
-struct SrcRgb {                                 // u8 [h][w][3]
+template <class Lay>
+struct SrcRgb {                                 // u8 [h][w][3]; Pitched: rows `pitch` bytes apart
+    typedef Lay lay;
     static bool size_ok(int h, int w) { return h >= 1 && w >= 1; }
     static const char *size_rule() { return ""; }
     __host__ __device__ static size_t frame_bytes(int h, int w) { return (size_t)h * w * 3; }
+    static size_t extent(const Packed &, int h, int w) { return frame_bytes(h, w); }
+    static size_t extent(const Pitched &L, int h, int w) { return (size_t)L.pitch * (h - 1) + (size_t)w * 3; }
+    static bool vec_ok(const Lay &) { return true; }        // ld48 takes any address
 
     template <bool BGR>
-    __device__ __forceinline__ static uint32_t px(const uint8_t *__restrict__ fr, int h, int w, int y, int x) {
-        const uint8_t *s = fr + ((size_t)y * w + x) * 3;
+    __device__ __forceinline__ static uint32_t px(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x) {
+        const uint8_t *s = fr + L.template rgb<size_t>(w, y, x);
         const uint32_t c0 = s[0], c1 = s[1], c2 = s[2];
         return BGR ? c2 | (c1 << 8) | (c0 << 16) : c0 | (c1 << 8) | (c2 << 16);
     }
 
     // one 48-byte run of the row, as it lies there
     template <bool BGR>
-    __device__ __forceinline__ static void px16(const uint8_t *__restrict__ fr, int h, int w, int y, int x, const uint8_t *end,
+    __device__ __forceinline__ static void px16(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x, const uint8_t *end,
                                                 uint32_t (&o)[12]) {
-        ld48(fr + ((ptrdiff_t)y * w + x) * 3, end, o);
+        ld48(fr + L.template rgb<ptrdiff_t>(w, y, x), end, o);
     }
 
     // BGR: a fixed byte permutation inside the group (it starts on a pixel boundary)
@@ -125,9 +163,9 @@ struct SrcRgb {                                 // u8 [h][w][3]
     }
 
     // vec: the aligned 16-byte words that hold the span, so the row starts at the span's own 16-byte phase
-    __device__ __forceinline__ static int stage_row(const uint8_t *__restrict__ fr, int h, int w, int y, int x, int bw,
+    __device__ __forceinline__ static int stage_row(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x, int bw,
                                                     uint8_t *row, int span_cap, const uint8_t *end, int vec) {
-        const uint8_t *a = fr + ((size_t)y * w + x) * 3;
+        const uint8_t *a = fr + L.template rgb<size_t>(w, y, x);
         const int span = bw * 3;
         if (vec) {
             const uint8_t *p = (const uint8_t *)((uintptr_t)a & ~(uintptr_t)15);
@@ -170,25 +208,33 @@ __device__ __forceinline__ uint32_t nv12_rgb(int Y, int U, int V) {
     return BGR ? (uint32_t)(b | (g << 8) | (r << 16)) : (uint32_t)(r | (g << 8) | (b << 16));
 }
 
-struct SrcNv12 {                                // u8 [h * 3 / 2][w]
+template <class Lay>
+struct SrcNv12 {                                // u8 [h * 3 / 2][w]; Pitched: luma rows `pitch` apart, U V rows `chroma_pitch` apart from `chroma_offset`
+    typedef Lay lay;
     static bool size_ok(int h, int w) { return h >= 2 && w >= 2 && !(h & 1) && !(w & 1); }       // even, >= 2
     static const char *size_rule() { return " (height and width of an NV12 picture are even)"; }
     __host__ __device__ static size_t frame_bytes(int h, int w) { return (size_t)(h + h / 2) * w; }
+    static size_t extent(const Packed &, int h, int w) { return frame_bytes(h, w); }
+    static size_t extent(const Pitched &L, int h, int w) { return (size_t)L.chroma_offset + (size_t)L.chroma_pitch * (h / 2 - 1) + (size_t)w; }
+    // px16 takes its 18 chroma bytes from an EVEN address (ld24 delivers 17 from an odd one).  `frames` is 16-aligned on that
+    // path, so every U V pair lies on an even address iff these three are even; a layout with an odd one takes the byte paths.
+    static bool vec_ok(const Packed &) { return true; }
+    static bool vec_ok(const Pitched &L) { return !((L.frame_stride | L.chroma_offset | L.chroma_pitch) & 1); }
 
     template <bool BGR>
-    __device__ __forceinline__ static uint32_t px(const uint8_t *__restrict__ fr, int h, int w, int y, int x) {
-        const uint8_t *c = fr + ((size_t)(h + (y >> 1)) * w + (x & ~1));
-        return nv12_rgb<BGR>(fr[(size_t)y * w + x], c[0], c[1]);
+    __device__ __forceinline__ static uint32_t px(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x) {
+        const uint8_t *c = fr + L.template chroma<size_t>(h, w, y, x);
+        return nv12_rgb<BGR>(fr[L.template luma<size_t>(w, y, x)], c[0], c[1]);
     }
 
     // the 16 luma bytes and the 18 bytes that hold their (at most nine) chroma pairs, each through two aligned 16-byte
     // loads; the chroma index is taken from frame coordinates, so x and y may be odd
     template <bool BGR>
-    __device__ __forceinline__ static void px16(const uint8_t *__restrict__ fr, int h, int w, int y, int x, const uint8_t *end,
+    __device__ __forceinline__ static void px16(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x, const uint8_t *end,
                                                 uint32_t (&o)[12]) {
-        uint64_t L[3], C[3];
-        ld24(fr + ((ptrdiff_t)y * w + x), end, L[0], L[1], L[2]);
-        ld24(fr + ((ptrdiff_t)(h + (y >> 1)) * w + (x & ~1)), end, C[0], C[1], C[2]);     // (x & ~1 = 2 * (x >> 1), also for x < 0)
+        uint64_t Y[3], C[3];
+        ld24(fr + L.template luma<ptrdiff_t>(w, y, x), end, Y[0], Y[1], Y[2]);
+        ld24(fr + L.template chroma<ptrdiff_t>(h, w, y, x), end, C[0], C[1], C[2]);      // (x & ~1 = 2 * (x >> 1), also for x < 0)
         const bool odd = x & 1;
         uint32_t p[16];
 #pragma unroll
@@ -197,7 +243,7 @@ struct SrcNv12 {                                // u8 [h * 3 / 2][w]
             const int p0 = i >> 1, p1 = (i + 1) >> 1;
             const uint32_t h0 = (uint32_t)(C[p0 >> 2] >> (16 * (p0 & 3))) & 0xffffu, h1 = (uint32_t)(C[p1 >> 2] >> (16 * (p1 & 3))) & 0xffffu;
             const uint32_t uv = (i & 1) && odd ? h1 : h0;
-            p[i] = nv12_rgb<BGR>((int)((L[i >> 3] >> (8 * (i & 7))) & 0xffu), (int)(uv & 0xffu), (int)(uv >> 8));
+            p[i] = nv12_rgb<BGR>((int)((Y[i >> 3] >> (8 * (i & 7))) & 0xffu), (int)(uv & 0xffu), (int)(uv >> 8));
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {                     // four pixels = three dwords
@@ -211,19 +257,19 @@ struct SrcNv12 {                                // u8 [h * 3 / 2][w]
     __device__ __forceinline__ static void order16(uint32_t (&)[12]) {}      // converted straight to the order asked for
 
     // the row is converted while it is staged; vec: 16 pixels per thread through px16
-    __device__ __forceinline__ static int stage_row(const uint8_t *__restrict__ fr, int h, int w, int y, int x, int bw,
+    __device__ __forceinline__ static int stage_row(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x, int bw,
                                                     uint8_t *row, int span_cap, const uint8_t *end, int vec) {
         if (vec) {
             for (int g = threadIdx.x; 16 * g < bw; g += 256) {
                 uint32_t o[12];
-                px16<false>(fr, h, w, y, x + 16 * g, end, o);
+                px16<false>(fr, L, h, w, y, x + 16 * g, end, o);
 #pragma unroll
                 for (int j = 0; j < 3; ++j)                     // (the last group's words past the row's capacity are never read)
                     if (48 * g + 16 * j + 16 <= span_cap) ((uint4 *)(row + 48 * g))[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
             }
         } else {
             for (int i = threadIdx.x; i < bw; i += 256) {
-                const uint32_t v = px<false>(fr, h, w, y, x + i);
+                const uint32_t v = px<false>(fr, L, h, w, y, x + i);
                 row[3 * i] = (uint8_t)v;
                 row[3 * i + 1] = (uint8_t)(v >> 8);
                 row[3 * i + 2] = (uint8_t)(v >> 16);
@@ -239,7 +285,8 @@ struct SrcNv12 {                                // u8 [h * 3 / 2][w]
 // --------------------------------------------------------------------------------------
 template <class Src>
 __global__ __launch_bounds__(256) void k_cv_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
-                                                   const int *__restrict__ tab, int n, int h, int w, int oh, int ow) {
+                                                   const int *__restrict__ tab, int n, int h, int w, int oh, int ow,
+                                                   const typename Src::lay L) {
     const CvLinear T(tab, oh, ow);
     size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
     size_t total = (size_t)n * oh * ow;
@@ -251,9 +298,9 @@ __global__ __launch_bounds__(256) void k_cv_resize(const uint8_t *__restrict__ i
     bool inner;
     T.row(oy, h, y0, y1, b0, b1);
     T.col(ox, w, sx, sx1, a0, a1, inner);
-    const uint8_t *fr = in + f * Src::frame_bytes(h, w);
-    const uint32_t p00 = Src::template px<false>(fr, h, w, y0, sx), p01 = Src::template px<false>(fr, h, w, y0, sx1);
-    const uint32_t p10 = Src::template px<false>(fr, h, w, y1, sx), p11 = Src::template px<false>(fr, h, w, y1, sx1);
+    const uint8_t *fr = in + f * L.template frame<Src>(h, w);
+    const uint32_t p00 = Src::template px<false>(fr, L, h, w, y0, sx), p01 = Src::template px<false>(fr, L, h, w, y0, sx1);
+    const uint32_t p10 = Src::template px<false>(fr, L, h, w, y1, sx), p11 = Src::template px<false>(fr, L, h, w, y1, sx1);
     uint8_t *o = out + gid * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c)
@@ -279,8 +326,8 @@ static int cv_tab(SvcHandle *h, int height, int width, int sh, int sw, const int
 }
 
 template <class Src>
-static int resize_frames(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width, uint8_t *out,
-                         int sh, int sw, void *stream) {
+static int resize_frames(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, int n, int height,
+                         int width, uint8_t *out, int sh, int sw, void *stream) {
     if (!h || n < 0 || (n > 0 && (!frames || !out)) || !Src::size_ok(height, width) || sh < 1 || sw < 1) {     // n = 0: a no-op, null buffers allowed
         svc_set_error("%s: invalid argument%s", name, Src::size_rule());
         return SVC_E_INVALID;
@@ -293,18 +340,18 @@ static int resize_frames(const char *name, SvcHandle *h, const uint8_t *frames, 
     size_t total = (size_t)n * sh * sw;
     ProfScope ps(h, SVC_K_RESIZE, (hipStream_t)stream);
     k_cv_resize<Src><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
-        frames, out, tab, n, height, width, sh, sw);
+        frames, out, tab, n, height, width, sh, sw, L);
     SVC_CHECK_LAUNCH();
     return SVC_OK;
 }
 
 extern "C" int svc_resize_frames_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
                                     uint8_t *out, int sh, int sw, void *stream) {
-    return resize_frames<SrcRgb>("svc_resize_frames_u8", h, frames, n, height, width, out, sh, sw, stream);
+    return resize_frames<SrcRgb<Packed>>("svc_resize_frames_u8", h, frames, Packed(), n, height, width, out, sh, sw, stream);
 }
 extern "C" int svc_resize_frames_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
                                       uint8_t *out, int sh, int sw, void *stream) {
-    return resize_frames<SrcNv12>("svc_resize_frames_nv12", h, frames, n, height, width, out, sh, sw, stream);
+    return resize_frames<SrcNv12<Packed>>("svc_resize_frames_nv12", h, frames, Packed(), n, height, width, out, sh, sw, stream);
 }
 
 // --------------------------------------------------------------------------------------
@@ -335,27 +382,29 @@ __device__ __forceinline__ void row_out(uint8_t *__restrict__ dst, const uint8_t
 // thread g owns output pixels [16 g, 16 g + 16) = bytes [48 g, 48 g + 48), written as three aligned 16-byte stores.  The
 // group's source is one run of 16 pixels of the window row it starts in (Src::px16), and when the group runs over the end
 // of that row, the rest comes from the next window row (of this frame or the next one) through a second run, placed so
-// that its pixel k is the first of that row, merged in by byte mask.
+// that its pixel k is the first of that row, merged in by byte mask.  Both runs take their address from (frame, y, x)
+// through the layout, so the second one lies one pitch (or one frame stride) further, not 3 w bytes; why its first k
+// pixels -- left of that row, in padding or in the row above -- are inside the buffer: see px16 above.
 template <class Src, bool BGR>
 __global__ __launch_bounds__(256) void k_render_copy_to_rgb(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                             const int32_t *__restrict__ boxes, int n, int height, int width, int bh,
-                                                            int bw, const uint8_t *in_end) {
+                                                            int bw, const uint8_t *in_end, const typename Src::lay L) {
     const long long total_px = (long long)n * bh * bw, p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 16;
     if (p0 >= total_px) return;
-    const size_t fstride = Src::frame_bytes(height, width);
+    const size_t fstride = L.template frame<Src>(height, width);
     const long long R = p0 / bw;
     const int col = (int)(p0 - R * bw);
     int f = (int)(R / bh), r = (int)(R - (long long)f * bh);
     int x0, y0;
     render_origin(boxes, f, height, width, bh, bw, x0, y0);
     uint32_t o[12];
-    Src::template px16<BGR>(in + f * fstride, height, width, y0 + r, x0 + col, in_end, o);
+    Src::template px16<BGR>(in + f * fstride, L, height, width, y0 + r, x0 + col, in_end, o);
     const int k = bw - col;                                     // pixels of the group in row R
     if (k < 16 && p0 + k < total_px) {
         if (++r == bh) { r = 0; ++f; }
         render_origin(boxes, f, height, width, bh, bw, x0, y0);
         uint32_t o2[12];                                         // bytes [3k, 48) = the first pixels of the next row
-        Src::template px16<BGR>(in + f * fstride, height, width, y0 + r, x0 - k, in_end, o2);
+        Src::template px16<BGR>(in + f * fstride, L, height, width, y0 + r, x0 - k, in_end, o2);
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
             const int lim = 3 * k - 4 * i;                       // bytes of dword i that stay with row R
@@ -439,7 +488,7 @@ __device__ __forceinline__ void st16_a8(uint8_t *d, const uint32_t (&v)[4], bool
 template <class Src>
 __global__ __launch_bounds__(256) void k_render_copy_to_nv12(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                              const int32_t *__restrict__ boxes, int n, int height, int width, int bh,
-                                                             int bw, const uint8_t *in_end) {
+                                                             int bw, const uint8_t *in_end, const typename Src::lay L) {
     const int G = (bw + 15) >> 4, hb = bh >> 1;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long long)n * hb * G) return;
@@ -447,10 +496,10 @@ __global__ __launch_bounds__(256) void k_render_copy_to_nv12(const uint8_t *__re
     const int g = (int)(t - R * G), f = (int)(R / hb), j = (int)(R - (long long)f * hb);
     int x0, y0;
     render_origin(boxes, f, height, width, bh, bw, x0, y0);
-    const uint8_t *fr = in + f * Src::frame_bytes(height, width);
+    const uint8_t *fr = in + f * L.template frame<Src>(height, width);
     uint32_t a[12], b[12];
-    Src::template px16<false>(fr, height, width, y0 + 2 * j, x0 + 16 * g, in_end, a);
-    Src::template px16<false>(fr, height, width, y0 + 2 * j + 1, x0 + 16 * g, in_end, b);
+    Src::template px16<false>(fr, L, height, width, y0 + 2 * j, x0 + 16 * g, in_end, a);
+    Src::template px16<false>(fr, L, height, width, y0 + 2 * j + 1, x0 + 16 * g, in_end, b);
     uint32_t ya[4] = {0u, 0u, 0u, 0u}, yb[4] = {0u, 0u, 0u, 0u}, uv[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int i = 0; i < 8; ++i) {                               // block i of the strip: pixels 2 i, 2 i + 1 of both rows
@@ -584,7 +633,7 @@ struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the form
 template <class Src, class Dst>
 __global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                         const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
-                                                        long long total) {
+                                                        long long total, const typename Src::lay L) {
     constexpr int B = Dst::rows;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
@@ -593,10 +642,10 @@ __global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restric
     const int i = (int)(t - R * wb), f = (int)(R / hb), j = (int)(R - (long long)f * hb);
     int x0, y0;
     render_origin(boxes, f, height, width, bh, bw, x0, y0);
-    const uint8_t *fr = in + f * Src::frame_bytes(height, width);
+    const uint8_t *fr = in + f * L.template frame<Src>(height, width);
     uint32_t p[B * B];
 #pragma unroll
-    for (int k = 0; k < B * B; ++k) p[k] = Src::template px<Dst::bgr>(fr, height, width, y0 + B * j + k / B, x0 + B * i + k % B);
+    for (int k = 0; k < B * B; ++k) p[k] = Src::template px<Dst::bgr>(fr, L, height, width, y0 + B * j + k / B, x0 + B * i + k % B);
     Dst::put_block(out + f * Dst::frame_bytes(bh, bw), bh, bw, j, i, p);
 }
 
@@ -608,13 +657,13 @@ template <class Src, class Dst>
 __global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                        const int *__restrict__ tab, const int32_t *__restrict__ boxes, int f0,
                                                        int height, int width, int bh, int bw, int oh, int ow, int span_cap,
-                                                       const uint8_t *in_end, int vec) {
+                                                       const uint8_t *in_end, int vec, const typename Src::lay L) {
     extern __shared__ __align__(16) uint8_t sm_rr[];
     const CvLinear T(tab, oh, ow);
     const int j = blockIdx.x, f = f0 + blockIdx.y;
     int x0, y0;
     render_origin(boxes, f, height, width, bh, bw, x0, y0);
-    const uint8_t *fr = in + f * Src::frame_bytes(height, width);
+    const uint8_t *fr = in + f * L.template frame<Src>(height, width);
     uint8_t *lds = sm_rr + 2 * span_cap, *dst[Dst::out_rows];
     for (int r = 0; r < Dst::rows; ++r) {
         int ry[2], b0, b1, sh[2];
@@ -622,7 +671,7 @@ __global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict
         if (r) __syncthreads();                                 // row 0's resampling has read the staged rows
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-            sh[k] = Src::stage_row(fr, height, width, y0 + ry[k], x0, bw, sm_rr + k * span_cap, span_cap, in_end, vec);
+            sh[k] = Src::stage_row(fr, L, height, width, y0 + ry[k], x0, bw, sm_rr + k * span_cap, span_cap, in_end, vec);
         if (!r) Dst::dst_rows(out, blockIdx.y, oh, ow, j, dst);
         uint8_t *orow = Dst::rgb_row(lds, dst, ow, r);
         __syncthreads();
@@ -642,8 +691,8 @@ __global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict
 }
 
 template <class Src, class Dst>
-static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
-                        int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, int n, int height,
+                        int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
     if (!h || n < 0 || (n > 0 && (!frames || !boxes || !out)) || !Src::size_ok(height, width) || bw < 1 || bh < 1 ||
         bw > width || bh > height) {                                                       // n = 0: a no-op, null buffers allowed
         svc_set_error("%s: invalid argument%s", name, Src::size_rule());
@@ -667,8 +716,9 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, i
     }
     if (n == 0) return SVC_OK;
     SVC_HIP(hipSetDevice(h->device));
-    const uint8_t *in_end = frames + n * Src::frame_bytes(height, width);
-    const bool aligned_in = ((uintptr_t)frames & 15) == 0, aligned_out = ((uintptr_t)out & 15) == 0;
+    // the end of the last frame's last plane row: what the 16-byte loads are guarded by (Packed: frames + n * frame_bytes)
+    const uint8_t *in_end = frames + (size_t)(n - 1) * L.template frame<Src>(height, width) + Src::extent(L, height, width);
+    const bool aligned_in = ((uintptr_t)frames & 15) == 0 && Src::vec_ok(L), aligned_out = ((uintptr_t)out & 15) == 0;
     hipStream_t s = (hipStream_t)stream;
     const int *tab = nullptr;
     if (!copy) {
@@ -679,10 +729,10 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, i
     if (copy) {
         if (Dst::vec_ok(bw) && aligned_in && aligned_out) {
             const unsigned grid = (unsigned)((Dst::vec_threads(n, bh, bw) + 255) / 256);
-            Dst::template vec_copy<Src>()<<<grid, 256, 0, s>>>(frames, out, boxes, n, height, width, bh, bw, in_end);
+            Dst::template vec_copy<Src>()<<<grid, 256, 0, s>>>(frames, out, boxes, n, height, width, bh, bw, in_end, L);
         } else {
             const long long total = (long long)n * (bh / Dst::rows) * (bw / Dst::rows);
-            k_render_copy_px<Src, Dst><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total);
+            k_render_copy_px<Src, Dst><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total, L);
         }
         SVC_CHECK_LAUNCH();
         return SVC_OK;
@@ -690,27 +740,125 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, i
     for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
         const dim3 grid((unsigned)(oh / Dst::rows), (unsigned)std::min(n - f0, 65535));
         k_render_resize<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * Dst::frame_bytes(oh, ow), tab, boxes, f0, height, width,
-                                                         bh, bw, oh, ow, span_cap, in_end, aligned_in);
+                                                         bh, bw, oh, ow, span_cap, in_end, aligned_in, L);
         SVC_CHECK_LAUNCH();
     }
     return SVC_OK;
 }
 
+// the four source x sink pairings of one layout (flags picks the RGB sink's channel order)
+template <class Lay>
+static int render_crops_fmt(const char *name, int pix_fmt, bool to_nv12, SvcHandle *h, const uint8_t *frames, const Lay &L, int n,
+                            int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags,
+                            void *stream) {
+    if (pix_fmt == SVC_FMT_NV12) {
+        if (to_nv12) return render_crops<SrcNv12<Lay>, DstNv12>(name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+        return (flags & SVC_RENDER_BGR ? render_crops<SrcNv12<Lay>, DstRgb<true>> : render_crops<SrcNv12<Lay>, DstRgb<false>>)(
+            name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    }
+    if (to_nv12) return render_crops<SrcRgb<Lay>, DstNv12>(name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return (flags & SVC_RENDER_BGR ? render_crops<SrcRgb<Lay>, DstRgb<true>> : render_crops<SrcRgb<Lay>, DstRgb<false>>)(
+        name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+}
+
 extern "C" int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                    int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return (flags & SVC_RENDER_BGR ? render_crops<SrcRgb, DstRgb<true>> : render_crops<SrcRgb, DstRgb<false>>)(
-        "svc_render_crops_u8", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_u8", SVC_FMT_RGB24, false, h, frames, Packed(), n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }
 extern "C" int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                      int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return (flags & SVC_RENDER_BGR ? render_crops<SrcNv12, DstRgb<true>> : render_crops<SrcNv12, DstRgb<false>>)(
-        "svc_render_crops_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_nv12", SVC_FMT_NV12, false, h, frames, Packed(), n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }
 extern "C" int svc_render_crops_u8_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                            int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops<SrcRgb, DstNv12>("svc_render_crops_u8_to_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_u8_to_nv12", SVC_FMT_RGB24, true, h, frames, Packed(), n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }
 extern "C" int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                              int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops<SrcNv12, DstNv12>("svc_render_crops_nv12_to_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_nv12_to_nv12", SVC_FMT_NV12, true, h, frames, Packed(), n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+}
+
+// --------------------------------------------------------------------------------------
+// the same launchers on frames in the caller's layout (SvcFrameLayout: include/svc.h states the rules)
+// --------------------------------------------------------------------------------------
+// The layout of a height x width picture, checked -> Pitched.  Plain integer comparisons, before any device work.
+static int layout_check(const char *name, const SvcFrameLayout *lay, int n, int height, int width, Pitched &L) {
+    if (!lay) {
+        svc_set_error("%s: layout is NULL", name);
+        return SVC_E_INVALID;
+    }
+    if (lay->struct_size != sizeof(SvcFrameLayout)) {
+        svc_set_error("%s: SvcFrameLayout.struct_size is %u, this library's is %zu (a stale binding)", name, lay->struct_size,
+                      sizeof(SvcFrameLayout));
+        return SVC_E_INVALID;
+    }
+    const bool nv12 = lay->pix_fmt == SVC_FMT_NV12;
+    if (!nv12 && lay->pix_fmt != SVC_FMT_RGB24) {
+        svc_set_error("%s: unknown pix_fmt %d (SVC_FMT_RGB24 or SVC_FMT_NV12)", name, lay->pix_fmt);
+        return SVC_E_INVALID;
+    }
+    if (!(nv12 ? SrcNv12<Pitched>::size_ok(height, width) : SrcRgb<Pitched>::size_ok(height, width))) {
+        svc_set_error("%s: invalid argument%s", name, nv12 ? SrcNv12<Pitched>::size_rule() : SrcRgb<Pitched>::size_rule());
+        return SVC_E_INVALID;
+    }
+    L = Pitched{lay->frame_stride, lay->pitch, lay->chroma_offset, lay->chroma_pitch};
+    if (L.frame_stride < 0 || L.pitch < 0 || L.chroma_offset < 0 || L.chroma_pitch < 0) {
+        svc_set_error("%s: layout values must be non-negative", name);
+        return SVC_E_INVALID;
+    }
+    const long long row = nv12 ? (long long)width : 3ll * width;
+    if (L.pitch < row) {
+        svc_set_error("%s: pitch %lld is below the row's %lld bytes", name, L.pitch, row);
+        return SVC_E_INVALID;
+    }
+    if (!nv12 && (L.chroma_offset || L.chroma_pitch)) {
+        svc_set_error("%s: chroma_offset and chroma_pitch must be 0 for rgb24", name);
+        return SVC_E_INVALID;
+    }
+    if (nv12 && L.chroma_pitch < width) {
+        svc_set_error("%s: chroma_pitch %lld is below the width %d", name, L.chroma_pitch, width);
+        return SVC_E_INVALID;
+    }
+    // (128-bit products: a pitch near 2^63 must fail these comparisons, not wrap past them)
+    const __int128 luma_end = (__int128)L.pitch * (height - 1) + width;
+    if (nv12 && L.chroma_offset < luma_end) {
+        svc_set_error("%s: chroma_offset %lld is below pitch * (height - 1) + width = %lld: the chroma plane overlaps the last luma row",
+                      name, L.chroma_offset, (long long)luma_end);
+        return SVC_E_INVALID;
+    }
+    const __int128 extent = nv12 ? (__int128)L.chroma_offset + (__int128)L.chroma_pitch * (height / 2 - 1) + width
+                                 : (__int128)L.pitch * (height - 1) + 3ll * width;      // = Src::extent(L, height, width)
+    if (L.frame_stride < extent) {
+        svc_set_error("%s: frame_stride %lld is below the frame's extent of %lld bytes", name, L.frame_stride, (long long)extent);
+        return SVC_E_INVALID;
+    }
+    // the launchers form frames + (n - 1) * frame_stride + extent in 64 bits: it must be an address
+    if (n > 0 && (__int128)(n - 1) * L.frame_stride + extent > (__int128)PTRDIFF_MAX) {
+        svc_set_error("%s: %d frames of frame_stride %lld span more than PTRDIFF_MAX bytes", name, n, L.frame_stride);
+        return SVC_E_INVALID;
+    }
+    return SVC_OK;
+}
+
+extern "C" int svc_resize_frames_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height,
+                                        int width, uint8_t *out, int sh, int sw, void *stream) {
+    const char *name = "svc_resize_frames_layout";
+    Pitched L;
+    int rc = layout_check(name, layout, n, height, width, L);
+    if (rc) return rc;
+    if (layout->pix_fmt == SVC_FMT_NV12) return resize_frames<SrcNv12<Pitched>>(name, h, frames, L, n, height, width, out, sh, sw, stream);
+    return resize_frames<SrcRgb<Pitched>>(name, h, frames, L, n, height, width, out, sh, sw, stream);
+}
+extern "C" int svc_render_crops_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height,
+                                       int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
+                                       int flags, void *stream) {
+    const char *name = "svc_render_crops_layout";
+    Pitched L;
+    int rc = layout_check(name, layout, n, height, width, L);
+    if (rc) return rc;
+    if (out_fmt != SVC_FMT_RGB24 && out_fmt != SVC_FMT_NV12) {
+        svc_set_error("%s: unknown out_fmt %d (SVC_FMT_RGB24 or SVC_FMT_NV12)", name, out_fmt);
+        return SVC_E_INVALID;
+    }
+    return render_crops_fmt(name, layout->pix_fmt, out_fmt == SVC_FMT_NV12, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }

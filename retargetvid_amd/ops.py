@@ -76,6 +76,104 @@ def picture_size(frames, pix_fmt):
     if shape[1:] != frame_shape(pix_fmt, h, w):
         raise ValueError('frames of shape %s are not %s frames' % (shape, pix_fmt))
     return n, h, w
+
+
+LAYOUT_KEYS = ('pitch', 'chroma_offset', 'chroma_pitch')
+
+
+class FrameLayout:
+    """Where the bytes of a h x w picture's frames lie (include/svc.h: SvcFrameLayout), checked: what frame_layout returns and
+    the layout= of Engine.resize_frames / render_crops takes.  extent: bytes from a frame's start to the end of its last plane row."""
+    __slots__ = ('pix_fmt', 'h', 'w', 'frame_stride', 'pitch', 'chroma_offset', 'chroma_pitch', 'extent')
+
+    def key(self):
+        return (self.pix_fmt, self.h, self.w, self.frame_stride, self.pitch, self.chroma_offset, self.chroma_pitch)
+
+    def __eq__(self, other):
+        return isinstance(other, FrameLayout) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'FrameLayout(%s %dx%d frame_stride=%d pitch=%d chroma_offset=%d chroma_pitch=%d)' % (
+            self.pix_fmt, self.w, self.h, self.frame_stride, self.pitch, self.chroma_offset, self.chroma_pitch)
+
+    def every(self, step):
+        """The layout of every step-th frame of these: the same planes, frames step * frame_stride apart (a strided view
+        frames[a::step] of the container is then read where it lies)."""
+        L = FrameLayout()
+        for k in self.__slots__:
+            setattr(L, k, getattr(self, k))
+        L.frame_stride = self.frame_stride * int(step)
+        return L
+
+    def struct(self):
+        """The SvcFrameLayout the C entries take."""
+        return _lib.SvcFrameLayout(ctypes.sizeof(_lib.SvcFrameLayout), PIX_FMTS.index(self.pix_fmt), self.frame_stride, self.pitch,
+                                   self.chroma_offset, self.chroma_pitch)
+
+
+def frame_layout(pix_fmt, h, w, layout=None, frame_stride=None):
+    """The layout of the frames of a h x w picture in `pix_fmt` -> FrameLayout.  layout: dict(pitch=, chroma_offset=,
+    chroma_pitch=) in bytes, missing keys (or None) taking their packed value (pitch 3 w | w, chroma_offset pitch * h,
+    chroma_pitch = pitch; both chroma values 0 for rgb24); frame_stride: bytes from frame to frame (None: the frame's extent, i.e. no
+    gap).  ValueError with the rule of include/svc.h that is broken -- the checks the C launchers make, made before any device work."""
+    shape = frame_shape(pix_fmt, h, w)
+    h, w = int(h), int(w)
+    layout = dict(layout or {})
+    unknown = sorted(set(layout) - set(LAYOUT_KEYS))
+    if unknown:
+        raise ValueError('unknown layout key %s (the keys are %s)' % (', '.join(map(repr, unknown)), ', '.join(LAYOUT_KEYS)))
+    nv12 = pix_fmt == 'nv12'
+    row = w if nv12 else 3 * w
+    L = FrameLayout()
+    L.pix_fmt, L.h, L.w = pix_fmt, h, w
+    L.pitch = int(layout['pitch']) if layout.get('pitch') is not None else row
+    if nv12:
+        L.chroma_offset = int(layout['chroma_offset']) if layout.get('chroma_offset') is not None else L.pitch * h
+        L.chroma_pitch = int(layout['chroma_pitch']) if layout.get('chroma_pitch') is not None else L.pitch
+    else:
+        L.chroma_offset, L.chroma_pitch = int(layout.get('chroma_offset') or 0), int(layout.get('chroma_pitch') or 0)
+    if min(L.pitch, L.chroma_offset, L.chroma_pitch, 0 if frame_stride is None else int(frame_stride)) < 0:
+        raise ValueError('layout values must be non-negative')
+    if L.pitch < row:
+        raise ValueError("pitch %d is below the row's %d bytes" % (L.pitch, row))
+    if not nv12 and (L.chroma_offset or L.chroma_pitch):
+        raise ValueError('chroma_offset and chroma_pitch must be 0 for rgb24')
+    if nv12 and L.chroma_pitch < w:
+        raise ValueError('chroma_pitch %d is below the width %d' % (L.chroma_pitch, w))
+    if nv12 and L.chroma_offset < L.pitch * (h - 1) + w:
+        raise ValueError('chroma_offset %d is below pitch * (height - 1) + width = %d: the chroma plane overlaps the last luma row'
+                         % (L.chroma_offset, L.pitch * (h - 1) + w))
+    L.extent = L.chroma_offset + L.chroma_pitch * (h // 2 - 1) + w if nv12 else L.pitch * (h - 1) + 3 * w
+    L.frame_stride = L.extent if frame_stride is None else int(frame_stride)
+    if L.frame_stride < L.extent:
+        raise ValueError("frame_stride %d is below the frame's extent of %d bytes" % (L.frame_stride, L.extent))
+    if max(L.key()[3:]) >= 1 << 62:
+        raise ValueError('layout values must be below 2^62')
+    assert layout or frame_stride is not None or L.extent == int(np.prod(shape))
+    return L
+
+
+def _pitched(frames, layout, pix_fmt):
+    """frames of a FrameLayout: a uint8 CUDA tensor [n, frame_stride] -- or any 2-D view with unit element stride whose rows are
+    frame_stride bytes apart and hold the frame's extent (the last frame need not have its trailing gap) -> n."""
+    if not isinstance(layout, FrameLayout):
+        raise TypeError('layout must be an ops.FrameLayout (ops.frame_layout(pix_fmt, h, w, dict(pitch=...), frame_stride))')
+    if layout.pix_fmt != pix_fmt:
+        raise ValueError('the layout is one of %s frames, pix_fmt says %s' % (layout.pix_fmt, pix_fmt))
+    if not (torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8):
+        raise TypeError('frames must be a CUDA tensor of dtype torch.uint8')
+    if frames.dim() != 2:
+        raise ValueError('frames with a layout are uint8 [n, frame_stride], not %s' % (tuple(frames.shape),))
+    n = int(frames.shape[0])
+    if n and (frames.stride(1) != 1 or int(frames.shape[1]) < layout.extent or (n > 1 and frames.stride(0) != layout.frame_stride)):
+        raise ValueError('frames of shape %s and strides %s do not hold frames of %d bytes that lie %d bytes apart'
+                         % (tuple(frames.shape), tuple(frames.stride()), layout.extent, layout.frame_stride))
+    return n
+
+
 BLEND_NEXT, MAP_HELD = 1, 2          # bits of cluster_center_'s per-map flags (include/svc.h: SVC_BLEND_NEXT, SVC_MAP_HELD)
 
 
@@ -123,9 +221,18 @@ class Engine:
             pass
 
     # -- ingest down-scale -------------------------------------------------------------
-    def resize_frames(self, frames, sh, sw, pix_fmt='rgb24'):
+    def resize_frames(self, frames, sh, sw, pix_fmt='rgb24', layout=None):
         """uint8 [n,h,w,3] -> uint8 [n,sh,sw,3], cv2.resize(INTER_LINEAR) semantics.  pix_fmt='nv12': frames uint8
-        [n,h*3/2,w], converted to RGB inside the kernel (svc_resize_frames_nv12): the bytes of the RGB call on the converted frames."""
+        [n,h*3/2,w], converted to RGB inside the kernel (svc_resize_frames_nv12): the bytes of the RGB call on the converted frames.
+        layout (an ops.FrameLayout): frames uint8 [n, frame_stride] as a decoder left them (svc_resize_frames_layout): the
+        bytes of the packed call on the packed pictures, without a repacking pass."""
+        if layout is not None:
+            n = _pitched(frames, layout, pix_fmt)
+            out = torch.empty((n, sh, sw, 3), dtype=torch.uint8, device=frames.device)
+            lay = layout.struct()
+            _lib.check(self.lib.svc_resize_frames_layout(self._h, _ptr(frames), ctypes.byref(lay), n, layout.h, layout.w, _ptr(out),
+                                                         sh, sw, _stream()))
+            return out
         _need_cuda(frames, torch.uint8, 'frames')
         n, h, w = picture_size(frames, pix_fmt)
         out = torch.empty((n, sh, sw, 3), dtype=torch.uint8, device=frames.device)
@@ -134,14 +241,16 @@ class Engine:
         return out
 
     # -- rendering ------------------------------------------------------------------------
-    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None, pix_fmt='rgb24', out_fmt='rgb24'):
+    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None, pix_fmt='rgb24', out_fmt='rgb24', layout=None):
         """uint8 [n,h,w,3] frames on the device (pix_fmt='nv12': uint8 [n,h*3/2,w], svc_render_crops_nv12; the crops are RGB / BGR
         either way) and int32 [n,4] boxes (x1,y1,x2,y2, one window size for all; a CUDA tensor, or
         host values that are copied over) -> uint8
         [n,oh,ow,3]: frame[y1:y2, x1:x2] copied (out_hw None or the window size) or resampled to out_hw = (oh, ow) with
         cv2.resize(INTER_LINEAR) semantics; bgr: R and B swapped.  Runs on the current stream (svc_render_crops_u8).
         out_fmt='nv12': the crops come out as NV12 frames uint8 [n,oh*3/2,ow] (BT.601 limited range of the RGB crop, fused
-        into the kernels: svc_render_crops_u8_to_nv12 / _nv12_to_nv12); oh and ow must be even and bgr unset (ValueError)."""
+        into the kernels: svc_render_crops_u8_to_nv12 / _nv12_to_nv12); oh and ow must be even and bgr unset (ValueError).
+        layout (an ops.FrameLayout): frames uint8 [n, frame_stride] as a decoder left them (svc_render_crops_layout); the
+        crops are the packed call's on the packed pictures."""
         n = int(frames.shape[0])
         on_dev = torch.is_tensor(boxes) and boxes.is_cuda
         if n:
@@ -151,18 +260,24 @@ class Engine:
         bw, bh = int(b0[2] - b0[0]), int(b0[3] - b0[1])
         oh, ow = (bh, bw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
         shape = (n,) + out_frame_shape(out_fmt, oh, ow, bgr)      # (the ValueErrors come before anything touches the device)
-        _need_cuda(frames, torch.uint8, 'frames')
+        if layout is None:
+            _need_cuda(frames, torch.uint8, 'frames')
+        else:
+            _pitched(frames, layout, pix_fmt)
         if not on_dev:
             boxes = torch.from_numpy(np.ascontiguousarray(boxes, np.int32)).to(frames.device)
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
-        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt, out_fmt)
+        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt, out_fmt, layout)
 
-    def _render(self, frames, boxes, bw, bh, out, bgr, pix_fmt='rgb24', out_fmt='rgb24'):
-        _need_cuda(frames, torch.uint8, 'frames')
+    def _render(self, frames, boxes, bw, bh, out, bgr, pix_fmt='rgb24', out_fmt='rgb24', layout=None):
         _need_cuda(boxes, torch.int32, 'boxes')
         _need_cuda(out, torch.uint8, 'out')
-        n, h, w = picture_size(frames, pix_fmt)
+        if layout is None:
+            _need_cuda(frames, torch.uint8, 'frames')
+            n, h, w = picture_size(frames, pix_fmt)
+        else:
+            n, h, w = _pitched(frames, layout, pix_fmt), layout.h, layout.w
         if out_fmt == 'nv12':
             on, oh, ow = picture_size(out, 'nv12')
             out_frame_shape(out_fmt, oh, ow, bgr)
@@ -171,6 +286,11 @@ class Engine:
             assert out.shape[3] == 3
             on, oh, ow = (int(v) for v in out.shape[:3])
         assert tuple(boxes.shape) == (n, 4) and on == n
+        if layout is not None:
+            lay = layout.struct()
+            _lib.check(self.lib.svc_render_crops_layout(self._h, _ptr(frames), ctypes.byref(lay), n, h, w, _ptr(boxes), bw, bh, _ptr(out),
+                                                        OUT_FMTS.index(out_fmt), oh, ow, RENDER_BGR if bgr else 0, _stream()))
+            return out
         fn = getattr(self.lib, RENDER_ENTRIES[pix_fmt, out_fmt])
         _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out), oh, ow, RENDER_BGR if bgr else 0, _stream()))
         return out

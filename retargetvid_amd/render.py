@@ -13,16 +13,48 @@ on-device generator (synth.LazyBlobVideo: select on the device).  A video dict w
 either way -- unless out_fmt='nv12' asks for NV12 crops (uint8 [m, oh * 3 / 2, ow], what a hardware encoder takes: BT.601
 limited range, fused into the render kernels, svc_render_crops_u8_to_nv12 / _nv12_to_nv12; half the bytes to copy back).
 The crops come back through pinned double buffers on a
-second side stream, so that the sink consumes chunk c while the device renders chunk c + 1."""
+second side stream, so that the sink consumes chunk c while the device renders chunk c + 1.
+A video dict with layout=dict(pitch=, chroma_offset=, chroma_pitch=) holds its frames as a decoder left them (uint8
+[n, frame_stride]: smartVidCrop.video_layout); they are staged as they are and read through the layout by the kernels
+(svc_render_crops_layout), and the crops are those of the packed pictures."""
 import numpy as np
 
 _MAX_CHUNK = 32
 _RING_BYTES = 96 << 20         # one output slot (device and pinned, two of each per engine): at most this many bytes
 
 
-def _container(video, pix_fmt=None):
+def _container(video, pix_fmt=None, layout=None):
     """-> frames, n, h, w (the PICTURE's size), pix_fmt.  The format is the video dict's ('rgb24' when it does not say), or
-    `pix_fmt` for a bare container; a dict's NV12 container is checked against its w, h (smartVidCrop.video_pix_fmt)."""
+    `pix_fmt` for a bare container; a dict's NV12 container is checked against its w, h (smartVidCrop.video_pix_fmt).  A
+    dict with a layout, or a bare container with `layout` (an ops.FrameLayout), holds uint8 [n, frame_stride] frames:
+    _frame_layout gives the checked layout."""
+    layout = _frame_layout(video, pix_fmt, layout)
+    return _layout_container(video, layout) if layout is not None else _packed_container(video, pix_fmt)
+
+
+def _layout_container(video, layout):
+    """_container for uint8 [n, frame_stride] frames of a checked ops.FrameLayout."""
+    frames = video['frames'] if isinstance(video, dict) else video
+    import torch
+    if hasattr(frames, 'select') and not hasattr(frames, 'shape'):
+        raise ValueError('a layout describes frames in memory, not an on-device generator')
+    if not torch.is_tensor(frames):
+        frames = np.asarray(frames)
+    if frames.dtype not in (np.uint8, torch.uint8) or frames.ndim != 2 or int(frames.shape[1]) != layout.frame_stride:
+        raise ValueError('frames with this layout are uint8 [n, %d], not %s %s' % (layout.frame_stride, frames.dtype, tuple(frames.shape)))
+    return frames, int(frames.shape[0]), layout.h, layout.w, layout.pix_fmt
+
+
+def _frame_layout(video, pix_fmt=None, layout=None):
+    """The ops.FrameLayout of a video dict that has one (smartVidCrop.video_layout: checked), else `layout` (a bare container's), else None."""
+    if isinstance(video, dict) and video.get('layout') is not None:
+        from .smartVidCrop import video_layout
+        return video_layout(video if pix_fmt is None else dict(video, pix_fmt=pix_fmt))
+    return layout
+
+
+def _packed_container(video, pix_fmt=None):
+    """_container for packed frames."""
     frames = video['frames'] if isinstance(video, dict) else video
     if isinstance(video, dict) and (pix_fmt is not None or video.get('pix_fmt')):
         from .smartVidCrop import video_pix_fmt
@@ -60,7 +92,7 @@ def check_boxes(bbs, fc, h, w):
     return (int(bw[0]), int(bh[0])) if fc else (0, 0)
 
 
-def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, chunk=32, pix_fmt=None, out_fmt='rgb24'):
+def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, chunk=32, pix_fmt=None, out_fmt='rgb24', layout=None):
     """Render VD['fc'] frames of `video` (the ingest_pickle dict, or its 'frames' container) at VD['bbs_np'].
     pix_fmt: the frames' format when `video` is a bare container (a dict brings its own 'pix_fmt'; default 'rgb24'); an
     unknown format, an NV12 picture of odd size or a container of another shape raise ValueError before any device work.
@@ -69,8 +101,10 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     buffer that is refilled after the call returns, so copy what you keep.  -> numpy uint8 [fc, oh, ow, 3] without a sink,
     else None.  Boxes of unequal size or outside the frame raise ValueError before any device work.
     out_fmt='nv12': chunks and the returned array are NV12 frames uint8 [m, oh * 3 / 2, ow] (include/svc.h states the formula);
-    an odd output size (pass an even out_size), bgr with it, or an unknown format raise ValueError before any device work."""
-    frames, n, h, w, pix_fmt = _container(video, pix_fmt)
+    an odd output size (pass an even out_size), bgr with it, or an unknown format raise ValueError before any device work.
+    layout: the ops.FrameLayout of a bare container of uint8 [n, frame_stride] frames (a dict brings its own 'layout')."""
+    layout = _frame_layout(video, pix_fmt, layout)             # (resolved and checked once)
+    frames, n, h, w, pix_fmt = _layout_container(video, layout) if layout is not None else _packed_container(video, pix_fmt)
     fc = int(VD['fc'])
     if n < fc:
         raise ValueError('the container holds %d frames, the video has %d' % (n, fc))
@@ -98,14 +132,14 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     out = _OutRing(engine, chunk, oh, ow, sink, out_fmt)
 
     def emit(staged, s):
-        out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr, pix_fmt)
+        out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr, pix_fmt, layout)
 
     if hasattr(frames, 'select') and not hasattr(frames, 'shape'):             # on-device generator
         for s in range(0, fc, chunk):
             emit(frames.select(range(s, min(fc, s + chunk))).to(dev).contiguous(), s)
     elif torch.is_tensor(frames) and frames.is_cuda:
         src = frames if frames.device == dev else frames[:fc].to(dev)
-        src = src.contiguous()
+        src = src.contiguous()                 # (frames with a layout are [n, frame_stride] rows: nothing is repacked)
         for s in range(0, fc, chunk):
             emit(src[s:min(fc, s + chunk)], s)
     else:
@@ -140,13 +174,13 @@ class _OutRing:
         self.c = 0
         self.pending = None                 # (slot, frames) of the chunk whose D2H is in flight
 
-    def push(self, staged, boxes, bw, bh, bgr, pix_fmt='rgb24'):
+    def push(self, staged, boxes, bw, bh, bgr, pix_fmt='rgb24', layout=None):
         m = int(staged.shape[0])
         cap = self.ring['key'][0]
         for s in range(0, m, cap):          # (a host feed stages at most 32 frames, the ring holds `chunk`)
-            self._one(staged[s:s + cap], boxes[s:s + cap], bw, bh, bgr, pix_fmt)
+            self._one(staged[s:s + cap], boxes[s:s + cap], bw, bh, bgr, pix_fmt, layout)
 
-    def _one(self, staged, boxes, bw, bh, bgr, pix_fmt='rgb24'):
+    def _one(self, staged, boxes, bw, bh, bgr, pix_fmt='rgb24', layout=None):
         import torch
         m = int(staged.shape[0])
         slot = self.c & 1
@@ -155,7 +189,7 @@ class _OutRing:
         if self.used[slot]:
             compute.wait_event(self.copied[slot])           # the device slot's previous D2H has read it
         dst = self.ring['dev'][slot][:m]
-        self.engine._render(staged, boxes, bw, bh, dst, bgr, pix_fmt, self.out_fmt)
+        self.engine._render(staged, boxes, bw, bh, dst, bgr, pix_fmt, self.out_fmt, layout)
         self.rendered[slot].record(compute)
         with torch.cuda.stream(side):
             side.wait_event(self.rendered[slot])

@@ -203,7 +203,8 @@ class _Lane:
         if len(net):
             idx = [plan['true_inds'][j] for j in net]
             with torch.cuda.stream(self.stream):
-                small = S._small_frames(self.eng, frames, idx, plan['sal_h'], plan['sal_w'], self.eng.device, plan['pix_fmt'])
+                small = S._small_frames(self.eng, frames, idx, plan['sal_h'], plan['sal_w'], self.eng.device, plan['pix_fmt'],
+                                        plan.get('layout'))
                 self.small[self.frames_in:self.frames_in + len(net)].copy_(small)
             self.row_of_frame[self.frames_in:self.frames_in + len(net)] = v.row0 + net
             self.frames_in += len(net)
@@ -499,7 +500,7 @@ class JobScheduler:
                         shots = None
                         if v.get('trans_inds') is None:
                             shots = S.detect_shots(v['frames'], v['fr'], self.CP, net=net, engine=net.eng, trans_threshold=S.TRANS_THRESHOLD,
-                                                   pix_fmt=S.video_pix_fmt(v))
+                                                   pix_fmt=S.video_pix_fmt(v), layout=S.video_layout(v))
                         else:
                             st.synchronize()                  # whatever the callable enqueued is done before a lane reads the frames
                         self._planned[i] = (v, shots)

@@ -271,13 +271,39 @@ def video_pix_fmt(video):
     from .ops import frame_shape
     fmt = video.get('pix_fmt') or 'rgb24'
     shape = frame_shape(fmt, video['h'], video['w'])
-    if fmt != 'rgb24':
+    if video.get('layout') is not None:
+        video_layout(video)
+    elif fmt != 'rgb24':
         frames = video['frames']
         got = getattr(getattr(frames, 'pinned', frames), 'shape', None)       # (an on-device generator has no shape: its select() is trusted)
         if got is not None and tuple(int(v) for v in got[1:]) != shape:
             raise ValueError('%s frames of a %d x %d picture are uint8 [n, %s], not %s'
                              % (fmt, video['w'], video['h'], ', '.join(str(v) for v in shape), tuple(got)))
     return fmt
+
+
+def video_layout(video):
+    """The ops.FrameLayout of a video dict that says ``layout=dict(pitch=, chroma_offset=, chroma_pitch=)`` beside its pix_fmt
+    (frames as a decoder left them: uint8 [n, frame_stride] on the device, in host memory or pinned), None for a dict without
+    one (packed frames).  Checked WITHOUT any device work: ValueError for a broken rule of ops.frame_layout, a container that
+    is not 2-D, or an on-device generator (.select), which has no bytes to lay out."""
+    lay = video.get('layout')
+    if lay is None:
+        return None
+    from .ops import FrameLayout, frame_layout
+    fmt = video.get('pix_fmt') or 'rgb24'
+    frames = video['frames']
+    got = getattr(getattr(frames, 'pinned', frames), 'shape', None)
+    if got is None:
+        if hasattr(frames, 'select'):
+            raise ValueError('a layout describes frames in memory: %s produces its frames on demand (.select) and takes none'
+                             % type(frames).__name__)
+        got = np.asarray(frames).shape
+    if len(got) != 2:
+        raise ValueError('frames with a layout are uint8 [n, frame_stride], not %s' % (tuple(got),))
+    if isinstance(lay, FrameLayout):
+        lay = dict(pitch=lay.pitch, chroma_offset=lay.chroma_offset, chroma_pitch=lay.chroma_pitch)
+    return frame_layout(fmt, video['h'], video['w'], lay, int(got[1]))
 
 
 class _HostFeed:
@@ -310,15 +336,16 @@ class _HostFeed:
             self.shape, self.k = shape, k
         return self.k
 
-    def downscale(self, frames, idx, sal_h, sal_w, pix_fmt='rgb24'):
-        """frames: host frames [n,h,w,3] u8 (pix_fmt='nv12': [n,h*3/2,w]) -- a numpy array (pageable memory: gathered into
+    def downscale(self, frames, idx, sal_h, sal_w, pix_fmt='rgb24', layout=None):
+        """frames: host frames [n,h,w,3] u8 (pix_fmt='nv12': [n,h*3/2,w]; with a layout: [n, frame_stride], staged as they are
+        and read through the layout on the device, no host repack) -- a numpy array (pageable memory: gathered into
         the pinned slots by a few threads) or a PINNED torch tensor (copied from where it lies, frame by frame); idx: selected
         frame numbers.  -> uint8 CUDA tensor [len(idx), sal_h, sal_w, 3] RGB, produced on the caller's current stream."""
         import torch
         out = torch.empty((len(idx), sal_h, sal_w, 3), dtype=torch.uint8, device=self.dev)
 
         def put(staged, s):
-            out[s:s + staged.shape[0]] = self.engine.resize_frames(staged, sal_h, sal_w, pix_fmt)
+            out[s:s + staged.shape[0]] = self.engine.resize_frames(staged, sal_h, sal_w, pix_fmt, layout)
         self.feed(frames, idx, put)
         return out
 
@@ -397,10 +424,37 @@ def device_index(engine, idx, dev=None):
     return out
 
 
-def _small_frames(engine, frames, idx, sal_h, sal_w, dev, pix_fmt='rgb24'):
-    """Frames idx at saliency size (RGB) on the device, whatever the container (CUDA tensor, on-device generator, host array)
-    and the video's pixel format."""
+def _runs(idx):
+    """Frame numbers, in order, as runs with a constant positive step: [(first, count, step)], greedily from the left, so that
+    each run is the strided view frames[first : first + (count - 1) * step + 1 : step].  A frame that continues no run (a
+    repeat, a step backwards, the last one) is a run of one with step 1."""
+    idx = [int(v) for v in idx]
+    runs, s = [], 0
+    while s < len(idx):
+        step = idx[s + 1] - idx[s] if s + 1 < len(idx) else 0
+        e = s + 1
+        while step > 0 and e < len(idx) and idx[e] - idx[e - 1] == step:
+            e += 1
+        runs.append((idx[s], e - s, step if e - s > 1 else 1))
+        s = e
+    return runs
+
+
+def _small_frames(engine, frames, idx, sal_h, sal_w, dev, pix_fmt='rgb24', layout=None):
+    """Frames idx at saliency size (RGB) on the device, whatever the container (CUDA tensor, on-device generator, host array),
+    the video's pixel format and its layout (ops.FrameLayout: the selected [k, frame_stride] rows are read where they lie)."""
     import torch
+    if layout is not None and torch.is_tensor(frames) and frames.is_cuda:
+        # nothing is gathered: a selection with a constant step (consecutive frames, or every skip-th: what the ingest selects)
+        # is one strided view, read with a frame stride of step surfaces; any other selection is cut into such runs
+        if frames.device != dev:
+            return engine.resize_frames(frames[device_index(engine, idx, frames.device)].to(dev), sal_h, sal_w, pix_fmt, layout)
+        runs = _runs(idx)
+        small = [engine.resize_frames(frames[first:first + (count - 1) * step + 1:step], sal_h, sal_w, pix_fmt,
+                                      layout if step == 1 else layout.every(step)) for first, count, step in runs]
+        return small[0] if len(small) == 1 else torch.cat(small) if small else torch.empty((0, sal_h, sal_w, 3), dtype=torch.uint8, device=dev)
+    if layout is not None and hasattr(frames, 'select') and not torch.is_tensor(frames):
+        raise ValueError('a layout describes frames in memory, not an on-device generator')
     if torch.is_tensor(frames) and frames.is_cuda:
         return engine.resize_frames(frames[device_index(engine, idx, frames.device)].to(dev).contiguous(), sal_h, sal_w, pix_fmt)
     if not torch.is_tensor(frames) and hasattr(frames, 'select'):             # an on-device generator (synth.LazyBlobVideo)
@@ -411,15 +465,19 @@ def _small_frames(engine, frames, idx, sal_h, sal_w, dev, pix_fmt='rgb24'):
     if feed is None:
         feed = engine._host_feed = _HostFeed(engine)
     if not torch.is_tensor(frames) and hasattr(frames, 'pinned') and hasattr(frames, 'rows'):   # selected frames in pinned host memory (synth.HostSelectedVideo)
-        return feed.downscale(frames.pinned, frames.rows(idx), sal_h, sal_w, pix_fmt)
-    return feed.downscale(_host_frames(frames, pix_fmt), idx, sal_h, sal_w, pix_fmt)
+        return feed.downscale(frames.pinned, frames.rows(idx), sal_h, sal_w, pix_fmt, layout)
+    return feed.downscale(_host_frames(frames, pix_fmt, layout), idx, sal_h, sal_w, pix_fmt, layout)
 
 
-def _host_frames(frames, pix_fmt):
-    """A host container (numpy array, anything numpy reads, host torch tensor) as an array / tensor of uint8 frames of `pix_fmt`."""
+def _host_frames(frames, pix_fmt, layout=None):
+    """A host container (numpy array, anything numpy reads, host torch tensor) as an array / tensor of uint8 frames of `pix_fmt`
+    (with a layout: uint8 [n, frame_stride], as they are)."""
     import torch
     host = frames if torch.is_tensor(frames) else np.asarray(frames)
-    if pix_fmt == 'nv12':
+    if layout is not None:
+        if (host.dtype not in (np.uint8, torch.uint8)) or host.ndim != 2 or host.shape[1] != layout.frame_stride:
+            raise TypeError('frames with a layout must be uint8 [n, %d]' % layout.frame_stride)
+    elif pix_fmt == 'nv12':
         if (host.dtype not in (np.uint8, torch.uint8)) or host.ndim != 3:
             raise TypeError('nv12 frames must be uint8 [n,h*3/2,w]')
     elif (host.dtype not in (np.uint8, torch.uint8)) or host.ndim != 4 or host.shape[3] != 3:
@@ -435,7 +493,8 @@ def plan_video(video, crop_params, engine=None, shot_net=None, shots=None):
     detect_shots returned for this video: the scheduler's planner thread runs it ahead of the lanes).  Shared by
     ingest_frames (one video at a time) and the multi-video scheduler (retargetvid_amd/scheduler.py)."""
     fr, frame_count, w, h = video['fr'], int(video['frame_count']), int(video['w']), int(video['h'])
-    pix_fmt = video_pix_fmt(video)        # (raises on a bad format / size / container before any device work)
+    layout = video_layout(video)          # (both raise on a bad format / size / container / layout before any device work)
+    pix_fmt = layout.pix_fmt if layout is not None else video_pix_fmt(video)
     frames = video['frames']              # ndarray / CUDA tensor [n,h,w,3] u8 RGB ([n,h*3/2,w] NV12), or an object with __len__ and .select(idx)
     n_frames = len(frames)
     dsr = float(max(w, h)) / crop_params['max_input_d']
@@ -446,7 +505,8 @@ def plan_video(video, crop_params, engine=None, shot_net=None, shots=None):
             if shot_net is None:
                 raise ValueError('the video dict has no trans_inds: pass shot_net= (a transnetv1_handler.ShotTransNet) to run shot '
                                  'detection inside the ingest, as the reference\'s video path does')
-            shots = detect_shots(frames, fr, crop_params, net=shot_net, engine=engine, trans_threshold=TRANS_THRESHOLD, pix_fmt=pix_fmt)
+            shots = detect_shots(frames, fr, crop_params, net=shot_net, engine=engine, trans_threshold=TRANS_THRESHOLD, pix_fmt=pix_fmt,
+                                 layout=layout)
         trans_probs = shots['trans_probs']
         true_inds, map2orig, batches = _select_frames_video(n_frames, frame_count, trans_probs, TRANS_THRESHOLD,
                                                             crop_params['skip'], crop_params['read_batch'])
@@ -483,7 +543,7 @@ def plan_video(video, crop_params, engine=None, shot_net=None, shots=None):
     for first, cnt in batches:
         if cnt:
             zero_map[first + cnt - 1] = True
-    return dict(fr=fr, frame_count=frame_count, w=w, h=h, pix_fmt=pix_fmt, n_frames=n_frames, sal_h=sal_h, sal_w=sal_w, true_inds=true_inds,
+    return dict(fr=fr, frame_count=frame_count, w=w, h=h, pix_fmt=pix_fmt, layout=layout, n_frames=n_frames, sal_h=sal_h, sal_w=sal_w, true_inds=true_inds,
                 map2orig=map2orig, batches=batches, seg=seg, seg_sel=seg_sel, n_sel=n_sel, trans_probs=trans_probs,
                 zero_map=zero_map, flags=blend_flags(n_sel, seg_sel) if crop_params['clust_filt'] else None)
 
@@ -521,7 +581,7 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
     engine = engine or get_engine()
     t = time.perf_counter()
     plan = plan_video(video, crop_params, engine=engine, shot_net=shot_net)
-    frames, pix_fmt = video['frames'], plan['pix_fmt']
+    frames, pix_fmt, layout = video['frames'], plan['pix_fmt'], plan['layout']
     true_inds, batches, seg_sel = plan['true_inds'], plan['batches'], plan['seg_sel']
     sal_h, sal_w = plan['sal_h'], plan['sal_w']
     sc_register_time(t, '_read_shot_det')
@@ -564,7 +624,7 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
             # piece by piece: the tail of a piece follows its network on the stream
             for s0 in range(first, first + cnt - 1, int(stream_batch)):
                 idx = true_inds[s0:min(s0 + int(stream_batch), first + cnt - 1)]
-                smaps[s0:s0 + len(idx)] = engine.saliency(_small_frames(engine, frames, idx, sal_h, sal_w, dev, pix_fmt))
+                smaps[s0:s0 + len(idx)] = engine.saliency(_small_frames(engine, frames, idx, sal_h, sal_w, dev, pix_fmt, layout))
                 feed_tail(s0 + len(idx))
             feed_tail(first + cnt)                    # the batch's last selected frame keeps its all-zero map (the off-by-one)
             continue
@@ -573,7 +633,7 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
             continue
         if cnt > 1:
             idx = true_inds[first:first + cnt - 1]
-            smaps[first:first + cnt - 1] = engine.saliency(_small_frames(engine, frames, idx, sal_h, sal_w, dev, pix_fmt))
+            smaps[first:first + cnt - 1] = engine.saliency(_small_frames(engine, frames, idx, sal_h, sal_w, dev, pix_fmt, layout))
     if pipe is not None:
         for g, x, y in pipe.finish():
             xy_stream[g] = (x, y)
@@ -585,10 +645,11 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
     return _ingest_dict(plan, smaps, xy_stream, border_profile)
 
 
-def detect_shots(frames, fr, crop_params=None, net=None, engine=None, trans_threshold=0.1, pix_fmt='rgb24'):
+def detect_shots(frames, fr, crop_params=None, net=None, engine=None, trans_threshold=0.1, pix_fmt='rgb24', layout=None):
     """Shot detection of the reference's video path (smartVidCrop.py:248-372, :452-457) on the device: frames
     [n, h, w, 3] uint8, or [n, h * 3 / 2, w] with pix_fmt='nv12' (CUDA tensor, NumPy / pinned host tensor, or an on-device generator with .select) ->
-    dict(trans_probs, segmentation, trans_inds).  `net` is a transnetv1_handler.ShotTransNet (it owns the weights; the
+    dict(trans_probs, segmentation, trans_inds).  layout (an ops.FrameLayout, e.g. video_layout(video)): the frames are uint8
+    [n, frame_stride] as a decoder left them and are read where they lie.  `net` is a transnetv1_handler.ShotTransNet (it owns the weights; the
     reference's checkpoint does not ship with it).  The frames are down-scaled to 48 x 27 in read_batch-sized pieces
     (host inputs through the pinned, double-buffered feed), so a long 1080p / 4K video never sits on the device in
     full; `segmentation` carries the reference's end-of-segment fix (every scene ends where the next one starts, the
@@ -605,7 +666,11 @@ def detect_shots(frames, fr, crop_params=None, net=None, engine=None, trans_thre
     step = max(1, int(CP['read_batch']))
     for s0 in range(0, n, step):
         idx = list(range(s0, min(n, s0 + step)))
-        if torch.is_tensor(frames) and frames.is_cuda:
+        if layout is not None and not torch.is_tensor(frames) and hasattr(frames, 'select') and not hasattr(frames, 'shape'):
+            raise ValueError('a layout describes frames in memory, not an on-device generator')
+        if torch.is_tensor(frames) and frames.is_cuda and layout is not None:
+            small[s0:s0 + len(idx)] = eng.resize_frames(frames[s0:s0 + len(idx)], th, tw, pix_fmt, layout)      # a view: nothing is copied
+        elif torch.is_tensor(frames) and frames.is_cuda:
             small[s0:s0 + len(idx)] = eng.resize_frames(frames[s0:s0 + len(idx)].contiguous(), th, tw, pix_fmt)
         elif not torch.is_tensor(frames) and hasattr(frames, 'select'):
             small[s0:s0 + len(idx)] = eng.resize_frames(frames.select(idx).to(eng.device).contiguous(), th, tw, pix_fmt)
@@ -614,7 +679,7 @@ def detect_shots(frames, fr, crop_params=None, net=None, engine=None, trans_thre
             if feed is None:
                 feed = eng._host_feed = _HostFeed(eng)
             host = frames if torch.is_tensor(frames) else np.asarray(frames)
-            small[s0:s0 + len(idx)] = feed.downscale(host, idx, th, tw, pix_fmt)
+            small[s0:s0 + len(idx)] = feed.downscale(host, idx, th, tw, pix_fmt, layout)
     probs = T.video_transition_probs(net, small, fr, CP['read_batch'])
     seg = np.array(T.predictions_to_scenes(probs, threshold=trans_threshold), dtype=np.int32)
     for i in range(len(seg) - 1):                      # "shot segmentation FIX" (smartVidCrop.py:452-456)
@@ -771,10 +836,7 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
     # reference keys its cache by the name alone, :2244-2256, and would silently re-use it)
     cache_key = None
     if cache_fn is not None:
-        cache_key = dict(skip=CP['skip'], read_batch=CP['read_batch'], max_input_d=CP['max_input_d'],
-                         frame_count=int(video['frame_count']), shots='net' if video.get('trans_inds') is None else
-                         [int(v) for v in video['trans_inds']], weights=getattr(engine, 'weights_id', None),
-                         pix_fmt=video.get('pix_fmt') or 'rgb24')
+        cache_key = feature_cache_key(video, CP, engine)
     cached = None
     if cache_fn is not None and os.path.isfile(cache_fn):
         with open(cache_fn, 'rb') as fp:
@@ -818,6 +880,18 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         sc_register_time(t, 'render')
         results['t_render'] = sc_all_times(VD['fc'] / VD['fr'])['render']
     return VD, results
+
+
+def feature_cache_key(video, CP, engine):
+    """What a cached analysis depends on besides the video's name: the frame selection, the shots, the checkpoint, the pixel
+    format and -- for frames with a layout -- where their bytes lie (a dict without one keeps the key it always had)."""
+    key = dict(skip=CP['skip'], read_batch=CP['read_batch'], max_input_d=CP['max_input_d'],
+               frame_count=int(video['frame_count']), shots='net' if video.get('trans_inds') is None else
+               [int(v) for v in video['trans_inds']], weights=getattr(engine, 'weights_id', None),
+               pix_fmt=video.get('pix_fmt') or 'rgb24')
+    if video.get('layout') is not None:
+        key['layout'] = video_layout(video).key()
+    return key
 
 
 def after_ingest(VD, CP, engine, verbose=False):
