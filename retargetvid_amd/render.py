@@ -6,74 +6,17 @@ output size with cv2.resize(INTER_LINEAR) semantics (svc_render_crops_u8, includ
     crops = render.render_video(video, VD)                            # uint8 [fc, fbb_h, fbb_w, 3] RGB
     render.render_video(video, VD, out_size=(1080, 1920), sink=enc)   # enc(chunk [m,1920,1080,3]) in frame order
 
-The frames come from any container the ingest accepts: a host numpy array (gathered into pinned double buffers, H2D on a
-side stream: smartVidCrop._HostFeed), a pinned torch tensor (copied from where it lies), a CUDA tensor (no copy) or an
-on-device generator (synth.LazyBlobVideo: select on the device).  A video dict with pix_fmt='nv12' holds NV12 frames
-(uint8 [n, h * 3 / 2, w]): they are converted inside the render kernels (svc_render_crops_nv12); the crops are RGB / BGR
-either way -- unless out_fmt='nv12' asks for NV12 crops (uint8 [m, oh * 3 / 2, ow], what a hardware encoder takes: BT.601
-limited range, fused into the render kernels, svc_render_crops_u8_to_nv12 / _nv12_to_nv12; half the bytes to copy back).
-The crops come back through pinned double buffers on a
-second side stream, so that the sink consumes chunk c while the device renders chunk c + 1.
-A video dict with layout=dict(pitch=, chroma_offset=, chroma_pitch=) holds its frames as a decoder left them (uint8
-[n, frame_stride]: smartVidCrop.video_layout); they are staged as they are and read through the layout by the kernels
-(svc_render_crops_layout), and the crops are those of the packed pictures."""
+The frames come from any container the ingest accepts, in either pixel format, packed or with a layout (frames.FrameSource
+describes the kinds and reads them: a dict's pix_fmt='nv12' frames are converted inside the render kernels,
+svc_render_crops_nv12, frames with a layout are staged as they are and read through it, svc_render_crops_layout; the crops
+are those of the packed RGB pictures).  The crops are RGB / BGR -- unless out_fmt='nv12' asks for NV12 crops (uint8
+[m, oh * 3 / 2, ow], what a hardware encoder takes: BT.601 limited range, fused into the render kernels,
+svc_render_crops_u8_to_nv12 / _nv12_to_nv12; half the bytes to copy back).  They come back through pinned double buffers on
+a second side stream, so that the sink consumes chunk c while the device renders chunk c + 1."""
 import numpy as np
 
 _MAX_CHUNK = 32
 _RING_BYTES = 96 << 20         # one output slot (device and pinned, two of each per engine): at most this many bytes
-
-
-def _container(video, pix_fmt=None, layout=None):
-    """-> frames, n, h, w (the PICTURE's size), pix_fmt.  The format is the video dict's ('rgb24' when it does not say), or
-    `pix_fmt` for a bare container; a dict's NV12 container is checked against its w, h (smartVidCrop.video_pix_fmt).  A
-    dict with a layout, or a bare container with `layout` (an ops.FrameLayout), holds uint8 [n, frame_stride] frames:
-    _frame_layout gives the checked layout."""
-    layout = _frame_layout(video, pix_fmt, layout)
-    return _layout_container(video, layout) if layout is not None else _packed_container(video, pix_fmt)
-
-
-def _layout_container(video, layout):
-    """_container for uint8 [n, frame_stride] frames of a checked ops.FrameLayout."""
-    frames = video['frames'] if isinstance(video, dict) else video
-    import torch
-    if hasattr(frames, 'select') and not hasattr(frames, 'shape'):
-        raise ValueError('a layout describes frames in memory, not an on-device generator')
-    if not torch.is_tensor(frames):
-        frames = np.asarray(frames)
-    if frames.dtype not in (np.uint8, torch.uint8) or frames.ndim != 2 or int(frames.shape[1]) != layout.frame_stride:
-        raise ValueError('frames with this layout are uint8 [n, %d], not %s %s' % (layout.frame_stride, frames.dtype, tuple(frames.shape)))
-    return frames, int(frames.shape[0]), layout.h, layout.w, layout.pix_fmt
-
-
-def _frame_layout(video, pix_fmt=None, layout=None):
-    """The ops.FrameLayout of a video dict that has one (smartVidCrop.video_layout: checked), else `layout` (a bare container's), else None."""
-    if isinstance(video, dict) and video.get('layout') is not None:
-        from .smartVidCrop import video_layout
-        return video_layout(video if pix_fmt is None else dict(video, pix_fmt=pix_fmt))
-    return layout
-
-
-def _packed_container(video, pix_fmt=None):
-    """_container for packed frames."""
-    frames = video['frames'] if isinstance(video, dict) else video
-    if isinstance(video, dict) and (pix_fmt is not None or video.get('pix_fmt')):
-        from .smartVidCrop import video_pix_fmt
-        pix_fmt = video_pix_fmt(video if pix_fmt is None else dict(video, pix_fmt=pix_fmt))
-    pix_fmt = pix_fmt or 'rgb24'
-    if hasattr(frames, 'pinned') and hasattr(frames, 'rows'):
-        raise ValueError('render_video needs every frame of the video; %s holds only the frames the ingest selected'
-                         % type(frames).__name__)
-    if hasattr(frames, 'select') and not hasattr(frames, 'shape'):              # an on-device generator (synth.LazyBlobVideo)
-        return frames, len(frames), int(frames.h), int(frames.w), pix_fmt
-    import torch
-    from .ops import picture_size
-    if not torch.is_tensor(frames):
-        frames = np.asarray(frames)
-    if pix_fmt == 'rgb24' and (frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype not in (np.uint8, torch.uint8)):
-        raise TypeError('frames must be uint8 [n,h,w,3] RGB')
-    if pix_fmt == 'nv12' and frames.dtype not in (np.uint8, torch.uint8):
-        raise TypeError('nv12 frames must be uint8 [n,h*3/2,w]')
-    return (frames,) + picture_size(frames, pix_fmt) + (pix_fmt,)
 
 
 def check_boxes(bbs, fc, h, w):
@@ -103,12 +46,12 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     out_fmt='nv12': chunks and the returned array are NV12 frames uint8 [m, oh * 3 / 2, ow] (include/svc.h states the formula);
     an odd output size (pass an even out_size), bgr with it, or an unknown format raise ValueError before any device work.
     layout: the ops.FrameLayout of a bare container of uint8 [n, frame_stride] frames (a dict brings its own 'layout')."""
-    layout = _frame_layout(video, pix_fmt, layout)             # (resolved and checked once)
-    frames, n, h, w, pix_fmt = _layout_container(video, layout) if layout is not None else _packed_container(video, pix_fmt)
+    from .frames import FrameSource
+    src = FrameSource.of(video, pix_fmt, layout).whole()       # (resolved and checked once)
     fc = int(VD['fc'])
-    if n < fc:
-        raise ValueError('the container holds %d frames, the video has %d' % (n, fc))
-    bw, bh = check_boxes(VD['bbs_np'][:fc] if fc else np.zeros((0, 4)), fc, h, w)
+    if src.n < fc:
+        raise ValueError('the container holds %d frames, the video has %d' % (src.n, fc))
+    bw, bh = check_boxes(VD['bbs_np'][:fc] if fc else np.zeros((0, 4)), fc, src.h, src.w)
     ow, oh = (bw, bh) if out_size is None else (int(out_size[0]), int(out_size[1]))
     if oh < 1 or ow < 1:
         raise ValueError('output size %s' % (out_size,))
@@ -129,24 +72,8 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     engine = engine or S.get_engine()
     dev = engine.device
     boxes = torch.from_numpy(np.ascontiguousarray(VD['bbs_np'][:fc], np.int32)).to(dev)
-    out = _OutRing(engine, chunk, oh, ow, sink, out_fmt)
-
-    def emit(staged, s):
-        out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr, pix_fmt, layout)
-
-    if hasattr(frames, 'select') and not hasattr(frames, 'shape'):             # on-device generator
-        for s in range(0, fc, chunk):
-            emit(frames.select(range(s, min(fc, s + chunk))).to(dev).contiguous(), s)
-    elif torch.is_tensor(frames) and frames.is_cuda:
-        src = frames if frames.device == dev else frames[:fc].to(dev)
-        src = src.contiguous()                 # (frames with a layout are [n, frame_stride] rows: nothing is repacked)
-        for s in range(0, fc, chunk):
-            emit(src[s:min(fc, s + chunk)], s)
-    else:
-        feed = engine.__dict__.get('_render_feed')
-        if feed is None:
-            feed = engine._render_feed = S._HostFeed(engine)                   # its own staging (the ingest's keeps its size)
-        feed.feed(frames, list(range(fc)), emit)
+    out = _OutRing(engine, chunk, oh, ow, sink, out_fmt, src.pix_fmt, src.layout)
+    src.chunks(engine, fc, chunk, lambda staged, s: out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr))
     out.flush()
     return result
 
@@ -155,10 +82,11 @@ class _OutRing:
     """Two device output slots and two pinned host slots: chunk c is rendered on the caller's stream into device slot c & 1,
     copied D2H on a side stream into pinned slot c & 1, and handed to the sink once the copy of chunk c + 1 is enqueued."""
 
-    def __init__(self, engine, cap, oh, ow, sink, out_fmt='rgb24'):
+    def __init__(self, engine, cap, oh, ow, sink, out_fmt='rgb24', pix_fmt='rgb24', layout=None):
         import torch
         from .ops import frame_shape
         self.engine, self.sink, self.dev, self.out_fmt = engine, sink, engine.device, out_fmt
+        self.pix_fmt, self.layout = pix_fmt, layout             # of the frames that will be pushed
         key = (cap, oh, ow, out_fmt)
         shape = (cap,) + frame_shape(out_fmt, oh, ow)           # slots shaped (and keyed) by the output format
         ring = engine.__dict__.get('_render_ring')
@@ -174,13 +102,13 @@ class _OutRing:
         self.c = 0
         self.pending = None                 # (slot, frames) of the chunk whose D2H is in flight
 
-    def push(self, staged, boxes, bw, bh, bgr, pix_fmt='rgb24', layout=None):
+    def push(self, staged, boxes, bw, bh, bgr):
         m = int(staged.shape[0])
         cap = self.ring['key'][0]
         for s in range(0, m, cap):          # (a host feed stages at most 32 frames, the ring holds `chunk`)
-            self._one(staged[s:s + cap], boxes[s:s + cap], bw, bh, bgr, pix_fmt, layout)
+            self._one(staged[s:s + cap], boxes[s:s + cap], bw, bh, bgr)
 
-    def _one(self, staged, boxes, bw, bh, bgr, pix_fmt='rgb24', layout=None):
+    def _one(self, staged, boxes, bw, bh, bgr):
         import torch
         m = int(staged.shape[0])
         slot = self.c & 1
@@ -189,7 +117,7 @@ class _OutRing:
         if self.used[slot]:
             compute.wait_event(self.copied[slot])           # the device slot's previous D2H has read it
         dst = self.ring['dev'][slot][:m]
-        self.engine._render(staged, boxes, bw, bh, dst, bgr, pix_fmt, self.out_fmt, layout)
+        self.engine._render(staged, boxes, bw, bh, dst, bgr, self.pix_fmt, self.out_fmt, self.layout)
         self.rendered[slot].record(compute)
         with torch.cuda.stream(side):
             side.wait_event(self.rendered[slot])

@@ -194,7 +194,6 @@ class _Lane:
         """The next piece of the current video: down-scaled frames behind the lane's frames, their rows behind its rows."""
         import torch
         v, plan, sc = self.cur, self.cur.plan, self.sched
-        frames = v.video['frames']
         n = plan['n_sel']
         per = max(sc.chunk, min(sc.piece_frames, sc.piece_bytes // max(1, plan['h'] * plan['w'] * 3)))     # (half the bytes as NV12: the same count)
         m = min(per, n - v.pos)
@@ -203,8 +202,7 @@ class _Lane:
         if len(net):
             idx = [plan['true_inds'][j] for j in net]
             with torch.cuda.stream(self.stream):
-                small = S._small_frames(self.eng, frames, idx, plan['sal_h'], plan['sal_w'], self.eng.device, plan['pix_fmt'],
-                                        plan.get('layout'))
+                small = plan['source'].small(self.eng, idx, plan['sal_h'], plan['sal_w'])
                 self.small[self.frames_in:self.frames_in + len(net)].copy_(small)
             self.row_of_frame[self.frames_in:self.frames_in + len(net)] = v.row0 + net
             self.frames_in += len(net)
@@ -499,8 +497,8 @@ class JobScheduler:
                         v = self.videos[i]() if callable(self.videos[i]) else self.videos[i]
                         shots = None
                         if v.get('trans_inds') is None:
-                            shots = S.detect_shots(v['frames'], v['fr'], self.CP, net=net, engine=net.eng, trans_threshold=S.TRANS_THRESHOLD,
-                                                   pix_fmt=S.video_pix_fmt(v), layout=S.video_layout(v))
+                            shots = S.detect_shots(S.FrameSource.of(v), v['fr'], self.CP, net=net, engine=net.eng,
+                                                   trans_threshold=S.TRANS_THRESHOLD)
                         else:
                             st.synchronize()                  # whatever the callable enqueued is done before a lane reads the frames
                         self._planned[i] = (v, shots)

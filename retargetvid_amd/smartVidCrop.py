@@ -22,6 +22,7 @@ TransNetV1; both stay outside this package.  ``video_path`` is therefore either 
 with fr, frame_count, w, h, frames [RGB uint8], trans_inds) or that dict itself.
 A dict with ``pix_fmt='nv12'`` holds its frames as uint8 [n, h * 3 / 2, w] (what decoders hand out; w, h = the picture's
 size): they are converted on the device inside the down-scale and the renderer, with the results of the converted RGB frames.
+What may hold the frames, and how each kind of container is read, is stated once, on frames.FrameSource.
 Failures raise exceptions; nothing blocks on input() (the reference does at :544-545).
 """
 import math
@@ -33,6 +34,7 @@ import time
 import numpy as np
 
 from . import temporal
+from .frames import FrameSource, _HostFeed, device_index, _runs      # (re-exported: tools and tests reach them here)
 
 _ENGINE = None            # module-level singleton like the reference's unisal_model (:77)
 
@@ -261,228 +263,18 @@ def _select_frames_video(n_frames, frame_count, trans_probs, trans_threshold, sk
 
 TRANS_THRESHOLD = 0.1          # smartVidCrop.py:64
 
-_STAGE_BYTES = 96 << 20        # pinned / device staging buffer size of the host-fed ingest (two of each per engine)
-
 
 def video_pix_fmt(video):
-    """The pixel format of a video dict's frames ('rgb24' unless the dict says otherwise), checked WITHOUT any device work:
-    ValueError for an unknown format, an NV12 picture of odd width or height, or an NV12 container whose frames are not
-    uint8 [n, h * 3 / 2, w] for the dict's w, h."""
-    from .ops import frame_shape
-    fmt = video.get('pix_fmt') or 'rgb24'
-    shape = frame_shape(fmt, video['h'], video['w'])
-    if video.get('layout') is not None:
-        video_layout(video)
-    elif fmt != 'rgb24':
-        frames = video['frames']
-        got = getattr(getattr(frames, 'pinned', frames), 'shape', None)       # (an on-device generator has no shape: its select() is trusted)
-        if got is not None and tuple(int(v) for v in got[1:]) != shape:
-            raise ValueError('%s frames of a %d x %d picture are uint8 [n, %s], not %s'
-                             % (fmt, video['w'], video['h'], ', '.join(str(v) for v in shape), tuple(got)))
-    return fmt
+    """The pixel format of a video dict's frames ('rgb24' unless the dict says otherwise), checked WITHOUT any device work
+    (FrameSource.of: ValueError for an unknown format, an NV12 picture of odd size, a container of another shape, a bad layout)."""
+    return FrameSource.of(video).pix_fmt
 
 
 def video_layout(video):
     """The ops.FrameLayout of a video dict that says ``layout=dict(pitch=, chroma_offset=, chroma_pitch=)`` beside its pix_fmt
     (frames as a decoder left them: uint8 [n, frame_stride] on the device, in host memory or pinned), None for a dict without
-    one (packed frames).  Checked WITHOUT any device work: ValueError for a broken rule of ops.frame_layout, a container that
-    is not 2-D, or an on-device generator (.select), which has no bytes to lay out."""
-    lay = video.get('layout')
-    if lay is None:
-        return None
-    from .ops import FrameLayout, frame_layout
-    fmt = video.get('pix_fmt') or 'rgb24'
-    frames = video['frames']
-    got = getattr(getattr(frames, 'pinned', frames), 'shape', None)
-    if got is None:
-        if hasattr(frames, 'select'):
-            raise ValueError('a layout describes frames in memory: %s produces its frames on demand (.select) and takes none'
-                             % type(frames).__name__)
-        got = np.asarray(frames).shape
-    if len(got) != 2:
-        raise ValueError('frames with a layout are uint8 [n, frame_stride], not %s' % (tuple(got),))
-    if isinstance(lay, FrameLayout):
-        lay = dict(pitch=lay.pitch, chroma_offset=lay.chroma_offset, chroma_pitch=lay.chroma_pitch)
-    return frame_layout(fmt, video['h'], video['w'], lay, int(got[1]))
-
-
-class _HostFeed:
-    """Host frames -> saliency-size frames on the device, selection applied BEFORE the copy, with the copies off the
-    critical path: two pinned host buffers and two device buffers per engine, H2D on a side stream, the down-scale
-    (svc_resize_frames_u8) on the caller's stream.  While chunk c is being copied and down-scaled the host gathers
-    chunk c+1 into the other pinned buffer; an event per buffer keeps a pinned slot from being refilled before its
-    copy has run and a device slot from being overwritten before its down-scale has read it.  Replaces the reference's
-    per-frame cv2.resize on the host inside the read loop (smartVidCrop.py:333-335, :633-635) for inputs that live in
-    host memory; the 4K stream of BASELINE config 5 is bound by this copy (24.9 MB per frame over PCIe as RGB, 12.4 MB as
-    NV12: the staging is sized by the frame's bytes, whatever its format)."""
-
-    def __init__(self, engine):
-        import torch
-        self.engine = engine
-        self.dev = engine.device
-        self.copy_stream = torch.cuda.Stream(device=self.dev)
-        self.shape = None
-
-    def _buffers(self, shape):
-        """Staging for frames of `shape` ((h, w, 3) RGB or (h * 3 / 2, w) NV12: the shape tells the format)."""
-        import torch
-        if self.shape != shape:
-            k = max(1, min(32, _STAGE_BYTES // int(np.prod(shape))))
-            self.pinned = [torch.empty((k,) + shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
-            self.staged = [torch.empty((k,) + shape, dtype=torch.uint8, device=self.dev) for _ in range(2)]
-            self.copied = [torch.cuda.Event(), torch.cuda.Event()]       # H2D of the slot has run
-            self.consumed = [torch.cuda.Event(), torch.cuda.Event()]     # the down-scale has read the device slot
-            self.used = [False, False]
-            self.shape, self.k = shape, k
-        return self.k
-
-    def downscale(self, frames, idx, sal_h, sal_w, pix_fmt='rgb24', layout=None):
-        """frames: host frames [n,h,w,3] u8 (pix_fmt='nv12': [n,h*3/2,w]; with a layout: [n, frame_stride], staged as they are
-        and read through the layout on the device, no host repack) -- a numpy array (pageable memory: gathered into
-        the pinned slots by a few threads) or a PINNED torch tensor (copied from where it lies, frame by frame); idx: selected
-        frame numbers.  -> uint8 CUDA tensor [len(idx), sal_h, sal_w, 3] RGB, produced on the caller's current stream."""
-        import torch
-        out = torch.empty((len(idx), sal_h, sal_w, 3), dtype=torch.uint8, device=self.dev)
-
-        def put(staged, s):
-            out[s:s + staged.shape[0]] = self.engine.resize_frames(staged, sal_h, sal_w, pix_fmt, layout)
-        self.feed(frames, idx, put)
-        return out
-
-    def feed(self, frames, idx, consume):
-        """The staging loop behind downscale (and render.render_video): frames idx of a host container reach the device in
-        chunks of at most k frames; consume(staged_chunk, s) enqueues the chunk's device work on the caller's current
-        stream (staged_chunk: uint8 CUDA [m, *frame shape], valid until that work has run; s: position of its first frame in idx)."""
-        import torch
-        shape = tuple(int(v) for v in frames.shape[1:])
-        nbytes = int(np.prod(shape))
-        k = self._buffers(shape)
-        compute = torch.cuda.current_stream(self.dev)
-        direct = torch.is_tensor(frames) and frames.is_pinned()
-        src = frames if direct else (frames.numpy() if torch.is_tensor(frames) else frames)
-        for c, s in enumerate(range(0, len(idx), k)):
-            part = idx[s:s + k]
-            slot = c & 1
-            if self.used[slot] and not direct:
-                self.copied[slot].synchronize()                 # the pinned slot's previous copy has run
-            if not direct:                                      # selection before the copy: only these frames cross PCIe
-                host = self.pinned[slot].numpy()
-                if len(part) > 1 and nbytes >= (1 << 20):       # big frames: the gather itself is the bottleneck (one thread
-                    list(self._pool().map(lambda jf: np.copyto(host[jf[0]], src[jf[1]]), enumerate(part)))   # copies ~10 GB/s)
-                else:
-                    np.take(src, part, axis=0, out=host[:len(part)], mode='clip')
-            with torch.cuda.stream(self.copy_stream):
-                if self.used[slot]:
-                    self.copy_stream.wait_event(self.consumed[slot])    # the device slot's previous reader is done
-                if direct:
-                    if len(part) > 1 and part[-1] - part[0] == len(part) - 1 and all(part[j + 1] == part[j] + 1 for j in range(len(part) - 1)):
-                        self.staged[slot][:len(part)].copy_(src[part[0]:part[0] + len(part)], non_blocking=True)     # a run of consecutive frames: one copy
-                    else:
-                        for j, f in enumerate(part):
-                            self.staged[slot][j].copy_(src[f], non_blocking=True)
-                else:
-                    self.staged[slot][:len(part)].copy_(self.pinned[slot][:len(part)], non_blocking=True)
-                self.copied[slot].record(self.copy_stream)
-            compute.wait_event(self.copied[slot])
-            consume(self.staged[slot][:len(part)], s)
-            self.consumed[slot].record(compute)
-            self.used[slot] = True
-
-    def _pool(self):
-        if getattr(self, '_tp', None) is None:
-            from concurrent.futures import ThreadPoolExecutor
-            self._tp = ThreadPoolExecutor(max_workers=4)
-        return self._tp
-
-
-def device_index(engine, idx, dev=None):
-    """Frame numbers -> int64 CUDA tensor WITHOUT a host-device synchronisation: torch.as_tensor(list, device=...) copies from
-    pageable memory, i.e. waits for everything the stream holds -- once per read batch that is the end of the host's run-ahead
-    (and, with several videos in flight, of their overlap).  An arithmetic progression is generated on the device; any
-    other list travels through a small ring of pinned slots (an event per slot: a slot is not refilled before its copy ran)."""
-    import torch
-    dev = dev or engine.device
-    n = len(idx)
-    if n == 0:
-        return torch.empty((0,), dtype=torch.int64, device=dev)
-    step = int(idx[1]) - int(idx[0]) if n > 1 else 1
-    if step > 0 and all(int(idx[i + 1]) - int(idx[i]) == step for i in range(n - 1)):
-        return torch.arange(int(idx[0]), int(idx[0]) + step * n, step, dtype=torch.int64, device=dev)
-    ring = engine.__dict__.get('_idx_ring')
-    if ring is None or ring['cap'] < n or ring['dev'] != dev:
-        cap = max(4096, n)
-        ring = engine.__dict__['_idx_ring'] = dict(cap=cap, dev=dev, k=0, host=[torch.empty(cap, dtype=torch.int64).pin_memory() for _ in range(4)],
-                                                   ev=[None] * 4)
-    k = ring['k'] = (ring['k'] + 1) & 3
-    if ring['ev'][k] is not None:
-        ring['ev'][k].synchronize()
-    host = ring['host'][k]
-    host[:n] = torch.as_tensor(np.asarray(idx, dtype=np.int64))
-    out = host[:n].to(dev, non_blocking=True)
-    ev = ring['ev'][k] = ring['ev'][k] or torch.cuda.Event()
-    ev.record(torch.cuda.current_stream(dev))
-    return out
-
-
-def _runs(idx):
-    """Frame numbers, in order, as runs with a constant positive step: [(first, count, step)], greedily from the left, so that
-    each run is the strided view frames[first : first + (count - 1) * step + 1 : step].  A frame that continues no run (a
-    repeat, a step backwards, the last one) is a run of one with step 1."""
-    idx = [int(v) for v in idx]
-    runs, s = [], 0
-    while s < len(idx):
-        step = idx[s + 1] - idx[s] if s + 1 < len(idx) else 0
-        e = s + 1
-        while step > 0 and e < len(idx) and idx[e] - idx[e - 1] == step:
-            e += 1
-        runs.append((idx[s], e - s, step if e - s > 1 else 1))
-        s = e
-    return runs
-
-
-def _small_frames(engine, frames, idx, sal_h, sal_w, dev, pix_fmt='rgb24', layout=None):
-    """Frames idx at saliency size (RGB) on the device, whatever the container (CUDA tensor, on-device generator, host array),
-    the video's pixel format and its layout (ops.FrameLayout: the selected [k, frame_stride] rows are read where they lie)."""
-    import torch
-    if layout is not None and torch.is_tensor(frames) and frames.is_cuda:
-        # nothing is gathered: a selection with a constant step (consecutive frames, or every skip-th: what the ingest selects)
-        # is one strided view, read with a frame stride of step surfaces; any other selection is cut into such runs
-        if frames.device != dev:
-            return engine.resize_frames(frames[device_index(engine, idx, frames.device)].to(dev), sal_h, sal_w, pix_fmt, layout)
-        runs = _runs(idx)
-        small = [engine.resize_frames(frames[first:first + (count - 1) * step + 1:step], sal_h, sal_w, pix_fmt,
-                                      layout if step == 1 else layout.every(step)) for first, count, step in runs]
-        return small[0] if len(small) == 1 else torch.cat(small) if small else torch.empty((0, sal_h, sal_w, 3), dtype=torch.uint8, device=dev)
-    if layout is not None and hasattr(frames, 'select') and not torch.is_tensor(frames):
-        raise ValueError('a layout describes frames in memory, not an on-device generator')
-    if torch.is_tensor(frames) and frames.is_cuda:
-        return engine.resize_frames(frames[device_index(engine, idx, frames.device)].to(dev).contiguous(), sal_h, sal_w, pix_fmt)
-    if not torch.is_tensor(frames) and hasattr(frames, 'select'):             # an on-device generator (synth.LazyBlobVideo)
-        if getattr(frames, 'accepts_device_index', False):
-            return engine.resize_frames(frames.select(idx, index=device_index(engine, idx, dev)).to(dev).contiguous(), sal_h, sal_w, pix_fmt)
-        return engine.resize_frames(frames.select(idx).to(dev).contiguous(), sal_h, sal_w, pix_fmt)
-    feed = getattr(engine, '_host_feed', None)
-    if feed is None:
-        feed = engine._host_feed = _HostFeed(engine)
-    if not torch.is_tensor(frames) and hasattr(frames, 'pinned') and hasattr(frames, 'rows'):   # selected frames in pinned host memory (synth.HostSelectedVideo)
-        return feed.downscale(frames.pinned, frames.rows(idx), sal_h, sal_w, pix_fmt, layout)
-    return feed.downscale(_host_frames(frames, pix_fmt, layout), idx, sal_h, sal_w, pix_fmt, layout)
-
-
-def _host_frames(frames, pix_fmt, layout=None):
-    """A host container (numpy array, anything numpy reads, host torch tensor) as an array / tensor of uint8 frames of `pix_fmt`
-    (with a layout: uint8 [n, frame_stride], as they are)."""
-    import torch
-    host = frames if torch.is_tensor(frames) else np.asarray(frames)
-    if layout is not None:
-        if (host.dtype not in (np.uint8, torch.uint8)) or host.ndim != 2 or host.shape[1] != layout.frame_stride:
-            raise TypeError('frames with a layout must be uint8 [n, %d]' % layout.frame_stride)
-    elif pix_fmt == 'nv12':
-        if (host.dtype not in (np.uint8, torch.uint8)) or host.ndim != 3:
-            raise TypeError('nv12 frames must be uint8 [n,h*3/2,w]')
-    elif (host.dtype not in (np.uint8, torch.uint8)) or host.ndim != 4 or host.shape[3] != 3:
-        raise TypeError('frames must be uint8 [n,h,w,3] RGB')
-    return host
+    one (packed frames).  Checked WITHOUT any device work (FrameSource.of)."""
+    return FrameSource.of(video).layout if video.get('layout') is not None else None      # (no layout: nothing else is looked at)
 
 
 def plan_video(video, crop_params, engine=None, shot_net=None, shots=None):
@@ -492,11 +284,10 @@ def plan_video(video, crop_params, engine=None, shot_net=None, shots=None):
     dict has no ``trans_inds`` (device work on the current stream) unless the caller did it already (``shots`` = what
     detect_shots returned for this video: the scheduler's planner thread runs it ahead of the lanes).  Shared by
     ingest_frames (one video at a time) and the multi-video scheduler (retargetvid_amd/scheduler.py)."""
-    fr, frame_count, w, h = video['fr'], int(video['frame_count']), int(video['w']), int(video['h'])
-    layout = video_layout(video)          # (both raise on a bad format / size / container / layout before any device work)
-    pix_fmt = layout.pix_fmt if layout is not None else video_pix_fmt(video)
-    frames = video['frames']              # ndarray / CUDA tensor [n,h,w,3] u8 RGB ([n,h*3/2,w] NV12), or an object with __len__ and .select(idx)
-    n_frames = len(frames)
+    src = FrameSource.of(video)           # (raises on a bad format / size / container / layout before any device work)
+    if src.kind is None:
+        raise TypeError('the video dict has no frames')
+    fr, frame_count, w, h, n_frames = video['fr'], int(video['frame_count']), src.w, src.h, src.n
     dsr = float(max(w, h)) / crop_params['max_input_d']
     sal_h, sal_w = int(h / dsr), int(w / dsr)
     trans_probs = None
@@ -505,8 +296,7 @@ def plan_video(video, crop_params, engine=None, shot_net=None, shots=None):
             if shot_net is None:
                 raise ValueError('the video dict has no trans_inds: pass shot_net= (a transnetv1_handler.ShotTransNet) to run shot '
                                  'detection inside the ingest, as the reference\'s video path does')
-            shots = detect_shots(frames, fr, crop_params, net=shot_net, engine=engine, trans_threshold=TRANS_THRESHOLD, pix_fmt=pix_fmt,
-                                 layout=layout)
+            shots = detect_shots(src, fr, crop_params, net=shot_net, engine=engine, trans_threshold=TRANS_THRESHOLD)
         trans_probs = shots['trans_probs']
         true_inds, map2orig, batches = _select_frames_video(n_frames, frame_count, trans_probs, TRANS_THRESHOLD,
                                                             crop_params['skip'], crop_params['read_batch'])
@@ -543,7 +333,7 @@ def plan_video(video, crop_params, engine=None, shot_net=None, shots=None):
     for first, cnt in batches:
         if cnt:
             zero_map[first + cnt - 1] = True
-    return dict(fr=fr, frame_count=frame_count, w=w, h=h, pix_fmt=pix_fmt, layout=layout, n_frames=n_frames, sal_h=sal_h, sal_w=sal_w, true_inds=true_inds,
+    return dict(fr=fr, frame_count=frame_count, w=w, h=h, source=src, n_frames=n_frames, sal_h=sal_h, sal_w=sal_w, true_inds=true_inds,
                 map2orig=map2orig, batches=batches, seg=seg, seg_sel=seg_sel, n_sel=n_sel, trans_probs=trans_probs,
                 zero_map=zero_map, flags=blend_flags(n_sel, seg_sel) if crop_params['clust_filt'] else None)
 
@@ -575,13 +365,12 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
     are those of the whole-video call.
     The down-scale to saliency size and the UNISAL forward run on the device.  Keeps the
     reference's off-by-one: the last selected frame of each read batch gets an all-zero map.
-    Host frames (ndarray) go through the pinned, double-buffered feed above; CUDA tensors and
-    on-device generators (``.select``) are used where they are."""
+    The frames are read through the plan's FrameSource (frames.py), whatever holds them."""
     import torch
     engine = engine or get_engine()
     t = time.perf_counter()
     plan = plan_video(video, crop_params, engine=engine, shot_net=shot_net)
-    frames, pix_fmt, layout = video['frames'], plan['pix_fmt'], plan['layout']
+    src = plan['source']
     true_inds, batches, seg_sel = plan['true_inds'], plan['batches'], plan['seg_sel']
     sal_h, sal_w = plan['sal_h'], plan['sal_w']
     sc_register_time(t, '_read_shot_det')
@@ -624,7 +413,7 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
             # piece by piece: the tail of a piece follows its network on the stream
             for s0 in range(first, first + cnt - 1, int(stream_batch)):
                 idx = true_inds[s0:min(s0 + int(stream_batch), first + cnt - 1)]
-                smaps[s0:s0 + len(idx)] = engine.saliency(_small_frames(engine, frames, idx, sal_h, sal_w, dev, pix_fmt, layout))
+                smaps[s0:s0 + len(idx)] = engine.saliency(src.small(engine, idx, sal_h, sal_w))
                 feed_tail(s0 + len(idx))
             feed_tail(first + cnt)                    # the batch's last selected frame keeps its all-zero map (the off-by-one)
             continue
@@ -633,7 +422,7 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
             continue
         if cnt > 1:
             idx = true_inds[first:first + cnt - 1]
-            smaps[first:first + cnt - 1] = engine.saliency(_small_frames(engine, frames, idx, sal_h, sal_w, dev, pix_fmt, layout))
+            smaps[first:first + cnt - 1] = engine.saliency(src.small(engine, idx, sal_h, sal_w))
     if pipe is not None:
         for g, x, y in pipe.finish():
             xy_stream[g] = (x, y)
@@ -647,7 +436,7 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
 
 def detect_shots(frames, fr, crop_params=None, net=None, engine=None, trans_threshold=0.1, pix_fmt='rgb24', layout=None):
     """Shot detection of the reference's video path (smartVidCrop.py:248-372, :452-457) on the device: frames
-    [n, h, w, 3] uint8, or [n, h * 3 / 2, w] with pix_fmt='nv12' (CUDA tensor, NumPy / pinned host tensor, or an on-device generator with .select) ->
+    [n, h, w, 3] uint8, or [n, h * 3 / 2, w] with pix_fmt='nv12', in any container FrameSource.of takes, or a FrameSource ->
     dict(trans_probs, segmentation, trans_inds).  layout (an ops.FrameLayout, e.g. video_layout(video)): the frames are uint8
     [n, frame_stride] as a decoder left them and are read where they lie.  `net` is a transnetv1_handler.ShotTransNet (it owns the weights; the
     reference's checkpoint does not ship with it).  The frames are down-scaled to 48 x 27 in read_batch-sized pieces
@@ -656,30 +445,21 @@ def detect_shots(frames, fr, crop_params=None, net=None, engine=None, trans_thre
     last one on the last frame) and trans_inds is consistent with it."""
     import torch
     from . import transnetv1_handler as T
+    src = FrameSource.of(frames, pix_fmt, layout)
+    if src.kind == 'selected':
+        raise ValueError('detect_shots needs every frame of the video; %s holds only the frames the ingest selected'
+                         % type(src.frames).__name__)
     if net is None:
         raise ValueError('detect_shots needs net= (a transnetv1_handler.ShotTransNet holding the weights)')
     CP = crop_params or sc_init_crop_params()
     eng = engine or net.eng
-    n = len(frames)
+    n = src.n
     th, tw = T.ShotTransNetParams.INPUT_HEIGHT, T.ShotTransNetParams.INPUT_WIDTH
     small = torch.empty((n, th, tw, 3), dtype=torch.uint8, device=eng.device)
     step = max(1, int(CP['read_batch']))
     for s0 in range(0, n, step):
-        idx = list(range(s0, min(n, s0 + step)))
-        if layout is not None and not torch.is_tensor(frames) and hasattr(frames, 'select') and not hasattr(frames, 'shape'):
-            raise ValueError('a layout describes frames in memory, not an on-device generator')
-        if torch.is_tensor(frames) and frames.is_cuda and layout is not None:
-            small[s0:s0 + len(idx)] = eng.resize_frames(frames[s0:s0 + len(idx)], th, tw, pix_fmt, layout)      # a view: nothing is copied
-        elif torch.is_tensor(frames) and frames.is_cuda:
-            small[s0:s0 + len(idx)] = eng.resize_frames(frames[s0:s0 + len(idx)].contiguous(), th, tw, pix_fmt)
-        elif not torch.is_tensor(frames) and hasattr(frames, 'select'):
-            small[s0:s0 + len(idx)] = eng.resize_frames(frames.select(idx).to(eng.device).contiguous(), th, tw, pix_fmt)
-        else:
-            feed = getattr(eng, '_host_feed', None)
-            if feed is None:
-                feed = eng._host_feed = _HostFeed(eng)
-            host = frames if torch.is_tensor(frames) else np.asarray(frames)
-            small[s0:s0 + len(idx)] = feed.downscale(host, idx, th, tw, pix_fmt, layout)
+        s1 = min(n, s0 + step)
+        small[s0:s1] = src.small(eng, range(s0, s1), th, tw)
     probs = T.video_transition_probs(net, small, fr, CP['read_batch'])
     seg = np.array(T.predictions_to_scenes(probs, threshold=trans_threshold), dtype=np.int32)
     for i in range(len(seg) - 1):                      # "shot segmentation FIX" (smartVidCrop.py:452-456)
@@ -887,10 +667,8 @@ def feature_cache_key(video, CP, engine):
     format and -- for frames with a layout -- where their bytes lie (a dict without one keeps the key it always had)."""
     key = dict(skip=CP['skip'], read_batch=CP['read_batch'], max_input_d=CP['max_input_d'],
                frame_count=int(video['frame_count']), shots='net' if video.get('trans_inds') is None else
-               [int(v) for v in video['trans_inds']], weights=getattr(engine, 'weights_id', None),
-               pix_fmt=video.get('pix_fmt') or 'rgb24')
-    if video.get('layout') is not None:
-        key['layout'] = video_layout(video).key()
+               [int(v) for v in video['trans_inds']], weights=getattr(engine, 'weights_id', None))
+    key.update(FrameSource.of(video).key())
     return key
 
 

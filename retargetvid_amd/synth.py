@@ -69,7 +69,7 @@ class LazyBlobVideo:
     def __len__(self):
         return self.n
 
-    accepts_device_index = True        # select(idx, index=<CUDA int64 tensor>): smartVidCrop._small_frames passes its own
+    accepts_device_index = True        # select(idx, index=<CUDA int64 tensor>): frames.FrameSource.small passes its own
 
     def select(self, idx, index=None):
         """index: the frame numbers as a CUDA tensor, if the caller has them there already (no host-device copy here)."""

@@ -308,7 +308,7 @@ def test_end_to_end_equals_the_packed_video(engine, synthetic_sd):
 
 
 def test_selected_frames_of_a_device_container_are_read_where_they_lie(engine):
-    """_small_frames on a CUDA container: consecutive frames, every k-th frame (one strided view, frames k surfaces apart) and
+    """FrameSource.small on a CUDA container: consecutive frames, every k-th frame (one strided view, frames k surfaces apart) and
     an irregular selection (cut into such runs) give the packed container's bytes, and nothing is gathered: the down-scale is
     handed views of the container itself."""
     packed, pitched = _videos()
@@ -322,10 +322,10 @@ def test_selected_frames_of_a_device_container_are_read_where_they_lie(engine):
         seen.append(lo <= frames.data_ptr() < hi)
         return real(frames, *a, **k)
     for idx in (list(range(4, 20)), list(range(1, 30, 6)), [0], [29], [0, 1, 2, 7, 12, 17, 18, 29], [5, 3, 1], [2, 2, 9]):
-        want = S._small_frames(engine, d_packed, idx, 140, 250, engine.device, 'nv12')
+        want = S.FrameSource.of(d_packed, 'nv12').small(engine, idx, 140, 250)
         engine.resize_frames = spy
         try:
-            got = S._small_frames(engine, d_pitched, idx, 140, 250, engine.device, 'nv12', L)
+            got = S.FrameSource.of(d_pitched, 'nv12', L).small(engine, idx, 140, 250)
         finally:
             del engine.resize_frames
         assert got.shape == want.shape and torch.equal(got, want), idx

@@ -340,7 +340,7 @@ def test_frame_numbers_reach_the_device_without_a_synchronising_copy(engine):
         assert got.dtype == torch.int64 and got.is_cuda and got.cpu().tolist() == list(idx)
     frames = torch.from_numpy(synth.blob_frames(24, 90, 160, seed=5)).cuda()
     idx = [0, 6, 7, 8, 14, 23]
-    small = S._small_frames(engine, frames, idx, 45, 80, engine.device)
+    small = S.FrameSource.of(frames).small(engine, idx, 45, 80)
     assert torch.equal(small, engine.resize_frames(frames[idx].contiguous(), 45, 80))
     v = synth.LazyBlobVideo(40, 90, 160, seed=2)
     assert torch.equal(v.select(idx), v.select(idx, index=S.device_index(engine, idx)))

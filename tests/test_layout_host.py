@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from retargetvid_amd import _lib, ops, render, smartVidCrop as S
+from retargetvid_amd.frames import FrameSource
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H, W = 36, 64
@@ -88,7 +89,7 @@ def test_every_kth_frame_is_a_layout_too():
     ([3, 9], [(3, 2, 6)]),
 ])
 def test_a_selection_is_cut_into_strided_runs(idx, runs):
-    """smartVidCrop._runs: what _small_frames reads from a device container, as views -- every run restores its frames in order."""
+    """smartVidCrop._runs: what FrameSource.small reads from a device container, as views -- every run restores its frames in order."""
     assert S._runs(idx) == runs
     assert S._runs(np.array(idx, np.int64)) == runs
     frames = np.arange(40)
@@ -155,6 +156,10 @@ def test_the_launchers_refuse_a_bad_layout_without_a_device():
     assert rc == -1 and 'unknown out_fmt 2' in lib.svc_last_error().decode()
 
 
+def _nhwf(src):
+    return src.n, src.h, src.w, src.pix_fmt
+
+
 def test_the_video_dict_carries_the_layout():
     v = _nv12_dict()
     assert S.video_pix_fmt(v) == 'nv12'
@@ -162,14 +167,14 @@ def test_the_video_dict_carries_the_layout():
     assert L == ops.frame_layout('nv12', H, W, dict(pitch=128, chroma_offset=6144, chroma_pitch=128), 9216)
     assert S.video_layout(dict(v, layout=None)) is None and S.video_layout({k: x for k, x in v.items() if k != 'layout'}) is None
     plan = S.plan_video(v, S.sc_init_crop_params())
-    assert plan['layout'] == L and plan['pix_fmt'] == 'nv12' and (plan['h'], plan['w']) == (H, W)
+    assert plan['source'].layout == L and plan['source'].pix_fmt == 'nv12' and (plan['h'], plan['w']) == (H, W)
     packed = dict(v, frames=np.zeros((4, 54, 64), np.uint8), layout=None)
-    assert S.plan_video(packed, S.sc_init_crop_params())['layout'] is None
-    assert render._container(v)[1:] == (4, H, W, 'nv12')
-    assert render._frame_layout(v) == L
+    assert S.plan_video(packed, S.sc_init_crop_params())['source'].layout is None
+    assert _nhwf(FrameSource.of(v)) == (4, H, W, 'nv12')
+    assert FrameSource.of(v).layout == L
     rgb = dict(frames=np.zeros((4, 200 * H), np.uint8), fr=25.0, frame_count=4, w=W, h=H, layout=dict(pitch=200), trans_inds=[0, 4])
-    assert S.video_pix_fmt(rgb) == 'rgb24' and S.plan_video(rgb, S.sc_init_crop_params())['layout'].pitch == 200
-    assert render._container(rgb)[1:] == (4, H, W, 'rgb24')
+    assert S.video_pix_fmt(rgb) == 'rgb24' and S.plan_video(rgb, S.sc_init_crop_params())['source'].layout.pitch == 200
+    assert _nhwf(FrameSource.of(rgb)) == (4, H, W, 'rgb24')
 
 
 def test_the_video_dict_is_refused_before_any_device_work():
@@ -180,7 +185,7 @@ def test_the_video_dict_is_refused_before_any_device_work():
                       (dict(_nv12_dict(), frames=np.zeros((4, 54, 64), np.uint8)), 'are uint8 [n, frame_stride], not (4, 54, 64)'),
                       (dict(frames=np.zeros((4, 200 * H), np.uint8), fr=25.0, frame_count=4, w=W, h=H, trans_inds=[0, 4],
                             layout=dict(pitch=200, chroma_offset=200 * H, chroma_pitch=200)), 'must be 0 for rgb24')):
-        for door in (S.video_pix_fmt, S.video_layout, lambda v: S.plan_video(v, S.sc_init_crop_params()), render._container,
+        for door in (S.video_pix_fmt, S.video_layout, lambda v: S.plan_video(v, S.sc_init_crop_params()), FrameSource.of,
                      lambda v: render.render_video(v, dict(fc=0, bbs_np=np.zeros((0, 4), np.int64)))):
             with pytest.raises(ValueError) as e:
                 door(bad)
@@ -194,7 +199,7 @@ def test_the_video_dict_is_refused_before_any_device_work():
 
         def select(self, idx):
             raise AssertionError('no frame may be asked for')
-    for door in (S.video_pix_fmt, lambda v: S.plan_video(v, S.sc_init_crop_params()), render._container):
+    for door in (S.video_pix_fmt, lambda v: S.plan_video(v, S.sc_init_crop_params()), FrameSource.of):
         with pytest.raises(ValueError) as e:
             door(dict(_nv12_dict(), frames=Gen()))
         assert '.select' in str(e.value)

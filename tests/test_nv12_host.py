@@ -5,6 +5,7 @@ import pytest
 
 import nv12_ref
 from retargetvid_amd import ops, render, smartVidCrop as S
+from retargetvid_amd.frames import FrameSource
 
 
 def test_fixed_point_conversion_against_float64_on_all_triples():
@@ -74,11 +75,11 @@ def _video(n=12, h=36, w=64, **kw):
 def test_plan_video_validates_the_format_without_a_gpu():
     CP = S.sc_init_crop_params()
     plan = S.plan_video(_video(), CP)
-    assert plan['pix_fmt'] == 'nv12' and (plan['h'], plan['w']) == (36, 64) and plan['n_frames'] == 12
+    assert plan['source'].pix_fmt == 'nv12' and (plan['h'], plan['w']) == (36, 64) and plan['n_frames'] == 12
     rgb = dict(_video(), frames=np.zeros((12, 36, 64, 3), np.uint8))
     del rgb['pix_fmt']
-    assert S.plan_video(rgb, CP)['pix_fmt'] == 'rgb24'
-    assert S.plan_video(dict(rgb, pix_fmt='rgb24'), CP)['pix_fmt'] == 'rgb24'
+    assert S.plan_video(rgb, CP)['source'].pix_fmt == 'rgb24'
+    assert S.plan_video(dict(rgb, pix_fmt='rgb24'), CP)['source'].pix_fmt == 'rgb24'
     with pytest.raises(ValueError, match='pix_fmt'):
         S.plan_video(_video(pix_fmt='yuv420p'), CP)
     with pytest.raises(ValueError, match='even'):
@@ -109,9 +110,10 @@ def test_render_video_validates_the_format_without_a_gpu():
         render.render_video(np.zeros((3, 54, 64), np.uint8), VD, engine=None, pix_fmt='nv21')
     with pytest.raises(ValueError, match='outside'):           # the window is checked against the PICTURE, not the container's rows
         render.render_video(good, dict(fc=3, bbs_np=np.array([[0, 0, 10, 40]] * 3, np.int64)), engine=None)
-    assert render._container(good)[1:] == (3, 36, 64, 'nv12')
-    assert render._container(np.zeros((3, 54, 64), np.uint8), 'nv12')[1:] == (3, 36, 64, 'nv12')
-    assert render._container(np.zeros((3, 36, 64, 3), np.uint8))[1:] == (3, 36, 64, 'rgb24')
+    nhwf = lambda src: (src.n, src.h, src.w, src.pix_fmt)
+    assert nhwf(FrameSource.of(good)) == (3, 36, 64, 'nv12')
+    assert nhwf(FrameSource.of(np.zeros((3, 54, 64), np.uint8), 'nv12')) == (3, 36, 64, 'nv12')
+    assert nhwf(FrameSource.of(np.zeros((3, 36, 64, 3), np.uint8))) == (3, 36, 64, 'rgb24')
 
 
 def test_frame_shapes():
