@@ -82,7 +82,9 @@ const char *svc_last_error(void);
  * 9 = svc_resize_frames_nv12 and svc_render_crops_nv12 exist (NV12 input).
  * 10 = svc_render_crops_u8_to_nv12 and svc_render_crops_nv12_to_nv12 exist (NV12 output).
  * 11 = svc_debug_run_node (SVC_NODE_*) exists.
- * 12 = SvcFrameLayout, svc_resize_frames_layout and svc_render_crops_layout exist (pitched frames). */
+ * 12 = SvcFrameLayout, svc_resize_frames_layout and svc_render_crops_layout exist (pitched frames).
+ * (12, no bump) svc_render_crops_filter (SVC_FILTER_*) was added without one: no struct and no existing signature changed, and
+ *     a binding finds the entry by its symbol (dlsym), not by the revision. */
 #define SVC_ABI_VERSION 12
 int svc_abi_version(void);
 
@@ -181,6 +183,41 @@ int svc_resize_frames_layout(SvcHandle *h, const uint8_t *frames, const SvcFrame
 int svc_render_crops_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height, int width,
                             const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
                             int flags, void *stream);
+
+/* svc_render_crops_layout with a choice of resampling filter.  Arguments and rules are that entry's: the same layout checks,
+ * out_fmt and flags rules, window rules (origins clamped exactly as there) and read range (only bytes of [frames, frames +
+ * (n - 1) * frame_stride + extent) are loaded).  Packed frames are passed with the packed layout's values.
+ * SVC_FILTER_LINEAR forwards to svc_render_crops_layout: its bytes, its errors.  Any other value but the two below:
+ * SVC_E_INVALID ("unknown filter %d").
+ * SVC_FILTER_LANCZOS: with (x1, y1) the clamped origin of frame f, the RGB crop is bit for bit
+ *   C = PIL.Image.fromarray(frame_rgb[y1:y1+bh, x1:x1+bw]).resize((ow, oh), PIL.Image.LANCZOS)            (Pillow 12.2.0)
+ * an a = 3 windowed sinc whose support grows with the shrink factor (antialiased going down, sharp going up), as two 8-bit
+ * fixed-point passes: the horizontal pass first, then the vertical one, a u8 intermediate clipped to 0..255 between them;
+ * coefficients with 22 fractional bits (normalised in float64, rounded half away from zero), int32 accumulation that starts
+ * from 1 << 21, arithmetic shift by 22, clip to 0..255.  A pass whose input and output sizes are equal is skipped (it runs on
+ * an identity table: the value itself); when both are equal the call is the exact copy of svc_render_crops_layout.  The
+ * filter is cut at the WINDOW's edge, not the frame's (crop first, then resize): pixels outside the window never contribute.
+ * NV12 input and pitched layouts change only where a source pixel comes from: the result is that of the converted, packed RGB
+ * frames.  out_fmt SVC_FMT_RGB24 with SVC_RENDER_BGR gives C[..., ::-1]; SVC_FMT_NV12 gives the forward transform of C stated
+ * at the _to_nv12 entries, unchanged.  No floating point and no global-memory intermediate on the device.
+ * One workgroup renders a band of B output rows of one frame out of LDS (B a multiple of R = 1 | 2 rows for an RGB | NV12
+ * output): B is the largest value <= 32 for which
+ *   2 * span + T(B) * tw + D <= 65536 bytes
+ *   span = 3 bw + 32 rounded up to 16          one staged window row (two are staged at a time)
+ *   tw   = 3 ow rounded up to 16               one row of the horizontally resampled tile
+ *   T(B) = the most window rows the vertical filters of one band of B output rows touch, over the bands of the table:
+ *          about B * bh / oh + 6 * max(1, bh / oh) (Pillow's bounds, cut at the window's edge)
+ *   D    = 3 ow + 16 (RGB output) | 2 * 3 ow + 3 * (ow + 16), every term rounded up to 16 (NV12 output): the linear path's
+ * SVC_E_INVALID, with nothing launched: whatever svc_render_crops_layout rejects (its LDS rule aside); B = R that does not fit
+ * (the message carries the byte count); a table with a coefficient of magnitude >= 2^23 or a row with 255 * sum |coefficient|
+ * + 2^21 >= 2^31 (the sizes in the message; the 24-bit multiplies and Pillow's int32 range: no size is known to break them).
+ * The coefficient tables are built on the host once per handle and (in, out) size of an axis.  Counts under SVC_K_RENDER.
+ * No counterpart in the reference (it never resamples its crops). */
+#define SVC_FILTER_LINEAR  0
+#define SVC_FILTER_LANCZOS 1
+int svc_render_crops_filter(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height, int width,
+                            const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
+                            int filter, int flags, void *stream);
 
 /* frames_nhwc[n][h][w][3] u8 RGB (saliency size, e.g. 140x250) -> maps_nhw[n][h][w] u8.
  * Frame-major output; the reference's [h][w][n] view is a transpose done by the
@@ -316,7 +353,7 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
 #define SVC_K_CORE 9
 #define SVC_K_PRIM 10
 #define SVC_K_FINISH 11
-#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 / _u8_to_nv12 / _nv12_to_nv12 / _layout */
+#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 / _u8_to_nv12 / _nv12_to_nv12 / _layout / _filter */
 #define SVC_K_BORDER 13    /* svc_border_profile_u8 (the fused form, svc_saliency_profile_u8, counts under SVC_K_SMOOTH) */
 #define SVC_K_COUNT 14
 int svc_profile_enable(SvcHandle *h, int kernel_class);

@@ -20,7 +20,7 @@ EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'sv
            'svc_saliency_census_u8', 'svc_transnet_predict_rows', 'svc_transnet_config_get', 'svc_transnet_config_set',
            'svc_render_crops_u8', 'svc_debug_transnet_tap', 'svc_border_profile_u8', 'svc_saliency_profile_u8',
            'svc_resize_frames_nv12', 'svc_render_crops_nv12', 'svc_render_crops_u8_to_nv12', 'svc_render_crops_nv12_to_nv12', 'svc_debug_run_node',
-           'svc_resize_frames_layout', 'svc_render_crops_layout')
+           'svc_resize_frames_layout', 'svc_render_crops_layout', 'svc_render_crops_filter')
 
 
 class SvcParams(ctypes.Structure):
@@ -36,6 +36,7 @@ class SvcTemporalParams(ctypes.Structure):
 
 
 FMT_RGB24, FMT_NV12 = 0, 1          # include/svc.h: SVC_FMT_*
+FILTER_LINEAR, FILTER_LANCZOS = 0, 1    # include/svc.h: SVC_FILTER_*
 
 
 class SvcFrameLayout(ctypes.Structure):
@@ -92,6 +93,7 @@ def load():
     lib.svc_render_crops_nv12_to_nv12.argtypes = lib.svc_render_crops_u8.argtypes
     lib.svc_resize_frames_layout.argtypes = [vp, vp, ctypes.POINTER(SvcFrameLayout), i32, i32, i32, vp, i32, i32, vp]
     lib.svc_render_crops_layout.argtypes = [vp, vp, ctypes.POINTER(SvcFrameLayout), i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
+    lib.svc_render_crops_filter.argtypes = [vp, vp, ctypes.POINTER(SvcFrameLayout), i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp]
     lib.svc_saliency_u8.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.svc_saliency_thresholded_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp]
     lib.svc_threshold_u8.argtypes = [vp, vp, sz, i32, vp]

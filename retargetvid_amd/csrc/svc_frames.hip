@@ -9,12 +9,14 @@
 //     k_render_copy_to_rgb, k_render_copy_to_nv12    the copy's vector kernels, one per sink
 //     k_render_copy_px<Src, Dst>                     the copy for everything they leave
 //     k_render_resize<Src, Dst>                      the resampled crop
+//     k_render_lanczos<Src, Dst>                     the crop resampled as PIL.Image.resize(LANCZOS) does it (no counterpart: svc_render_crops_filter)
 //   SrcNv12          BT.601 conversion fused into both (no counterpart: the reference is handed RGB)
 //   DstNv12          the same crops written as NV12, the forward BT.601 transform fused in (no counterpart: the reference hands RGB to its writer)
 #include <algorithm>
 
 #include "svc_cvlinear.h"
 #include "svc_internal.h"
+#include "svc_lanczos.h"
 
 // --------------------------------------------------------------------------------------
 // loads at arbitrary addresses of a 16-aligned buffer ending at `end`, through aligned 16-byte loads
@@ -690,9 +692,10 @@ __global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict
     Dst::rows_out(lds, dst, ow);
 }
 
+// the argument checks of both render launchers (render_crops, render_crops_lanczos): plain comparisons, before any device work
 template <class Src, class Dst>
-static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, int n, int height,
-                        int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+static int render_args_check(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width,
+                             const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags) {
     if (!h || n < 0 || (n > 0 && (!frames || !boxes || !out)) || !Src::size_ok(height, width) || bw < 1 || bh < 1 ||
         bw > width || bh > height) {                                                       // n = 0: a no-op, null buffers allowed
         svc_set_error("%s: invalid argument%s", name, Src::size_rule());
@@ -706,6 +709,14 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, c
         svc_set_error("%s: %s", name, Dst::flags_rule());
         return SVC_E_INVALID;
     }
+    return SVC_OK;
+}
+
+template <class Src, class Dst>
+static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, int n, int height,
+                        int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    int rc = render_args_check<Src, Dst>(name, h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags);
+    if (rc) return rc;
     const int span_cap = (bw * 3 + 32 + 15) / 16 * 16;
     const size_t lds = 2 * (size_t)span_cap + Dst::lds_bytes(ow);
     const bool copy = oh == bh && ow == bw;
@@ -722,7 +733,7 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, c
     hipStream_t s = (hipStream_t)stream;
     const int *tab = nullptr;
     if (!copy) {
-        int rc = cv_tab(h, bh, bw, oh, ow, &tab);
+        rc = cv_tab(h, bh, bw, oh, ow, &tab);
         if (rc) return rc;
     }
     ProfScope ps(h, SVC_K_RENDER, s);
@@ -741,6 +752,212 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, c
         const dim3 grid((unsigned)(oh / Dst::rows), (unsigned)std::min(n - f0, 65535));
         k_render_resize<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * Dst::frame_bytes(oh, ow), tab, boxes, f0, height, width,
                                                          bh, bw, oh, ow, span_cap, in_end, aligned_in, L);
+        SVC_CHECK_LAUNCH();
+    }
+    return SVC_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// Lanczos path: PIL.Image.resize(LANCZOS) of the window (Pillow's two 8-bit fixed-point passes, svc_lanczos.h builds its tables;
+// no counterpart in the reference, which never resamples its crops).  One workgroup = one frame x a band of B output rows (B a
+// multiple of Dst::rows).  From the vertical bounds it takes the window rows [r_lo, r_hi) that the band's filters touch, stages
+// them LZ_STAGE at a time as RGB bytes (Src::stage_row, as k_render_resize does: NV12 is converted there), resamples every
+// staged row horizontally ONCE into the LDS tile T[r_hi - r_lo][3 ow] u8 (the u8 intermediate of Pillow's two passes; nothing of
+// it goes to global memory), then runs the vertical pass from the tile into the sink's LDS rows, Dst::rows of them at a time,
+// and lets the sink store them (Dst::rows_out).  The filters are cut at the window's edge because the tables are those of a
+// bw x bh picture: a pixel outside the window is never staged.  A pass whose sizes are equal runs on lanczos_tab's identity
+// table (one tap of 1 << 22: the value itself).  Integer arithmetic only: int32 accumulators from 1 << 21, products by
+// __mul24 (the launcher checked |coefficient| < 2^23), arithmetic shift by 22, clamp to 0..255.
+// LDS: LZ_STAGE rows of span_cap bytes | tile_cap rows of tw = 3 ow rounded up to 16 bytes | Dst::lds_bytes(ow).
+// The horizontal tables are read from global memory (every workgroup reads the same few KB: L2 / L1 hits); the vertical
+// coefficients of an output row are the same for the whole workgroup.
+// --------------------------------------------------------------------------------------
+#define LZ_STAGE 2
+
+// clamp(acc >> 22, 0, 255), taken as clamp(acc, 0, 2^30 - 1) >> 22 for the reason given at nv12_rgb
+__device__ __forceinline__ uint8_t lz_u8(int acc) { return (uint8_t)(min(max(acc, 0), (256 << LZ_PREC) - 1) >> LZ_PREC); }
+
+template <class Src, class Dst>
+__global__ __launch_bounds__(256) void k_render_lanczos(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                        const int *__restrict__ hb, const int *__restrict__ hk, int hks,
+                                                        const int *__restrict__ vb, const int *__restrict__ vk, int vks,
+                                                        const int32_t *__restrict__ boxes, int f0, int height, int width, int bh,
+                                                        int bw, int oh, int ow, int B, int span_cap, int tile_cap,
+                                                        const uint8_t *in_end, int vec, const typename Src::lay L) {
+    extern __shared__ __align__(16) uint8_t sm_lz[];
+    const int tw = (ow * 3 + 15) / 16 * 16;
+    uint8_t *tile = sm_lz + LZ_STAGE * span_cap, *lds = tile + tile_cap * tw;
+    const int f = f0 + blockIdx.y, oy0 = blockIdx.x * B, oy1 = min(oh, oy0 + B);
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    const uint8_t *fr = in + f * L.template frame<Src>(height, width);
+    const int r_lo = vb[2 * oy0], nr = min(vb[2 * (oy1 - 1)] + vb[2 * (oy1 - 1) + 1] - r_lo, tile_cap);
+
+    // horizontal pass: window rows r_lo + r .. -> tile rows r ..; a thread owns output columns, three channels of LZ_STAGE rows
+    for (int r = 0; r < nr; r += LZ_STAGE) {
+        if (r) __syncthreads();                                 // the rows staged before have been resampled
+        int sh[LZ_STAGE];
+#pragma unroll
+        for (int s = 0; s < LZ_STAGE; ++s)                      // (r + s < nr is the same for the whole workgroup)
+            sh[s] = r + s < nr ? Src::stage_row(fr, L, height, width, y0 + r_lo + r + s, x0, bw, sm_lz + s * span_cap, span_cap, in_end, vec) : 0;
+        __syncthreads();
+        for (int ox = threadIdx.x; ox < ow; ox += 256) {
+            const int xmin = hb[2 * ox], cnt = hb[2 * ox + 1];
+            const int *k = hk + (size_t)ox * hks;
+            int acc[LZ_STAGE][3];
+#pragma unroll
+            for (int s = 0; s < LZ_STAGE; ++s)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[s][c] = 1 << (LZ_PREC - 1);
+            for (int j = 0; j < cnt; ++j) {
+                const int kj = k[j];
+#pragma unroll
+                for (int s = 0; s < LZ_STAGE; ++s) {            // (a row past nr: whatever the staging row holds, never stored)
+                    const uint8_t *p = sm_lz + s * span_cap + sh[s] + (xmin + j) * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc[s][c] += __mul24((int)p[c], kj);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < LZ_STAGE; ++s)
+                if (r + s < nr) {
+                    uint8_t *t = tile + (r + s) * tw + ox * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) t[c] = lz_u8(acc[s][c]);
+                }
+        }
+    }
+    __syncthreads();
+
+    // vertical pass: a thread owns four consecutive bytes of the output row (one dword of every tile row it taps)
+    const int nb = ow * 3, nd = (nb + 3) >> 2, tw4 = tw >> 2;
+    uint8_t *dst[Dst::out_rows];
+    for (int oy = oy0; oy < oy1; oy += Dst::rows) {
+        if (oy > oy0) __syncthreads();                          // the sink has stored the rows before
+        Dst::dst_rows(out, blockIdx.y, oh, ow, oy / Dst::rows, dst);
+#pragma unroll
+        for (int r = 0; r < Dst::rows; ++r) {
+            const int ymin = vb[2 * (oy + r)], cnt = vb[2 * (oy + r) + 1];
+            const int *k = vk + (size_t)(oy + r) * vks;
+            const uint32_t *t = (const uint32_t *)(tile + (ymin - r_lo) * tw);
+            uint8_t *orow = Dst::rgb_row(lds, dst, ow, r);
+            for (int d = threadIdx.x; d < nd; d += 256) {
+                int acc[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] = 1 << (LZ_PREC - 1);
+                for (int j = 0; j < cnt; ++j) {
+                    const uint32_t v = t[j * tw4 + d];
+                    const int kj = k[j];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[e] += __mul24((int)((v >> (8 * e)) & 0xffu), kj);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int b = 4 * d + e, c = b % 3;
+                    if (b < nb) orow[Dst::bgr ? b + 2 - 2 * c : b] = lz_u8(acc[e]);      // R and B swapped on the way out
+                }
+            }
+        }
+        __syncthreads();
+        Dst::rows_out(lds, dst, ow);
+    }
+}
+
+// The LANCZOS table of one axis, in -> out, built once per handle and size pair and checked on the host:
+//   every |coefficient| < 2^23                 __mul24 is exact
+//   255 * sum |coefficient| + 2^21 < 2^31      no accumulator leaves int32 (Pillow's own range)
+static int lz_tab(const char *name, SvcHandle *h, int in_size, int out_size, ResampleTab **out) {
+    auto key = std::make_pair(in_size, out_size);
+    auto it = h->lztabs.find(key);
+    if (it == h->lztabs.end()) {
+        ResampleTab t;
+        lanczos_tab(in_size, out_size, t.bounds_host, t.coeff_host, t.ksize);
+        for (int i = 0; i < out_size; ++i) {
+            long long sum = 0;
+            for (int j = 0; j < t.ksize; ++j) {
+                const long long c = std::abs((long long)t.coeff_host[(size_t)i * t.ksize + j]);
+                if (c >= (1ll << 23)) {
+                    svc_set_error("%s: LANCZOS table %d -> %d has a coefficient of magnitude %lld (>= 2^23)", name, in_size, out_size, c);
+                    return SVC_E_INVALID;
+                }
+                sum += c;
+            }
+            if (255 * sum + (1ll << (LZ_PREC - 1)) >= (1ll << 31)) {
+                svc_set_error("%s: LANCZOS table %d -> %d: 255 * %lld + 2^21 leaves int32", name, in_size, out_size, sum);
+                return SVC_E_INVALID;
+            }
+        }
+        it = h->lztabs.emplace(key, std::move(t)).first;
+    }
+    *out = &it->second;
+    return SVC_OK;
+}
+static int lz_upload(ResampleTab &t) {
+    if (t.coeff.p) return SVC_OK;
+    int rc = t.bounds.ensure(t.bounds_host.size() * 4);
+    if (rc) return rc;
+    SVC_HIP(hipMemcpy(t.bounds.p, t.bounds_host.data(), t.bounds_host.size() * 4, hipMemcpyHostToDevice));
+    DevBuf c;
+    rc = c.ensure(t.coeff_host.size() * 4);
+    if (rc) return rc;
+    SVC_HIP(hipMemcpy(c.p, t.coeff_host.data(), t.coeff_host.size() * 4, hipMemcpyHostToDevice));
+    t.coeff = c;
+    std::vector<int>().swap(t.coeff_host);
+    return SVC_OK;
+}
+
+// the most window rows a band of B output rows touches (the tile's height), from the vertical bounds
+static int lz_tile_rows(const std::vector<int> &vb, int oh, int B) {
+    int cap = 0;
+    for (int y0 = 0; y0 < oh; y0 += B) {
+        int lo = INT32_MAX, hi = 0;
+        for (int y = y0; y < std::min(oh, y0 + B); ++y) {
+            lo = std::min(lo, vb[2 * y]);
+            hi = std::max(hi, vb[2 * y] + vb[2 * y + 1]);
+        }
+        cap = std::max(cap, hi - lo);
+    }
+    return cap;
+}
+
+// render_crops with the Lanczos filter.  The band: the largest B <= 32 (a multiple of Dst::rows) whose LDS fits in 64 KiB
+// (include/svc.h states the formula).
+template <class Src, class Dst>
+static int render_crops_lanczos(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, int n, int height,
+                                int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+    int rc = render_args_check<Src, Dst>(name, h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags);
+    if (rc) return rc;
+    if (oh == bh && ow == bw)                               // both passes skipped: the exact copy
+        return render_crops<Src, Dst>(name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    ResampleTab *ht = nullptr, *vt = nullptr;
+    if ((rc = lz_tab(name, h, bw, ow, &ht)) || (rc = lz_tab(name, h, bh, oh, &vt))) return rc;
+    const int span_cap = (bw * 3 + 32 + 15) / 16 * 16, tw = (ow * 3 + 15) / 16 * 16;
+    const size_t fixed = (size_t)LZ_STAGE * span_cap + Dst::lds_bytes(ow);
+    int B = std::min(32, (oh + Dst::rows - 1) / Dst::rows * Dst::rows) / Dst::rows * Dst::rows, tile_cap = 0;
+    size_t lds = 0;
+    for (;; B -= Dst::rows) {
+        tile_cap = lz_tile_rows(vt->bounds_host, oh, B);
+        lds = fixed + (size_t)tile_cap * tw;
+        if (lds <= 65536) break;
+        if (B == Dst::rows) {
+            svc_set_error("%s: window %dx%d -> %dx%d (lanczos) needs %zu bytes of LDS per %s (> 64 KiB)", name, bw, bh, ow, oh, lds,
+                          Dst::rows == 1 ? "output row" : "pair of output rows");
+            return SVC_E_INVALID;
+        }
+    }
+    if (n == 0) return SVC_OK;
+    SVC_HIP(hipSetDevice(h->device));
+    if ((rc = lz_upload(*ht)) || (rc = lz_upload(*vt))) return rc;
+    const uint8_t *in_end = frames + (size_t)(n - 1) * L.template frame<Src>(height, width) + Src::extent(L, height, width);
+    const int vec = ((uintptr_t)frames & 15) == 0 && Src::vec_ok(L);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(h, SVC_K_RENDER, s);
+    for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
+        const dim3 grid((unsigned)((oh + B - 1) / B), (unsigned)std::min(n - f0, 65535));
+        k_render_lanczos<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * Dst::frame_bytes(oh, ow), (const int *)ht->bounds.p,
+                                                          (const int *)ht->coeff.p, ht->ksize, (const int *)vt->bounds.p,
+                                                          (const int *)vt->coeff.p, vt->ksize, boxes, f0, height, width, bh, bw, oh, ow,
+                                                          B, span_cap, tile_cap, in_end, vec, L);
         SVC_CHECK_LAUNCH();
     }
     return SVC_OK;
@@ -861,4 +1078,37 @@ extern "C" int svc_render_crops_layout(SvcHandle *h, const uint8_t *frames, cons
         return SVC_E_INVALID;
     }
     return render_crops_fmt(name, layout->pix_fmt, out_fmt == SVC_FMT_NV12, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+}
+
+// --------------------------------------------------------------------------------------
+// svc_render_crops_layout with a choice of filter (include/svc.h).  The Lanczos kernels exist for the Pitched layouts only, 2
+// sources x 3 sinks: packed frames arrive as the packed layout's values.  profiles/pitched_frames.json measured that policy
+// within 4 % of the compile-time packed one on the linear kernels; six more instances would buy nothing that has been measured.
+// --------------------------------------------------------------------------------------
+extern "C" int svc_render_crops_filter(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height, int width,
+                                       const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
+                                       int filter, int flags, void *stream) {
+    const char *name = "svc_render_crops_filter";
+    if (filter == SVC_FILTER_LINEAR)
+        return svc_render_crops_layout(h, frames, layout, n, height, width, boxes, bw, bh, out, out_fmt, oh, ow, flags, stream);
+    if (filter != SVC_FILTER_LANCZOS) {
+        svc_set_error("%s: unknown filter %d (SVC_FILTER_LINEAR or SVC_FILTER_LANCZOS)", name, filter);
+        return SVC_E_INVALID;
+    }
+    Pitched L;
+    int rc = layout_check(name, layout, n, height, width, L);
+    if (rc) return rc;
+    if (out_fmt != SVC_FMT_RGB24 && out_fmt != SVC_FMT_NV12) {
+        svc_set_error("%s: unknown out_fmt %d (SVC_FMT_RGB24 or SVC_FMT_NV12)", name, out_fmt);
+        return SVC_E_INVALID;
+    }
+    const bool nv12 = layout->pix_fmt == SVC_FMT_NV12;
+    if (out_fmt == SVC_FMT_NV12)
+        return (nv12 ? render_crops_lanczos<SrcNv12<Pitched>, DstNv12> : render_crops_lanczos<SrcRgb<Pitched>, DstNv12>)(
+            name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    if (flags & SVC_RENDER_BGR)
+        return (nv12 ? render_crops_lanczos<SrcNv12<Pitched>, DstRgb<true>> : render_crops_lanczos<SrcRgb<Pitched>, DstRgb<true>>)(
+            name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return (nv12 ? render_crops_lanczos<SrcNv12<Pitched>, DstRgb<false>> : render_crops_lanczos<SrcRgb<Pitched>, DstRgb<false>>)(
+        name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }

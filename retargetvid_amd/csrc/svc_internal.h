@@ -116,6 +116,7 @@ struct ResampleTab {
     DevBuf coeff;     // int32[out][ksize]
     int max_span = 0; // max over blocks of rows spanned (host-computed helper)
     std::vector<int> bounds_host;
+    std::vector<int> coeff_host;      // until the first upload (a table is built and checked on the host before any device work)
 };
 
 struct NetPlan;     // svc_net.hip
@@ -130,6 +131,8 @@ struct SvcHandle {
     NetPlan *plan = nullptr;
     // ingest resize tables keyed by (in_h, in_w, out_h, out_w)
     std::map<std::tuple<int, int, int, int>, DevBuf> cvtabs;
+    // the renderer's LANCZOS tables keyed by the (in, out) size of one axis (svc_frames.hip: lz_tab; never rewritten)
+    std::map<std::pair<int, int>, ResampleTab> lztabs;
     // tail workspace (svc_tail.hip)
     DevBuf tail_ws;
     DevBuf tail_offsets;     // ring-walk offset table

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "svc_internal.h"
+#include "svc_lanczos.h"
 #include "svc_x3.h"
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -78,7 +79,6 @@ extern "C" int svc_abi_version(void) { return SVC_ABI_VERSION; }
 // --------------------------------------------------------------------------------------
 // K0: Pillow LANCZOS (two 8-bit fixed-point passes) + /255 + normalise (via LUT) -> NHWC fp32
 // --------------------------------------------------------------------------------------
-#define LZ_PREC 22
 // One workgroup = one frame x rows_per_block output rows.  The input rows it needs, the horizontal
 // coefficients and the normalisation LUT are staged in LDS first (coalesced), so both passes run
 // out of LDS.  LDS layout: in_s[in_cap][w*3] u8 | tile[tile_cap][NW*3] u8 | hk[NW][hks] i32 | lut[768] f32
@@ -128,48 +128,6 @@ __global__ __launch_bounds__(256) void k_lanczos_norm(
             for (int j = 0; j < cnt; ++j) acc += __mul24((int)p[j * rowlen], k[j]);
             dst[(size_t)(y - y0) * rowlen + i] = lc[min(max(acc >> LZ_PREC, 0), 255)];
         }
-    }
-}
-
-static double lz_sinc(double x) {
-    if (x == 0.0) return 1.0;
-    x *= M_PI;
-    return sin(x) / x;
-}
-static double lz_filter(double x) { return (-3.0 <= x && x < 3.0) ? lz_sinc(x) * lz_sinc(x / 3.0) : 0.0; }
-
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc.  Identity table when sizes match
-// (Pillow skips that pass).
-static void lanczos_tab(int in_size, int out_size, std::vector<int> &bounds, std::vector<int> &coef, int &ksize) {
-    bounds.assign(2 * out_size, 0);
-    if (in_size == out_size) {
-        ksize = 1;
-        coef.assign(out_size, 1 << LZ_PREC);
-        for (int i = 0; i < out_size; ++i) { bounds[2 * i] = i; bounds[2 * i + 1] = 1; }
-        return;
-    }
-    double scale = (double)in_size / out_size, filterscale = std::max(scale, 1.0);
-    double support = 3.0 * filterscale, ss = 1.0 / filterscale;
-    ksize = (int)ceil(support) * 2 + 1;
-    coef.assign((size_t)out_size * ksize, 0);
-    std::vector<double> k(ksize);
-    for (int xx = 0; xx < out_size; ++xx) {
-        double center = (xx + 0.5) * scale, ww = 0.0;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        for (int x = 0; x < xmax; ++x) {
-            k[x] = lz_filter((x + xmin - center + 0.5) * ss);
-            ww += k[x];
-        }
-        for (int x = 0; x < xmax; ++x) {
-            double v = (ww != 0.0) ? k[x] / ww : k[x];
-            coef[(size_t)xx * ksize + x] = v < 0 ? (int)(-0.5 + v * (1 << LZ_PREC)) : (int)(0.5 + v * (1 << LZ_PREC));
-        }
-        bounds[2 * xx] = xmin;
-        bounds[2 * xx + 1] = xmax;
     }
 }
 
@@ -1446,6 +1404,8 @@ int svc_net_release(SvcHandle *h) {
     }
     for (auto &kv : h->cvtabs) kv.second.release();
     h->cvtabs.clear();
+    for (auto &kv : h->lztabs) { kv.second.bounds.release(); kv.second.coeff.release(); }
+    h->lztabs.clear();
     return SVC_OK;
 }
 

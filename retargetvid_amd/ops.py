@@ -33,6 +33,7 @@ def _need_cuda(t, dtype, name):
 RENDER_BGR = 1                       # svc_render_crops_u8 flag (include/svc.h: SVC_RENDER_BGR)
 PIX_FMTS = ('rgb24', 'nv12')         # input pixel formats: uint8 [n,h,w,3] RGB | uint8 [n,h*3/2,w] (include/svc.h: the _nv12 entries)
 OUT_FMTS = ('rgb24', 'nv12')         # the renderer's output formats: the same two shapes (include/svc.h: the _to_nv12 entries)
+INTERPS = ('linear', 'lanczos')      # the renderer's resampling filters (include/svc.h: SVC_FILTER_*, by index)
 RENDER_ENTRIES = {('rgb24', 'rgb24'): 'svc_render_crops_u8', ('nv12', 'rgb24'): 'svc_render_crops_nv12',        # (pix_fmt, out_fmt)
                   ('rgb24', 'nv12'): 'svc_render_crops_u8_to_nv12', ('nv12', 'nv12'): 'svc_render_crops_nv12_to_nv12'}
 
@@ -60,6 +61,13 @@ def out_frame_shape(out_fmt, oh, ow, bgr=False):
         if oh < 2 or ow < 2 or oh % 2 or ow % 2:
             raise ValueError('an nv12 output has even width and height (>= 2), not %d x %d: pass an even out_size' % (ow, oh))
     return frame_shape(out_fmt, oh, ow)
+
+
+def check_interp(interp):
+    """ValueError unless `interp` is one of INTERPS -- what the renderer's doors check before any device work."""
+    if interp not in INTERPS:
+        raise ValueError('unknown interp %r (one of %s)' % (interp, ', '.join(INTERPS)))
+    return interp
 
 
 def picture_size(frames, pix_fmt):
@@ -241,7 +249,7 @@ class Engine:
         return out
 
     # -- rendering ------------------------------------------------------------------------
-    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None, pix_fmt='rgb24', out_fmt='rgb24', layout=None):
+    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None, pix_fmt='rgb24', out_fmt='rgb24', layout=None, interp='linear'):
         """uint8 [n,h,w,3] frames on the device (pix_fmt='nv12': uint8 [n,h*3/2,w], svc_render_crops_nv12; the crops are RGB / BGR
         either way) and int32 [n,4] boxes (x1,y1,x2,y2, one window size for all; a CUDA tensor, or
         host values that are copied over) -> uint8
@@ -250,7 +258,11 @@ class Engine:
         out_fmt='nv12': the crops come out as NV12 frames uint8 [n,oh*3/2,ow] (BT.601 limited range of the RGB crop, fused
         into the kernels: svc_render_crops_u8_to_nv12 / _nv12_to_nv12); oh and ow must be even and bgr unset (ValueError).
         layout (an ops.FrameLayout): frames uint8 [n, frame_stride] as a decoder left them (svc_render_crops_layout); the
-        crops are the packed call's on the packed pictures."""
+        crops are the packed call's on the packed pictures.
+        interp='lanczos': resampled as PIL.Image.resize(LANCZOS) does it instead, bit for bit, window cropped first
+        (svc_render_crops_filter; include/svc.h states the arithmetic); the window size is the exact copy either way.  Any
+        value outside ops.INTERPS: ValueError."""
+        check_interp(interp)
         n = int(frames.shape[0])
         on_dev = torch.is_tensor(boxes) and boxes.is_cuda
         if n:
@@ -268,9 +280,10 @@ class Engine:
             boxes = torch.from_numpy(np.ascontiguousarray(boxes, np.int32)).to(frames.device)
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
-        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt, out_fmt, layout)
+        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt, out_fmt, layout, interp)
 
-    def _render(self, frames, boxes, bw, bh, out, bgr, pix_fmt='rgb24', out_fmt='rgb24', layout=None):
+    def _render(self, frames, boxes, bw, bh, out, bgr, pix_fmt='rgb24', out_fmt='rgb24', layout=None, interp='linear'):
+        check_interp(interp)
         _need_cuda(boxes, torch.int32, 'boxes')
         _need_cuda(out, torch.uint8, 'out')
         if layout is None:
@@ -286,6 +299,12 @@ class Engine:
             assert out.shape[3] == 3
             on, oh, ow = (int(v) for v in out.shape[:3])
         assert tuple(boxes.shape) == (n, 4) and on == n
+        if interp != 'linear':              # one entry for every format and layout: packed frames as the packed layout's values
+            lay = (layout or frame_layout(pix_fmt, h, w)).struct()
+            _lib.check(self.lib.svc_render_crops_filter(self._h, _ptr(frames), ctypes.byref(lay), n, h, w, _ptr(boxes), bw, bh, _ptr(out),
+                                                        OUT_FMTS.index(out_fmt), oh, ow, INTERPS.index(interp),
+                                                        RENDER_BGR if bgr else 0, _stream()))
+            return out
         if layout is not None:
             lay = layout.struct()
             _lib.check(self.lib.svc_render_crops_layout(self._h, _ptr(frames), ctypes.byref(lay), n, h, w, _ptr(boxes), bw, bh, _ptr(out),

@@ -541,7 +541,7 @@ class _LazySmaps(dict):
 def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn='', frames_dir='',
                    temp_path=None, verbose=False, save_vid=True, callback_progress=None,
                    callback_session=None, callback_status=None, copy_sound=False, engine=None, shot_net=None, stream_batch=0,
-                   out_size=None, out_pix_fmt='rgb24'):
+                   out_size=None, out_pix_fmt='rgb24', out_interp='linear'):
     """Saliency -> crop windows for one video.  Returns (VD, smart_crop_results) like the
     reference; VD['bbs'] holds one [x1,y1,x2,y2] per decoded frame.  A video dict without ``trans_inds`` takes the
     reference's video path: ``shot_net`` (transnetv1_handler.ShotTransNet) detects the shots inside the ingest.
@@ -558,7 +558,9 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         NV12 (uint8 [h * 3 / 2, w], render.render_video(out_fmt='nv12'); the size must be even) and the writer is opened as
         fn(final_vid_fn, VD['fr'], size, pix_fmt='nv12') (ingest.write_frames_raw takes it); with the default 'rgb24' the
         call is the three-argument one.  The pickle mode is defined as BGR crops: with 'nv12' it raises ValueError, as does
-        an unknown format, before any work.
+        an unknown format, before any work.  out_interp: the filter out_size is resampled with, 'linear' or 'lanczos'
+        (render.render_video(interp=): PIL.Image.resize LANCZOS of the cropped window, bit for bit); another value raises
+        ValueError before any work.  The pickle mode is native-size BGR and ignores it.
     demo_fn (the five-panel demo) and copy_sound (ffmpeg) with a render raise NotImplementedError."""
     import torch
     sc_init_time()
@@ -571,8 +573,9 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         raise NotImplementedError('the five-panel demo video (cv2 drawing and text) is not rendered by this package; '
                                   'pass demo_fn=\'\'')
     render_pkl = render_writer = False
-    from .ops import out_frame_shape
+    from .ops import check_interp, out_frame_shape
     out_frame_shape(out_pix_fmt, *((2, 2) if out_size is None else (out_size[1], out_size[0])))     # unknown format, odd out_size: ValueError
+    check_interp(out_interp)
     if save_vid and final_vid_fn:
         if copy_sound:
             raise NotImplementedError('copy_sound needs ffmpeg, which is not part of this package; pass copy_sound=False')
@@ -654,7 +657,7 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
                 _video_writer(final_vid_fn, VD['fr'], size, pix_fmt=out_pix_fmt)
             try:
                 render.render_video(video, VD, engine=engine, out_size=size, sink=lambda chunk: [writer.write(f) for f in chunk],
-                                    out_fmt=out_pix_fmt)
+                                    out_fmt=out_pix_fmt, interp=out_interp)
             finally:
                 writer.release()
         sc_register_time(t, 'render')
