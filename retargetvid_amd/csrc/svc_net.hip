@@ -223,6 +223,14 @@ __global__ __launch_bounds__(256) void k_stem_mfma(const float *__restrict__ X, 
 // the 32 MFMA columns are padding), horizontal pass 10, source words 6, workgroup start-up 23.  A persistent variant (one
 // workgroup walking a run of tiles with the next tile's loads in flight) was slower (143 us): fewer independent workgroups
 // hide less.
+// Since then the two resampling passes and the prologue do less per sample (profiles/front_passes.json: 104 -> 93 us alone, 113 ->
+// 103 with four batches in flight): the vertical pass keeps a column's source bytes in a register window and takes a row's
+// coefficients through the scalar path (one new LDS byte per output sample instead of eight, plus vb and two coefficient rows);
+// what a patch column needs -- place, first source byte, coefficients -- is a record of the plan, two 16-byte loads per lane
+// instead of nine gathered words; both passes sum seven taps (a table is never wider here, the eighth coefficient was always 0);
+// features.0 leaves out the MFMA whose two taps are both padding.  Tried beside them and not kept: several rows of the horizontal
+// pass in flight (no gain), the features.0 bias loads ahead of the tile loop (spills at 128 registers), the two double-tile waves
+// rotating with the workgroup (slower).
 // --------------------------------------------------------------------------------------
 #define FR_TH 8
 #define FR_TW 16
@@ -236,11 +244,23 @@ __global__ __launch_bounds__(256) void k_stem_mfma(const float *__restrict__ X, 
 
 #define FR_MAXT 32                  // tiles per frame side (NH, NW <= 416: at most 26 x 13)
 
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(4))) const i32x8 FrVRec;      // a vertical record, read from constant memory: a uniform index makes it one scalar load
+
+// acc + byte * coef on the full-rate 24-bit multiplier, the coefficient in a scalar register (|coefficient| < 2^23).  Written out
+// because the bytes of the vertical window are carried round a loop, where the compiler no longer knows them to be bytes and
+// takes the quarter-rate 32-bit multiply for __mul24.
+__device__ static inline int mad24_s(int byte, int coef, int acc) {
+    int r;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(byte), "s"(coef), "v"(acc));
+    return r;
+}
+
 struct FrontArgs {
     const uint8_t *frames;          // [n][h][w][3]
     int h, w, NH, NW, OH, OW, tiles_x, tiles_y;
-    const int *hb, *hk, *vb, *vk;   // LANCZOS tables (lanczos_tab); coefficient rows are zero-padded to hks / vks
-    int hks, vks;
+    const int4 *ht;                 // [tiles_x][2][128] column records (build_plan): a patch column-channel's place and seven coefficients, in lane order
+    const int *vt;                  // [NH][8] vertical records (build_plan): a row's seven coefficients, then its first source row
     const float *lut;               // [3][256]
     const float *Wstem, *bstem;     // [32 out][32 taps], [32]
     const float *Wstem_l, *Wp_l;    // lane-order copies of Wstem and Wp (k_lane_weights): a wave's weight load is one contiguous KB
@@ -260,12 +280,12 @@ __host__ __device__ static inline int front_in_offset(int nr_cap, int nc_cap) {
     return (nr_cap * (front_src_stride(nc_cap) + FR_PRS) + 15) & ~15;
 }
 // LDS (round 4): 35 KB and <= 128 registers = FOUR workgroups per CU (rounds 2-3: 52 KB, three).  [input patch 9.4 KB][S 25.9 KB]:
-// the source patch, the horizontal-pass rows, the vertical coefficients and the LUT are dead when features.0 starts writing S,
+// the source patch, the horizontal-pass rows and the LUT are dead when features.0 starts writing S,
 // so they live INSIDE S's array; D is written over S behind a barrier (the depthwise outputs wait in registers); the three
 // layers' weights are not parked in LDS but requested from L2 one phase before their use.
 #define FR_IN_BYTES (FR_PR * FR_PRS * 4)
 #define FR_SONLY_BYTES (FR_NPX * FR_ES * 4)
-static inline int front_small_bytes(int nr_cap, int nc_cap) { return front_in_offset(nr_cap, nc_cap) + (FR_PR * 8 + 24 + 768) * 4; }
+static inline int front_small_bytes(int nr_cap, int nc_cap) { return front_in_offset(nr_cap, nc_cap) + 768 * 4; }
 static inline int front_lds_bytes() { return FR_IN_BYTES + FR_SONLY_BYTES; }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_front(const FrontArgs A) {       // <= 128 registers: four workgroups per CU
@@ -275,20 +295,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     const int tx = bid % A.tiles_x;
     bid /= A.tiles_x;
     const int ty = bid % A.tiles_y, f = bid / A.tiles_y;
-    const int oy0 = ty * FR_TH, ox0 = tx * FR_TW, py0 = 2 * oy0 - 3, px0 = 2 * ox0 - 3;
+    const int oy0 = ty * FR_TH, ox0 = tx * FR_TW, py0 = 2 * oy0 - 3;
     const int srs = front_src_stride(A.nc_cap);
     float *IN_s = (float *)sm_fr;                               // [FR_PR][FR_PRS]  normalised input patch, 0 outside the image
     float *S = (float *)(sm_fr + FR_IN_BYTES);                  // [180][FR_ES]
-    uint8_t *src_s = (uint8_t *)S;                              // [nr_cap][srs]      source patch (rows start at an aligned word): inside S's array, like the next four
+    uint8_t *src_s = (uint8_t *)S;                              // [nr_cap][srs]      source patch (rows start at an aligned word): inside S's array, like the next two
     uint8_t *tile_s = src_s + A.nr_cap * srs;                   // [nr_cap][FR_PRS]   after the horizontal pass
-    int *vk_s = (int *)(src_s + front_in_offset(A.nr_cap, A.nc_cap));   // [FR_PR][8]  vertical coefficient rows
-    int *vb_s = vk_s + FR_PR * 8;                               // [FR_PR]            first source row of every patch row
-    float *lut_s = (float *)(vb_s + 24);                        // [768]
+    float *lut_s = (float *)(src_s + front_in_offset(A.nr_cap, A.nc_cap));     // [768]
     float *D = S;                                               // [128][FR_ES]  over S once every depthwise tap has been read
-    // 1. the source patch (aligned words), coefficients and LUT are requested here, before anything waits
+    // 1. the source patch (aligned words), the column's record and the LUT are requested here, before anything waits
     const int c4 = tid & 7;
-    const int ya = max(py0, 0), yb = min(py0 + FR_PR, A.NH), xa = max(px0, 0), xb = min(px0 + FR_PC, A.NW);
-    const int r_lo = A.row_lo[ty], nr = A.row_n[ty], c_lo = A.col_lo[tx], nc3 = A.col_n[tx] * 3, ncol3 = (xb - xa) * 3;
+    const int ya = max(py0, 0), yb = min(py0 + FR_PR, A.NH);
+    const int r_lo = A.row_lo[ty], nr = A.row_n[ty], c_lo = A.col_lo[tx], nc3 = A.col_n[tx] * 3;
     const uintptr_t g0 = (uintptr_t)A.frames + (((size_t)f * A.h + r_lo) * A.w + c_lo) * 3;     // first byte of the patch
     const int rstep = A.w * 3, gm0 = (int)(g0 & 3), rs3 = rstep & 3;
     const int srow = tid >> 5, swi = tid & 31;                  // source words: 8 rows x 32 words per round
@@ -300,22 +318,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         const int nwords = ((int)(ga & 3) + nc3 + 3) >> 2;
         sv[it] = (row < nr && swi < nwords) ? *(const uint32_t *)((ga & ~(uintptr_t)3) + 4 * swi) : 0u;
     }
-    // a thread owns one (column, channel) of the patch in both passes, and every second row
+    // a thread owns one (column, channel) of the patch in both passes: every second row of the horizontal one, half the rows of the vertical one
     const int ci = tid & 127, half = __builtin_amdgcn_readfirstlane(tid >> 7);
-    const bool col_ok = ci < ncol3;
-    const int xi = ci / 3, cc = ci - 3 * xi, x = min(xa + xi, A.NW - 1), pcol = (x - px0) * 3 + cc;
-    const int xmin = A.hb[2 * x];
-    int kh[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) kh[j] = j < A.hks ? A.hk[x * A.hks + j] : 0;
-    int vkv = 0, vbv = 0;
-    if (tid < FR_PR * 8) {
-        const int y = ya + (tid >> 3), j = tid & 7;
-        if (y < yb && j < A.vks) vkv = A.vk[y * A.vks + j];
-    } else if (tid < FR_PR * 8 + FR_PR) {
-        const int y = ya + tid - FR_PR * 8;
-        if (y < yb) vbv = A.vb[2 * y];
-    }
+    // the column's record (build_plan): where its source bytes start in a patch row, where it lies in the patch, its coefficients
+    const int4 h0 = A.ht[(tx * 2) * 128 + ci], h1 = A.ht[(tx * 2 + 1) * 128 + ci];
+    const bool col_ok = h0.x < 0;
+    const int poff = h0.x & 255, pcol = (h0.x >> 8) & 127, cc = (h0.x >> 15) & 3, x = (h0.x >> 17) & 1023;
+    const int kh[7] = {h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
     float lv[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) lv[i] = A.lut[tid + 256 * i];
@@ -325,20 +334,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         const int row = srow + 8 * it;
         if (row < nr && swi < (srs >> 2)) ((uint32_t *)src_s)[row * (srs >> 2) + swi] = sv[it];
     }
-    if (tid < FR_PR * 8) vk_s[tid] = vkv;
-    else if (tid < FR_PR * 8 + FR_PR) vb_s[tid - FR_PR * 8] = vbv;
 #pragma unroll
     for (int i = 0; i < 3; ++i) lut_s[tid + 256 * i] = lv[i];
     __syncthreads();
-    // 2. horizontal pass: the column's (at most eight) coefficients are in registers; taps past the end of the row of
-    //    coefficients carry 0 (their bytes are whatever follows in LDS), so the eight reads of a row are independent
+    // 2. horizontal pass: the column's (at most seven) coefficients are in registers; taps past the end of the row of
+    //    coefficients carry 0 (their bytes are whatever follows in LDS), so the seven reads of a row are independent
     if (col_ok) {
-        const uint8_t *p = src_s + (xmin - c_lo) * 3 + cc;
+        const uint8_t *p = src_s + poff;
         for (int row = half; row < nr; row += 2) {
             const uint8_t *q = p + row * srs + ((gm0 + row * rs3) & 3);
             int acc = 1 << (LZ_PREC - 1);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) acc += __mul24((int)q[3 * j], kh[j]);     // |coefficient| < 2^23: the 24-bit multiply is exact and full-rate
+            for (int j = 0; j < 7; ++j) acc += __mul24((int)q[3 * j], kh[j]);     // |coefficient| < 2^23: the 24-bit multiply is exact and full-rate
             tile_s[row * FR_PRS + pcol] = (uint8_t)min(max(acc >> LZ_PREC, 0), 255);
         }
     }
@@ -346,20 +353,48 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 #pragma unroll
     for (int q = 0; q < 4; ++q) wv[q] = *(const float4 *)(A.Wstem_l + (q * 64 + lane) * 4);
     __syncthreads();
-    // 3. vertical pass + normalisation LUT
+    // 3. vertical pass + normalisation LUT.  A thread walks one half of the patch rows (the upper or the lower: uniform in its
+    //    wave) with the seven source bytes of its (column, channel) in registers.  A row's record -- coefficients and first source
+    //    row -- depends on y alone and arrives through the scalar path, the next row's while this one is summed.  The geometries
+    //    that run this kernel never shrink, so the window moves on by 0 or 1 rows per output row (build_plan checks it): one new
+    //    byte per row instead of eight.
     if (col_ok) {
         const float *lc = lut_s + cc * 256;
         const bool dbg_col = A.in_dbg && x >= 2 * ox0 && x < 2 * ox0 + 2 * FR_TW;
-        for (int y = ya + half; y < yb; y += 2) {
-            const int vrow = y - ya;
-            const int4 k0 = *(const int4 *)(vk_s + vrow * 8), k1 = *(const int4 *)(vk_s + vrow * 8 + 4);
-            const uint8_t *q = tile_s + (vb_s[vrow] - r_lo) * FR_PRS + pcol;
-            int acc = 1 << (LZ_PREC - 1);
-            acc += __mul24((int)q[0], k0.x) + __mul24((int)q[FR_PRS], k0.y) + __mul24((int)q[2 * FR_PRS], k0.z) + __mul24((int)q[3 * FR_PRS], k0.w);
-            acc += __mul24((int)q[4 * FR_PRS], k1.x) + __mul24((int)q[5 * FR_PRS], k1.y) + __mul24((int)q[6 * FR_PRS], k1.z) + __mul24((int)q[7 * FR_PRS], k1.w);
-            const float v = lc[min(max(acc >> LZ_PREC, 0), 255)];
-            IN_s[(y - py0) * FR_PRS + pcol] = v;
+        const int ymid = ya + ((yb - ya + 1) >> 1), y0 = half ? ymid : ya, y1 = half ? yb : ymid;
+        const FrVRec *vt = (const FrVRec *)A.vt;
+        const uint8_t *col = tile_s + pcol;
+        float *dst = IN_s + pcol - py0 * FR_PRS;
+        auto emit = [&](int y, float v) {
+            dst[y * FR_PRS] = v;
             if (dbg_col && y >= 2 * oy0 && y < 2 * oy0 + 2 * FR_TH) A.in_dbg[(((size_t)f * A.NH + y) * A.NW + x) * 3 + cc] = v;
+        };
+        if (y0 < y1) {
+            i32x8 rc = vt[y0];
+            int s = rc[7] - r_lo, wd7[7];                      // the window: patch rows s .. s + 6
+#pragma unroll
+            for (int j = 0; j < 7; ++j) wd7[j] = col[(s + j) * FR_PRS];
+            // the sum of the row whose record is in rc; then the window and rc move on to row ynext
+            auto sum_and_advance = [&](int ynext) {
+                const i32x8 nx = vt[min(ynext, A.NH - 1)];
+                const int nb = col[(s + 7) * FR_PRS];          // the byte that enters if the window moves (rows past the patch: any value, its coefficient is 0)
+                int acc = 1 << (LZ_PREC - 1);
+#pragma unroll
+                for (int j = 0; j < 7; ++j) acc = mad24_s(wd7[j], rc[j], acc);
+                const bool adv = nx[7] - r_lo != s;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) wd7[j] = adv ? wd7[j + 1] : wd7[j];
+                wd7[6] = adv ? nb : wd7[6];
+                s += adv;
+                rc = nx;
+                return min(max(acc >> LZ_PREC, 0), 255);
+            };
+            int idx = sum_and_advance(y0 + 1);
+            for (int y = y0; y < y1; ++y) {
+                const float v = lc[idx];
+                idx = sum_and_advance(y + 2);                  // the next row's sum covers the LUT read (past the last row: discarded)
+                emit(y, v);
+            }
         }
     }
     __syncthreads();
@@ -386,8 +421,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[q].x, tp[0], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[q].y, tp[1], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[q].z, tp[2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[q].w, tp[3], acc, 0, 0, 0);
-        }
+            if (q < 3) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[q].w, tp[3], acc, 0, 0, 0);      // q = 3: taps 27 and 31, both padding -- an exact + 0 that
+        }                                                                                              // cannot change acc (never -0: it starts at +0), left out
         if (hp < FR_NPX) {
             const bool in = (unsigned)(oy0 - 1 + hy) < (unsigned)A.OH && (unsigned)(ox0 - 1 + hx) < (unsigned)A.OW;
             float *sp = S + hp * FR_ES + 4 * hh;
@@ -1255,6 +1290,8 @@ struct NetPlan {
     size_t off[B_COUNT + 1];      // per-frame float offsets
     DevBuf ws, fmax, lut, gauss;
     DevBuf hb, hk, vb, vk;
+    DevBuf fr_vt;                                             // k_front: [NH][8] vertical records (seven coefficients, first source row)
+    DevBuf fr_ht;                                             // k_front: [tile columns][2][128] int4 column records (place in the patch, first source byte, seven coefficients)
     int hks = 0, vks = 0, lz_tile_cap = 0;                    // k_lanczos_norm: source rows one workgroup needs at most
     int fr_nr = 0, fr_nc = 0;                                 // source rows / columns one tile of k_front needs at most
     bool fr_ok = false;                                       // the geometry can run k_front
@@ -1329,7 +1366,8 @@ static int build_plan(SvcHandle *h, int height, int width, int nb) {
     // eight taps per pass) whose source patch is at most 32 rows of 32 words; anything else runs the three kernels.
     p->fr_nr = p->fr_nc = 0;
     const int fty = ceil_div(NH / 2, FR_TH), ftx = ceil_div(NW / 2, FR_TW);
-    p->fr_ok = p->hks <= 8 && p->vks <= 8 && fty <= FR_MAXT && ftx <= FR_MAXT;
+    p->fr_ok = p->hks <= 7 && p->vks <= 7 && fty <= FR_MAXT && ftx <= FR_MAXT;     // (a table's width is odd: at most seven taps either way)
+    for (int y = 1; y < NH && p->fr_ok; ++y) p->fr_ok = vb[2 * y] - vb[2 * (y - 1)] <= 1;  // the vertical window moves by 0 or 1 rows per output row
     for (int t = 0; t < FR_MAXT; ++t) p->fr_row_lo[t] = p->fr_row_n[t] = p->fr_col_lo[t] = p->fr_col_n[t] = 0;
     for (int t = 0; t < fty && p->fr_ok; ++t) {
         const int ya = std::max(2 * t * FR_TH - 3, 0), yb = std::min(2 * t * FR_TH - 3 + FR_PR, NH);
@@ -1352,6 +1390,30 @@ static int build_plan(SvcHandle *h, int height, int width, int nb) {
     SVC_HIP(hipMemcpy(p->hk.p, hk.data(), hk.size() * 4, hipMemcpyHostToDevice));
     SVC_HIP(hipMemcpy(p->vb.p, vb.data(), vb.size() * 4, hipMemcpyHostToDevice));
     SVC_HIP(hipMemcpy(p->vk.p, vk.data(), vk.size() * 4, hipMemcpyHostToDevice));
+    if (p->fr_ok) {
+        std::vector<int> vt((size_t)NH * 8, 0);
+        for (int y = 0; y < NH; ++y) {
+            for (int j = 0; j < p->vks; ++j) vt[y * 8 + j] = vk[(size_t)y * p->vks + j];
+            vt[y * 8 + 7] = vb[2 * y];
+        }
+        if ((rc = p->fr_vt.ensure(vt.size() * 4))) return rc;
+        SVC_HIP(hipMemcpy(p->fr_vt.p, vt.data(), vt.size() * 4, hipMemcpyHostToDevice));
+        // column records: thread ci of a tile in column t owns patch column xa + ci / 3, channel ci % 3.  Word 0: bit 31 = the column
+        // exists, bits 0-7 the first source byte within a patch row, 8-14 the place in the input patch, 15-16 the channel, 17-26 x.
+        std::vector<int> ht((size_t)ftx * 2 * 128 * 4, 0);
+        for (int t = 0; t < ftx; ++t) {
+            const int px0 = 2 * t * FR_TW - 3, xa = std::max(px0, 0), xb = std::min(px0 + FR_PC, NW);
+            for (int ci = 0; ci < (xb - xa) * 3; ++ci) {
+                const int x = xa + ci / 3, cc = ci % 3;
+                const int poff = (hb[2 * x] - p->fr_col_lo[t]) * 3 + cc, pcol = (x - px0) * 3 + cc;
+                int *r0 = &ht[((size_t)(t * 2) * 128 + ci) * 4], *r1 = r0 + 128 * 4;
+                r0[0] = (int)(0x80000000u | (unsigned)poff | (unsigned)pcol << 8 | (unsigned)cc << 15 | (unsigned)x << 17);
+                for (int j = 0; j < p->hks; ++j) (j < 3 ? r0[1 + j] : r1[j - 3]) = hk[(size_t)x * p->hks + j];
+            }
+        }
+        if ((rc = p->fr_ht.ensure(ht.size() * 4))) return rc;
+        SVC_HIP(hipMemcpy(p->fr_ht.p, ht.data(), ht.size() * 4, hipMemcpyHostToDevice));
+    }
     // ToTensor (/255) + Normalize LUT, float32 arithmetic like torchvision
     std::vector<float> lut(3 * 256);
     const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
@@ -1398,7 +1460,7 @@ int svc_net_release(SvcHandle *h) {
     if (h->plan) {
         NetPlan *p = h->plan;
         p->ws.release(); p->fmax.release(); p->lut.release(); p->gauss.release();
-        p->hb.release(); p->hk.release(); p->vb.release(); p->vk.release();
+        p->hb.release(); p->hk.release(); p->vb.release(); p->vk.release(); p->fr_vt.release(); p->fr_ht.release();
         delete p;
         h->plan = nullptr;
     }
@@ -2558,8 +2620,8 @@ static int net_front(SvcHandle *h, hipStream_t s, const uint8_t *frames, int n, 
         FrontArgs A;
         A.frames = frames; A.h = p->h; A.w = p->w; A.NH = NH; A.NW = NW; A.OH = H; A.OW = W;
         A.tiles_x = ceil_div(W, FR_TW); A.tiles_y = ceil_div(H, FR_TH);
-        A.hb = (const int *)p->hb.p; A.hk = (const int *)p->hk.p; A.vb = (const int *)p->vb.p; A.vk = (const int *)p->vk.p;
-        A.hks = p->hks; A.vks = p->vks; A.lut = (const float *)p->lut.p;
+        A.ht = (const int4 *)p->fr_ht.p; A.vt = (const int *)p->fr_vt.p;
+        A.lut = (const float *)p->lut.p;
         A.Wstem = (const float *)h->stem_wt.p; A.bstem = g.stem.b.dev;
         const void *wl;
         RC(weight_copy(h, s, F32_LANES, (const float *)h->stem_wt.p, 32, 32, 32, &wl));
