@@ -84,7 +84,7 @@ const char *svc_last_error(void);
  * 11 = svc_debug_run_node (SVC_NODE_*) exists.
  * 12 = SvcFrameLayout, svc_resize_frames_layout and svc_render_crops_layout exist (pitched frames).
  * (12, no bump) svc_render_crops_filter (SVC_FILTER_*) was added without one: no struct and no existing signature changed, and
- *     a binding finds the entry by its symbol (dlsym), not by the revision. */
+ *     a binding finds the entry by its symbol (dlsym), not by the revision.  Likewise svc_debug_net_plan (SVC_PLAN_*). */
 #define SVC_ABI_VERSION 12
 int svc_abi_version(void);
 
@@ -221,7 +221,13 @@ int svc_render_crops_filter(SvcHandle *h, const uint8_t *frames, const SvcFrameL
 
 /* frames_nhwc[n][h][w][3] u8 RGB (saliency size, e.g. 140x250) -> maps_nhw[n][h][w] u8.
  * Frame-major output; the reference's [h][w][n] view is a transpose done by the
- * caller only when someone asks for VD['smaps']. */
+ * caller only when someone asks for VD['smaps'].
+ * height, width >= 8.  The frames are meant to be at the saliency size (svc_resize_frames_u8 brings them there): a larger frame is
+ * resampled DOWN to the network size by a kernel that keeps a tile's source rows in LDS, and is refused with SVC_E_INVALID, before
+ * anything is launched or the handle's plan changes, when that tile needs more than the CU's 160 KB (the message carries the frame
+ * size and the byte count; svc_debug_net_plan reports the count as SVC_PLAN_LZ_LDS).  540x960 is the largest 16:9 frame that runs
+ * (143 616 B); 720x1280 (226 272 B) and 1080x1920 are refused.  The other svc_saliency_* entries and svc_debug_run_node plan
+ * the same way. */
 int svc_saliency_u8(SvcHandle *h, const uint8_t *frames_nhwc, int n, int height, int width,
                     uint8_t *maps_nhw, void *stream);
 
@@ -468,6 +474,31 @@ int svc_debug_tap(SvcHandle *h, int which, int frame, float *out_host, size_t ca
 #define SVC_NODE_F2X (SVC_NODE_FULL + 14)
 int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int width, const void *in0_host, const void *in1_host,
                        float *out_host, size_t cap_floats);
+/* Test/diagnostic door: what the plan of a height x width saliency map decides from the shape alone -- host arithmetic, no handle
+ * and no device: out[0 .. SVC_PLAN_WORDS) = the SVC_PLAN_* words below (an LDS figure is the dynamic request of a launch in bytes; a
+ * *_LDS_MAX figure the most the launcher lets that kernel ask for).  The rows per band are those of a handle created without
+ * SVC_SD_ROWS.  Returns SVC_PLAN_WORDS.  SVC_E_INVALID: out NULL, height or width below 8, cap below SVC_PLAN_WORDS.  A shape whose
+ * SVC_PLAN_LZ_LDS exceeds SVC_PLAN_LZ_LDS_MAX is reported like any other; svc_saliency_u8 refuses it. */
+#define SVC_PLAN_NH 0            /* network input size that (height, width) selects                  */
+#define SVC_PLAN_NW 1
+#define SVC_PLAN_HKS 2           /* taps of a LANCZOS column / row table (1: the axis is not resampled) */
+#define SVC_PLAN_VKS 3
+#define SVC_PLAN_FR_OK 4         /* 1: the fused front kernel serves the shape (0: the three kernels)  */
+#define SVC_PLAN_FR_NR 5         /* source rows / columns one of its tiles needs at most (0 without it) */
+#define SVC_PLAN_FR_NC 6
+#define SVC_PLAN_FR_TILES_Y 7    /* its tile rows / columns                                           */
+#define SVC_PLAN_FR_TILES_X 8
+#define SVC_PLAN_LZ_TILE_CAP 9   /* three-kernel LANCZOS: source rows one workgroup stages at most     */
+#define SVC_PLAN_LZ_LDS 10
+#define SVC_PLAN_SD_ROWS 11      /* smoothing + resize: map rows per workgroup                         */
+#define SVC_PLAN_SD_TILE_CAP 12  /* ... and the network-size rows it stages at most                    */
+#define SVC_PLAN_SD_LDS 13
+#define SVC_PLAN_FR_LDS 14
+#define SVC_PLAN_LZ_LDS_MAX 15
+#define SVC_PLAN_SD_LDS_MAX 16
+#define SVC_PLAN_FR_LDS_MAX 17
+#define SVC_PLAN_WORDS 18
+int svc_debug_net_plan(int height, int width, int32_t *out, int cap);
 /* SVC_TAP_INPUT with the fused front kernel (the default): the input is written to memory only by handles created
  * with SVC_KEEP_INPUT=1 in the environment; otherwise the call fails with SVC_E_INVALID.
  * svc_front_fused: 1 when the last svc_saliency_u8 call ran LANCZOS + features.0 + features.1 as one kernel

@@ -20,7 +20,7 @@ EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'sv
            'svc_saliency_census_u8', 'svc_transnet_predict_rows', 'svc_transnet_config_get', 'svc_transnet_config_set',
            'svc_render_crops_u8', 'svc_debug_transnet_tap', 'svc_border_profile_u8', 'svc_saliency_profile_u8',
            'svc_resize_frames_nv12', 'svc_render_crops_nv12', 'svc_render_crops_u8_to_nv12', 'svc_render_crops_nv12_to_nv12', 'svc_debug_run_node',
-           'svc_resize_frames_layout', 'svc_render_crops_layout', 'svc_render_crops_filter')
+           'svc_resize_frames_layout', 'svc_render_crops_layout', 'svc_render_crops_filter', 'svc_debug_net_plan')
 
 
 class SvcParams(ctypes.Structure):
@@ -102,6 +102,7 @@ def load():
     lib.svc_debug_cluster_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     lib.svc_debug_tap.argtypes = [vp, i32, i32, vp, sz]
     lib.svc_debug_run_node.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, sz]
+    lib.svc_debug_net_plan.argtypes = [i32, i32, vp, i32]
     lib.svc_front_fused.argtypes = [vp]
     lib.svc_matrix_pipe.argtypes = [vp]
     lib.svc_transnet_matrix_pipe.argtypes = [vp]

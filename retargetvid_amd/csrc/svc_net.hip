@@ -1283,20 +1283,36 @@ static const struct { int div, ch; } BUF_SHAPE[B_COUNT] = {
 static size_t buf_floats(int NH, int NW, int b) { return (size_t)(NH / BUF_SHAPE[b].div) * (NW / BUF_SHAPE[b].div) * BUF_SHAPE[b].ch; }
 
 #define LZ_ROWS 8       // output rows per workgroup of k_lanczos_norm
-#define SD_ROWS 7       // output rows per workgroup of k_smooth_down_mfma
+#define SD_ROWS 7       // output rows per workgroup of k_smooth_down_mfma at most (net_geometry chooses them)
+// Dynamic LDS a launch may ask for.  k_lanczos_norm: the CU's 160 KB (a frame whose tile needs more is refused in the plan);
+// k_smooth_down_mfma: 64 KB (the rows per band shrink until the band fits); k_front: its fixed request, below the default limit.
+#define LZ_LDS_MAX (160 * 1024)
+#define SD_LDS_MAX (64 * 1024)
+#define FR_LDS_MAX (64 * 1024)
 
-struct NetPlan {
-    int h = 0, w = 0, NH = 0, NW = 0, nb = 0;
+// What the plan decides from the map shape (h, w) alone, by host arithmetic (net_geometry): the network size, the LANCZOS
+// tables' widths, whether and how k_front runs, the tiles of k_lanczos_norm and k_smooth_down_mfma and the dynamic LDS of the
+// three.  svc_debug_net_plan reports it without a handle or a device.
+struct NetGeom {
+    int h = 0, w = 0, NH = 0, NW = 0;
+    int hks = 0, vks = 0, lz_tile_cap = 0;                    // k_lanczos_norm: source rows one workgroup needs at most
+    size_t lz_lds = 0;                                        // ... and its dynamic LDS
+    int fr_nr = 0, fr_nc = 0;                                 // source rows / columns one tile of k_front needs at most
+    int fr_ty = 0, fr_tx = 0;                                 // tile rows / columns of k_front
+    bool fr_ok = false;                                       // the geometry can run k_front
+    short fr_row_lo[32], fr_row_n[32], fr_col_lo[32], fr_col_n[32];
+    int sd_rows = 0, sd_tile_cap = 0;                         // k_smooth_down_mfma: output rows per workgroup, network-size rows one workgroup needs at most
+    size_t sd_lds = 0;                                        // ... and its dynamic LDS
+};
+struct LzTabs { std::vector<int> hb, hk, vb, vk; };           // lanczos_tab's bounds and coefficients, columns and rows
+
+struct NetPlan : NetGeom {
+    int nb = 0;
     size_t off[B_COUNT + 1];      // per-frame float offsets
     DevBuf ws, fmax, lut, gauss;
     DevBuf hb, hk, vb, vk;
     DevBuf fr_vt;                                             // k_front: [NH][8] vertical records (seven coefficients, first source row)
     DevBuf fr_ht;                                             // k_front: [tile columns][2][128] int4 column records (place in the patch, first source byte, seven coefficients)
-    int hks = 0, vks = 0, lz_tile_cap = 0;                    // k_lanczos_norm: source rows one workgroup needs at most
-    int fr_nr = 0, fr_nc = 0;                                 // source rows / columns one tile of k_front needs at most
-    bool fr_ok = false;                                       // the geometry can run k_front
-    short fr_row_lo[32], fr_row_n[32], fr_col_lo[32], fr_col_n[32];
-    int sd_tile_cap = 0;                                      // k_smooth_down_mfma: network-size rows one workgroup needs at most
     int last_n = 0;
     bool last_front = false;       // the last pass ran k_front (the network input is then kept only under SVC_KEEP_INPUT=1)
     int gauss_filled = 0;          // frames of the workspace whose Gaussian-prior channels of CAT1 are already written
@@ -1327,15 +1343,91 @@ static void linspace01(int steps, std::vector<float> &v) {
     for (int i = 0; i < steps; ++i) v[i] = (i < half) ? (0.f + step * i) : (1.f - step * (steps - 1 - i));
 }
 
+// network-size rows a band of `rows` output rows of k_smooth_down_mfma needs at most (the kernel's own ylo / yhi)
+static int sd_band_rows(int height, int NH, int rows) {
+    const float scy = (float)NH / (float)height;
+    int cap = 0;
+    for (int oy0 = 0; oy0 < height; oy0 += rows) {
+        int oy1 = std::min(height, oy0 + rows);
+        int ylo = (int)std::max(scy * (oy0 + 0.5f) - 0.5f, 0.f);
+        int yhi = std::min((int)std::max(scy * ((oy1 - 1) + 0.5f) - 0.5f, 0.f) + 1, NH - 1);
+        cap = std::max(cap, yhi - ylo + 1);
+    }
+    return cap;
+}
+
+// The geometry of a height x width map (NetGeom) and its LANCZOS tables.  sd_rows_max: the rows per band of
+// k_smooth_down_mfma at most (0: SD_ROWS; SVC_SD_ROWS).  Host arithmetic only.
+static void net_geometry(int height, int width, int sd_rows_max, NetGeom &g, LzTabs &t) {
+    int NH, NW;
+    optimal_out_size(height, width, NH, NW);
+    g.h = height; g.w = width; g.NH = NH; g.NW = NW;
+    std::vector<int> &hb = t.hb, &vb = t.vb;
+    lanczos_tab(width, NW, t.hb, t.hk, g.hks);
+    lanczos_tab(height, NH, t.vb, t.vk, g.vks);
+    int cap = 0;
+    for (int y0 = 0; y0 < NH; y0 += LZ_ROWS) {
+        int y1 = std::min(NH, y0 + LZ_ROWS);
+        cap = std::max(cap, vb[2 * (y1 - 1)] + vb[2 * (y1 - 1) + 1] - vb[2 * y0]);
+    }
+    g.lz_tile_cap = cap;
+    g.lz_lds = ((size_t)cap * width * 3 + 15) / 16 * 16 + ((size_t)cap * NW * 3 + 15) / 16 * 16 + (size_t)NW * g.hks * 4 + 768 * 4;
+    // k_front: source rows / columns of every tile row / column.  The kernel serves up-scaling geometries (at most
+    // eight taps per pass) whose source patch is at most 32 rows of 32 words; anything else runs the three kernels.
+    g.fr_nr = g.fr_nc = 0;
+    const int fty = g.fr_ty = ceil_div(NH / 2, FR_TH), ftx = g.fr_tx = ceil_div(NW / 2, FR_TW);
+    g.fr_ok = g.hks <= 7 && g.vks <= 7 && fty <= FR_MAXT && ftx <= FR_MAXT;     // (a table's width is odd: at most seven taps either way)
+    for (int y = 1; y < NH && g.fr_ok; ++y) g.fr_ok = vb[2 * y] - vb[2 * (y - 1)] <= 1;  // the vertical window moves by 0 or 1 rows per output row
+    for (int i = 0; i < FR_MAXT; ++i) g.fr_row_lo[i] = g.fr_row_n[i] = g.fr_col_lo[i] = g.fr_col_n[i] = 0;
+    for (int i = 0; i < fty && g.fr_ok; ++i) {
+        const int ya = std::max(2 * i * FR_TH - 3, 0), yb = std::min(2 * i * FR_TH - 3 + FR_PR, NH);
+        g.fr_row_lo[i] = (short)vb[2 * ya];
+        g.fr_row_n[i] = (short)(vb[2 * (yb - 1)] + vb[2 * (yb - 1) + 1] - vb[2 * ya]);
+        g.fr_nr = std::max(g.fr_nr, (int)g.fr_row_n[i]);
+    }
+    for (int i = 0; i < ftx && g.fr_ok; ++i) {
+        const int xa = std::max(2 * i * FR_TW - 3, 0), xb = std::min(2 * i * FR_TW - 3 + FR_PC, NW);
+        g.fr_col_lo[i] = (short)hb[2 * xa];
+        g.fr_col_n[i] = (short)(hb[2 * (xb - 1)] + hb[2 * (xb - 1) + 1] - hb[2 * xa]);
+        g.fr_nc = std::max(g.fr_nc, (int)g.fr_col_n[i]);
+    }
+    g.fr_ok = g.fr_ok && g.fr_nr <= 32 && front_src_stride(g.fr_nc) <= 128 &&
+              front_small_bytes(g.fr_nr, g.fr_nc) <= FR_SONLY_BYTES;
+    // k_smooth_down_mfma stages the network-size rows of a band of output rows: the largest band of at most sd_rows_max rows
+    // whose LDS fits.  A wide strip (h x 250 with h < 64) spreads few output rows over many network rows; one output row
+    // needs two of them, about 24 KB with the logits and the phase table, so every shape has a band that fits.  A pixel is
+    // computed from its own cell's MFMA chain and its own four tile values: the map does not depend on the band.
+    for (g.sd_rows = sd_rows_max > 0 ? std::min(sd_rows_max, SD_ROWS) : SD_ROWS;; --g.sd_rows) {
+        g.sd_tile_cap = sd_band_rows(height, NH, g.sd_rows);
+        g.sd_lds = ((size_t)(NH / 8) * (NW / 8) + 64 * SD_KP + (size_t)g.sd_tile_cap * NW) * sizeof(float);
+        if (g.sd_lds <= SD_LDS_MAX || g.sd_rows == 1) break;
+    }
+}
+
 static int build_plan(SvcHandle *h, int height, int width, int nb) {
     NetPlan *p = h->plan;
     if (!p) p = h->plan = new NetPlan();
     if (p->h == height && p->w == width && p->nb >= nb) return SVC_OK;
-    p->gauss_filled = 0;            // the workspace layout (and possibly the maps) change below
-    int NH, NW;
-    optimal_out_size(height, width, NH, NW);
     const bool same_size = (p->h == height && p->w == width);
-    p->h = height; p->w = width; p->NH = NH; p->NW = NW; p->nb = nb;
+    NetGeom geom;
+    LzTabs tabs;
+    if (!same_size) {
+        net_geometry(height, width, h->sd_rows, geom, tabs);
+        // a frame this large is meant to come through the ingest; refused here, before the plan changes or anything launches
+        if (geom.lz_lds > LZ_LDS_MAX) {
+            svc_set_error("svc_saliency_u8: a %dx%d frame needs %zu bytes of LDS for its LANCZOS tile (at most %d): "
+                          "down-scale it to the saliency size with svc_resize_frames_u8 first", height, width, geom.lz_lds, LZ_LDS_MAX);
+            return SVC_E_INVALID;
+        }
+        if (geom.sd_lds > SD_LDS_MAX) {       // (no map of 8 x 8 or more comes here: see net_geometry)
+            svc_set_error("svc_saliency_u8: a %dx%d map needs %zu bytes of LDS for one row of its smoothing band", height, width, geom.sd_lds);
+            return SVC_E_INVALID;
+        }
+        static_cast<NetGeom &>(*p) = geom;
+    }
+    p->gauss_filled = 0;            // the workspace layout (and possibly the maps) change below
+    const int NH = p->NH, NW = p->NW;
+    p->nb = nb;
     const size_t H1 = NH / 2, W1 = NW / 2, H2 = NH / 4, W2 = NW / 4, H3 = NH / 8, W3 = NW / 8, H4 = NH / 16,
                  W4 = NW / 16, H5 = NH / 32, W5 = NW / 32;
     size_t sz[B_COUNT];
@@ -1353,36 +1445,8 @@ static int build_plan(SvcHandle *h, int height, int width, int nb) {
     if (rc) return rc;
     if (same_size) return SVC_OK;
     // resampling tables
-    std::vector<int> hb, hk, vb, vk;
-    lanczos_tab(width, NW, hb, hk, p->hks);
-    lanczos_tab(height, NH, vb, vk, p->vks);
-    int cap = 0;
-    for (int y0 = 0; y0 < NH; y0 += LZ_ROWS) {
-        int y1 = std::min(NH, y0 + LZ_ROWS);
-        cap = std::max(cap, vb[2 * (y1 - 1)] + vb[2 * (y1 - 1) + 1] - vb[2 * y0]);
-    }
-    p->lz_tile_cap = cap;
-    // k_front: source rows / columns of every tile row / column.  The kernel serves up-scaling geometries (at most
-    // eight taps per pass) whose source patch is at most 32 rows of 32 words; anything else runs the three kernels.
-    p->fr_nr = p->fr_nc = 0;
-    const int fty = ceil_div(NH / 2, FR_TH), ftx = ceil_div(NW / 2, FR_TW);
-    p->fr_ok = p->hks <= 7 && p->vks <= 7 && fty <= FR_MAXT && ftx <= FR_MAXT;     // (a table's width is odd: at most seven taps either way)
-    for (int y = 1; y < NH && p->fr_ok; ++y) p->fr_ok = vb[2 * y] - vb[2 * (y - 1)] <= 1;  // the vertical window moves by 0 or 1 rows per output row
-    for (int t = 0; t < FR_MAXT; ++t) p->fr_row_lo[t] = p->fr_row_n[t] = p->fr_col_lo[t] = p->fr_col_n[t] = 0;
-    for (int t = 0; t < fty && p->fr_ok; ++t) {
-        const int ya = std::max(2 * t * FR_TH - 3, 0), yb = std::min(2 * t * FR_TH - 3 + FR_PR, NH);
-        p->fr_row_lo[t] = (short)vb[2 * ya];
-        p->fr_row_n[t] = (short)(vb[2 * (yb - 1)] + vb[2 * (yb - 1) + 1] - vb[2 * ya]);
-        p->fr_nr = std::max(p->fr_nr, (int)p->fr_row_n[t]);
-    }
-    for (int t = 0; t < ftx && p->fr_ok; ++t) {
-        const int xa = std::max(2 * t * FR_TW - 3, 0), xb = std::min(2 * t * FR_TW - 3 + FR_PC, NW);
-        p->fr_col_lo[t] = (short)hb[2 * xa];
-        p->fr_col_n[t] = (short)(hb[2 * (xb - 1)] + hb[2 * (xb - 1) + 1] - hb[2 * xa]);
-        p->fr_nc = std::max(p->fr_nc, (int)p->fr_col_n[t]);
-    }
-    p->fr_ok = p->fr_ok && p->fr_nr <= 32 && front_src_stride(p->fr_nc) <= 128 &&
-               front_small_bytes(p->fr_nr, p->fr_nc) <= FR_SONLY_BYTES;
+    const std::vector<int> &hb = tabs.hb, &hk = tabs.hk, &vb = tabs.vb, &vk = tabs.vk;
+    const int ftx = p->fr_tx;
     if ((rc = p->hb.ensure(hb.size() * 4)) || (rc = p->hk.ensure(hk.size() * 4)) || (rc = p->vb.ensure(vb.size() * 4)) ||
         (rc = p->vk.ensure(vk.size() * 4)))
         return rc;
@@ -1443,16 +1507,6 @@ static int build_plan(SvcHandle *h, int height, int width, int nb) {
     }
     if ((rc = p->gauss.ensure(g.size() * 4))) return rc;
     SVC_HIP(hipMemcpy(p->gauss.p, g.data(), g.size() * 4, hipMemcpyHostToDevice));
-    // tile rows for k_smooth_down_mfma
-    float scy = (float)NH / (float)height;
-    cap = 0;
-    for (int oy0 = 0; oy0 < height; oy0 += SD_ROWS) {
-        int oy1 = std::min(height, oy0 + SD_ROWS);
-        int ylo = (int)std::max(scy * (oy0 + 0.5f) - 0.5f, 0.f);
-        int yhi = std::min((int)std::max(scy * ((oy1 - 1) + 0.5f) - 0.5f, 0.f) + 1, NH - 1);
-        cap = std::max(cap, yhi - ylo + 1);
-    }
-    p->sd_tile_cap = cap;
     return SVC_OK;
 }
 
@@ -2642,9 +2696,10 @@ static int net_front(SvcHandle *h, hipStream_t s, const uint8_t *frames, int n, 
     {   // K0
         ProfScope ps(h, SVC_K_LANCZOS, s);
         dim3 grid(ceil_div(NH, LZ_ROWS), n);
-        size_t lds = ((size_t)p->lz_tile_cap * p->w * 3 + 15) / 16 * 16 + ((size_t)p->lz_tile_cap * NW * 3 + 15) / 16 * 16 +
-                     (size_t)NW * p->hks * 4 + 768 * 4;
-        k_lanczos_norm<<<grid, 256, lds, s>>>(frames, IN, p->h, p->w, NH, NW, (const int *)p->hb.p, (const int *)p->hk.p,
+        // (the same call as for the other kernels that may ask for more than 64 KB: 360x640 frames asked for 81 568 B before
+        // this kernel had it and ran, so the call is there for uniformity and shows nothing either way)
+        RC(raise_lds_limit(h, (const void *)k_lanczos_norm, LZ_LDS_MAX));
+        k_lanczos_norm<<<grid, 256, p->lz_lds, s>>>(frames, IN, p->h, p->w, NH, NW, (const int *)p->hb.p, (const int *)p->hk.p,
                                              p->hks, (const int *)p->vb.p, (const int *)p->vk.p, p->vks,
                                              (const float *)p->lut.p, LZ_ROWS, p->lz_tile_cap);
         SVC_CHECK_LAUNCH();
@@ -2770,10 +2825,10 @@ static int tail_adapt(SvcHandle *h, hipStream_t s, int n, int H3, int W3) {
 static int tail_smooth(SvcHandle *h, hipStream_t s, int n, int H3, int W3) {
     NetPlan *p = h->plan;
     const int NH = p->NH, NW = p->NW;
-    dim3 grid(ceil_div(p->h, SD_ROWS), n);
-    const size_t lds = ((size_t)H3 * W3 + 64 * SD_KP + (size_t)p->sd_tile_cap * NW) * sizeof(float);
-    k_smooth_down_mfma<<<grid, 256, lds, s>>>(p->buf(B_LOGIT), h->net.smooth.w.dev, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3,
-                                              NH, NW, p->h, p->w, SD_ROWS, p->sd_tile_cap, make_fdiv(p->w));
+    dim3 grid(ceil_div(p->h, p->sd_rows), n);
+    RC(raise_lds_limit(h, (const void *)k_smooth_down_mfma, SD_LDS_MAX));       // (for uniformity, as in net_front: the plan keeps the request within the default)
+    k_smooth_down_mfma<<<grid, 256, p->sd_lds, s>>>(p->buf(B_LOGIT), h->net.smooth.w.dev, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3,
+                                                    NH, NW, p->h, p->w, p->sd_rows, p->sd_tile_cap, make_fdiv(p->w));
     SVC_CHECK_LAUNCH();
     return SVC_OK;
 }
@@ -3005,6 +3060,22 @@ extern "C" int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int
     return rc ? rc : (int)count;
 }
 
+// The plan's geometry through a door that needs neither a handle nor a device (include/svc.h: SVC_PLAN_*).
+extern "C" int svc_debug_net_plan(int height, int width, int32_t *out, int cap) {
+    if (!out || height < 8 || width < 8 || cap < SVC_PLAN_WORDS) { svc_set_error("svc_debug_net_plan: invalid argument"); return SVC_E_INVALID; }
+    NetGeom g;
+    LzTabs t;
+    net_geometry(height, width, 0, g, t);
+    out[SVC_PLAN_NH] = g.NH; out[SVC_PLAN_NW] = g.NW; out[SVC_PLAN_HKS] = g.hks; out[SVC_PLAN_VKS] = g.vks;
+    out[SVC_PLAN_FR_OK] = g.fr_ok; out[SVC_PLAN_FR_NR] = g.fr_nr; out[SVC_PLAN_FR_NC] = g.fr_nc;
+    out[SVC_PLAN_FR_TILES_Y] = g.fr_ty; out[SVC_PLAN_FR_TILES_X] = g.fr_tx;
+    out[SVC_PLAN_LZ_TILE_CAP] = g.lz_tile_cap; out[SVC_PLAN_LZ_LDS] = (int32_t)std::min<size_t>(g.lz_lds, INT32_MAX);
+    out[SVC_PLAN_SD_ROWS] = g.sd_rows; out[SVC_PLAN_SD_TILE_CAP] = g.sd_tile_cap; out[SVC_PLAN_SD_LDS] = (int32_t)std::min<size_t>(g.sd_lds, INT32_MAX);
+    out[SVC_PLAN_FR_LDS] = front_lds_bytes();
+    out[SVC_PLAN_LZ_LDS_MAX] = LZ_LDS_MAX; out[SVC_PLAN_SD_LDS_MAX] = SD_LDS_MAX; out[SVC_PLAN_FR_LDS_MAX] = FR_LDS_MAX;
+    return SVC_PLAN_WORDS;
+}
+
 extern "C" int svc_front_fused(const SvcHandle *h) { return h && h->plan && h->plan->last_front ? 1 : 0; }
 extern "C" int svc_matrix_pipe(const SvcHandle *h) { return h ? h->mx : 0; }
 
@@ -3113,6 +3184,13 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
     if (env) h->front = atoi(env) != 0;
     env = getenv("SVC_KEEP_INPUT");
     if (env) h->keep_input = atoi(env) != 0;
+    env = getenv("SVC_SD_ROWS");
+    if (env) {
+        char *end = nullptr;
+        const long v = strtol(env, &end, 10);
+        if (end == env || *end || v < 1 || v > SD_ROWS) { svc_set_error("svc_create: SVC_SD_ROWS=%s (expected 1 .. %d)", env, SD_ROWS); delete h; return SVC_E_INVALID; }
+        h->sd_rows = (int)v;
+    }
     env = getenv("SVC_MX");
     if (env) {                                               // a typo must not silently select another pipe
         if (!strcmp(env, "bf16x6") || !strcmp(env, "6")) h->mx = 6;

@@ -17,6 +17,21 @@ NODE_FRONT, NODE_F18, NODE_SKIP_2X, NODE_SKIP_4X, NODE_POST_CNN, NODE_US2, NODE_
 NODE_F4X, NODE_F2X = 107, 114
 
 
+# words of svc_debug_net_plan (include/svc.h: SVC_PLAN_*), in order
+PLAN_WORDS = ('NH', 'NW', 'hks', 'vks', 'fr_ok', 'fr_nr', 'fr_nc', 'fr_tiles_y', 'fr_tiles_x', 'lz_tile_cap', 'lz_lds', 'sd_rows',
+              'sd_tile_cap', 'sd_lds', 'fr_lds', 'lz_lds_max', 'sd_lds_max', 'fr_lds_max')
+
+
+def net_plan(height, width):
+    """Test door (svc_debug_net_plan): what the network's plan decides from the map shape alone, as a dict of PLAN_WORDS.  Host
+    arithmetic of the library: needs no GPU."""
+    out = (ctypes.c_int32 * len(PLAN_WORDS))()
+    n = _lib.check(_lib.load().svc_debug_net_plan(int(height), int(width), ctypes.cast(out, ctypes.c_void_p), len(PLAN_WORDS)))
+    if n != len(PLAN_WORDS):
+        raise _lib.SvcError('svc_debug_net_plan reports %d words, this binding knows %d' % (n, len(PLAN_WORDS)))
+    return dict(zip(PLAN_WORDS, (int(v) for v in out)))
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
