@@ -374,13 +374,37 @@ int svc_profile_read_raw(SvcHandle *h, double *raw_total_ms, double *pair_ms, in
  *   core_host[cap]  core distances (squared)
  *   mst_host[cap][3] MST edges in Prim order: from, to, weight
  *   labels_host[cap] final labels (-1 = noise)
- *   hdr_host[32]    frame header: [0] points, [1] clusters selected, [2] cluster kept, [3] clustered,
- *                   [4] condensed clusters, [8..11] k_finish phase stamps in 10 ns units
- *                   (sorted, hierarchy built, cluster chosen, done), [12] Prim duration,
- *                   [16] rounds and [17] level rises of k_prim_lvl, [18..22] its phase sums (10 ns units)
+ *   hdr_host[32]    frame header: the SVC_HDR_* words below
  * Returns the number of points of that frame (or a negative error). */
 int svc_debug_cluster_state(SvcHandle *h, int frame, int cap, uint32_t *pts_host, uint32_t *core_host,
                             uint32_t *mst_host, int32_t *labels_host, int32_t *hdr_host);
+/* The words of a frame header (int32 each; retargetvid_amd/ops.py carries the same numbers as HDR_*).  Times are in units
+ * of 10 ns, measured from the start of the stage that writes them; a range is named by its first word and a count. */
+#define SVC_HDR_WORDS        32
+#define SVC_HDR_N            0    /* points of the map */
+#define SVC_HDR_NSEL         1    /* clusters selected */
+#define SVC_HDR_KEPT         2    /* the cluster kept (-1: none) */
+#define SVC_HDR_CLUSTERED    3    /* 1: the map went through the cluster filter (clust_filt and more than hdbscan_min + 1 points) */
+#define SVC_HDR_NCLUSTERS    4    /* condensed clusters */
+#define SVC_HDR_CORE_STAMP0  5    /* k_core: end of phase 1 (thread per point), of phase 2 (wavefront per point), of the kernel */
+#define SVC_HDR_CORE_STAMPS  3
+#define SVC_HDR_T_SORTED     8    /* k_sort: done */
+#define SVC_HDR_T_HIERARCHY  9    /* k_tree / k_tree_par: stabilities summed, clusters selected */
+#define SVC_HDR_T_CHOSEN     10   /* ... labels written, kept cluster chosen */
+#define SVC_HDR_T_FINISHED   11   /* k_finish: done */
+#define SVC_HDR_T_PRIM       12   /* duration of the Prim kernel that took the map */
+#define SVC_HDR_T_BUILT      13   /* k_tree: union-find pass done; k_tree_par: row lists of the clusters written */
+#define SVC_HDR_TREE_CLOCKS  14   /* k_tree: shader clocks ... */
+#define SVC_HDR_T_TREE       15   /* ... during this long (k_tree_par: a copy of T_CHOSEN) */
+#define SVC_HDR_LVL_ROUNDS   16   /* k_prim_lvl / k_prim_lvl_big: rounds (0: the map took neither) */
+#define SVC_HDR_LVL_RISES    17   /* ... level rises */
+#define SVC_HDR_LVL_PHASE0   18   /* k_prim_lvl, SVC_PRIM_LVL=3: time summed per phase (rise, extract, probe, accept + commit, mark) */
+#define SVC_HDR_LVL_PHASES   5
+#define SVC_HDR_TREE_PAR     23   /* 1: k_tree_par has done the map's hierarchy (0: left to k_tree) */
+#define SVC_HDR_T_LVL_SETUP  24   /* k_prim_lvl / k_prim_lvl_big: set-up done */
+#define SVC_HDR_TP_STAMP0    25   /* k_tree_par: -, nearest greater ranks, clusters numbered, chains jumped, chain tops (the first is not written) */
+#define SVC_HDR_TP_STAMPS    5
+#define SVC_HDR_BACK_DONE    30   /* 1: k_tail_back has finished the map (zeroing, CLOSE, centre); k_finish then leaves it alone */
 
 /* Test/diagnostic door: the edge-order routine of the cluster filter (numpy's default argsort, an unstable
  * introsort, emulated on the device; hdbscan sorts the MST edges with it, call site smartVidCrop.py:1099) on

@@ -160,10 +160,9 @@ struct SvcHandle {
     bool front = true;                 // LANCZOS + features.0 + features.1 as one kernel, k_front (SVC_FRONT=0: three kernels)
     bool keep_input = false;           // ... which then also writes the normalised network input for svc_debug_tap(SVC_TAP_INPUT) (SVC_KEEP_INPUT=1)
     int sd_rows = 0;                   // output rows per workgroup of k_smooth_down_mfma at most (0: SD_ROWS; SVC_SD_ROWS=1..SD_ROWS: the reference of a bit-identity test; the plan shrinks the band further where its LDS would not fit)
-    int prim_pt = 2;                   // legacy Prim (k_prim_pt): smallest points-per-thread variant (SVC_PRIM_PT: 2, 4, 8, 16)
     int tail_merge = 1;                // a round's kernels as two fused launches, k_tail_front / k_tail_back (SVC_TAIL_MERGE=0: one launch per stage, for per-kernel profiles)
     int tree_par = 1;                  // data-parallel hierarchy k_tree_par for maps of up to 4352 points (SVC_TREE_PAR=0: the serial builder k_tree)
-    int prim_lvl = 1;                  // level-bucketed Prim k_prim_lvl for maps of up to 8192 points (SVC_PRIM_LVL=0: one node per step)
+    int prim_lvl = 1;                  // Prim in rounds, k_prim_lvl / k_prim_lvl_big (SVC_PRIM_LVL=0: one node per step, k_prim_ref, the tests' device reference; 3: k_prim_lvl's phase stamps)
     // TransNet V1 (svc_shot.hip)
     DevBuf shot_blob, shot_ws, shot_w3;   // shot_w3: split-bf16 copies of the cells' weights (svc_shot.hip), valid for shot_w3_mx
     int shot_w3_mx = 0;
@@ -185,5 +184,12 @@ struct ProfScope {
     }
     ~ProfScope() { if (on) { (void)hipEventRecord(b, s); h->prof_events.emplace_back(a, b); } }
 };
+
+// Raises a kernel's dynamic-LDS limit, once per kernel and handle: the attribute is per device, so the once-flag lives in the
+// handle (one handle = one device), not in the process.
+static inline int raise_lds_limit(SvcHandle *h, const void *kfn, int bytes) {
+    if (h->lds_attr_done.insert(kfn).second) SVC_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return SVC_OK;
+}
 
 int svc_net_release(SvcHandle *h);

@@ -1532,13 +1532,6 @@ int svc_net_release(SvcHandle *h) {
 
 static inline unsigned blocks256(size_t total) { return (unsigned)((total + 255) / 256); }
 
-// Raises a kernel's dynamic-LDS limit, once per kernel and handle: the attribute is per device, so the once-flag lives in the
-// handle (one handle = one device), not in the process.
-static int raise_lds_limit(SvcHandle *h, const void *kfn, int bytes) {
-    if (h->lds_attr_done.insert(kfn).second) SVC_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    return SVC_OK;
-}
-
 // F32_LANES: lane-order copy of a weight matrix for k_pw_sk<.., true>: out[((st * tiles + tile) * 64 + lane)] (float4) =
 // W[tile * 32 + (lane & 31)][8 st + 4 (lane >> 5) .. + 3] -- what the lane loads in k-step st for column tile `tile`.
 __global__ void k_lane_weights(const float *__restrict__ Wt, int ldw, int nsteps, int tiles, int nrows, float4 *__restrict__ out) {
@@ -3215,8 +3208,6 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
     }
     env = getenv("SVC_SHOT_XCD");
     if (env) h->shot_xcd = atoi(env) != 0;
-    env = getenv("SVC_PRIM_PT");
-    if (env && atoi(env) > 0) h->prim_pt = atoi(env);
     env = getenv("SVC_TAIL_MERGE");
     if (env) h->tail_merge = atoi(env);
     env = getenv("SVC_TREE_PAR");

@@ -13,8 +13,8 @@
 //   k_compact     coo_matrix gather, raster order    smartVidCrop.py:1089-1091
 //   k_core        HDBSCAN core distances                 \
 //   k_prim_lvl    Prim on mutual reachability (rounds)   |  hdbscan generic path, call site smartVidCrop.py:1099
-//   k_sort        numpy's argsort order of the edges      |  (k_prim_pt / k_prim_big, k_tree: the one-node-per-step Prim and the
-//   k_tree_par    hierarchy, EOM, labels                 /   serial union-find builder, for maps the parallel kernels do not take)
+//   k_sort        numpy's argsort order of the edges      |  (k_prim_ref, k_tree: the one-node-per-step Prim the tests use as their second
+//   k_tree_par    hierarchy, EOM, labels                 /   device reference; the serial union-find builder, for maps k_tree_par does not take)
 //   k_finish      cluster weights / first arg-max / zeroing (smartVidCrop.py:1107-1122), CLOSE 5x5 (:1126-1128),
 //                 centroid (:1163-1219); k_centre_argmax: com_km = False (:1165-1178)
 //   k_tail_front / k_tail_back  the stages of a round fused into two launches
@@ -36,8 +36,8 @@
 // What the kernels below assume of TB, stated once (round 4's TB = 512 build did not terminate: three block reductions read
 // sixteen per-wavefront slots whatever NW16 was, i.e. the other parity's stale minima): the per-wavefront slots of a block
 // reduction are read back as slot[lane & (NW16 - 1)] and reduced inside a row of 16 lanes, so NW16 must be a power of two of
-// at most 16; k_prim_lvl's rounds run on LVL_WORKERS (8, at most NW16) wavefronts.  Every launch below uses TB, and the fused kernels
-// refuse to run under any other block size (tail_block_ok).
+// at most 16; k_prim_lvl's rounds run on LVL_WORKERS (8, at most NW16) wavefronts.  Every per-map kernel below is launched with TB
+// threads (k_tree with one wavefront) and takes TB as a compile-time constant.
 static_assert(TB % 64 == 0 && (NW16 & (NW16 - 1)) == 0 && NW16 >= 4 && NW16 <= 16,
               "the tail kernels need 4, 8 or 16 wavefronts per workgroup");
 #define RING_R 20               // ring table radius for core distances
@@ -49,7 +49,7 @@ static_assert(TB % 64 == 0 && (NW16 & (NW16 - 1)) == 0 && NW16 >= 4 && NW16 <= 1
 // per-frame workspace layout (all offsets in bytes from the frame base)
 // --------------------------------------------------------------------------------------
 struct FrameWS {
-    uint32_t hdr;        // int32[32]: [0]=N  [1]=nsel  [2]=kept cluster  [3]=clustered flag  [16],[17]=k_prim_lvl rounds, rises
+    uint32_t hdr;        // int32[SVC_HDR_WORDS]: the SVC_HDR_* words of include/svc.h
     uint32_t pts;        // u32[cap]   row | col<<8 | value<<16
     uint32_t core;       // u32[cap]
     uint32_t mst;        // Edge[cap]  Prim order
@@ -66,7 +66,7 @@ static FrameWS make_layout(int cap, int mc) {
     FrameWS L;
     uint32_t o = 0;
     auto take = [&](size_t bytes) { uint32_t r = o; o += (uint32_t)((bytes + 63) / 64 * 64); return r; };
-    L.hdr = take(128);
+    L.hdr = take(4 * SVC_HDR_WORDS);
     L.pts = take(4u * cap); L.core = take(4u * cap);
     L.mst = take(8u * cap); L.ea = take(8u * cap); L.eb = take(8u * cap);
     L.labels = take(4u * cap); L.reach = take(4u * cap); L.srt = take(16u * cap + 128);
@@ -91,12 +91,11 @@ struct TailArgs {
     int n, h, w;
     FDiv dW;                // division by w
     int mcs, min_samples, select_sum, op_close, clust_filt;
-    int prim_pt;            // tuning: smallest points-per-thread variant of k_prim
     const uint32_t *ring;   // sorted neighbour offsets
     const int32_t *ring_delta;  // dr * w + dc of the same offsets
     int n_ring, n_ring1;    // all offsets within RING_R / the prefix within RING_R1
     const uint16_t *ring_cnt;   // [RING_R^2 + 1]: offsets with d2 <= index
-    int prim_lvl;           // 1: k_prim_lvl for maps of up to LVL_CAP points (SVC_PRIM_LVL)
+    int prim_lvl;           // SVC_PRIM_LVL: 0 = k_prim_ref, 1 = k_prim_lvl / k_prim_lvl_big, 3 = ... with k_prim_lvl's phase stamps
     double *xy;
     int32_t *stats;
     FrameWS L;
@@ -335,12 +334,12 @@ __device__ __forceinline__ void compact_body(const TailArgs &A) {
         }
     }
     if (threadIdx.x == 0) {
-        hdr[0] = total;
-        hdr[1] = 0;
-        hdr[2] = -1;
-        hdr[3] = (A.clust_filt && total > A.mcs + 1) ? 1 : 0;
-        hdr[23] = 0;                                                     // k_tree_par sets it when it has done the map's hierarchy
-        hdr[30] = 0;                                                     // k_tail_back sets it when it has finished the map (zeroing, CLOSE, centre)
+        hdr[SVC_HDR_N] = total;
+        hdr[SVC_HDR_NSEL] = 0;
+        hdr[SVC_HDR_KEPT] = -1;
+        hdr[SVC_HDR_CLUSTERED] = (A.clust_filt && total > A.mcs + 1) ? 1 : 0;
+        hdr[SVC_HDR_TREE_PAR] = 0;                                       // k_tree_par sets it when it has done the map's hierarchy
+        hdr[SVC_HDR_BACK_DONE] = 0;                                      // k_tail_back sets it when it has finished the map (zeroing, CLOSE, centre)
     }
 }
 __global__ __launch_bounds__(TB) void k_compact(TailArgs A) { compact_body(A); }
@@ -392,8 +391,8 @@ __device__ __forceinline__ void core_body(const TailArgs &A) {
     const int f = A.order[blockIdx.x];
     uint8_t *ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
     const int32_t *hdr = (const int32_t *)(ws + A.L.hdr);
-    if (!hdr[3]) return;
-    const int N = hdr[0];
+    if (!hdr[SVC_HDR_CLUSTERED]) return;
+    const int N = hdr[SVC_HDR_N];
     extern __shared__ uint8_t sm_core[];
     const int hw = A.h * A.w;
     uint8_t *occ = sm_core;                                   // [hw]
@@ -462,8 +461,8 @@ __device__ __forceinline__ void core_body(const TailArgs &A) {
         else fb[atomicAdd(&n_fb, 1)] = p;
     }
     __syncthreads();
-    int32_t *stamp = (int32_t *)(ws + A.L.hdr);                 // [5] phase 1, [6] phase 2, [7] end (10 ns units; debug door)
-    if (threadIdx.x == 0) stamp[5] = (int)(wall_clock64() - tc0);
+    int32_t *stamp = (int32_t *)(ws + A.L.hdr) + SVC_HDR_CORE_STAMP0;     // [0] phase 1, [1] phase 2, [2] end (10 ns units; debug door)
+    if (threadIdx.x == 0) stamp[0] = (int)(wall_clock64() - tc0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long lt = (1ull << lane) - 1ull;
     const int nf = n_fb;
@@ -504,7 +503,7 @@ __device__ __forceinline__ void core_body(const TailArgs &A) {
     }
     __syncthreads();
     const int nf2 = n_fb2;
-    if (threadIdx.x == 0) { stamp[6] = (int)(wall_clock64() - tc0); stamp[7] = stamp[6]; }
+    if (threadIdx.x == 0) { stamp[1] = (int)(wall_clock64() - tc0); stamp[2] = stamp[1]; }
     if (nf2 == 0) return;
     // phase 3 counts over all points many times: their coordinates go to LDS (over the occupancy map and the ring
     // table, which are no longer needed) when they fit
@@ -550,18 +549,11 @@ __device__ __forceinline__ void core_body(const TailArgs &A) {
         if (lane == 0) core[p] = lo;
     }
     __syncthreads();
-    if (threadIdx.x == 0) stamp[7] = (int)(wall_clock64() - tc0);
+    if (threadIdx.x == 0) stamp[2] = (int)(wall_clock64() - tc0);
 }
 __global__ __launch_bounds__(TB) void k_core(TailArgs A) { core_body(A); }
 
-// --------------------------------------------------------------------------------------
-// k_prim: the library's Prim over the mutual-reachability graph, start node 0, lowest
-// index wins ties, edge = (last added node, new node, weight).  Each thread keeps the
-// running reachability and core distance of PT points in registers; coordinates live
-// in LDS; one min-reduction of (reach | index) per step with the winner's core distance
-// as payload, one barrier per step.  For N <= 32768 the key fits 32 bits and the
-// wavefront reduction is six DPP-fused v_min_u32; larger N use a 64-bit key.
-// --------------------------------------------------------------------------------------
+// block and wavefront minima (the Prim kernels, k_finish's bounding box)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ uint32_t dpp_min_u32(uint32_t v) {
     const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFF, (int)v, CTRL, ROW_MASK, 0xF, false);
@@ -585,67 +577,14 @@ __device__ __forceinline__ uint32_t row16_min_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 15);
 }
 
-template <int PT>
-__device__ __forceinline__ void prim_regs32(const uint32_t *__restrict__ core_g, hdb::Edge *__restrict__ mst, int N,
-                                            const uint16_t *rc16, uint4 *slots) {
-    // Thread t owns points t*PT .. t*PT+PT-1 entirely in registers (coordinates, core distance,
-    // reachability); wavefronts that own no point leave, so the barrier spans only ceil(N/(64*PT)) waves.
-    // A point that joined the tree gets core = reach = REACH_INF: its key sorts behind every live one and
-    // no update can lower it, so the inner loop has no liveness test.  The winner's core distance and
-    // coordinates travel with its key, so one step has a single LDS round trip (slot write, barrier, read).
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nw = (N + 64 * PT - 1) / (64 * PT);
-    for (int i = tid; i < 2 * NW16; i += TB) slots[i] = make_uint4(0xFFFFFFFFu, 0, 0, 0);
-    __syncthreads();
-    if (wave >= nw) return;
-    uint32_t reach[PT], corev[PT], rcv[PT];
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-        const int p = tid * PT + i;
-        reach[i] = REACH_INF;
-        corev[i] = REACH_INF;
-        rcv[i] = 0;
-        if (p < N) { corev[i] = core_g[p]; rcv[i] = rc16[p]; }
-    }
-    if (tid == 0) corev[0] = REACH_INF;                    // point 0 starts the tree
-    uint32_t cur = 0;
-    const uint32_t cv0 = rc16[0];
-    int cr = cv0 & 255, cc = cv0 >> 8;
-    uint32_t ccore = core_g[0];
-    for (int step = 0; step < N - 1; ++step) {
-        uint32_t best = 0xFFFFFFFFu, bcore = 0, brc = 0;
-#pragma unroll
-        for (int i = 0; i < PT; ++i) {
-            const int dr = (int)(rcv[i] & 255) - cr, dc = (int)(rcv[i] >> 8) - cc;
-            const uint32_t m = max(max((uint32_t)(dr * dr + dc * dc), corev[i]), ccore);
-            reach[i] = min(reach[i], m);
-            const uint32_t key = (reach[i] << 15) | (uint32_t)(tid * PT + i);
-            if (key < best) { best = key; bcore = corev[i]; brc = rcv[i]; }
-        }
-        const uint32_t wmin = wave_min_u32(best);
-        uint4 *sl = slots + (step & 1) * NW16;
-        if (best == wmin) sl[wave] = make_uint4(wmin, bcore, brc, 0);   // keys are unique: one lane
-        __syncthreads();
-        // second level: lanes 0..15 of every row hold one slot each; row minimum by DPP, the winner's
-        // payload by readlane
-        const uint4 t = sl[lane & (NW16 - 1)];
-        const uint32_t kmin = row16_min_u32(t.x);
-        const int src = __ffsll((unsigned long long)__ballot(t.x == kmin)) - 1;
-        const uint32_t nidx = kmin & 0x7FFFu;
-        if (tid == 0) mst[step] = hdb::Edge{(uint16_t)cur, (uint16_t)nidx, kmin >> 15};
-        if ((int)(nidx / PT) == tid) {
-#pragma unroll
-            for (int i = 0; i < PT; ++i)
-                if ((int)(nidx % PT) == i) { corev[i] = REACH_INF; reach[i] = REACH_INF; }
-        }
-        ccore = (uint32_t)__builtin_amdgcn_readlane((int)t.y, src);
-        const uint32_t cv = (uint32_t)__builtin_amdgcn_readlane((int)t.z, src);
-        cr = cv & 255; cc = cv >> 8;
-        cur = nidx;
-    }
-}
-
-// generic path for very large N: 64-bit keys, reachability kept in global memory
+// --------------------------------------------------------------------------------------
+// k_prim_ref: the library's Prim over the mutual-reachability graph, start node 0, smallest
+// reach then lowest index wins, edge = (last added node, new node, weight), one node per step:
+// the plainest correct form, which the tests use as the device reference of k_prim_lvl /
+// k_prim_lvl_big (SVC_PRIM_LVL=0).  Coordinates live in LDS, the running reachability in the
+// frame's workspace; one block minimum of (reach | index | core distance) and one barrier per step.
+// --------------------------------------------------------------------------------------
+// 64-bit keys reach << 33 | index << 17 | core distance; reachability in global memory, bit 31 = in the tree
 __device__ __forceinline__ void prim_global(const uint32_t *__restrict__ core_g, uint32_t *__restrict__ reach_g,
                                             hdb::Edge *__restrict__ mst, int N, const uint16_t *rc16,
                                             unsigned long long *slots) {
@@ -685,29 +624,17 @@ __device__ __forceinline__ void prim_global(const uint32_t *__restrict__ core_g,
     }
 }
 
-// The register-resident variant (points per thread) the legacy Prim uses for a map of N points: the first of 2, 4, 8
-// that holds N and is >= the handle's SVC_PRIM_PT, else 16 / 32, else 0 = the global-memory form.
-__device__ __forceinline__ int prim_variant(int N, int pt) {
-    if (N <= 2 * TB && pt <= 2) return 2;
-    if (N <= 4 * TB && pt <= 4) return 4;
-    if (N <= 8 * TB && pt <= 8) return 8;
-    if (N <= 16 * TB) return 16;
-    if (N <= 32 * TB) return 32;
-    return 0;
-}
-
 struct PrimFrame {
     uint8_t *ws; int N; uint16_t *rc16; unsigned long long *slots;
     const uint32_t *core; hdb::Edge *mst;
 };
-// common prologue of the legacy kernels: false = nothing to do for this map
-__device__ __forceinline__ bool prim_frame(const TailArgs &A, uint8_t *sm, PrimFrame &P, int n_min) {
+// false = nothing to do for this map (not clustered)
+__device__ __forceinline__ bool prim_frame(const TailArgs &A, uint8_t *sm, PrimFrame &P) {
     P.ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
     const int32_t *hdr = (const int32_t *)(P.ws + A.L.hdr);
-    if (!hdr[3]) return false;
-    P.N = hdr[0];
-    if (P.N <= n_min) return false;
-    P.slots = (unsigned long long *)sm;                               // [2][NW16] (uint4 or u64)
+    if (!hdr[SVC_HDR_CLUSTERED]) return false;
+    P.N = hdr[SVC_HDR_N];
+    P.slots = (unsigned long long *)sm;                               // [2][NW16] u64 (16 B reserved per slot)
     P.rc16 = (uint16_t *)(sm + 2 * NW16 * 16);                        // [N]
     P.core = (const uint32_t *)(P.ws + A.L.core);
     P.mst = (hdb::Edge *)(P.ws + A.L.mst);
@@ -719,35 +646,14 @@ __device__ __forceinline__ void prim_stage_points(const TailArgs &A, const PrimF
     __syncthreads();
 }
 
-// Legacy Prim (one node per step), one kernel per register-resident variant so that each has its own register
-// budget: k_prim_pt<2|4|8> carry no private segment (profiles/r03_kernel_resources.txt); launched back to back, a
-// map is taken by the kernel whose variant it is.  n_min: maps of at most n_min points are left to k_prim_lvl.
-template <int PT>
-__global__ __launch_bounds__(TB) void k_prim_pt(TailArgs A, int n_min) {
+__global__ __launch_bounds__(TB) void k_prim_ref(TailArgs A) {
     extern __shared__ uint8_t sm_prim[];
     PrimFrame P;
-    if (!prim_frame(A, sm_prim, P, n_min)) return;
-    if (prim_variant(P.N, A.prim_pt) != PT) return;
+    if (!prim_frame(A, sm_prim, P)) return;
     prim_stage_points(A, P);
     const long long t0 = wall_clock64();
-    prim_regs32<PT>(P.core, P.mst, P.N, P.rc16, (uint4 *)P.slots);
-    if (threadIdx.x == 0) ((int32_t *)(P.ws + A.L.hdr))[12] = (int)(wall_clock64() - t0);
-}
-
-// maps of more than 8192 points: 16 / 32 points per thread (these spill: the price of N up to 32768 in registers) or
-// reachability in global memory
-__global__ __launch_bounds__(TB) void k_prim_big(TailArgs A, int n_min) {
-    extern __shared__ uint8_t sm_prim[];
-    PrimFrame P;
-    if (!prim_frame(A, sm_prim, P, n_min)) return;
-    const int v = prim_variant(P.N, A.prim_pt);
-    if (v != 16 && v != 32 && v != 0) return;
-    prim_stage_points(A, P);
-    const long long t0 = wall_clock64();
-    if (v == 16) prim_regs32<16>(P.core, P.mst, P.N, P.rc16, (uint4 *)P.slots);
-    else if (v == 32) prim_regs32<32>(P.core, P.mst, P.N, P.rc16, (uint4 *)P.slots);
-    else prim_global(P.core, (uint32_t *)(P.ws + A.L.reach), P.mst, P.N, P.rc16, P.slots);
-    if (threadIdx.x == 0) ((int32_t *)(P.ws + A.L.hdr))[12] = (int)(wall_clock64() - t0);
+    prim_global(P.core, (uint32_t *)(P.ws + A.L.reach), P.mst, P.N, P.rc16, P.slots);
+    if (threadIdx.x == 0) ((int32_t *)(P.ws + A.L.hdr))[SVC_HDR_T_PRIM] = (int)(wall_clock64() - t0);
 }
 
 // --------------------------------------------------------------------------------------
@@ -866,27 +772,6 @@ __device__ __forceinline__ int lvl_extract(const unsigned long long *F64, int NF
                                            bool have_w0 = false, unsigned long long w0 = 0ull) {
     const int lane = threadIdx.x & 63;
     int ncand = 0;
-#ifdef LVL_EXTRACT_LOOP                                     // rounds 3-5 (A/B builds): one pass per word that holds members, all lanes placing that word's members
-    for (int wb = 0; wb < NF64 && ncand < 64; wb += 64) {
-        const int k = wb + lane;
-        const unsigned long long W = k < NF64 ? F64[k] : 0ull;
-        unsigned long long nz = __ballot(W != 0ull);
-        while (nz && ncand < 64) {
-            const int src = __builtin_ctzll(nz);
-            nz &= nz - 1ull;
-            const unsigned long long Wk = readlane_u64(W, src);
-            if ((Wk >> lane) & 1ull) {
-                const int rank = ncand + __popcll(Wk & ((1ull << lane) - 1ull));
-                if (rank < 64) cw[rank] = (uint32_t)((wb + src) * 64 + lane);
-            }
-            ncand += __popcll(Wk);
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    ncand = min(ncand, 64);
-    mycand = lane < ncand ? cw[lane] : LVL_NONE;
-    return ncand;
-#endif
     for (int wb = 0; wb < NF64 && ncand < 64; wb += 64) {
         const int k = wb + lane;
         const unsigned long long W = (have_w0 && wb == 0) ? w0 : (k < NF64 ? F64[k] : 0ull);      // have_w0: word `lane` of F as the caller read it (nothing has written F since)
@@ -1009,7 +894,7 @@ struct LvlSmall {                                  // <= LVL_CAP points: tnode /
     static constexpr int NB = LVL_NB;              // pending-batch table
     static constexpr bool STAGED = false;          // a batch is relaxed straight from S.tnode (LDS)
     static constexpr bool SHORTCUTS = true;        // round 6: F words kept in registers (fkeep), the commit re-uses the probe's reads, entrants from j4
-    static constexpr bool STAMPS = true;           // SVC_PRIM_LVL=3: phase stamps -> hdr[18..22]
+    static constexpr bool STAMPS = true;           // SVC_PRIM_LVL=3: phase stamps -> SVC_HDR_LVL_PHASE0 ..
 };
 struct LvlBig {                                    // > LVL_CAP points: tnode / corei / rc in the frame's workspace, R in L.absw + cmin / cbx
     static constexpr int NB = LVL_NBB;
@@ -1026,7 +911,7 @@ struct LvlRun {
     int n_rounds = 0;
     unsigned long long fkeep = 0ull;               // word `lane` of F as the F-empty test read it (maps of <= 4 096 points)
     bool fkeep_ok = false;
-    long long ph[5] = {0, 0, 0, 0, 0}, tp = 0;     // phase stamps (10 ns units): rise, extract, probe, accept + commit, mark
+    long long ph[SVC_HDR_LVL_PHASES] = {0, 0, 0, 0, 0}, tp = 0;     // phase stamps (10 ns units): rise, extract, probe, accept + commit, mark
     bool stamps = false;                           // SVC_PRIM_LVL=3: phase stamps (each costs a scalar memory round trip)
 };
 template <class P>
@@ -1342,8 +1227,8 @@ __device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
     typedef LvlSmall P;
     uint8_t *ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
     int32_t *hdr = (int32_t *)(ws + A.L.hdr);
-    if (!hdr[3]) return;
-    const int N = hdr[0];
+    if (!hdr[SVC_HDR_CLUSTERED]) return;
+    const int N = hdr[SVC_HDR_N];
     if (N > LVL_CAP) return;                                          // k_prim_lvl_big, launched after this kernel, takes it
     extern __shared__ uint8_t sm_lvl[];
     __shared__ int lds16[NW16];
@@ -1389,7 +1274,7 @@ __device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
     int n_rises = 0;
     st.tp = wall_clock64();
     st.stamps = (A.prim_lvl & 2) != 0;
-    if (tid == 0) hdr[24] = (int)(st.tp - t0);
+    if (tid == 0) hdr[SVC_HDR_T_LVL_SETUP] = (int)(st.tp - t0);
     __syncthreads();
     // minimum of R over the block (all wavefronts get it); one barrier
     auto block_min_R = [&]() -> uint32_t {
@@ -1506,8 +1391,8 @@ __device__ __forceinline__ void prim_lvl_body(const TailArgs &A) {
         if (!lvl_round<P>(S, st, mst, N, NF64)) break;
     }
     if (tid == 0) {
-        hdr[12] = (int)(wall_clock64() - t0); hdr[16] = st.n_rounds; hdr[17] = n_rises;
-        for (int i = 0; i < 5; ++i) hdr[18 + i] = (int)st.ph[i];
+        hdr[SVC_HDR_T_PRIM] = (int)(wall_clock64() - t0); hdr[SVC_HDR_LVL_ROUNDS] = st.n_rounds; hdr[SVC_HDR_LVL_RISES] = n_rises;
+        for (int i = 0; i < SVC_HDR_LVL_PHASES; ++i) hdr[SVC_HDR_LVL_PHASE0 + i] = (int)st.ph[i];
     }
 }
 __global__ __launch_bounds__(TB) void k_prim_lvl(TailArgs A) { prim_lvl_body(A); }
@@ -1523,9 +1408,9 @@ __global__ __launch_bounds__(TB) void k_prim_lvl(TailArgs A) { prim_lvl_body(A);
 //           instead of sitting in registers, a batch's 64 tree nodes are staged into a per-wave LDS slab (one coalesced load) before
 //           they are broadcast to the lanes, and more new nodes than the batch table holds are entered a table at a time.
 // Same (last node, new node, weight) sequence as k_prim_lvl and the library (tests: test_tail_maximum_size_all_pixels_set, the
-// 288-map comparison with the one-node-per-step kernels, the four maps around LVL_CAP, tools/soak_tail.py).  Replaces the
-// one-node-per-step k_prim_big (3 171 spilled VGPRs; 12 ms per map at N = 10 k, 3.3 s at 25 k: profiles/r04_tail_vs_N.txt) on
-// the default path.
+// 288-map comparison with the one-node-per-step kernel, the four maps around LVL_CAP, tools/soak_tail.py).  Replaced the
+// one-node-per-step Prim of the time (register-resident, spilling: 12 ms per map at N = 10 k, 3.3 s at 25 k:
+// profiles/r04_tail_vs_N.txt) on the default path.
 // --------------------------------------------------------------------------------------
 static size_t lvl_big_lds_bytes(int h, int w, int n_ring) {
     const size_t cap = (size_t)h * w;
@@ -1541,8 +1426,8 @@ __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
     typedef LvlBig P;
     uint8_t *ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
     int32_t *hdr = (int32_t *)(ws + A.L.hdr);
-    if (!hdr[3]) return;
-    const int N = hdr[0];
+    if (!hdr[SVC_HDR_CLUSTERED]) return;
+    const int N = hdr[SVC_HDR_N];
     if (N <= LVL_CAP) return;                                         // k_prim_lvl (inside k_tail_front) has done it
     extern __shared__ uint8_t sm_lvl[];
     __shared__ int lds16[NW16];
@@ -1589,7 +1474,7 @@ __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
     int done = 0, nb = 0, parity = 0;
     uint32_t swept = 0;
     int n_rises = 0;
-    if (tid == 0) hdr[24] = (int)(wall_clock64() - t0);
+    if (tid == 0) hdr[SVC_HDR_T_LVL_SETUP] = (int)(wall_clock64() - t0);
     // minimum of cmin over the block (all wavefronts get it); one barrier
     auto block_min_R = [&]() -> uint32_t {
         uint32_t best = LVL_RINF;
@@ -1719,7 +1604,7 @@ __device__ __forceinline__ void prim_lvl_big_body(const TailArgs &A) {
         }
         if (!lvl_round<P>(S, st, mst, N, NF64)) break;
     }
-    if (tid == 0) { hdr[12] = (int)(wall_clock64() - t0); hdr[16] = st.n_rounds; hdr[17] = n_rises; }
+    if (tid == 0) { hdr[SVC_HDR_T_PRIM] = (int)(wall_clock64() - t0); hdr[SVC_HDR_LVL_ROUNDS] = st.n_rounds; hdr[SVC_HDR_LVL_RISES] = n_rises; }
 }
 __global__ __launch_bounds__(TB) void k_prim_lvl_big(TailArgs A) { prim_lvl_big_body(A); }
 
@@ -2032,18 +1917,18 @@ __device__ __forceinline__ int cluster_phase(const TailArgs &A, uint8_t *ws, uin
     }
     __syncthreads();
     const bool built = build_wave(t, edges, N, A.mcs);       // the block is one wavefront (k_tree)
-    if (tid == 0) hdr[13] = (int)(wall_clock64() - t0);
+    if (tid == 0) hdr[SVC_HDR_T_BUILT] = (int)(wall_clock64() - t0);
     if (built) accumulate_wave(t, edges);
     if (tid == 0) {
         const bool ok = built;
         if (ok) S.nsel = hdb::choose(t);
         S.ok = ok;
-        hdr[4] = t.nclusters;
-        hdr[9] = (int)(wall_clock64() - t0);
+        hdr[SVC_HDR_NCLUSTERS] = t.nclusters;
+        hdr[SVC_HDR_T_HIERARCHY] = (int)(wall_clock64() - t0);
     }
     __syncthreads();
     if (!S.ok) return -2;
-    t.nclusters = hdr[4];
+    t.nclusters = hdr[SVC_HDR_NCLUSTERS];
     const int nsel = S.nsel;
     uint32_t *cweight = (uint32_t *)(ws + A.L.cweight);
     for (int c = tid; c < t.nclusters; c += nthr) cweight[c] = 0;
@@ -2067,9 +1952,9 @@ __device__ __forceinline__ int cluster_phase(const TailArgs &A, uint8_t *ws, uin
             if (b < 0 || cweight[c] > cweight[b] || (cweight[c] == cweight[b] && hdb::cluster_before(t, c, b))) b = c;
         }
         S.best = b;
-        hdr[1] = nsel;
-        hdr[2] = b;
-        hdr[10] = (int)(wall_clock64() - t0);
+        hdr[SVC_HDR_NSEL] = nsel;
+        hdr[SVC_HDR_KEPT] = b;
+        hdr[SVC_HDR_T_CHOSEN] = (int)(wall_clock64() - t0);
     }
     __syncthreads();
     return S.best;
@@ -2296,8 +2181,8 @@ __device__ __forceinline__ void sort_carve(uint8_t *lds, uint8_t *glob, int n, S
 __device__ __forceinline__ void sort_body(const TailArgs &A) {
     uint8_t *ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
     int32_t *hdr = (int32_t *)(ws + A.L.hdr);
-    if (!hdr[3]) return;
-    const int n = hdr[0] - 1;
+    if (!hdr[SVC_HDR_CLUSTERED]) return;
+    const int n = hdr[SVC_HDR_N] - 1;
     extern __shared__ uint8_t sm_sort[];
     const long long t0 = wall_clock64();
     const hdb::Edge *mst = (const hdb::Edge *)(ws + A.L.mst);
@@ -2308,7 +2193,7 @@ __device__ __forceinline__ void sort_body(const TailArgs &A) {
     uint16_t *perm = (uint16_t *)(ws + A.L.eb);            // sorted position -> Prim position
     np_argsort_block(a, st, n, perm, sh);
     for (int i = threadIdx.x; i < n; i += TB) ea[i] = mst[perm[i]];
-    if (threadIdx.x == 0) hdr[8] = (int)(wall_clock64() - t0);
+    if (threadIdx.x == 0) hdr[SVC_HDR_T_SORTED] = (int)(wall_clock64() - t0);
 }
 __global__ __launch_bounds__(TB) void k_sort(TailArgs A) { sort_body(A); }
 
@@ -2327,8 +2212,8 @@ __global__ __launch_bounds__(TB) void k_argsort_test(const uint32_t *keys, int n
 __global__ __launch_bounds__(64) void k_tree(TailArgs A) {
     uint8_t *ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
     int32_t *hdr = (int32_t *)(ws + A.L.hdr);
-    if (!hdr[3] || hdr[23]) return;
-    const int N = hdr[0];
+    if (!hdr[SVC_HDR_CLUSTERED] || hdr[SVC_HDR_TREE_PAR]) return;
+    const int N = hdr[SVC_HDR_N];
     extern __shared__ uint8_t sm_tree[];
     __shared__ TreeShared S;
     const long long t0 = wall_clock64();
@@ -2336,7 +2221,7 @@ __global__ __launch_bounds__(64) void k_tree(TailArgs A) {
     int best = -2;
     if (N <= TREE_LDS_CAP) best = cluster_phase<true>(A, ws, sm_tree, S, hdr, N, t0);
     if (best == -2) best = cluster_phase<false>(A, ws, sm_tree, S, hdr, N, t0);
-    if (threadIdx.x == 0) { hdr[14] = (int)(clock64() - c0); hdr[15] = (int)(wall_clock64() - t0); }
+    if (threadIdx.x == 0) { hdr[SVC_HDR_TREE_CLOCKS] = (int)(clock64() - c0); hdr[SVC_HDR_T_TREE] = (int)(wall_clock64() - t0); }
 }
 
 // --------------------------------------------------------------------------------------
@@ -2387,11 +2272,7 @@ static size_t tp_lds_bytes(int hw, int mcs, int *cap_clusters, int *cap_clusters
 #define TP_LDS_BUDGET (160 * 1024 - 4096)     // LDS a tail workgroup may ask for (experiment builds: 78 KB = two workgroups per CU)
 #endif
     const size_t budget = TP_LDS_BUDGET;
-#ifdef TP_CC_EXACT                                         // (experiment builds with a small budget: every cluster the budget holds, not the next power-of-two fraction)
-    if (per_edge + (size_t)cc * 48 + 512 > budget) cc = std::max(8, (int)((budget > per_edge + 512 ? budget - per_edge - 512 : 0) / 48));
-#else
     while (cc > 8 && per_edge + (size_t)cc * 48 + 512 > budget) cc /= 2;
-#endif
     *cap_clusters = cc;
     const size_t total = per_edge + (size_t)cc * 48 + 512;
     if (cap_clusters_huge) {                               // MODE 2 keeps only the rank-maxima levels in LDS: the rest of the launch's allocation is cluster tables
@@ -2428,7 +2309,7 @@ template <int MODE>
 __device__ __forceinline__ void tp_body(const TailArgs &A, int cap_clusters, uint8_t *ws, int32_t *hdr, int N, uint8_t *sm_tp,
                                         int *lds16, int &sh_nc, int &sh_nsel) {
     const int E = N - 1, mcs = A.mcs;
-#define TP_STAMP(i) do { if (tid == 0) hdr[25 + (i)] = (int)(wall_clock64() - t0); } while (0)
+#define TP_STAMP(i) do { if (tid == 0) hdr[SVC_HDR_TP_STAMP0 + (i)] = (int)(wall_clock64() - t0); } while (0)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long t0 = wall_clock64();
     constexpr bool BIG = MODE >= 1, HUGE = MODE == 2;
@@ -2598,7 +2479,7 @@ __device__ __forceinline__ void tp_body(const TailArgs &A, int cap_clusters, uin
     }
     __syncthreads();
     const int nc = sh_nc;
-    if (nc > cap_clusters) return;                                     // tables too small: k_tree redoes the map (hdr[23] stays 0)
+    if (nc > cap_clusters) return;                                     // tables too small: k_tree redoes the map (SVC_HDR_TREE_PAR stays 0)
     TP_STAMP(2);
     // ---- pointer jumping down the big-child chains: every absorption learns its cluster's first edge and its distance to it
     uint32_t *ja = jA, *jb = jB;
@@ -2649,7 +2530,7 @@ __device__ __forceinline__ void tp_body(const TailArgs &A, int cap_clusters, uin
         rowlist[C.off[c] + (C.len[c] - 1 - (j >> 16))] = (uint16_t)k;  // top of the chain first = descending rank
     }
     __syncthreads();
-    if (tid == 0) hdr[13] = (int)(wall_clock64() - t0);
+    if (tid == 0) hdr[SVC_HDR_T_BUILT] = (int)(wall_clock64() - t0);
     // ---- stabilities: one wavefront per cluster, rows in the library's order (hdb::accumulate), terms 64 at a time
     for (int c = wave; c < nc; c += NW16) {
         const uint32_t bw = C.birthw[c];
@@ -2704,8 +2585,8 @@ __device__ __forceinline__ void tp_body(const TailArgs &A, int cap_clusters, uin
             else C.rep[c] = (int16_t)hdb::ROOT_NOISE;
         }
         sh_nsel = nsel;
-        hdr[4] = nc;
-        hdr[9] = (int)(wall_clock64() - t0);
+        hdr[SVC_HDR_NCLUSTERS] = nc;
+        hdr[SVC_HDR_T_HIERARCHY] = (int)(wall_clock64() - t0);
     }
     // ---- (meanwhile) the edge at which every small union's component falls out: first ancestor that is not one
     uint16_t *fo = (uint16_t *)jb;                                      // the spare jump buffer
@@ -2763,11 +2644,11 @@ __device__ __forceinline__ void tp_body(const TailArgs &A, int cap_clusters, uin
             if (C.rep[c] != c) continue;
             if (b < 0 || C.weight[c] > C.weight[b] || (C.weight[c] == C.weight[b] && before(c, b))) b = c;
         }
-        hdr[1] = nsel;
-        hdr[2] = b;
-        hdr[23] = 1;                                                    // done: k_tree leaves the map alone
-        hdr[10] = (int)(wall_clock64() - t0);
-        hdr[15] = hdr[10];
+        hdr[SVC_HDR_NSEL] = nsel;
+        hdr[SVC_HDR_KEPT] = b;
+        hdr[SVC_HDR_TREE_PAR] = 1;                                                    // done: k_tree leaves the map alone
+        hdr[SVC_HDR_T_CHOSEN] = (int)(wall_clock64() - t0);
+        hdr[SVC_HDR_T_TREE] = hdr[SVC_HDR_T_CHOSEN];
     }
 }
 #undef TP_ORDER
@@ -2776,8 +2657,8 @@ __device__ __forceinline__ void tp_body(const TailArgs &A, int cap_clusters, uin
 __device__ __forceinline__ void tree_par_body(const TailArgs &A, int cap_clusters, int cap_clusters_huge) {
     uint8_t *ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
     int32_t *hdr = (int32_t *)(ws + A.L.hdr);
-    if (!hdr[3]) return;
-    const int N = hdr[0];
+    if (!hdr[SVC_HDR_CLUSTERED]) return;
+    const int N = hdr[SVC_HDR_N];
     if (N > TP_CAP_HUGE) return;                                       // (never: the tail takes maps of up to 255 x 255)
     extern __shared__ uint8_t sm_tp[];
     __shared__ int lds16[NW16];
@@ -2793,8 +2674,8 @@ __device__ __forceinline__ void finish_body(const TailArgs &A) {
     const int f = A.order[blockIdx.x];
     uint8_t *ws = A.ws + (size_t)(A.slot0 + (int)blockIdx.x) * A.ws_stride;
     int32_t *hdr = (int32_t *)(ws + A.L.hdr);
-    if (hdr[30]) return;                                               // k_tail_back has finished this map already
-    const int N = hdr[0];
+    if (hdr[SVC_HDR_BACK_DONE]) return;                                               // k_tail_back has finished this map already
+    const int N = hdr[SVC_HDR_N];
     const int hw = A.h * A.w;
     uint8_t *map = A.maps + (size_t)f * hw;
     extern __shared__ uint8_t sm_fin[];
@@ -2802,10 +2683,10 @@ __device__ __forceinline__ void finish_body(const TailArgs &A) {
     __shared__ uint32_t box[4];
     const int tid = threadIdx.x;
     if (tid < 4) box[tid] = 255u;                          // (published by the barrier behind the map copy)
-    const bool clustered = hdr[3] != 0;
+    const bool clustered = hdr[SVC_HDR_CLUSTERED] != 0;
     long long t0 = 0;
     if (tid == 0) t0 = wall_clock64();
-    const int best = clustered ? hdr[2] : -1;
+    const int best = clustered ? hdr[SVC_HDR_KEPT] : -1;
     // ---- map phase: the LDS buffer now holds the map (the hierarchy state is no longer needed)
     uint8_t *m0 = sm_fin;                            // [hw]
     uint8_t *m1 = sm_fin + (hw + 15) / 16 * 16;      // [hw]
@@ -2867,11 +2748,11 @@ __device__ __forceinline__ void finish_body(const TailArgs &A) {
         }
         if (A.stats) {
             A.stats[4 * f] = N;
-            A.stats[4 * f + 1] = clustered ? hdr[1] : 0;
-            A.stats[4 * f + 2] = clustered ? hdr[2] : -1;
+            A.stats[4 * f + 1] = clustered ? hdr[SVC_HDR_NSEL] : 0;
+            A.stats[4 * f + 2] = clustered ? hdr[SVC_HDR_KEPT] : -1;
             A.stats[4 * f + 3] = (int)cnt;
         }
-        hdr[11] = (int)(wall_clock64() - t0);
+        hdr[SVC_HDR_T_FINISHED] = (int)(wall_clock64() - t0);
     }
 }
 __global__ __launch_bounds__(TB) void k_finish(TailArgs A) { finish_body(A); }
@@ -2898,10 +2779,10 @@ __global__ __launch_bounds__(TB) void k_tail_back(TailArgs A, int cap_clusters, 
     __syncthreads();
     tree_par_body(A, cap_clusters, cap_clusters_huge);
     __syncthreads();
-    if (hdr[3] && !hdr[23]) return;                                        // hierarchy not done here: k_tree, then k_finish
+    if (hdr[SVC_HDR_CLUSTERED] && !hdr[SVC_HDR_TREE_PAR]) return;                                        // hierarchy not done here: k_tree, then k_finish
     finish_body(A);
     __syncthreads();
-    if (threadIdx.x == 0) hdr[30] = 1;
+    if (threadIdx.x == 0) hdr[SVC_HDR_BACK_DONE] = 1;
 }
 
 // --------------------------------------------------------------------------------------
@@ -3016,9 +2897,254 @@ extern "C" int svc_debug_round_plan(const uint8_t *flags_host, int n, int32_t *r
     return any ? maxd + 1 : 0;
 }
 
+// ---- svc_cluster_center, step by step: argument checks, shrink tables, round list and its upload, launches
+static int check_cluster_args(SvcHandle *h, const uint8_t *maps, int n, int height, int width, const SvcParams *params, const double *xy) {
+    if (!h || !params || n < 0 || (n > 0 && (!maps || !xy)) || height < 1 || width < 1) {     // n = 0: a no-op, null buffers allowed
+        svc_set_error("svc_cluster_center: invalid argument");
+        return SVC_E_INVALID;
+    }
+    if (height > 255 || width > 255 || height * width > 65535) {
+        svc_set_error("svc_cluster_center: map %dx%d exceeds the supported 255x255", height, width);
+        return SVC_E_INVALID;
+    }
+    if (params->struct_size != sizeof(SvcParams)) {
+        svc_set_error("svc_cluster_center: SvcParams.struct_size is %u, this library expects %zu (ABI %d): rebuild the binding "
+                      "against include/svc.h", params->struct_size, sizeof(SvcParams), SVC_ABI_VERSION);
+        return SVC_E_INVALID;
+    }
+    if (params->hdbscan_min < 2) { svc_set_error("svc_cluster_center: hdbscan_min must be >= 2"); return SVC_E_INVALID; }
+    if (params->resize_factor < 1 || params->resize_factor > 16) { svc_set_error("svc_cluster_center: resize_factor must be an integer in 1..16"); return SVC_E_INVALID; }
+    if (n > DEPTH_SLOT) { svc_set_error("svc_cluster_center: more than %d maps per call", DEPTH_SLOT); return SVC_E_INVALID; }
+    return SVC_OK;
+}
+
+// resize_factor > 1: the INTER_LINEAR tables full size -> (sh, sw) and back, and room for n shrunk maps (h->rs_maps)
+static int ensure_shrink_tables(SvcHandle *h, int n, int full_h, int full_w, int sh, int sw, int factor, const int **down, const int **up) {
+    int rc;
+    auto key = std::make_tuple(full_h, full_w, factor);
+    auto it = h->rs_tabs.find(key);
+    if (it == h->rs_tabs.end()) {       // tables are keyed by shape and never rewritten (earlier calls may still read theirs)
+        std::pair<DevBuf, DevBuf> t;
+        if ((rc = upload_map_tab(t.first, full_h, full_w, sh, sw, (double)factor, (double)factor))) return rc;
+        if ((rc = upload_map_tab(t.second, sh, sw, full_h, full_w, (double)sh / full_h, (double)sw / full_w))) return rc;
+        it = h->rs_tabs.emplace(key, t).first;
+    }
+    *down = (const int *)it->second.first.p;
+    *up = (const int *)it->second.second.p;
+    return h->rs_maps.ensure((size_t)n * sh * sw);
+}
+
+// The maps of a call sorted by round (stable), one slice per round, on the host and on the device.
+struct RoundList {
+    std::vector<uint16_t> order;        // [0, n): maps sorted by round; [n, n + blend0.size()): the round-0 blend targets
+    std::vector<int> round_start;       // [maxd + 2]: round r is order[round_start[r] .. round_start[r + 1])
+    std::vector<uint16_t> blend0;       // round-0 maps that take a blend from a held predecessor first
+    int maxd = 0, n_proc = 0;           // last round; maps the call processes (the others are held)
+    const uint16_t *dev = nullptr;      // `order` on the device
+};
+static const size_t TAIL_LISTS_BYTES = 8 * 4 * (size_t)DEPTH_SLOT;     // a ring of 8 round lists at the head of the tail workspace
+
+// A round's kernels are launched over the maps of THAT round only.  (One workgroup per map of the call in every round -- 31 of
+// 32 exiting at once in the follower rounds -- still has each of them claim a whole CU's wave slots / up to 154 KB of LDS
+// before it can exit: in the pipelined run those claims keep the network's workgroups off the CUs.)
+static int make_round_list(const uint8_t *flags, int n, RoundList &R) {
+    const int HELD = 255;
+    std::vector<uint8_t> depth;
+    int rc = plan_rounds(flags, n, depth, R.blend0, R.maxd);
+    if (rc) return rc;
+    R.order.assign(2 * (size_t)n, 0);
+    R.round_start.assign(R.maxd + 2, 0);
+    for (int i = 0; i < n; ++i) if (depth[i] != HELD) ++R.round_start[depth[i] + 1];
+    for (int r = 0; r <= R.maxd; ++r) R.round_start[r + 1] += R.round_start[r];
+    std::vector<int> fill(R.round_start.begin(), R.round_start.end() - 1);
+    for (int i = 0; i < n; ++i) if (depth[i] != HELD) R.order[fill[depth[i]]++] = (uint16_t)i;
+    for (size_t i = 0; i < R.blend0.size(); ++i) R.order[n + i] = R.blend0[i];
+    R.n_proc = R.round_start[R.maxd + 1];
+    return SVC_OK;
+}
+
+// The tail workspace -- the round lists (a ring of 8 slots, fixed size) and behind them one slot of `frame_bytes` per map that
+// takes part in a round (a streamed call spans up to twice as many maps as it processes: the held ones need none); grown in
+// steps of 32 slots, since a re-allocation is a hipFree, i.e. a device-wide synchronisation, and used to happen whenever a
+// call was one map longer than any before it -- and the list's upload.  The lists travel through a small ring of pinned host
+// slots so that the upload is asynchronous (up to 8 calls may be in flight on the stream before a slot is reused).
+static int upload_round_list(SvcHandle *h, int n, size_t frame_bytes, hipStream_t s, RoundList &R) {
+    int rc = h->tail_ws.ensure(TAIL_LISTS_BYTES + frame_bytes * std::max<size_t>(32, ((size_t)R.n_proc + 31) / 32 * 32));
+    if (rc) return rc;
+    if (!h->depth_pinned) SVC_HIP(hipHostMalloc((void **)&h->depth_pinned, TAIL_LISTS_BYTES, hipHostMallocDefault));
+    const int slot = h->depth_slot++ & 7;
+    if (h->depth_ev[slot]) SVC_HIP(hipEventSynchronize(h->depth_ev[slot]));      // the upload that last used this slot has run
+    else SVC_HIP(hipEventCreateWithFlags(&h->depth_ev[slot], hipEventDisableTiming));
+    uint16_t *order_dev = (uint16_t *)((uint8_t *)h->tail_ws.p + (size_t)slot * 4 * DEPTH_SLOT);
+    memcpy(h->depth_pinned + (size_t)slot * 4 * DEPTH_SLOT, R.order.data(), (size_t)n * 4);
+    SVC_HIP(hipMemcpyAsync(order_dev, h->depth_pinned + (size_t)slot * 4 * DEPTH_SLOT, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    SVC_HIP(hipEventRecord(h->depth_ev[slot], s));
+    R.dev = order_dev;
+    return SVC_OK;
+}
+
+// The tail kernels that may ask for more dynamic LDS than the default 64 KB, and how much each may ask for; raised once per
+// handle = per device (the attribute is per device)
+static int raise_tail_lds_limits(SvcHandle *h) {
+    static const struct { const void *kfn; int bytes; } limits[] = {
+        {(const void *)k_core, 160 * 1024 - 1024},
+        {(const void *)k_prim_ref, 160 * 1024 - 1024},
+        {(const void *)k_prim_lvl, 160 * 1024 - 256},        // (255 x 255 maps: 162 896 bytes with eight workers; static LDS 136)
+        {(const void *)k_prim_lvl_big, 160 * 1024 - 1024},
+        {(const void *)k_finish, 160 * 1024 - 8 * 1024},
+        {(const void *)k_tree, 160 * 1024 - 8 * 1024},
+        {(const void *)k_tree_par, 160 * 1024 - 1024},
+        {(const void *)k_tail_front, 160 * 1024 - 256},      // (as k_prim_lvl)
+        {(const void *)k_tail_back, 160 * 1024 - 1024},
+        {(const void *)k_sort, SORT_LDS_BYTES},
+    };
+    if (h->lds_attr_done.count(limits[0].kfn)) return SVC_OK;
+    for (const auto &l : limits) RC_TAIL(raise_lds_limit(h, l.kfn, l.bytes));
+    return SVC_OK;
+}
+
+// What the launches of a call have in common: LDS requests, cluster-table capacities, which form a round takes
+struct TailPlan {
+    size_t lds_compact, lds_core, lds_prim_ref, lds_lvl, lds_lvl_big, lds_tp, lds_fin, lds_front, lds_back;
+    int cap_cl, cap_cl_huge;            // condensed clusters k_tree_par's LDS tables hold (maps of up to / beyond TP_CAP_BIG points)
+    bool fused;                         // a round is k_tail_front + k_tail_back (else one launch per stage)
+    bool lvl_big;                       // a map may have more than LVL_CAP points: k_prim_lvl_big follows k_prim_lvl
+    bool tree_fallback;                 // a map may be left to the serial builder: k_tree (and k_finish) follow
+};
+static TailPlan plan_tail(const SvcHandle *h, const SvcParams *params, int height, int width) {
+    TailPlan T;
+    const int hw = height * width, mcs = params->hdbscan_min;
+    T.lds_compact = (size_t)(hw + 15) / 16 * 16;
+    T.lds_core = T.lds_compact + (size_t)h->tail_n_offsets * 4 + (size_t)h->tail_n_offsets1 * 4;
+    T.lds_prim_ref = 2 * NW16 * 16 + (size_t)hw * 2;
+    T.lds_lvl = lvl_lds_bytes(height, width, h->tail_n_offsets);
+    T.lds_lvl_big = lvl_big_lds_bytes(height, width, h->tail_n_offsets);
+    T.lds_tp = tp_lds_bytes(hw, mcs, &T.cap_cl, &T.cap_cl_huge);
+    T.lds_fin = 2 * T.lds_compact;
+    T.lds_front = std::max({T.lds_compact, T.lds_core, T.lds_lvl});
+    T.lds_back = std::max({(size_t)SORT_LDS_BYTES, T.lds_tp, T.lds_fin});
+    T.fused = params->clust_filt && h->tail_merge && h->prim_lvl && h->tree_par;
+    T.lvl_big = h->prim_lvl && hw > LVL_CAP;
+    // the serial builder: maps the parallel one does not hold in LDS (more points or clusters), or all (SVC_TREE_PAR=0)
+    T.tree_fallback = !h->tree_par || hw > TP_CAP_HUGE || hdb::max_clusters(std::min(hw, TP_CAP_BIG), mcs) > T.cap_cl ||
+                      (hw > TP_CAP_BIG && hdb::max_clusters(std::min(hw, TP_CAP_HUGE), mcs) > T.cap_cl_huge);
+    return T;
+}
+
+// The cluster filter and the centre for the m maps of one round (A.order, A.slot0): every kernel has one launch here.  Fused,
+// k_tail_front stands in for k_compact, k_core and k_prim_lvl and k_tail_back for k_sort, k_tree_par and k_finish; what they
+// leave -- maps of more than LVL_CAP points, maps for the serial builder -- goes to the stand-alone kernels behind them.
+static int launch_round(SvcHandle *h, const TailArgs &A, const TailPlan &T, int m, hipStream_t s) {
+    if (!T.fused) {
+        {
+            ProfScope ps(h, SVC_K_COMPACT, s);
+            k_compact<<<m, TB, T.lds_compact, s>>>(A);
+            SVC_CHECK_LAUNCH();
+        }
+        if (A.clust_filt) {
+            ProfScope ps(h, SVC_K_CORE, s);
+            k_core<<<m, TB, T.lds_core, s>>>(A);
+            SVC_CHECK_LAUNCH();
+        }
+    }
+    if (A.clust_filt) {
+        ProfScope ps(h, SVC_K_PRIM, s);
+        if (T.fused) k_tail_front<<<m, TB, T.lds_front, s>>>(A);
+        else if (h->prim_lvl) k_prim_lvl<<<m, TB, T.lds_lvl, s>>>(A);
+        else k_prim_ref<<<m, TB, T.lds_prim_ref, s>>>(A);
+        SVC_CHECK_LAUNCH();
+        if (T.lvl_big) { k_prim_lvl_big<<<m, TB, T.lds_lvl_big, s>>>(A); SVC_CHECK_LAUNCH(); }
+    }
+    ProfScope ps(h, SVC_K_FINISH, s);
+    if (T.fused) {
+        k_tail_back<<<m, TB, T.lds_back, s>>>(A, T.cap_cl, T.cap_cl_huge);
+        SVC_CHECK_LAUNCH();
+    } else if (A.clust_filt) {
+        k_sort<<<m, TB, SORT_LDS_BYTES, s>>>(A);
+        SVC_CHECK_LAUNCH();
+        if (h->tree_par) { k_tree_par<<<m, TB, T.lds_tp, s>>>(A, T.cap_cl, T.cap_cl_huge); SVC_CHECK_LAUNCH(); }
+    }
+    if (A.clust_filt && T.tree_fallback) { k_tree<<<m, 64, FIN_LDS_BYTES, s>>>(A); SVC_CHECK_LAUNCH(); }
+    if (!T.fused || T.tree_fallback) { k_finish<<<m, TB, T.lds_fin, s>>>(A); SVC_CHECK_LAUNCH(); }
+    return SVC_OK;
+}
+
 static int cluster_center_impl(SvcHandle *h, uint8_t *maps, int n, int height, int width,
-                                  const uint8_t *blend_flags_host, const SvcParams *params, double *xy,
-                                  int32_t *stats, void *stream);
+                               const uint8_t *blend_flags_host, const SvcParams *params, double *xy,
+                               int32_t *stats, void *stream) {
+    RC_TAIL(check_cluster_args(h, maps, n, height, width, params, xy));
+    if (n == 0) return SVC_OK;
+    SVC_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    RC_TAIL(ensure_ring(h));
+    // best settings: the cluster filter runs on maps shrunk by resize_factor and the centre is taken on the nearest-shrunk map,
+    // both of the size cv2.resize gives fx = fy = 1 / factor (cvRound, half to even).  cv2.resize refuses an empty size, so a
+    // map that shrinks to nothing is an error whenever one of the two would shrink it (smartVidCrop.py:1080, :1184).
+    const int full_h = height, full_w = width;
+    const int rs_h = (int)lrint((double)full_h * (1.0 / params->resize_factor));
+    const int rs_w = (int)lrint((double)full_w * (1.0 / params->resize_factor));
+    if (params->resize_factor > 1 && (params->clust_filt || params->com_km) && (rs_h < 1 || rs_w < 1)) {
+        svc_set_error("svc_cluster_center: map %dx%d too small for resize_factor %d", full_h, full_w, params->resize_factor);
+        return SVC_E_INVALID;
+    }
+    const int factor = params->clust_filt ? params->resize_factor : 1;
+    uint8_t *full_maps = maps;
+    const int *rs_down = nullptr, *rs_up = nullptr;
+    if (factor > 1) {
+        height = rs_h;
+        width = rs_w;
+        RC_TAIL(ensure_shrink_tables(h, n, full_h, full_w, height, width, factor, &rs_down, &rs_up));
+        maps = (uint8_t *)h->rs_maps.p;
+    }
+    const FrameWS L = make_layout(height * width, hdb::max_clusters(height * width, params->hdbscan_min));
+    RoundList R;
+    RC_TAIL(make_round_list(blend_flags_host, n, R));
+    RC_TAIL(upload_round_list(h, n, L.total, s, R));
+    h->tail_frames = n; h->tail_h = height; h->tail_w = width; h->tail_frame_stride = L.total;
+    h->tail_slot_of.assign((size_t)n, -1);                       // (svc_debug_cluster_state: map -> workspace slot)
+    for (int i = 0; i < R.n_proc; ++i) h->tail_slot_of[R.order[i]] = i;
+    TailArgs A;
+    A.maps = maps; A.ws = (uint8_t *)h->tail_ws.p + TAIL_LISTS_BYTES; A.ws_stride = L.total; A.order = R.dev; A.slot0 = 0;
+    A.n = n; A.h = height; A.w = width; A.dW = make_fdiv(width);
+    A.mcs = params->hdbscan_min; A.min_samples = params->hdbscan_min_samples; A.select_sum = params->select_sum;
+    A.op_close = params->op_close; A.clust_filt = params->clust_filt;
+    RC_TAIL(ensure_ring_delta(h, width, &A.ring_delta));
+    A.ring = (const uint32_t *)h->tail_offsets.p; A.n_ring = h->tail_n_offsets; A.n_ring1 = h->tail_n_offsets1;
+    A.ring_cnt = (const uint16_t *)h->tail_ring_cnt.p; A.prim_lvl = h->prim_lvl;
+    A.xy = xy; A.stats = stats; A.L = L;
+    const TailPlan T = plan_tail(h, params, height, width);
+    RC_TAIL(raise_tail_lds_limits(h));
+    for (int r = 0; r <= R.maxd; ++r) {
+        const int m = R.round_start[r + 1] - R.round_start[r];   // maps of this round
+        const uint16_t *ord = R.dev + R.round_start[r];
+        A.order = ord; A.slot0 = R.round_start[r];
+        // the round's blends: every map of a later round from its predecessor; in round 0 the maps whose predecessor is held (final already)
+        const int n_blend = r == 0 ? (int)R.blend0.size() : m;
+        if (n_blend) {
+            k_blend<<<dim3(8, n_blend), 256, 0, s>>>(full_maps, r == 0 ? R.dev + n : ord, full_h * full_w);
+            SVC_CHECK_LAUNCH();
+        }
+        if (m == 0) continue;                                // every map of the call is held
+        if (factor > 1) {
+            k_map_resize<<<dim3(8, m), 256, 0, s>>>(full_maps, maps, rs_down, ord, full_h, full_w, height, width);
+            SVC_CHECK_LAUNCH();
+        }
+        RC_TAIL(launch_round(h, A, T, m, s));
+        if (factor > 1) {
+            k_map_resize<<<dim3(16, m), 256, 0, s>>>(maps, full_maps, rs_up, ord, height, width, full_h, full_w);
+            SVC_CHECK_LAUNCH();
+        }
+    }
+    if (!params->com_km) {                 // centre = arg-max pixel of the final full-size map (held maps keep what the caller has)
+        k_centre_argmax<<<n, 256, 0, s>>>(full_maps, full_h, full_w, make_fdiv(full_w), xy);
+        SVC_CHECK_LAUNCH();
+    } else if (params->resize_factor > 1) {       // centre of the nearest-neighbour shrunk final map (also when clust_filt is off)
+        k_centre_nearest<<<n, 256, 0, s>>>(full_maps, full_h, full_w, rs_h, rs_w, params->resize_factor, xy);
+        SVC_CHECK_LAUNCH();
+    }
+    return SVC_OK;
+}
+
 // SVC_HOST_TIMING=1: the call's host-side duration goes to stderr (every 100 calls; every call above 2 ms) -- a call is
 // supposed to enqueue and return; a workspace re-allocation or a full upload ring shows up here
 static std::atomic<long long> g_cc_ns{0}, g_cc_calls{0}, g_cc_max{0};
@@ -3036,230 +3162,6 @@ extern "C" int svc_cluster_center(SvcHandle *h, uint8_t *maps, int n, int height
     if (c % 100 == 0) fprintf(stderr, "svc_cluster_center host time: %lld calls, mean %.1f us, max %.1f us\n", c, g_cc_ns / 1e3 / c, g_cc_max / 1e3);
     return rc;
 }
-static int cluster_center_impl(SvcHandle *h, uint8_t *maps, int n, int height, int width,
-                                  const uint8_t *blend_flags_host, const SvcParams *params, double *xy,
-                                  int32_t *stats, void *stream) {
-    if (!h || !params || n < 0 || (n > 0 && (!maps || !xy)) || height < 1 || width < 1) {     // n = 0: a no-op, null buffers allowed
-        svc_set_error("svc_cluster_center: invalid argument");
-        return SVC_E_INVALID;
-    }
-    if (height > 255 || width > 255 || height * width > 65535) {
-        svc_set_error("svc_cluster_center: map %dx%d exceeds the supported 255x255", height, width);
-        return SVC_E_INVALID;
-    }
-    if (params->struct_size != sizeof(SvcParams)) {
-        svc_set_error("svc_cluster_center: SvcParams.struct_size is %u, this library expects %zu (ABI %d): rebuild the binding "
-                      "against include/svc.h", params->struct_size, sizeof(SvcParams), SVC_ABI_VERSION);
-        return SVC_E_INVALID;
-    }
-    if (params->hdbscan_min < 2) { svc_set_error("svc_cluster_center: hdbscan_min must be >= 2"); return SVC_E_INVALID; }
-    if (params->resize_factor < 1 || params->resize_factor > 16) { svc_set_error("svc_cluster_center: resize_factor must be an integer in 1..16"); return SVC_E_INVALID; }
-    if (n == 0) return SVC_OK;
-    SVC_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    int rc = ensure_ring(h);
-    if (rc) return rc;
-    // best settings: the cluster filter runs on maps shrunk by resize_factor and the centre is taken on the nearest-shrunk map,
-    // both of the size cv2.resize gives fx = fy = 1 / factor (cvRound, half to even).  cv2.resize refuses an empty size, so a
-    // map that shrinks to nothing is an error whenever one of the two would shrink it (smartVidCrop.py:1080, :1184).
-    const int full_h = height, full_w = width;
-    const int rs_h = (int)lrint((double)full_h * (1.0 / params->resize_factor));
-    const int rs_w = (int)lrint((double)full_w * (1.0 / params->resize_factor));
-    if (params->resize_factor > 1 && (params->clust_filt || params->com_km) && (rs_h < 1 || rs_w < 1)) {
-        svc_set_error("svc_cluster_center: map %dx%d too small for resize_factor %d", full_h, full_w, params->resize_factor);
-        return SVC_E_INVALID;
-    }
-    const int factor = params->clust_filt ? params->resize_factor : 1;
-    uint8_t *full_maps = maps;
-    const int *rs_down = nullptr, *rs_up = nullptr;
-    if (factor > 1) {
-        height = rs_h;
-        width = rs_w;
-        auto key = std::make_tuple(full_h, full_w, factor);
-        auto it = h->rs_tabs.find(key);
-        if (it == h->rs_tabs.end()) {       // tables are keyed by shape and never rewritten (earlier calls may still read theirs)
-            std::pair<DevBuf, DevBuf> t;
-            if ((rc = upload_map_tab(t.first, full_h, full_w, height, width, (double)factor, (double)factor))) return rc;
-            if ((rc = upload_map_tab(t.second, height, width, full_h, full_w, (double)height / full_h, (double)width / full_w))) return rc;
-            it = h->rs_tabs.emplace(key, t).first;
-        }
-        rs_down = (const int *)it->second.first.p;
-        rs_up = (const int *)it->second.second.p;
-        if ((rc = h->rs_maps.ensure((size_t)n * height * width))) return rc;
-        maps = (uint8_t *)h->rs_maps.p;
-    }
-    const int cap = height * width;
-    const int mc = hdb::max_clusters(cap, params->hdbscan_min);
-    FrameWS L = make_layout(cap, mc);
-    const int HELD = 255;
-    std::vector<uint8_t> depth;
-    std::vector<uint16_t> blend0;                       // round-0 maps that take a blend from a held predecessor first
-    int maxd = 0;
-    if ((rc = plan_rounds(blend_flags_host, n, depth, blend0, maxd))) return rc;
-    if (n > DEPTH_SLOT) { svc_set_error("svc_cluster_center: more than %d maps per call", DEPTH_SLOT); return SVC_E_INVALID; }
-    // A round's kernels are launched over the maps of THAT round only: the list of all maps sorted by round (stable),
-    // one slice per round.  (One workgroup per map of the call in every round -- 31 of 32 exiting at once in the
-    // follower rounds -- still has each of them claim a whole CU's wave slots / up to 154 KB of LDS before it can exit:
-    // in the pipelined run those claims keep the network's workgroups off the CUs.)
-    std::vector<uint16_t> order(2 * (size_t)n, 0);      // [0, n): maps sorted by round; [n, n + blend0.size()): the round-0 blend targets
-    std::vector<int> round_start(maxd + 2, 0);
-    for (int i = 0; i < n; ++i) if (depth[i] != HELD) ++round_start[depth[i] + 1];
-    for (int r = 0; r <= maxd; ++r) round_start[r + 1] += round_start[r];
-    {
-        std::vector<int> fill(round_start.begin(), round_start.end() - 1);
-        for (int i = 0; i < n; ++i) if (depth[i] != HELD) order[fill[depth[i]]++] = (uint16_t)i;
-    }
-    for (size_t i = 0; i < blend0.size(); ++i) order[n + i] = blend0[i];
-    // workspace: the round lists (a ring of 8 slots, fixed size) and behind them one slot per map that takes part in a
-    // round (a streamed call spans up to twice as many maps as it processes: the held ones need none); grown in steps of
-    // 32 slots -- a re-allocation is a hipFree, i.e. a device-wide synchronisation, and used to happen whenever a call
-    // was one map longer than any before it
-    const size_t lists_bytes = 8 * 4 * (size_t)DEPTH_SLOT;
-    const int n_proc = round_start[maxd + 1];
-    if ((rc = h->tail_ws.ensure(lists_bytes + (size_t)L.total * std::max<size_t>(32, ((size_t)n_proc + 31) / 32 * 32)))) return rc;
-    // the lists travel through a small ring of pinned host slots so that the upload is asynchronous (up to 8 calls may
-    // be in flight on the stream before a slot is reused)
-    if (!h->depth_pinned) SVC_HIP(hipHostMalloc((void **)&h->depth_pinned, 8 * 4 * (size_t)DEPTH_SLOT, hipHostMallocDefault));
-    const int slot = h->depth_slot++ & 7;
-    if (h->depth_ev[slot]) SVC_HIP(hipEventSynchronize(h->depth_ev[slot]));      // the upload that last used this slot has run
-    else SVC_HIP(hipEventCreateWithFlags(&h->depth_ev[slot], hipEventDisableTiming));
-    uint16_t *order_dev = (uint16_t *)((uint8_t *)h->tail_ws.p + (size_t)slot * 4 * DEPTH_SLOT);
-    memcpy(h->depth_pinned + (size_t)slot * 4 * DEPTH_SLOT, order.data(), (size_t)n * 4);
-    SVC_HIP(hipMemcpyAsync(order_dev, h->depth_pinned + (size_t)slot * 4 * DEPTH_SLOT, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    SVC_HIP(hipEventRecord(h->depth_ev[slot], s));
-    h->tail_frames = n; h->tail_h = height; h->tail_w = width; h->tail_frame_stride = L.total;
-    h->tail_slot_of.assign((size_t)n, -1);                       // (svc_debug_cluster_state: map -> workspace slot)
-    for (int i = 0; i < n_proc; ++i) h->tail_slot_of[order[i]] = i;
-    TailArgs A;
-    A.maps = maps; A.ws = (uint8_t *)h->tail_ws.p + lists_bytes; A.ws_stride = L.total; A.order = order_dev; A.slot0 = 0;
-    A.n = n; A.h = height; A.w = width; A.dW = make_fdiv(width);
-    A.mcs = params->hdbscan_min; A.min_samples = params->hdbscan_min_samples; A.select_sum = params->select_sum;
-    A.op_close = params->op_close; A.clust_filt = params->clust_filt;
-    A.prim_pt = h->prim_pt;
-    const int32_t *ring_delta = nullptr;
-    RC_TAIL(ensure_ring_delta(h, width, &ring_delta));
-    A.ring = (const uint32_t *)h->tail_offsets.p; A.n_ring = h->tail_n_offsets; A.n_ring1 = h->tail_n_offsets1;
-    A.ring_delta = ring_delta;
-    A.ring_cnt = (const uint16_t *)h->tail_ring_cnt.p; A.prim_lvl = h->prim_lvl;
-    A.xy = xy; A.stats = stats; A.L = L;
-    const int hw = height * width;
-    const size_t lds_core = (size_t)(hw + 15) / 16 * 16 + (size_t)h->tail_n_offsets * 4 + (size_t)h->tail_n_offsets1 * 4;
-    const size_t lds_prim = 2 * NW16 * 16 + (size_t)hw * 2;
-    const size_t lds_fin = 2 * ((size_t)(hw + 15) / 16 * 16);
-    if (h->lds_attr_done.insert((const void *)k_core).second) {      // per handle = per device (the attribute is per device)
-        SVC_HIP(hipFuncSetAttribute((const void *)k_core, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        SVC_HIP(hipFuncSetAttribute((const void *)k_prim_pt<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        SVC_HIP(hipFuncSetAttribute((const void *)k_prim_pt<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        SVC_HIP(hipFuncSetAttribute((const void *)k_prim_pt<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        SVC_HIP(hipFuncSetAttribute((const void *)k_prim_big, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        SVC_HIP(hipFuncSetAttribute((const void *)k_prim_lvl, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));      // (255 x 255 maps: 162 896 bytes with eight workers; static LDS 136)
-        SVC_HIP(hipFuncSetAttribute((const void *)k_prim_lvl_big, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        SVC_HIP(hipFuncSetAttribute((const void *)k_finish, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024));
-        SVC_HIP(hipFuncSetAttribute((const void *)k_tree, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024));
-        SVC_HIP(hipFuncSetAttribute((const void *)k_tree_par, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        SVC_HIP(hipFuncSetAttribute((const void *)k_tail_front, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));      // (255 x 255 maps: 162 896 bytes with eight workers; static LDS 136)
-        SVC_HIP(hipFuncSetAttribute((const void *)k_tail_back, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        SVC_HIP(hipFuncSetAttribute((const void *)k_sort, hipFuncAttributeMaxDynamicSharedMemorySize, SORT_LDS_BYTES));
-    }
-    for (int r = 0; r <= maxd; ++r) {
-        const int m = round_start[r + 1] - round_start[r];   // maps of this round
-        const uint16_t *ord = order_dev + round_start[r];
-        A.order = ord; A.slot0 = round_start[r];
-        if (r == 0 && !blend0.empty()) {                     // blends from held (already final) predecessors
-            k_blend<<<dim3(8, (unsigned)blend0.size()), 256, 0, s>>>(full_maps, order_dev + n, full_h * full_w);
-            SVC_CHECK_LAUNCH();
-        }
-        if (m == 0) continue;                                // every map of the call is held
-        if (r > 0) {
-            k_blend<<<dim3(8, m), 256, 0, s>>>(full_maps, ord, full_h * full_w);
-            SVC_CHECK_LAUNCH();
-        }
-        if (factor > 1) {
-            k_map_resize<<<dim3(8, m), 256, 0, s>>>(full_maps, maps, rs_down, ord, full_h, full_w, height, width);
-            SVC_CHECK_LAUNCH();
-        }
-        int cap_cl = 0, cap_cl_huge = 0;
-        const size_t lds_tp = tp_lds_bytes(hw, params->hdbscan_min, &cap_cl, &cap_cl_huge);
-        const bool tree_fallback = !h->tree_par || hw > TP_CAP_HUGE || hdb::max_clusters(std::min(hw, TP_CAP_BIG), params->hdbscan_min) > cap_cl ||
-                                   (hw > TP_CAP_BIG && hdb::max_clusters(std::min(hw, TP_CAP_HUGE), params->hdbscan_min) > cap_cl_huge);
-        if (params->clust_filt && h->tail_merge && h->prim_lvl && h->tree_par) {
-            // two fused launches per round (k_tail_front, k_tail_back) + the stand-alone kernels for what they leave
-            const size_t lds_front = std::max({(size_t)(hw + 15) / 16 * 16, lds_core, lvl_lds_bytes(height, width, h->tail_n_offsets)});
-            const size_t lds_back = std::max({(size_t)SORT_LDS_BYTES, lds_tp, lds_fin});
-            {
-                ProfScope ps(h, SVC_K_PRIM, s);
-                k_tail_front<<<m, TB, lds_front, s>>>(A);
-                SVC_CHECK_LAUNCH();
-                if (hw > LVL_CAP) { k_prim_lvl_big<<<m, TB, lvl_big_lds_bytes(height, width, h->tail_n_offsets), s>>>(A); SVC_CHECK_LAUNCH(); }
-            }
-            ProfScope ps(h, SVC_K_FINISH, s);
-            k_tail_back<<<m, TB, lds_back, s>>>(A, cap_cl, cap_cl_huge);
-            SVC_CHECK_LAUNCH();
-            if (tree_fallback) {
-                k_tree<<<m, 64, FIN_LDS_BYTES, s>>>(A);
-                SVC_CHECK_LAUNCH();
-                k_finish<<<m, TB, lds_fin, s>>>(A);
-                SVC_CHECK_LAUNCH();
-            }
-        } else {
-        {
-            ProfScope ps(h, SVC_K_COMPACT, s);
-            k_compact<<<m, TB, (size_t)(hw + 15) / 16 * 16, s>>>(A);
-            SVC_CHECK_LAUNCH();
-        }
-        if (params->clust_filt) {
-            {
-                ProfScope ps(h, SVC_K_CORE, s);
-                k_core<<<m, TB, lds_core, s>>>(A);
-                SVC_CHECK_LAUNCH();
-            }
-            ProfScope ps(h, SVC_K_PRIM, s);
-            // maps of up to LVL_CAP points: the level-bucketed Prim; larger ones (or all, SVC_PRIM_LVL=0): one node per step
-            const int n_min = h->prim_lvl ? LVL_CAP : 0;
-            if (h->prim_lvl) {
-                k_prim_lvl<<<m, TB, lvl_lds_bytes(height, width, h->tail_n_offsets), s>>>(A);
-                SVC_CHECK_LAUNCH();
-            } else {
-                if (h->prim_pt <= 2) { k_prim_pt<2><<<m, TB, lds_prim, s>>>(A, n_min); SVC_CHECK_LAUNCH(); }
-                if (h->prim_pt <= 4 && (hw > 2 * TB || h->prim_pt > 2)) { k_prim_pt<4><<<m, TB, lds_prim, s>>>(A, n_min); SVC_CHECK_LAUNCH(); }
-                if (hw > 4 * TB || h->prim_pt > 4) { k_prim_pt<8><<<m, TB, lds_prim, s>>>(A, n_min); SVC_CHECK_LAUNCH(); }
-            }
-            if (hw > LVL_CAP && h->prim_lvl) { k_prim_lvl_big<<<m, TB, lvl_big_lds_bytes(height, width, h->tail_n_offsets), s>>>(A); SVC_CHECK_LAUNCH(); }
-            else if (hw > 8 * TB) { k_prim_big<<<m, TB, lds_prim, s>>>(A, n_min); SVC_CHECK_LAUNCH(); }
-        }
-        {
-            ProfScope ps(h, SVC_K_FINISH, s);
-            if (params->clust_filt) {
-                k_sort<<<m, TB, SORT_LDS_BYTES, s>>>(A);
-                SVC_CHECK_LAUNCH();
-                if (h->tree_par) {
-                    k_tree_par<<<m, TB, lds_tp, s>>>(A, cap_cl, cap_cl_huge);
-                    SVC_CHECK_LAUNCH();
-                }
-                // the serial builder: maps the parallel one does not hold in LDS (more points or clusters), or all (SVC_TREE_PAR=0)
-                if (tree_fallback) {
-                    k_tree<<<m, 64, FIN_LDS_BYTES, s>>>(A);
-                    SVC_CHECK_LAUNCH();
-                }
-            }
-            k_finish<<<m, TB, lds_fin, s>>>(A);
-            SVC_CHECK_LAUNCH();
-        }
-        }
-        if (factor > 1) {
-            k_map_resize<<<dim3(16, m), 256, 0, s>>>(maps, full_maps, rs_up, ord, height, width, full_h, full_w);
-            SVC_CHECK_LAUNCH();
-        }
-    }
-    if (!params->com_km) {                 // centre = arg-max pixel of the final full-size map (held maps keep what the caller has)
-        k_centre_argmax<<<n, 256, 0, s>>>(full_maps, full_h, full_w, make_fdiv(full_w), xy);
-        SVC_CHECK_LAUNCH();
-    } else if (params->resize_factor > 1) {       // centre of the nearest-neighbour shrunk final map (also when clust_filt is off)
-        k_centre_nearest<<<n, 256, 0, s>>>(full_maps, full_h, full_w, rs_h, rs_w, params->resize_factor, xy);
-        SVC_CHECK_LAUNCH();
-    }
-    return SVC_OK;
-}
 
 extern "C" int svc_debug_argsort_u32(SvcHandle *h, const uint32_t *keys_host, int n, int32_t *order_host) {
     if (!h || !keys_host || !order_host || n < 1 || n > 65535) { svc_set_error("svc_debug_argsort_u32: invalid argument"); return SVC_E_INVALID; }
@@ -3268,8 +3170,7 @@ extern "C" int svc_debug_argsort_u32(SvcHandle *h, const uint32_t *keys_host, in
     int rc;
     if ((rc = keys.ensure((size_t)n * 4)) || (rc = out.ensure((size_t)n * 2)) || (rc = scratch.ensure((size_t)n * 16 + 128))) return rc;
     SVC_HIP(hipMemcpy(keys.p, keys_host, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (h->lds_attr_done.insert((const void *)k_argsort_test).second)
-        SVC_HIP(hipFuncSetAttribute((const void *)k_argsort_test, hipFuncAttributeMaxDynamicSharedMemorySize, SORT_LDS_BYTES));
+    RC_TAIL(raise_lds_limit(h, (const void *)k_argsort_test, SORT_LDS_BYTES));
     k_argsort_test<<<1, TB, SORT_LDS_BYTES, 0>>>((const uint32_t *)keys.p, n, (uint16_t *)out.p, (uint8_t *)scratch.p);
     SVC_CHECK_LAUNCH();
     SVC_HIP(hipDeviceSynchronize());
@@ -3290,14 +3191,14 @@ extern "C" int svc_debug_cluster_state(SvcHandle *h, int frame, int cap, uint32_
     SVC_HIP(hipDeviceSynchronize());
     const int fcap = h->tail_h * h->tail_w;
     FrameWS L = make_layout(fcap, 1);      // point-array offsets do not depend on the cluster capacity
-    const uint8_t *ws = (const uint8_t *)h->tail_ws.p + 8 * 4 * (size_t)DEPTH_SLOT + (size_t)h->tail_slot_of[frame] * h->tail_frame_stride;
-    int32_t hdr[32];
+    const uint8_t *ws = (const uint8_t *)h->tail_ws.p + TAIL_LISTS_BYTES + (size_t)h->tail_slot_of[frame] * h->tail_frame_stride;
+    int32_t hdr[SVC_HDR_WORDS];
     SVC_HIP(hipMemcpy(hdr, ws + L.hdr, sizeof hdr, hipMemcpyDeviceToHost));
-    const int N = hdr[0];
+    const int N = hdr[SVC_HDR_N];
     const int m = std::min(N, cap);
     if (hdr_host) memcpy(hdr_host, hdr, sizeof hdr);
     if (pts_host) SVC_HIP(hipMemcpy(pts_host, ws + L.pts, (size_t)m * 4, hipMemcpyDeviceToHost));
-    if (hdr[3]) {
+    if (hdr[SVC_HDR_CLUSTERED]) {
         if (core_host) SVC_HIP(hipMemcpy(core_host, ws + L.core, (size_t)m * 4, hipMemcpyDeviceToHost));
         if (labels_host) SVC_HIP(hipMemcpy(labels_host, ws + L.labels, (size_t)m * 4, hipMemcpyDeviceToHost));
         if (mst_host && m > 1) {

@@ -21,6 +21,18 @@ NODE_F4X, NODE_F2X = 107, 114
 PLAN_WORDS = ('NH', 'NW', 'hks', 'vks', 'fr_ok', 'fr_nr', 'fr_nc', 'fr_tiles_y', 'fr_tiles_x', 'lz_tile_cap', 'lz_lds', 'sd_rows',
               'sd_tile_cap', 'sd_lds', 'fr_lds', 'lz_lds_max', 'sd_lds_max', 'fr_lds_max')
 
+# words of a frame header, cluster_state(...)['hdr'] (include/svc.h: SVC_HDR_*, the same numbers; a range is its first word and a count)
+HDR_WORDS = 32
+HDR_N, HDR_NSEL, HDR_KEPT, HDR_CLUSTERED, HDR_NCLUSTERS = 0, 1, 2, 3, 4
+HDR_CORE_STAMP0, HDR_CORE_STAMPS = 5, 3
+HDR_T_SORTED, HDR_T_HIERARCHY, HDR_T_CHOSEN, HDR_T_FINISHED, HDR_T_PRIM, HDR_T_BUILT = 8, 9, 10, 11, 12, 13
+HDR_TREE_CLOCKS, HDR_T_TREE = 14, 15
+HDR_LVL_ROUNDS, HDR_LVL_RISES = 16, 17
+HDR_LVL_PHASE0, HDR_LVL_PHASES = 18, 5
+HDR_TREE_PAR, HDR_T_LVL_SETUP = 23, 24
+HDR_TP_STAMP0, HDR_TP_STAMPS = 25, 5
+HDR_BACK_DONE = 30
+
 
 def net_plan(height, width):
     """Test door (svc_debug_net_plan): what the network's plan decides from the map shape alone, as a dict of PLAN_WORDS.  Host
@@ -474,13 +486,34 @@ class Engine:
         core = np.zeros(cap, np.uint32)
         mst = np.zeros((cap, 3), np.uint32)
         labels = np.zeros(cap, np.int32)
-        hdr = np.zeros(32, np.int32)
+        hdr = np.zeros(HDR_WORDS, np.int32)
         vp = ctypes.c_void_p
         n = _lib.check(self.lib.svc_debug_cluster_state(self._h, frame, cap, pts.ctypes.data_as(vp),
                                                          core.ctypes.data_as(vp), mst.ctypes.data_as(vp),
                                                          labels.ctypes.data_as(vp), hdr.ctypes.data_as(vp)))
         m = min(n, cap)
         return dict(n=n, pts=pts[:m], core=core[:m], mst=mst[:max(m - 1, 0)], labels=labels[:m], hdr=hdr)
+
+
+TAIL_KNOBS = ('SVC_PRIM_LVL', 'SVC_TREE_PAR', 'SVC_TAIL_MERGE')       # read by svc_create
+
+
+def tail_engine(reference, state_dict=None, seed=0):
+    """An Engine whose tail form does not depend on the caller's environment.  reference=True: the one-node-per-step Prim
+    (k_prim_ref), the serial hierarchy (k_tree) and one kernel per stage -- the second device reference of the tests, itself
+    checked against the oracle; False: the default form (the three knobs unset).  The environment is restored."""
+    import os
+    saved = {k: os.environ.pop(k, None) for k in TAIL_KNOBS}
+    try:
+        if reference:
+            os.environ.update({k: '0' for k in TAIL_KNOBS})
+        return Engine(state_dict, seed=seed)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def iou_boxes(a, b):

@@ -141,3 +141,18 @@ def test_transnet_tap_door_constants_and_argument_checks():
     assert len(Hd.ShotTransNet.TAP_SHAPES) == ids['DENSE'] + 1
     out = (ctypes.c_float * 4)()
     assert _lib.load().svc_debug_transnet_tap(None, None, 1, 4, 0, 4, 0, out, 4) == -1
+
+
+def test_frame_header_words_are_the_headers():
+    """The words of svc_debug_cluster_state's frame header: every SVC_HDR_* of include/svc.h is ops.HDR_* with the same number,
+    neither side has a name the other lacks, and the named words and ranges lie side by side inside the header."""
+    from retargetvid_amd import ops
+    text = open(os.path.join(ROOT, 'include', 'svc.h')).read()
+    words = {k: int(v) for k, v in re.findall(r'#define SVC_HDR_([A-Z0-9_]+)\s+(\d+)', text)}
+    assert words == {k[4:]: v for k, v in vars(ops).items() if k.startswith('HDR_')} and len(words) == 25
+    counts = {'CORE_STAMP0': 'CORE_STAMPS', 'LVL_PHASE0': 'LVL_PHASES', 'TP_STAMP0': 'TP_STAMPS'}      # first word of a range -> its count
+    taken = []
+    for k, v in words.items():
+        if k != 'WORDS' and k not in counts.values():
+            taken += range(v, v + (words[counts[k]] if k in counts else 1))
+    assert sorted(taken) == list(range(31)) and words['WORDS'] == 32

@@ -334,10 +334,9 @@ def _state_is_the_oracles(engine, i, clustered, CP):
     assert len(pairs) == len({a for a, _ in pairs}) == len({b for _, b in pairs}), 'labels of map %d' % i
 
 
-def test_prim_rounds_and_parallel_hierarchy_on_adversarial_maps(engine):
-    """k_prim_lvl (rounds of up to 64 nodes, drops, rises, jumps beyond the ring table, the batch table running full)
-    and k_tree_par (nearest greater ranks, pointer jumping) against the oracle's one-node-per-step Prim and its
-    union-find hierarchy: sparse noise (every step a jump), dense noise, lines, lattices, blobs with outliers."""
+def _adversarial_maps():
+    """(nine 140 x 250 maps, four 35 x 62 maps): sparse noise (every step a jump), dense noise, lines, lattices, blobs with
+    outliers; small noise maps of about 110, 430, 1 090 and 1 950 points."""
     rng = np.random.RandomState(11)
     maps = []
     for dens in (0.002, 0.01, 0.03, 0.08, 0.2):
@@ -350,12 +349,40 @@ def test_prim_rounds_and_parallel_hierarchy_on_adversarial_maps(engine):
     for (cy, cx, r) in ((30, 40, 12), (100, 200, 18), (70, 120, 9)):
         m[(ys - cy) ** 2 + (xs - cx) ** 2 < r * r] = 210
     m[rng.rand(140, 250) < 0.003] = 150; maps.append(m)                                              # three blobs + outliers
-    maps = np.stack(maps)
+    small = np.stack([((rng.rand(35, 62) < d) * 200).astype(np.uint8) for d in (0.05, 0.2, 0.5, 0.9)])
+    return np.stack(maps), small
+
+
+def test_prim_rounds_and_parallel_hierarchy_on_adversarial_maps(engine):
+    """k_prim_lvl (rounds of up to 64 nodes, drops, rises, jumps beyond the ring table, the batch table running full)
+    and k_tree_par (nearest greater ranks, pointer jumping) against the oracle's one-node-per-step Prim and its
+    union-find hierarchy: sparse noise (every step a jump), dense noise, lines, lattices, blobs with outliers."""
+    maps, small = _adversarial_maps()
     _prim_and_labels(engine, maps, P.init_crop_params())
     _prim_and_labels(engine, maps, dict(P.init_crop_params(), hdbscan_min=5, hdbscan_min_samples=3))
-    small = np.stack([((rng.rand(35, 62) < d) * 200).astype(np.uint8) for d in (0.05, 0.2, 0.5, 0.9)])
     _prim_and_labels(engine, small, dict(P.init_crop_params(), hdbscan_min=5, hdbscan_min_samples=3))
     _prim_and_labels(engine, small, dict(P.init_crop_params(), hdbscan_min=2, hdbscan_min_samples=1))
+
+
+def test_the_reference_tail_engine_against_the_oracle():
+    """The second device reference itself (ops.tail_engine(reference=True): k_prim_ref, k_tree, one kernel per stage) against
+    the oracle -- point list, core distances, Prim edge list, labels.  k_prim_ref walks the points TB = 1 024 at a time: the
+    four small noise maps have fewer points than that, about as many and nearly twice as many (one and two strides, ragged
+    ends); a 140 x 250 map at density 0.01 makes every step a jump; a 12 x 12 map with three points is not clustered."""
+    _, small = _adversarial_maps()
+    sparse = ((np.random.RandomState(12).rand(1, 140, 250) < 0.01) * 200).astype(np.uint8)
+    tiny = np.zeros((1, 12, 12), np.uint8)
+    tiny[0, [2, 5, 9], [3, 8, 1]] = 200
+    ref = ops.tail_engine(reference=True)
+    try:
+        for CP in (P.init_crop_params(), dict(P.init_crop_params(), hdbscan_min=5, hdbscan_min_samples=3)):
+            for maps in (small, sparse, tiny):
+                _prim_and_labels(ref, maps, CP)
+                for i in range(len(maps)):
+                    hdr = ref.cluster_state(i, maps[i].size)['hdr']
+                    assert hdr[ops.HDR_CLUSTERED] == (hdr[ops.HDR_N] > CP['hdbscan_min'] + 1) == (maps is not tiny)
+    finally:
+        ref.close()
 
 
 def test_tail_bit_exact_other_parameters(engine):
@@ -455,18 +482,8 @@ def test_maps_beyond_8192_points_new_kernels_equal_the_round2_kernels_and_the_or
     (k_prim_lvl_big) and the path-structured hierarchy with its per-edge arrays there (tp_body<2>) instead of the
     one-node-per-step Prim and the serial union-find.  24 maps of 8.5 - 22 k points (blobs, dense noise, blobs with holes,
     lattices) x both parameter sets against those round-2 kernels (Prim edge list, labels, maps, centres: identical), one
-    ~9 k-point map against the oracle, and no map left to the fall-back kernels (hdr[23] = done by k_tree_par)."""
-    import os
-    saved = {k: os.environ.get(k) for k in ('SVC_PRIM_LVL', 'SVC_TREE_PAR', 'SVC_TAIL_MERGE')}
-    try:
-        os.environ.update(SVC_PRIM_LVL='0', SVC_TREE_PAR='0', SVC_TAIL_MERGE='0')
-        old = ops.Engine(seed=0)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    ~9 k-point map against the oracle, and no map left to the fall-back kernels (HDR_TREE_PAR = done by k_tree_par)."""
+    old = ops.tail_engine(reference=True)
     try:
         rng = np.random.RandomState(77)
         maps = _dense_maps(rng, 24, 8500, 22000)
@@ -483,28 +500,13 @@ def test_maps_beyond_8192_points_new_kernels_equal_the_round2_kernels_and_the_or
                 s_old, s_new = old.cluster_state(i, 35000), engine.cluster_state(i, 35000)
                 assert np.array_equal(s_old['mst'], s_new['mst']), 'Prim sequence of map %d (N = %d)' % (i, s_old['n'])
                 assert np.array_equal(s_old['labels'], s_new['labels']), 'labels of map %d' % i
-                assert s_new['hdr'][16] > 0                                    # Prim in rounds (k_prim_lvl_big)
+                assert s_new['hdr'][ops.HDR_LVL_ROUNDS] > 0                    # Prim in rounds (k_prim_lvl_big)
                 if CP['hdbscan_min'] == 26:                                    # (min_cluster_size 5 on 20 k points: more clusters than the
-                    assert s_new['hdr'][23] == 1                               #  LDS tables hold -> the serial builder; not a shipped setting)
+                    assert s_new['hdr'][ops.HDR_TREE_PAR] == 1                 #  LDS tables hold -> the serial builder; not a shipped setting)
         small = _dense_maps(np.random.RandomState(78), 1, 8300, 9500)
         _check_tail(engine, small, None, P.init_crop_params())                  # (the O(N^2) oracle: ~10 s)
     finally:
         old.close()
-
-
-def _round2_engine():
-    """An engine on the one-node-per-step Prim and the serial hierarchy, one kernel per stage (the second device reference)."""
-    import os
-    saved = {k: os.environ.get(k) for k in ('SVC_PRIM_LVL', 'SVC_TREE_PAR', 'SVC_TAIL_MERGE')}
-    try:
-        os.environ.update(SVC_PRIM_LVL='0', SVC_TREE_PAR='0', SVC_TAIL_MERGE='0')
-        return ops.Engine(seed=0)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _noise_map_with_n_points(rng, h, w, dens, n):
@@ -527,7 +529,7 @@ def test_the_seam_between_k_prim_lvl_and_k_prim_lvl_big_at_8192_points(engine):
     rng = np.random.RandomState(8192)
     counts = (8191, 8192, 8193, 8256)
     maps = np.stack([_noise_map_with_n_points(rng, 96, 96, 0.9, n) for n in counts])
-    old = _round2_engine()
+    old = ops.tail_engine(reference=True)
     try:
         for CP in (P.init_crop_params(), dict(P.init_crop_params(), hdbscan_min=5, hdbscan_min_samples=3, select_sum=1)):
             for flags in (np.array([1, 0, 1, 0], np.uint8), None):
@@ -542,7 +544,7 @@ def test_the_seam_between_k_prim_lvl_and_k_prim_lvl_big_at_8192_points(engine):
                     s_old, s_new = old.cluster_state(i, 96 * 96), engine.cluster_state(i, 96 * 96)
                     assert np.array_equal(s_old['mst'], s_new['mst']), 'Prim sequence of map %d (N = %d)' % (i, s_old['n'])
                     assert np.array_equal(s_old['labels'], s_new['labels']), 'labels of map %d' % i
-                    assert s_new['hdr'][16] > 0                                # Prim in rounds, either kernel
+                    assert s_new['hdr'][ops.HDR_LVL_ROUNDS] > 0                # Prim in rounds, either kernel
             if CP['hdbscan_min'] == 26:
                 _state_is_the_oracles(engine, 2, maps[2], CP)                  # (the last call had no flags: map 2 is the 8 193-point one)
     finally:
@@ -554,17 +556,7 @@ def test_largest_geometries_up_to_65025_points_equal_the_round2_kernels(engine):
     rise), the fourth level of the hierarchy's nearest-greater search (> 8 192 x 4 edges), a 255 x 255 map with every pixel set
     (65 025 points).  Against the round-2 kernels: Prim edge list, labels, maps, centres identical (tools/soak_big_maps.py is
     the long form: four geometries x 8 maps x two parameter sets)."""
-    import os
-    saved = {k: os.environ.get(k) for k in ('SVC_PRIM_LVL', 'SVC_TREE_PAR', 'SVC_TAIL_MERGE')}
-    try:
-        os.environ.update(SVC_PRIM_LVL='0', SVC_TREE_PAR='0', SVC_TAIL_MERGE='0')
-        old = ops.Engine(seed=0)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    old = ops.tail_engine(reference=True)
     try:
         rng = np.random.RandomState(91)
         for (h, w) in ((187, 250), (255, 255)):
@@ -755,20 +747,7 @@ def test_new_tail_kernels_equal_the_round2_kernels_on_random_maps():
     (SVC_PRIM_LVL=0, SVC_TREE_PAR=0; both verified against the oracle by the tests above) on 288 random maps of four
     sizes and both parameter sets: Prim edge lists, labels, filtered maps and centres must be identical.  A wide net for
     the rare paths (drops, rises, jumps, full batch tables, maps above 4 352 points) that costs seconds on the device."""
-    import os
-    saved = {k: os.environ.get(k) for k in ('SVC_PRIM_LVL', 'SVC_TREE_PAR', 'SVC_TAIL_MERGE')}
-    try:
-        os.environ.update(SVC_PRIM_LVL='0', SVC_TREE_PAR='0', SVC_TAIL_MERGE='0')
-        old = ops.Engine(seed=0)
-        for k in saved:
-            os.environ.pop(k, None)
-        new = ops.Engine(seed=0)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    old, new = ops.tail_engine(reference=True), ops.tail_engine(reference=False)
     try:
         rng = np.random.RandomState(31)
         n_maps = 0

@@ -26,14 +26,15 @@ for tag in ('flags', 'none'):
 m = maps.clone(); eng.cluster_center_(m, np.zeros(32, np.uint8), CP); torch.cuda.synchronize()
 for i in range(0, 32, 6):
     st = eng.cluster_state(i, 35000)
-    h = st['hdr']
+    h, H = st['hdr'], ops
     print('  map %2d: N=%5d clusters %3d  stamps (us, 100 MHz wall clock): k_sort %.1f | k_tree built %.1f hierarchy %.1f chosen %.1f | '
-          'k_finish %.1f | k_prim %.1f' % (i, st['n'], h[4], h[8] / 100.0, h[13] / 100.0, h[9] / 100.0, h[10] / 100.0, h[11] / 100.0, h[12] / 100.0))
-    print('           k_core stamps (us): phase 1 (thread per point, inner ring) %.1f, phase 2 (wavefront per point) %.1f, end %.1f' % (h[5] / 100.0, h[6] / 100.0, h[7] / 100.0))
-    if h[23]:
+          'k_finish %.1f | k_prim %.1f' % (i, st['n'], h[H.HDR_NCLUSTERS], h[H.HDR_T_SORTED] / 100.0, h[H.HDR_T_BUILT] / 100.0, h[H.HDR_T_HIERARCHY] / 100.0,
+                                           h[H.HDR_T_CHOSEN] / 100.0, h[H.HDR_T_FINISHED] / 100.0, h[H.HDR_T_PRIM] / 100.0))
+    print('           k_core stamps (us): phase 1 (thread per point, inner ring) %.1f, phase 2 (wavefront per point) %.1f, end %.1f' % tuple(
+        x / 100.0 for x in h[H.HDR_CORE_STAMP0:H.HDR_CORE_STAMP0 + H.HDR_CORE_STAMPS]))
+    if h[H.HDR_TREE_PAR]:
         print('           k_tree_par stamps (us): loaded %.1f nearest-greater %.1f clusters %.1f jumped %.1f tops %.1f | rows %.1f stabilities %.1f labels+kept %.1f' % tuple(
-            x / 100.0 for x in list(h[25:30]) + [h[13], h[9], h[10]]))
-    if h[16]:
-        print('           k_prim_lvl: %d rounds, %d rises; setup %.1f us, phases (us): rise %.1f extract %.1f probe %.1f commit %.1f mark %.1f' % (
-            h[16], h[17], h[24] / 100.0, h[18] / 100.0, h[19] / 100.0, h[20] / 100.0, h[21] / 100.0, h[22] / 100.0))
-
+            x / 100.0 for x in list(h[H.HDR_TP_STAMP0:H.HDR_TP_STAMP0 + H.HDR_TP_STAMPS]) + [h[H.HDR_T_BUILT], h[H.HDR_T_HIERARCHY], h[H.HDR_T_CHOSEN]]))
+    if h[H.HDR_LVL_ROUNDS]:
+        print('           k_prim_lvl: %d rounds, %d rises; setup %.1f us, phases (us): rise %.1f extract %.1f probe %.1f commit %.1f mark %.1f' % ((
+            h[H.HDR_LVL_ROUNDS], h[H.HDR_LVL_RISES], h[H.HDR_T_LVL_SETUP] / 100.0) + tuple(x / 100.0 for x in h[H.HDR_LVL_PHASE0:H.HDR_LVL_PHASE0 + H.HDR_LVL_PHASES])))

@@ -104,7 +104,7 @@ try:
             core = H.core_distances(X, k)
             u, v, w = H.prim_mst(X, core)
             print('    core mismatch %d  mst mismatch %d  finish stamps (us) %s prim %.1f us nclusters %d' % (
-                (core != st['core']).sum(), (np.stack([u, v, w], 1) != st['mst']).sum(), (st['hdr'][8:12] / 100.0).tolist(), st['hdr'][12] / 100.0, st['hdr'][4]))
+                (core != st['core']).sum(), (np.stack([u, v, w], 1) != st['mst']).sum(), (st['hdr'][ops.HDR_T_SORTED:ops.HDR_T_FINISHED + 1] / 100.0).tolist(), st['hdr'][ops.HDR_T_PRIM] / 100.0, st['hdr'][ops.HDR_NCLUSTERS]))
 except Exception:
     traceback.print_exc(); ok = False
 
@@ -140,14 +140,16 @@ try:
         torch.cuda.synchronize(); t3 = time.time()
         print('B=32: resize %.2f ms, saliency %.2f ms, tail %.2f ms  (N mean %.0f)' % (
             (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, stats[:, 0].float().mean().item()))
-    core_end = [eng.cluster_state(i, 8)['hdr'][5:8] / 100.0 for i in range(32)]
+    core_end = [eng.cluster_state(i, 8)['hdr'][ops.HDR_CORE_STAMP0:ops.HDR_CORE_STAMP0 + ops.HDR_CORE_STAMPS] / 100.0 for i in range(32)]
     worst = int(np.argmax([c[2] for c in core_end]))
     print('  k_core stamps (us): median phase1 %.1f phase2 %.1f end %.1f | slowest map %d: %.1f %.1f %.1f' % (
         np.median([c[0] for c in core_end]), np.median([c[1] for c in core_end]), np.median([c[2] for c in core_end]), worst, *core_end[worst]))
     for i in range(0, 32, 4):
         st = eng.cluster_state(i, 35000)
+        hd = st['hdr']
         print('  warm frame %2d: N=%5d nclusters %3d  finish stamps (us): sorted %.1f built %.1f hierarchy %.1f chosen %.1f done %.1f | prim %.1f us | k_tree shader clock %.0f MHz' % (
-            i, st['n'], st['hdr'][4], st['hdr'][8] / 100.0, st['hdr'][13] / 100.0, st['hdr'][9] / 100.0, st['hdr'][10] / 100.0, st['hdr'][11] / 100.0, st['hdr'][12] / 100.0, st['hdr'][14] / max(st['hdr'][15], 1) * 100.0))
+            i, st['n'], hd[ops.HDR_NCLUSTERS], hd[ops.HDR_T_SORTED] / 100.0, hd[ops.HDR_T_BUILT] / 100.0, hd[ops.HDR_T_HIERARCHY] / 100.0, hd[ops.HDR_T_CHOSEN] / 100.0, hd[ops.HDR_T_FINISHED] / 100.0,
+            hd[ops.HDR_T_PRIM] / 100.0, hd[ops.HDR_TREE_CLOCKS] / max(hd[ops.HDR_T_TREE], 1) * 100.0))
 except Exception:
     traceback.print_exc(); ok = False
 

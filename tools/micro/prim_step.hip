@@ -1,4 +1,5 @@
-// Micro-benchmark: where does one Prim step of k_prim (svc_tail.hip: prim_regs32) spend its ~1100 cycles?
+// Micro-benchmark (round 3): where did one step of the register-resident one-node-per-step Prim the tail then ran (prim_regs32,
+// its own copy below; svc_tail.hip keeps only the plain form, k_prim_ref) spend its ~1100 cycles?
 // Same loop with pieces switched off by template flags (results are wrong when a piece is off; only time matters).
 // hipcc -O3 --offload-arch=gfx950 -o /tmp/prim_step tools/micro/prim_step.hip && /tmp/prim_step
 #include <hip/hip_runtime.h>

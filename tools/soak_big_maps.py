@@ -11,12 +11,7 @@ from oracle import pipeline_ref as P
 from retargetvid_amd import ops
 n_maps = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 5)
-saved = {k: os.environ.get(k) for k in ('SVC_PRIM_LVL', 'SVC_TREE_PAR', 'SVC_TAIL_MERGE')}
-os.environ.update(SVC_PRIM_LVL='0', SVC_TREE_PAR='0', SVC_TAIL_MERGE='0')
-old = ops.Engine(seed=0)
-for k, v in saved.items():
-    os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
-new = ops.Engine(seed=0)
+old, new = ops.tail_engine(reference=True), ops.tail_engine(reference=False)
 bad = 0
 for (h, w) in ((140, 250), (187, 250), (250, 140), (255, 255)):
     ys, xs = np.mgrid[0:h, 0:w]
@@ -49,7 +44,7 @@ for (h, w) in ((140, 250), (187, 250), (250, 140), (255, 255)):
             s_old, s_new = old.cluster_state(i, h * w), new.cluster_state(i, h * w)
             same = np.array_equal(s_old['mst'], s_new['mst']) and np.array_equal(s_old['labels'], s_new['labels'])
             ok = ok and same
-            detail.append('%d%s%s' % (s_new['n'], '' if same else '!', '' if s_new['hdr'][23] else 's'))
+            detail.append('%d%s%s' % (s_new['n'], '' if same else '!', '' if s_new['hdr'][ops.HDR_TREE_PAR] else 's'))
         bad += 0 if ok else 1
         print('%3dx%3d mcs %2d: %s   points per map (! = differs, s = hierarchy by the serial builder): %s' % (h, w, CP['hdbscan_min'], 'identical' if ok else 'MISMATCH', ' '.join(detail)), flush=True)
 print('mismatching (geometry, parameter set) pairs:', bad)

@@ -29,7 +29,8 @@ for sigma, thr in (((30, 44), 120), ((60, 90), 120), ((90, 110), 120), ((120, 15
     st = eng.cluster_state(0, 35000)
     h = st['hdr']
     rows.append('N %5d .. %5d (mean %5.0f)  round of 32 maps %8.3f ms | map 0 (N = %5d): Prim %8.1f us (%4d rounds, %3d rises), sort %7.1f us, hierarchy %7.1f us (by %s), %4d clusters' % (
-        n.min(), n.max(), n.mean(), ms, st['n'], h[12] / 100.0, h[16], h[17], h[8] / 100.0, h[10] / 100.0, 'k_tree_par' if h[23] else 'k_tree', h[4]))
+        n.min(), n.max(), n.mean(), ms, st['n'], h[ops.HDR_T_PRIM] / 100.0, h[ops.HDR_LVL_ROUNDS], h[ops.HDR_LVL_RISES], h[ops.HDR_T_SORTED] / 100.0, h[ops.HDR_T_CHOSEN] / 100.0,
+        'k_tree_par' if h[ops.HDR_TREE_PAR] else 'k_tree', h[ops.HDR_NCLUSTERS]))
     print(rows[-1], flush=True)
 out = os.path.join(ROOT, 'gpurun_out', 'r04_tail_vs_N.txt')
 os.makedirs(os.path.dirname(out), exist_ok=True)
