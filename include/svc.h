@@ -84,7 +84,8 @@ const char *svc_last_error(void);
  * 11 = svc_debug_run_node (SVC_NODE_*) exists.
  * 12 = SvcFrameLayout, svc_resize_frames_layout and svc_render_crops_layout exist (pitched frames).
  * (12, no bump) svc_render_crops_filter (SVC_FILTER_*) was added without one: no struct and no existing signature changed, and
- *     a binding finds the entry by its symbol (dlsym), not by the revision.  Likewise svc_debug_net_plan (SVC_PLAN_*). */
+ *     a binding finds the entry by its symbol (dlsym), not by the revision.  Likewise svc_debug_net_plan (SVC_PLAN_*), and
+ *     SvcColour with svc_resize_frames_colour and svc_render_crops_colour (NV12 colour): a new struct and two new entries. */
 #define SVC_ABI_VERSION 12
 int svc_abi_version(void);
 
@@ -118,7 +119,8 @@ int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, 
  * fused into the resampling / the copy: out is bit for bit what the _u8 entry gives on the converted frames -- same output
  * layout, flags, clamping of the window origins (which may be odd in x and y: the chroma index comes from frame coordinates)
  * and LDS limit.  They count under SVC_K_RESIZE / SVC_K_RENDER.  No counterpart in the reference (OpenCV decodes to RGB before
- * it sees a frame); the output of these two is RGB / BGR (NV12 output: the _to_nv12 entries below). */
+ * it sees a frame); the output of these two is RGB / BGR (NV12 output: the _to_nv12 entries below).  BT.709 or full-range
+ * frames: svc_resize_frames_colour / svc_render_crops_colour below. */
 int svc_resize_frames_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
                            uint8_t *out, int sh, int sw, void *stream);
 int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
@@ -139,7 +141,8 @@ int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height
  * not done.  SVC_E_INVALID: whatever the RGB entries reject; oh or ow odd or below 2 (a native-size render of a window with
  * an odd bw or bh does not exist: pass an even output size); flags != 0 (SVC_RENDER_BGR has no meaning here); a resampled
  * window that needs more than 64 KiB of LDS per pair of output rows: 2 * (3 bw + 32) + 2 * 3 ow + 3 * (ow + 16) bytes, every
- * term rounded up to 16.  They count under SVC_K_RENDER.  No counterpart in the reference. */
+ * term rounded up to 16.  They count under SVC_K_RENDER.  No counterpart in the reference.  Another matrix or range for the
+ * output (or the NV12 input): svc_render_crops_colour below. */
 int svc_render_crops_u8_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                 int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
 int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
@@ -218,6 +221,60 @@ int svc_render_crops_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameL
 int svc_render_crops_filter(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height, int width,
                             const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
                             int filter, int flags, void *stream);
+
+/* The colour of NV12 frames: which YUV <-> RGB transform an NV12 source is decoded with and an NV12 output is encoded with.
+ * Two matrices (BT.601, BT.709) and two ranges (limited: Y 16..235, U V 16..240; full: 0..255, AVCOL_RANGE_JPEG) give four
+ * transforms.  svc_resize_frames_colour is svc_resize_frames_layout with the source's colour; svc_render_crops_colour is
+ * svc_render_crops_filter with the source's (in_colour) and the output's (out_colour), chosen independently.  Everything else
+ * is those entries': layout rules, window rules, filters, flags, LDS limits, read range, the packed outputs.  Every other
+ * entry of this header converts with BT.601 limited and gives the bytes it always gave: it is the entry below with NULL
+ * colours, under its own name and with its own errors.
+ * The arithmetic has one shape for all four: 20-bit fixed point, int32, arithmetic shifts, clamp to 0..255.  Decode, for a
+ * pixel's Y and its replicated U V pair:
+ *   yy = max(0, Y - Y0) * CY + (1 << 19),  u = U - 128,  v = V - 128
+ *   R = clamp((yy + CVR v) >> 20)   G = clamp((yy + CVG v + CUG u) >> 20)   B = clamp((yy + CUB u) >> 20)
+ * Encode, for the RGB crop C (r, g, b = C[y][x]; sr, sg, sb = sums over C[2j .. 2j+1][2i .. 2i+1]):
+ *   Y = clamp((YR r + YG g + YB b + (Y0 << 20) + (1 << 19)) >> 20)
+ *   U = clamp((UR sr + UG sg + UB sb + (128 << 22) + (1 << 21)) >> 22)        V likewise with VR VG VB
+ *
+ *   variant        Y0  CY       CVR      CVG      CUG      CUB      | YR     YG     YB     | UR      UG      UB     | VR     VG      VB
+ *   bt601 limited  16  1220542  1673527  -852492  -409993  2116026  | 269484 528482 102760 | -155188 -305135 460324 | 460324 -385875 -74448
+ *   bt601 full      0  1048576  1470104  -748826  -360853  1858077  | 313524 615514 119538 | -176932 -347356 524288 | 524288 -439026 -85262
+ *   bt709 limited  16  1220945  1879825  -558796  -223607  2215014  | 191455 644068 65019  | -105533 -355018 460551 | 460551 -418321 -42230
+ *   bt709 full      0  1048576  1651297  -490864  -196424  1945738  | 222927 749942 75707  | -120138 -404150 524288 | 524288 -476214 -48074
+ *
+ * BT.601 limited keeps the constants OpenCV publishes (three-decimal coefficients; the _nv12 and _to_nv12 entries state them).
+ * The other three rows come from the exact rational coefficients: Kr, Kb = 0.299, 0.114 (BT.601) | 0.2126, 0.0722 (BT.709),
+ * Kg = 1 - Kr - Kb; S = 255 / 219 and C = 255 / 224 for limited range, 1 and 1 for full.  Each of
+ *   CY = S   CVR = 2 (1 - Kr) C   CUB = 2 (1 - Kb) C   CVG = -2 Kr (1 - Kr) C / Kg   CUG = -2 Kb (1 - Kb) C / Kg
+ *   YR = Kr / S   YB = Kb / S   UR = -Kr / (2 (1 - Kb) C)   UB = 1 / (2 C)   VR = 1 / (2 C)   VB = -Kb / (2 (1 - Kr) C)
+ * is multiplied by 2^20 and rounded half away from zero.  YG = round(2^20 / S) - YR - YB, so white gives exactly 235 (limited)
+ * or 255 (full); UG = -UB - UR and VG = -VR - VB, so grey gives exactly 128.
+ * Every coefficient is below 2^23 (the kernels' 24-bit multiplies are exact) and every intermediate fits int32 (decode at most
+ * 5.8e8 in magnitude, encode 5.2e5 .. 1.074e9).  Limited-range encodes land in 16..235 (Y) and 16..240 (U V) and the clamp
+ * never fires; full-range ones reach 256 in U for pure blue and in V for pure red, which the clamp makes 255.  Encoding a flat
+ * colour and decoding it with the same variant gives it back within 2 grey levels (limited) or 1 (full).
+ * Chroma stays replicated on the way in and summed over 2 x 2 on the way out for every variant: no siting, no interpolation.
+ * A NULL colour is BT.601 limited.  SVC_E_INVALID before any device work, the rule in svc_last_error(): struct_size is not this
+ * header's; matrix or range is not one of the values below; reserved is not 0; in_colour (colour) is given and layout->pix_fmt
+ * is SVC_FMT_RGB24; out_colour is given and out_fmt is SVC_FMT_RGB24 (nothing would read it: pass NULL).
+ * The constants travel with the kernel arguments (scalar registers): one kernel set serves the four variants.
+ * They count under SVC_K_RESIZE / SVC_K_RENDER.  No counterpart in the reference (it is handed RGB). */
+#define SVC_MATRIX_BT601  0
+#define SVC_MATRIX_BT709  1
+#define SVC_RANGE_LIMITED 0
+#define SVC_RANGE_FULL    1
+typedef struct SvcColour {
+    uint32_t struct_size;     /* sizeof(SvcColour), as SvcParams: a stale binding is refused */
+    int32_t  matrix;          /* SVC_MATRIX_* */
+    int32_t  range;           /* SVC_RANGE_* */
+    int32_t  reserved;        /* 0 */
+} SvcColour;
+int svc_resize_frames_colour(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *colour, int n,
+                             int height, int width, uint8_t *out, int sh, int sw, void *stream);
+int svc_render_crops_colour(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *in_colour, int n,
+                            int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt,
+                            const SvcColour *out_colour, int oh, int ow, int filter, int flags, void *stream);
 
 /* frames_nhwc[n][h][w][3] u8 RGB (saliency size, e.g. 140x250) -> maps_nhw[n][h][w] u8.
  * Frame-major output; the reference's [h][w][n] view is a transpose done by the
@@ -347,7 +404,7 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
  * the same stream, measured at read time, is taken off every launch: calibrated against rocprofv3 kernel durations) and the number of launches recorded since the last
  * read, and resets the log.  Nothing like it exists in the
  * reference (its timers are host wall-clock accumulators, smartVidCrop.py:98-127). */
-#define SVC_K_RESIZE 0     /* svc_resize_frames_u8 / _nv12 / _layout */
+#define SVC_K_RESIZE 0     /* svc_resize_frames_u8 / _nv12 / _layout / _colour */
 #define SVC_K_LANCZOS 1
 #define SVC_K_STEM 2
 #define SVC_K_PW 3
@@ -359,7 +416,7 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
 #define SVC_K_CORE 9
 #define SVC_K_PRIM 10
 #define SVC_K_FINISH 11
-#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 / _u8_to_nv12 / _nv12_to_nv12 / _layout / _filter */
+#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 / _u8_to_nv12 / _nv12_to_nv12 / _layout / _filter / _colour */
 #define SVC_K_BORDER 13    /* svc_border_profile_u8 (the fused form, svc_saliency_profile_u8, counts under SVC_K_SMOOTH) */
 #define SVC_K_COUNT 14
 int svc_profile_enable(SvcHandle *h, int kernel_class);

@@ -20,7 +20,8 @@ EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'sv
            'svc_saliency_census_u8', 'svc_transnet_predict_rows', 'svc_transnet_config_get', 'svc_transnet_config_set',
            'svc_render_crops_u8', 'svc_debug_transnet_tap', 'svc_border_profile_u8', 'svc_saliency_profile_u8',
            'svc_resize_frames_nv12', 'svc_render_crops_nv12', 'svc_render_crops_u8_to_nv12', 'svc_render_crops_nv12_to_nv12', 'svc_debug_run_node',
-           'svc_resize_frames_layout', 'svc_render_crops_layout', 'svc_render_crops_filter', 'svc_debug_net_plan')
+           'svc_resize_frames_layout', 'svc_render_crops_layout', 'svc_render_crops_filter', 'svc_debug_net_plan',
+           'svc_resize_frames_colour', 'svc_render_crops_colour')
 
 
 class SvcParams(ctypes.Structure):
@@ -42,6 +43,17 @@ FILTER_LINEAR, FILTER_LANCZOS = 0, 1    # include/svc.h: SVC_FILTER_*
 class SvcFrameLayout(ctypes.Structure):
     _fields_ = [('struct_size', ctypes.c_uint32), ('pix_fmt', ctypes.c_int32), ('frame_stride', ctypes.c_int64),
                 ('pitch', ctypes.c_int64), ('chroma_offset', ctypes.c_int64), ('chroma_pitch', ctypes.c_int64)]
+
+
+MATRIX_BT601, MATRIX_BT709 = 0, 1       # include/svc.h: SVC_MATRIX_*
+RANGE_LIMITED, RANGE_FULL = 0, 1        # include/svc.h: SVC_RANGE_*
+
+
+COLOUR_ENTRIES = ('svc_resize_frames_colour', 'svc_render_crops_colour')
+
+
+class SvcColour(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_uint32), ('matrix', ctypes.c_int32), ('range', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
 def make_params(CP):
@@ -94,6 +106,13 @@ def load():
     lib.svc_resize_frames_layout.argtypes = [vp, vp, ctypes.POINTER(SvcFrameLayout), i32, i32, i32, vp, i32, i32, vp]
     lib.svc_render_crops_layout.argtypes = [vp, vp, ctypes.POINTER(SvcFrameLayout), i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     lib.svc_render_crops_filter.argtypes = [vp, vp, ctypes.POINTER(SvcFrameLayout), i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp]
+    # (the two colour entries came without an ABI bump, as svc_render_crops_filter did: a build of the same revision that lacks
+    # them -- SVC_LIB, an A/B run against an older build -- loads, and a call with a non-default colour fails by the symbol's name)
+    if all(hasattr(lib, name) for name in COLOUR_ENTRIES):
+        cp = ctypes.POINTER(SvcColour)
+        lib.svc_resize_frames_colour.argtypes = [vp, vp, ctypes.POINTER(SvcFrameLayout), cp, i32, i32, i32, vp, i32, i32, vp]
+        lib.svc_render_crops_colour.argtypes = [vp, vp, ctypes.POINTER(SvcFrameLayout), cp, i32, i32, i32, vp, i32, i32, vp, i32, cp, i32, i32,
+                                                i32, i32, vp]
     lib.svc_saliency_u8.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.svc_saliency_thresholded_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp]
     lib.svc_threshold_u8.argtypes = [vp, vp, sz, i32, vp]
@@ -132,7 +151,7 @@ def load():
     f64 = ctypes.c_double
     lib.svc_host_focus_stability.argtypes = [vp, vp, i32, vp, i32, i32, f64, i32, f64, f64, f64, vp, vp]
     for name in EXPORTS:
-        if name not in ('svc_last_error', 'svc_abi_version'):
+        if name not in ('svc_last_error', 'svc_abi_version') and (name not in COLOUR_ENTRIES or hasattr(lib, name)):
             getattr(lib, name).restype = i32
     _lib = lib
     return lib

@@ -10,8 +10,9 @@
 //     k_render_copy_px<Src, Dst>                     the copy for everything they leave
 //     k_render_resize<Src, Dst>                      the resampled crop
 //     k_render_lanczos<Src, Dst>                     the crop resampled as PIL.Image.resize(LANCZOS) does it (no counterpart: svc_render_crops_filter)
-//   SrcNv12          BT.601 conversion fused into both (no counterpart: the reference is handed RGB)
-//   DstNv12          the same crops written as NV12, the forward BT.601 transform fused in (no counterpart: the reference hands RGB to its writer)
+//   SrcNv12          YUV -> RGB conversion fused into both (no counterpart: the reference is handed RGB)
+//   DstNv12          the same crops written as NV12, the forward transform fused in (no counterpart: the reference hands RGB to its writer)
+//   Nv12Dec, Nv12Enc the colour (matrix x range: SvcColour) of those two, run-time kernel arguments
 #include <algorithm>
 
 #include "svc_cvlinear.h"
@@ -99,12 +100,69 @@ struct Pitched {
 };
 
 // --------------------------------------------------------------------------------------
+// Colours: the constants of an NV12 frame's YUV <-> RGB transform (SvcColour: a matrix and a range; include/svc.h states the
+// table and the rule it is derived by).  They reach the kernels by value with the kernel arguments, so every use is a scalar
+// register.  NoColour: what an RGB source or sink takes in their place (an empty struct, like Packed).
+// --------------------------------------------------------------------------------------
+struct NoColour {};
+struct Nv12Dec { int yoff, cy, cvr, cvg, cug, cub; };                   // SrcNv12: nv12_rgb; yoff = (1 << 19) - Y0 * CY
+struct Nv12Enc { int yoff, yr, yg, yb, ur, ug, ub, vr, vg, vb; };       // DstNv12: rgb_luma, rgb_chroma; yoff = (Y0 << 20) + (1 << 19)
+struct Colours { Nv12Dec dec; Nv12Enc enc; };                           // of a call's source and sink (each takes its part: col)
+
+#define YOFF(y0) (((y0) << 20) + (1 << 19))
+#define DOFF(y0, cy) ((1 << 19) - (y0) * (cy)), (cy)
+static const Nv12Dec COLOUR_DEC[2][2] = {         // [matrix][range]
+    {{DOFF(16, 1220542), 1673527, -852492, -409993, 2116026}, {DOFF(0, 1048576), 1470104, -748826, -360853, 1858077}},
+    {{DOFF(16, 1220945), 1879825, -558796, -223607, 2215014}, {DOFF(0, 1048576), 1651297, -490864, -196424, 1945738}}};
+#undef DOFF
+static const Nv12Enc COLOUR_ENC[2][2] = {
+    {{YOFF(16), 269484, 528482, 102760, -155188, -305135, 460324, 460324, -385875, -74448},
+     {YOFF(0), 313524, 615514, 119538, -176932, -347356, 524288, 524288, -439026, -85262}},
+    {{YOFF(16), 191455, 644068, 65019, -105533, -355018, 460551, 460551, -418321, -42230},
+     {YOFF(0), 222927, 749942, 75707, -120138, -404150, 524288, 524288, -476214, -48074}}};
+#undef YOFF
+static const Colours COLOURS_DEFAULT = {COLOUR_DEC[SVC_MATRIX_BT601][SVC_RANGE_LIMITED], COLOUR_ENC[SVC_MATRIX_BT601][SVC_RANGE_LIMITED]};
+
+// One SvcColour of a call, checked (`what`: "colour", "in_colour", "out_colour") -> its indices.  NULL: BT.601 limited.  A
+// colour given for an RGB side (`nv12` false) is refused: nothing there would read it.  Plain comparisons, before any device work.
+static int colour_check(const char *name, const char *what, const SvcColour *c, bool nv12, int &matrix, int &range) {
+    matrix = SVC_MATRIX_BT601;
+    range = SVC_RANGE_LIMITED;
+    if (!c) return SVC_OK;
+    if (c->struct_size != sizeof(SvcColour)) {
+        svc_set_error("%s: %s: SvcColour.struct_size is %u, this library's is %zu (a stale binding)", name, what, c->struct_size, sizeof(SvcColour));
+        return SVC_E_INVALID;
+    }
+    if (c->matrix != SVC_MATRIX_BT601 && c->matrix != SVC_MATRIX_BT709) {
+        svc_set_error("%s: %s: unknown matrix %d (SVC_MATRIX_BT601 or SVC_MATRIX_BT709)", name, what, c->matrix);
+        return SVC_E_INVALID;
+    }
+    if (c->range != SVC_RANGE_LIMITED && c->range != SVC_RANGE_FULL) {
+        svc_set_error("%s: %s: unknown range %d (SVC_RANGE_LIMITED or SVC_RANGE_FULL)", name, what, c->range);
+        return SVC_E_INVALID;
+    }
+    if (c->reserved != 0) {
+        svc_set_error("%s: %s: reserved is %d, it must be 0", name, what, c->reserved);
+        return SVC_E_INVALID;
+    }
+    if (!nv12) {
+        svc_set_error("%s: %s is given but that side is rgb24: a colour describes NV12 frames (pass NULL)", name, what);
+        return SVC_E_INVALID;
+    }
+    matrix = c->matrix;
+    range = c->range;
+    return SVC_OK;
+}
+
+// --------------------------------------------------------------------------------------
 // Pixel sources: what the kernels below ask of a frame format, in the layout Lay (`L`: the kernel's layout argument).
 //   size_ok, size_rule   the pictures the format can hold, and the words the error text says it with
 //   frame_bytes          bytes of one packed frame
 //   extent               bytes from a frame's start to the end of its last plane row: the kernels read inside
 //                        [frames, frames + (n - 1) * L.frame + extent) and nowhere else
 //   vec_ok               whether the 16-byte paths (px16, stage_row's vec) may run on this layout
+//   colour, col          the colour constants the source converts with (a kernel argument, K below; NoColour for RGB) and the
+//                        source's part of a Colours pair
 //   px<BGR>              pixel (y, x) of the frame at `fr` as r | g << 8 | b << 16 (BGR: b | g << 8 | r << 16), byte loads
 //   px16<BGR>            pixels x .. x + 15 of row y as 48 bytes (o[12], little-endian dwords) through aligned 16-byte loads
 //                        (the buffer is 16-aligned and ends at `end`).  x may be below 0 by less than 16 (the copy kernel's
@@ -124,6 +182,8 @@ struct Pitched {
 template <class Lay>
 struct SrcRgb {                                 // u8 [h][w][3]; Pitched: rows `pitch` bytes apart
     typedef Lay lay;
+    typedef NoColour colour;
+    static colour col(const Colours &) { return NoColour(); }
     static bool size_ok(int h, int w) { return h >= 1 && w >= 1; }
     static const char *size_rule() { return ""; }
     __host__ __device__ static size_t frame_bytes(int h, int w) { return (size_t)h * w * 3; }
@@ -132,7 +192,7 @@ struct SrcRgb {                                 // u8 [h][w][3]; Pitched: rows `
     static bool vec_ok(const Lay &) { return true; }        // ld48 takes any address
 
     template <bool BGR>
-    __device__ __forceinline__ static uint32_t px(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x) {
+    __device__ __forceinline__ static uint32_t px(const uint8_t *__restrict__ fr, const Lay &L, const colour &, int h, int w, int y, int x) {
         const uint8_t *s = fr + L.template rgb<size_t>(w, y, x);
         const uint32_t c0 = s[0], c1 = s[1], c2 = s[2];
         return BGR ? c2 | (c1 << 8) | (c0 << 16) : c0 | (c1 << 8) | (c2 << 16);
@@ -140,8 +200,8 @@ struct SrcRgb {                                 // u8 [h][w][3]; Pitched: rows `
 
     // one 48-byte run of the row, as it lies there
     template <bool BGR>
-    __device__ __forceinline__ static void px16(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x, const uint8_t *end,
-                                                uint32_t (&o)[12]) {
+    __device__ __forceinline__ static void px16(const uint8_t *__restrict__ fr, const Lay &L, const colour &, int h, int w, int y, int x,
+                                                const uint8_t *end, uint32_t (&o)[12]) {
         ld48(fr + L.template rgb<ptrdiff_t>(w, y, x), end, o);
     }
 
@@ -165,8 +225,8 @@ struct SrcRgb {                                 // u8 [h][w][3]; Pitched: rows `
     }
 
     // vec: the aligned 16-byte words that hold the span, so the row starts at the span's own 16-byte phase
-    __device__ __forceinline__ static int stage_row(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x, int bw,
-                                                    uint8_t *row, int span_cap, const uint8_t *end, int vec) {
+    __device__ __forceinline__ static int stage_row(const uint8_t *__restrict__ fr, const Lay &L, const colour &, int h, int w, int y, int x,
+                                                    int bw, uint8_t *row, int span_cap, const uint8_t *end, int vec) {
         const uint8_t *a = fr + L.template rgb<size_t>(w, y, x);
         const int span = bw * 3;
         if (vec) {
@@ -182,37 +242,36 @@ struct SrcRgb {                                 // u8 [h][w][3]; Pitched: rows `
 
 // NV12 (no counterpart in the reference: its frames are decoded to RGB by OpenCV before it sees them).  A frame of a
 // height x width picture is u8 [height * 3 / 2][width]: `height` luma rows, then height / 2 rows of interleaved U V pairs;
-// pixel (y, x) takes Y[y][x] and the pair (y >> 1, x >> 1).  The conversion is BT.601 limited range in 20-bit fixed point
-// (the constants OpenCV publishes for COLOR_YUV2RGB_NV12); everything behind it -- the INTER_LINEAR arithmetic, the
-// window rules, the output layouts -- is shared with the RGB source, so the results are the RGB source's on the converted
-// frames.  Another matrix or range changes these constants and nothing else.
+// pixel (y, x) takes Y[y][x] and the pair (y >> 1, x >> 1).  The conversion is 20-bit fixed point in the frames' colour
+// (Nv12Dec: BT.601 or BT.709, limited or full range; include/svc.h states the table); everything behind it -- the
+// INTER_LINEAR arithmetic, the window rules, the output layouts -- is shared with the RGB source, so the results are the RGB
+// source's on the converted frames.  Another matrix or range changes the constants and nothing else, so they are a kernel
+// argument (wave-uniform: scalar registers), not a template parameter: the kernels are bound by memory, and a compile-time
+// colour would multiply the NV12 -> NV12 instances by 16.
 #define NV12_SHIFT 20
-#define NV12_Y0 16
 #define NV12_C0 128
-#define NV12_CY 1220542
-#define NV12_CVR 1673527
-#define NV12_CVG (-852492)
-#define NV12_CUG (-409993)
-#define NV12_CUB 2116026
 
-// one pixel -> r | g << 8 | b << 16 (BGR: b | g << 8 | r << 16); int32 throughout (largest magnitude 5.7e8)
+// one pixel -> r | g << 8 | b << 16 (BGR: b | g << 8 | r << 16); int32 throughout (largest magnitude 5.8e8)
 template <bool BGR>
-__device__ __forceinline__ uint32_t nv12_rgb(int Y, int U, int V) {
+__device__ __forceinline__ uint32_t nv12_rgb(const Nv12Dec &K, int Y, int U, int V) {
     // (__mul24: both factors fit 24 bits and the products 32, so the full-rate 24-bit multiply is exact)
-    const int yy = __mul24(max(0, Y - NV12_Y0), NV12_CY) + (1 << (NV12_SHIFT - 1)), u = U - NV12_C0, v = V - NV12_C0;
+    // yy = max(0, Y - Y0) * CY + (1 << 19), taken as max(Y * CY + yoff, 1 << 19): the same number for every Y (CY > 0)
+    const int yy = max(__mul24(Y, K.cy) + K.yoff, 1 << (NV12_SHIFT - 1)), u = U - NV12_C0, v = V - NV12_C0;
     // clamp(x >> 20, 0, 255) taken as clamp(x, 0, 2^28 - 1) >> 20 (the same value).  Written the first way, hipcc turns two
     // clamped shifts that are packed next to each other into one v_ashr_pk_u8_i32 and then relies on the upper half of its
     // result being zero, which it is not on gfx950 (seen as stray bits in bytes 2 and 3 of every third output dword).
     const int top = (256 << NV12_SHIFT) - 1;
-    const int r = min(max(yy + __mul24(NV12_CVR, v), 0), top) >> NV12_SHIFT;
-    const int g = min(max(yy + __mul24(NV12_CVG, v) + __mul24(NV12_CUG, u), 0), top) >> NV12_SHIFT;
-    const int b = min(max(yy + __mul24(NV12_CUB, u), 0), top) >> NV12_SHIFT;
+    const int r = min(max(yy + __mul24(K.cvr, v), 0), top) >> NV12_SHIFT;
+    const int g = min(max(yy + __mul24(K.cvg, v) + __mul24(K.cug, u), 0), top) >> NV12_SHIFT;
+    const int b = min(max(yy + __mul24(K.cub, u), 0), top) >> NV12_SHIFT;
     return BGR ? (uint32_t)(b | (g << 8) | (r << 16)) : (uint32_t)(r | (g << 8) | (b << 16));
 }
 
 template <class Lay>
 struct SrcNv12 {                                // u8 [h * 3 / 2][w]; Pitched: luma rows `pitch` apart, U V rows `chroma_pitch` apart from `chroma_offset`
     typedef Lay lay;
+    typedef Nv12Dec colour;
+    static colour col(const Colours &c) { return c.dec; }
     static bool size_ok(int h, int w) { return h >= 2 && w >= 2 && !(h & 1) && !(w & 1); }       // even, >= 2
     static const char *size_rule() { return " (height and width of an NV12 picture are even)"; }
     __host__ __device__ static size_t frame_bytes(int h, int w) { return (size_t)(h + h / 2) * w; }
@@ -224,16 +283,16 @@ struct SrcNv12 {                                // u8 [h * 3 / 2][w]; Pitched: l
     static bool vec_ok(const Pitched &L) { return !((L.frame_stride | L.chroma_offset | L.chroma_pitch) & 1); }
 
     template <bool BGR>
-    __device__ __forceinline__ static uint32_t px(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x) {
+    __device__ __forceinline__ static uint32_t px(const uint8_t *__restrict__ fr, const Lay &L, const colour &K, int h, int w, int y, int x) {
         const uint8_t *c = fr + L.template chroma<size_t>(h, w, y, x);
-        return nv12_rgb<BGR>(fr[L.template luma<size_t>(w, y, x)], c[0], c[1]);
+        return nv12_rgb<BGR>(K, fr[L.template luma<size_t>(w, y, x)], c[0], c[1]);
     }
 
     // the 16 luma bytes and the 18 bytes that hold their (at most nine) chroma pairs, each through two aligned 16-byte
     // loads; the chroma index is taken from frame coordinates, so x and y may be odd
     template <bool BGR>
-    __device__ __forceinline__ static void px16(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x, const uint8_t *end,
-                                                uint32_t (&o)[12]) {
+    __device__ __forceinline__ static void px16(const uint8_t *__restrict__ fr, const Lay &L, const colour &K, int h, int w, int y, int x,
+                                                const uint8_t *end, uint32_t (&o)[12]) {
         uint64_t Y[3], C[3];
         ld24(fr + L.template luma<ptrdiff_t>(w, y, x), end, Y[0], Y[1], Y[2]);
         ld24(fr + L.template chroma<ptrdiff_t>(h, w, y, x), end, C[0], C[1], C[2]);      // (x & ~1 = 2 * (x >> 1), also for x < 0)
@@ -245,7 +304,7 @@ struct SrcNv12 {                                // u8 [h * 3 / 2][w]; Pitched: l
             const int p0 = i >> 1, p1 = (i + 1) >> 1;
             const uint32_t h0 = (uint32_t)(C[p0 >> 2] >> (16 * (p0 & 3))) & 0xffffu, h1 = (uint32_t)(C[p1 >> 2] >> (16 * (p1 & 3))) & 0xffffu;
             const uint32_t uv = (i & 1) && odd ? h1 : h0;
-            p[i] = nv12_rgb<BGR>((int)((Y[i >> 3] >> (8 * (i & 7))) & 0xffu), (int)(uv & 0xffu), (int)(uv >> 8));
+            p[i] = nv12_rgb<BGR>(K, (int)((Y[i >> 3] >> (8 * (i & 7))) & 0xffu), (int)(uv & 0xffu), (int)(uv >> 8));
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {                     // four pixels = three dwords
@@ -259,19 +318,19 @@ struct SrcNv12 {                                // u8 [h * 3 / 2][w]; Pitched: l
     __device__ __forceinline__ static void order16(uint32_t (&)[12]) {}      // converted straight to the order asked for
 
     // the row is converted while it is staged; vec: 16 pixels per thread through px16
-    __device__ __forceinline__ static int stage_row(const uint8_t *__restrict__ fr, const Lay &L, int h, int w, int y, int x, int bw,
-                                                    uint8_t *row, int span_cap, const uint8_t *end, int vec) {
+    __device__ __forceinline__ static int stage_row(const uint8_t *__restrict__ fr, const Lay &L, const colour &K, int h, int w, int y, int x,
+                                                    int bw, uint8_t *row, int span_cap, const uint8_t *end, int vec) {
         if (vec) {
             for (int g = threadIdx.x; 16 * g < bw; g += 256) {
                 uint32_t o[12];
-                px16<false>(fr, L, h, w, y, x + 16 * g, end, o);
+                px16<false>(fr, L, K, h, w, y, x + 16 * g, end, o);
 #pragma unroll
                 for (int j = 0; j < 3; ++j)                     // (the last group's words past the row's capacity are never read)
                     if (48 * g + 16 * j + 16 <= span_cap) ((uint4 *)(row + 48 * g))[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
             }
         } else {
             for (int i = threadIdx.x; i < bw; i += 256) {
-                const uint32_t v = px<false>(fr, L, h, w, y, x + i);
+                const uint32_t v = px<false>(fr, L, K, h, w, y, x + i);
                 row[3 * i] = (uint8_t)v;
                 row[3 * i + 1] = (uint8_t)(v >> 8);
                 row[3 * i + 2] = (uint8_t)(v >> 16);
@@ -288,7 +347,7 @@ struct SrcNv12 {                                // u8 [h * 3 / 2][w]; Pitched: l
 template <class Src>
 __global__ __launch_bounds__(256) void k_cv_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                    const int *__restrict__ tab, int n, int h, int w, int oh, int ow,
-                                                   const typename Src::lay L) {
+                                                   const typename Src::lay L, const typename Src::colour K) {
     const CvLinear T(tab, oh, ow);
     size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
     size_t total = (size_t)n * oh * ow;
@@ -301,8 +360,8 @@ __global__ __launch_bounds__(256) void k_cv_resize(const uint8_t *__restrict__ i
     T.row(oy, h, y0, y1, b0, b1);
     T.col(ox, w, sx, sx1, a0, a1, inner);
     const uint8_t *fr = in + f * L.template frame<Src>(h, w);
-    const uint32_t p00 = Src::template px<false>(fr, L, h, w, y0, sx), p01 = Src::template px<false>(fr, L, h, w, y0, sx1);
-    const uint32_t p10 = Src::template px<false>(fr, L, h, w, y1, sx), p11 = Src::template px<false>(fr, L, h, w, y1, sx1);
+    const uint32_t p00 = Src::template px<false>(fr, L, K, h, w, y0, sx), p01 = Src::template px<false>(fr, L, K, h, w, y0, sx1);
+    const uint32_t p10 = Src::template px<false>(fr, L, K, h, w, y1, sx), p11 = Src::template px<false>(fr, L, K, h, w, y1, sx1);
     uint8_t *o = out + gid * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c)
@@ -328,8 +387,8 @@ static int cv_tab(SvcHandle *h, int height, int width, int sh, int sw, const int
 }
 
 template <class Src>
-static int resize_frames(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, int n, int height,
-                         int width, uint8_t *out, int sh, int sw, void *stream) {
+static int resize_frames(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, const Colours &C, int n,
+                         int height, int width, uint8_t *out, int sh, int sw, void *stream) {
     if (!h || n < 0 || (n > 0 && (!frames || !out)) || !Src::size_ok(height, width) || sh < 1 || sw < 1) {     // n = 0: a no-op, null buffers allowed
         svc_set_error("%s: invalid argument%s", name, Src::size_rule());
         return SVC_E_INVALID;
@@ -342,18 +401,18 @@ static int resize_frames(const char *name, SvcHandle *h, const uint8_t *frames, 
     size_t total = (size_t)n * sh * sw;
     ProfScope ps(h, SVC_K_RESIZE, (hipStream_t)stream);
     k_cv_resize<Src><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
-        frames, out, tab, n, height, width, sh, sw, L);
+        frames, out, tab, n, height, width, sh, sw, L, Src::col(C));
     SVC_CHECK_LAUNCH();
     return SVC_OK;
 }
 
 extern "C" int svc_resize_frames_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
                                     uint8_t *out, int sh, int sw, void *stream) {
-    return resize_frames<SrcRgb<Packed>>("svc_resize_frames_u8", h, frames, Packed(), n, height, width, out, sh, sw, stream);
+    return resize_frames<SrcRgb<Packed>>("svc_resize_frames_u8", h, frames, Packed(), COLOURS_DEFAULT, n, height, width, out, sh, sw, stream);
 }
 extern "C" int svc_resize_frames_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
                                       uint8_t *out, int sh, int sw, void *stream) {
-    return resize_frames<SrcNv12<Packed>>("svc_resize_frames_nv12", h, frames, Packed(), n, height, width, out, sh, sw, stream);
+    return resize_frames<SrcNv12<Packed>>("svc_resize_frames_nv12", h, frames, Packed(), COLOURS_DEFAULT, n, height, width, out, sh, sw, stream);
 }
 
 // --------------------------------------------------------------------------------------
@@ -390,7 +449,8 @@ __device__ __forceinline__ void row_out(uint8_t *__restrict__ dst, const uint8_t
 template <class Src, bool BGR>
 __global__ __launch_bounds__(256) void k_render_copy_to_rgb(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                             const int32_t *__restrict__ boxes, int n, int height, int width, int bh,
-                                                            int bw, const uint8_t *in_end, const typename Src::lay L) {
+                                                            int bw, const uint8_t *in_end, const typename Src::lay L, const typename Src::colour KI,
+                                                            const NoColour) {
     const long long total_px = (long long)n * bh * bw, p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 16;
     if (p0 >= total_px) return;
     const size_t fstride = L.template frame<Src>(height, width);
@@ -400,13 +460,13 @@ __global__ __launch_bounds__(256) void k_render_copy_to_rgb(const uint8_t *__res
     int x0, y0;
     render_origin(boxes, f, height, width, bh, bw, x0, y0);
     uint32_t o[12];
-    Src::template px16<BGR>(in + f * fstride, L, height, width, y0 + r, x0 + col, in_end, o);
+    Src::template px16<BGR>(in + f * fstride, L, KI, height, width, y0 + r, x0 + col, in_end, o);
     const int k = bw - col;                                     // pixels of the group in row R
     if (k < 16 && p0 + k < total_px) {
         if (++r == bh) { r = 0; ++f; }
         render_origin(boxes, f, height, width, bh, bw, x0, y0);
         uint32_t o2[12];                                         // bytes [3k, 48) = the first pixels of the next row
-        Src::template px16<BGR>(in + f * fstride, L, height, width, y0 + r, x0 - k, in_end, o2);
+        Src::template px16<BGR>(in + f * fstride, L, KI, height, width, y0 + r, x0 - k, in_end, o2);
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
             const int lim = 3 * k - 4 * i;                       // bytes of dword i that stay with row R
@@ -432,42 +492,37 @@ __global__ __launch_bounds__(256) void k_render_copy_to_rgb(const uint8_t *__res
 // --------------------------------------------------------------------------------------
 // render to NV12 (no counterpart in the reference, whose renderer hands RGB / BGR to OpenCV's writer).  The RGB crop C of a
 // frame is exactly what the RGB output is (same window rules, same clamping, the copy or the INTER_LINEAR
-// resampling); the output frame u8 [oh * 3 / 2][ow] (oh, ow even) is BT.601 limited range of C in 20-bit fixed point, int32:
-//   Y[y][x] = (269484 r + 528482 g + 102760 b + (16 << 20) + (1 << 19)) >> 20
-//   U[j][i] = (-155188 sr - 305135 sg + 460324 sb + (128 << 22) + (1 << 21)) >> 22      sr, sg, sb = sums over the 2 x 2 block
-//   V[j][i] = ( 460324 sr - 385875 sg -  74448 sb + (128 << 22) + (1 << 21)) >> 22      C[2j .. 2j+1][2i .. 2i+1]
-// Y lands in 16..235 and U, V in 16..240 for every input: no clamp.  Another matrix or range changes these constants only.
+// resampling); the output frame u8 [oh * 3 / 2][ow] (oh, ow even) is C in the output's colour (Nv12Enc: BT.601 or BT.709,
+// limited or full range; include/svc.h states the table), 20-bit fixed point, int32:
+//   Y[y][x] = clamp((YR r + YG g + YB b + (Y0 << 20) + (1 << 19)) >> 20)
+//   U[j][i] = clamp((UR sr + UG sg + UB sb + (128 << 22) + (1 << 21)) >> 22)      sr, sg, sb = sums over the 2 x 2 block
+//   V[j][i] = clamp((VR sr + VG sg + VB sb + (128 << 22) + (1 << 21)) >> 22)      C[2j .. 2j+1][2i .. 2i+1]
+// Limited range lands in 16..235 (Y) and 16..240 (U, V) for every input and the clamp never fires; full range reaches 256 in
+// U for pure blue and in V for pure red, which the clamp makes 255.  Another matrix or range changes the constants only.
 // NV12 in, NV12 out is the same thing on the converted crop; copying the planes of a native-size window at an even origin
 // would give other bytes (and a picture that was never RGB) and is not done here.
 // --------------------------------------------------------------------------------------
-#define YUV_CRY 269484
-#define YUV_CGY 528482
-#define YUV_CBY 102760
-#define YUV_CRU (-155188)
-#define YUV_CGU (-305135)
-#define YUV_CBU 460324
-#define YUV_CRV 460324
-#define YUV_CGV (-385875)
-#define YUV_CBV (-74448)
-
 // (__mul24: the coefficients are below 2^23 in magnitude, the other factor at most 1020, the products fit 32 bits: exact.
-// Every sum is positive (largest 1.01e9), so the shift is taken on the unsigned value -- the same number as the arithmetic
-// one -- and the byte is masked before it is packed: nothing here has the shape of the clamped shifts of nv12_rgb.)
-__device__ __forceinline__ uint32_t rgb_luma(uint32_t p) {                 // p = r | g << 8 | b << 16
+// Every sum is positive (5.2e5 .. 1.074e9), so the shift is taken on the unsigned value -- the same number as the arithmetic
+// one -- and the clamp has only its upper side.  Y needs none in any of the four colours (it ends in 0..255: the byte is
+// masked, as it always was); U and V are cut at 2^30 - 1 BEFORE the shift, on the unsigned value: nothing here has the shape
+// of the clamped shifts of nv12_rgb.)
+__device__ __forceinline__ uint32_t rgb_luma(const Nv12Enc &K, uint32_t p) {                 // p = r | g << 8 | b << 16
     const int r = (int)(p & 0xffu), g = (int)((p >> 8) & 0xffu), b = (int)((p >> 16) & 0xffu);
-    const int v = __mul24(YUV_CRY, r) + __mul24(YUV_CGY, g) + __mul24(YUV_CBY, b) + ((16 << 20) + (1 << 19));
+    const int v = __mul24(K.yr, r) + __mul24(K.yg, g) + __mul24(K.yb, b) + K.yoff;
     return ((uint32_t)v >> 20) & 0xffu;
 }
 // the four pixels of a 2 x 2 block -> U | V << 8
-__device__ __forceinline__ uint32_t rgb_chroma(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3) {
+__device__ __forceinline__ uint32_t rgb_chroma(const Nv12Enc &K, uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3) {
     // r and b summed in place (10-bit fields at bits 0 and 16), g on its own
     const uint32_t rb = (p0 & 0xff00ffu) + (p1 & 0xff00ffu) + (p2 & 0xff00ffu) + (p3 & 0xff00ffu);
     const int sr = (int)(rb & 0xffffu), sb = (int)(rb >> 16);
     const int sg = (int)(((p0 >> 8) & 0xffu) + ((p1 >> 8) & 0xffu) + ((p2 >> 8) & 0xffu) + ((p3 >> 8) & 0xffu));
     const int off = (128 << 22) + (1 << 21);
-    const int u = __mul24(YUV_CRU, sr) + __mul24(YUV_CGU, sg) + __mul24(YUV_CBU, sb) + off;
-    const int v = __mul24(YUV_CRV, sr) + __mul24(YUV_CGV, sg) + __mul24(YUV_CBV, sb) + off;
-    return (((uint32_t)u >> 22) & 0xffu) | ((((uint32_t)v >> 22) & 0xffu) << 8);
+    const uint32_t top = (256u << 22) - 1u;
+    const int u = __mul24(K.ur, sr) + __mul24(K.ug, sg) + __mul24(K.ub, sb) + off;
+    const int v = __mul24(K.vr, sr) + __mul24(K.vg, sg) + __mul24(K.vb, sb) + off;
+    return (min((uint32_t)u, top) >> 22) | ((min((uint32_t)v, top) >> 22) << 8);
 }
 
 // pixel i (a constant once unrolled) of the 48 bytes of a px16 run -> r | g << 8 | b << 16
@@ -490,7 +545,8 @@ __device__ __forceinline__ void st16_a8(uint8_t *d, const uint32_t (&v)[4], bool
 template <class Src>
 __global__ __launch_bounds__(256) void k_render_copy_to_nv12(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                              const int32_t *__restrict__ boxes, int n, int height, int width, int bh,
-                                                             int bw, const uint8_t *in_end, const typename Src::lay L) {
+                                                             int bw, const uint8_t *in_end, const typename Src::lay L, const typename Src::colour KI,
+                                                             const Nv12Enc KO) {
     const int G = (bw + 15) >> 4, hb = bh >> 1;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long long)n * hb * G) return;
@@ -500,15 +556,15 @@ __global__ __launch_bounds__(256) void k_render_copy_to_nv12(const uint8_t *__re
     render_origin(boxes, f, height, width, bh, bw, x0, y0);
     const uint8_t *fr = in + f * L.template frame<Src>(height, width);
     uint32_t a[12], b[12];
-    Src::template px16<false>(fr, L, height, width, y0 + 2 * j, x0 + 16 * g, in_end, a);
-    Src::template px16<false>(fr, L, height, width, y0 + 2 * j + 1, x0 + 16 * g, in_end, b);
+    Src::template px16<false>(fr, L, KI, height, width, y0 + 2 * j, x0 + 16 * g, in_end, a);
+    Src::template px16<false>(fr, L, KI, height, width, y0 + 2 * j + 1, x0 + 16 * g, in_end, b);
     uint32_t ya[4] = {0u, 0u, 0u, 0u}, yb[4] = {0u, 0u, 0u, 0u}, uv[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int i = 0; i < 8; ++i) {                               // block i of the strip: pixels 2 i, 2 i + 1 of both rows
         const uint32_t p0 = run_px(a, 2 * i), p1 = run_px(a, 2 * i + 1), p2 = run_px(b, 2 * i), p3 = run_px(b, 2 * i + 1);
-        ya[i >> 1] |= (rgb_luma(p0) | (rgb_luma(p1) << 8)) << (16 * (i & 1));
-        yb[i >> 1] |= (rgb_luma(p2) | (rgb_luma(p3) << 8)) << (16 * (i & 1));
-        uv[i >> 1] |= rgb_chroma(p0, p1, p2, p3) << (16 * (i & 1));
+        ya[i >> 1] |= (rgb_luma(KO, p0) | (rgb_luma(KO, p1) << 8)) << (16 * (i & 1));
+        yb[i >> 1] |= (rgb_luma(KO, p2) | (rgb_luma(KO, p3) << 8)) << (16 * (i & 1));
+        uv[i >> 1] |= rgb_chroma(KO, p0, p1, p2, p3) << (16 * (i & 1));
     }
     uint8_t *o = out + (size_t)f * (bh + hb) * bw + 16 * g;
     const bool half = 16 * g + 16 > bw;
@@ -524,6 +580,8 @@ __global__ __launch_bounds__(256) void k_render_copy_to_nv12(const uint8_t *__re
 //   flags_ok, flags_rule     the same for the SVC_RENDER_* flags
 //   frame_bytes              bytes of one frame
 //   rows                     B: a thread of the per-pixel copy owns a B x B block of the crop, a resize workgroup B output rows
+//   colour, col              the colour constants the sink converts with (a kernel argument, K below; NoColour for RGB) and
+//                            the sink's part of a Colours pair
 //   put_block                block (j, i) of the frame at `fo` from its pixels p[B * B] (row-major, as Src::px gives them)
 //   vec_ok, vec_threads,     the copy path's vector kernel: the window widths it takes when both buffers are 16-aligned, its
 //   vec_copy<Src>            threads, the kernel
@@ -534,6 +592,8 @@ __global__ __launch_bounds__(256) void k_render_copy_to_nv12(const uint8_t *__re
 // --------------------------------------------------------------------------------------
 template <bool BGR>
 struct DstRgb {                                 // u8 [oh][ow][3]
+    typedef NoColour colour;
+    static colour col(const Colours &) { return NoColour(); }
     static constexpr bool bgr = BGR;
     static constexpr int rows = 1;
     static bool size_ok(int oh, int ow) { return oh >= 1 && ow >= 1; }
@@ -547,7 +607,7 @@ struct DstRgb {                                 // u8 [oh][ow][3]
     static auto vec_copy() { return k_render_copy_to_rgb<Src, BGR>; }
     static size_t lds_bytes(int ow) { return (size_t)ow * 3 + 16; }
 
-    __device__ __forceinline__ static void put_block(uint8_t *fo, int oh, int ow, int j, int i, const uint32_t (&p)[1]) {
+    __device__ __forceinline__ static void put_block(const colour &, uint8_t *fo, int oh, int ow, int j, int i, const uint32_t (&p)[1]) {
         uint8_t *d = fo + ((size_t)j * ow + i) * 3;
         d[0] = (uint8_t)p[0];
         d[1] = (uint8_t)(p[0] >> 8);
@@ -561,12 +621,14 @@ struct DstRgb {                                 // u8 [oh][ow][3]
     __device__ __forceinline__ static uint8_t *rgb_row(uint8_t *lds, uint8_t *const (&dst)[1], int ow, int r) {
         return lds + (int)((uintptr_t)dst[0] & 15);
     }
-    __device__ __forceinline__ static void rows_out(uint8_t *lds, uint8_t *const (&dst)[1], int ow) {
+    __device__ __forceinline__ static void rows_out(const colour &, uint8_t *lds, uint8_t *const (&dst)[1], int ow) {
         row_out(dst[0], rgb_row(lds, dst, ow, 0), ow * 3);
     }
 };
 
 struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the formula above
+    typedef Nv12Enc colour;
+    static colour col(const Colours &c) { return c.enc; }
     static constexpr bool bgr = false;
     static constexpr int rows = 2;
     static bool size_ok(int oh, int ow) { return oh >= 2 && ow >= 2 && !(oh & 1) && !(ow & 1); }
@@ -585,13 +647,13 @@ struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the form
     __host__ __device__ static int row_cap(int ow) { return (ow + 15) / 16 * 16 + 16; }
     static size_t lds_bytes(int ow) { return 2 * (size_t)rgb_cap(ow) + 3 * (size_t)row_cap(ow); }
 
-    __device__ __forceinline__ static void put_block(uint8_t *fo, int oh, int ow, int j, int i, const uint32_t (&p)[4]) {
+    __device__ __forceinline__ static void put_block(const colour &K, uint8_t *fo, int oh, int ow, int j, int i, const uint32_t (&p)[4]) {
         uint8_t *d0 = fo + (size_t)(2 * j) * ow + 2 * i, *d1 = d0 + ow, *dc = fo + (size_t)(oh + j) * ow + 2 * i;
-        const uint32_t c = rgb_chroma(p[0], p[1], p[2], p[3]);
-        d0[0] = (uint8_t)rgb_luma(p[0]);
-        d0[1] = (uint8_t)rgb_luma(p[1]);
-        d1[0] = (uint8_t)rgb_luma(p[2]);
-        d1[1] = (uint8_t)rgb_luma(p[3]);
+        const uint32_t c = rgb_chroma(K, p[0], p[1], p[2], p[3]);
+        d0[0] = (uint8_t)rgb_luma(K, p[0]);
+        d0[1] = (uint8_t)rgb_luma(K, p[1]);
+        d1[0] = (uint8_t)rgb_luma(K, p[2]);
+        d1[1] = (uint8_t)rgb_luma(K, p[3]);
         dc[0] = (uint8_t)c;
         dc[1] = (uint8_t)(c >> 8);
     }
@@ -607,7 +669,7 @@ struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the form
     }
     // every 2 x 2 block of the two RGB rows is converted into the three output rows, each at the 16-byte phase of its
     // place in the output
-    __device__ __forceinline__ static void rows_out(uint8_t *lds, uint8_t *const (&dst)[3], int ow) {
+    __device__ __forceinline__ static void rows_out(const colour &K, uint8_t *lds, uint8_t *const (&dst)[3], int ow) {
         const int cap = rgb_cap(ow);
         uint8_t *lrow[3];
 #pragma unroll
@@ -616,11 +678,11 @@ struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the form
             const uint8_t *s0 = lds + 6 * i, *s1 = s0 + cap;
             const uint32_t p0 = s0[0] | (s0[1] << 8) | (s0[2] << 16), p1 = s0[3] | (s0[4] << 8) | (s0[5] << 16);
             const uint32_t p2 = s1[0] | (s1[1] << 8) | (s1[2] << 16), p3 = s1[3] | (s1[4] << 8) | (s1[5] << 16);
-            const uint32_t c = rgb_chroma(p0, p1, p2, p3);
-            lrow[0][2 * i] = (uint8_t)rgb_luma(p0);
-            lrow[0][2 * i + 1] = (uint8_t)rgb_luma(p1);
-            lrow[1][2 * i] = (uint8_t)rgb_luma(p2);
-            lrow[1][2 * i + 1] = (uint8_t)rgb_luma(p3);
+            const uint32_t c = rgb_chroma(K, p0, p1, p2, p3);
+            lrow[0][2 * i] = (uint8_t)rgb_luma(K, p0);
+            lrow[0][2 * i + 1] = (uint8_t)rgb_luma(K, p1);
+            lrow[1][2 * i] = (uint8_t)rgb_luma(K, p2);
+            lrow[1][2 * i + 1] = (uint8_t)rgb_luma(K, p3);
             lrow[2][2 * i] = (uint8_t)c;
             lrow[2][2 * i + 1] = (uint8_t)(c >> 8);
         }
@@ -635,7 +697,8 @@ struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the form
 template <class Src, class Dst>
 __global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                         const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
-                                                        long long total, const typename Src::lay L) {
+                                                        long long total, const typename Src::lay L, const typename Src::colour KI,
+                                                        const typename Dst::colour KO) {
     constexpr int B = Dst::rows;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
@@ -647,19 +710,22 @@ __global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restric
     const uint8_t *fr = in + f * L.template frame<Src>(height, width);
     uint32_t p[B * B];
 #pragma unroll
-    for (int k = 0; k < B * B; ++k) p[k] = Src::template px<Dst::bgr>(fr, L, height, width, y0 + B * j + k / B, x0 + B * i + k % B);
-    Dst::put_block(out + f * Dst::frame_bytes(bh, bw), bh, bw, j, i, p);
+    for (int k = 0; k < B * B; ++k) p[k] = Src::template px<Dst::bgr>(fr, L, KI, height, width, y0 + B * j + k / B, x0 + B * i + k % B);
+    Dst::put_block(KO, out + f * Dst::frame_bytes(bh, bw), bh, bw, j, i, p);
 }
 
 // Resize path: k_cv_resize's arithmetic on a window of the full frame.  One workgroup = B output rows of one frame (B =
 // Dst::rows).  Per row, the two window rows it reads are staged in LDS as RGB (Src::stage_row; R and B are swapped only on
 // the way out of them) and resampled into the LDS row the sink names; then the sink stores its rows with aligned 16-byte
 // stores (row_out).  LDS: two source rows of span_cap bytes, then Dst::lds_bytes.
+// (amdgpu_num_sgpr: 256-thread blocks are resident 8 | 7 | 6 per CU at <= 80 | <= 96 | more scalar registers, which the compiler
+// does not count as a cost; the NV12 sink's colour constants, live from the kernel's entry, would take it from 96 to 106)
 template <class Src, class Dst>
-__global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_render_resize(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                        const int *__restrict__ tab, const int32_t *__restrict__ boxes, int f0,
                                                        int height, int width, int bh, int bw, int oh, int ow, int span_cap,
-                                                       const uint8_t *in_end, int vec, const typename Src::lay L) {
+                                                       const uint8_t *in_end, int vec, const typename Src::lay L, const typename Src::colour KI,
+                                                       const typename Dst::colour KO) {
     extern __shared__ __align__(16) uint8_t sm_rr[];
     const CvLinear T(tab, oh, ow);
     const int j = blockIdx.x, f = f0 + blockIdx.y;
@@ -673,7 +739,7 @@ __global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict
         if (r) __syncthreads();                                 // row 0's resampling has read the staged rows
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-            sh[k] = Src::stage_row(fr, L, height, width, y0 + ry[k], x0, bw, sm_rr + k * span_cap, span_cap, in_end, vec);
+            sh[k] = Src::stage_row(fr, L, KI, height, width, y0 + ry[k], x0, bw, sm_rr + k * span_cap, span_cap, in_end, vec);
         if (!r) Dst::dst_rows(out, blockIdx.y, oh, ow, j, dst);
         uint8_t *orow = Dst::rgb_row(lds, dst, ow, r);
         __syncthreads();
@@ -689,7 +755,7 @@ __global__ __launch_bounds__(256) void k_render_resize(const uint8_t *__restrict
         }
     }
     __syncthreads();
-    Dst::rows_out(lds, dst, ow);
+    Dst::rows_out(KO, lds, dst, ow);
 }
 
 // the argument checks of both render launchers (render_crops, render_crops_lanczos): plain comparisons, before any device work
@@ -713,8 +779,8 @@ static int render_args_check(const char *name, SvcHandle *h, const uint8_t *fram
 }
 
 template <class Src, class Dst>
-static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, int n, int height,
-                        int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, const Colours &C, int n,
+                        int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
     int rc = render_args_check<Src, Dst>(name, h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags);
     if (rc) return rc;
     const int span_cap = (bw * 3 + 32 + 15) / 16 * 16;
@@ -740,10 +806,10 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, c
     if (copy) {
         if (Dst::vec_ok(bw) && aligned_in && aligned_out) {
             const unsigned grid = (unsigned)((Dst::vec_threads(n, bh, bw) + 255) / 256);
-            Dst::template vec_copy<Src>()<<<grid, 256, 0, s>>>(frames, out, boxes, n, height, width, bh, bw, in_end, L);
+            Dst::template vec_copy<Src>()<<<grid, 256, 0, s>>>(frames, out, boxes, n, height, width, bh, bw, in_end, L, Src::col(C), Dst::col(C));
         } else {
             const long long total = (long long)n * (bh / Dst::rows) * (bw / Dst::rows);
-            k_render_copy_px<Src, Dst><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total, L);
+            k_render_copy_px<Src, Dst><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total, L, Src::col(C), Dst::col(C));
         }
         SVC_CHECK_LAUNCH();
         return SVC_OK;
@@ -751,7 +817,7 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, c
     for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
         const dim3 grid((unsigned)(oh / Dst::rows), (unsigned)std::min(n - f0, 65535));
         k_render_resize<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * Dst::frame_bytes(oh, ow), tab, boxes, f0, height, width,
-                                                         bh, bw, oh, ow, span_cap, in_end, aligned_in, L);
+                                                         bh, bw, oh, ow, span_cap, in_end, aligned_in, L, Src::col(C), Dst::col(C));
         SVC_CHECK_LAUNCH();
     }
     return SVC_OK;
@@ -783,7 +849,8 @@ __global__ __launch_bounds__(256) void k_render_lanczos(const uint8_t *__restric
                                                         const int *__restrict__ vb, const int *__restrict__ vk, int vks,
                                                         const int32_t *__restrict__ boxes, int f0, int height, int width, int bh,
                                                         int bw, int oh, int ow, int B, int span_cap, int tile_cap,
-                                                        const uint8_t *in_end, int vec, const typename Src::lay L) {
+                                                        const uint8_t *in_end, int vec, const typename Src::lay L, const typename Src::colour KI,
+                                                        const typename Dst::colour KO) {
     extern __shared__ __align__(16) uint8_t sm_lz[];
     const int tw = (ow * 3 + 15) / 16 * 16;
     uint8_t *tile = sm_lz + LZ_STAGE * span_cap, *lds = tile + tile_cap * tw;
@@ -799,7 +866,7 @@ __global__ __launch_bounds__(256) void k_render_lanczos(const uint8_t *__restric
         int sh[LZ_STAGE];
 #pragma unroll
         for (int s = 0; s < LZ_STAGE; ++s)                      // (r + s < nr is the same for the whole workgroup)
-            sh[s] = r + s < nr ? Src::stage_row(fr, L, height, width, y0 + r_lo + r + s, x0, bw, sm_lz + s * span_cap, span_cap, in_end, vec) : 0;
+            sh[s] = r + s < nr ? Src::stage_row(fr, L, KI, height, width, y0 + r_lo + r + s, x0, bw, sm_lz + s * span_cap, span_cap, in_end, vec) : 0;
         __syncthreads();
         for (int ox = threadIdx.x; ox < ow; ox += 256) {
             const int xmin = hb[2 * ox], cnt = hb[2 * ox + 1];
@@ -859,7 +926,7 @@ __global__ __launch_bounds__(256) void k_render_lanczos(const uint8_t *__restric
             }
         }
         __syncthreads();
-        Dst::rows_out(lds, dst, ow);
+        Dst::rows_out(KO, lds, dst, ow);
     }
 }
 
@@ -923,12 +990,12 @@ static int lz_tile_rows(const std::vector<int> &vb, int oh, int B) {
 // render_crops with the Lanczos filter.  The band: the largest B <= 32 (a multiple of Dst::rows) whose LDS fits in 64 KiB
 // (include/svc.h states the formula).
 template <class Src, class Dst>
-static int render_crops_lanczos(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, int n, int height,
-                                int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+static int render_crops_lanczos(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, const Colours &C,
+                                int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
     int rc = render_args_check<Src, Dst>(name, h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags);
     if (rc) return rc;
     if (oh == bh && ow == bw)                               // both passes skipped: the exact copy
-        return render_crops<Src, Dst>(name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+        return render_crops<Src, Dst>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
     ResampleTab *ht = nullptr, *vt = nullptr;
     if ((rc = lz_tab(name, h, bw, ow, &ht)) || (rc = lz_tab(name, h, bh, oh, &vt))) return rc;
     const int span_cap = (bw * 3 + 32 + 15) / 16 * 16, tw = (ow * 3 + 15) / 16 * 16;
@@ -957,7 +1024,7 @@ static int render_crops_lanczos(const char *name, SvcHandle *h, const uint8_t *f
         k_render_lanczos<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * Dst::frame_bytes(oh, ow), (const int *)ht->bounds.p,
                                                           (const int *)ht->coeff.p, ht->ksize, (const int *)vt->bounds.p,
                                                           (const int *)vt->coeff.p, vt->ksize, boxes, f0, height, width, bh, bw, oh, ow,
-                                                          B, span_cap, tile_cap, in_end, vec, L);
+                                                          B, span_cap, tile_cap, in_end, vec, L, Src::col(C), Dst::col(C));
         SVC_CHECK_LAUNCH();
     }
     return SVC_OK;
@@ -965,34 +1032,34 @@ static int render_crops_lanczos(const char *name, SvcHandle *h, const uint8_t *f
 
 // the four source x sink pairings of one layout (flags picks the RGB sink's channel order)
 template <class Lay>
-static int render_crops_fmt(const char *name, int pix_fmt, bool to_nv12, SvcHandle *h, const uint8_t *frames, const Lay &L, int n,
+static int render_crops_fmt(const char *name, int pix_fmt, bool to_nv12, SvcHandle *h, const uint8_t *frames, const Lay &L, const Colours &C, int n,
                             int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags,
                             void *stream) {
     if (pix_fmt == SVC_FMT_NV12) {
-        if (to_nv12) return render_crops<SrcNv12<Lay>, DstNv12>(name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+        if (to_nv12) return render_crops<SrcNv12<Lay>, DstNv12>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
         return (flags & SVC_RENDER_BGR ? render_crops<SrcNv12<Lay>, DstRgb<true>> : render_crops<SrcNv12<Lay>, DstRgb<false>>)(
-            name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
     }
-    if (to_nv12) return render_crops<SrcRgb<Lay>, DstNv12>(name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    if (to_nv12) return render_crops<SrcRgb<Lay>, DstNv12>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
     return (flags & SVC_RENDER_BGR ? render_crops<SrcRgb<Lay>, DstRgb<true>> : render_crops<SrcRgb<Lay>, DstRgb<false>>)(
-        name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+        name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }
 
 extern "C" int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                    int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_u8", SVC_FMT_RGB24, false, h, frames, Packed(), n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_u8", SVC_FMT_RGB24, false, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }
 extern "C" int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                      int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_nv12", SVC_FMT_NV12, false, h, frames, Packed(), n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_nv12", SVC_FMT_NV12, false, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }
 extern "C" int svc_render_crops_u8_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                            int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_u8_to_nv12", SVC_FMT_RGB24, true, h, frames, Packed(), n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_u8_to_nv12", SVC_FMT_RGB24, true, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }
 extern "C" int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                              int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_nv12_to_nv12", SVC_FMT_NV12, true, h, frames, Packed(), n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_nv12_to_nv12", SVC_FMT_NV12, true, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1057,58 +1124,85 @@ static int layout_check(const char *name, const SvcFrameLayout *lay, int n, int 
     return SVC_OK;
 }
 
-extern "C" int svc_resize_frames_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height,
-                                        int width, uint8_t *out, int sh, int sw, void *stream) {
-    const char *name = "svc_resize_frames_layout";
+// the launchers behind the layout entries: `name` is the entry's own, the colours are checked SvcColours (NULL: BT.601 limited)
+static int resize_frames_any(const char *name, SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *colour,
+                             int n, int height, int width, uint8_t *out, int sh, int sw, void *stream) {
     Pitched L;
-    int rc = layout_check(name, layout, n, height, width, L);
+    int rc = layout_check(name, layout, n, height, width, L), m, r;
     if (rc) return rc;
-    if (layout->pix_fmt == SVC_FMT_NV12) return resize_frames<SrcNv12<Pitched>>(name, h, frames, L, n, height, width, out, sh, sw, stream);
-    return resize_frames<SrcRgb<Pitched>>(name, h, frames, L, n, height, width, out, sh, sw, stream);
-}
-extern "C" int svc_render_crops_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height,
-                                       int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
-                                       int flags, void *stream) {
-    const char *name = "svc_render_crops_layout";
-    Pitched L;
-    int rc = layout_check(name, layout, n, height, width, L);
-    if (rc) return rc;
-    if (out_fmt != SVC_FMT_RGB24 && out_fmt != SVC_FMT_NV12) {
-        svc_set_error("%s: unknown out_fmt %d (SVC_FMT_RGB24 or SVC_FMT_NV12)", name, out_fmt);
-        return SVC_E_INVALID;
-    }
-    return render_crops_fmt(name, layout->pix_fmt, out_fmt == SVC_FMT_NV12, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    const bool nv12 = layout->pix_fmt == SVC_FMT_NV12;
+    if ((rc = colour_check(name, "colour", colour, nv12, m, r))) return rc;
+    const Colours C = {COLOUR_DEC[m][r], COLOURS_DEFAULT.enc};
+    if (nv12) return resize_frames<SrcNv12<Pitched>>(name, h, frames, L, C, n, height, width, out, sh, sw, stream);
+    return resize_frames<SrcRgb<Pitched>>(name, h, frames, L, C, n, height, width, out, sh, sw, stream);
 }
 
-// --------------------------------------------------------------------------------------
-// svc_render_crops_layout with a choice of filter (include/svc.h).  The Lanczos kernels exist for the Pitched layouts only, 2
-// sources x 3 sinks: packed frames arrive as the packed layout's values.  profiles/pitched_frames.json measured that policy
-// within 4 % of the compile-time packed one on the linear kernels; six more instances would buy nothing that has been measured.
-// --------------------------------------------------------------------------------------
-extern "C" int svc_render_crops_filter(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height, int width,
-                                       const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
-                                       int filter, int flags, void *stream) {
-    const char *name = "svc_render_crops_filter";
-    if (filter == SVC_FILTER_LINEAR)
-        return svc_render_crops_layout(h, frames, layout, n, height, width, boxes, bw, bh, out, out_fmt, oh, ow, flags, stream);
-    if (filter != SVC_FILTER_LANCZOS) {
+// The Lanczos kernels exist for the Pitched layouts only, 2 sources x 3 sinks: packed frames arrive as the packed layout's
+// values.  profiles/pitched_frames.json measured that policy within 4 % of the compile-time packed one on the linear kernels; six
+// more instances would buy nothing that has been measured.  linear_name: the name the SVC_FILTER_LINEAR path reports under
+// (svc_render_crops_filter forwards to svc_render_crops_layout: its bytes, its errors).
+static int render_crops_any(const char *name, const char *linear_name, SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout,
+                            const SvcColour *in_colour, int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out,
+                            int out_fmt, const SvcColour *out_colour, int oh, int ow, int filter, int flags, void *stream) {
+    if (filter == SVC_FILTER_LINEAR) name = linear_name;
+    else if (filter != SVC_FILTER_LANCZOS) {
         svc_set_error("%s: unknown filter %d (SVC_FILTER_LINEAR or SVC_FILTER_LANCZOS)", name, filter);
         return SVC_E_INVALID;
     }
     Pitched L;
-    int rc = layout_check(name, layout, n, height, width, L);
+    int rc = layout_check(name, layout, n, height, width, L), mi, ri, mo, ro;
     if (rc) return rc;
     if (out_fmt != SVC_FMT_RGB24 && out_fmt != SVC_FMT_NV12) {
         svc_set_error("%s: unknown out_fmt %d (SVC_FMT_RGB24 or SVC_FMT_NV12)", name, out_fmt);
         return SVC_E_INVALID;
     }
     const bool nv12 = layout->pix_fmt == SVC_FMT_NV12;
+    if ((rc = colour_check(name, "in_colour", in_colour, nv12, mi, ri)) ||
+        (rc = colour_check(name, "out_colour", out_colour, out_fmt == SVC_FMT_NV12, mo, ro)))
+        return rc;
+    const Colours C = {COLOUR_DEC[mi][ri], COLOUR_ENC[mo][ro]};
+    if (filter == SVC_FILTER_LINEAR)
+        return render_crops_fmt(name, layout->pix_fmt, out_fmt == SVC_FMT_NV12, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
     if (out_fmt == SVC_FMT_NV12)
         return (nv12 ? render_crops_lanczos<SrcNv12<Pitched>, DstNv12> : render_crops_lanczos<SrcRgb<Pitched>, DstNv12>)(
-            name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
     if (flags & SVC_RENDER_BGR)
         return (nv12 ? render_crops_lanczos<SrcNv12<Pitched>, DstRgb<true>> : render_crops_lanczos<SrcRgb<Pitched>, DstRgb<true>>)(
-            name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
     return (nv12 ? render_crops_lanczos<SrcNv12<Pitched>, DstRgb<false>> : render_crops_lanczos<SrcRgb<Pitched>, DstRgb<false>>)(
-        name, h, frames, L, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+        name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+}
+
+extern "C" int svc_resize_frames_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height,
+                                        int width, uint8_t *out, int sh, int sw, void *stream) {
+    return resize_frames_any("svc_resize_frames_layout", h, frames, layout, nullptr, n, height, width, out, sh, sw, stream);
+}
+extern "C" int svc_render_crops_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height,
+                                       int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
+                                       int flags, void *stream) {
+    const char *name = "svc_render_crops_layout";
+    return render_crops_any(name, name, h, frames, layout, nullptr, n, height, width, boxes, bw, bh, out, out_fmt, nullptr, oh, ow,
+                            SVC_FILTER_LINEAR, flags, stream);
+}
+// svc_render_crops_layout with a choice of filter (include/svc.h)
+extern "C" int svc_render_crops_filter(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height, int width,
+                                       const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
+                                       int filter, int flags, void *stream) {
+    return render_crops_any("svc_render_crops_filter", "svc_render_crops_layout", h, frames, layout, nullptr, n, height, width, boxes, bw, bh,
+                            out, out_fmt, nullptr, oh, ow, filter, flags, stream);
+}
+
+// --------------------------------------------------------------------------------------
+// the same with the colour of NV12 frames chosen by the caller, per call, in and out (SvcColour: include/svc.h)
+// --------------------------------------------------------------------------------------
+extern "C" int svc_resize_frames_colour(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *colour, int n,
+                                        int height, int width, uint8_t *out, int sh, int sw, void *stream) {
+    return resize_frames_any("svc_resize_frames_colour", h, frames, layout, colour, n, height, width, out, sh, sw, stream);
+}
+extern "C" int svc_render_crops_colour(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *in_colour, int n,
+                                       int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt,
+                                       const SvcColour *out_colour, int oh, int ow, int filter, int flags, void *stream) {
+    const char *name = "svc_render_crops_colour";
+    return render_crops_any(name, name, h, frames, layout, in_colour, n, height, width, boxes, bw, bh, out, out_fmt, out_colour, oh, ow,
+                            filter, flags, stream);
 }

@@ -36,16 +36,17 @@ class _HostFeed:
             self.shape, self.k = shape, k
         return self.k
 
-    def downscale(self, frames, idx, sal_h, sal_w, pix_fmt='rgb24', layout=None):
+    def downscale(self, frames, idx, sal_h, sal_w, pix_fmt='rgb24', layout=None, colour=None):
         """frames: host frames [n,h,w,3] u8 (pix_fmt='nv12': [n,h*3/2,w]; with a layout: [n, frame_stride], staged as they are
         and read through the layout on the device, no host repack) -- a numpy array (pageable memory: gathered into
         the pinned slots by a few threads) or a PINNED torch tensor (copied from where it lies, frame by frame); idx: selected
-        frame numbers.  -> uint8 CUDA tensor [len(idx), sal_h, sal_w, 3] RGB, produced on the caller's current stream."""
+        frame numbers; colour: of nv12 frames (Engine.resize_frames').  -> uint8 CUDA tensor [len(idx), sal_h, sal_w, 3] RGB, produced
+        on the caller's current stream."""
         import torch
         out = torch.empty((len(idx), sal_h, sal_w, 3), dtype=torch.uint8, device=self.dev)
 
         def put(staged, s):
-            out[s:s + staged.shape[0]] = self.engine.resize_frames(staged, sal_h, sal_w, pix_fmt, layout)
+            out[s:s + staged.shape[0]] = self.engine.resize_frames(staged, sal_h, sal_w, pix_fmt, layout, colour)
         self.feed(frames, idx, put)
         return out
 
@@ -164,17 +165,20 @@ class FrameSource:
 
     frames: the container (np.asarray of what is neither a tensor nor one of the two objects); pix_fmt 'rgb24' (uint8
     [n, h, w, 3]) or 'nv12' (uint8 [n, h * 3 / 2, w]); layout: None for such packed frames, else the checked ops.FrameLayout
-    of uint8 [n, frame_stride] frames as a decoder left them (device, host, pinned and selected); n frames of an h x w PICTURE."""
-    __slots__ = ('kind', 'frames', 'pix_fmt', 'layout', 'n', 'h', 'w')
+    of uint8 [n, frame_stride] frames as a decoder left them (device, host, pinned and selected); n frames of an h x w PICTURE;
+    colour: the (matrix, range) nv12 frames are decoded with (ops.frame_colour's; ('bt601', 'limited') unless the video says
+    otherwise), None for rgb24, which has none."""
+    __slots__ = ('kind', 'frames', 'pix_fmt', 'layout', 'n', 'h', 'w', 'colour')
 
     @classmethod
-    def of(cls, video, pix_fmt=None, layout=None):
+    def of(cls, video, pix_fmt=None, layout=None, colour=None):
         """video: an ingest_pickle dict (frames, w, h, and optionally pix_fmt and layout=dict(pitch=, chroma_offset=,
-        chroma_pitch=) or an ops.FrameLayout), a bare container, or a FrameSource (returned as it is).  pix_fmt / layout
+        chroma_pitch=) or an ops.FrameLayout, and colour=dict(matrix='bt709', range='full'), missing keys 'bt601' / 'limited'), a bare
+        container, or a FrameSource (returned as it is).  pix_fmt / layout / colour
         describe a bare container; a dict's own entries win.  A packed dict without h / w takes them from the container's shape.
         Every refusal is raised here, before any device work: ValueError for an unknown format, an NV12 picture of odd size, a
-        container of another shape, a broken rule of ops.frame_layout, a layout on a generator; TypeError for frames that are
-        not uint8."""
+        container of another shape, a broken rule of ops.frame_layout, a layout on a generator, an unknown colour matrix or
+        range, a colour on rgb24 frames (which have none); TypeError for frames that are not uint8."""
         if isinstance(video, cls):
             return video
         import torch
@@ -186,6 +190,11 @@ class FrameSource:
         lay = video.get('layout') if is_dict and video.get('layout') is not None else layout
         fmt = (is_dict and video.get('pix_fmt')) or pix_fmt or (lay.pix_fmt if isinstance(lay, ops.FrameLayout) else 'rgb24')
         h, w = (video.get('h'), video.get('w')) if is_dict else (None, None)
+        col = video.get('colour') if is_dict and video.get('colour') is not None else colour
+        if col is not None:
+            col = ops.frame_colour(col)
+            if fmt == 'rgb24':
+                raise ValueError('colour=%r describes nv12 frames; these are rgb24, which are the colours themselves' % (col,))
         if frames is None:
             kind = None
         elif torch.is_tensor(frames):
@@ -226,13 +235,18 @@ class FrameSource:
         elif shape is not None and fmt != 'rgb24' and shape[1:] != want:
             raise ValueError('%s frames of a %d x %d picture are uint8 [n, %s], not %s' % (fmt, w, h, ', '.join(str(v) for v in want), shape))
         self.kind, self.frames, self.pix_fmt, self.layout = kind, frames, fmt, lay
+        self.colour = (col or ops.DEFAULT_COLOUR) if fmt == 'nv12' else None
         self.n = None if kind is None else len(frames) if shape is None or kind == 'selected' else shape[0]
         self.h, self.w = int(h), int(w)
         return self
 
     def key(self):
-        """The feature cache's entries for the format and -- for frames with a layout -- where their bytes lie."""
+        """The feature cache's entries for the format, -- for frames with a layout -- where their bytes lie, and -- for nv12 frames
+        that are not BT.601 limited -- their colour: features computed under one colour are never read under another."""
+        from .ops import DEFAULT_COLOUR
         key = dict(pix_fmt=self.pix_fmt)
+        if self.colour not in (None, DEFAULT_COLOUR):
+            key['colour'] = self.colour
         if self.layout is not None:
             key['layout'] = self.layout.key()
         return key
@@ -248,18 +262,18 @@ class FrameSource:
         """Frames idx (a list or a range; any order, repeats allowed) at sh x sw as RGB -> uint8 CUDA [len(idx), sh, sw, 3] on the engine's device,
         produced on the current stream."""
         import torch
-        dev, frames, fmt, lay = engine.device, self.frames, self.pix_fmt, self.layout
+        dev, frames, fmt, lay, col = engine.device, self.frames, self.pix_fmt, self.layout, self.colour
         if self.kind == 'device':
             if frames.device != dev:               # gathered where the container lies, then moved
-                return engine.resize_frames(frames[device_index(engine, idx, frames.device)].to(dev).contiguous(), sh, sw, fmt, lay)
+                return engine.resize_frames(frames[device_index(engine, idx, frames.device)].to(dev).contiguous(), sh, sw, fmt, lay, col)
             if lay is None:
                 # one run of consecutive frames is a slice of the container; any other selection is gathered with a device index
                 if _is_run(idx):
-                    return engine.resize_frames(frames[int(idx[0]):int(idx[0]) + len(idx)].contiguous(), sh, sw, fmt)
-                return engine.resize_frames(frames[device_index(engine, idx, dev)].contiguous(), sh, sw, fmt)
+                    return engine.resize_frames(frames[int(idx[0]):int(idx[0]) + len(idx)].contiguous(), sh, sw, fmt, None, col)
+                return engine.resize_frames(frames[device_index(engine, idx, dev)].contiguous(), sh, sw, fmt, None, col)
             # nothing is gathered: a selection with a constant step (consecutive frames, or every skip-th: what the ingest selects)
             # is one strided view, read with a frame stride of step surfaces; any other selection is cut into such runs
-            small = [engine.resize_frames(frames[first:first + (count - 1) * step + 1:step], sh, sw, fmt, lay if step == 1 else lay.every(step))
+            small = [engine.resize_frames(frames[first:first + (count - 1) * step + 1:step], sh, sw, fmt, lay if step == 1 else lay.every(step), col)
                      for first, count, step in _runs(idx)]
             return small[0] if len(small) == 1 else torch.cat(small) if small else torch.empty((0, sh, sw, 3), dtype=torch.uint8, device=dev)
         if self.kind == 'generator':
@@ -267,13 +281,13 @@ class FrameSource:
                 sel = frames.select(idx, index=device_index(engine, idx, dev))
             else:
                 sel = frames.select(idx)
-            return engine.resize_frames(sel.to(dev).contiguous(), sh, sw, fmt)
+            return engine.resize_frames(sel.to(dev).contiguous(), sh, sw, fmt, None, col)
         feed = getattr(engine, '_host_feed', None)
         if feed is None:
             feed = engine._host_feed = _HostFeed(engine)
         if self.kind == 'selected':
-            return feed.downscale(frames.pinned, frames.rows(idx), sh, sw, fmt, lay)
-        return feed.downscale(frames, idx, sh, sw, fmt, lay)
+            return feed.downscale(frames.pinned, frames.rows(idx), sh, sw, fmt, lay, col)
+        return feed.downscale(frames, idx, sh, sw, fmt, lay, col)
 
     def chunks(self, engine, count, chunk, consume):
         """The first `count` frames, in order and at full size, as staged chunks on the engine's device: consume(staged, s)

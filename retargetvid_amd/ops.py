@@ -65,6 +65,57 @@ RENDER_ENTRIES = {('rgb24', 'rgb24'): 'svc_render_crops_u8', ('nv12', 'rgb24'): 
                   ('rgb24', 'nv12'): 'svc_render_crops_u8_to_nv12', ('nv12', 'nv12'): 'svc_render_crops_nv12_to_nv12'}
 
 
+MATRICES = ('bt601', 'bt709')        # the colour matrices of NV12 frames (include/svc.h: SVC_MATRIX_*, by index)
+RANGES = ('limited', 'full')         # and their ranges (include/svc.h: SVC_RANGE_*, by index)
+DEFAULT_COLOUR = ('bt601', 'limited')
+# other names the same things go by (libav's colorspace / color_range names), lower case
+_MATRIX_NAMES = dict(bt601='bt601', bt470bg='bt601', smpte170m='bt601', bt709='bt709')
+_RANGE_NAMES = dict(limited='limited', tv='limited', mpeg='limited', full='full', pc='full', jpeg='full')
+
+
+def frame_colour(spec):
+    """The colour of NV12 frames, checked and normalised -> (matrix, range), one of MATRICES x RANGES.  spec: None (BT.601
+    limited), dict(matrix=, range=) with missing keys (or None) taking 'bt601' / 'limited', or a (matrix, range) pair.  Names
+    are case-insensitive; 'bt470bg' and 'smpte170m' say bt601, 'tv' / 'mpeg' say limited, 'pc' / 'jpeg' say full.  ValueError for
+    an unknown matrix, range or key -- before any device work."""
+    if spec is None:
+        return DEFAULT_COLOUR
+    if isinstance(spec, dict):
+        unknown = sorted(set(spec) - {'matrix', 'range'})
+        if unknown:
+            raise ValueError('unknown colour key %s (the keys are matrix, range)' % ', '.join(map(repr, unknown)))
+        matrix, rng = spec.get('matrix'), spec.get('range')
+    elif isinstance(spec, (tuple, list)) and len(spec) == 2:
+        matrix, rng = spec
+    else:
+        raise ValueError('a colour is dict(matrix=, range=) or a (matrix, range) pair, not %r' % (spec,))
+    m = _MATRIX_NAMES.get(str(matrix).lower()) if matrix is not None else 'bt601'
+    r = _RANGE_NAMES.get(str(rng).lower()) if rng is not None else 'limited'
+    if m is None:
+        raise ValueError('unknown colour matrix %r (one of %s)' % (matrix, ', '.join(MATRICES)))
+    if r is None:
+        raise ValueError('unknown colour range %r (one of %s)' % (rng, ', '.join(RANGES)))
+    return (m, r)
+
+
+def _side_colour(spec, fmt, what):
+    """frame_colour of one side of a call (`what` names the keyword) -> (matrix, range) or None for the default; a colour given
+    for an rgb24 side is a ValueError: nothing would read it."""
+    if spec is None:
+        return None
+    c = frame_colour(spec)
+    if fmt != 'nv12':
+        raise ValueError('%s describes nv12 frames; this side is %s (pass None)' % (what, fmt))
+    return None if c == DEFAULT_COLOUR else c
+
+
+def _colour_struct(c):
+    """(matrix, range) -> the SvcColour the C entries take; None -> NULL (BT.601 limited)."""
+    if c is None:
+        return None
+    return ctypes.byref(_lib.SvcColour(ctypes.sizeof(_lib.SvcColour), MATRICES.index(c[0]), RANGES.index(c[1]), 0))
+
+
 def frame_shape(pix_fmt, h, w):
     """Shape of one frame of a h x w picture in `pix_fmt`; ValueError for an unknown format or an NV12 picture of odd size."""
     h, w = int(h), int(w)
@@ -256,11 +307,25 @@ class Engine:
             pass
 
     # -- ingest down-scale -------------------------------------------------------------
-    def resize_frames(self, frames, sh, sw, pix_fmt='rgb24', layout=None):
+    def resize_frames(self, frames, sh, sw, pix_fmt='rgb24', layout=None, colour=None):
         """uint8 [n,h,w,3] -> uint8 [n,sh,sw,3], cv2.resize(INTER_LINEAR) semantics.  pix_fmt='nv12': frames uint8
         [n,h*3/2,w], converted to RGB inside the kernel (svc_resize_frames_nv12): the bytes of the RGB call on the converted frames.
         layout (an ops.FrameLayout): frames uint8 [n, frame_stride] as a decoder left them (svc_resize_frames_layout): the
-        bytes of the packed call on the packed pictures, without a repacking pass."""
+        bytes of the packed call on the packed pictures, without a repacking pass.
+        colour (what ops.frame_colour takes; nv12 only, else ValueError): the matrix and range the frames are decoded with
+        (svc_resize_frames_colour); None, or BT.601 limited spelled out, is the call without it."""
+        colour = _side_colour(colour, pix_fmt, 'colour')
+        if colour is not None:              # one entry for every layout: packed frames as the packed layout's values
+            if layout is None:
+                _need_cuda(frames, torch.uint8, 'frames')
+                n, h, w = picture_size(frames, pix_fmt)
+            else:
+                n, h, w = _pitched(frames, layout, pix_fmt), layout.h, layout.w
+            out = torch.empty((n, sh, sw, 3), dtype=torch.uint8, device=frames.device)
+            lay = (layout or frame_layout(pix_fmt, h, w)).struct()
+            _lib.check(self.lib.svc_resize_frames_colour(self._h, _ptr(frames), ctypes.byref(lay), _colour_struct(colour), n, h, w,
+                                                         _ptr(out), sh, sw, _stream()))
+            return out
         if layout is not None:
             n = _pitched(frames, layout, pix_fmt)
             out = torch.empty((n, sh, sw, 3), dtype=torch.uint8, device=frames.device)
@@ -276,7 +341,8 @@ class Engine:
         return out
 
     # -- rendering ------------------------------------------------------------------------
-    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None, pix_fmt='rgb24', out_fmt='rgb24', layout=None, interp='linear'):
+    def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None, pix_fmt='rgb24', out_fmt='rgb24', layout=None, interp='linear',
+                     colour=None, out_colour=None):
         """uint8 [n,h,w,3] frames on the device (pix_fmt='nv12': uint8 [n,h*3/2,w], svc_render_crops_nv12; the crops are RGB / BGR
         either way) and int32 [n,4] boxes (x1,y1,x2,y2, one window size for all; a CUDA tensor, or
         host values that are copied over) -> uint8
@@ -288,8 +354,13 @@ class Engine:
         crops are the packed call's on the packed pictures.
         interp='lanczos': resampled as PIL.Image.resize(LANCZOS) does it instead, bit for bit, window cropped first
         (svc_render_crops_filter; include/svc.h states the arithmetic); the window size is the exact copy either way.  Any
-        value outside ops.INTERPS: ValueError."""
+        value outside ops.INTERPS: ValueError.
+        colour / out_colour (what ops.frame_colour takes): the matrix and range nv12 frames are decoded with / an nv12 output
+        is encoded with, chosen independently (svc_render_crops_colour; include/svc.h states the table); None is BT.601
+        limited, and the call it always was.  A colour given for an rgb24 side: ValueError."""
         check_interp(interp)
+        _side_colour(colour, pix_fmt, 'colour')
+        _side_colour(out_colour, out_fmt if out_fmt in OUT_FMTS else 'nv12', 'out_colour')      # (an unknown out_fmt is reported as that, below)
         n = int(frames.shape[0])
         on_dev = torch.is_tensor(boxes) and boxes.is_cuda
         if n:
@@ -307,10 +378,12 @@ class Engine:
             boxes = torch.from_numpy(np.ascontiguousarray(boxes, np.int32)).to(frames.device)
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
-        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt, out_fmt, layout, interp)
+        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt, out_fmt, layout, interp, colour, out_colour)
 
-    def _render(self, frames, boxes, bw, bh, out, bgr, pix_fmt='rgb24', out_fmt='rgb24', layout=None, interp='linear'):
+    def _render(self, frames, boxes, bw, bh, out, bgr, pix_fmt='rgb24', out_fmt='rgb24', layout=None, interp='linear', colour=None,
+                out_colour=None):
         check_interp(interp)
+        colour, out_colour = _side_colour(colour, pix_fmt, 'colour'), _side_colour(out_colour, out_fmt, 'out_colour')
         _need_cuda(boxes, torch.int32, 'boxes')
         _need_cuda(out, torch.uint8, 'out')
         if layout is None:
@@ -326,6 +399,12 @@ class Engine:
             assert out.shape[3] == 3
             on, oh, ow = (int(v) for v in out.shape[:3])
         assert tuple(boxes.shape) == (n, 4) and on == n
+        if colour is not None or out_colour is not None:        # one entry for every format, layout and filter
+            lay = (layout or frame_layout(pix_fmt, h, w)).struct()
+            _lib.check(self.lib.svc_render_crops_colour(self._h, _ptr(frames), ctypes.byref(lay), _colour_struct(colour), n, h, w,
+                                                        _ptr(boxes), bw, bh, _ptr(out), OUT_FMTS.index(out_fmt), _colour_struct(out_colour),
+                                                        oh, ow, INTERPS.index(interp), RENDER_BGR if bgr else 0, _stream()))
+            return out
         if interp != 'linear':              # one entry for every format and layout: packed frames as the packed layout's values
             lay = (layout or frame_layout(pix_fmt, h, w)).struct()
             _lib.check(self.lib.svc_render_crops_filter(self._h, _ptr(frames), ctypes.byref(lay), n, h, w, _ptr(boxes), bw, bh, _ptr(out),

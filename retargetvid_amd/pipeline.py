@@ -103,9 +103,9 @@ class StreamPipeline:
             self.base, end = 0, k
         return self.ring[end:end + n]
 
-    def submit_frames(self, frames, blend_next, small=False, pix_fmt='rgb24', layout=None):
+    def submit_frames(self, frames, blend_next, small=False, pix_fmt='rgb24', layout=None, colour=None):
         """frames: uint8 CUDA [n,H,W,3] (full size: down-scaled here -- pix_fmt='nv12': [n,H*3/2,W]; layout, an ops.FrameLayout:
-        [n, frame_stride] as a decoder left them; small=True: already at
+        [n, frame_stride] as a decoder left them; colour: of nv12 frames, Engine.resize_frames'; small=True: already at
         saliency size, RGB).  Runs
         down-scale -> UNISAL saliency -> threshold -> one clustering round.  blend_next[n]: the cut test per map."""
         import torch
@@ -115,7 +115,7 @@ class StreamPipeline:
         with torch.cuda.stream(self.stream):
             if tev:
                 tev[0].record(self.stream)
-            sm = frames if small else self.eng.resize_frames(frames, self.h, self.w, pix_fmt, layout)
+            sm = frames if small else self.eng.resize_frames(frames, self.h, self.w, pix_fmt, layout, colour)
             self.eng.saliency(sm, out=dst, threshold=self.CP['t_threshold'])       # (threshold fused into the network's last kernel)
             if tev:
                 tev[1].record(self.stream)

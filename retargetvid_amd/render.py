@@ -36,7 +36,7 @@ def check_boxes(bbs, fc, h, w):
 
 
 def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, chunk=32, pix_fmt=None, out_fmt='rgb24', layout=None,
-                 interp='linear'):
+                 interp='linear', colour=None, out_colour=None):
     """Render VD['fc'] frames of `video` (the ingest_pickle dict, or its 'frames' container) at VD['bbs_np'].
     pix_fmt: the frames' format when `video` is a bare container (a dict brings its own 'pix_fmt'; default 'rgb24'); an
     unknown format, an NV12 picture of odd size or a container of another shape raise ValueError before any device work.
@@ -48,11 +48,20 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     an odd output size (pass an even out_size), bgr with it, or an unknown format raise ValueError before any device work.
     layout: the ops.FrameLayout of a bare container of uint8 [n, frame_stride] frames (a dict brings its own 'layout').
     interp: the filter an out_size is resampled with, one of ops.INTERPS: 'linear' (cv2.resize INTER_LINEAR) or 'lanczos'
-    (PIL.Image.resize LANCZOS on the cropped window, bit for bit); another value raises ValueError before any device work."""
+    (PIL.Image.resize LANCZOS on the cropped window, bit for bit); another value raises ValueError before any device work.
+    colour: the matrix and range of a bare container of nv12 frames (a dict brings its own 'colour'; ops.frame_colour states the
+    spellings).  out_colour: the colour an nv12 output is encoded with; None means the source's (BT.601 limited for an rgb24
+    source).  With out_fmt='rgb24' a given out_colour raises ValueError, as does an unknown matrix or range."""
     from .frames import FrameSource
-    from .ops import check_interp
+    from .ops import check_interp, frame_colour
     check_interp(interp)
-    src = FrameSource.of(video, pix_fmt, layout).whole()       # (resolved and checked once)
+    src = FrameSource.of(video, pix_fmt, layout, colour).whole()       # (resolved and checked once)
+    if out_colour is not None:
+        out_colour = frame_colour(out_colour)
+        if out_fmt == 'rgb24':
+            raise ValueError("out_colour=%r describes an nv12 output; out_fmt is 'rgb24'" % (out_colour,))
+    elif out_fmt == 'nv12':
+        out_colour = src.colour                                 # (None for an rgb24 source: BT.601 limited)
     fc = int(VD['fc'])
     if src.n < fc:
         raise ValueError('the container holds %d frames, the video has %d' % (src.n, fc))
@@ -77,7 +86,7 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     engine = engine or S.get_engine()
     dev = engine.device
     boxes = torch.from_numpy(np.ascontiguousarray(VD['bbs_np'][:fc], np.int32)).to(dev)
-    out = _OutRing(engine, chunk, oh, ow, sink, out_fmt, src.pix_fmt, src.layout, interp)
+    out = _OutRing(engine, chunk, oh, ow, sink, out_fmt, src.pix_fmt, src.layout, interp, src.colour, out_colour)
     src.chunks(engine, fc, chunk, lambda staged, s: out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr))
     out.flush()
     return result
@@ -87,12 +96,13 @@ class _OutRing:
     """Two device output slots and two pinned host slots: chunk c is rendered on the caller's stream into device slot c & 1,
     copied D2H on a side stream into pinned slot c & 1, and handed to the sink once the copy of chunk c + 1 is enqueued."""
 
-    def __init__(self, engine, cap, oh, ow, sink, out_fmt='rgb24', pix_fmt='rgb24', layout=None, interp='linear'):
+    def __init__(self, engine, cap, oh, ow, sink, out_fmt='rgb24', pix_fmt='rgb24', layout=None, interp='linear', colour=None, out_colour=None):
         import torch
         from .ops import frame_shape
         self.engine, self.sink, self.dev, self.out_fmt = engine, sink, engine.device, out_fmt
         self.pix_fmt, self.layout = pix_fmt, layout             # of the frames that will be pushed
         self.interp = interp
+        self.colour, self.out_colour = colour, out_colour       # of nv12 frames pushed / of an nv12 output (None: BT.601 limited)
         key = (cap, oh, ow, out_fmt)
         shape = (cap,) + frame_shape(out_fmt, oh, ow)           # slots shaped (and keyed) by the output format
         ring = engine.__dict__.get('_render_ring')
@@ -123,7 +133,7 @@ class _OutRing:
         if self.used[slot]:
             compute.wait_event(self.copied[slot])           # the device slot's previous D2H has read it
         dst = self.ring['dev'][slot][:m]
-        self.engine._render(staged, boxes, bw, bh, dst, bgr, self.pix_fmt, self.out_fmt, self.layout, self.interp)
+        self.engine._render(staged, boxes, bw, bh, dst, bgr, self.pix_fmt, self.out_fmt, self.layout, self.interp, self.colour, self.out_colour)
         self.rendered[slot].record(compute)
         with torch.cuda.stream(side):
             side.wait_event(self.rendered[slot])

@@ -22,6 +22,8 @@ TransNetV1; both stay outside this package.  ``video_path`` is therefore either 
 with fr, frame_count, w, h, frames [RGB uint8], trans_inds) or that dict itself.
 A dict with ``pix_fmt='nv12'`` holds its frames as uint8 [n, h * 3 / 2, w] (what decoders hand out; w, h = the picture's
 size): they are converted on the device inside the down-scale and the renderer, with the results of the converted RGB frames.
+Beside it, ``colour=dict(matrix='bt709', range='full')`` says which transform they are converted with (BT.601 or BT.709,
+limited or full range; missing keys 'bt601' / 'limited', ops.frame_colour); an NV12 render takes the same colour unless out_colour= names another.
 What may hold the frames, and how each kind of container is read, is stated once, on frames.FrameSource.
 Failures raise exceptions; nothing blocks on input() (the reference does at :544-545).
 """
@@ -434,18 +436,18 @@ def ingest_frames(video, crop_params, engine=None, verbose=False, shot_net=None,
     return _ingest_dict(plan, smaps, xy_stream, border_profile)
 
 
-def detect_shots(frames, fr, crop_params=None, net=None, engine=None, trans_threshold=0.1, pix_fmt='rgb24', layout=None):
+def detect_shots(frames, fr, crop_params=None, net=None, engine=None, trans_threshold=0.1, pix_fmt='rgb24', layout=None, colour=None):
     """Shot detection of the reference's video path (smartVidCrop.py:248-372, :452-457) on the device: frames
     [n, h, w, 3] uint8, or [n, h * 3 / 2, w] with pix_fmt='nv12', in any container FrameSource.of takes, or a FrameSource ->
     dict(trans_probs, segmentation, trans_inds).  layout (an ops.FrameLayout, e.g. video_layout(video)): the frames are uint8
-    [n, frame_stride] as a decoder left them and are read where they lie.  `net` is a transnetv1_handler.ShotTransNet (it owns the weights; the
+    [n, frame_stride] as a decoder left them and are read where they lie; colour: the matrix and range of bare nv12 frames (ops.frame_colour).  `net` is a transnetv1_handler.ShotTransNet (it owns the weights; the
     reference's checkpoint does not ship with it).  The frames are down-scaled to 48 x 27 in read_batch-sized pieces
     (host inputs through the pinned, double-buffered feed), so a long 1080p / 4K video never sits on the device in
     full; `segmentation` carries the reference's end-of-segment fix (every scene ends where the next one starts, the
     last one on the last frame) and trans_inds is consistent with it."""
     import torch
     from . import transnetv1_handler as T
-    src = FrameSource.of(frames, pix_fmt, layout)
+    src = FrameSource.of(frames, pix_fmt, layout, colour)
     if src.kind == 'selected':
         raise ValueError('detect_shots needs every frame of the video; %s holds only the frames the ingest selected'
                          % type(src.frames).__name__)
@@ -541,7 +543,7 @@ class _LazySmaps(dict):
 def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn='', frames_dir='',
                    temp_path=None, verbose=False, save_vid=True, callback_progress=None,
                    callback_session=None, callback_status=None, copy_sound=False, engine=None, shot_net=None, stream_batch=0,
-                   out_size=None, out_pix_fmt='rgb24', out_interp='linear'):
+                   out_size=None, out_pix_fmt='rgb24', out_interp='linear', out_colour=None):
     """Saliency -> crop windows for one video.  Returns (VD, smart_crop_results) like the
     reference; VD['bbs'] holds one [x1,y1,x2,y2] per decoded frame.  A video dict without ``trans_inds`` takes the
     reference's video path: ``shot_net`` (transnetv1_handler.ShotTransNet) detects the shots inside the ingest.
@@ -560,7 +562,11 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         call is the three-argument one.  The pickle mode is defined as BGR crops: with 'nv12' it raises ValueError, as does
         an unknown format, before any work.  out_interp: the filter out_size is resampled with, 'linear' or 'lanczos'
         (render.render_video(interp=): PIL.Image.resize LANCZOS of the cropped window, bit for bit); another value raises
-        ValueError before any work.  The pickle mode is native-size BGR and ignores it.
+        ValueError before any work.  The pickle mode is native-size BGR and ignores it.  out_colour: the matrix and range
+        an 'nv12' output is encoded with (what ops.frame_colour takes); None means the source's own (a dict's colour=, BT.601
+        limited for rgb24 frames).  A colour other than BT.601 limited is handed to the writer as
+        fn(final_vid_fn, VD['fr'], size, pix_fmt='nv12', colour=dict(matrix=, range=)); the default keeps the call without it.
+        With out_pix_fmt='rgb24' a given out_colour raises ValueError, as does an unknown matrix or range, before any work.
     demo_fn (the five-panel demo) and copy_sound (ffmpeg) with a render raise NotImplementedError."""
     import torch
     sc_init_time()
@@ -573,9 +579,13 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         raise NotImplementedError('the five-panel demo video (cv2 drawing and text) is not rendered by this package; '
                                   'pass demo_fn=\'\'')
     render_pkl = render_writer = False
-    from .ops import check_interp, out_frame_shape
+    from .ops import DEFAULT_COLOUR, check_interp, frame_colour, out_frame_shape
     out_frame_shape(out_pix_fmt, *((2, 2) if out_size is None else (out_size[1], out_size[0])))     # unknown format, odd out_size: ValueError
     check_interp(out_interp)
+    if out_colour is not None:
+        out_colour = frame_colour(out_colour)
+        if out_pix_fmt == 'rgb24':
+            raise ValueError("out_colour=%r describes an nv12 output; out_pix_fmt is 'rgb24'" % (out_colour,))
     if save_vid and final_vid_fn:
         if copy_sound:
             raise NotImplementedError('copy_sound needs ffmpeg, which is not part of this package; pass copy_sound=False')
@@ -653,11 +663,15 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         else:
             size = tuple(int(v) for v in out_size) if out_size is not None else (int(VD['fbb_w']), int(VD['fbb_h']))
             out_frame_shape(out_pix_fmt, size[1], size[0])        # (an odd crop window as NV12: ValueError before the writer creates anything)
-            writer = _video_writer(final_vid_fn, VD['fr'], size) if out_pix_fmt == 'rgb24' else \
-                _video_writer(final_vid_fn, VD['fr'], size, pix_fmt=out_pix_fmt)
+            if out_pix_fmt == 'rgb24':
+                writer = _video_writer(final_vid_fn, VD['fr'], size)
+            else:
+                col = out_colour or FrameSource.of(video).colour or DEFAULT_COLOUR      # (None: the source's own)
+                writer = _video_writer(final_vid_fn, VD['fr'], size, pix_fmt=out_pix_fmt) if col == DEFAULT_COLOUR else \
+                    _video_writer(final_vid_fn, VD['fr'], size, pix_fmt=out_pix_fmt, colour=dict(matrix=col[0], range=col[1]))
             try:
                 render.render_video(video, VD, engine=engine, out_size=size, sink=lambda chunk: [writer.write(f) for f in chunk],
-                                    out_fmt=out_pix_fmt, interp=out_interp)
+                                    out_fmt=out_pix_fmt, interp=out_interp, out_colour=out_colour)
             finally:
                 writer.release()
         sc_register_time(t, 'render')
@@ -667,7 +681,8 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
 
 def feature_cache_key(video, CP, engine):
     """What a cached analysis depends on besides the video's name: the frame selection, the shots, the checkpoint, the pixel
-    format and -- for frames with a layout -- where their bytes lie (a dict without one keeps the key it always had)."""
+    format, -- for frames with a layout -- where their bytes lie and -- for nv12 frames that are not BT.601 limited -- their colour
+    (a dict without them keeps the key it always had)."""
     key = dict(skip=CP['skip'], read_batch=CP['read_batch'], max_input_d=CP['max_input_d'],
                frame_count=int(video['frame_count']), shots='net' if video.get('trans_inds') is None else
                [int(v) for v in video['trans_inds']], weights=getattr(engine, 'weights_id', None))
