@@ -94,7 +94,8 @@ int svc_abi_version(void);
 int svc_create(const void *weights_blob_host, size_t n_bytes, int device, SvcHandle **out);
 int svc_destroy(SvcHandle *h);
 
-/* frames[n][h][w][3] u8 RGB -> out[n][sh][sw][3] u8, OpenCV INTER_LINEAR semantics. */
+/* frames[n][h][w][3] u8 RGB -> out[n][sh][sw][3] u8, OpenCV INTER_LINEAR semantics.  Writes all n * sh * sw * 3 bytes of out and
+ * no other byte; out needs no alignment. */
 int svc_resize_frames_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
                          uint8_t *out, int sh, int sw, void *stream);
 
@@ -104,7 +105,9 @@ int svc_resize_frames_u8(SvcHandle *h, const uint8_t *frames, int n, int height,
  * flags: SVC_RENDER_BGR swaps R and B (smartVidCrop.py:1894).  Source reads are clamped into the frame (x1 to
  * [0, width - bw], y1 to [0, height - bh]; x2 / y2 are not read), so a bad box never reads outside `frames`.
  * SVC_E_INVALID: bw > width, bh > height, a size < 1, an unknown flag, or a resampled window / output row that needs
- * more than 64 KiB of LDS (2 * (3 bw + 32) + 3 ow + 16 bytes). */
+ * more than 64 KiB of LDS (2 * (3 bw + 32) + 3 ow + 16 bytes).
+ * Writes all n * oh * ow * 3 bytes of out and no other byte, wherever out begins: 16-byte stores are used where the address allows
+ * them, and the head and tail of an output row that share a 16-byte word with a neighbour are stored bytewise. */
 #define SVC_RENDER_BGR 1
 int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                         int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
@@ -120,7 +123,7 @@ int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, 
  * layout, flags, clamping of the window origins (which may be odd in x and y: the chroma index comes from frame coordinates)
  * and LDS limit.  They count under SVC_K_RESIZE / SVC_K_RENDER.  No counterpart in the reference (OpenCV decodes to RGB before
  * it sees a frame); the output of these two is RGB / BGR (NV12 output: the _to_nv12 entries below).  BT.709 or full-range
- * frames: svc_resize_frames_colour / svc_render_crops_colour below. */
+ * frames: svc_resize_frames_colour / svc_render_crops_colour below.  The bytes written are those of the _u8 entries: all of out, nothing else. */
 int svc_resize_frames_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width,
                            uint8_t *out, int sh, int sw, void *stream);
 int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
@@ -142,7 +145,8 @@ int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height
  * an odd bw or bh does not exist: pass an even output size); flags != 0 (SVC_RENDER_BGR has no meaning here); a resampled
  * window that needs more than 64 KiB of LDS per pair of output rows: 2 * (3 bw + 32) + 2 * 3 ow + 3 * (ow + 16) bytes, every
  * term rounded up to 16.  They count under SVC_K_RENDER.  No counterpart in the reference.  Another matrix or range for the
- * output (or the NV12 input): svc_render_crops_colour below. */
+ * output (or the NV12 input): svc_render_crops_colour below.  Writes all n * (oh * 3 / 2) * ow bytes of out and no other byte,
+ * wherever out begins. */
 int svc_render_crops_u8_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                 int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream);
 int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
@@ -170,7 +174,8 @@ int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, in
  * may be loaded (the 16-byte loads are aligned down and guarded by the range's end) and never reach a result.
  * The layout only decides which path runs: the 16-byte paths need `frames` (and, for the copy, `out`) 16-aligned, as for the
  * packed entries, and for NV12 an even frame_stride, chroma_offset and chroma_pitch (a U V pair on an odd address is read
- * by the byte paths).  They count under SVC_K_RESIZE / SVC_K_RENDER.  No counterpart in the reference. */
+ * by the byte paths).  What is written: all of the packed output, as by the packed entries, and nothing else.
+ * They count under SVC_K_RESIZE / SVC_K_RENDER.  No counterpart in the reference. */
 #define SVC_FMT_RGB24 0
 #define SVC_FMT_NV12  1
 typedef struct SvcFrameLayout {
@@ -284,20 +289,22 @@ int svc_render_crops_colour(SvcHandle *h, const uint8_t *frames, const SvcFrameL
  * anything is launched or the handle's plan changes, when that tile needs more than the CU's 160 KB (the message carries the frame
  * size and the byte count; svc_debug_net_plan reports the count as SVC_PLAN_LZ_LDS).  540x960 is the largest 16:9 frame that runs
  * (143 616 B); 720x1280 (226 272 B) and 1080x1920 are refused.  The other svc_saliency_* entries and svc_debug_run_node plan
- * the same way. */
+ * the same way.  Writes all n * height * width bytes of maps_nhw and no other byte of the caller's; maps_nhw needs no alignment. */
 int svc_saliency_u8(SvcHandle *h, const uint8_t *frames_nhwc, int n, int height, int width,
                     uint8_t *maps_nhw, void *stream);
 
 /* svc_saliency_u8 followed by svc_threshold_u8(t) in one pass: the last kernel of the network writes the thresholded map
  * (sc_threshold, smartVidCrop.py:1050-1059, applied to the u8 value as the reference applies it to the stored map).
- * Identical bytes; one launch less per chunk.  t in 0..255 (0 = svc_saliency_u8). */
+ * Identical bytes; one launch less per chunk.  t in 0..255 (0 = svc_saliency_u8).  Every byte of maps_nhw is written (a pixel below
+ * t as 0). */
 int svc_saliency_thresholded_u8(SvcHandle *h, const uint8_t *frames_nhwc, int n, int height, int width,
                                 uint8_t *maps_nhw, int t, void *stream);
 
 /* svc_saliency_thresholded_u8 (t in 1..255) that also ADDS, per frame, how many pixels of the UN-thresholded map sit at t - 1, t
  * and t + 1 to the caller's DEVICE rows census_n4[n][4] (uint32; column 3 unused; the caller zeroes them): svc_threshold_census
  * per frame, for callers whose passes mix the frames of several videos (retargetvid_amd/scheduler.py reports the regime
- * diagnostic per video from these rows).  census_n4 may be NULL (= svc_saliency_thresholded_u8).  No counterpart in the reference. */
+ * diagnostic per video from these rows).  census_n4 may be NULL (= svc_saliency_thresholded_u8).  No counterpart in the reference.
+ * maps_nhw is written in full; of census_n4 only columns 0..2 of the n rows are added to (column 3 is neither read nor written). */
 int svc_saliency_census_u8(SvcHandle *h, const uint8_t *frames_nhwc, int n, int height, int width,
                            uint8_t *maps_nhw, int t, uint32_t *census_n4, void *stream);
 
@@ -307,7 +314,9 @@ int svc_saliency_census_u8(SvcHandle *h, const uint8_t *frames_nhwc, int n, int 
  * profile_n[i][height + width] (uint32): the first `height` entries are the row maxima (max over x), the next `width` the
  * column maxima (max over y).  The caller zeroes the rows and reduces a video's rows with one maximum over i; counting, the
  * 0.45 cap and the scaling to the original frame (:880-913) are four numbers per video and stay on the host
- * (retargetvid_amd.smartVidCrop.sc_border_detection).  Maximum is order-independent: the rows do not depend on the schedule. */
+ * (retargetvid_amd.smartVidCrop.sc_border_detection).  Maximum is order-independent: the rows do not depend on the schedule.
+ * Only the n * (height + width) entries of profile_n are touched, each by an atomic maximum (an entry the map does not exceed
+ * keeps its value); the maps are only read.  Any width: a thread takes several columns. */
 int svc_border_profile_u8(SvcHandle *h, const uint8_t *maps_nhw, int n, int height, int width,
                           uint32_t *profile_n, void *stream);
 
@@ -315,11 +324,14 @@ int svc_border_profile_u8(SvcHandle *h, const uint8_t *maps_nhw, int n, int heig
  * network's last kernel, for callers that never hold the raw maps (retargetvid_amd/scheduler.py: the frames of several
  * videos share a pass and come out thresholded).  maps_nhw and census_n4 are byte for byte those of svc_saliency_census_u8.
  * t in 0..255 (0 = the plain map); census_n4 may be NULL (required NULL with t = 0); profile_n == NULL takes exactly the
- * launches of svc_saliency_census_u8 / svc_saliency_thresholded_u8. */
+ * launches of svc_saliency_census_u8 / svc_saliency_thresholded_u8.  Written: maps_nhw in full, columns 0..2 of census_n4, the
+ * n * (height + width) entries of profile_n (max-combined), nothing else. */
 int svc_saliency_profile_u8(SvcHandle *h, const uint8_t *frames_nhwc, int n, int height, int width,
                             uint8_t *maps_nhw, int t, uint32_t *census_n4, uint32_t *profile_n, void *stream);
 
-/* maps[i] = maps[i] < t ? 0 : maps[i], in place. */
+/* maps[i] = maps[i] < t ? 0 : maps[i], in place.  Only bytes of [maps, maps + n_bytes) are written, whatever the alignment of maps
+ * and of n_bytes (a 16-byte access is made only on a whole 16-aligned group inside the range, every other byte on its own);
+ * n_bytes = 0 touches nothing. */
 int svc_threshold_u8(SvcHandle *h, uint8_t *maps, size_t n_bytes, int t, void *stream);
 
 /* Cluster filter + cut blend + centre of every map, in place on thresholded maps.
@@ -331,7 +343,11 @@ int svc_threshold_u8(SvcHandle *h, uint8_t *maps, size_t n_bytes, int t, void *s
  *                   A chain that straddles two calls gives the same maps and centres as in one call
  *                   (tests/test_gpu_parity.py::test_blend_chain_carried_over_between_calls).
  * xy[n][2] receives (x, y) centres as float64 in saliency-map pixels, NaN = None (empty map); the entries of held
- * maps are unspecified.  stats may be NULL. */
+ * maps are unspecified.  stats may be NULL.
+ * What is written: the height * width bytes of every processed map (in place; with resize_factor > 1 the grown map is written
+ * back over it) and not one byte of a held map; the xy rows of the processed maps (the row of a held map is left alone or
+ * receives a centre of the map as it stands, depending on the settings: do not read it); the stats rows of the processed maps
+ * (the row of a held map is left alone).  Nothing outside maps_nhw[n][height][width], xy[n][2] and stats[n][4]. */
 #define SVC_BLEND_NEXT 1
 #define SVC_MAP_HELD 2
 int svc_cluster_center(SvcHandle *h, uint8_t *maps_nhw, int n, int height, int width,
@@ -343,7 +359,7 @@ int svc_cluster_center(SvcHandle *h, uint8_t *maps_nhw, int n, int height, int w
  * Returns the number of rounds (0 when every map is held) or a negative error. */
 int svc_debug_round_plan(const uint8_t *flags_host, int n, int32_t *round_out, int32_t *blend0_out);
 
-/* a[n][4], b[n][4] int32 boxes (x1,y1,x2,y2) -> out[n] float64 IoU, inclusive +1 pixel convention. */
+/* a[n][4], b[n][4] int32 boxes (x1,y1,x2,y2) -> out[n] float64 IoU, inclusive +1 pixel convention.  Writes out[0 .. n) and nothing else. */
 int svc_iou_i32(const int32_t *a, const int32_t *b, size_t n, double *out, void *stream);
 
 /* ---- host stages between the per-frame centres and the crop windows (csrc/svc_host.cpp) ----
@@ -477,6 +493,7 @@ int svc_debug_argsort_u32(SvcHandle *h, const uint32_t *keys_host, int n, int32_
  *   Dense(256) and Dense(2) transposed); n_floats is checked.
  * svc_transnet_predict: frames = DEVICE uint8 [n_windows][frames_per_window][27][48][3] (RGB, already 48x27),
  *   probs = DEVICE float32 [n_windows][frames_per_window] = P(transition) of every frame (softmax class 1).
+ *   All n_windows * frames_per_window floats of probs are written, and nothing else of the caller's.
  *   Windowing of a video (100-frame windows, stride 50, edge padding) is host logic: transnetv1_handler.predict_video. */
 int svc_transnet_load(SvcHandle *h, const float *blob_host, size_t n_floats);
 int svc_transnet_predict(SvcHandle *h, const uint8_t *frames, int n_windows, int frames_per_window, float *probs, void *stream);
@@ -485,7 +502,7 @@ int svc_transnet_predict(SvcHandle *h, const uint8_t *frames, int n_windows, int
  * svc_transnet_predict's; the others are UNSPECIFIED (left as they were on the split-bf16 pipes, computed on the fp32 pipe).
  * A cell's temporal reach is 8 frames (its largest dilation), so on the split-bf16 pipes every layer is computed only on the frames
  * the kept rows depend on: 50 / 66 / 82 / 98 of 100 frames in the last four cells = a fifth of the network's FLOPs less.
- * 0 <= row0 < row1 <= frames_per_window. */
+ * 0 <= row0 < row1 <= frames_per_window.  No store lands outside probs[n_windows][frames_per_window]. */
 int svc_transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_windows, int frames_per_window, int row0, int row1,
                               float *probs, void *stream);
 /* The handle's TransNet knobs as three int32: {matrix pipe: -1 = the handle's SVC_MX | 0 fp32 | 6 bf16x6 | 3 bf16x3, 16-position

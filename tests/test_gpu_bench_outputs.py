@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from poison import poisoned_outputs  # noqa: F401  (a fixture)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 

@@ -6,11 +6,12 @@ import numpy as np
 import pytest
 import torch
 
+from poison import poisoned_outputs  # noqa: F401  (a fixture)
 import nv12_ref
 from retargetvid_amd import ops, smartVidCrop as S
 from retargetvid_amd.frames import FrameSource
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
 
 N, H, W = 70, 36, 64
 SH, SW = 14, 25

@@ -11,7 +11,10 @@ import numpy as np
 import pytest
 import torch
 
+from poison import poisoned_outputs  # noqa: F401  (a fixture)
 from retargetvid_amd import _lib, smartVidCrop as S, synth, unisal_handler, weights
+
+pytestmark = pytest.mark.usefixtures('poisoned_outputs')
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

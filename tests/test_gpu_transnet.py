@@ -5,10 +5,11 @@ import numpy as np
 import pytest
 import torch
 
+from poison import poisoned_outputs  # noqa: F401  (a fixture)
 from oracle import cv_ref, transnet_ref as R
 from retargetvid_amd import ops, transnetv1_handler as Hd, weights
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
 TOL = 1e-4
 
 
