@@ -85,7 +85,8 @@ const char *svc_last_error(void);
  * 12 = SvcFrameLayout, svc_resize_frames_layout and svc_render_crops_layout exist (pitched frames).
  * (12, no bump) svc_render_crops_filter (SVC_FILTER_*) was added without one: no struct and no existing signature changed, and
  *     a binding finds the entry by its symbol (dlsym), not by the revision.  Likewise svc_debug_net_plan (SVC_PLAN_*), and
- *     SvcColour with svc_resize_frames_colour and svc_render_crops_colour (NV12 colour): a new struct and two new entries. */
+ *     SvcColour with svc_resize_frames_colour and svc_render_crops_colour (NV12 colour): a new struct and two new entries; and
+ *     svc_render_crops_to_layout (pitched output): one new entry that takes the existing SvcFrameLayout, unchanged, for the output. */
 #define SVC_ABI_VERSION 12
 int svc_abi_version(void);
 
@@ -280,6 +281,34 @@ int svc_resize_frames_colour(SvcHandle *h, const uint8_t *frames, const SvcFrame
 int svc_render_crops_colour(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *in_colour, int n,
                             int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt,
                             const SvcColour *out_colour, int oh, int ow, int filter, int flags, void *stream);
+
+/* Render into an encoder's surfaces: svc_render_crops_colour with a layout for the OUTPUT.  out_layout (required) says where the
+ * bytes of the n output frames of oh x ow lie, in the same struct and under the same rules as the frames' layout, applied to the
+ * oh x ow picture; its pix_fmt is the output format and takes the place of out_fmt.  Byte 0 of output pixel (y, x) of frame f is
+ *   RGB   out + f * frame_stride + y * pitch + 3 x
+ *   NV12  Y at out + f * frame_stride + y * pitch + x,  the U V pair of block (j, i) at ... + chroma_offset + j * chroma_pitch + 2 i
+ * The contract mirrors the input side: the picture bytes are bit for bit those svc_render_crops_colour writes into a packed
+ * output, and EVERY OTHER BYTE of the caller's buffer is left untouched.  What is written is the bytes of every picture row of
+ * every plane of the n frames (3 ow bytes per RGB row; ow per luma and per chroma row), all inside [out, out + (n - 1) *
+ * frame_stride + extent) -- not the row padding, not the gap between the luma and the chroma plane, not the gap between frames,
+ * nothing behind the last frame's extent (its trailing gap need not be mapped).
+ * Rules for out_layout, checked before any device work (SVC_E_INVALID, svc_last_error() names the side: "out_layout: ..."): it
+ * is not NULL; struct_size is this header's; pix_fmt is one of SVC_FMT_*; every value is non-negative; pitch >= 3 ow | ow;
+ * RGB: chroma_offset = chroma_pitch = 0; NV12: chroma_pitch >= ow and chroma_offset >= pitch * (oh - 1) + ow; frame_stride >=
+ * extent; (n - 1) * frame_stride + extent <= PTRDIFF_MAX.  No alignment is demanded.  Everything else is
+ * svc_render_crops_colour's: the frames' layout, window clamping, filters, flags (by the output format), LDS limits, the read
+ * range, the colour rules (out_colour is refused for an RGB out_layout).
+ * The layout decides which path runs, never whether the call is legal.  The resampling paths store rows through aligned
+ * 16-byte words with bytewise heads and tails at any phase.  The copy's 16-byte path to RGB needs bw >= 16 and out, frame_stride
+ * and pitch multiples of 16 (every row start aligned; a row's last group stores exactly its bytes); to NV12 it needs bw % 8 == 0,
+ * bw >= 16 and out, frame_stride, pitch, chroma_offset and chroma_pitch multiples of 8; both need the 16-aligned frames of the
+ * packed entries.  Anything else -- an odd pitch -- takes the byte path.  An out_layout that holds the packed values (pitch 3 ow |
+ * ow, chroma_offset ow * oh, chroma_pitch ow, frame_stride the packed frame's bytes) runs the packed kernels.
+ * Counts under SVC_K_RENDER.  No counterpart in the reference. */
+int svc_render_crops_to_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *in_colour,
+                               int n, int height, int width, const int32_t *boxes, int bw, int bh,
+                               uint8_t *out, const SvcFrameLayout *out_layout, const SvcColour *out_colour,
+                               int oh, int ow, int filter, int flags, void *stream);
 
 /* frames_nhwc[n][h][w][3] u8 RGB (saliency size, e.g. 140x250) -> maps_nhw[n][h][w] u8.
  * Frame-major output; the reference's [h][w][n] view is a transpose done by the

@@ -1,12 +1,15 @@
 // svc_frames.hip — frame I/O for gfx950: the ingest down-scale and the renderer, from RGB and NV12 frames (packed, or in a
 // decoder's layout: Packed / Pitched below), the renderer to packed RGB / BGR and to NV12.  Every kernel is written once: it
-// takes its pixels from a source (SrcRgb<Lay>, SrcNv12<Lay>) and the render kernels hand theirs to a sink (DstRgb<BGR>, DstNv12); the INTER_LINEAR rule is svc_cvlinear.h's.  The one
-// pair that is two bodies is the copy path's vector kernel, whose decomposition of the output is the sink's own.
+// takes its pixels from a source (SrcRgb<Lay>, SrcNv12<Lay>) and the render kernels hand theirs to a sink (DstRgb<BGR, OLay>,
+// DstNv12<OLay>: packed, or in an encoder's layout, the same two policies on the output side); the INTER_LINEAR rule is
+// svc_cvlinear.h's.  The one set that is several bodies is the copy path's vector kernel, whose decomposition of the output is the
+// sink's own (and, to RGB, the output layout's: a packed output is one run of pixels, a pitched one is rows).
 //
 // Reference semantics restated per kernel (paths relative to the reference tree):
 //   k_cv_resize      cv2.resize(INTER_LINEAR)         smartVidCrop.py:333-335, :633-635
 //   k_render_*       frame[by1:by2, bx1:bx2, :] (+ cv2.resize INTER_LINEAR, + RGB2BGR)  smartVidCrop.py:1801-1921
 //     k_render_copy_to_rgb, k_render_copy_to_nv12    the copy's vector kernels, one per sink
+//     k_render_copy_to_rgb_rows                      the first of them for a pitched output (groups per output row)
 //     k_render_copy_px<Src, Dst>                     the copy for everything they leave
 //     k_render_resize<Src, Dst>                      the resampled crop
 //     k_render_lanczos<Src, Dst>                     the crop resampled as PIL.Image.resize(LANCZOS) does it (no counterpart: svc_render_crops_filter)
@@ -14,6 +17,7 @@
 //   DstNv12          the same crops written as NV12, the forward transform fused in (no counterpart: the reference hands RGB to its writer)
 //   Nv12Dec, Nv12Enc the colour (matrix x range: SvcColour) of those two, run-time kernel arguments
 #include <algorithm>
+#include <type_traits>
 
 #include "svc_cvlinear.h"
 #include "svc_internal.h"
@@ -75,17 +79,21 @@ __device__ __forceinline__ void ld24(const uint8_t *a, const uint8_t *end, uint6
 }
 
 // --------------------------------------------------------------------------------------
-// Frame layouts: where the bytes of a source frame lie (SvcFrameLayout, include/svc.h).  A layout is a compile-time policy of
-// the pixel source and travels as the kernels' last argument.  Packed is an empty struct whose offsets are the expressions
+// Frame layouts: where the bytes of a source frame -- or of an output frame -- lie (SvcFrameLayout, include/svc.h).  A layout is
+// a compile-time policy of the pixel source (Lay, kernel argument L) and of the pixel sink (OLay, kernel argument O) and travels
+// behind the kernels' other arguments.  Packed is an empty struct whose offsets are the expressions
 // in w that these kernels have always used, so the packed instances are the kernels they were; Pitched carries the four
 // strides.  T: the integer type the caller's expression is formed in (size_t for byte loads, ptrdiff_t where x may be < 0).
 //   frame<Src>   bytes from frame f to frame f + 1
 //   rgb          offset of byte 0 of pixel (y, x) of an RGB frame
 //   luma, chroma offsets of Y[y][x] and of the U V pair of pixel (y, x) of an NV12 frame
+//   rgb_row      offset of row y of RGB frame f from the buffer's start (the RGB sink's row address: Packed keeps the one
+//                expression in ow the sink has always formed it with)
 // --------------------------------------------------------------------------------------
 struct Packed {
     template <class Src> __host__ __device__ __forceinline__ size_t frame(int h, int w) const { return Src::frame_bytes(h, w); }
     template <class T> __device__ __forceinline__ T rgb(int w, int y, int x) const { return ((T)y * w + x) * 3; }
+    template <class T> __device__ __forceinline__ T rgb_row(int f, int h, int w, int y) const { return ((T)f * h + y) * w * 3; }
     template <class T> __device__ __forceinline__ T luma(int w, int y, int x) const { return (T)y * w + x; }
     template <class T> __device__ __forceinline__ T chroma(int h, int w, int y, int x) const { return (T)(h + (y >> 1)) * w + (x & ~1); }
 };
@@ -93,6 +101,7 @@ struct Pitched {
     long long frame_stride, pitch, chroma_offset, chroma_pitch;
     template <class Src> __host__ __device__ __forceinline__ size_t frame(int, int) const { return (size_t)frame_stride; }
     template <class T> __device__ __forceinline__ T rgb(int, int y, int x) const { return (T)y * (T)pitch + x * 3; }
+    template <class T> __device__ __forceinline__ T rgb_row(int f, int, int, int y) const { return (T)f * (T)frame_stride + (T)y * (T)pitch; }
     template <class T> __device__ __forceinline__ T luma(int, int y, int x) const { return (T)y * (T)pitch + x; }
     template <class T> __device__ __forceinline__ T chroma(int, int, int y, int x) const {
         return (T)chroma_offset + (T)(y >> 1) * (T)chroma_pitch + (x & ~1);
@@ -450,7 +459,7 @@ template <class Src, bool BGR>
 __global__ __launch_bounds__(256) void k_render_copy_to_rgb(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                             const int32_t *__restrict__ boxes, int n, int height, int width, int bh,
                                                             int bw, const uint8_t *in_end, const typename Src::lay L, const typename Src::colour KI,
-                                                            const NoColour) {
+                                                            const NoColour, const Packed) {
     const long long total_px = (long long)n * bh * bw, p0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 16;
     if (p0 >= total_px) return;
     const size_t fstride = L.template frame<Src>(height, width);
@@ -483,6 +492,41 @@ __global__ __launch_bounds__(256) void k_render_copy_to_rgb(const uint8_t *__res
         d4[2] = make_uint4(o[8], o[9], o[10], o[11]);
     } else {
         const int nb = (int)(total_px - p0) * 3;
+#pragma unroll
+        for (int i = 0; i < 48; ++i)
+            if (i < nb) dst[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
+    }
+}
+
+// The same to a pitched RGB output, whose rows are not one run: thread t owns pixels [16 g, 16 g + 16) of ONE output row (G =
+// ceil(bw / 16) groups per row), one run through Src::px16 (the pixels right of the window are loaded -- inside the buffer or
+// zero past its end, as for the NV12 kernel below -- and dropped).  Every row starts on 16 bytes (the launcher: out, frame_stride
+// and pitch are multiples of 16), so a whole group is three aligned 16-byte stores; the last group of a row holds k = bw - 16 g
+// < 16 pixels and stores exactly its 3 k bytes: the padding behind the row is never written.
+template <class Src, bool BGR>
+__global__ __launch_bounds__(256) void k_render_copy_to_rgb_rows(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                                 const int32_t *__restrict__ boxes, int n, int height, int width, int bh,
+                                                                 int bw, const uint8_t *in_end, const typename Src::lay L,
+                                                                 const typename Src::colour KI, const NoColour, const Pitched O) {
+    const int G = (bw + 15) >> 4;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)n * bh * G) return;
+    const long long R = t / G;
+    const int g = (int)(t - R * G), f = (int)(R / bh), r = (int)(R - (long long)f * bh);
+    int x0, y0;
+    render_origin(boxes, f, height, width, bh, bw, x0, y0);
+    uint32_t o[12];
+    Src::template px16<BGR>(in + f * L.template frame<Src>(height, width), L, KI, height, width, y0 + r, x0 + 16 * g, in_end, o);
+    Src::template order16<BGR>(o);
+    uint8_t *dst = out + (size_t)f * (size_t)O.frame_stride + O.template rgb<size_t>(bw, r, 16 * g);
+    const int k = bw - 16 * g;
+    if (k >= 16) {
+        uint4 *d4 = (uint4 *)dst;
+        d4[0] = make_uint4(o[0], o[1], o[2], o[3]);
+        d4[1] = make_uint4(o[4], o[5], o[6], o[7]);
+        d4[2] = make_uint4(o[8], o[9], o[10], o[11]);
+    } else {
+        const int nb = 3 * k;
 #pragma unroll
         for (int i = 0; i < 48; ++i)
             if (i < nb) dst[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
@@ -538,15 +582,17 @@ __device__ __forceinline__ void st16_a8(uint8_t *d, const uint32_t (&v)[4], bool
     else { *(uint2 *)d = make_uint2(v[0], v[1]); *(uint2 *)(d + 8) = make_uint2(v[2], v[3]); }
 }
 
-// To NV12, bw % 8 == 0, bw >= 16 (every output row, luma or chroma, then starts on 8 bytes).
+template <class OLay> struct DstNv12;
+// To NV12, bw % 8 == 0, bw >= 16, every output row, luma or chroma, starting on 8 bytes (packed: out 16-aligned and that width;
+// pitched: out, frame_stride, pitch, chroma_offset and chroma_pitch multiples of 8 -- DstNv12::vec_ok).
 // Thread t owns the strip of window rows 2j, 2j + 1 by pixels [16 g, 16 g + 16) (the last strip of a row is 8 wide when
 // bw % 16 == 8): two runs through Src::px16 (odd x, odd y and the frame's end are its business; the pixels past the window
 // are converted and dropped), 32 luma bytes and the strip's 8 interleaved chroma pairs, each row of it as one aligned store.
-template <class Src>
+template <class Src, class OLay>
 __global__ __launch_bounds__(256) void k_render_copy_to_nv12(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                              const int32_t *__restrict__ boxes, int n, int height, int width, int bh,
                                                              int bw, const uint8_t *in_end, const typename Src::lay L, const typename Src::colour KI,
-                                                             const Nv12Enc KO) {
+                                                             const Nv12Enc KO, const OLay O) {
     const int G = (bw + 15) >> 4, hb = bh >> 1;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long long)n * hb * G) return;
@@ -566,11 +612,11 @@ __global__ __launch_bounds__(256) void k_render_copy_to_nv12(const uint8_t *__re
         yb[i >> 1] |= (rgb_luma(KO, p2) | (rgb_luma(KO, p3) << 8)) << (16 * (i & 1));
         uv[i >> 1] |= rgb_chroma(KO, p0, p1, p2, p3) << (16 * (i & 1));
     }
-    uint8_t *o = out + (size_t)f * (bh + hb) * bw + 16 * g;
+    uint8_t *o = out + f * O.template frame<DstNv12<OLay>>(bh, bw);
     const bool half = 16 * g + 16 > bw;
-    st16_a8(o + (size_t)(2 * j) * bw, ya, half);
-    st16_a8(o + (size_t)(2 * j + 1) * bw, yb, half);
-    st16_a8(o + (size_t)(bh + j) * bw, uv, half);
+    st16_a8(o + O.template luma<size_t>(bw, 2 * j, 16 * g), ya, half);
+    st16_a8(o + O.template luma<size_t>(bw, 2 * j + 1, 16 * g), yb, half);
+    st16_a8(o + O.template chroma<size_t>(bh, bw, 2 * j, 16 * g), uv, half);
 }
 
 // --------------------------------------------------------------------------------------
@@ -578,20 +624,24 @@ __global__ __launch_bounds__(256) void k_render_copy_to_nv12(const uint8_t *__re
 // a sink stores it.
 //   size_ok, size_rule       the pictures the format can hold, and the words the error text says it with
 //   flags_ok, flags_rule     the same for the SVC_RENDER_* flags
-//   frame_bytes              bytes of one frame
+//   frame_bytes              bytes of one packed frame
+//   olay                     the output layout OLay (`O`: the kernel's output-layout argument): every address of the output is the
+//                            frame's start out + f * O.frame plus O.rgb / O.luma / O.chroma of the PICTURE's row and column
+//                            (the RGB sink's row start: O.rgb_row, the same sum)
 //   rows                     B: a thread of the per-pixel copy owns a B x B block of the crop, a resize workgroup B output rows
 //   colour, col              the colour constants the sink converts with (a kernel argument, K below; NoColour for RGB) and
 //                            the sink's part of a Colours pair
 //   put_block                block (j, i) of the frame at `fo` from its pixels p[B * B] (row-major, as Src::px gives them)
-//   vec_ok, vec_threads,     the copy path's vector kernel: the window widths it takes when both buffers are 16-aligned, its
-//   vec_copy<Src>            threads, the kernel
+//   vec_ok, vec_threads,     the copy path's vector kernel: the window widths, output addresses and layouts it takes (the frames
+//   vec_copy<Src>            16-aligned besides), its threads, the kernel
 //   lds_bytes                LDS of the resize kernel behind the two staged window rows
 //   out_rows, dst_rows       the output rows that rows B j .. B j + B - 1 of the crop become (frame fy of `out`): how many, where
 //   rgb_row                  where in that LDS row r of the workgroup's B rows is resampled to
 //   rows_out                 the B resampled rows -> the output rows, by the whole workgroup (called behind a barrier)
 // --------------------------------------------------------------------------------------
-template <bool BGR>
-struct DstRgb {                                 // u8 [oh][ow][3]
+template <bool BGR, class OLay = Packed>
+struct DstRgb {                                 // u8 [oh][ow][3]; Pitched: rows `pitch` bytes apart
+    typedef OLay olay;
     typedef NoColour colour;
     static colour col(const Colours &) { return NoColour(); }
     static constexpr bool bgr = BGR;
@@ -601,22 +651,31 @@ struct DstRgb {                                 // u8 [oh][ow][3]
     static bool flags_ok(int flags) { return !(flags & ~SVC_RENDER_BGR); }
     static const char *flags_rule() { return "flags has bits other than SVC_RENDER_BGR"; }
     __host__ __device__ static size_t frame_bytes(int oh, int ow) { return (size_t)oh * ow * 3; }
-    static bool vec_ok(int bw) { return bw >= 16; }
-    static long long vec_threads(int n, int bh, int bw) { return ((long long)n * bh * bw + 15) / 16; }
+    // Packed: one run of pixels from a 16-aligned start; Pitched: every row starts on 16 bytes
+    static bool vec_ok(const Packed &, const uint8_t *out, int bw) { return bw >= 16 && ((uintptr_t)out & 15) == 0; }
+    static bool vec_ok(const Pitched &O, const uint8_t *out, int bw) {
+        return bw >= 16 && (((uintptr_t)out | (uintptr_t)O.frame_stride | (uintptr_t)O.pitch) & 15) == 0;
+    }
+    static long long vec_threads(int n, int bh, int bw) {
+        return std::is_same<OLay, Packed>::value ? ((long long)n * bh * bw + 15) / 16 : (long long)n * bh * ((bw + 15) / 16);
+    }
     template <class Src>
-    static auto vec_copy() { return k_render_copy_to_rgb<Src, BGR>; }
+    static auto vec_copy() {
+        if constexpr (std::is_same<OLay, Packed>::value) return k_render_copy_to_rgb<Src, BGR>;
+        else return k_render_copy_to_rgb_rows<Src, BGR>;
+    }
     static size_t lds_bytes(int ow) { return (size_t)ow * 3 + 16; }
 
-    __device__ __forceinline__ static void put_block(const colour &, uint8_t *fo, int oh, int ow, int j, int i, const uint32_t (&p)[1]) {
-        uint8_t *d = fo + ((size_t)j * ow + i) * 3;
+    __device__ __forceinline__ static void put_block(const colour &, const OLay &O, uint8_t *fo, int oh, int ow, int j, int i, const uint32_t (&p)[1]) {
+        uint8_t *d = fo + O.template rgb<size_t>(ow, j, i);
         d[0] = (uint8_t)p[0];
         d[1] = (uint8_t)(p[0] >> 8);
         d[2] = (uint8_t)(p[0] >> 16);
     }
     // the row is resampled at the output row's own 16-byte phase and stored as it is
     static constexpr int out_rows = 1;
-    __device__ __forceinline__ static void dst_rows(uint8_t *out, int fy, int oh, int ow, int j, uint8_t *(&dst)[1]) {
-        dst[0] = out + ((size_t)fy * oh + j) * ow * 3;
+    __device__ __forceinline__ static void dst_rows(const OLay &O, uint8_t *out, int fy, int oh, int ow, int j, uint8_t *(&dst)[1]) {
+        dst[0] = out + O.template rgb_row<size_t>(fy, oh, ow, j);
     }
     __device__ __forceinline__ static uint8_t *rgb_row(uint8_t *lds, uint8_t *const (&dst)[1], int ow, int r) {
         return lds + (int)((uintptr_t)dst[0] & 15);
@@ -626,7 +685,9 @@ struct DstRgb {                                 // u8 [oh][ow][3]
     }
 };
 
-struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the formula above
+template <class OLay = Packed>
+struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the formula above; Pitched: as SrcNv12's
+    typedef OLay olay;
     typedef Nv12Enc colour;
     static colour col(const Colours &c) { return c.enc; }
     static constexpr bool bgr = false;
@@ -637,18 +698,24 @@ struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the form
     }
     static bool flags_ok(int flags) { return flags == 0; }
     static const char *flags_rule() { return "flags must be 0 (SVC_RENDER_BGR has no meaning for an NV12 output)"; }
-    __host__ __device__ static size_t frame_bytes(int oh, int ow) { return (size_t)(oh + oh / 2) * ow; }
-    static bool vec_ok(int bw) { return bw >= 16 && bw % 8 == 0; }
+    __host__ __device__ static size_t frame_bytes(int oh, int ow) { return (size_t)(oh + (oh >> 1)) * ow; }
+    // st16_a8 needs every luma and chroma row start on 8 bytes (the packed path keeps the 16-aligned out it has always asked for)
+    static bool vec_ok(const Packed &, const uint8_t *out, int bw) { return bw >= 16 && bw % 8 == 0 && ((uintptr_t)out & 15) == 0; }
+    static bool vec_ok(const Pitched &O, const uint8_t *out, int bw) {
+        return bw >= 16 && bw % 8 == 0 &&
+               (((uintptr_t)out | (uintptr_t)O.frame_stride | (uintptr_t)O.pitch | (uintptr_t)O.chroma_offset | (uintptr_t)O.chroma_pitch) & 7) == 0;
+    }
     static long long vec_threads(int n, int bh, int bw) { return (long long)n * (bh / 2) * ((bw + 15) / 16); }
     template <class Src>
-    static auto vec_copy() { return k_render_copy_to_nv12<Src>; }
+    static auto vec_copy() { return k_render_copy_to_nv12<Src, OLay>; }
     // two RGB rows of rgb_cap bytes, then three output rows (two of luma, one of chroma) of row_cap bytes
     __host__ __device__ static int rgb_cap(int ow) { return (ow * 3 + 15) / 16 * 16; }
     __host__ __device__ static int row_cap(int ow) { return (ow + 15) / 16 * 16 + 16; }
     static size_t lds_bytes(int ow) { return 2 * (size_t)rgb_cap(ow) + 3 * (size_t)row_cap(ow); }
 
-    __device__ __forceinline__ static void put_block(const colour &K, uint8_t *fo, int oh, int ow, int j, int i, const uint32_t (&p)[4]) {
-        uint8_t *d0 = fo + (size_t)(2 * j) * ow + 2 * i, *d1 = d0 + ow, *dc = fo + (size_t)(oh + j) * ow + 2 * i;
+    __device__ __forceinline__ static void put_block(const colour &K, const OLay &O, uint8_t *fo, int oh, int ow, int j, int i, const uint32_t (&p)[4]) {
+        uint8_t *d0 = fo + O.template luma<size_t>(ow, 2 * j, 2 * i), *d1 = fo + O.template luma<size_t>(ow, 2 * j + 1, 2 * i);
+        uint8_t *dc = fo + O.template chroma<size_t>(oh, ow, 2 * j, 2 * i);
         const uint32_t c = rgb_chroma(K, p[0], p[1], p[2], p[3]);
         d0[0] = (uint8_t)rgb_luma(K, p[0]);
         d0[1] = (uint8_t)rgb_luma(K, p[1]);
@@ -658,11 +725,11 @@ struct DstNv12 {                                // u8 [oh * 3 / 2][ow], the form
         dc[1] = (uint8_t)(c >> 8);
     }
     static constexpr int out_rows = 3;
-    __device__ __forceinline__ static void dst_rows(uint8_t *out, int fy, int oh, int ow, int j, uint8_t *(&dst)[3]) {
-        uint8_t *fo = out + (size_t)fy * (oh + (oh >> 1)) * ow;
-        dst[0] = fo + (size_t)(2 * j) * ow;
-        dst[1] = fo + (size_t)(2 * j + 1) * ow;
-        dst[2] = fo + (size_t)(oh + j) * ow;
+    __device__ __forceinline__ static void dst_rows(const OLay &O, uint8_t *out, int fy, int oh, int ow, int j, uint8_t *(&dst)[3]) {
+        uint8_t *fo = out + fy * O.template frame<DstNv12>(oh, ow);
+        dst[0] = fo + O.template luma<size_t>(ow, 2 * j, 0);
+        dst[1] = fo + O.template luma<size_t>(ow, 2 * j + 1, 0);
+        dst[2] = fo + O.template chroma<size_t>(oh, ow, 2 * j, 0);
     }
     __device__ __forceinline__ static uint8_t *rgb_row(uint8_t *lds, uint8_t *const (&dst)[3], int ow, int r) {
         return lds + r * rgb_cap(ow);
@@ -698,7 +765,7 @@ template <class Src, class Dst>
 __global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                         const int32_t *__restrict__ boxes, int height, int width, int bh, int bw,
                                                         long long total, const typename Src::lay L, const typename Src::colour KI,
-                                                        const typename Dst::colour KO) {
+                                                        const typename Dst::colour KO, const typename Dst::olay O) {
     constexpr int B = Dst::rows;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
@@ -711,7 +778,7 @@ __global__ __launch_bounds__(256) void k_render_copy_px(const uint8_t *__restric
     uint32_t p[B * B];
 #pragma unroll
     for (int k = 0; k < B * B; ++k) p[k] = Src::template px<Dst::bgr>(fr, L, KI, height, width, y0 + B * j + k / B, x0 + B * i + k % B);
-    Dst::put_block(KO, out + f * Dst::frame_bytes(bh, bw), bh, bw, j, i, p);
+    Dst::put_block(KO, O, out + f * O.template frame<Dst>(bh, bw), bh, bw, j, i, p);
 }
 
 // Resize path: k_cv_resize's arithmetic on a window of the full frame.  One workgroup = B output rows of one frame (B =
@@ -725,7 +792,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_re
                                                        const int *__restrict__ tab, const int32_t *__restrict__ boxes, int f0,
                                                        int height, int width, int bh, int bw, int oh, int ow, int span_cap,
                                                        const uint8_t *in_end, int vec, const typename Src::lay L, const typename Src::colour KI,
-                                                       const typename Dst::colour KO) {
+                                                       const typename Dst::colour KO, const typename Dst::olay O) {
     extern __shared__ __align__(16) uint8_t sm_rr[];
     const CvLinear T(tab, oh, ow);
     const int j = blockIdx.x, f = f0 + blockIdx.y;
@@ -740,7 +807,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_re
 #pragma unroll
         for (int k = 0; k < 2; ++k)
             sh[k] = Src::stage_row(fr, L, KI, height, width, y0 + ry[k], x0, bw, sm_rr + k * span_cap, span_cap, in_end, vec);
-        if (!r) Dst::dst_rows(out, blockIdx.y, oh, ow, j, dst);
+        if (!r) Dst::dst_rows(O, out, blockIdx.y, oh, ow, j, dst);
         uint8_t *orow = Dst::rgb_row(lds, dst, ow, r);
         __syncthreads();
         const uint8_t *r0 = sm_rr + sh[0], *r1 = sm_rr + span_cap + sh[1];
@@ -780,7 +847,8 @@ static int render_args_check(const char *name, SvcHandle *h, const uint8_t *fram
 
 template <class Src, class Dst>
 static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, const Colours &C, int n,
-                        int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+                        int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, const typename Dst::olay &O, int oh, int ow,
+                        int flags, void *stream) {
     int rc = render_args_check<Src, Dst>(name, h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags);
     if (rc) return rc;
     const int span_cap = (bw * 3 + 32 + 15) / 16 * 16;
@@ -795,7 +863,7 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, c
     SVC_HIP(hipSetDevice(h->device));
     // the end of the last frame's last plane row: what the 16-byte loads are guarded by (Packed: frames + n * frame_bytes)
     const uint8_t *in_end = frames + (size_t)(n - 1) * L.template frame<Src>(height, width) + Src::extent(L, height, width);
-    const bool aligned_in = ((uintptr_t)frames & 15) == 0 && Src::vec_ok(L), aligned_out = ((uintptr_t)out & 15) == 0;
+    const bool aligned_in = ((uintptr_t)frames & 15) == 0 && Src::vec_ok(L);
     hipStream_t s = (hipStream_t)stream;
     const int *tab = nullptr;
     if (!copy) {
@@ -804,20 +872,20 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, c
     }
     ProfScope ps(h, SVC_K_RENDER, s);
     if (copy) {
-        if (Dst::vec_ok(bw) && aligned_in && aligned_out) {
+        if (aligned_in && Dst::vec_ok(O, out, bw)) {               // (the layout decides which path runs, never whether the call is legal)
             const unsigned grid = (unsigned)((Dst::vec_threads(n, bh, bw) + 255) / 256);
-            Dst::template vec_copy<Src>()<<<grid, 256, 0, s>>>(frames, out, boxes, n, height, width, bh, bw, in_end, L, Src::col(C), Dst::col(C));
+            Dst::template vec_copy<Src>()<<<grid, 256, 0, s>>>(frames, out, boxes, n, height, width, bh, bw, in_end, L, Src::col(C), Dst::col(C), O);
         } else {
             const long long total = (long long)n * (bh / Dst::rows) * (bw / Dst::rows);
-            k_render_copy_px<Src, Dst><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total, L, Src::col(C), Dst::col(C));
+            k_render_copy_px<Src, Dst><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total, L, Src::col(C), Dst::col(C), O);
         }
         SVC_CHECK_LAUNCH();
         return SVC_OK;
     }
     for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
         const dim3 grid((unsigned)(oh / Dst::rows), (unsigned)std::min(n - f0, 65535));
-        k_render_resize<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * Dst::frame_bytes(oh, ow), tab, boxes, f0, height, width,
-                                                         bh, bw, oh, ow, span_cap, in_end, aligned_in, L, Src::col(C), Dst::col(C));
+        k_render_resize<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * O.template frame<Dst>(oh, ow), tab, boxes, f0, height, width,
+                                                         bh, bw, oh, ow, span_cap, in_end, aligned_in, L, Src::col(C), Dst::col(C), O);
         SVC_CHECK_LAUNCH();
     }
     return SVC_OK;
@@ -850,7 +918,7 @@ __global__ __launch_bounds__(256) void k_render_lanczos(const uint8_t *__restric
                                                         const int32_t *__restrict__ boxes, int f0, int height, int width, int bh,
                                                         int bw, int oh, int ow, int B, int span_cap, int tile_cap,
                                                         const uint8_t *in_end, int vec, const typename Src::lay L, const typename Src::colour KI,
-                                                        const typename Dst::colour KO) {
+                                                        const typename Dst::colour KO, const typename Dst::olay O) {
     extern __shared__ __align__(16) uint8_t sm_lz[];
     const int tw = (ow * 3 + 15) / 16 * 16;
     uint8_t *tile = sm_lz + LZ_STAGE * span_cap, *lds = tile + tile_cap * tw;
@@ -901,7 +969,7 @@ __global__ __launch_bounds__(256) void k_render_lanczos(const uint8_t *__restric
     uint8_t *dst[Dst::out_rows];
     for (int oy = oy0; oy < oy1; oy += Dst::rows) {
         if (oy > oy0) __syncthreads();                          // the sink has stored the rows before
-        Dst::dst_rows(out, blockIdx.y, oh, ow, oy / Dst::rows, dst);
+        Dst::dst_rows(O, out, blockIdx.y, oh, ow, oy / Dst::rows, dst);
 #pragma unroll
         for (int r = 0; r < Dst::rows; ++r) {
             const int ymin = vb[2 * (oy + r)], cnt = vb[2 * (oy + r) + 1];
@@ -991,11 +1059,12 @@ static int lz_tile_rows(const std::vector<int> &vb, int oh, int B) {
 // (include/svc.h states the formula).
 template <class Src, class Dst>
 static int render_crops_lanczos(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, const Colours &C,
-                                int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
+                                int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, const typename Dst::olay &O,
+                                int oh, int ow, int flags, void *stream) {
     int rc = render_args_check<Src, Dst>(name, h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags);
     if (rc) return rc;
     if (oh == bh && ow == bw)                               // both passes skipped: the exact copy
-        return render_crops<Src, Dst>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+        return render_crops<Src, Dst>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
     ResampleTab *ht = nullptr, *vt = nullptr;
     if ((rc = lz_tab(name, h, bw, ow, &ht)) || (rc = lz_tab(name, h, bh, oh, &vt))) return rc;
     const int span_cap = (bw * 3 + 32 + 15) / 16 * 16, tw = (ow * 3 + 15) / 16 * 16;
@@ -1021,104 +1090,122 @@ static int render_crops_lanczos(const char *name, SvcHandle *h, const uint8_t *f
     ProfScope ps(h, SVC_K_RENDER, s);
     for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
         const dim3 grid((unsigned)((oh + B - 1) / B), (unsigned)std::min(n - f0, 65535));
-        k_render_lanczos<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * Dst::frame_bytes(oh, ow), (const int *)ht->bounds.p,
+        k_render_lanczos<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * O.template frame<Dst>(oh, ow), (const int *)ht->bounds.p,
                                                           (const int *)ht->coeff.p, ht->ksize, (const int *)vt->bounds.p,
                                                           (const int *)vt->coeff.p, vt->ksize, boxes, f0, height, width, bh, bw, oh, ow,
-                                                          B, span_cap, tile_cap, in_end, vec, L, Src::col(C), Dst::col(C));
+                                                          B, span_cap, tile_cap, in_end, vec, L, Src::col(C), Dst::col(C), O);
         SVC_CHECK_LAUNCH();
     }
     return SVC_OK;
 }
 
-// the four source x sink pairings of one layout (flags picks the RGB sink's channel order)
-template <class Lay>
+// the source x sink pairings of one source layout and one output layout (flags picks the RGB sink's channel order), per filter
+template <class Lay, class OLay>
 static int render_crops_fmt(const char *name, int pix_fmt, bool to_nv12, SvcHandle *h, const uint8_t *frames, const Lay &L, const Colours &C, int n,
-                            int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags,
+                            int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, const OLay &O, int oh, int ow, int flags,
                             void *stream) {
     if (pix_fmt == SVC_FMT_NV12) {
-        if (to_nv12) return render_crops<SrcNv12<Lay>, DstNv12>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
-        return (flags & SVC_RENDER_BGR ? render_crops<SrcNv12<Lay>, DstRgb<true>> : render_crops<SrcNv12<Lay>, DstRgb<false>>)(
-            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+        if (to_nv12) return render_crops<SrcNv12<Lay>, DstNv12<OLay>>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+        return (flags & SVC_RENDER_BGR ? render_crops<SrcNv12<Lay>, DstRgb<true, OLay>> : render_crops<SrcNv12<Lay>, DstRgb<false, OLay>>)(
+            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
     }
-    if (to_nv12) return render_crops<SrcRgb<Lay>, DstNv12>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
-    return (flags & SVC_RENDER_BGR ? render_crops<SrcRgb<Lay>, DstRgb<true>> : render_crops<SrcRgb<Lay>, DstRgb<false>>)(
-        name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    if (to_nv12) return render_crops<SrcRgb<Lay>, DstNv12<OLay>>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+    return (flags & SVC_RENDER_BGR ? render_crops<SrcRgb<Lay>, DstRgb<true, OLay>> : render_crops<SrcRgb<Lay>, DstRgb<false, OLay>>)(
+        name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+}
+template <class Lay, class OLay>
+static int render_crops_lanczos_fmt(const char *name, int pix_fmt, bool to_nv12, SvcHandle *h, const uint8_t *frames, const Lay &L, const Colours &C,
+                                    int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, const OLay &O, int oh, int ow,
+                                    int flags, void *stream) {
+    const bool nv12 = pix_fmt == SVC_FMT_NV12;
+    if (to_nv12)
+        return (nv12 ? render_crops_lanczos<SrcNv12<Lay>, DstNv12<OLay>> : render_crops_lanczos<SrcRgb<Lay>, DstNv12<OLay>>)(
+            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+    if (flags & SVC_RENDER_BGR)
+        return (nv12 ? render_crops_lanczos<SrcNv12<Lay>, DstRgb<true, OLay>> : render_crops_lanczos<SrcRgb<Lay>, DstRgb<true, OLay>>)(
+            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+    return (nv12 ? render_crops_lanczos<SrcNv12<Lay>, DstRgb<false, OLay>> : render_crops_lanczos<SrcRgb<Lay>, DstRgb<false, OLay>>)(
+        name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
 }
 
 extern "C" int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                    int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_u8", SVC_FMT_RGB24, false, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_u8", SVC_FMT_RGB24, false, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
 }
 extern "C" int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                      int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_nv12", SVC_FMT_NV12, false, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_nv12", SVC_FMT_NV12, false, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
 }
 extern "C" int svc_render_crops_u8_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                            int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_u8_to_nv12", SVC_FMT_RGB24, true, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_u8_to_nv12", SVC_FMT_RGB24, true, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
 }
 extern "C" int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                              int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_nv12_to_nv12", SVC_FMT_NV12, true, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    return render_crops_fmt("svc_render_crops_nv12_to_nv12", SVC_FMT_NV12, true, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
 }
 
 // --------------------------------------------------------------------------------------
 // the same launchers on frames in the caller's layout (SvcFrameLayout: include/svc.h states the rules)
 // --------------------------------------------------------------------------------------
-// The layout of a height x width picture, checked -> Pitched.  Plain integer comparisons, before any device work.
-static int layout_check(const char *name, const SvcFrameLayout *lay, int n, int height, int width, Pitched &L) {
+// The layout of a height x width picture, checked -> Pitched.  Plain integer comparisons, before any device work.  side: "" for the
+// frames' layout, "out_layout: " for an output's (the errors name the side, as colour_check's do; there the picture is the oh x ow
+// output and its size rule is the sink's).
+static int layout_check(const char *name, const char *side, const SvcFrameLayout *lay, int n, int height, int width, Pitched &L) {
+    const bool out = side[0] != 0;
     if (!lay) {
-        svc_set_error("%s: layout is NULL", name);
+        svc_set_error("%s: %slayout is NULL", name, side);
         return SVC_E_INVALID;
     }
     if (lay->struct_size != sizeof(SvcFrameLayout)) {
-        svc_set_error("%s: SvcFrameLayout.struct_size is %u, this library's is %zu (a stale binding)", name, lay->struct_size,
+        svc_set_error("%s: %sSvcFrameLayout.struct_size is %u, this library's is %zu (a stale binding)", name, side, lay->struct_size,
                       sizeof(SvcFrameLayout));
         return SVC_E_INVALID;
     }
     const bool nv12 = lay->pix_fmt == SVC_FMT_NV12;
     if (!nv12 && lay->pix_fmt != SVC_FMT_RGB24) {
-        svc_set_error("%s: unknown pix_fmt %d (SVC_FMT_RGB24 or SVC_FMT_NV12)", name, lay->pix_fmt);
+        svc_set_error("%s: %sunknown pix_fmt %d (SVC_FMT_RGB24 or SVC_FMT_NV12)", name, side, lay->pix_fmt);
         return SVC_E_INVALID;
     }
-    if (!(nv12 ? SrcNv12<Pitched>::size_ok(height, width) : SrcRgb<Pitched>::size_ok(height, width))) {
-        svc_set_error("%s: invalid argument%s", name, nv12 ? SrcNv12<Pitched>::size_rule() : SrcRgb<Pitched>::size_rule());
+    if (!(nv12 ? SrcNv12<Pitched>::size_ok(height, width) : SrcRgb<Pitched>::size_ok(height, width))) {       // (the sinks' size_ok are these)
+        if (out) svc_set_error("%s: %san output of %dx%d (%s)", name, side, width, height, nv12 ? DstNv12<>::size_rule() : DstRgb<false>::size_rule());
+        else svc_set_error("%s: invalid argument%s", name, nv12 ? SrcNv12<Pitched>::size_rule() : SrcRgb<Pitched>::size_rule());
         return SVC_E_INVALID;
     }
     L = Pitched{lay->frame_stride, lay->pitch, lay->chroma_offset, lay->chroma_pitch};
     if (L.frame_stride < 0 || L.pitch < 0 || L.chroma_offset < 0 || L.chroma_pitch < 0) {
-        svc_set_error("%s: layout values must be non-negative", name);
+        svc_set_error("%s: %slayout values must be non-negative", name, side);
         return SVC_E_INVALID;
     }
     const long long row = nv12 ? (long long)width : 3ll * width;
     if (L.pitch < row) {
-        svc_set_error("%s: pitch %lld is below the row's %lld bytes", name, L.pitch, row);
+        svc_set_error("%s: %spitch %lld is below the row's %lld bytes", name, side, L.pitch, row);
         return SVC_E_INVALID;
     }
     if (!nv12 && (L.chroma_offset || L.chroma_pitch)) {
-        svc_set_error("%s: chroma_offset and chroma_pitch must be 0 for rgb24", name);
+        svc_set_error("%s: %schroma_offset and chroma_pitch must be 0 for rgb24", name, side);
         return SVC_E_INVALID;
     }
     if (nv12 && L.chroma_pitch < width) {
-        svc_set_error("%s: chroma_pitch %lld is below the width %d", name, L.chroma_pitch, width);
+        svc_set_error("%s: %schroma_pitch %lld is below the width %d", name, side, L.chroma_pitch, width);
         return SVC_E_INVALID;
     }
     // (128-bit products: a pitch near 2^63 must fail these comparisons, not wrap past them)
     const __int128 luma_end = (__int128)L.pitch * (height - 1) + width;
     if (nv12 && L.chroma_offset < luma_end) {
-        svc_set_error("%s: chroma_offset %lld is below pitch * (height - 1) + width = %lld: the chroma plane overlaps the last luma row",
-                      name, L.chroma_offset, (long long)luma_end);
+        svc_set_error("%s: %schroma_offset %lld is below pitch * (height - 1) + width = %lld: the chroma plane overlaps the last luma row",
+                      name, side, L.chroma_offset, (long long)luma_end);
         return SVC_E_INVALID;
     }
     const __int128 extent = nv12 ? (__int128)L.chroma_offset + (__int128)L.chroma_pitch * (height / 2 - 1) + width
                                  : (__int128)L.pitch * (height - 1) + 3ll * width;      // = Src::extent(L, height, width)
     if (L.frame_stride < extent) {
-        svc_set_error("%s: frame_stride %lld is below the frame's extent of %lld bytes", name, L.frame_stride, (long long)extent);
+        svc_set_error("%s: %sframe_stride %lld is below the frame's extent of %lld bytes", name, side, L.frame_stride, (long long)extent);
         return SVC_E_INVALID;
     }
     // the launchers form frames + (n - 1) * frame_stride + extent in 64 bits: it must be an address
     if (n > 0 && (__int128)(n - 1) * L.frame_stride + extent > (__int128)PTRDIFF_MAX) {
-        svc_set_error("%s: %d frames of frame_stride %lld span more than PTRDIFF_MAX bytes", name, n, L.frame_stride);
+        svc_set_error("%s: %s%d frames of frame_stride %lld span more than PTRDIFF_MAX bytes", name, side, n, L.frame_stride);
         return SVC_E_INVALID;
     }
     return SVC_OK;
@@ -1128,7 +1215,7 @@ static int layout_check(const char *name, const SvcFrameLayout *lay, int n, int 
 static int resize_frames_any(const char *name, SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *colour,
                              int n, int height, int width, uint8_t *out, int sh, int sw, void *stream) {
     Pitched L;
-    int rc = layout_check(name, layout, n, height, width, L), m, r;
+    int rc = layout_check(name, "", layout, n, height, width, L), m, r;
     if (rc) return rc;
     const bool nv12 = layout->pix_fmt == SVC_FMT_NV12;
     if ((rc = colour_check(name, "colour", colour, nv12, m, r))) return rc;
@@ -1141,36 +1228,43 @@ static int resize_frames_any(const char *name, SvcHandle *h, const uint8_t *fram
 // values.  profiles/pitched_frames.json measured that policy within 4 % of the compile-time packed one on the linear kernels; six
 // more instances would buy nothing that has been measured.  linear_name: the name the SVC_FILTER_LINEAR path reports under
 // (svc_render_crops_filter forwards to svc_render_crops_layout: its bytes, its errors).
+// out_layout (svc_render_crops_to_layout; NULL for every other entry, whose output is packed and whose format is out_fmt): where
+// the bytes of the oh x ow output frames lie.  The pitched sinks are instantiated for this launcher only -- i.e. for the Pitched
+// source policy, all four kernels, 2 sources x 3 sinks -- and an out_layout that holds the packed values runs the packed sinks.
 static int render_crops_any(const char *name, const char *linear_name, SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout,
                             const SvcColour *in_colour, int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out,
-                            int out_fmt, const SvcColour *out_colour, int oh, int ow, int filter, int flags, void *stream) {
+                            int out_fmt, const SvcFrameLayout *out_layout, const SvcColour *out_colour, int oh, int ow, int filter, int flags,
+                            void *stream) {
     if (filter == SVC_FILTER_LINEAR) name = linear_name;
     else if (filter != SVC_FILTER_LANCZOS) {
         svc_set_error("%s: unknown filter %d (SVC_FILTER_LINEAR or SVC_FILTER_LANCZOS)", name, filter);
         return SVC_E_INVALID;
     }
-    Pitched L;
-    int rc = layout_check(name, layout, n, height, width, L), mi, ri, mo, ro;
+    Pitched L, O = {0, 0, 0, 0};
+    int rc = layout_check(name, "", layout, n, height, width, L), mi, ri, mo, ro;
     if (rc) return rc;
-    if (out_fmt != SVC_FMT_RGB24 && out_fmt != SVC_FMT_NV12) {
+    bool packed_out = true;
+    if (out_layout) {
+        if ((rc = layout_check(name, "out_layout: ", out_layout, n, oh, ow, O))) return rc;
+        out_fmt = out_layout->pix_fmt;
+        packed_out = out_fmt == SVC_FMT_NV12
+            ? O.pitch == ow && O.chroma_pitch == ow && O.chroma_offset == (long long)oh * ow && (size_t)O.frame_stride == DstNv12<>::frame_bytes(oh, ow)
+            : O.pitch == 3ll * ow && (size_t)O.frame_stride == DstRgb<false>::frame_bytes(oh, ow);
+    } else if (out_fmt != SVC_FMT_RGB24 && out_fmt != SVC_FMT_NV12) {
         svc_set_error("%s: unknown out_fmt %d (SVC_FMT_RGB24 or SVC_FMT_NV12)", name, out_fmt);
         return SVC_E_INVALID;
     }
-    const bool nv12 = layout->pix_fmt == SVC_FMT_NV12;
-    if ((rc = colour_check(name, "in_colour", in_colour, nv12, mi, ri)) ||
-        (rc = colour_check(name, "out_colour", out_colour, out_fmt == SVC_FMT_NV12, mo, ro)))
+    const bool to_nv12 = out_fmt == SVC_FMT_NV12;
+    if ((rc = colour_check(name, "in_colour", in_colour, layout->pix_fmt == SVC_FMT_NV12, mi, ri)) ||
+        (rc = colour_check(name, "out_colour", out_colour, to_nv12, mo, ro)))
         return rc;
     const Colours C = {COLOUR_DEC[mi][ri], COLOUR_ENC[mo][ro]};
-    if (filter == SVC_FILTER_LINEAR)
-        return render_crops_fmt(name, layout->pix_fmt, out_fmt == SVC_FMT_NV12, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
-    if (out_fmt == SVC_FMT_NV12)
-        return (nv12 ? render_crops_lanczos<SrcNv12<Pitched>, DstNv12> : render_crops_lanczos<SrcRgb<Pitched>, DstNv12>)(
-            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
-    if (flags & SVC_RENDER_BGR)
-        return (nv12 ? render_crops_lanczos<SrcNv12<Pitched>, DstRgb<true>> : render_crops_lanczos<SrcRgb<Pitched>, DstRgb<true>>)(
-            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
-    return (nv12 ? render_crops_lanczos<SrcNv12<Pitched>, DstRgb<false>> : render_crops_lanczos<SrcRgb<Pitched>, DstRgb<false>>)(
-        name, h, frames, L, C, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream);
+    if (filter == SVC_FILTER_LINEAR) {
+        if (packed_out) return render_crops_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
+        return render_crops_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+    }
+    if (packed_out) return render_crops_lanczos_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
+    return render_crops_lanczos_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
 }
 
 extern "C" int svc_resize_frames_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height,
@@ -1181,7 +1275,7 @@ extern "C" int svc_render_crops_layout(SvcHandle *h, const uint8_t *frames, cons
                                        int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
                                        int flags, void *stream) {
     const char *name = "svc_render_crops_layout";
-    return render_crops_any(name, name, h, frames, layout, nullptr, n, height, width, boxes, bw, bh, out, out_fmt, nullptr, oh, ow,
+    return render_crops_any(name, name, h, frames, layout, nullptr, n, height, width, boxes, bw, bh, out, out_fmt, nullptr, nullptr, oh, ow,
                             SVC_FILTER_LINEAR, flags, stream);
 }
 // svc_render_crops_layout with a choice of filter (include/svc.h)
@@ -1189,7 +1283,7 @@ extern "C" int svc_render_crops_filter(SvcHandle *h, const uint8_t *frames, cons
                                        const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
                                        int filter, int flags, void *stream) {
     return render_crops_any("svc_render_crops_filter", "svc_render_crops_layout", h, frames, layout, nullptr, n, height, width, boxes, bw, bh,
-                            out, out_fmt, nullptr, oh, ow, filter, flags, stream);
+                            out, out_fmt, nullptr, nullptr, oh, ow, filter, flags, stream);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1203,6 +1297,22 @@ extern "C" int svc_render_crops_colour(SvcHandle *h, const uint8_t *frames, cons
                                        int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt,
                                        const SvcColour *out_colour, int oh, int ow, int filter, int flags, void *stream) {
     const char *name = "svc_render_crops_colour";
-    return render_crops_any(name, name, h, frames, layout, in_colour, n, height, width, boxes, bw, bh, out, out_fmt, out_colour, oh, ow,
+    return render_crops_any(name, name, h, frames, layout, in_colour, n, height, width, boxes, bw, bh, out, out_fmt, nullptr, out_colour, oh, ow,
+                            filter, flags, stream);
+}
+
+// --------------------------------------------------------------------------------------
+// the same into the caller's output layout: an encoder's surfaces (include/svc.h states the write contract)
+// --------------------------------------------------------------------------------------
+extern "C" int svc_render_crops_to_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *in_colour,
+                                          int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out,
+                                          const SvcFrameLayout *out_layout, const SvcColour *out_colour, int oh, int ow, int filter, int flags,
+                                          void *stream) {
+    const char *name = "svc_render_crops_to_layout";
+    if (!out_layout) {
+        svc_set_error("%s: out_layout: layout is NULL", name);
+        return SVC_E_INVALID;
+    }
+    return render_crops_any(name, name, h, frames, layout, in_colour, n, height, width, boxes, bw, bh, out, 0, out_layout, out_colour, oh, ow,
                             filter, flags, stream);
 }

@@ -134,12 +134,16 @@ class _RawFrameWriter:
         self.fp.close()
 
 
-def write_frames_raw(path, fr, size, pix_fmt='rgb24', colour=None):
+def write_frames_raw(path, fr, size, pix_fmt='rgb24', colour=None, layout=None):
     """A writer for smartVidCrop.set_video_writer that appends every frame's bytes to the one file ``path``: a raw stream
     as ``ffmpeg -f rawvideo -pix_fmt <pix_fmt> -s <w>x<h> -r <fr>`` reads it.  ``pix_fmt``: 'rgb24' (frames [h,w,3] u8) or
     'nv12' (frames [h*3/2,w] u8, w and h even: smart_vid_crop(..., out_pix_fmt='nv12')); ``size`` = (w, h).  A raw file keeps
     neither size nor rate nor colour: ``fr``, and the ``colour=dict(matrix=, range=)`` that smart_vid_crop hands over for an NV12
-    output that is not BT.601 limited, are accepted for the writer signature and ignored.  Needs nothing beyond numpy."""
+    output that is not BT.601 limited, are accepted for the writer signature and ignored.  ``layout``: what
+    smart_vid_crop(out_layout=...) hands its writer; a raw file is packed, so anything but None is refused with ValueError (before
+    the file is created).  Needs nothing beyond numpy."""
+    if layout is not None:
+        raise ValueError('write_frames_raw writes packed frames: a raw file has no pitch (layout=%r); render without out_layout' % (layout,))
     return _RawFrameWriter(path, fr, size, pix_fmt)
 
 

@@ -242,22 +242,45 @@ def frame_layout(pix_fmt, h, w, layout=None, frame_stride=None):
     return L
 
 
-def _pitched(frames, layout, pix_fmt):
+def _pitched(frames, layout, pix_fmt, what='frames'):
     """frames of a FrameLayout: a uint8 CUDA tensor [n, frame_stride] -- or any 2-D view with unit element stride whose rows are
-    frame_stride bytes apart and hold the frame's extent (the last frame need not have its trailing gap) -> n."""
+    frame_stride bytes apart and hold the frame's extent (the last frame need not have its trailing gap) -> n.  what: the
+    keyword the errors name ('frames'; 'out' for an output with an out_layout, which lies under the same rules)."""
     if not isinstance(layout, FrameLayout):
-        raise TypeError('layout must be an ops.FrameLayout (ops.frame_layout(pix_fmt, h, w, dict(pitch=...), frame_stride))')
+        raise TypeError('%s must be an ops.FrameLayout (ops.frame_layout(pix_fmt, h, w, dict(pitch=...), frame_stride))'
+                        % ('layout' if what == 'frames' else 'out_layout'))
     if layout.pix_fmt != pix_fmt:
-        raise ValueError('the layout is one of %s frames, pix_fmt says %s' % (layout.pix_fmt, pix_fmt))
+        raise ValueError('the layout is one of %s frames, %s says %s' % (layout.pix_fmt, 'pix_fmt' if what == 'frames' else 'out_fmt', pix_fmt))
     if not (torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8):
-        raise TypeError('frames must be a CUDA tensor of dtype torch.uint8')
+        raise TypeError('%s must be a CUDA tensor of dtype torch.uint8' % what)
     if frames.dim() != 2:
-        raise ValueError('frames with a layout are uint8 [n, frame_stride], not %s' % (tuple(frames.shape),))
+        raise ValueError('%s with a layout are uint8 [n, frame_stride], not %s' % (what, tuple(frames.shape),))
     n = int(frames.shape[0])
     if n and (frames.stride(1) != 1 or int(frames.shape[1]) < layout.extent or (n > 1 and frames.stride(0) != layout.frame_stride)):
-        raise ValueError('frames of shape %s and strides %s do not hold frames of %d bytes that lie %d bytes apart'
-                         % (tuple(frames.shape), tuple(frames.stride()), layout.extent, layout.frame_stride))
+        raise ValueError('%s of shape %s and strides %s do not hold frames of %d bytes that lie %d bytes apart'
+                         % (what, tuple(frames.shape), tuple(frames.stride()), layout.extent, layout.frame_stride))
     return n
+
+
+def out_layout_of(out_layout, out_fmt, oh, ow, frame_stride=None):
+    """The layout of an output of oh x ow in `out_fmt`, checked -> FrameLayout (None stays None).  out_layout: an
+    ops.FrameLayout, which must be one of that format and picture size, or dict(pitch=, chroma_offset=, chroma_pitch=) (frames
+    `frame_stride` apart; None: their extent), resolved by frame_layout.  ValueError with the broken rule -- what the renderer's
+    doors check before any device work."""
+    if out_layout is None:
+        return None
+    if isinstance(out_layout, FrameLayout):
+        if out_layout.pix_fmt != out_fmt:
+            raise ValueError('out_layout is one of %s frames, out_fmt says %s' % (out_layout.pix_fmt, out_fmt))
+        if (out_layout.h, out_layout.w) != (int(oh), int(ow)):
+            raise ValueError('out_layout is one of %d x %d pictures, the output is %d x %d' % (out_layout.w, out_layout.h, ow, oh))
+        return out_layout
+    if not isinstance(out_layout, dict):
+        raise ValueError('out_layout is an ops.FrameLayout or dict(pitch=, chroma_offset=, chroma_pitch=), not %r' % (out_layout,))
+    try:
+        return frame_layout(out_fmt, oh, ow, out_layout, frame_stride)
+    except ValueError as e:
+        raise ValueError('out_layout: %s' % e) from None
 
 
 BLEND_NEXT, MAP_HELD = 1, 2          # bits of cluster_center_'s per-map flags (include/svc.h: SVC_BLEND_NEXT, SVC_MAP_HELD)
@@ -342,7 +365,7 @@ class Engine:
 
     # -- rendering ------------------------------------------------------------------------
     def render_crops(self, frames, boxes, out_hw=None, bgr=False, out=None, pix_fmt='rgb24', out_fmt='rgb24', layout=None, interp='linear',
-                     colour=None, out_colour=None):
+                     colour=None, out_colour=None, out_layout=None):
         """uint8 [n,h,w,3] frames on the device (pix_fmt='nv12': uint8 [n,h*3/2,w], svc_render_crops_nv12; the crops are RGB / BGR
         either way) and int32 [n,4] boxes (x1,y1,x2,y2, one window size for all; a CUDA tensor, or
         host values that are copied over) -> uint8
@@ -357,7 +380,13 @@ class Engine:
         value outside ops.INTERPS: ValueError.
         colour / out_colour (what ops.frame_colour takes): the matrix and range nv12 frames are decoded with / an nv12 output
         is encoded with, chosen independently (svc_render_crops_colour; include/svc.h states the table); None is BT.601
-        limited, and the call it always was.  A colour given for an rgb24 side: ValueError."""
+        limited, and the call it always was.  A colour given for an rgb24 side: ValueError.
+        out_layout (an ops.FrameLayout of the out_fmt picture of oh x ow: ops.frame_layout(out_fmt, oh, ow, dict(pitch=...),
+        frame_stride)): the crops are written where an encoder's surfaces want them (svc_render_crops_to_layout) -> uint8
+        [n, frame_stride].  The picture bytes are those of the call without it; no other byte is written (without out= they are
+        whatever the allocation held).  out= may be the caller's own 2-D view -- unit element stride, rows frame_stride bytes
+        apart that hold the frame's extent, e.g. pool[first:first + n * k:k] of a surface pool: the door for an encoder on the
+        same GPU.  A layout of another format or picture size: ValueError before any device work."""
         check_interp(interp)
         _side_colour(colour, pix_fmt, 'colour')
         _side_colour(out_colour, out_fmt if out_fmt in OUT_FMTS else 'nv12', 'out_colour')      # (an unknown out_fmt is reported as that, below)
@@ -370,6 +399,10 @@ class Engine:
         bw, bh = int(b0[2] - b0[0]), int(b0[3] - b0[1])
         oh, ow = (bh, bw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
         shape = (n,) + out_frame_shape(out_fmt, oh, ow, bgr)      # (the ValueErrors come before anything touches the device)
+        if out_layout is not None:
+            if not isinstance(out_layout, FrameLayout):
+                raise TypeError('out_layout must be an ops.FrameLayout (ops.frame_layout(out_fmt, oh, ow, dict(pitch=...), frame_stride))')
+            shape = (n, out_layout_of(out_layout, out_fmt, oh, ow).frame_stride)
         if layout is None:
             _need_cuda(frames, torch.uint8, 'frames')
         else:
@@ -378,13 +411,33 @@ class Engine:
             boxes = torch.from_numpy(np.ascontiguousarray(boxes, np.int32)).to(frames.device)
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
-        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt, out_fmt, layout, interp, colour, out_colour)
+        return self._render(frames, boxes, bw, bh, out, bgr, pix_fmt, out_fmt, layout, interp, colour, out_colour, out_layout)
 
     def _render(self, frames, boxes, bw, bh, out, bgr, pix_fmt='rgb24', out_fmt='rgb24', layout=None, interp='linear', colour=None,
-                out_colour=None):
+                out_colour=None, out_layout=None):
         check_interp(interp)
         colour, out_colour = _side_colour(colour, pix_fmt, 'colour'), _side_colour(out_colour, out_fmt, 'out_colour')
         _need_cuda(boxes, torch.int32, 'boxes')
+        if out_layout is not None:          # one entry for every format, layout, filter and colour; out: [n, frame_stride] or a view like it
+            out_frame_shape(out_fmt, out_layout.h, out_layout.w, bgr)
+            on = _pitched(out, out_layout, out_fmt, 'out')
+            if layout is None:
+                _need_cuda(frames, torch.uint8, 'frames')
+                n, h, w = picture_size(frames, pix_fmt)
+            else:
+                n, h, w = _pitched(frames, layout, pix_fmt), layout.h, layout.w
+            if on != n:
+                raise ValueError('out holds %d frames, frames holds %d' % (on, n))
+            if tuple(boxes.shape) != (n, 4):
+                raise ValueError('boxes of shape %s for %d frames (int32 [n, 4])' % (tuple(boxes.shape), n))
+            if not hasattr(self.lib, 'svc_render_crops_to_layout'):
+                raise _lib.SvcError('%s lacks svc_render_crops_to_layout: an out_layout needs a build that has it' % _lib.LIB_PATH)
+            lay, olay = (layout or frame_layout(pix_fmt, h, w)).struct(), out_layout.struct()
+            _lib.check(self.lib.svc_render_crops_to_layout(self._h, _ptr(frames), ctypes.byref(lay), _colour_struct(colour), n, h, w,
+                                                           _ptr(boxes), bw, bh, _ptr(out), ctypes.byref(olay), _colour_struct(out_colour),
+                                                           out_layout.h, out_layout.w, INTERPS.index(interp), RENDER_BGR if bgr else 0,
+                                                           _stream()))
+            return out
         _need_cuda(out, torch.uint8, 'out')
         if layout is None:
             _need_cuda(frames, torch.uint8, 'frames')

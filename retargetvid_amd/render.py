@@ -12,7 +12,8 @@ svc_render_crops_nv12, frames with a layout are staged as they are and read thro
 are those of the packed RGB pictures).  The crops are RGB / BGR -- unless out_fmt='nv12' asks for NV12 crops (uint8
 [m, oh * 3 / 2, ow], what a hardware encoder takes: BT.601 limited range, fused into the render kernels,
 svc_render_crops_u8_to_nv12 / _nv12_to_nv12; half the bytes to copy back).  They come back through pinned double buffers on
-a second side stream, so that the sink consumes chunk c while the device renders chunk c + 1."""
+a second side stream, so that the sink consumes chunk c while the device renders chunk c + 1.  out_layout= renders them into an
+encoder's layout instead (svc_render_crops_to_layout): chunks uint8 [m, frame_stride], picture bytes in place, 0 elsewhere."""
 import numpy as np
 
 _MAX_CHUNK = 32
@@ -36,7 +37,7 @@ def check_boxes(bbs, fc, h, w):
 
 
 def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, chunk=32, pix_fmt=None, out_fmt='rgb24', layout=None,
-                 interp='linear', colour=None, out_colour=None):
+                 interp='linear', colour=None, out_colour=None, out_layout=None):
     """Render VD['fc'] frames of `video` (the ingest_pickle dict, or its 'frames' container) at VD['bbs_np'].
     pix_fmt: the frames' format when `video` is a bare container (a dict brings its own 'pix_fmt'; default 'rgb24'); an
     unknown format, an NV12 picture of odd size or a container of another shape raise ValueError before any device work.
@@ -51,7 +52,12 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     (PIL.Image.resize LANCZOS on the cropped window, bit for bit); another value raises ValueError before any device work.
     colour: the matrix and range of a bare container of nv12 frames (a dict brings its own 'colour'; ops.frame_colour states the
     spellings).  out_colour: the colour an nv12 output is encoded with; None means the source's (BT.601 limited for an rgb24
-    source).  With out_fmt='rgb24' a given out_colour raises ValueError, as does an unknown matrix or range."""
+    source).  With out_fmt='rgb24' a given out_colour raises ValueError, as does an unknown matrix or range.
+    out_layout: where the bytes of every output frame lie, as an encoder's surfaces want them -- dict(pitch=, chroma_offset=,
+    chroma_pitch=) (frames their extent apart) or an ops.FrameLayout of the out_fmt picture of the final size; resolved once,
+    against the final (oh, ow), and a broken rule or another format or size raises ValueError before any device work.  Chunks
+    and the returned array are then uint8 [m, frame_stride]: the picture bytes are those of the call without it, every other
+    byte is 0 (svc_render_crops_to_layout writes the picture rows and nothing else, into slots that were allocated zeroed)."""
     from .frames import FrameSource
     from .ops import check_interp, frame_colour
     check_interp(interp)
@@ -69,8 +75,11 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     ow, oh = (bw, bh) if out_size is None else (int(out_size[0]), int(out_size[1]))
     if oh < 1 or ow < 1:
         raise ValueError('output size %s' % (out_size,))
-    from .ops import out_frame_shape
+    from .ops import out_frame_shape, out_layout_of
     shape = out_frame_shape(out_fmt, oh, ow, bgr)
+    out_layout = out_layout_of(out_layout, out_fmt, oh, ow)
+    if out_layout is not None:
+        shape = (out_layout.frame_stride,)
     chunk = max(1, min(int(chunk), _MAX_CHUNK, _RING_BYTES // int(np.prod(shape))))       # (the real bytes per frame)
     result = None
     if sink is None:
@@ -86,7 +95,7 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     engine = engine or S.get_engine()
     dev = engine.device
     boxes = torch.from_numpy(np.ascontiguousarray(VD['bbs_np'][:fc], np.int32)).to(dev)
-    out = _OutRing(engine, chunk, oh, ow, sink, out_fmt, src.pix_fmt, src.layout, interp, src.colour, out_colour)
+    out = _OutRing(engine, chunk, oh, ow, sink, out_fmt, src.pix_fmt, src.layout, interp, src.colour, out_colour, out_layout)
     src.chunks(engine, fc, chunk, lambda staged, s: out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr))
     out.flush()
     return result
@@ -96,20 +105,25 @@ class _OutRing:
     """Two device output slots and two pinned host slots: chunk c is rendered on the caller's stream into device slot c & 1,
     copied D2H on a side stream into pinned slot c & 1, and handed to the sink once the copy of chunk c + 1 is enqueued."""
 
-    def __init__(self, engine, cap, oh, ow, sink, out_fmt='rgb24', pix_fmt='rgb24', layout=None, interp='linear', colour=None, out_colour=None):
+    def __init__(self, engine, cap, oh, ow, sink, out_fmt='rgb24', pix_fmt='rgb24', layout=None, interp='linear', colour=None, out_colour=None,
+                 out_layout=None):
         import torch
         from .ops import frame_shape
         self.engine, self.sink, self.dev, self.out_fmt = engine, sink, engine.device, out_fmt
         self.pix_fmt, self.layout = pix_fmt, layout             # of the frames that will be pushed
         self.interp = interp
         self.colour, self.out_colour = colour, out_colour       # of nv12 frames pushed / of an nv12 output (None: BT.601 limited)
-        key = (cap, oh, ow, out_fmt)
-        shape = (cap,) + frame_shape(out_fmt, oh, ow)           # slots shaped (and keyed) by the output format
+        self.out_layout = out_layout                            # of the output frames (None: packed)
+        key = (cap, oh, ow, out_fmt) if out_layout is None else (cap, oh, ow, out_fmt, out_layout.key())
+        # slots shaped (and keyed) by the output format -- and by the output layout: [cap, frame_stride], allocated zeroed, and
+        # the kernels write picture bytes only, so what is delivered is 0 outside the picture for as long as the slots live
+        shape = (cap,) + (frame_shape(out_fmt, oh, ow) if out_layout is None else (out_layout.frame_stride,))
+        make = torch.empty if out_layout is None else torch.zeros
         ring = engine.__dict__.get('_render_ring')
         if ring is None or ring['key'] != key:
             ring = engine._render_ring = dict(
-                key=key, dev=[torch.empty(shape, dtype=torch.uint8, device=self.dev) for _ in range(2)],
-                host=[torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(2)],
+                key=key, dev=[make(shape, dtype=torch.uint8, device=self.dev) for _ in range(2)],
+                host=[make(shape, dtype=torch.uint8).pin_memory() for _ in range(2)],
                 stream=torch.cuda.Stream(device=self.dev))
         self.ring = ring
         self.rendered = [torch.cuda.Event(), torch.cuda.Event()]
@@ -133,7 +147,8 @@ class _OutRing:
         if self.used[slot]:
             compute.wait_event(self.copied[slot])           # the device slot's previous D2H has read it
         dst = self.ring['dev'][slot][:m]
-        self.engine._render(staged, boxes, bw, bh, dst, bgr, self.pix_fmt, self.out_fmt, self.layout, self.interp, self.colour, self.out_colour)
+        self.engine._render(staged, boxes, bw, bh, dst, bgr, self.pix_fmt, self.out_fmt, self.layout, self.interp, self.colour, self.out_colour,
+                            self.out_layout)
         self.rendered[slot].record(compute)
         with torch.cuda.stream(side):
             side.wait_event(self.rendered[slot])

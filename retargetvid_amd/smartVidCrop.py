@@ -543,7 +543,7 @@ class _LazySmaps(dict):
 def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn='', frames_dir='',
                    temp_path=None, verbose=False, save_vid=True, callback_progress=None,
                    callback_session=None, callback_status=None, copy_sound=False, engine=None, shot_net=None, stream_batch=0,
-                   out_size=None, out_pix_fmt='rgb24', out_interp='linear', out_colour=None):
+                   out_size=None, out_pix_fmt='rgb24', out_interp='linear', out_colour=None, out_layout=None):
     """Saliency -> crop windows for one video.  Returns (VD, smart_crop_results) like the
     reference; VD['bbs'] holds one [x1,y1,x2,y2] per decoded frame.  A video dict without ``trans_inds`` takes the
     reference's video path: ``shot_net`` (transnetv1_handler.ShotTransNet) detects the shots inside the ingest.
@@ -567,6 +567,12 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         limited for rgb24 frames).  A colour other than BT.601 limited is handed to the writer as
         fn(final_vid_fn, VD['fr'], size, pix_fmt='nv12', colour=dict(matrix=, range=)); the default keeps the call without it.
         With out_pix_fmt='rgb24' a given out_colour raises ValueError, as does an unknown matrix or range, before any work.
+        out_layout: where the bytes of every written frame lie (render.render_video(out_layout=): a dict of pitch /
+        chroma_offset / chroma_pitch, or an ops.FrameLayout of the out_pix_fmt picture of the output size).  The frames handed
+        to the writer are then uint8 [frame_stride] -- picture bytes in place, 0 elsewhere -- and the writer is opened with an
+        extra layout=<the resolved ops.FrameLayout> keyword; without an out_layout the call stays without it.  A broken layout,
+        or one of another format or size, raises ValueError before the writer is opened -- with an out_size before any work;
+        the pickle mode with a layout raises ValueError (ingest.write_frames_raw refuses one too: a raw file is packed).
     demo_fn (the five-panel demo) and copy_sound (ffmpeg) with a render raise NotImplementedError."""
     import torch
     sc_init_time()
@@ -579,13 +585,21 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         raise NotImplementedError('the five-panel demo video (cv2 drawing and text) is not rendered by this package; '
                                   'pass demo_fn=\'\'')
     render_pkl = render_writer = False
-    from .ops import DEFAULT_COLOUR, check_interp, frame_colour, out_frame_shape
+    from .ops import DEFAULT_COLOUR, FrameLayout, check_interp, frame_colour, out_frame_shape, out_layout_of
     out_frame_shape(out_pix_fmt, *((2, 2) if out_size is None else (out_size[1], out_size[0])))     # unknown format, odd out_size: ValueError
     check_interp(out_interp)
     if out_colour is not None:
         out_colour = frame_colour(out_colour)
         if out_pix_fmt == 'rgb24':
             raise ValueError("out_colour=%r describes an nv12 output; out_pix_fmt is 'rgb24'" % (out_colour,))
+    if out_layout is not None:
+        if out_size is not None:            # (the final size is known: every rule is checked now)
+            out_layout_of(out_layout, out_pix_fmt, out_size[1], out_size[0])
+        elif isinstance(out_layout, FrameLayout):
+            if out_layout.pix_fmt != out_pix_fmt:
+                raise ValueError('out_layout is one of %s frames, out_pix_fmt says %s' % (out_layout.pix_fmt, out_pix_fmt))
+        elif not isinstance(out_layout, dict):
+            raise ValueError('out_layout is an ops.FrameLayout or dict(pitch=, chroma_offset=, chroma_pitch=), not %r' % (out_layout,))
     if save_vid and final_vid_fn:
         if copy_sound:
             raise NotImplementedError('copy_sound needs ffmpeg, which is not part of this package; pass copy_sound=False')
@@ -593,6 +607,8 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         if render_pkl and out_pix_fmt != 'rgb24':
             raise ValueError('the pickle mode writes BGR crops; out_pix_fmt=%r needs a writer (a video that is not a .pkl path)'
                              % (out_pix_fmt,))
+        if render_pkl and out_layout is not None:
+            raise ValueError('the pickle mode writes packed BGR crops; out_layout needs a writer (a video that is not a .pkl path)')
         render_writer = not render_pkl
         if render_writer and _video_writer is None:
             raise NotImplementedError('rendering to %r needs a video writer: install one with set_video_writer() (for '
@@ -663,15 +679,19 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         else:
             size = tuple(int(v) for v in out_size) if out_size is not None else (int(VD['fbb_w']), int(VD['fbb_h']))
             out_frame_shape(out_pix_fmt, size[1], size[0])        # (an odd crop window as NV12: ValueError before the writer creates anything)
-            if out_pix_fmt == 'rgb24':
-                writer = _video_writer(final_vid_fn, VD['fr'], size)
-            else:
+            out_layout = out_layout_of(out_layout, out_pix_fmt, size[1], size[0])     # (resolved against the final size, before the writer)
+            kw = {}                         # the writer's keywords beyond the three-argument call: only what was asked for
+            if out_pix_fmt != 'rgb24':
+                kw['pix_fmt'] = out_pix_fmt
                 col = out_colour or FrameSource.of(video).colour or DEFAULT_COLOUR      # (None: the source's own)
-                writer = _video_writer(final_vid_fn, VD['fr'], size, pix_fmt=out_pix_fmt) if col == DEFAULT_COLOUR else \
-                    _video_writer(final_vid_fn, VD['fr'], size, pix_fmt=out_pix_fmt, colour=dict(matrix=col[0], range=col[1]))
+                if col != DEFAULT_COLOUR:
+                    kw['colour'] = dict(matrix=col[0], range=col[1])
+            if out_layout is not None:
+                kw['layout'] = out_layout
+            writer = _video_writer(final_vid_fn, VD['fr'], size, **kw)
             try:
                 render.render_video(video, VD, engine=engine, out_size=size, sink=lambda chunk: [writer.write(f) for f in chunk],
-                                    out_fmt=out_pix_fmt, interp=out_interp, out_colour=out_colour)
+                                    out_fmt=out_pix_fmt, interp=out_interp, out_colour=out_colour, out_layout=out_layout)
             finally:
                 writer.release()
         sc_register_time(t, 'render')
