@@ -86,7 +86,8 @@ const char *svc_last_error(void);
  * (12, no bump) svc_render_crops_filter (SVC_FILTER_*) was added without one: no struct and no existing signature changed, and
  *     a binding finds the entry by its symbol (dlsym), not by the revision.  Likewise svc_debug_net_plan (SVC_PLAN_*), and
  *     SvcColour with svc_resize_frames_colour and svc_render_crops_colour (NV12 colour): a new struct and two new entries; and
- *     svc_render_crops_to_layout (pitched output): one new entry that takes the existing SvcFrameLayout, unchanged, for the output. */
+ *     svc_render_crops_to_layout (pitched output): one new entry that takes the existing SvcFrameLayout, unchanged, for the output; and
+ *     svc_render_windows_q8 (sub-pixel windows): one new entry, no struct. */
 #define SVC_ABI_VERSION 12
 int svc_abi_version(void);
 
@@ -310,6 +311,45 @@ int svc_render_crops_to_layout(SvcHandle *h, const uint8_t *frames, const SvcFra
                                uint8_t *out, const SvcFrameLayout *out_layout, const SvcColour *out_colour,
                                int oh, int ow, int filter, int flags, void *stream);
 
+/* Sub-pixel windows: svc_render_crops_to_layout with SVC_FILTER_LINEAR, the top-left corner of every frame's bw x bh window given
+ * in 1/256 pixel (origins_q8[n][2] int32 on the device: x, y) instead of by a box.  A crop delivered at a fixed size then follows a
+ * smooth trajectory without the steps a whole-pixel origin gives it (a 607 x 1080 window delivered at 1080 x 1920 steps by 1.78
+ * output pixels).  Integers only, on the host and on the device; nothing is built per call.
+ * Origin.  X = clamp(origins_q8[f][0], 0, (width - bw) * 256), xi = X >> 8, xf = X & 255; Y, yi, yf likewise with height and bh.
+ * A bad origin (INT32_MIN, INT32_MAX) never reads outside the frame, as a bad box does not.
+ * Columns.  T is the INTER_LINEAR table of (bh, bw) -> (oh, ow) the integer entries use (for equal sizes the identity).  For
+ * output column ox it gives the left tap sx in window coordinates (clamped to 0 .. bw - 1, the fraction zero where it was clamped),
+ * the right tap min(sx + 1, bw - 1) and the 11-bit weights a0 + a1 = 2048, a1 the right tap's.  xf == 0: taps and weights are the
+ * table's, unchanged.  xf > 0:
+ *   p = sx * 2048 + a1 + 8 * xf        the table's position in 1/2048 pixel, moved right by xf / 256 pixel
+ *   sx' = p >> 11,  a1' = p & 2047,  a0' = 2048 - a1'
+ * and the taps are frame columns xi + sx' and xi + sx' + 1, both weighted (no column is a plain copy).  sx' <= bw - 1 (from the
+ * table's xmax on, sx = bw - 1 and a1 = 0, and 8 * 255 < 2048), and xf > 0 implies xi < width - bw, so the right tap is at most xi +
+ * bw <= width - 1: a pixel of the frame.  At the window's clamped edge columns it is the table's CLAMPED position that is
+ * shifted: this is the definition.
+ * Rows.  The same with yf, bh and height, on the table's rows as the integer entries fetch them: y0 = clamp(sy, 0, bh - 1), y1 =
+ * clamp(sy + 1, 0, bh - 1) with the weights b0 + b1 = 2048.  yf == 0: those rows and weights, unchanged.  yf > 0:
+ *   q = y0 * 2048 + (y1 > y0 ? b1 : 0) + 8 * yf        (both rows clamped to one: the position is that row, fraction zero)
+ *   sy' = q >> 11,  b1' = q & 2047,  b0' = 2048 - b1',  frame rows yi + sy' and yi + sy' + 1 <= yi + bh <= height - 1
+ * Value.  Each channel is the integer entries' blend of the four taps t<row><column>,
+ *   h0 = t00 a0 + t01 a1,  h1 = t10 a0 + t11 a1,  clamp((((b0 (h0 >> 4)) >> 16) + ((b1 (h1 >> 4)) >> 16) + 2) >> 2, 0, 255)
+ * with the shifted weights.  For NV12 frames each tap is the converted pixel, its chroma index taken from frame coordinates.
+ * RGB, BGR and NV12 outputs are made from that RGB crop exactly as by svc_render_crops_to_layout.  oh == bh && ow == bw is NOT a
+ * copy here: it runs the same arithmetic on the identity table, a pure fractional shift.
+ * Consequence: with every origin a multiple of 256 the output is bit for bit that of svc_render_crops_to_layout (SVC_FILTER_LINEAR)
+ * with the boxes (xi, yi, xi + bw, yi + bh).
+ * Everything else is svc_render_crops_to_layout's, checked before any device work with the rule in svc_last_error(): the frames'
+ * layout rules; out_layout (required; one that holds the packed values runs the packed sinks); the colour rules; flags by the
+ * output format; the output contract (all picture bytes and no other byte); the read range [frames, frames + (n - 1) *
+ * frame_stride + extent) -- the column xi + bw is loaded only where the frame has it, the row yi + bh only where a phase above zero taps it; n == 0 is a
+ * successful no-op; origins_q8 == NULL with n > 0 is SVC_E_INVALID.  The LDS rule is the linear path's with one more staged column:
+ * 2 * span + D bytes, span = 3 (bw + 1) + 32 rounded up to 16, D as for the linear path; above 64 KiB the call is refused with the
+ * byte count.  Counts under SVC_K_RENDER.  No counterpart in the reference (its windows start on whole pixels). */
+int svc_render_windows_q8(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *in_colour,
+                          int n, int height, int width, const int32_t *origins_q8 /* [n][2]: x, y */, int bw, int bh,
+                          uint8_t *out, const SvcFrameLayout *out_layout, const SvcColour *out_colour,
+                          int oh, int ow, int flags, void *stream);
+
 /* frames_nhwc[n][h][w][3] u8 RGB (saliency size, e.g. 140x250) -> maps_nhw[n][h][w] u8.
  * Frame-major output; the reference's [h][w][n] view is a transpose done by the
  * caller only when someone asks for VD['smaps'].
@@ -461,7 +501,7 @@ int svc_host_boxes(const double *xs, const double *ys, int fc, int w_orig, int h
 #define SVC_K_CORE 9
 #define SVC_K_PRIM 10
 #define SVC_K_FINISH 11
-#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 / _u8_to_nv12 / _nv12_to_nv12 / _layout / _filter / _colour */
+#define SVC_K_RENDER 12    /* svc_render_crops_u8 / _nv12 / _u8_to_nv12 / _nv12_to_nv12 / _layout / _filter / _colour / _to_layout, svc_render_windows_q8 */
 #define SVC_K_BORDER 13    /* svc_border_profile_u8 (the fused form, svc_saliency_profile_u8, counts under SVC_K_SMOOTH) */
 #define SVC_K_COUNT 14
 int svc_profile_enable(SvcHandle *h, int kernel_class);

@@ -12,6 +12,7 @@
 //     k_render_copy_to_rgb_rows                      the first of them for a pitched output (groups per output row)
 //     k_render_copy_px<Src, Dst>                     the copy for everything they leave
 //     k_render_resize<Src, Dst>                      the resampled crop
+//     k_render_resize_q8<Src, Dst>                   the same at a window origin in 1/256 pixel (no counterpart: svc_render_windows_q8)
 //     k_render_lanczos<Src, Dst>                     the crop resampled as PIL.Image.resize(LANCZOS) does it (no counterpart: svc_render_crops_filter)
 //   SrcNv12          YUV -> RGB conversion fused into both (no counterpart: the reference is handed RGB)
 //   DstNv12          the same crops written as NV12, the forward transform fused in (no counterpart: the reference hands RGB to its writer)
@@ -825,7 +826,81 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_re
     Dst::rows_out(KO, lds, dst, ow);
 }
 
-// the argument checks of both render launchers (render_crops, render_crops_lanczos): plain comparisons, before any device work
+// Sub-pixel windows (svc_render_windows_q8; no counterpart in the reference, whose windows start on whole pixels): k_render_resize
+// with the window's top-left corner given in 1/256 pixel.  The origin is clamped to [0, (width - bw) * 256] x [0, (height - bh) *
+// 256] and split into a whole pixel (xi, yi) and a phase (xf, yf); a zero phase keeps the table's taps and weights, and a phase
+// above zero moves the position the table gives -- tap * 2048 + the 11-bit weight of the far tap, the fraction zero where the
+// table clamped it at the window's edge -- by 8 * phase, i.e. by phase / 256 pixel in units of 1 / 2048.  The position stays
+// <= bw - 1 (bh - 1), and a phase above zero means xi < width - bw (yi < height - bh), so the far tap xi + bw (yi + bh) is a
+// pixel of the frame; with a zero phase it is not tapped, and staged only where the frame has it.  Integers only; nothing is
+// built per call.
+__device__ __forceinline__ void render_origin_q8(const int32_t *__restrict__ origins, int f, int height, int width, int bh, int bw,
+                                                 int &xi, int &xf, int &yi, int &yf) {
+    const int X = (int)min(max((long long)origins[2 * f], 0ll), (long long)(width - bw) * 256);
+    const int Y = (int)min(max((long long)origins[2 * f + 1], 0ll), (long long)(height - bh) * 256);
+    xi = X >> 8; xf = X & 255;
+    yi = Y >> 8; yf = Y & 255;
+}
+
+// The structure, the sources, the sinks and the register cap are k_render_resize's.  What differs: the origin and the phases are
+// read once per workgroup (wave-uniform), a staged row holds min(bw + 1, width - xi) columns (the far column only where the
+// frame has it), and every row and column derives its taps from the shared table with a multiply-add, a shift and a mask.
+// LDS: two source rows of span_cap = 3 (bw + 1) + 32 (rounded up to 16) bytes, then Dst::lds_bytes.
+template <class Src, class Dst>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_render_resize_q8(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                       const int *__restrict__ tab, const int32_t *__restrict__ origins, int f0,
+                                                       int height, int width, int bh, int bw, int oh, int ow, int span_cap,
+                                                       const uint8_t *in_end, int vec, const typename Src::lay L, const typename Src::colour KI,
+                                                       const typename Dst::colour KO, const typename Dst::olay O) {
+    extern __shared__ __align__(16) uint8_t sm_rq[];
+    const CvLinear T(tab, oh, ow);
+    const int j = blockIdx.x, f = f0 + blockIdx.y;
+    int xi, xf, yi, yf;
+    render_origin_q8(origins, f, height, width, bh, bw, xi, xf, yi, yf);
+    const int ncols = min(bw + 1, width - xi);
+    const uint8_t *fr = in + f * L.template frame<Src>(height, width);
+    uint8_t *lds = sm_rq + 2 * span_cap, *dst[Dst::out_rows];
+    for (int r = 0; r < Dst::rows; ++r) {
+        int ry[2], b0, b1, sh[2];
+        T.row(Dst::rows * j + r, bh, ry[0], ry[1], b0, b1);
+        if (yf) {                                               // (both rows clamped to one: the table's position is that row)
+            const int q = ry[0] * 2048 + (ry[1] > ry[0] ? b1 : 0) + 8 * yf;
+            ry[0] = q >> 11;
+            ry[1] = ry[0] + 1;                                  // <= bh, and yi + bh is a row of the frame
+            b1 = q & 2047;
+            b0 = 2048 - b1;
+        }
+        if (r) __syncthreads();                                 // row 0's resampling has read the staged rows
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            sh[k] = Src::stage_row(fr, L, KI, height, width, yi + ry[k], xi, ncols, sm_rq + k * span_cap, span_cap, in_end, vec);
+        if (!r) Dst::dst_rows(O, out, blockIdx.y, oh, ow, j, dst);
+        uint8_t *orow = Dst::rgb_row(lds, dst, ow, r);
+        __syncthreads();
+        const uint8_t *r0 = sm_rq + sh[0], *r1 = sm_rq + span_cap + sh[1];
+        for (int ox = threadIdx.x; ox < ow; ox += 256) {
+            int sx, sx1, a0, a1;
+            bool inner;
+            T.col(ox, bw, sx, sx1, a0, a1, inner);
+            // selects on the wave-uniform phase, not a branch; xf > 0: sx1 <= bw = ncols - 1
+            const int p = sx * 2048 + a1 + 8 * xf, ps = p >> 11, pa = p & 2047;
+            sx = xf ? ps : sx;
+            sx1 = xf ? ps + 1 : sx1;
+            a1 = xf ? pa : a1;
+            a0 = xf ? 2048 - pa : a0;
+            // every column blends both taps: from xmax on the table holds sx = bw - 1, a0 = 2048 and a1 = 0 exactly (its fraction is
+            // set to zero there), so t00 * a0 + t01 * a1 IS the plain copy t00 * 2048 of the integer kernel, without its per-lane branch
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                orow[ox * 3 + (Dst::bgr ? 2 - c : c)] = CvLinear::blend(r0[sx * 3 + c], r0[sx1 * 3 + c], r1[sx * 3 + c], r1[sx1 * 3 + c],
+                                                                        a0, a1, b0, b1, true);
+        }
+    }
+    __syncthreads();
+    Dst::rows_out(KO, lds, dst, ow);
+}
+
+// the argument checks of the render launchers (render_crops, render_crops_lanczos, render_windows): plain comparisons, before any device work
 template <class Src, class Dst>
 static int render_args_check(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width,
                              const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags) {
@@ -886,6 +961,38 @@ static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, c
         const dim3 grid((unsigned)(oh / Dst::rows), (unsigned)std::min(n - f0, 65535));
         k_render_resize<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * O.template frame<Dst>(oh, ow), tab, boxes, f0, height, width,
                                                          bh, bw, oh, ow, span_cap, in_end, aligned_in, L, Src::col(C), Dst::col(C), O);
+        SVC_CHECK_LAUNCH();
+    }
+    return SVC_OK;
+}
+
+// render_crops for windows whose origins are given in 1/256 pixel (svc_render_windows_q8): always the resampling kernel, also at
+// oh == bh && ow == bw (the identity table: a pure fractional shift), with one more staged column in the LDS rule.
+template <class Src, class Dst>
+static int render_windows(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, const Colours &C, int n,
+                          int height, int width, const int32_t *origins_q8, int bw, int bh, uint8_t *out, const typename Dst::olay &O, int oh,
+                          int ow, int flags, void *stream) {
+    int rc = render_args_check<Src, Dst>(name, h, frames, n, height, width, origins_q8, bw, bh, out, oh, ow, flags);
+    if (rc) return rc;
+    const int span_cap = ((bw + 1) * 3 + 32 + 15) / 16 * 16;
+    const size_t lds = 2 * (size_t)span_cap + Dst::lds_bytes(ow);
+    if (lds > 65536) {
+        svc_set_error("%s: window %dx%d -> %dx%d needs %zu bytes of LDS per %s (> 64 KiB)", name, bw, bh, ow, oh, lds,
+                      Dst::rows == 1 ? "output row" : "pair of output rows");
+        return SVC_E_INVALID;
+    }
+    if (n == 0) return SVC_OK;
+    SVC_HIP(hipSetDevice(h->device));
+    const uint8_t *in_end = frames + (size_t)(n - 1) * L.template frame<Src>(height, width) + Src::extent(L, height, width);
+    const int vec = ((uintptr_t)frames & 15) == 0 && Src::vec_ok(L);
+    hipStream_t s = (hipStream_t)stream;
+    const int *tab = nullptr;
+    if ((rc = cv_tab(h, bh, bw, oh, ow, &tab))) return rc;
+    ProfScope ps(h, SVC_K_RENDER, s);
+    for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
+        const dim3 grid((unsigned)(oh / Dst::rows), (unsigned)std::min(n - f0, 65535));
+        k_render_resize_q8<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * O.template frame<Dst>(oh, ow), tab, origins_q8, f0, height, width,
+                                                            bh, bw, oh, ow, span_cap, in_end, vec, L, Src::col(C), Dst::col(C), O);
         SVC_CHECK_LAUNCH();
     }
     return SVC_OK;
@@ -1128,6 +1235,22 @@ static int render_crops_lanczos_fmt(const char *name, int pix_fmt, bool to_nv12,
         name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
 }
 
+// (the sub-pixel kernels exist for the Pitched source policy only, as the Lanczos ones: 2 sources x 3 sinks per output layout)
+template <class OLay>
+static int render_windows_fmt(const char *name, int pix_fmt, bool to_nv12, SvcHandle *h, const uint8_t *frames, const Pitched &L, const Colours &C,
+                              int n, int height, int width, const int32_t *origins_q8, int bw, int bh, uint8_t *out, const OLay &O, int oh, int ow,
+                              int flags, void *stream) {
+    const bool nv12 = pix_fmt == SVC_FMT_NV12;
+    if (to_nv12)
+        return (nv12 ? render_windows<SrcNv12<Pitched>, DstNv12<OLay>> : render_windows<SrcRgb<Pitched>, DstNv12<OLay>>)(
+            name, h, frames, L, C, n, height, width, origins_q8, bw, bh, out, O, oh, ow, flags, stream);
+    if (flags & SVC_RENDER_BGR)
+        return (nv12 ? render_windows<SrcNv12<Pitched>, DstRgb<true, OLay>> : render_windows<SrcRgb<Pitched>, DstRgb<true, OLay>>)(
+            name, h, frames, L, C, n, height, width, origins_q8, bw, bh, out, O, oh, ow, flags, stream);
+    return (nv12 ? render_windows<SrcNv12<Pitched>, DstRgb<false, OLay>> : render_windows<SrcRgb<Pitched>, DstRgb<false, OLay>>)(
+        name, h, frames, L, C, n, height, width, origins_q8, bw, bh, out, O, oh, ow, flags, stream);
+}
+
 extern "C" int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                    int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
     return render_crops_fmt("svc_render_crops_u8", SVC_FMT_RGB24, false, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
@@ -1231,10 +1354,11 @@ static int resize_frames_any(const char *name, SvcHandle *h, const uint8_t *fram
 // out_layout (svc_render_crops_to_layout; NULL for every other entry, whose output is packed and whose format is out_fmt): where
 // the bytes of the oh x ow output frames lie.  The pitched sinks are instantiated for this launcher only -- i.e. for the Pitched
 // source policy, all four kernels, 2 sources x 3 sinks -- and an out_layout that holds the packed values runs the packed sinks.
+// q8 (svc_render_windows_q8): `boxes` holds window origins [n][2] in 1/256 pixel, not boxes; every check above the launcher is shared.
 static int render_crops_any(const char *name, const char *linear_name, SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout,
                             const SvcColour *in_colour, int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out,
                             int out_fmt, const SvcFrameLayout *out_layout, const SvcColour *out_colour, int oh, int ow, int filter, int flags,
-                            void *stream) {
+                            void *stream, bool q8 = false) {
     if (filter == SVC_FILTER_LINEAR) name = linear_name;
     else if (filter != SVC_FILTER_LANCZOS) {
         svc_set_error("%s: unknown filter %d (SVC_FILTER_LINEAR or SVC_FILTER_LANCZOS)", name, filter);
@@ -1259,6 +1383,10 @@ static int render_crops_any(const char *name, const char *linear_name, SvcHandle
         (rc = colour_check(name, "out_colour", out_colour, to_nv12, mo, ro)))
         return rc;
     const Colours C = {COLOUR_DEC[mi][ri], COLOUR_ENC[mo][ro]};
+    if (q8) {                               // svc_render_windows_q8: `boxes` holds the origins [n][2] in 1/256 pixel, the filter is LINEAR
+        if (packed_out) return render_windows_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
+        return render_windows_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+    }
     if (filter == SVC_FILTER_LINEAR) {
         if (packed_out) return render_crops_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
         return render_crops_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
@@ -1315,4 +1443,19 @@ extern "C" int svc_render_crops_to_layout(SvcHandle *h, const uint8_t *frames, c
     }
     return render_crops_any(name, name, h, frames, layout, in_colour, n, height, width, boxes, bw, bh, out, 0, out_layout, out_colour, oh, ow,
                             filter, flags, stream);
+}
+
+// --------------------------------------------------------------------------------------
+// the same at sub-pixel window origins: INTER_LINEAR taps shifted by a per-frame phase (include/svc.h states the arithmetic)
+// --------------------------------------------------------------------------------------
+extern "C" int svc_render_windows_q8(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *in_colour,
+                                     int n, int height, int width, const int32_t *origins_q8, int bw, int bh, uint8_t *out,
+                                     const SvcFrameLayout *out_layout, const SvcColour *out_colour, int oh, int ow, int flags, void *stream) {
+    const char *name = "svc_render_windows_q8";
+    if (!out_layout) {
+        svc_set_error("%s: out_layout: layout is NULL", name);
+        return SVC_E_INVALID;
+    }
+    return render_crops_any(name, name, h, frames, layout, in_colour, n, height, width, origins_q8, bw, bh, out, 0, out_layout, out_colour, oh, ow,
+                            SVC_FILTER_LINEAR, flags, stream, true);
 }

@@ -473,6 +473,60 @@ class Engine:
         _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out), oh, ow, RENDER_BGR if bgr else 0, _stream()))
         return out
 
+    def render_windows(self, frames, origins_q8, win_wh, out_hw=None, bgr=False, out=None, pix_fmt='rgb24', out_fmt='rgb24', layout=None,
+                       colour=None, out_colour=None, out_layout=None):
+        """render_crops(interp='linear') at sub-pixel window origins (svc_render_windows_q8; include/svc.h states the arithmetic).
+        origins_q8: int32 CUDA tensor [n, 2], the top-left corner (x, y) of every frame's window in 1/256 pixel, clamped by the
+        kernel into the frame; win_wh = (bw, bh), one window size for all.  out_hw None is the window size -- not a copy here but
+        the window shifted by its fraction.  Origins that are multiples of 256 give the bytes of render_crops with the boxes
+        (x >> 8, y >> 8, + bw, + bh).  Every other argument is render_crops's, with its checks (ValueError / TypeError before any
+        device work)."""
+        _side_colour(colour, pix_fmt, 'colour')
+        _side_colour(out_colour, out_fmt if out_fmt in OUT_FMTS else 'nv12', 'out_colour')
+        n = int(frames.shape[0])
+        bw, bh = int(win_wh[0]), int(win_wh[1])
+        if bw < 1 or bh < 1:
+            raise ValueError('empty window %d x %d' % (bw, bh))
+        oh, ow = (bh, bw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        shape = (n,) + out_frame_shape(out_fmt, oh, ow, bgr)
+        if out_layout is not None:
+            if not isinstance(out_layout, FrameLayout):
+                raise TypeError('out_layout must be an ops.FrameLayout (ops.frame_layout(out_fmt, oh, ow, dict(pitch=...), frame_stride))')
+            shape = (n, out_layout_of(out_layout, out_fmt, oh, ow).frame_stride)
+        if not (torch.is_tensor(origins_q8) and origins_q8.dtype == torch.int32):
+            raise TypeError('origins_q8 must be a CUDA tensor of dtype torch.int32 (window origins in 1/256 pixel)')
+        if tuple(origins_q8.shape) != (n, 2):
+            raise ValueError('origins_q8 of shape %s for %d frames (int32 [n, 2]: x, y)' % (tuple(origins_q8.shape), n))
+        if layout is None:
+            _need_cuda(frames, torch.uint8, 'frames')
+            _, h, w = picture_size(frames, pix_fmt)
+        else:
+            _pitched(frames, layout, pix_fmt)
+            h, w = layout.h, layout.w
+        if bw > w or bh > h:
+            raise ValueError('a window of %d x %d does not fit the %d x %d picture' % (bw, bh, w, h))
+        _need_cuda(origins_q8, torch.int32, 'origins_q8')
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+        if out_layout is not None:
+            on = _pitched(out, out_layout, out_fmt, 'out')
+        else:
+            _need_cuda(out, torch.uint8, 'out')
+            on = int(out.shape[0])
+            if tuple(out.shape) != shape:
+                raise ValueError('out of shape %s, the output is %s' % (tuple(out.shape), shape))
+        if on != n:
+            raise ValueError('out holds %d frames, frames holds %d' % (on, n))
+        if not hasattr(self.lib, 'svc_render_windows_q8'):
+            raise _lib.SvcError('%s lacks svc_render_windows_q8: sub-pixel windows need a build that has it' % _lib.LIB_PATH)
+        colour, out_colour = _side_colour(colour, pix_fmt, 'colour'), _side_colour(out_colour, out_fmt, 'out_colour')
+        lay = (layout or frame_layout(pix_fmt, h, w)).struct()
+        olay = (out_layout or frame_layout(out_fmt, oh, ow)).struct()       # (the packed values run the packed sinks)
+        _lib.check(self.lib.svc_render_windows_q8(self._h, _ptr(frames), ctypes.byref(lay), _colour_struct(colour), n, h, w, _ptr(origins_q8),
+                                                  bw, bh, _ptr(out), ctypes.byref(olay), _colour_struct(out_colour), oh, ow,
+                                                  RENDER_BGR if bgr else 0, _stream()))
+        return out
+
     # -- saliency ------------------------------------------------------------------------
     def saliency(self, frames, out=None, threshold=0, census=None, profile=None):
         """uint8 [n,h,w,3] RGB at saliency size -> uint8 [n,h,w] maps (frame-major); `out`: write into this tensor.

@@ -37,7 +37,7 @@ def check_boxes(bbs, fc, h, w):
 
 
 def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, chunk=32, pix_fmt=None, out_fmt='rgb24', layout=None,
-                 interp='linear', colour=None, out_colour=None, out_layout=None):
+                 interp='linear', colour=None, out_colour=None, out_layout=None, subpixel=False):
     """Render VD['fc'] frames of `video` (the ingest_pickle dict, or its 'frames' container) at VD['bbs_np'].
     pix_fmt: the frames' format when `video` is a bare container (a dict brings its own 'pix_fmt'; default 'rgb24'); an
     unknown format, an NV12 picture of odd size or a container of another shape raise ValueError before any device work.
@@ -57,10 +57,19 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     chroma_pitch=) (frames their extent apart) or an ops.FrameLayout of the out_fmt picture of the final size; resolved once,
     against the final (oh, ow), and a broken rule or another format or size raises ValueError before any device work.  Chunks
     and the returned array are then uint8 [m, frame_stride]: the picture bytes are those of the call without it, every other
-    byte is 0 (svc_render_crops_to_layout writes the picture rows and nothing else, into slots that were allocated zeroed)."""
+    byte is 0 (svc_render_crops_to_layout writes the picture rows and nothing else, into slots that were allocated zeroed).
+    subpixel: render the windows at VD['bbs_q8'] -- their origins in 1/256 pixel, as sc_compute_bb keeps them from the smoothed
+    centres before the truncation -- instead of at the whole pixels of VD['bbs_np'], so that a crop delivered at an out_size follows
+    the smoothed pan without steps (svc_render_windows_q8; include/svc.h states the arithmetic; the window size stays that of
+    VD['bbs_np']).  Every other option as without it; without an out_size the window is shifted by its fraction.  With
+    interp='lanczos' (the phase is defined on the INTER_LINEAR taps), or a VD without 'bbs_q8': ValueError before any device work."""
     from .frames import FrameSource
     from .ops import check_interp, frame_colour
     check_interp(interp)
+    if subpixel and interp != 'linear':
+        raise ValueError("subpixel=True renders with interp='linear' (the phase shifts the INTER_LINEAR taps), not %r" % (interp,))
+    if subpixel and VD.get('bbs_q8') is None:
+        raise ValueError("subpixel=True needs VD['bbs_q8'] (sc_compute_bb sets it); this VD has none")
     src = FrameSource.of(video, pix_fmt, layout, colour).whole()       # (resolved and checked once)
     if out_colour is not None:
         out_colour = frame_colour(out_colour)
@@ -80,6 +89,11 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     out_layout = out_layout_of(out_layout, out_fmt, oh, ow)
     if out_layout is not None:
         shape = (out_layout.frame_stride,)
+    if subpixel:
+        q8 = np.asarray(VD['bbs_q8'])[:fc]
+        if q8.shape != (fc, 2) or q8.dtype.kind not in 'iu':
+            raise ValueError("VD['bbs_q8'] holds integer origins [fc, 2] (x, y in 1/256 pixel), not %s %s" % (q8.dtype, q8.shape))
+        q8 = np.clip(q8, -2 ** 31, 2 ** 31 - 1).astype(np.int32)          # (the kernel clamps into the frame)
     chunk = max(1, min(int(chunk), _MAX_CHUNK, _RING_BYTES // int(np.prod(shape))))       # (the real bytes per frame)
     result = None
     if sink is None:
@@ -94,8 +108,8 @@ def render_video(video, VD, engine=None, out_size=None, bgr=False, sink=None, ch
     from . import smartVidCrop as S
     engine = engine or S.get_engine()
     dev = engine.device
-    boxes = torch.from_numpy(np.ascontiguousarray(VD['bbs_np'][:fc], np.int32)).to(dev)
-    out = _OutRing(engine, chunk, oh, ow, sink, out_fmt, src.pix_fmt, src.layout, interp, src.colour, out_colour, out_layout)
+    boxes = torch.from_numpy(np.ascontiguousarray(q8 if subpixel else VD['bbs_np'][:fc], np.int32)).to(dev)      # subpixel: the origins
+    out = _OutRing(engine, chunk, oh, ow, sink, out_fmt, src.pix_fmt, src.layout, interp, src.colour, out_colour, out_layout, subpixel)
     src.chunks(engine, fc, chunk, lambda staged, s: out.push(staged, boxes[s:s + staged.shape[0]], bw, bh, bgr))
     out.flush()
     return result
@@ -106,7 +120,7 @@ class _OutRing:
     copied D2H on a side stream into pinned slot c & 1, and handed to the sink once the copy of chunk c + 1 is enqueued."""
 
     def __init__(self, engine, cap, oh, ow, sink, out_fmt='rgb24', pix_fmt='rgb24', layout=None, interp='linear', colour=None, out_colour=None,
-                 out_layout=None):
+                 out_layout=None, subpixel=False):
         import torch
         from .ops import frame_shape
         self.engine, self.sink, self.dev, self.out_fmt = engine, sink, engine.device, out_fmt
@@ -114,6 +128,7 @@ class _OutRing:
         self.interp = interp
         self.colour, self.out_colour = colour, out_colour       # of nv12 frames pushed / of an nv12 output (None: BT.601 limited)
         self.out_layout = out_layout                            # of the output frames (None: packed)
+        self.subpixel = subpixel                                # push() is handed origins [m, 2] in 1/256 pixel, not boxes
         key = (cap, oh, ow, out_fmt) if out_layout is None else (cap, oh, ow, out_fmt, out_layout.key())
         # slots shaped (and keyed) by the output format -- and by the output layout: [cap, frame_stride], allocated zeroed, and
         # the kernels write picture bytes only, so what is delivered is 0 outside the picture for as long as the slots live
@@ -147,8 +162,12 @@ class _OutRing:
         if self.used[slot]:
             compute.wait_event(self.copied[slot])           # the device slot's previous D2H has read it
         dst = self.ring['dev'][slot][:m]
-        self.engine._render(staged, boxes, bw, bh, dst, bgr, self.pix_fmt, self.out_fmt, self.layout, self.interp, self.colour, self.out_colour,
-                            self.out_layout)
+        if self.subpixel:
+            self.engine.render_windows(staged, boxes, (bw, bh), (int(self.ring['key'][1]), int(self.ring['key'][2])), bgr, dst, self.pix_fmt,
+                                       self.out_fmt, self.layout, self.colour, self.out_colour, self.out_layout)
+        else:
+            self.engine._render(staged, boxes, bw, bh, dst, bgr, self.pix_fmt, self.out_fmt, self.layout, self.interp, self.colour, self.out_colour,
+                                self.out_layout)
         self.rendered[slot].record(compute)
         with torch.cuda.stream(side):
             side.wait_event(self.rendered[slot])

@@ -206,9 +206,15 @@ def sc_border_detection(crop_params, vid_data, verbose=False, engine=None):
 
 
 def sc_compute_bb(vid_data, crop_params, verbose=False):
-    """smartVidCrop.py:979-1048: centres (saliency-map pixels) -> [x1,y1,x2,y2] per frame (native: svc_host_boxes)."""
+    """smartVidCrop.py:979-1048: centres (saliency-map pixels) -> [x1,y1,x2,y2] per frame (native: svc_host_boxes).
+    Beside what the reference sets, VD['bbs_q8'] (int64 [fc, 2]) keeps the window origins in 1/256 pixel, taken from the smoothed
+    centres BEFORE they are truncated: X = floor(dxs / scale_w * 256) - hbbw1 * 256 clamped to [border_l * 256, (w_orig - border_r -
+    fbb_w) * 256] (the reference's order: the upper clamp last), Y likewise; bbs_q8 >> 8 == bbs_np[:, :2] on every frame.  What
+    render_video(subpixel=True) renders; no counterpart in the reference, whose windows start on whole pixels."""
     fc = vid_data['fc']
     borders = tuple(vid_data.get(k, 0) for k in ('border_t', 'border_b', 'border_l', 'border_r'))
+    cx = np.asarray(vid_data['dxs'][:fc], np.float64) / (float(vid_data['w_process']) / float(vid_data['w_orig']))
+    cy = np.asarray(vid_data['dys'][:fc], np.float64) / (float(vid_data['h_process']) / float(vid_data['h_orig']))
     boxes, ctr, fbb_w, fbb_h = temporal.boxes(vid_data['dxs'][:fc], vid_data['dys'][:fc], vid_data['w_orig'], vid_data['h_orig'],
                                               vid_data['w_process'], vid_data['h_process'], vid_data['w_final'],
                                               vid_data['h_final'], borders)
@@ -217,6 +223,12 @@ def sc_compute_bb(vid_data, crop_params, verbose=False):
     vid_data['dys'][:fc] = ctr[:, 1].tolist()
     vid_data['fbb_w'], vid_data['fbb_h'] = fbb_w, fbb_h
     vid_data['bbs_np'] = boxes                         # int64 [fc, 4]: what the multi-video job gathers (dist.crop_job)
+    bt, bb, bl, br = (int(v) for v in borders)
+    hw1, hh1 = int(fbb_w / 2.0), int(fbb_h / 2.0)      # hbbw1, hbbh1 (:1018-1021)
+    q8 = np.stack([np.floor(cx * 256.0) - hw1 * 256.0, np.floor(cy * 256.0) - hh1 * 256.0], 1)
+    lo = np.array([bl, bt], np.float64) * 256.0
+    hi = np.array([int(vid_data['w_orig']) - br - fbb_w, int(vid_data['h_orig']) - bb - fbb_h], np.float64) * 256.0
+    vid_data['bbs_q8'] = np.minimum(np.maximum(np.nan_to_num(q8), lo), hi).astype(np.int64).reshape(fc, 2)
     if isinstance(vid_data, _LazySmaps):
         dict.pop(vid_data, 'bbs', None)                # the list-of-lists form (the reference's VD['bbs']) is made on first access
     else:
@@ -543,7 +555,7 @@ class _LazySmaps(dict):
 def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn='', frames_dir='',
                    temp_path=None, verbose=False, save_vid=True, callback_progress=None,
                    callback_session=None, callback_status=None, copy_sound=False, engine=None, shot_net=None, stream_batch=0,
-                   out_size=None, out_pix_fmt='rgb24', out_interp='linear', out_colour=None, out_layout=None):
+                   out_size=None, out_pix_fmt='rgb24', out_interp='linear', out_colour=None, out_layout=None, out_subpixel=False):
     """Saliency -> crop windows for one video.  Returns (VD, smart_crop_results) like the
     reference; VD['bbs'] holds one [x1,y1,x2,y2] per decoded frame.  A video dict without ``trans_inds`` takes the
     reference's video path: ``shot_net`` (transnetv1_handler.ShotTransNet) detects the shots inside the ingest.
@@ -573,6 +585,9 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         extra layout=<the resolved ops.FrameLayout> keyword; without an out_layout the call stays without it.  A broken layout,
         or one of another format or size, raises ValueError before the writer is opened -- with an out_size before any work;
         the pickle mode with a layout raises ValueError (ingest.write_frames_raw refuses one too: a raw file is packed).
+        out_subpixel: both modes render the windows at their sub-pixel origins VD['bbs_q8'] (render.render_video(subpixel=True)):
+        a crop written at an out_size follows the smoothed pan without the steps of whole-pixel windows.  With
+        out_interp='lanczos' it raises ValueError before any work.  VD and the results are the same either way.
     demo_fn (the five-panel demo) and copy_sound (ffmpeg) with a render raise NotImplementedError."""
     import torch
     sc_init_time()
@@ -588,6 +603,9 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
     from .ops import DEFAULT_COLOUR, FrameLayout, check_interp, frame_colour, out_frame_shape, out_layout_of
     out_frame_shape(out_pix_fmt, *((2, 2) if out_size is None else (out_size[1], out_size[0])))     # unknown format, odd out_size: ValueError
     check_interp(out_interp)
+    if out_subpixel and out_interp != 'linear':
+        raise ValueError("out_subpixel renders with out_interp='linear' (the phase shifts the INTER_LINEAR taps), not %r" % (out_interp,))
+    sub = dict(subpixel=True) if out_subpixel else {}          # (the renderer's call stays the one it was without it)
     if out_colour is not None:
         out_colour = frame_colour(out_colour)
         if out_pix_fmt == 'rgb24':
@@ -673,7 +691,7 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         from . import render
         t = time.perf_counter()
         if render_pkl:                  # the reference's pickle mode (:1821-1825, :1890-1896, :2151-2154): BGR crops, native size
-            crops = render.render_video(video, VD, engine=engine, bgr=True)
+            crops = render.render_video(video, VD, engine=engine, bgr=True, **sub)
             with open(video_path.replace('.pkl', '_sc.pkl'), 'wb') as fp:
                 pickle.dump(list(crops), fp)
         else:
@@ -691,7 +709,7 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
             writer = _video_writer(final_vid_fn, VD['fr'], size, **kw)
             try:
                 render.render_video(video, VD, engine=engine, out_size=size, sink=lambda chunk: [writer.write(f) for f in chunk],
-                                    out_fmt=out_pix_fmt, interp=out_interp, out_colour=out_colour, out_layout=out_layout)
+                                    out_fmt=out_pix_fmt, interp=out_interp, out_colour=out_colour, out_layout=out_layout, **sub)
             finally:
                 writer.release()
         sc_register_time(t, 'render')
