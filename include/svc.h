@@ -87,7 +87,7 @@ const char *svc_last_error(void);
  *     a binding finds the entry by its symbol (dlsym), not by the revision.  Likewise svc_debug_net_plan (SVC_PLAN_*), and
  *     SvcColour with svc_resize_frames_colour and svc_render_crops_colour (NV12 colour): a new struct and two new entries; and
  *     svc_render_crops_to_layout (pitched output): one new entry that takes the existing SvcFrameLayout, unchanged, for the output; and
- *     svc_render_windows_q8 (sub-pixel windows): one new entry, no struct. */
+ *     svc_render_windows_q8 (sub-pixel windows): one new entry, no struct; and svc_debug_tail_plan (SVC_TAILPLAN_*): one new test door. */
 #define SVC_ABI_VERSION 12
 int svc_abi_version(void);
 
@@ -666,6 +666,36 @@ int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int width, con
 #define SVC_PLAN_FR_LDS_MAX 17
 #define SVC_PLAN_WORDS 18
 int svc_debug_net_plan(int height, int width, int32_t *out, int cap);
+/* Test/diagnostic door: what svc_cluster_center plans for maps of height x width with `params` on this handle, and the compile-time
+ * thresholds by which its kernels choose a form per map at run time -- host arithmetic, nothing is launched and the handle is not
+ * changed: out[0 .. SVC_TAILPLAN_WORDS) = the SVC_TAILPLAN_* words below.  The plan is made for the shape the tail clusters on
+ * (SVC_TAILPLAN_H x SVC_TAILPLAN_W: the map shrunk by resize_factor when the cluster filter is on) and for the handle's tail form
+ * (environment SVC_PRIM_LVL / SVC_TREE_PAR / SVC_TAIL_MERGE when it was created).  With these words, a map's point list and
+ * its condensed-cluster count, the path of every map through k_core and the hierarchy kernels is determined; the frame header
+ * (SVC_HDR_*) records which one it took (tests/tail_paths.py predicts it, tests/test_gpu_tail_paths.py compares).
+ * Returns SVC_TAILPLAN_WORDS.  SVC_E_INVALID: h, params or out NULL, cap below SVC_TAILPLAN_WORDS, whatever svc_cluster_center
+ * refuses of the shape and of params (struct_size, hdbscan_min, resize_factor, a map that shrinks to nothing). */
+#define SVC_TAILPLAN_H 0                  /* the shape the tail clusters on                                              */
+#define SVC_TAILPLAN_W 1
+#define SVC_TAILPLAN_FUSED 2              /* 1: a round is k_tail_front + k_tail_back (0: one launch per stage)             */
+#define SVC_TAILPLAN_LVL_BIG 3            /* 1: k_prim_lvl_big is launched (a map may have more than LVL_CAP points)        */
+#define SVC_TAILPLAN_TREE_FALLBACK 4      /* 1: k_tree and k_finish are launched behind (a map may be left to them)         */
+#define SVC_TAILPLAN_CAP_CL 5             /* condensed clusters k_tree_par's tables hold, maps of up to TP_CAP_BIG points   */
+#define SVC_TAILPLAN_CAP_CL_HUGE 6        /* ... maps of more points                                                        */
+#define SVC_TAILPLAN_LVL_CAP 7            /* points: k_prim_lvl up to here, k_prim_lvl_big beyond                           */
+#define SVC_TAILPLAN_TP_CAP 8             /* points: k_tree_par with everything in LDS up to here                           */
+#define SVC_TAILPLAN_TP_CAP_BIG 9         /* ... with the per-edge arrays partly in the workspace up to here, wholly beyond */
+#define SVC_TAILPLAN_TREE_LDS_CAP 10      /* points: k_tree tries its LDS form up to here                                   */
+#define SVC_TAILPLAN_TREE_LDS_CLUSTERS 11 /* condensed clusters that form holds (more: k_tree retries in global memory)     */
+#define SVC_TAILPLAN_N_RING 12            /* neighbour offsets within RING_R (k_core phase 2 scans them)                    */
+#define SVC_TAILPLAN_N_RING1 13           /* ... within RING_R1 (phase 1 walks them)                                        */
+#define SVC_TAILPLAN_RING_R 14            /* radius of the ring table: a point with its k-th neighbour beyond goes to phase 3 */
+#define SVC_TAILPLAN_RING_R1 15           /* radius of phase 1                                                              */
+#define SVC_TAILPLAN_CORE_REG_STEP 16     /* phase 3 in registers: one form per this many points (4 forms) ...              */
+#define SVC_TAILPLAN_CORE_REG_MAX 17      /* ... for maps of up to this many points                                         */
+#define SVC_TAILPLAN_CORE_LDS_MAX 18      /* the largest N for which phase 3 keeps the points in LDS (beyond: global loop)  */
+#define SVC_TAILPLAN_WORDS 19
+int svc_debug_tail_plan(const SvcHandle *h, int height, int width, const SvcParams *params, int32_t *out, int cap);
 /* SVC_TAP_INPUT with the fused front kernel (the default): the input is written to memory only by handles created
  * with SVC_KEEP_INPUT=1 in the environment; otherwise the call fails with SVC_E_INVALID.
  * svc_front_fused: 1 when the last svc_saliency_u8 call ran LANCZOS + features.0 + features.1 as one kernel

@@ -42,6 +42,8 @@ static_assert(TB % 64 == 0 && (NW16 & (NW16 - 1)) == 0 && NW16 >= 4 && NW16 <= 1
               "the tail kernels need 4, 8 or 16 wavefronts per workgroup");
 #define RING_R 20               // ring table radius for core distances
 #define RING_R1 4                // radius walked by the one-thread-per-point phase
+#define CORE_REG_STEP 512        // k_core phase 3 in registers: 8, 16, 24 or 32 distances per lane, one form per 512 points ...
+#define CORE_REG_MAX (4 * CORE_REG_STEP)   // ... for maps of up to this many points
 #define DEPTH_SLOT 4096          // maps per svc_cluster_center call
 #define REACH_INF 0x1FFFFu      // > any squared distance on a <=256x256 grid (17 bits)
 
@@ -353,6 +355,9 @@ __global__ __launch_bounds__(TB) void k_compact(TailArgs A) { compact_body(A); }
 //  3. points with fewer than k neighbours within RING_R: wave-wide bisection on the count
 //     of points within distance t over all N points.
 // --------------------------------------------------------------------------------------
+// the largest N for which phase 3 keeps the points' coordinates (2 bytes each) in LDS, over the occupancy map and the ring table
+__host__ __device__ inline int core_lds_max_points(int hw, int n_ring) { return (int)(((size_t)(hw + 15) / 16 * 16 + (size_t)n_ring * 4) / 2); }
+
 // k_core phase 3, maps of up to 64 * NI points: the smallest t with #{d2 <= t} >= k + 1 (self included) for the point (r, c),
 // by bisection over the point's distances to all N points held in registers (NI per lane)
 template <int NI>
@@ -508,7 +513,7 @@ __device__ __forceinline__ void core_body(const TailArgs &A) {
     // phase 3 counts over all points many times: their coordinates go to LDS (over the occupancy map and the ring
     // table, which are no longer needed) when they fit
     uint16_t *rcl = (uint16_t *)sm_core;
-    const bool in_lds = (size_t)N * 2 <= (size_t)(hw + 15) / 16 * 16 + (size_t)A.n_ring * 4;
+    const bool in_lds = N <= core_lds_max_points(hw, A.n_ring);
     if (in_lds) {
         for (int j = threadIdx.x; j < N; j += TB) rcl[j] = (uint16_t)(pts[j] & 0xFFFFu);
         __syncthreads();
@@ -519,8 +524,9 @@ __device__ __forceinline__ void core_body(const TailArgs &A) {
         const uint32_t v = pts[p];
         const int r = v & 255, c = (v >> 8) & 255;
         uint32_t lo = RING_R * RING_R + 1, hi = maxd;         // smallest t with #{d2 <= t} >= k+1 (self included)
-        if (in_lds && N <= 64 * 32) {
+        if (in_lds && N <= CORE_REG_MAX) {
             // all N distances of this point in registers (8, 16, 24 or 32 per lane), the bisection then touches no memory
+            static_assert(CORE_REG_STEP == 64 * 8, "the four register forms hold 8, 16, 24 and 32 distances per lane");
             const int ni = (N + 63) >> 6;
             const uint32_t ans = ni <= 8 ? core_kth_regs<8>(rcl, N, r, c, k, lo, hi) : ni <= 16 ? core_kth_regs<16>(rcl, N, r, c, k, lo, hi)
                                : ni <= 24 ? core_kth_regs<24>(rcl, N, r, c, k, lo, hi) : core_kth_regs<32>(rcl, N, r, c, k, lo, hi);
@@ -2816,8 +2822,8 @@ static int upload_map_tab(DevBuf &buf, int h, int w, int oh, int ow, double sy, 
 
 #define RC_TAIL(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
-static int ensure_ring(SvcHandle *h) {
-    if (h->tail_n_offsets) return SVC_OK;
+// the neighbour offsets within RING_R, sorted by distance: (dr + 128) | (dc + 128) << 8 | d2 << 16
+static std::vector<uint32_t> ring_offsets() {
     std::vector<uint32_t> v;
     for (int dr = -RING_R; dr <= RING_R; ++dr)
         for (int dc = -RING_R; dc <= RING_R; ++dc) {
@@ -2826,13 +2832,23 @@ static int ensure_ring(SvcHandle *h) {
             v.push_back((uint32_t)(dr + 128) | ((uint32_t)(dc + 128) << 8) | ((uint32_t)d2 << 16));
         }
     std::stable_sort(v.begin(), v.end(), [](uint32_t x, uint32_t y) { return (x >> 16) < (y >> 16); });
+    return v;
+}
+static int ring_offsets_within(const std::vector<uint32_t> &v, int radius) {
+    int n = 0;
+    for (uint32_t x : v) n += (int)((x >> 16) <= (uint32_t)(radius * radius));
+    return n;
+}
+
+static int ensure_ring(SvcHandle *h) {
+    if (h->tail_n_offsets) return SVC_OK;
+    const std::vector<uint32_t> v = ring_offsets();
     int rc = h->tail_offsets.ensure(v.size() * 4);
     if (rc) return rc;
     SVC_HIP(hipMemcpy(h->tail_offsets.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
     h->tail_offsets_host = v;
     h->tail_n_offsets = (int)v.size();
-    h->tail_n_offsets1 = 0;
-    for (uint32_t x : v) h->tail_n_offsets1 += (int)((x >> 16) <= RING_R1 * RING_R1);
+    h->tail_n_offsets1 = ring_offsets_within(v, RING_R1);
     std::vector<uint16_t> cnt(RING_R * RING_R + 1, 0);       // offsets with d2 <= m, for k_prim_lvl's discs
     for (uint32_t x : v) ++cnt[x >> 16];
     for (size_t m = 1; m < cnt.size(); ++m) cnt[m] = (uint16_t)(cnt[m] + cnt[m - 1]);
@@ -2895,6 +2911,12 @@ extern "C" int svc_debug_round_plan(const uint8_t *flags_host, int n, int32_t *r
     for (int i = 0; i < n; ++i) { round_out[i] = depth[i] == 255 ? -1 : depth[i]; blend0_out[i] = 0; any = any || depth[i] != 255; }
     for (uint16_t i : blend0) blend0_out[i] = 1;
     return any ? maxd + 1 : 0;
+}
+
+// the size cv2.resize gives a map with fx = fy = 1 / factor (cvRound, half to even)
+static void shrunk_size(int height, int width, int factor, int *rs_h, int *rs_w) {
+    *rs_h = (int)lrint((double)height * (1.0 / factor));
+    *rs_w = (int)lrint((double)width * (1.0 / factor));
 }
 
 // ---- svc_cluster_center, step by step: argument checks, shrink tables, round list and its upload, launches
@@ -3081,8 +3103,8 @@ static int cluster_center_impl(SvcHandle *h, uint8_t *maps, int n, int height, i
     // both of the size cv2.resize gives fx = fy = 1 / factor (cvRound, half to even).  cv2.resize refuses an empty size, so a
     // map that shrinks to nothing is an error whenever one of the two would shrink it (smartVidCrop.py:1080, :1184).
     const int full_h = height, full_w = width;
-    const int rs_h = (int)lrint((double)full_h * (1.0 / params->resize_factor));
-    const int rs_w = (int)lrint((double)full_w * (1.0 / params->resize_factor));
+    int rs_h, rs_w;
+    shrunk_size(full_h, full_w, params->resize_factor, &rs_h, &rs_w);
     if (params->resize_factor > 1 && (params->clust_filt || params->com_km) && (rs_h < 1 || rs_w < 1)) {
         svc_set_error("svc_cluster_center: map %dx%d too small for resize_factor %d", full_h, full_w, params->resize_factor);
         return SVC_E_INVALID;
@@ -3143,6 +3165,36 @@ static int cluster_center_impl(SvcHandle *h, uint8_t *maps, int n, int height, i
         SVC_CHECK_LAUNCH();
     }
     return SVC_OK;
+}
+
+// Test door (no launch): the plan of a call and the thresholds of the kernels' run-time forms (include/svc.h: SVC_TAILPLAN_*)
+extern "C" int svc_debug_tail_plan(const SvcHandle *h, int height, int width, const SvcParams *params, int32_t *out, int cap) {
+    if (!out || cap < SVC_TAILPLAN_WORDS) { svc_set_error("svc_debug_tail_plan: invalid argument"); return SVC_E_INVALID; }
+    uint8_t none = 0;
+    double nowhere = 0;
+    RC_TAIL(check_cluster_args(const_cast<SvcHandle *>(h), &none, 1, height, width, params, &nowhere));     // (the checks read neither buffer)
+    if (params->clust_filt && params->resize_factor > 1) {
+        int rs_h, rs_w;
+        shrunk_size(height, width, params->resize_factor, &rs_h, &rs_w);
+        if (rs_h < 1 || rs_w < 1) {
+            svc_set_error("svc_debug_tail_plan: map %dx%d too small for resize_factor %d", height, width, params->resize_factor);
+            return SVC_E_INVALID;
+        }
+        height = rs_h;
+        width = rs_w;
+    }
+    const std::vector<uint32_t> ring = ring_offsets();
+    const TailPlan T = plan_tail(h, params, height, width);
+    out[SVC_TAILPLAN_H] = height; out[SVC_TAILPLAN_W] = width;
+    out[SVC_TAILPLAN_FUSED] = T.fused; out[SVC_TAILPLAN_LVL_BIG] = T.lvl_big; out[SVC_TAILPLAN_TREE_FALLBACK] = T.tree_fallback;
+    out[SVC_TAILPLAN_CAP_CL] = T.cap_cl; out[SVC_TAILPLAN_CAP_CL_HUGE] = T.cap_cl_huge;
+    out[SVC_TAILPLAN_LVL_CAP] = LVL_CAP; out[SVC_TAILPLAN_TP_CAP] = TP_CAP; out[SVC_TAILPLAN_TP_CAP_BIG] = TP_CAP_BIG;
+    out[SVC_TAILPLAN_TREE_LDS_CAP] = TREE_LDS_CAP; out[SVC_TAILPLAN_TREE_LDS_CLUSTERS] = TREE_LDS_CLUSTERS;
+    out[SVC_TAILPLAN_N_RING] = (int32_t)ring.size(); out[SVC_TAILPLAN_N_RING1] = ring_offsets_within(ring, RING_R1);
+    out[SVC_TAILPLAN_RING_R] = RING_R; out[SVC_TAILPLAN_RING_R1] = RING_R1;
+    out[SVC_TAILPLAN_CORE_REG_STEP] = CORE_REG_STEP; out[SVC_TAILPLAN_CORE_REG_MAX] = CORE_REG_MAX;
+    out[SVC_TAILPLAN_CORE_LDS_MAX] = core_lds_max_points(height * width, (int)ring.size());
+    return SVC_TAILPLAN_WORDS;
 }
 
 // SVC_HOST_TIMING=1: the call's host-side duration goes to stderr (every 100 calls; every call above 2 ms) -- a call is

@@ -21,6 +21,10 @@ NODE_F4X, NODE_F2X = 107, 114
 PLAN_WORDS = ('NH', 'NW', 'hks', 'vks', 'fr_ok', 'fr_nr', 'fr_nc', 'fr_tiles_y', 'fr_tiles_x', 'lz_tile_cap', 'lz_lds', 'sd_rows',
               'sd_tile_cap', 'sd_lds', 'fr_lds', 'lz_lds_max', 'sd_lds_max', 'fr_lds_max')
 
+# words of svc_debug_tail_plan (include/svc.h: SVC_TAILPLAN_*), in order
+TAIL_PLAN_WORDS = ('h', 'w', 'fused', 'lvl_big', 'tree_fallback', 'cap_cl', 'cap_cl_huge', 'LVL_CAP', 'TP_CAP', 'TP_CAP_BIG', 'TREE_LDS_CAP',
+                   'TREE_LDS_CLUSTERS', 'n_ring', 'n_ring1', 'RING_R', 'RING_R1', 'CORE_REG_STEP', 'CORE_REG_MAX', 'core_lds_max')
+
 # words of a frame header, cluster_state(...)['hdr'] (include/svc.h: SVC_HDR_*, the same numbers; a range is its first word and a count)
 HDR_WORDS = 32
 HDR_N, HDR_NSEL, HDR_KEPT, HDR_CLUSTERED, HDR_NCLUSTERS = 0, 1, 2, 3, 4
@@ -617,6 +621,19 @@ class Engine:
             self._h, _ptr(maps), n, h, w, flags.ctypes.data_as(ctypes.c_void_p) if flags is not None else None,
             ctypes.byref(p), _ptr(xy), _ptr(stats) if want_stats else None, _stream()))
         return (xy, stats) if want_stats else xy
+
+    def tail_plan(self, h, w, CP):
+        """Test door (svc_debug_tail_plan): what cluster_center_ plans for maps of h x w with CP on this engine, and the thresholds
+        by which the tail's kernels choose a form per map, as a dict of TAIL_PLAN_WORDS ('h', 'w': the shape the tail clusters
+        on, after resize_factor).  Host arithmetic of the library: nothing is launched."""
+        if not hasattr(self.lib, 'svc_debug_tail_plan'):
+            raise _lib.SvcError('%s lacks svc_debug_tail_plan: the plan door of the tail needs a build that has it' % _lib.LIB_PATH)
+        p = _lib.make_params(CP)
+        out = (ctypes.c_int32 * len(TAIL_PLAN_WORDS))()
+        n = _lib.check(self.lib.svc_debug_tail_plan(self._h, int(h), int(w), ctypes.byref(p), ctypes.cast(out, ctypes.c_void_p), len(TAIL_PLAN_WORDS)))
+        if n != len(TAIL_PLAN_WORDS):
+            raise _lib.SvcError('svc_debug_tail_plan reports %d words, this binding knows %d' % (n, len(TAIL_PLAN_WORDS)))
+        return dict(zip(TAIL_PLAN_WORDS, (int(v) for v in out)))
 
     # -- measurement door (bench.py) -------------------------------------------------------
     KERNEL_CLASSES = ('resize', 'lanczos', 'stem', 'pw', 'dw', 'resample', 'smooth', 'threshold', 'compact',

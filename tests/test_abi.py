@@ -143,6 +143,23 @@ def test_transnet_tap_door_constants_and_argument_checks():
     assert _lib.load().svc_debug_transnet_tap(None, None, 1, 4, 0, 4, 0, out, 4) == -1
 
 
+def test_tail_plan_door_checks_its_arguments():
+    """svc_debug_tail_plan (no ABI bump): without a handle, without an output or with too few words the call is refused with
+    SVC_E_INVALID and a message, before anything is read."""
+    from retargetvid_amd import ops
+    from oracle import pipeline_ref as P
+    lib = _lib.load()
+    p = _lib.make_params(P.init_crop_params())
+    n = len(ops.TAIL_PLAN_WORDS)
+    out = (ctypes.c_int32 * n)()
+    vp = ctypes.c_void_p
+    assert lib.svc_debug_tail_plan(None, 140, 250, ctypes.byref(p), ctypes.cast(out, vp), n) == -1 and b'invalid argument' in lib.svc_last_error()
+    assert lib.svc_debug_tail_plan(None, 140, 250, ctypes.byref(p), None, n) == -1 and b'svc_debug_tail_plan' in lib.svc_last_error()
+    assert lib.svc_debug_tail_plan(None, 140, 250, ctypes.byref(p), ctypes.cast(out, vp), n - 1) == -1
+    text = open(os.path.join(ROOT, 'include', 'svc.h')).read()
+    assert int(re.search(r'#define SVC_TAILPLAN_WORDS (\d+)', text).group(1)) == n
+
+
 def test_frame_header_words_are_the_headers():
     """The words of svc_debug_cluster_state's frame header: every SVC_HDR_* of include/svc.h is ops.HDR_* with the same number,
     neither side has a name the other lacks, and the named words and ranges lie side by side inside the header."""

@@ -19,7 +19,8 @@ from oracle import hdbscan_ref as H
 SMALL, BIRTH, SPLIT, ABS_A, ABS_B = range(5)      # ABS_A: the a (left) side is the big one, the right side falls out
 
 
-def labels_path(u, v, w, order, mcs):
+def labels_path(u, v, w, order, mcs, with_nc=False):
+    """with_nc: -> (labels, condensed clusters = births + splits: what the kernel stores in SVC_HDR_NCLUSTERS)."""
     n = len(w) + 1
     E = n - 1
     seq = np.concatenate([[u[0]], v])
@@ -114,7 +115,7 @@ def labels_path(u, v, w, order, mcs):
             labels[seq[i]] = rep if w[e] <= cminw[root] else -1
         else:
             labels[seq[i]] = rep
-    return labels
+    return (labels, nc) if with_nc else labels
 
 
 def same_partition(a, b):
