@@ -87,7 +87,8 @@ const char *svc_last_error(void);
  *     a binding finds the entry by its symbol (dlsym), not by the revision.  Likewise svc_debug_net_plan (SVC_PLAN_*), and
  *     SvcColour with svc_resize_frames_colour and svc_render_crops_colour (NV12 colour): a new struct and two new entries; and
  *     svc_render_crops_to_layout (pitched output): one new entry that takes the existing SvcFrameLayout, unchanged, for the output; and
- *     svc_render_windows_q8 (sub-pixel windows): one new entry, no struct; and svc_debug_tail_plan (SVC_TAILPLAN_*): one new test door. */
+ *     svc_render_windows_q8 (sub-pixel windows): one new entry, no struct; and svc_debug_tail_plan (SVC_TAILPLAN_*): one new test door; and
+ *     SVC_NODE_MAP / SVC_NODE_MAP_PROFILE: two new node ids of svc_debug_run_node, which an older library refuses as unknown. */
 #define SVC_ABI_VERSION 12
 int svc_abi_version(void);
 
@@ -620,6 +621,15 @@ int svc_debug_tap(SvcHandle *h, int which, int frame, float *out_host, size_t ca
  *                              ([NH/16][NW/16][128] / [NH/8][NW/8][64]) -> [NH/16][NW/16][128] / [NH/8][NW/8][64]
  *   SVC_NODE_ADAPT             in0 [NH/8][NW/8][64] -> logits [NH/8][NW/8]
  *   SVC_NODE_SMOOTH            in0 = logits -> the pre-softmax map [height][width]
+ *   SVC_NODE_MAP               in0 = logits -> [2][height][width]: plane 0 the pre-softmax map (the bytes of SVC_NODE_SMOOTH), plane 1
+ *                              the uint8 saliency map's values as floats.  What a pass runs behind the adaptation, in one run: the
+ *                              per-frame maxima cleared, the smoothing, then the quantising kernel with threshold 0, no census
+ *                              rows and no profile rows into a uint8 buffer of the door's own.
+ *   SVC_NODE_MAP_PROFILE       the same with scratch profile rows, so that the kernel of svc_saliency_profile_u8 writes the map.
+ *                              A uint8 has no spare value for "not written", so the quantising kernel is launched twice on the one
+ *                              pre-softmax map, into a buffer filled with 0x00 and into one filled with 0xFF: a byte that differs
+ *                              between the two was not written and comes back as the NaN pattern below.  Both buffers end in 256
+ *                              guard bytes of their fill; a guard byte that changed makes the call fail with SVC_E_HIP.
  * Before the node runs, its output buffer and the scratch buffers of the pass are filled with a NaN bit pattern (all ones):
  * whatever the node's kernels do not write -- the other half of a row included -- comes back as that.  Returns the floats
  * per frame of the output.  SVC_E_INVALID, with nothing launched: an unknown node, n outside 1..SVC_CHUNK, in0 (or a
@@ -636,6 +646,8 @@ int svc_debug_tap(SvcHandle *h, int which, int frame, float *out_host, size_t ca
 #define SVC_NODE_POST_US2 23
 #define SVC_NODE_ADAPT 24
 #define SVC_NODE_SMOOTH 25
+#define SVC_NODE_MAP 26
+#define SVC_NODE_MAP_PROFILE 27
 #define SVC_NODE_FULL 100                /* + 7 / 14: the full-resolution output of that block */
 #define SVC_NODE_F4X (SVC_NODE_FULL + 7)
 #define SVC_NODE_F2X (SVC_NODE_FULL + 14)

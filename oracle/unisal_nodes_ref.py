@@ -206,6 +206,8 @@ class NodeRef:
             return y, F.interpolate(y, size=tuple(out_hw), mode='bilinear', align_corners=False)[:, 0].numpy()
 
         y, v = run(np.ascontiguousarray(logit, np.float64), self.k41)
+        if not self.bounds:                                              # the value alone: half the convolutions
+            return v, 0.0
         _, e1 = run(np.abs(logit), np.abs(self.k41))                      # the convolution's terms through the blend
         e2 = F.interpolate(y.abs(), size=tuple(out_hw), mode='bilinear', align_corners=False)[:, 0].numpy()   # the blend's own
         return v, e1 + e2

@@ -16,25 +16,14 @@
 
 void svc_set_error(const char *fmt, ...);
 
-// Division of a 31-bit index by a launch-invariant divisor as multiply + shift (a runtime integer
-// division costs ~40 VALU instructions on gfx950, more than the arithmetic of most element-wise
-// kernels here).  Exact for n < 2^31, 1 <= d < 2^16.
-struct FDiv {
-    uint64_t m;
-    uint32_t d;
-    int s;
-};
-static inline FDiv make_fdiv(uint32_t d) {
-    FDiv f;
-    f.d = d;
-    int l = 0;
-    while ((1u << l) < d) ++l;
-    f.s = 32 + l;
-    f.m = (((uint64_t)1 << f.s) + d - 1) / d;
-    return f;
-}
+// Division of a 31-bit index by a launch-invariant divisor as multiply + shift: FDiv, make_fdiv and the expression fdiv_q live in
+// svc_fdiv.h (no HIP dependency; the tests build it on the host).  Exact for every n < 2^31 and every divisor a launch here uses
+// (1 <= d <= 2^31: k_quantise divides by h * w, 106 496 at 416x256 and 518 400 at 540x960); wrong for n >= 2^31, where the
+// 64-bit product wraps.  The launcher of k_quantise does not assert n * h * w < 2^31: a handle's chunk (SVC_CHUNK) has
+// no upper limit, so the assertion could fire on a call that is accepted today (a default chunk of 32 maps of 540x960 is 2^24).
+#include "svc_fdiv.h"
 #ifdef __HIPCC__
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FDiv &f) { return (uint32_t)(((uint64_t)n * f.m) >> f.s); }
+__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FDiv &f) { return fdiv_q(n, f.m, f.s); }
 __device__ __forceinline__ uint32_t fdivmod(uint32_t n, const FDiv &f, uint32_t &rem) {
     const uint32_t q = fdiv(n, f);
     rem = n - q * f.d;

@@ -2992,11 +2992,13 @@ extern "C" int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int
         case SVC_NODE_US2: ib = B_PC; ipx = px5; ich = 256; cat = B_CAT2; i1px = 4 * px5; i1ch = 128; ob = B_U2; opx = 4 * px5; och = 128; break;
         case SVC_NODE_POST_US2: ib = B_U2; ipx = 4 * px5; ich = 128; cat = B_CAT3; i1px = 16 * px5; i1ch = 64; ob = B_DEC; opx = 16 * px5; och = 64; break;
         case SVC_NODE_ADAPT: ib = B_DEC; ipx = 16 * px5; ich = 64; ob = B_LOGIT; opx = 16 * px5; och = 1; break;
-        case SVC_NODE_SMOOTH: ib = B_LOGIT; ipx = 16 * px5; ich = 1; ob = B_PRE; opx = (size_t)height * width; och = 1; break;
+        case SVC_NODE_SMOOTH: case SVC_NODE_MAP: case SVC_NODE_MAP_PROFILE:
+            ib = B_LOGIT; ipx = 16 * px5; ich = 1; ob = B_PRE; opx = (size_t)height * width; och = 1; break;
         default: svc_set_error("svc_debug_run_node: unknown node %d", node); return SVC_E_INVALID;
     }
     if (cat >= 0 && !in1_host) { svc_set_error("svc_debug_run_node: node %d needs its skip input", node); return SVC_E_INVALID; }
-    const size_t count = opx * och;
+    const bool map_node = node == SVC_NODE_MAP || node == SVC_NODE_MAP_PROFILE;     // out = two planes: PRE, the map as floats
+    const size_t count = opx * och * (map_node ? 2 : 1);
     if (count * n > cap_floats) { svc_set_error("svc_debug_run_node: buffer too small (%zu needed)", count * n); return SVC_E_INVALID; }
     SVC_HIP(hipSetDevice(h->device));
     RC(build_plan(h, height, width, n));
@@ -3010,6 +3012,11 @@ extern "C" int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int
     p->gauss_filled = 0;                    // the prior channels of CAT1 may hold the fill or the caller's values now
     p->last_n = 0;                          // the workspace is no pass's any more (svc_debug_tap)
     struct Owned : DevBuf { ~Owned() { release(); } } frames;      // the front's uint8 input: freed on every way out
+    // SVC_NODE_MAP / _MAP_PROFILE: the map is quantised twice from the one PRE, into two buffers of the door's own filled with 0x00
+    // and with 0xFF -- a byte that was written is the same in both, one that was not differs.  Each buffer ends in MAP_GUARD
+    // bytes of fill that must survive.  The profile variant max-combines into zeroed scratch rows.
+    const size_t MAP_GUARD = 256, map_bytes = (size_t)n * height * width;
+    Owned map_a, map_b, map_prof;
     int rc = SVC_OK;
     if (node == SVC_NODE_FRONT) {
         SVC_HIP(fill(B_P0));
@@ -3039,13 +3046,54 @@ extern "C" int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int
                                    p->buf(B_DEC), n);
                 break;
             case SVC_NODE_ADAPT: rc = tail_adapt(h, s, n, 4 * h5, 4 * w5); break;
-            default:                        // SVC_NODE_SMOOTH: the per-frame maxima k_adapt clears in a pass
+            default:                        // SVC_NODE_SMOOTH, _MAP, _MAP_PROFILE: the per-frame maxima k_adapt clears in a pass
                 SVC_HIP(hipMemsetAsync(p->fmax.p, 0, (size_t)n * sizeof(unsigned), s));
                 rc = tail_smooth(h, s, n, 4 * h5, 4 * w5);
+                if (!rc && map_node) {      // ... and what the pass runs behind it, thr = 0, no census rows
+                    unsigned *prof = nullptr;
+                    RC(map_a.ensure(map_bytes + MAP_GUARD));
+                    RC(map_b.ensure(map_bytes + MAP_GUARD));
+                    SVC_HIP(hipMemsetAsync(map_a.p, 0x00, map_bytes + MAP_GUARD, s));
+                    SVC_HIP(hipMemsetAsync(map_b.p, 0xFF, map_bytes + MAP_GUARD, s));
+                    if (node == SVC_NODE_MAP_PROFILE) {
+                        const size_t pb = (size_t)n * (height + width) * sizeof(unsigned);
+                        RC(map_prof.ensure(pb));
+                        SVC_HIP(hipMemsetAsync(map_prof.p, 0, pb, s));
+                        prof = (unsigned *)map_prof.p;
+                    }
+                    rc = tail_quantise(h, s, n, (uint8_t *)map_a.p, 0, nullptr, prof);
+                    if (!rc) rc = tail_quantise(h, s, n, (uint8_t *)map_b.p, 0, nullptr, prof);
+                }
                 break;
         }
     }
     if (!rc && hipDeviceSynchronize() != hipSuccess) { svc_set_error("svc_debug_run_node: node %d failed on the device", node); rc = SVC_E_HIP; }
+    if (!rc && map_node) {                  // per frame: plane 0 = PRE, plane 1 = the map's values, the fill where a byte was not written
+        std::vector<float> pre(map_bytes);
+        std::vector<uint8_t> a(map_bytes + MAP_GUARD), b(map_bytes + MAP_GUARD);
+        if (hipMemcpy(pre.data(), p->buf(ob), map_bytes * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(a.data(), map_a.p, a.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(b.data(), map_b.p, b.size(), hipMemcpyDeviceToHost) != hipSuccess) {
+            svc_set_error("svc_debug_run_node: copying the output failed");
+            return SVC_E_HIP;
+        }
+        for (size_t i = 0; i < MAP_GUARD; ++i)
+            if (a[map_bytes + i] != 0x00 || b[map_bytes + i] != 0xFF) {
+                svc_set_error("svc_debug_run_node: node %d wrote past the end of its map (guard byte %zu)", node, i);
+                return SVC_E_HIP;
+            }
+        for (int f = 0; f < n; ++f) {
+            float *o = out_host + (size_t)f * count;
+            memcpy(o, pre.data() + (size_t)f * opx, opx * sizeof(float));
+            for (size_t i = 0; i < opx; ++i) {
+                const size_t j = (size_t)f * opx + i;
+                const float v = (float)a[j];
+                const uint32_t fill = 0xFFFFFFFFu;
+                memcpy(o + opx + i, a[j] == b[j] ? (const void *)&v : (const void *)&fill, sizeof(float));
+            }
+        }
+        return (int)count;
+    }
     if (!rc && hipMemcpy(out_host, p->buf(ob), count * n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
         svc_set_error("svc_debug_run_node: copying the output failed");
         rc = SVC_E_HIP;

@@ -15,6 +15,7 @@ TAP_INPUT, TAP_FEAT4X, TAP_FEAT2X, TAP_FEAT1X, TAP_POSTCNN, TAP_DEC, TAP_PRE = r
 # nodes of svc_debug_run_node (include/svc.h: SVC_NODE_*); backbone block idx = 2 .. 17 is node idx
 NODE_FRONT, NODE_F18, NODE_SKIP_2X, NODE_SKIP_4X, NODE_POST_CNN, NODE_US2, NODE_POST_US2, NODE_ADAPT, NODE_SMOOTH = 1, 18, 19, 20, 21, 22, 23, 24, 25
 NODE_F4X, NODE_F2X = 107, 114
+NODE_MAP, NODE_MAP_PROFILE = 26, 27     # logits -> [2, h, w]: the pre-softmax map and the uint8 map's values (k_quantise / k_quantise_profile)
 
 
 # words of svc_debug_net_plan (include/svc.h: SVC_PLAN_*), in order
@@ -586,7 +587,8 @@ class Engine:
     def run_node(self, node, n, height, width, in0, in1=None, out_shape=None):
         """Test door (svc_debug_run_node): one node of the network on the caller's host arrays -- fp32 NHWC of n frames (uint8
         frames for NODE_FRONT) -- for saliency maps of height x width.  -> fp32 [n, *out_shape] (out_shape: the per-frame shape
-        of the node's output buffer; include/svc.h lists them).  What the node did not write comes back as NaN."""
+        of the node's output buffer; include/svc.h lists them -- (2, height, width) for NODE_MAP / NODE_MAP_PROFILE: the
+        pre-softmax map and the uint8 map's values as floats).  What the node did not write comes back as NaN."""
         vp = ctypes.c_void_p
         in0 = np.ascontiguousarray(in0, np.uint8 if node == NODE_FRONT else np.float32)
         in1 = None if in1 is None else np.ascontiguousarray(in1, np.float32)

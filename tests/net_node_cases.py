@@ -15,7 +15,7 @@ FILL = 0xFFFFFFFF                         # svc_debug_run_node's fill: a NaN bit
 # nodes of the exact cases and of the per-element gate (all but 'smooth' and 'front', which have gates of their own)
 MAIN_NODES = [n for n in N.NODES if n not in ('front', 'smooth')]
 DEV_NODE = dict({'block%d' % i: i for i in range(2, 18)}, front=1, f18=18, skip_2x=19, skip_4x=20, post_cnn=21, us2=22, post_us2=23,
-                adapt=24, smooth=25, f4x=107, f2x=114)
+                adapt=24, smooth=25, map=26, map_profile=27, f4x=107, f2x=114)
 
 
 def node_io(node, NH, NW, h, w):
@@ -35,7 +35,9 @@ def node_io(node, NH, NW, h, w):
             'us2': ((H5, W5, 256), (H4, W4, 128), (H4, W4, 128), slice(0, 128)),
             'post_us2': ((H4, W4, 128), (H3, W3, 64), (H3, W3, 64), slice(0, 64)),
             'adapt': ((H3, W3, 64), None, (H3, W3), None),
-            'smooth': ((H3, W3), None, (h, w), None)}[node]
+            'smooth': ((H3, W3), None, (h, w), None),
+            'map': ((H3, W3), None, (2, h, w), None),               # plane 0: PRE, plane 1: the uint8 map's values
+            'map_profile': ((H3, W3), None, (2, h, w), None)}[node]
 
 
 def run_device(eng, node, n, h, w, NH, NW, in0, in1=None):

@@ -143,6 +143,30 @@ def test_transnet_tap_door_constants_and_argument_checks():
     assert _lib.load().svc_debug_transnet_tap(None, None, 1, 4, 0, 4, 0, out, 4) == -1
 
 
+def test_node_door_ids_are_the_headers_and_the_door_checks_its_arguments():
+    """svc_debug_run_node: every SVC_NODE_* number of include/svc.h is ops.NODE_* and the tests' name table (net_node_cases.DEV_NODE),
+    the two map nodes (26, 27; no ABI bump) included, and neither side has a name the other lacks; a call without a handle is refused."""
+    from retargetvid_amd import ops
+    import net_node_cases as C
+    text = open(os.path.join(ROOT, 'include', 'svc.h')).read()
+    ids = {k: int(v) for k, v in re.findall(r'#define SVC_NODE_([A-Z0-9_]+) (\d+)', text)}
+    full = ids.pop('FULL')
+    ids.update(F4X=full + 7, F2X=full + 14)
+    assert re.search(r'#define SVC_NODE_F4X \(SVC_NODE_FULL \+ 7\)', text) and re.search(r'#define SVC_NODE_F2X \(SVC_NODE_FULL \+ 14\)', text)
+    assert ids == {k[5:]: v for k, v in vars(ops).items() if k.startswith('NODE_')}
+    assert (ids['MAP'], ids['MAP_PROFILE']) == (26, 27) == (ids['SMOOTH'] + 1, ids['SMOOTH'] + 2)
+    named = {k.lower(): v for k, v in ids.items()}
+    named.update({'block%d' % i: i for i in range(2, 18)})
+    assert named == C.DEV_NODE
+    for node in ('map', 'map_profile'):
+        assert C.node_io(node, 256, 416, 140, 250) == ((32, 52), None, (2, 140, 250), None)
+    out = (ctypes.c_float * 4)()
+    lib = _lib.load()
+    for node in (25, 26, 27, 28):
+        assert lib.svc_debug_run_node(None, node, 1, 140, 250, ctypes.cast(out, ctypes.c_void_p), None, ctypes.cast(out, ctypes.c_void_p), 4) == -1
+        assert b'svc_debug_run_node: invalid argument' in lib.svc_last_error()
+
+
 def test_tail_plan_door_checks_its_arguments():
     """svc_debug_tail_plan (no ABI bump): without a handle, without an output or with too few words the call is refused with
     SVC_E_INVALID and a message, before anything is read."""

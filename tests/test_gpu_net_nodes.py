@@ -225,3 +225,17 @@ def test_the_door_refuses_invalid_arguments(engines):
         eng.run_node(ops.NODE_US2, 1, 140, 250, np.zeros((1, 8, 13, 256), np.float32), None, (16, 26, 128))
     with pytest.raises(Exception, match='too small'):
         eng.run_node(ops.NODE_F18, 1, 140, 250, x, None, (8, 13, 1280))
+    # the map nodes (26, 27): the ids behind them are still unknown, and they need room for both planes
+    logit = np.zeros((1, 32, 52), np.float32)
+    for node in (28, 29, 0, -1):
+        with pytest.raises(Exception, match='unknown node'):
+            eng.run_node(node, 1, 140, 250, logit, None, (2, 140, 250))
+    for node in (ops.NODE_MAP, ops.NODE_MAP_PROFILE):
+        with pytest.raises(Exception, match='too small'):
+            eng.run_node(node, 1, 140, 250, logit, None, (140, 250))
+        with pytest.raises(Exception, match='frames'):
+            eng.run_node(node, 0, 140, 250, logit, None, (2, 140, 250))
+        with pytest.raises(Exception, match='frames'):
+            eng.run_node(node, 33, 140, 250, np.zeros((33, 32, 52), np.float32), None, (2, 140, 250))
+        got = eng.run_node(node, 1, 140, 250, logit, None, (2, 140, 250))
+        assert got.shape == (1, 2, 140, 250) and (got[0, 0] == 0.0).all() and (got[0, 1] == 255.0).all(), node
