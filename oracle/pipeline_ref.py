@@ -12,7 +12,8 @@ cluster choice, focus stability, Savitzky-Golay instead of LOESS) is restated to
 
 Quirks reproduced on purpose: the off-by-one that leaves the last
 selected frame of every read batch with an all-zero map (:696-709), the batch-local
-after-cut test (:683), the u8 wrap in the cut blend (:2371-2373).
+after-cut test (:683), the u8 wrap in the cut blend (:2371-2373), and the pickle door's
+map array that is enlarged in place and scatters the maps it holds (:700-703, hold_maps).
 """
 import numpy as np
 
@@ -74,6 +75,40 @@ def scenes_from_trans_inds(trans_inds, frame_count):
     return np.array(scenes, dtype=np.int32)
 
 
+def maps_estimate(frame_count, skip):
+    """How many maps ingest_pickle makes room for before it reads a frame (:594-599, :604)."""
+    fcs = sum(1 for i in range(frame_count) if i % skip == 0 or i == 0 or i == frame_count - 1)
+    return fcs + int(frame_count * 0.1)
+
+
+def hold_maps(maps_of_batch, batches, sal_h, sal_w, frame_count, skip):
+    """The map array as ingest_pickle keeps it (:604, :696-709, :734).  maps_of_batch(first, count) -> uint8 [h, w, count]: the
+    network's maps of `count` selected frames from `first` on.  Two quirks are restated:
+
+      * the last selected frame of every read batch is never sent to the network (frames[:process_ind], :708-709);
+      * when a batch ends with as many selected frames as the estimate made room for (or more), the array is enlarged with
+        ndarray.resize (:700-703).  That keeps the BYTES in place and lays [H, W, n + 100] over them: every map stored by an
+        earlier batch is scattered over the new maps.  A video of one read batch regrows before anything is stored (harmless);
+        one of several short batches with a cut quirk's extra frame per batch (:683) does not.
+
+    -> (uint8 [h, w, n_sel], True if stored maps were scattered)."""
+    smaps = np.zeros((sal_h, sal_w, maps_estimate(frame_count, skip)), np.uint8)
+    scattered, stored = False, False
+    n_sel = 0
+    for first, cnt in batches:
+        n_sel = first + cnt
+        ei = n_sel - 1
+        if ei + 1 >= smaps.shape[2]:
+            grown = np.zeros(sal_h * sal_w * (ei + 100), np.uint8)
+            grown[:smaps.size] = smaps.reshape(-1)
+            smaps = grown.reshape(sal_h, sal_w, ei + 100)
+            scattered = scattered or stored
+        if cnt > 1:
+            smaps[:, :, first:ei] = maps_of_batch(first, cnt - 1)
+            stored = True
+    return np.ascontiguousarray(smaps[:, :, :n_sel]), scattered
+
+
 def ingest(video, CP, sd, stage=None):
     """video: dict(fr, frame_count, w, h, frames[RGB u8], trans_inds) -> VD dict."""
     fr, frame_count, w, h = video['fr'], video['frame_count'], video['w'], video['h']
@@ -82,14 +117,15 @@ def ingest(video, CP, sd, stage=None):
     true_inds, map2orig, batches = select_frames(len(frames_full), frame_count, list(video['trans_inds']),
                                                  CP['skip'], CP['read_batch'])
     n_sel = len(true_inds)
-    smaps = np.zeros((sal_h, sal_w, n_sel), np.uint8)
-    for first, cnt in batches:
-        if cnt > 1:                                # the last selected frame of a batch is never sent
-            idx = true_inds[first:first + cnt - 1]
-            small = np.stack([cv_ref.resize_linear_u8(frames_full[g], sal_h, sal_w) for g in idx])
-            if stage is not None:
-                stage.setdefault('sal_frames', []).append(small)
-            smaps[:, :, first:first + cnt - 1] = unisal_ref.saliency_u8(sd, small)
+
+    def maps_of_batch(first, count):               # the last selected frame of a batch is never sent
+        small = np.stack([cv_ref.resize_linear_u8(frames_full[g], sal_h, sal_w) for g in true_inds[first:first + count]])
+        if stage is not None:
+            stage.setdefault('sal_frames', []).append(small)
+        return unisal_ref.saliency_u8(sd, small)
+    smaps, scattered = hold_maps(maps_of_batch, batches, sal_h, sal_w, frame_count, CP['skip'])
+    if stage is not None:
+        stage['maps_scattered'] = scattered
     seg = scenes_from_trans_inds(list(video['trans_inds']), frame_count)
     seg_sel = np.array([[map2orig[v] for v in row] for row in seg], dtype=np.int32)
     return dict(smaps=smaps, segmentation=seg, segmentation_sel=seg_sel, true_inds=true_inds,
@@ -176,15 +212,23 @@ def crop_from_maps(VD, CP, stage=None):
     if stage is not None:
         stage['centres_raw'] = (list(dx), list(dy))
     VD['dx'], VD['dy'] = temporal_ref.handle_empty_centers(dx, dy, VD['segmentation_sel'])
+    VD['jumps'], VD['jumps_inds'] = [255] * len(VD['dx']), []                   # (:2425-2426)
+    if stage is not None:
+        stage['centres_filled'] = (list(VD['dx']), list(VD['dy']))              # dxnf / dynf (:2450-2451)
     if CP['focus_stability']:
         VD['dx'], VD['dy'], VD['jumps'], VD['jumps_inds'] = temporal_ref.focus_stability(
             VD['dx'], VD['dy'], VD['smaps'], VD['fr'], CP)
+    if stage is not None:
+        stage['centres_stab'] = (list(VD['dx']), list(VD['dy']))
+        stage['jumps'], stage['jumps_inds'] = list(VD['jumps']), list(VD['jumps_inds'])
     VD['dxi'], VD['dyi'] = temporal_ref.interpolate_centres(VD['dx'], VD['dy'], VD['segmentation'],
                                                             VD['segmentation_sel'], VD['true_inds'])
     VD['dxs'], VD['dys'] = temporal_ref.smoothing(VD['dxi'], VD['dyi'], VD['segmentation'], VD['fr'], CP)
     VD['bbs'], VD['fbb_w'], VD['fbb_h'] = tail_ref.compute_bb(
         VD['dxs'], VD['dys'], VD['fc'], VD['w_orig'], VD['h_orig'], VD['w_process'], VD['h_process'],
         VD['w_final'], VD['h_final'])
+    if stage is not None:
+        stage['bbs_pre'] = [list(b) for b in VD['bbs']]                         # before sc_shift_time
     if CP['shift_time'] > 0:
         temporal_ref.shift_time(VD['bbs'], CP['shift_time'])
     return VD

@@ -14,55 +14,16 @@ matplotlib ...).  Nothing at test, bench or smoke time imports this file, and th
 
 Run from the repo root:  python tools/make_golden_border.py <directory of the reference's smartVidCrop.py>"""
 import contextlib
-import importlib.util
 import io
 import os
 import sys
-import types
 
 import numpy as np
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ref_import_svc import load_reference  # noqa: E402  (the stubbed import of the reference: tools/ref_import_svc.py)
+
 FC = 16
-
-
-class _Any:
-    def __init__(self, *a, **k):
-        pass
-
-    def __call__(self, *a, **k):
-        return _Any()
-
-    def __getattr__(self, n):
-        return _Any()
-
-
-def load_reference(ref_dir):
-    for name in ('cv2', 'ffmpeg', 'hdbscan', 'imutils', 'imutils.video', 'tensorflow', 'transnetv1_handler', 'unisal_handler',
-                 'matplotlib', 'matplotlib.pyplot', 'sklearn', 'sklearn.cluster', 'scipy', 'scipy.signal', 'scipy.interpolate',
-                 'pyloess'):
-        if name in sys.modules:
-            continue
-        try:
-            __import__(name)
-        except Exception:
-            sys.modules[name] = types.ModuleType(name)
-    cv2 = sys.modules['cv2']
-    if not hasattr(cv2, 'getTickCount'):
-        cv2.getTickCount, cv2.getTickFrequency = (lambda: 0), (lambda: 1.0)
-    tf = sys.modules['tensorflow']
-    if not hasattr(tf, 'Session'):
-        tf.GPUOptions = tf.Session = tf.ConfigProto = _Any
-    th = sys.modules['transnetv1_handler']
-    th.ShotTransNetParams = th.ShotTransNet = _Any
-    sys.modules['unisal_handler'].init_unisal_for_images = lambda: None
-    iv = sys.modules['imutils.video']
-    if not hasattr(iv, 'FileVideoStream'):
-        iv.FileVideoStream = iv.FPS = object
-    spec = importlib.util.spec_from_file_location('ref_svc', os.path.join(ref_dir, 'smartVidCrop.py'))
-    m = importlib.util.module_from_spec(spec)
-    with contextlib.redirect_stdout(io.StringIO()):
-        spec.loader.exec_module(m)
-    return m
 
 
 # process size, original size: the ratios 360/140, 640/250, 1080/141, 2160/250, 480/166 ... are not integers, so the float order
