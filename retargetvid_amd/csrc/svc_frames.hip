@@ -390,7 +390,7 @@ static int cv_tab(SvcHandle *h, int height, int width, int sh, int sw, const int
         int rc = buf.ensure(tab.size() * 4);
         if (rc) return rc;
         SVC_HIP(hipMemcpy(buf.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-        it = h->cvtabs.emplace(key, buf).first;
+        it = h->cvtabs.emplace(key, std::move(buf)).first;
     }
     *out = (const int *)it->second.p;
     return SVC_OK;
@@ -1143,7 +1143,7 @@ static int lz_upload(ResampleTab &t) {
     rc = c.ensure(t.coeff_host.size() * 4);
     if (rc) return rc;
     SVC_HIP(hipMemcpy(c.p, t.coeff_host.data(), t.coeff_host.size() * 4, hipMemcpyHostToDevice));
-    t.coeff = c;
+    t.coeff = std::move(c);
     std::vector<int>().swap(t.coeff_host);
     return SVC_OK;
 }

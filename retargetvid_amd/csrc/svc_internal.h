@@ -7,14 +7,14 @@
 #include <string.h>
 
 #include <map>
+#include <memory>
 #include <set>
 #include <string>
 #include <tuple>
 #include <vector>
 
 #include "../../include/svc.h"
-
-void svc_set_error(const char *fmt, ...);
+#include "svc_devbuf.h"      // DevBuf, ResampleTab; declares svc_set_error
 
 // Division of a 31-bit index by a launch-invariant divisor as multiply + shift: FDiv, make_fdiv and the expression fdiv_q live in
 // svc_fdiv.h (no HIP dependency; the tests build it on the host).  Exact for every n < 2^31 and every divisor a launch here uses
@@ -83,31 +83,6 @@ struct NetGraph {
     SvcLayer adapt, smooth;               // adaptation 64 -> 1; the smoothing kernel's phase table (w only)
 };
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t need) {
-        if (need <= bytes) return SVC_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        hipError_t e = hipMalloc(&p, need);
-        if (e != hipSuccess) { svc_set_error("hipMalloc(%zu) failed: %s", need, hipGetErrorString(e)); return SVC_E_NOMEM; }
-        bytes = need;
-        return SVC_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-
-// Fixed-point resampling tables for one (in, out) size pair, device resident.
-struct ResampleTab {
-    int ksize = 0;
-    DevBuf bounds;    // int32[out][2]  (first, count)
-    DevBuf coeff;     // int32[out][ksize]
-    int max_span = 0; // max over blocks of rows spanned (host-computed helper)
-    std::vector<int> bounds_host;
-    std::vector<int> coeff_host;      // until the first upload (a table is built and checked on the host before any device work)
-};
-
 struct NetPlan;     // svc_net.hip
 
 struct SvcHandle {
@@ -117,7 +92,7 @@ struct SvcHandle {
     NetGraph net = {};                    // the layers by name (svc_net.hip: fill_graph)
     std::vector<float> gauss_params;      // coarse_gaussians_salicon [16][2][2]
     // network workspace + plan (svc_net.hip)
-    NetPlan *plan = nullptr;
+    std::unique_ptr<NetPlan> plan;
     // ingest resize tables keyed by (in_h, in_w, out_h, out_w)
     std::map<std::tuple<int, int, int, int>, DevBuf> cvtabs;
     // the renderer's LANCZOS tables keyed by the (in, out) size of one axis (svc_frames.hip: lz_tab; never rewritten)
@@ -163,6 +138,7 @@ struct SvcHandle {
     int prof_class = -1;
     hipStream_t prof_cal_stream = nullptr;      // a stream of the handle's own for the empty-event-pair calibration of svc_profile_read
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
+    ~SvcHandle();                      // svc_net.hip, where NetPlan is complete
 };
 
 // Records an event pair around the launches in its scope when the class is being profiled.
@@ -180,5 +156,3 @@ static inline int raise_lds_limit(SvcHandle *h, const void *kfn, int bytes) {
     if (h->lds_attr_done.insert(kfn).second) SVC_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     return SVC_OK;
 }
-
-int svc_net_release(SvcHandle *h);

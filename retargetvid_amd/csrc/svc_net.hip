@@ -1405,8 +1405,8 @@ static void net_geometry(int height, int width, int sd_rows_max, NetGeom &g, LzT
 }
 
 static int build_plan(SvcHandle *h, int height, int width, int nb) {
-    NetPlan *p = h->plan;
-    if (!p) p = h->plan = new NetPlan();
+    if (!h->plan) h->plan.reset(new NetPlan());
+    NetPlan *p = h->plan.get();
     if (p->h == height && p->w == width && p->nb >= nb) return SVC_OK;
     const bool same_size = (p->h == height && p->w == width);
     NetGeom geom;
@@ -1510,19 +1510,13 @@ static int build_plan(SvcHandle *h, int height, int width, int nb) {
     return SVC_OK;
 }
 
-int svc_net_release(SvcHandle *h) {
-    if (h->plan) {
-        NetPlan *p = h->plan;
-        p->ws.release(); p->fmax.release(); p->lut.release(); p->gauss.release();
-        p->hb.release(); p->hk.release(); p->vb.release(); p->vk.release(); p->fr_vt.release(); p->fr_ht.release();
-        delete p;
-        h->plan = nullptr;
-    }
-    for (auto &kv : h->cvtabs) kv.second.release();
-    h->cvtabs.clear();
-    for (auto &kv : h->lztabs) { kv.second.bounds.release(); kv.second.coeff.release(); }
-    h->lztabs.clear();
-    return SVC_OK;
+// The raw HIP objects the handle owns; the plan, every DevBuf member and every map of them then free themselves.
+SvcHandle::~SvcHandle() {
+    (void)hipSetDevice(device);
+    for (auto &e : prof_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    if (prof_cal_stream) (void)hipStreamDestroy(prof_cal_stream);
+    for (auto &e : depth_ev) if (e) (void)hipEventDestroy(e);
+    if (depth_pinned) (void)hipHostFree(depth_pinned);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1586,7 +1580,7 @@ static int weight_copy(SvcHandle *h, hipStream_t s, WForm form, const float *Wt,
         else k_x3_weights<<<blocks256(cells), 256, 0, s>>>(Wt, ldw, K, Q, tiles, Npad, form, (uint4 *)b.p);
         SVC_CHECK_LAUNCH();
         SVC_HIP(hipStreamSynchronize(s));
-        it = h->w_copies.emplace(key, b).first;
+        it = h->w_copies.emplace(key, std::move(b)).first;
     }
     *out = it->second.p;
     return SVC_OK;
@@ -2656,7 +2650,7 @@ static int launch_irb(SvcHandle *h, hipStream_t s, const float *X, int n, int H,
 // The front of the network: LANCZOS, features.0 (stem), features.1 -> y at half the input size.  One kernel (k_front) where a
 // tile's resampling arrays fit in LDS, else the three kernels (the stem's output in `stem_out`).
 static int net_front(SvcHandle *h, hipStream_t s, const uint8_t *frames, int n, float *stem_out, float *y) {
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     const NetGraph &g = h->net;
     const InvRes &B = g.block[0];
     const int NH = p->NH, NW = p->NW, H = NH / 2, W = NW / 2;
@@ -2718,7 +2712,7 @@ static int dw_project(SvcHandle *h, hipStream_t s, const float *X, const InvRes 
 
 // Backbone block idx = 2 .. 17 (features.idx) on the H x W level: x -> out, H and W updated to the block's output level.
 static int backbone_block(SvcHandle *h, hipStream_t s, int idx, const float *x, float *out, int n, int &H, int &W) {
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     const InvRes &B = h->net.block[idx - 1];
     const float *res = (B.stride == 1 && B.inp == B.oup) ? x : nullptr;
     const bool tap = (idx == 7 || idx == 14);               // full-resolution output feeds a skip
@@ -2753,17 +2747,17 @@ static int head_f18(SvcHandle *h, hipStream_t s, const float *x, int n, int H5, 
 }
 
 static int head_skip_2x(SvcHandle *h, hipStream_t s, int n, int H5, int W5) {
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     return launch_pwpw(h, s, p->buf(B_F2X), 160, h->net.skip2x_expand, h->net.skip2x_reduce, p->buf(B_CAT2) + 256, 384, n * 4 * H5 * W5);
 }
 
 static int head_skip_4x(SvcHandle *h, hipStream_t s, int n, int H5, int W5) {
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     return launch_pwpw(h, s, p->buf(B_F4X), 64, h->net.skip4x_expand, h->net.skip4x_reduce, p->buf(B_CAT3) + 128, 192, n * 16 * H5 * W5);
 }
 
 static int head_priors(SvcHandle *h, hipStream_t s, int n, int H5, int W5) {
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     if (p->gauss_filled < n) {       // the prior maps are constants: nothing else writes channels 1280..1295 of CAT1
         ProfScope ps(h, SVC_K_RESAMPLE, s);
         k_gauss_fill<<<blocks256((size_t)n * H5 * W5 * 16), 256, 0, s>>>((const float *)p->gauss.p, p->buf(B_CAT1), n, H5 * W5,
@@ -2775,7 +2769,7 @@ static int head_priors(SvcHandle *h, hipStream_t s, int n, int H5, int W5) {
 }
 
 static int head_post_cnn(SvcHandle *h, hipStream_t s, int n, int H5, int W5) {
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     return dw_project(h, s, p->buf(B_CAT1), h->net.post_cnn, nullptr, 0, p->buf(B_PCD), p->buf(B_PC), n, H5, W5);
 }
 
@@ -2804,7 +2798,7 @@ static int decoder_block(SvcHandle *h, hipStream_t s, const InvRes &B, const flo
 // the per-frame maxima and folds the census), smoothing + resize to the saliency size LOGIT -> PRE, quantise (profile_rows:
 // the banded variant, which also fills the caller's border-profile rows for svc_saliency_profile_u8).
 static int tail_adapt(SvcHandle *h, hipStream_t s, int n, int H3, int W3) {
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     ProfScope ps(h, SVC_K_RESAMPLE, s);
     k_adapt<<<blocks256((size_t)n * H3 * W3), 256, 0, s>>>(p->buf(B_DEC), h->net.adapt.w.dev, h->net.adapt.b.dev, p->buf(B_LOGIT),
                                                           (size_t)n * H3 * W3, (unsigned *)p->fmax.p, n,
@@ -2816,7 +2810,7 @@ static int tail_adapt(SvcHandle *h, hipStream_t s, int n, int H3, int W3) {
 // B_LOGIT per-frame stride may exceed H3*W3 (rounded to 4): compact layout is used instead.  NH, NW = 8 H3, 8 W3 (the
 // network input sizes are multiples of 32)
 static int tail_smooth(SvcHandle *h, hipStream_t s, int n, int H3, int W3) {
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     const int NH = p->NH, NW = p->NW;
     dim3 grid(ceil_div(p->h, p->sd_rows), n);
     RC(raise_lds_limit(h, (const void *)k_smooth_down_mfma, SD_LDS_MAX));       // (for uniformity, as in net_front: the plan keeps the request within the default)
@@ -2827,7 +2821,7 @@ static int tail_smooth(SvcHandle *h, hipStream_t s, int n, int H3, int W3) {
 }
 
 static int tail_quantise(SvcHandle *h, hipStream_t s, int n, uint8_t *maps, int thr, unsigned *census_rows, unsigned *profile_rows) {
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     if (profile_rows) {
         k_quantise_profile<<<dim3(ceil_div(p->h, BP_ROWS), n), 256, 0, s>>>(p->buf(B_PRE), (const unsigned *)p->fmax.p, maps, p->h, p->w,
                                                                             thr, (unsigned long long *)h->census.p, census_rows,
@@ -2851,7 +2845,7 @@ static int net_tail(SvcHandle *h, hipStream_t s, int n, int H3, int W3, uint8_t 
 // One pass of the network over n <= plan->nb frames.
 static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *maps, hipStream_t s, int thr = 0, unsigned *census_rows = nullptr,
                          unsigned *profile_rows = nullptr) {
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     const NetGraph &g = h->net;
     float *P[2] = {p->buf(B_P0), p->buf(B_P1)};
     int H = p->NH / 2, W = p->NW / 2, cur = 1;
@@ -2946,7 +2940,7 @@ static int saliency_impl(SvcHandle *h, const uint8_t *frames, int n, int height,
 
 extern "C" int svc_debug_tap(SvcHandle *h, int which, int frame, float *out_host, size_t cap_floats) {
     if (!h || !h->plan || !out_host) { svc_set_error("svc_debug_tap: no forward pass has run"); return SVC_E_INVALID; }
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     static const int map[7] = {B_IN, B_F4X, B_F2X, B_CAT1, B_PC, B_DEC, B_PRE};
     if (which < 0 || which > 6 || frame < 0 || frame >= p->last_n) { svc_set_error("svc_debug_tap: bad tap/frame"); return SVC_E_INVALID; }
     const size_t count = which == SVC_TAP_PRE ? (size_t)p->h * p->w : buf_floats(p->NH, p->NW, map[which]);     // PRE: at the saliency size
@@ -3002,7 +2996,7 @@ extern "C" int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int
     if (count * n > cap_floats) { svc_set_error("svc_debug_run_node: buffer too small (%zu needed)", count * n); return SVC_E_INVALID; }
     SVC_HIP(hipSetDevice(h->device));
     RC(build_plan(h, height, width, n));
-    NetPlan *p = h->plan;
+    NetPlan *p = h->plan.get();
     hipStream_t s = nullptr;
     // a NaN bit pattern (all ones) in everything the node may write: what its kernels skip comes back as NaN
     auto fill = [&](int b) { return hipMemsetAsync(p->buf(b), 0xFF, p->per_frame(b) * (size_t)n * sizeof(float), s); };
@@ -3011,12 +3005,12 @@ extern "C" int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int
     if (idx == 7 || idx == 14) SVC_HIP(fill(idx == 7 ? B_F4X : B_F2X));
     p->gauss_filled = 0;                    // the prior channels of CAT1 may hold the fill or the caller's values now
     p->last_n = 0;                          // the workspace is no pass's any more (svc_debug_tap)
-    struct Owned : DevBuf { ~Owned() { release(); } } frames;      // the front's uint8 input: freed on every way out
+    DevBuf frames;                          // the front's uint8 input
     // SVC_NODE_MAP / _MAP_PROFILE: the map is quantised twice from the one PRE, into two buffers of the door's own filled with 0x00
     // and with 0xFF -- a byte that was written is the same in both, one that was not differs.  Each buffer ends in MAP_GUARD
     // bytes of fill that must survive.  The profile variant max-combines into zeroed scratch rows.
     const size_t MAP_GUARD = 256, map_bytes = (size_t)n * height * width;
-    Owned map_a, map_b, map_prof;
+    DevBuf map_a, map_b, map_prof;
     int rc = SVC_OK;
     if (node == SVC_NODE_FRONT) {
         SVC_HIP(fill(B_P0));
@@ -3217,7 +3211,7 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
     SVC_HIP(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) { svc_set_error("svc_create: device %d of %d", device, ndev); return SVC_E_INVALID; }
     SVC_HIP(hipSetDevice(device));
-    SvcHandle *h = new SvcHandle();
+    std::unique_ptr<SvcHandle> h(new SvcHandle());      // freed, with all it holds, on every return but the last
     h->device = device;
     const char *env = getenv("SVC_CHUNK");
     if (env && atoi(env) > 0) h->chunk = atoi(env);
@@ -3229,14 +3223,14 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
     if (env) {
         char *end = nullptr;
         const long v = strtol(env, &end, 10);
-        if (end == env || *end || v < 1 || v > SD_ROWS) { svc_set_error("svc_create: SVC_SD_ROWS=%s (expected 1 .. %d)", env, SD_ROWS); delete h; return SVC_E_INVALID; }
+        if (end == env || *end || v < 1 || v > SD_ROWS) { svc_set_error("svc_create: SVC_SD_ROWS=%s (expected 1 .. %d)", env, SD_ROWS); return SVC_E_INVALID; }
         h->sd_rows = (int)v;
     }
     env = getenv("SVC_MX");
     if (env) {                                               // a typo must not silently select another pipe
         if (!strcmp(env, "bf16x6") || !strcmp(env, "6")) h->mx = 6;
         else if (!strcmp(env, "f32") || !strcmp(env, "0")) h->mx = 0;
-        else { svc_set_error("svc_create: SVC_MX=%s (expected f32 or bf16x6)", env); delete h; return SVC_E_INVALID; }
+        else { svc_set_error("svc_create: SVC_MX=%s (expected f32 or bf16x6)", env); return SVC_E_INVALID; }
     }
     env = getenv("SVC_SK_LANE");
     if (env) h->sk_lane = atoi(env) != 0;
@@ -3245,13 +3239,13 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
         if (!strcmp(env, "bf16x6") || !strcmp(env, "6")) h->shot_mx = 6;
         else if (!strcmp(env, "bf16x3") || !strcmp(env, "3")) h->shot_mx = 3;
         else if (!strcmp(env, "f32") || !strcmp(env, "0")) h->shot_mx = 0;
-        else { svc_set_error("svc_create: SVC_SHOT_MX=%s (expected f32, bf16x6 or bf16x3)", env); delete h; return SVC_E_INVALID; }
+        else { svc_set_error("svc_create: SVC_SHOT_MX=%s (expected f32, bf16x6 or bf16x3)", env); return SVC_E_INVALID; }
     }
     env = getenv("SVC_SHOT_M16");
     if (env) {
         char *end = nullptr;
         const long v = strtol(env, &end, 10);
-        if (end == env || *end || v < 2 || v > 4) { svc_set_error("svc_create: SVC_SHOT_M16=%s (expected 2, 3 or 4)", env); delete h; return SVC_E_INVALID; }
+        if (end == env || *end || v < 2 || v > 4) { svc_set_error("svc_create: SVC_SHOT_M16=%s (expected 2, 3 or 4)", env); return SVC_E_INVALID; }
         h->shot_m16 = (int)v;
     }
     env = getenv("SVC_SHOT_XCD");
@@ -3263,24 +3257,21 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
     env = getenv("SVC_PRIM_LVL");
     if (env) h->prim_lvl = atoi(env);
     int rc = h->blob.ensure(n_bytes);
-    if (rc) { delete h; return rc; }
+    if (rc) return rc;
     if ((rc = h->census.ensure(32 + (size_t)h->chunk * 16)) || hipMemset(h->census.p, 0, 32 + (size_t)h->chunk * 16) != hipSuccess) {
         if (!rc) { svc_set_error("svc_create: census buffer"); rc = SVC_E_HIP; }
-        h->blob.release(); h->census.release(); delete h;
         return rc;
     }
     if (hipMemcpy(h->blob.p, blob_host, n_bytes, hipMemcpyHostToDevice) != hipSuccess) {
         svc_set_error("svc_create: blob upload failed");
-        h->blob.release(); delete h;
         return SVC_E_HIP;
     }
     for (size_t i = 0; i < nt; ++i) {
         uint64_t off = hd[2 + 2 * i], cnt = hd[3 + 2 * i];
-        if ((off + cnt) * 4 > n_bytes) { svc_set_error("svc_create: tensor %zu out of range", i); svc_destroy(h); return SVC_E_BLOB; }
+        if ((off + cnt) * 4 > n_bytes) { svc_set_error("svc_create: tensor %zu out of range", i); return SVC_E_BLOB; }
         h->tensors.push_back(SvcTensor{(const float *)h->blob.p + off, (size_t)cnt});
     }
-    auto fail = [&](int code) { svc_destroy(h); return code; };
-    if ((rc = fill_graph(h))) return fail(rc);
+    if ((rc = fill_graph(h.get()))) return rc;
     // host copies of what the host computes with (the blob's device image is at the same offsets)
     const float *host = (const float *)blob_host, *dev = (const float *)h->blob.p;
     h->gauss_params.assign(host + (h->net.gauss.dev - dev), host + (h->net.gauss.dev - dev) + 64);
@@ -3289,12 +3280,12 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
     std::vector<float> wt(32 * 32, 0.f);
     for (int k = 0; k < 27; ++k)
         for (int co = 0; co < 32; ++co) wt[co * 32 + k] = w_host[k * 32 + co];
-    if ((rc = h->stem_wt.ensure(wt.size() * 4))) return fail(rc);
+    if ((rc = h->stem_wt.ensure(wt.size() * 4))) return rc;
     if (hipMemcpy(h->stem_wt.p, wt.data(), wt.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         svc_set_error("svc_create: stem weight upload failed");
-        return fail(SVC_E_HIP);
+        return SVC_E_HIP;
     }
-    *out = h;
+    *out = h.release();
     return SVC_OK;
 }
 
@@ -3315,14 +3306,17 @@ extern "C" int svc_profile_read_raw(SvcHandle *h, double *raw_total_ms, double *
         if (!h->prof_cal_stream) SVC_HIP(hipStreamCreateWithFlags(&h->prof_cal_stream, hipStreamNonBlocking));
         std::vector<float> emp;
         for (int i = 0; i < 15; ++i) {
-            hipEvent_t a, b;
+            hipEvent_t a = nullptr, b = nullptr;
+            struct Pair {                   // destroys the two events on every way out of the iteration
+                hipEvent_t &a, &b;
+                ~Pair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+            } guard{a, b};
             SVC_HIP(hipEventCreate(&a)); SVC_HIP(hipEventCreate(&b));
             SVC_HIP(hipEventRecord(a, h->prof_cal_stream)); SVC_HIP(hipEventRecord(b, h->prof_cal_stream));
             SVC_HIP(hipEventSynchronize(b));
             float ms = 0.f;
             SVC_HIP(hipEventElapsedTime(&ms, a, b));
             emp.push_back(ms);
-            (void)hipEventDestroy(a); (void)hipEventDestroy(b);
         }
         std::sort(emp.begin(), emp.end());
         *pair_ms = emp[emp.size() / 2];
@@ -3356,26 +3350,6 @@ extern "C" int svc_profile_read(SvcHandle *h, double *total_ms, int *launches) {
 
 extern "C" int svc_destroy(SvcHandle *h) {
     if (!h) return SVC_OK;
-    (void)hipSetDevice(h->device);
-    for (auto &e : h->prof_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    h->prof_events.clear();
-    if (h->prof_cal_stream) { (void)hipStreamDestroy(h->prof_cal_stream); h->prof_cal_stream = nullptr; }
-    svc_net_release(h);
-    h->tail_ws.release();
-    h->tail_offsets.release();
-    h->tail_ring_cnt.release();
-    for (auto &kv : h->w_copies) kv.second.release();
-    h->census.release();
-    for (auto &kv : h->tail_delta) kv.second.release();
-    h->stem_wt.release();
-    h->shot_blob.release();
-    h->shot_ws.release();
-    h->shot_w3.release();
-    h->rs_maps.release();
-    for (auto &kv : h->rs_tabs) { kv.second.first.release(); kv.second.second.release(); }
-    for (auto &e : h->depth_ev) if (e) (void)hipEventDestroy(e);
-    if (h->depth_pinned) (void)hipHostFree(h->depth_pinned);
-    h->blob.release();
     delete h;
     return SVC_OK;
 }

@@ -2870,8 +2870,7 @@ static int ensure_ring_delta(SvcHandle *h, int width, const int32_t **out) {
     int rc = buf.ensure(d.size() * 4);
     if (rc) return rc;
     SVC_HIP(hipMemcpy(buf.p, d.data(), d.size() * 4, hipMemcpyHostToDevice));
-    h->tail_delta.emplace(width, buf);
-    *out = (const int32_t *)buf.p;
+    *out = (const int32_t *)h->tail_delta.emplace(width, std::move(buf)).first->second.p;
     return SVC_OK;
 }
 
@@ -2949,7 +2948,7 @@ static int ensure_shrink_tables(SvcHandle *h, int n, int full_h, int full_w, int
         std::pair<DevBuf, DevBuf> t;
         if ((rc = upload_map_tab(t.first, full_h, full_w, sh, sw, (double)factor, (double)factor))) return rc;
         if ((rc = upload_map_tab(t.second, sh, sw, full_h, full_w, (double)sh / full_h, (double)sw / full_w))) return rc;
-        it = h->rs_tabs.emplace(key, t).first;
+        it = h->rs_tabs.emplace(key, std::move(t)).first;
     }
     *down = (const int *)it->second.first.p;
     *up = (const int *)it->second.second.p;
@@ -3229,7 +3228,6 @@ extern "C" int svc_debug_argsort_u32(SvcHandle *h, const uint32_t *keys_host, in
     std::vector<uint16_t> o(n);
     SVC_HIP(hipMemcpy(o.data(), out.p, (size_t)n * 2, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) order_host[i] = o[i];
-    keys.release(); out.release(); scratch.release();
     return n;
 }
 
