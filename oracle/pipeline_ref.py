@@ -196,8 +196,8 @@ def ingest_video(video, CP, sd, trans_probs, trans_threshold=0.1, stage=None):
                 h_process=sal_h, w_process=sal_w)
 
 
-def crop_from_maps(VD, CP, stage=None):
-    """smart_vid_crop after ingest (:2293-2522).  Adds 'bbs' etc. to VD."""
+def crop_from_maps(VD, CP, stage=None, labels_fn=None):
+    """smart_vid_crop after ingest (:2293-2522).  Adds 'bbs' etc. to VD.  labels_fn: see tail_ref.clustering_filt."""
     VD['w_final'], VD['h_final'], VD['conversion_mode'] = tail_ref.calc_dest_size(
         VD['w_orig'], VD['h_orig'], CP['out_ratio'])
     cuts = tail_ref.segm_cuts_of(VD['segmentation_sel'])
@@ -205,7 +205,7 @@ def crop_from_maps(VD, CP, stage=None):
     if stage is not None:
         stage['thresholded'] = VD['smaps'].copy()
     if CP['clust_filt']:
-        tail_ref.cluster_loop(VD['smaps'], cuts, CP)
+        tail_ref.cluster_loop(VD['smaps'], cuts, CP, labels_fn)
     if stage is not None:
         stage['filtered'] = VD['smaps'].copy()
     dx, dy = tail_ref.centers(VD['smaps'], CP)

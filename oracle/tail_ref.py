@@ -85,11 +85,11 @@ def segm_cuts_of(segmentation_sel):
     return cuts
 
 
-def cluster_loop(smaps_hwn, segm_cuts, CP):
-    """smartVidCrop.py:2359-2373 on [H,W,N] u8 (thresholded), in place."""
+def cluster_loop(smaps_hwn, segm_cuts, CP, labels_fn=None):
+    """smartVidCrop.py:2359-2373 on [H,W,N] u8 (thresholded), in place.  labels_fn: see clustering_filt."""
     n = smaps_hwn.shape[2]
     for i in range(n):
-        smaps_hwn[:, :, i] = clustering_filt(smaps_hwn[:, :, i], CP)
+        smaps_hwn[:, :, i] = clustering_filt(smaps_hwn[:, :, i], CP, labels_fn=labels_fn)
         if i < n - 2:
             if any(x in segm_cuts for x in (i - 1, i, i + 1)):
                 smaps_hwn[:, :, i + 1] = blend_next(smaps_hwn[:, :, i], smaps_hwn[:, :, i + 1])

@@ -10,8 +10,9 @@ what this file adds for the run itself:
   hdbscan.HDBSCAN     a dummy (constructed at :2340, never used with clust_filt = False)
   numpy.int           = int where NumPy no longer has it (the reference's get_points_on_line casts with it, :1377, :1384;
                       without it every diagonal jump raises inside its try block and counts as "no statistic")
-  get_points_on_line  receives its four coordinates as numpy.float32 scalars of the same value (refused unless float32 holds the
-                      value exactly; the arg-max centres of the best-settings cases are small integers).  The reference pins
+  get_points_on_line  receives its four coordinates as numpy.float32 scalars of the same value where float32 holds the value
+                      exactly (the arg-max centres of the best-settings cases are small integers), as _WeakFloat otherwise (the
+                      k-means centres of tools/make_golden_refpath_clustered.py; none occurs here).  The reference pins
                       SciPy 1.5.1 and scikit-learn 0.24.1 (README.md:89-92) and needs numpy.int, so the NumPy it runs on promotes
                       `float32 array - numpy.int64 scalar` to float32 (value-based casting); NumPy 2 makes it float64, the product
                       slope * offset of :1377 / :1384 is then rounded once less, and int() of it falls on the other side of a
@@ -23,8 +24,10 @@ original and return its result.  The fixture holds arrays and strings of setting
 tests/refpath_cases.py, which reads it back).  Nothing at test, bench or smoke time imports this file, except the staleness test of
 tests/test_refpath_host.py, which runs where the reference tree is present and is skipped elsewhere.
 
-Out of reach, NOT generated here: the clustered path (sc_clustering_filt needs hdbscan and cv2's morphology) and com_km = True
-with resize_factor > 1 (needs cv2.resize INTER_NEAREST itself).
+NOT generated here: the clustered path.  Its two third-party algorithms are out of reach (hdbscan's labels, cv2's CLOSE 5x5 and
+its resize for resize_factor > 1), the reference's own code around them is not: tools/make_golden_refpath_clustered.py runs it
+with op_close = False, resize_factor = 1 and scikit-learn's labels.  Also out of reach: com_km = True with resize_factor > 1
+(needs cv2.resize INTER_NEAREST itself).
 
 Run from the repo root:  python tools/make_golden_refpath.py <directory of the reference's smartVidCrop.py>"""
 import contextlib
@@ -121,8 +124,8 @@ class Stubs:
 
         def points_with_the_references_promotion(p1x, p1y, p2x, p2y, *a, **k):
             p = [np.float32(v) for v in (p1x, p1y, p2x, p2y)]
-            if any(float(q) != float(v) for q, v in zip(p, (p1x, p1y, p2x, p2y))):
-                raise NotImplementedError('get_points_on_line: a coordinate that float32 does not hold exactly')
+            if any(float(q) != float(v) for q, v in zip(p, (p1x, p1y, p2x, p2y))):      # (a k-means centre)
+                p = [_WeakFloat(v) for v in (p1x, p1y, p2x, p2y)]
             return points(*p, *a, **k)
         ref.get_points_on_line = points_with_the_references_promotion
 
@@ -148,6 +151,30 @@ class Stubs:
         return np.stack([self.prepared[n] for n in nums], 2)
 
 
+class _WeakFloat(float):
+    """A float64 coordinate that float32 does not hold exactly (a k-means centre), for get_points_on_line.  The reference's NumPy
+    computed `float32 array - float64 scalar` in float32, the scalar rounded to float32 first; NumPy 2 does that for a Python
+    float of exactly that type and for nothing else.  So: a float that stays one under the function's + and -, that an array
+    hands its own + and - to (__array_priority__) to be met as a plain Python float, with the .astype the function calls on the
+    differences (:1372, :1379).  Everything else the function does with the coordinates is float64 arithmetic either way."""
+    __array_priority__ = 1000
+
+    def astype(self, dtype):
+        return dtype(float(self))
+
+    def __add__(self, o):
+        return _WeakFloat(float(self) + float(o))
+
+    def __sub__(self, o):
+        return _WeakFloat(float(self) - float(o))
+
+    def __rsub__(self, o):
+        return o - float(self) if isinstance(o, np.ndarray) else _WeakFloat(float(o) - float(self))
+
+    def __radd__(self, o):
+        return o + float(self) if isinstance(o, np.ndarray) else _WeakFloat(float(o) + float(self))
+
+
 class Recorder:
     """Thin wrappers on the reference module's functions: before(*args) / after(result, *args) copy what they see."""
 
@@ -156,7 +183,7 @@ class Recorder:
 
     def wrap(self, name, before=None, after=None):
         orig = getattr(self.ref, name)
-        self.orig[name] = orig
+        self.orig.setdefault(name, orig)                    # (a name wrapped twice is restored to the reference's own function)
 
         def wrapper(*a, **k):
             if before is not None:
@@ -290,8 +317,9 @@ def _dim(maps, k, t_thr, rng):
 
 
 # ---- one case -------------------------------------------------------------------------------------------------------------------
-def run_case(ref, stubs, spec, seed):
-    """-> record (dict of arrays and scalars) of one video, or raises what the reference raised."""
+def run_case(ref, stubs, spec, seed, design=None, hooks=None):
+    """-> record (dict of arrays and scalars) of one video, or raises what the reference raised.  design: another design_maps;
+    hooks(R, rec): further wrappers of the caller's (tools/make_golden_refpath_clustered.py), set before the ones below."""
     rng = np.random.RandomState(seed)
     CP = ref.sc_init_crop_params(use_best_settings=spec['best'])
     CP.update(spec['overrides'])
@@ -305,10 +333,12 @@ def run_case(ref, stubs, spec, seed):
             VD0 = ref.ingest_pickle(path, CP)
         hp, wp = int(VD0['h_process']), int(VD0['w_process'])
         true_inds = [int(v) for v in VD0['true_inds']]
-        prep, tags = design_maps(spec, rng, true_inds, np.asarray(VD0['segmentation_sel']), hp, wp)
+        prep, tags = (design or design_maps)(spec, rng, true_inds, np.asarray(VD0['segmentation_sel']), hp, wp)
         stubs.prepared = {g: prep[k] for k, g in enumerate(true_inds)}
         stubs.asked = []
         R = Recorder(ref)
+        if hooks is not None:
+            hooks(R, rec)
 
         def after_ingest(VD, *a, **k):
             rec.update(true_inds=np.asarray(VD['true_inds'], np.int32), inds_to_orig=np.asarray(VD['inds_to_orig'], np.int32),

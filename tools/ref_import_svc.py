@@ -3,7 +3,7 @@ time and the fixture generators never use (cv2, ffmpeg, hdbscan, imutils, tensor
 A module that is installed is imported as it is; only a missing one is replaced by an empty module.  The reference's own LOESS
 (3rd_party_libs/loess/pyloess.py) is found the way the reference finds it: its directory is put on sys.path first.
 
-Shared by tools/make_golden_border.py and tools/make_golden_refpath.py.  Nothing at test, bench or smoke time imports this file."""
+Shared by tools/make_golden_border.py, tools/make_golden_refpath.py and tools/make_golden_refpath_clustered.py.  Nothing at test, bench or smoke time imports this file."""
 import contextlib
 import importlib.util
 import io
