@@ -88,9 +88,26 @@ const char *svc_last_error(void);
  *     SvcColour with svc_resize_frames_colour and svc_render_crops_colour (NV12 colour): a new struct and two new entries; and
  *     svc_render_crops_to_layout (pitched output): one new entry that takes the existing SvcFrameLayout, unchanged, for the output; and
  *     svc_render_windows_q8 (sub-pixel windows): one new entry, no struct; and svc_debug_tail_plan (SVC_TAILPLAN_*): one new test door; and
- *     SVC_NODE_MAP / SVC_NODE_MAP_PROFILE: two new node ids of svc_debug_run_node, which an older library refuses as unknown. */
-#define SVC_ABI_VERSION 12
+ *     SVC_NODE_MAP / SVC_NODE_MAP_PROFILE: two new node ids of svc_debug_run_node, which an older library refuses as unknown.
+ * 13 = svc_debug_scratch_fill exists. */
+#define SVC_ABI_VERSION 13
 int svc_abi_version(void);
+
+/* Test switch, process-wide (one atomic): byte = -1 switches it off (the default), 0 .. 255 on.  While it is on, every entry that
+ * runs device work on a handle's scratch fills that scratch with the byte first -- a hipMemsetAsync on the call's own stream, after
+ * the workspace has its size and before the first kernel -- and does so before EVERY pass over the workspace, not once per call:
+ * every chunk of a svc_saliency_* call (and svc_debug_run_node), every group of windows of svc_transnet_predict / _predict_rows /
+ * svc_debug_transnet_tap, every svc_cluster_center call.  Scratch is the network's activations and per-frame maxima, TransNet's two
+ * activation buffers, the tail's shrunk maps and the tail's workspace; the last holds indices and counts and is filled with 0x00
+ * whatever the byte, so that a stale read changes a result and never an address.  Weights and their copies, every table, the
+ * census totals and the host staging ring are state and are never filled (csrc/svc_internal.h has the list).  The doors that read
+ * what the last pass left (svc_debug_tap, svc_debug_cluster_state, svc_threshold_census) fill nothing.
+ * A kernel that reads what its pass did not write then reads the fill instead of the previous call's value -- which tests that
+ * compare two calls on one handle otherwise make the right one.  0xFF reads as NaN in fp32 and bf16; 0x7F as 3.39e38, which
+ * survives a clamp and wins a maximum where NaN does not.
+ * Off, an entry pays one relaxed atomic load and launches nothing more; bench.py never turns it on.  (Expected from the code, not
+ * measured.)  Process-wide so that every handle of a test session obeys it; not for production.  SVC_E_INVALID outside -1 .. 255. */
+int svc_debug_scratch_fill(int byte);
 
 /* weights_blob_host: the packed, BN-folded static SALICON slice of a UNISAL
  * checkpoint (retargetvid_amd.weights.pack_blob).  The blob is copied to `device`. */

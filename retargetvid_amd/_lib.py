@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SVC_LIB') or os.path.join(_HERE, 'libsvc_hip.so')      # SVC_LIB: another build of the same ABI (A/B runs)
 
-ABI_VERSION = 12         # include/svc.h SVC_ABI_VERSION this binding was written against
+ABI_VERSION = 13         # include/svc.h SVC_ABI_VERSION this binding was written against
 
 EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'svc_resize_frames_u8', 'svc_saliency_u8',
            'svc_threshold_u8', 'svc_cluster_center', 'svc_iou_i32', 'svc_debug_cluster_state', 'svc_debug_tap', 'svc_front_fused', 'svc_matrix_pipe', 'svc_threshold_census', 'svc_debug_round_plan', 'svc_transnet_load', 'svc_transnet_predict', 'svc_transnet_matrix_pipe',
@@ -22,7 +22,7 @@ EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'sv
            'svc_resize_frames_nv12', 'svc_render_crops_nv12', 'svc_render_crops_u8_to_nv12', 'svc_render_crops_nv12_to_nv12', 'svc_debug_run_node',
            'svc_resize_frames_layout', 'svc_render_crops_layout', 'svc_render_crops_filter', 'svc_debug_net_plan',
            'svc_resize_frames_colour', 'svc_render_crops_colour', 'svc_render_crops_to_layout',
-           'svc_render_windows_q8', 'svc_debug_tail_plan')
+           'svc_render_windows_q8', 'svc_debug_tail_plan', 'svc_debug_scratch_fill')
 
 
 class SvcParams(ctypes.Structure):
@@ -150,6 +150,7 @@ def load():
     lib.svc_saliency_profile_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]
     lib.svc_border_profile_u8.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.svc_debug_argsort_u32.argtypes = [vp, vp, i32, vp]
+    lib.svc_debug_scratch_fill.argtypes = [i32]
     lib.svc_profile_enable.argtypes = [vp, i32]
     lib.svc_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
     lib.svc_profile_read_raw.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]

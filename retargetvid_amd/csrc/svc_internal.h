@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
 #include <map>
 #include <memory>
 #include <set>
@@ -54,6 +55,31 @@ __device__ __forceinline__ uint32_t fdivmod(uint32_t n, const FDiv &f, uint32_t 
     } while (0)
 
 #define SVC_CHECK_LAUNCH()  SVC_HIP(hipGetLastError())
+
+// The test switch svc_debug_scratch_fill (include/svc.h): -1 = off, 0..255 = the byte every pass fills its SCRATCH with before its
+// first kernel.  Process-wide (svc_net.hip holds it), so every handle obeys it; off costs the one relaxed load below and adds no launch.
+//
+// Which DevBuf is scratch -- its contents mean nothing when a pass starts, so it is filled -- and which is state, never filled:
+//   scratch  NetPlan::ws        activations of one network pass.  One exception lives inside it: the Gaussian-prior channels of
+//                               CAT1 are constants written once per plan (NetPlan::gauss_filled); a filled pass writes them again
+//            NetPlan::fmax      per-frame maxima of one pass: k_adapt clears them, k_smooth_down_mfma raises them
+//            SvcHandle::shot_ws TransNet's two ping-pong activation buffers of one pass over a group of windows
+//            SvcHandle::rs_maps the shrunk maps of one svc_cluster_center call (resize_factor > 1)
+//            SvcHandle::tail_ws the round list and the per-map slots of one svc_cluster_center call.  It holds indices and
+//                               counts, so it is always filled with 0x00: a stale read changes a result, never an address
+//   state    blob, shot_blob (weights), w_copies, shot_w3, stem_wt (their re-ordered copies), cvtabs, lztabs, rs_tabs,
+//            NetPlan::hb/hk/vb/vk/fr_vt/fr_ht (resampling tables), tail_offsets, tail_ring_cnt, tail_delta (ring tables),
+//            NetPlan::lut, NetPlan::gauss (constants of a plan), census (totals that accumulate over calls by contract),
+//            depth_pinned (host staging ring: calls still in flight read their slot)
+// svc_debug_tap, svc_debug_cluster_state and the census / profile reads look at what the last pass left: they fill nothing.
+extern std::atomic<int> g_svc_scratch_fill;
+// Fills the whole block (not only what this pass lays out in it) on the pass's stream; byte < 0: the byte asked for.
+static inline hipError_t scratch_fill(DevBuf &b, hipStream_t s, int byte = -1) {
+    const int f = g_svc_scratch_fill.load(std::memory_order_relaxed);
+    if (f < 0 || !b.p) return hipSuccess;
+    return hipMemsetAsync(b.p, byte < 0 ? f : byte, b.bytes, s);
+}
+static inline bool scratch_fill_on() { return g_svc_scratch_fill.load(std::memory_order_relaxed) >= 0; }
 
 struct SvcTensor {
     const float *dev;     // device pointer into the blob

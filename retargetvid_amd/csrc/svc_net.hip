@@ -76,6 +76,14 @@ void svc_set_error(const char *fmt, ...) {
 extern "C" const char *svc_last_error(void) { return g_err; }
 extern "C" int svc_abi_version(void) { return SVC_ABI_VERSION; }
 
+// The scratch-fill test switch (svc_internal.h lists what is scratch; include/svc.h states the contract)
+std::atomic<int> g_svc_scratch_fill{-1};
+extern "C" int svc_debug_scratch_fill(int byte) {
+    if (byte < -1 || byte > 255) { svc_set_error("svc_debug_scratch_fill: %d is neither -1 (off) nor a byte", byte); return SVC_E_INVALID; }
+    g_svc_scratch_fill.store(byte, std::memory_order_relaxed);
+    return SVC_OK;
+}
+
 // --------------------------------------------------------------------------------------
 // K0: Pillow LANCZOS (two 8-bit fixed-point passes) + /255 + normalise (via LUT) -> NHWC fp32
 // --------------------------------------------------------------------------------------
@@ -2849,6 +2857,11 @@ static int forward_chunk(SvcHandle *h, const uint8_t *frames, int n, uint8_t *ma
     const NetGraph &g = h->net;
     float *P[2] = {p->buf(B_P0), p->buf(B_P1)};
     int H = p->NH / 2, W = p->NW / 2, cur = 1;
+    if (scratch_fill_on()) {                                // test switch: the pass starts on filled scratch
+        SVC_HIP(scratch_fill(p->ws, s));
+        SVC_HIP(scratch_fill(p->fmax, s));
+        p->gauss_filled = 0;                                // the prior channels of CAT1 hold the fill now: head_priors writes them again
+    }
     RC(net_front(h, s, frames, n, P[0], P[1]));
     for (int idx = 2; idx <= 17; ++idx, cur ^= 1) RC(backbone_block(h, s, idx, P[cur], P[cur ^ 1], n, H, W));
     const int H5 = H, W5 = W;                               // the levels: /32, /16 (H4 = 2 H5), /8 (H3 = 4 H5)
@@ -2998,6 +3011,8 @@ extern "C" int svc_debug_run_node(SvcHandle *h, int node, int n, int height, int
     RC(build_plan(h, height, width, n));
     NetPlan *p = h->plan.get();
     hipStream_t s = nullptr;
+    SVC_HIP(scratch_fill(p->ws, s));        // test switch: the whole workspace first, with the byte asked for ...
+    SVC_HIP(scratch_fill(p->fmax, s));
     // a NaN bit pattern (all ones) in everything the node may write: what its kernels skip comes back as NaN
     auto fill = [&](int b) { return hipMemsetAsync(p->buf(b), 0xFF, p->per_frame(b) * (size_t)n * sizeof(float), s); };
     for (int b : {ob, (int)B_E0, (int)B_E1, (int)B_T1, (int)B_T2, (int)B_PCD, (int)B_U2E, (int)B_P3E}) SVC_HIP(fill(b));

@@ -1053,6 +1053,7 @@ static int transnet_predict_rows(SvcHandle *h, const uint8_t *frames, int n_wind
         const size_t nfr = (size_t)nw * T;
         int H = SHOT_H, W = SHOT_W, cur = 0;
         const bool first_x3 = mx != 0;
+        SVC_HIP(scratch_fill(h->shot_ws, s));                // test switch: every pass (the tap door's too) starts on filled buffers
         {
             const size_t npix = nfr * H * W;
             if (first_x3)

@@ -2940,7 +2940,7 @@ static int check_cluster_args(SvcHandle *h, const uint8_t *maps, int n, int heig
 }
 
 // resize_factor > 1: the INTER_LINEAR tables full size -> (sh, sw) and back, and room for n shrunk maps (h->rs_maps)
-static int ensure_shrink_tables(SvcHandle *h, int n, int full_h, int full_w, int sh, int sw, int factor, const int **down, const int **up) {
+static int ensure_shrink_tables(SvcHandle *h, hipStream_t s, int n, int full_h, int full_w, int sh, int sw, int factor, const int **down, const int **up) {
     int rc;
     auto key = std::make_tuple(full_h, full_w, factor);
     auto it = h->rs_tabs.find(key);
@@ -2952,7 +2952,9 @@ static int ensure_shrink_tables(SvcHandle *h, int n, int full_h, int full_w, int
     }
     *down = (const int *)it->second.first.p;
     *up = (const int *)it->second.second.p;
-    return h->rs_maps.ensure((size_t)n * sh * sw);
+    if ((rc = h->rs_maps.ensure((size_t)n * sh * sw))) return rc;
+    SVC_HIP(scratch_fill(h->rs_maps, s));                    // test switch
+    return SVC_OK;
 }
 
 // The maps of a call sorted by round (stable), one slice per round, on the host and on the device.
@@ -2992,6 +2994,7 @@ static int make_round_list(const uint8_t *flags, int n, RoundList &R) {
 static int upload_round_list(SvcHandle *h, int n, size_t frame_bytes, hipStream_t s, RoundList &R) {
     int rc = h->tail_ws.ensure(TAIL_LISTS_BYTES + frame_bytes * std::max<size_t>(32, ((size_t)R.n_proc + 31) / 32 * 32));
     if (rc) return rc;
+    SVC_HIP(scratch_fill(h->tail_ws, s, 0x00));              // test switch: indices and counts, so zeros whatever byte was asked for; before this call's list lands
     if (!h->depth_pinned) SVC_HIP(hipHostMalloc((void **)&h->depth_pinned, TAIL_LISTS_BYTES, hipHostMallocDefault));
     const int slot = h->depth_slot++ & 7;
     if (h->depth_ev[slot]) SVC_HIP(hipEventSynchronize(h->depth_ev[slot]));      // the upload that last used this slot has run
@@ -3114,7 +3117,7 @@ static int cluster_center_impl(SvcHandle *h, uint8_t *maps, int n, int height, i
     if (factor > 1) {
         height = rs_h;
         width = rs_w;
-        RC_TAIL(ensure_shrink_tables(h, n, full_h, full_w, height, width, factor, &rs_down, &rs_up));
+        RC_TAIL(ensure_shrink_tables(h, s, n, full_h, full_w, height, width, factor, &rs_down, &rs_up));
         maps = (uint8_t *)h->rs_maps.p;
     }
     const FrameWS L = make_layout(height * width, hdb::max_clusters(height * width, params->hdbscan_min));

@@ -49,6 +49,13 @@ def net_plan(height, width):
     return dict(zip(PLAN_WORDS, (int(v) for v in out)))
 
 
+def scratch_fill(byte):
+    """Test door (svc_debug_scratch_fill), process-wide: byte 0..255 = every pass of every handle fills its scratch workspaces with that
+    byte before its first kernel (the tail's index workspace with zeros); None = off, the default.  For tests: a pass that reads what
+    it did not write reads the fill, not what the previous call left.  Needs no GPU to set."""
+    _lib.check(_lib.load().svc_debug_scratch_fill(-1 if byte is None else int(byte)))
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 

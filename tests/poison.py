@@ -13,7 +13,11 @@ equals its reference under both fills was written.  G = 256 keeps the 16-byte ph
 512-aligned), so every test takes the vector kernels it took before; phase= moves the data to G + phase for the directed tests.
 
 The fixture `poisoned_outputs` puts one Poison in place for one test and checks the guards at teardown; a module opts in with
-pytest.mark.usefixtures('poisoned_outputs') after importing the fixture from here."""
+pytest.mark.usefixtures('poisoned_outputs') after importing the fixture from here.
+
+The same hole inside the library: a handle keeps its workspaces from call to call (DevBuf::ensure only grows), so a kernel that reads a
+value its pass should have computed reads the previous call's -- often the right one.  The fixture `poisoned_workspaces` turns the
+library's test switch on (svc_debug_scratch_fill, 0xFF) for one test; tests/test_gpu_scratch.py has the directed cases."""
 import sys
 import threading
 
@@ -107,6 +111,23 @@ class Poison:
                         bad.append('%s: %d byte(s) written below the data (nearest %d before its start), %d behind it (first at end + %d)'
                                    % (what, len(front), off - front[-1] if front else 0, len(back), back[0] if back else 0))
         assert not bad, 'stores outside an output:\n  ' + '\n  '.join(bad)
+
+
+WS_FILL, WS_FILL2 = 0xFF, 0x7F     # the library's scratch: NaN in fp32 and in every bf16 plane; 3.39e38, which a clamp and a maximum keep
+WS_SETTINGS = (None, WS_FILL, WS_FILL2)
+
+
+@pytest.fixture
+def poisoned_workspaces():
+    """The library's own scratch -- the workspaces a handle keeps from call to call at the same addresses -- is filled with 0xFF before
+    every pass of this test (ops.scratch_fill, process-wide: the session's engine, module-scoped nets, cloned nets and scheduler lanes
+    all obey it), so no pass rides what the previous call left there; switched off at teardown, also when the test raised."""
+    from retargetvid_amd import ops
+    ops.scratch_fill(WS_FILL)
+    try:
+        yield WS_FILL
+    finally:
+        ops.scratch_fill(None)
 
 
 @pytest.fixture

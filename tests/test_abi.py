@@ -184,6 +184,24 @@ def test_tail_plan_door_checks_its_arguments():
     assert int(re.search(r'#define SVC_TAILPLAN_WORDS (\d+)', text).group(1)) == n
 
 
+def test_scratch_fill_door_takes_a_byte_or_off_and_nothing_else():
+    """svc_debug_scratch_fill (ABI 13; needs no handle and no GPU): -1 and every byte are accepted, anything else is refused with
+    SVC_E_INVALID and a message; ops.scratch_fill(None) is -1; the switch ends off."""
+    from retargetvid_amd import ops
+    lib = _lib.load()
+    assert 'svc_debug_scratch_fill' in _lib.EXPORTS and 'svc_debug_scratch_fill' not in _lib.LATER_ENTRIES
+    try:
+        for byte in (0, 0x7F, 0xFF, -1):
+            assert lib.svc_debug_scratch_fill(byte) == 0, byte
+        for bad in (-2, 256, 1 << 20):
+            assert lib.svc_debug_scratch_fill(bad) == -1 and b'svc_debug_scratch_fill' in lib.svc_last_error(), bad
+            with pytest.raises(_lib.SvcError):
+                ops.scratch_fill(bad)
+        ops.scratch_fill(0xFF)
+    finally:
+        ops.scratch_fill(None)
+
+
 def test_frame_header_words_are_the_headers():
     """The words of svc_debug_cluster_state's frame header: every SVC_HDR_* of include/svc.h is ops.HDR_* with the same number,
     neither side has a name the other lacks, and the named words and ranges lie side by side inside the header."""

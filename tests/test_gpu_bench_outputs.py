@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 

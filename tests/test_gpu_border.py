@@ -8,12 +8,12 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from oracle import tail_ref as T
 from retargetvid_amd import ops, render, scheduler, smartVidCrop as S, synth
 from test_oracle_unisal import ELEVEN
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 KEYS = ('border_t', 'border_b', 'border_l', 'border_r')
 SHAPES = sorted(set(ELEVEN.values())) + [(35, 35), (141, 249)]

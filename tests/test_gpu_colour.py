@@ -6,13 +6,13 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 import colour_ref as C
 import nv12_out_ref
 import nv12_ref
 from retargetvid_amd import ops, render, smartVidCrop as S, synth, weights
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 BT709_FULL = ('bt709', 'full')
 

@@ -15,11 +15,11 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from oracle import cv_ref, pipeline_ref as P, tail_ref as T, unisal_ref as U
 from retargetvid_amd import dist as D, evaluate as E, smartVidCrop as S, synth
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 
 def _device_frames(n, h, w, seed, chunk=16):

@@ -6,12 +6,12 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 import nv12_ref
 from retargetvid_amd import ops, smartVidCrop as S
 from retargetvid_amd.frames import FrameSource
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 N, H, W = 70, 36, 64
 SH, SW = 14, 25

@@ -16,11 +16,11 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from oracle import unisal_ref as U
 from retargetvid_amd import ops
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 # one saliency-map shape per network input size get_optimal_out_size can select; all eleven up-scale, so all run k_front
 _SHAPES = [(140, 250), (187, 250), (250, 140), (166, 250), (200, 250), (230, 250), (249, 249), (250, 230), (250, 200),

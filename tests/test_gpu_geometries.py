@@ -12,13 +12,13 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from oracle import unisal_ref as U
 from retargetvid_amd import ops, synth, weights
 from test_gpu_parity import _TAPS, _TOL
 from test_oracle_unisal import ELEVEN, NET_SIZES, golden5_checkpoint, golden5_frames, golden5_u8
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 OLD = ('16x9', '4x3', 'port')                 # the geometries of golden2-4

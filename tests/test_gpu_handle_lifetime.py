@@ -9,12 +9,12 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from oracle import pipeline_ref as P
 from retargetvid_amd import ops, synth, weights
 from retargetvid_amd import transnetv1_handler as TH
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 CP = P.init_crop_params()
 FLAGS = np.array([1, 0, 0, 0], np.uint8)

@@ -11,10 +11,10 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from retargetvid_amd import _lib, smartVidCrop as S, synth, unisal_handler, weights
 
-pytestmark = pytest.mark.usefixtures('poisoned_outputs')
+pytestmark = pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

@@ -15,14 +15,14 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 import last_stage_cases as LS
 import net_node_cases as C
 from oracle import last_stage_ref as L, unisal_ref as U
 from retargetvid_amd import ops, synth
 from test_net_plan_census import SHAPES
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 DOOR_SHAPES = list(SHAPES) + [(140, 250)]               # the door plans like svc_saliency_u8: it accepts every shape of the table
 CHUNK = int(os.environ.get('SVC_CHUNK') or 32)          # frames of one pass

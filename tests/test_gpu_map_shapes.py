@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 import net_node_cases as C
 from oracle import unisal_nodes_ref as N, unisal_ref as U
 from retargetvid_amd import _lib, ops, synth, weights
@@ -24,7 +24,7 @@ from test_gpu_net_nodes import PIPES, _assert_rest_is_fill, _engine, _gate
 from test_gpu_parity import _TOL
 from test_net_plan_census import DOWN_SHAPES, REFUSED, SD_ROWS, SHAPES
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 IDENTITY = [(416, 256), (416, 250)]                     # saliency entry only: the tail takes maps of at most 255 a side
 NODE_SHAPES = [s for s in SHAPES if s not in IDENTITY]

@@ -13,13 +13,13 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 import net_node_cases as C
 from oracle import unisal_nodes_ref as N
 from retargetvid_amd import ops
 from test_oracle_unisal import ELEVEN, NET_SIZES
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 PIPES = ('bf16x6', 'f32')
 

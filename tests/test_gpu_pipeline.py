@@ -6,11 +6,11 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from oracle import pipeline_ref as P, unisal_ref as U
 from retargetvid_amd import evaluate as E, smartVidCrop as S, synth, unisal_handler
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 
 def _video(n, seed, trans):

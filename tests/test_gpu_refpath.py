@@ -18,10 +18,10 @@ import pytest
 import torch
 
 import refpath_cases as RC
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from retargetvid_amd import ops, smartVidCrop as S
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 CASES, EXTRAS = RC.load()
 IDS = [RC.case_id(c) for c in CASES]

@@ -17,10 +17,10 @@ import pytest
 import torch
 
 import refpath_clustered_cases as RCC
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from retargetvid_amd import ops, pipeline as PL, smartVidCrop as S
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 CASES, DIRECT = RCC.load()
 IDS = [RCC.case_id(c) for c in CASES]

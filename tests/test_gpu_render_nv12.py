@@ -6,13 +6,13 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 import nv12_out_ref
 import nv12_ref
 from oracle import cv_ref
 from retargetvid_amd import ingest, ops, render, smartVidCrop as S, synth
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 SOURCES = ('rgb24', 'nv12')
 forward = nv12_out_ref.rgb_to_nv12_fixed

@@ -12,12 +12,12 @@ import pytest
 import torch
 
 import tail_paths as tp
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from oracle import hdbscan_ref as H
 from retargetvid_amd import ops
 from test_gpu_parity import _check_tail
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 
 def _plan(engine, shape, CP):

@@ -9,14 +9,14 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from oracle import cv_ref, pipeline_ref as P, tail_ref as T
 from retargetvid_amd import ops
 from retargetvid_amd._lib import SvcError
 from test_gpu_parity import _check_tail, _ref_tail, _state_is_the_oracles
 from test_oracle_unisal import ELEVEN
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 BEST = P.init_crop_params(True)
 STRADDLE = (89, 90, 91, 119, 120, 121)          # around both thresholds: best settings 90, default 120

@@ -16,11 +16,11 @@ import numpy as np
 import pytest
 import torch
 
-from poison import poisoned_outputs  # noqa: F401  (a fixture)
+from poison import poisoned_outputs, poisoned_workspaces  # noqa: F401  (fixtures)
 from oracle import transnet_ref as R
 from retargetvid_amd import _lib, transnetv1_handler as Hd
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs')]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures('poisoned_outputs', 'poisoned_workspaces')]
 
 # (ATOL, RTOL, logit tolerance); a cell's and a pool's max|ref| is that of the cell's pre-ReLU values.  Measured on the MI355X
 # (profiles/transnet_layer_error.md), largest over every layer, variant and case: bf16x6 with every tile knob 2.1e-6 of max|ref|, f32

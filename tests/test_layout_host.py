@@ -113,7 +113,7 @@ def test_the_struct_is_the_headers():
 
 def test_abi_version_agrees_everywhere():
     hdr = open(os.path.join(ROOT, 'include', 'svc.h')).read()
-    assert int(re.search(r'#define SVC_ABI_VERSION (\d+)', hdr).group(1)) == _lib.ABI_VERSION == _lib.load().svc_abi_version() == 12
+    assert int(re.search(r'#define SVC_ABI_VERSION (\d+)', hdr).group(1)) == _lib.ABI_VERSION == _lib.load().svc_abi_version() == 13
     assert re.search(r'\* 12 = .*svc_resize_frames_layout.*svc_render_crops_layout', hdr)
     lib = _lib.load()
     assert hasattr(lib, 'svc_resize_frames_layout') and hasattr(lib, 'svc_render_crops_layout')

@@ -39,12 +39,12 @@ def test_header_binding_and_exports_agree():
     assert fn.argtypes == want and fn.restype == i32
 
 
-def test_abi_version_is_12_everywhere_and_the_history_names_the_entry():
+def test_abi_version_agrees_everywhere_and_the_history_names_the_entry():
     hdr = _header()
-    assert int(re.search(r'#define SVC_ABI_VERSION (\d+)', hdr).group(1)) == _lib.ABI_VERSION == _lib.load().svc_abi_version() == 12
+    assert int(re.search(r'#define SVC_ABI_VERSION (\d+)', hdr).group(1)) == _lib.ABI_VERSION == _lib.load().svc_abi_version() == 13
     assert re.search(r'\* 12 = .*svc_resize_frames_layout.*svc_render_crops_layout', hdr)       # the line is not reshaped
     history = hdr[hdr.index('ABI revision of the loaded library'):hdr.index('#define SVC_ABI_VERSION')]
-    assert ENTRY in history and '(12, no bump)' in history
+    assert ENTRY in history[history.index('(12, no bump)'):history.index(' * 13 = ')]      # the entry came under revision 12, without a bump
     assert ctypes.sizeof(_lib.SvcFrameLayout) == 40             # the struct is the one the frames' layout uses, unchanged
 
 

@@ -35,7 +35,7 @@ def test_header_binding_and_abi_version_agree():
     ids = {k: int(v) for k, v in re.findall(r'#define SVC_FILTER_([A-Z]+)\s+(\d+)', text)}
     assert ids == {'LINEAR': _lib.FILTER_LINEAR, 'LANCZOS': _lib.FILTER_LANCZOS}
     assert [ids[k.upper()] for k in ops.INTERPS] == [0, 1] and ops.INTERPS == ('linear', 'lanczos')
-    assert int(re.search(r'#define SVC_ABI_VERSION (\d+)', text).group(1)) == 12 == _lib.ABI_VERSION == lib.svc_abi_version()
+    assert int(re.search(r'#define SVC_ABI_VERSION (\d+)', text).group(1)) == 13 == _lib.ABI_VERSION == lib.svc_abi_version()
 
 
 def test_entry_checks_its_arguments():
