@@ -88,7 +88,8 @@ const char *svc_last_error(void);
  *     SvcColour with svc_resize_frames_colour and svc_render_crops_colour (NV12 colour): a new struct and two new entries; and
  *     svc_render_crops_to_layout (pitched output): one new entry that takes the existing SvcFrameLayout, unchanged, for the output; and
  *     svc_render_windows_q8 (sub-pixel windows): one new entry, no struct; and svc_debug_tail_plan (SVC_TAILPLAN_*): one new test door; and
- *     SVC_NODE_MAP / SVC_NODE_MAP_PROFILE: two new node ids of svc_debug_run_node, which an older library refuses as unknown.
+ *     SVC_NODE_MAP / SVC_NODE_MAP_PROFILE: two new node ids of svc_debug_run_node, which an older library refuses as unknown; and
+ *     svc_debug_sort_plan (SVC_SORTPLAN_*): one new test door that takes no handle, no struct.
  * 13 = svc_debug_scratch_fill exists. */
 #define SVC_ABI_VERSION 13
 int svc_abi_version(void);
@@ -571,6 +572,16 @@ int svc_debug_cluster_state(SvcHandle *h, int frame, int cap, uint32_t *pts_host
  * arbitrary keys: order_host[p] = index of the key that the sort puts at position p.  n <= 65535.  Synchronises.
  * Returns n (or a negative error). */
 int svc_debug_argsort_u32(SvcHandle *h, const uint32_t *keys_host, int n, int32_t *order_host);
+/* Test/diagnostic door: what that routine (k_sort and the door above alike) decides from the number of keys alone -- host
+ * arithmetic, the very function the kernels carve their working arrays by; needs no handle and no GPU:
+ * out[0 .. SVC_SORTPLAN_WORDS) = the SVC_SORTPLAN_* words below.  Returns SVC_SORTPLAN_WORDS.  SVC_E_INVALID: out NULL, cap below
+ * SVC_SORTPLAN_WORDS, n outside 1 .. 65535. */
+#define SVC_SORTPLAN_IN_LDS 0     /* 1: the 16 bytes per key of working arrays are in LDS (0: in global scratch)           */
+#define SVC_SORTPLAN_NSEG 1       /* capacity of the per-range tables: ranges alive at one depth of the recursion          */
+#define SVC_SORTPLAN_DEPTH 2      /* the depth limit, 2 * floor(log2 n): a range popped below it is heap-sorted            */
+#define SVC_SORTPLAN_LDS_BYTES 3  /* LDS bytes the routine uses: the range tables, and the working arrays when IN_LDS      */
+#define SVC_SORTPLAN_WORDS 4
+int svc_debug_sort_plan(int n, int32_t *out, int cap);
 
 /* ---- TransNet V1 shot-boundary network ----
  * Replaces ShotTransNet._restore / predict_raw (3rd_party_libs/transnetv1/transnetv1_handler.py:86-97; the reference

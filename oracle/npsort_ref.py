@@ -75,7 +75,8 @@ def aheapsort(v, a, lo, n):
 
 
 def argsort(keys, stats=None):
-    """np.argsort(keys) (default kind) for a 1-D sequence of numbers, scalar code path.  -> list of indices."""
+    """np.argsort(keys) (default kind) for a 1-D sequence of numbers, scalar code path.  -> list of indices.
+    stats (a dict, optional): 'heapsorts' counts the ranges that ran out of depth, 'ranges' lists them as (lo, n, cdepth)."""
     v = [x for x in keys]
     num = len(v)
     a = list(range(num))
@@ -88,6 +89,7 @@ def argsort(keys, stats=None):
         if cdepth < 0:
             if stats is not None:
                 stats['heapsorts'] = stats.get('heapsorts', 0) + 1
+                stats.setdefault('ranges', []).append((pl, pr - pl + 1, cdepth))      # (lo, n, cdepth) of every heap-sorted range
             aheapsort(v, a, pl, pr - pl + 1)
         else:
             while pr - pl > SMALL_QUICKSORT:

@@ -22,7 +22,7 @@ EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'sv
            'svc_resize_frames_nv12', 'svc_render_crops_nv12', 'svc_render_crops_u8_to_nv12', 'svc_render_crops_nv12_to_nv12', 'svc_debug_run_node',
            'svc_resize_frames_layout', 'svc_render_crops_layout', 'svc_render_crops_filter', 'svc_debug_net_plan',
            'svc_resize_frames_colour', 'svc_render_crops_colour', 'svc_render_crops_to_layout',
-           'svc_render_windows_q8', 'svc_debug_tail_plan', 'svc_debug_scratch_fill')
+           'svc_render_windows_q8', 'svc_debug_tail_plan', 'svc_debug_scratch_fill', 'svc_debug_sort_plan')
 
 
 class SvcParams(ctypes.Structure):
@@ -51,7 +51,7 @@ RANGE_LIMITED, RANGE_FULL = 0, 1        # include/svc.h: SVC_RANGE_*
 
 
 COLOUR_ENTRIES = ('svc_resize_frames_colour', 'svc_render_crops_colour')
-LATER_ENTRIES = COLOUR_ENTRIES + ('svc_render_crops_to_layout', 'svc_render_windows_q8', 'svc_debug_tail_plan')        # entries that came without an ABI bump: bound where the build has them
+LATER_ENTRIES = COLOUR_ENTRIES + ('svc_render_crops_to_layout', 'svc_render_windows_q8', 'svc_debug_tail_plan', 'svc_debug_sort_plan')        # entries that came without an ABI bump: bound where the build has them
 
 
 class SvcColour(ctypes.Structure):
@@ -126,6 +126,9 @@ def load():
     # (svc_debug_tail_plan likewise: Engine.tail_plan on an older build fails by the symbol's name)
     if hasattr(lib, 'svc_debug_tail_plan'):
         lib.svc_debug_tail_plan.argtypes = [vp, i32, i32, ctypes.POINTER(SvcParams), vp, i32]
+    # (svc_debug_sort_plan likewise: ops.sort_plan on an older build fails by the symbol's name)
+    if hasattr(lib, 'svc_debug_sort_plan'):
+        lib.svc_debug_sort_plan.argtypes = [i32, vp, i32]
     lib.svc_saliency_u8.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.svc_saliency_thresholded_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp]
     lib.svc_threshold_u8.argtypes = [vp, vp, sz, i32, vp]

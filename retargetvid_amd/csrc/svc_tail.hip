@@ -2000,6 +2000,22 @@ struct SortSegs {                // capacity n / 17 + 2 ranges, two generations
     uint32_t *vp, *K;
 };
 
+// The arithmetic of sort_carve and the depth limit, stated once for the kernels and for the plan door (svc_debug_sort_plan):
+// the bytes of the per-range tables (always in LDS, behind the block-scan slots) and whether the 16 bytes per edge fit behind them.
+struct SortPlan { int nseg, depth, head_bytes, lds_bytes; bool in_lds; };
+__host__ __device__ inline size_t sort_round16(size_t bytes) { return (bytes + 15) / 16 * 16; }      // carve's rounding
+__host__ __device__ inline SortPlan sort_plan(int n) {
+    SortPlan P;
+    P.nseg = n / 17 + 2;
+    P.depth = 0;
+    for (int v = n >> 1; v; v >>= 1) P.depth += 2;                                                  // 2 * npy_get_msb(n)
+    const size_t head = sort_round16((NW16 + 4) * sizeof(int)) + 9 * sort_round16((size_t)P.nseg * 2) + 2 * sort_round16((size_t)P.nseg * 4);
+    P.head_bytes = (int)head;
+    P.in_lds = head + (size_t)n * 16 + 6 * 16 <= SORT_LDS_BYTES;
+    P.lds_bytes = (int)(P.in_lds ? head + 2 * sort_round16((size_t)n * 4) + 4 * sort_round16((size_t)n * 2) : head);
+    return P;
+}
+
 __device__ __forceinline__ void sort_swap(const SortArrays &a, int i, int j) {
     const uint32_t k = a.key[i]; a.key[i] = a.key[j]; a.key[j] = k;
     const uint16_t x = a.idx[i]; a.idx[i] = a.idx[j]; a.idx[j] = x;
@@ -2042,9 +2058,7 @@ __device__ __forceinline__ void np_argsort_block(const SortArrays &a, const Sort
     if (tid == 0) {
         cnt[0] = cnt[1] = 0;
         if (n - 1 > SORT_SMALL) {
-            int d = 0;
-            for (int v = n >> 1; v; v >>= 1) ++d;          // npy_get_msb(n)
-            st.lo[0][0] = 0; st.hi[0][0] = (uint16_t)(n - 1); st.dep[0][0] = (int16_t)(2 * d);
+            st.lo[0][0] = 0; st.hi[0][0] = (uint16_t)(n - 1); st.dep[0][0] = (int16_t)sort_plan(n).depth;    // 2 * npy_get_msb(n)
             cnt[0] = 1;
         }
     }
@@ -2173,13 +2187,14 @@ __device__ __forceinline__ void np_argsort_block(const SortArrays &a, const Sort
 
 // carve the working arrays of np_argsort_block: in LDS when they fit, else in the caller's global scratch
 __device__ __forceinline__ void sort_carve(uint8_t *lds, uint8_t *glob, int n, SortArrays &a, SortSegs &st, int *&sh) {
+    const SortPlan P = sort_plan(n);
     uint8_t *p = lds;
     sh = carve<int>(p, NW16 + 4);
-    const int nseg = n / 17 + 2;
+    const int nseg = P.nseg;
     for (int g = 0; g < 2; ++g) { st.lo[g] = carve<uint16_t>(p, nseg); st.hi[g] = carve<uint16_t>(p, nseg); st.dep[g] = carve<int16_t>(p, nseg); }
     st.pi = carve<uint16_t>(p, nseg); st.ls = carve<uint16_t>(p, nseg); st.rs = carve<uint16_t>(p, nseg);
     st.vp = carve<uint32_t>(p, nseg); st.K = carve<uint32_t>(p, nseg);
-    uint8_t *q = ((size_t)(p - lds) + (size_t)n * 16 + 6 * 16 <= SORT_LDS_BYTES) ? p : glob;
+    uint8_t *q = P.in_lds ? lds + P.head_bytes : glob;
     a.key = carve<uint32_t>(q, n); a.scan = carve<uint32_t>(q, n);
     a.idx = carve<uint16_t>(q, n); a.seg = carve<uint16_t>(q, n); a.lpos = carve<uint16_t>(q, n); a.rpos = carve<uint16_t>(q, n);
 }
@@ -3232,6 +3247,15 @@ extern "C" int svc_debug_argsort_u32(SvcHandle *h, const uint32_t *keys_host, in
     SVC_HIP(hipMemcpy(o.data(), out.p, (size_t)n * 2, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) order_host[i] = o[i];
     return n;
+}
+
+// Test door (no handle, no launch): what sort_carve decides for n keys (include/svc.h: SVC_SORTPLAN_*)
+extern "C" int svc_debug_sort_plan(int n, int32_t *out, int cap) {
+    if (!out || cap < SVC_SORTPLAN_WORDS || n < 1 || n > 65535) { svc_set_error("svc_debug_sort_plan: invalid argument"); return SVC_E_INVALID; }
+    const SortPlan P = sort_plan(n);
+    out[SVC_SORTPLAN_IN_LDS] = P.in_lds ? 1 : 0; out[SVC_SORTPLAN_NSEG] = P.nseg;
+    out[SVC_SORTPLAN_DEPTH] = P.depth; out[SVC_SORTPLAN_LDS_BYTES] = P.lds_bytes;
+    return SVC_SORTPLAN_WORDS;
 }
 
 extern "C" int svc_debug_cluster_state(SvcHandle *h, int frame, int cap, uint32_t *pts_host, uint32_t *core_host,

@@ -26,6 +26,9 @@ PLAN_WORDS = ('NH', 'NW', 'hks', 'vks', 'fr_ok', 'fr_nr', 'fr_nc', 'fr_tiles_y',
 TAIL_PLAN_WORDS = ('h', 'w', 'fused', 'lvl_big', 'tree_fallback', 'cap_cl', 'cap_cl_huge', 'LVL_CAP', 'TP_CAP', 'TP_CAP_BIG', 'TREE_LDS_CAP',
                    'TREE_LDS_CLUSTERS', 'n_ring', 'n_ring1', 'RING_R', 'RING_R1', 'CORE_REG_STEP', 'CORE_REG_MAX', 'core_lds_max')
 
+# words of svc_debug_sort_plan (include/svc.h: SVC_SORTPLAN_*), in order
+SORT_PLAN_WORDS = ('in_lds', 'nseg', 'depth', 'lds_bytes')
+
 # words of a frame header, cluster_state(...)['hdr'] (include/svc.h: SVC_HDR_*, the same numbers; a range is its first word and a count)
 HDR_WORDS = 32
 HDR_N, HDR_NSEL, HDR_KEPT, HDR_CLUSTERED, HDR_NCLUSTERS = 0, 1, 2, 3, 4
@@ -47,6 +50,20 @@ def net_plan(height, width):
     if n != len(PLAN_WORDS):
         raise _lib.SvcError('svc_debug_net_plan reports %d words, this binding knows %d' % (n, len(PLAN_WORDS)))
     return dict(zip(PLAN_WORDS, (int(v) for v in out)))
+
+
+def sort_plan(n):
+    """Test door (svc_debug_sort_plan): what the edge sort (k_sort, Engine.argsort_u32) decides from the number of keys alone, as a
+    dict of SORT_PLAN_WORDS -- 'in_lds': the working arrays are in LDS (0: in global scratch), 'nseg', 'depth' (the depth limit,
+    2 * floor(log2 n)), 'lds_bytes'.  The function the kernels carve their arrays by, run on the host: needs no GPU."""
+    lib = _lib.load()
+    if not hasattr(lib, 'svc_debug_sort_plan'):
+        raise _lib.SvcError('%s lacks svc_debug_sort_plan: the plan door of the edge sort needs a build that has it' % _lib.LIB_PATH)
+    out = (ctypes.c_int32 * len(SORT_PLAN_WORDS))()
+    got = _lib.check(lib.svc_debug_sort_plan(int(n), ctypes.cast(out, ctypes.c_void_p), len(SORT_PLAN_WORDS)))
+    if got != len(SORT_PLAN_WORDS):
+        raise _lib.SvcError('svc_debug_sort_plan reports %d words, this binding knows %d' % (got, len(SORT_PLAN_WORDS)))
+    return dict(zip(SORT_PLAN_WORDS, (int(v) for v in out)))
 
 
 def scratch_fill(byte):

@@ -15,6 +15,11 @@ function of the map, and the frame header (ops.HDR_*) records which one was take
               HDR_BACK_DONE.  k_tree (every map of the reference engine): the LDS form up to TREE_LDS_CAP points, retried in
               global memory beyond TREE_LDS_CLUSTERS clusters.
 
+  k_sort      its form follows from the number of edges N - 1 alone and has a door of its own (ops.sort_plan ->
+              svc_debug_sort_plan: working arrays in LDS or in the workspace, the depth limit): insertion sort up to 16 elements,
+              partition above, heapsort for a range popped below the depth limit.  Its cases and their census live in
+              tests/edge_order_cases.py, tests/test_edge_order_host.py and tests/test_gpu_edge_order.py; header: HDR_T_SORTED.
+
 Nothing here restates a formula of plan_tail: every threshold is read from the plan dict.  What IS restated is the order of the
 ring table (offsets sorted by squared distance, stable over dr then dc ascending), which decides the slot of a point's k-th hit;
 its length is checked against the plan's n_ring / n_ring1."""

@@ -184,6 +184,33 @@ def test_tail_plan_door_checks_its_arguments():
     assert int(re.search(r'#define SVC_TAILPLAN_WORDS (\d+)', text).group(1)) == n
 
 
+def test_sort_plan_door_words_and_argument_checks():
+    """svc_debug_sort_plan (no ABI bump; needs no handle and no GPU): every SVC_SORTPLAN_* of include/svc.h is a word of
+    ops.SORT_PLAN_WORDS at the same index (case aside); n outside 1 .. 65 535, no output or too few words are refused with
+    SVC_E_INVALID and a message; the entry came under revision 12 without a bump and is bound where the build has it."""
+    from retargetvid_amd import ops
+    lib = _lib.load()
+    text = open(os.path.join(ROOT, 'include', 'svc.h')).read()
+    words = {k: int(v) for k, v in re.findall(r'#define SVC_SORTPLAN_([A-Z0-9_]+)\s+(\d+)', text)}
+    n = words.pop('WORDS')
+    assert n == len(ops.SORT_PLAN_WORDS) and words == {w.upper(): i for i, w in enumerate(ops.SORT_PLAN_WORDS)}
+    history = text[:text.index('#define SVC_ABI_VERSION')]
+    assert 'svc_debug_sort_plan' in history[history.index('(12, no bump)'):history.index(' * 13 = ')]
+    assert 'svc_debug_sort_plan' in _lib.EXPORTS and 'svc_debug_sort_plan' in _lib.LATER_ENTRIES
+    out = (ctypes.c_int32 * n)()
+    ptr = ctypes.cast(out, ctypes.c_void_p)
+    assert lib.svc_debug_sort_plan(1000, ptr, n) == n
+    for args in ((0, ptr, n), (-1, ptr, n), (65536, ptr, n), (1000, None, n), (1000, ptr, n - 1)):
+        assert lib.svc_debug_sort_plan(*args) == -1 and b'svc_debug_sort_plan' in lib.svc_last_error(), args
+    for bad in (0, 65536):
+        with pytest.raises(_lib.SvcError):
+            ops.sort_plan(bad)
+    for k in (1, 2, 3, 4, 1000, 32767, 32768, 65535):
+        plan = ops.sort_plan(k)
+        assert plan['depth'] == 2 * (k.bit_length() - 1) and plan['nseg'] == k // 17 + 2, k
+        assert 0 < plan['lds_bytes'] and (plan['lds_bytes'] >= 16 * k) == bool(plan['in_lds']), k
+
+
 def test_scratch_fill_door_takes_a_byte_or_off_and_nothing_else():
     """svc_debug_scratch_fill (ABI 13; needs no handle and no GPU): -1 and every byte are accepted, anything else is refused with
     SVC_E_INVALID and a message; ops.scratch_fill(None) is -1; the switch ends off."""

@@ -38,40 +38,13 @@ from sklearn.cluster import HDBSCAN                  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import cv_ref, hdbscan_ref as H, npsort_ref, pipeline_ref as P, tail_ref as T, unisal_ref as U     # noqa: E402
 from retargetvid_amd import synth, weights                                                                     # noqa: E402
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+from edge_order_cases import killer                  # noqa: E402  (McIlroy's adversary: one definition, the tests' -- they cannot import this script, which re-executes itself)
 
 warnings.filterwarnings('ignore')
 
 
 # ---- part 0: the sort ------------------------------------------------------------------------------------
-def killer(n):
-    """McIlroy's adversary run against the restated introsort: a key array on which it degenerates, so that the
-    depth limit is hit and popped ranges are heap-sorted."""
-    gas = n
-    val = [gas] * n
-    state = dict(nsolid=0, cand=0)
-
-    class Item:
-        __slots__ = ('i',)
-
-        def __init__(self, i):
-            self.i = i
-
-        def __lt__(self, other):
-            x, y = self.i, other.i
-            if val[x] == gas and val[y] == gas:
-                f = x if x == state['cand'] else y
-                val[f] = state['nsolid']
-                state['nsolid'] += 1
-            if val[x] == gas:
-                state['cand'] = x
-            elif val[y] == gas:
-                state['cand'] = y
-            return val[x] < val[y]
-
-    npsort_ref.argsort([Item(i) for i in range(n)])
-    return np.array([v if v != gas else n for v in val], np.float64)
-
-
 def part0():
     r = np.random.RandomState(1)
     out, n_heap = {}, 0
