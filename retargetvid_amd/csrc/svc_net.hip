@@ -1698,7 +1698,8 @@ static int launch_dw(SvcHandle *h, hipStream_t s, const float *X, const SvcLayer
 // One workgroup = one patch of 32 pixels (PW x 32/PW) of one frame x NT*32 output channels.  Its four
 // waves split the K (channel) range in 32-channel chunks, chunk c -> wave c % 4, and each wave works
 // alone, without barriers: it computes the depthwise output of its chunk for the 32 pixels (a lane owns
-// 4 consecutive pixels x 4 channels: 18 tap loads + 9 weights for 4 outputs, like k_dw_tile), parks the
+// 4 consecutive pixels x 4 channels: 18 tap loads + 9 weights for 4 outputs, like k_dw_tile; the taps are
+// range-checked buffer loads from a resource that spans the frame, so the halo costs no instruction), parks the
 // 32 x 32 tile in its private LDS slab in MFMA A layout, and multiplies it with the chunk's slice of the
 // project weights (B straight from global/L2) into NT accumulators.  The four partial sums meet in LDS at
 // the end and are added in wave order, so the result is deterministic and independent of the batch.
@@ -1713,6 +1714,13 @@ static int launch_dw(SvcHandle *h, hipStream_t s, const float *X, const SvcLayer
 #ifndef IRB_STAMP
 #define IRB_STAMP(i)   // phase stamps of k_irb: defined by tools/micro/irb_phases.hip only (no code in the product)
 #endif
+
+// 16 bytes through a buffer resource: vector offset voff (range-checked against the resource's size: 0 comes back from beyond
+// it, and nothing is read), scalar offset soff (wave-uniform, not checked)
+__device__ __forceinline__ float4 buffer_load_float4(__amdgpu_buffer_rsrc_t rs, unsigned voff, int soff) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, soff, 0);
+    return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+}
 
 // MX (round 5): the project GEMM on split-bf16 operands (x3_split): Wp is the X3_LANES copy (lw_tiles column tiles), the wave's
 // depthwise tile is split as it is read back from the slab (each element once per workgroup), a 32-channel chunk = two 16-deep steps.
@@ -1740,7 +1748,6 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2, 8))
     const int c4 = lane & 7, p0 = (lane >> 3) * 4;
     const int py = p0 / PW, pxs = p0 % PW;
     const int oy = y0 + py, ox0 = x0 + pxs;
-    const float *xf = X + (size_t)f * H * W * C;
     float *D = Dw[wave];
     f32x16 acc[NT];
 #pragma unroll
@@ -1752,8 +1759,27 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2, 8))
     // s_waitcnt vmcnt(0), and the project weights of a k-step requested only when its MFMAs were next: a full L2 round
     // trip per 8-deep k-step).  So: (1) the chunk's slice of the project weights is requested FIRST and parked in
     // registers through the depthwise phase (NT <= 2: the whole 32-deep slice; wider tiles keep one k-step in flight
-    // ahead of the MFMAs); (2) the 18 tap loads are unconditional -- coordinates clamped into the image, out-of-image
-    // taps zeroed by a select -- so they are issued back to back.  A zeroed tap adds 0 * w: the sums are unchanged.
+    // ahead of the MFMAs); (2) the 18 tap loads are unconditional, issued back to back, and an out-of-image tap costs
+    // no instruction in the chunk loop: the taps are range-checked buffer loads from a resource that spans the frame
+    // (H*W*C*4 bytes: launch_dwpw holds that below 2^31), and a load whose vector offset is not below that size returns
+    // 0 without touching memory.  Whether a tap lies in the image depends on the lane's pixel and the tap, not on the
+    // chunk, so the 18 byte offsets (channel group included) are fixed here, an out-of-image tap at DWPW_OOB, and the
+    // chunk's channel offset rides in the scalar offset, which the range check does not see -- no tap in the image plus
+    // a chunk offset leaves its pixel, let alone the frame.  A zeroed tap adds 0 * w: the sums are unchanged.
+    constexpr unsigned DWPW_OOB = 0x80000000u;
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)(X + (size_t)f * H * W * C), 0, H * W * C * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)Wd, 0, 9 * C * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void *)bd, 0, C * 4, 0x00020000);
+    unsigned toff[3][6];
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        const int iy = oy - 1 + ky;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const int ix = ox0 - 1 + j;
+            toff[ky][j] = (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W ? (unsigned)((iy * W + ix) * C * 4 + 16 * c4) : DWPW_OOB;
+        }
+    }
     constexpr bool PRE = false;        // (the whole 32-deep slice in registers costs the second wave per SIMD: 22 -> 33 us at NT = 2)
     const float *wrow[NT];
 #pragma unroll
@@ -1761,7 +1787,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2, 8))
         wrow[t] = lw_tiles ? Wp + ((size_t)min((int)blockIdx.y * NT + t, lw_tiles - 1) * 64 + lane) * 4
                            : Wp + (size_t)min(n0 + t * 32 + r, Npad - 1) * C + 4 * hh;
     const size_t wstep = lw_tiles ? (size_t)lw_tiles * 256 : 8;      // floats from one k-step's float4 to the next
-    for (int ch = wave; ch < nchunks; ch += NWV) {
+    for (int ch = __builtin_amdgcn_readfirstlane(wave); ch < nchunks; ch += NWV) {     // (a scalar: the taps' scalar offset)
         const int kend = min(32, C - ch * 32);
         float4 Bw[PRE ? NT : 1][4];
         if (PRE) {
@@ -1771,52 +1797,43 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2, 8))
                 for (int q = 0; q < 4; ++q)
                     Bw[PRE ? t : 0][q] = *(const float4 *)(wrow[t] + wstep * (ch * 4 + min(q, (kend >> 3) - 1)));      // (a short last chunk re-reads its last k-step: unused)
         }
-        const int c = ch * 32 + c4 * 4;
-        const bool cok = c < C;
-        const int cc = cok ? c : 0;
+        // The depthwise weights and the bias come the same way (resources over Wd's 9 rows and over bd; the lane's channel
+        // group in the vector offset, tap row and chunk in the scalar offset): no 64-bit address arithmetic in the loop.
+        // A short last chunk (C % 32 != 0: post_cnn, C = 1296) is the only place where a lane's channel group can lie
+        // beyond C, where the chunk offset would carry its loads out of the pixel and out of the weight rows: there, on a
+        // wave-uniform path, such a lane loads everything at DWPW_OOB -- taps, weights and bias 0 -- and so parks
+        // relu6(0 * 0 + 0) = 0 in the slab, as the select did that stood here.
         float4 o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         {
-            float4 w[9];
+            float4 w[9], row[3][6], b;
+            const auto dw_loads = [&](bool cok) {
+                const unsigned cvo = cok ? 16u * c4 : DWPW_OOB;
 #pragma unroll
-            for (int t = 0; t < 9; ++t) w[t] = *(const float4 *)(Wd + (size_t)t * C + cc);
+                for (int t = 0; t < 9; ++t) w[t] = buffer_load_float4(wrs, cvo, (t * C + ch * 32) * 4);
 #pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                const int iy = oy - 1 + ky, iyc = min(max(iy, 0), H - 1);
-                const bool yok = iy >= 0 && iy < H;
-                float4 row[6];
+                for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    const int ix = ox0 - 1 + j, ixc = min(max(ix, 0), W - 1);
-                    if (NT >= 5) {                          // five accumulator tiles: keep the loads conditional (fewer live registers: 108 instead of 187 VGPRs)
-                        row[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (yok && ix >= 0 && ix < W) row[j] = *(const float4 *)(xf + ((size_t)iy * W + ix) * C + cc);
-                    } else {
-                        row[j] = *(const float4 *)(xf + ((size_t)iyc * W + ixc) * C + cc);
-                    }
-                }
-                if (NT < 5) {
+                    for (int j = 0; j < 6; ++j) row[ky][j] = buffer_load_float4(xrs, cok ? toff[ky][j] : DWPW_OOB, ch * 128);
+                b = buffer_load_float4(brs, cvo, ch * 128);
+            };
+            if (kend < 32) dw_loads(ch * 32 + c4 * 4 < C);
+            else dw_loads(true);
 #pragma unroll
-                    for (int j = 0; j < 6; ++j) {
-                        const int ix = ox0 - 1 + j;
-                        if (!(yok && ix >= 0 && ix < W)) row[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-                }
+            for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
 #pragma unroll
                     for (int kx = 0; kx < 3; ++kx) {
-                        fma4(o[j], row[j + kx], w[ky * 3 + kx]);
+                        fma4(o[j], row[ky][j + kx], w[ky * 3 + kx]);
                     }
-            }
-            const float4 b = *(const float4 *)(bd + cc);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                o[j].x = cok ? fminf(fmaxf(o[j].x + b.x, 0.f), 6.f) : 0.f;
-                o[j].y = cok ? fminf(fmaxf(o[j].y + b.y, 0.f), 6.f) : 0.f;
-                o[j].z = cok ? fminf(fmaxf(o[j].z + b.z, 0.f), 6.f) : 0.f;
-                o[j].w = cok ? fminf(fmaxf(o[j].w + b.w, 0.f), 6.f) : 0.f;
+                o[j].x = fminf(fmaxf(o[j].x + b.x, 0.f), 6.f);
+                o[j].y = fminf(fmaxf(o[j].y + b.y, 0.f), 6.f);
+                o[j].z = fminf(fmaxf(o[j].z + b.z, 0.f), 6.f);
+                o[j].w = fminf(fmaxf(o[j].w + b.w, 0.f), 6.f);
             }
         }
 #pragma unroll
@@ -2125,6 +2142,12 @@ static int launch_dwpw(SvcHandle *h, hipStream_t s, const float *X, const SvcLay
                        int ldr, float *Y, int ldy, int n, int H, int W) {
     ProfScope ps(h, SVC_K_PW, s);
     const int C = Ld.cout, N = Lp.cout, Npad = (N + 31) / 32 * 32, tiles = Npad / 32;
+    // the kernel reads its taps through a buffer resource that spans one frame, by 32-bit byte offsets of which the upper
+    // half of the range stands for "outside the image"
+    if ((size_t)H * W * C * 4 >= ((size_t)1 << 31)) {
+        svc_set_error("k_dwpw: a frame of %d x %d x %d floats does not fit a 2 GiB buffer resource", H, W, C);
+        return SVC_E_INVALID;
+    }
     // output-channel groups of at most DWPW_MAX_NT tiles, as even as possible (the depthwise part is redone per group)
     const int groups = ceil_div(tiles, DWPW_MAX_NT), nt = ceil_div(tiles, groups);
     const int pw = (W % 8 == 0 || W > 16) ? 8 : 16;          // 8x4 patches; 16x2 on the narrow 13-wide level
