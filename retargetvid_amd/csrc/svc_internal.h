@@ -67,7 +67,7 @@ __device__ __forceinline__ uint32_t fdivmod(uint32_t n, const FDiv &f, uint32_t 
 //            SvcHandle::rs_maps the shrunk maps of one svc_cluster_center call (resize_factor > 1)
 //            SvcHandle::tail_ws the round list and the per-map slots of one svc_cluster_center call.  It holds indices and
 //                               counts, so it is always filled with 0x00: a stale read changes a result, never an address
-//   state    blob, shot_blob (weights), w_copies, shot_w3, stem_wt (their re-ordered copies), cvtabs, lztabs, rs_tabs,
+//   state    blob, shot_blob (weights), w_copies, shot_w3, stem_wt, smooth_pad (their re-ordered copies), cvtabs, lztabs, rs_tabs,
 //            NetPlan::hb/hk/vb/vk/fr_vt/fr_ht (resampling tables), tail_offsets, tail_ring_cnt, tail_delta (ring tables),
 //            NetPlan::lut, NetPlan::gauss (constants of a plan), census (totals that accumulate over calls by contract),
 //            depth_pinned (host staging ring: calls still in flight read their slot)
@@ -147,6 +147,7 @@ struct SvcHandle {
     DevBuf census;                     // threshold census (svc_threshold_census): [4] u64 totals, then [chunk][4] u32 per-frame counts of the last pass
     unsigned long long census_maps = 0;
     DevBuf stem_wt;                    // stem weights transposed to [32 out][32 taps, 27 used] for the MFMA stem
+    DevBuf smooth_pad;                 // the smoothing phase table padded to [64 phases][56 taps, 49 used]: k_smooth_down_mfma's LDS image
     bool front = true;                 // LANCZOS + features.0 + features.1 as one kernel, k_front (SVC_FRONT=0: three kernels)
     bool keep_input = false;           // ... which then also writes the normalised network input for svc_debug_tap(SVC_TAP_INPUT) (SVC_KEEP_INPUT=1)
     int sd_rows = 0;                   // output rows per workgroup of k_smooth_down_mfma at most (0: SD_ROWS; SVC_SD_ROWS=1..SD_ROWS: the reference of a bit-identity test; the plan shrinks the band further where its LDS would not fit)

@@ -15,9 +15,11 @@
 //   k_smooth_down_mfma nearest x8 + replicate pad 20 + 41x41 smoothing + bilinear to (h,w)
 //                                                      unisal/model.py:485-495
 //   k_quantise       log-softmax/exp/max/x255/u8 cast  unisal/utils.py:132-136, unisal/train.py:1267-1274
+#include <assert.h>
 #include <math.h>
 
 #include <algorithm>
+#include <utility>
 
 #include "svc_internal.h"
 #include "svc_lanczos.h"
@@ -557,6 +559,33 @@ struct UpsAdd {
 // loads together, and nothing overlaps them).  Transposed through the slab, a store instruction writes 8 rows x 128 B:
 // eight whole lines.
 #define PWR_SLAB 36            // floats per slab row: 32 channels + 4 pad
+// k_pwr: column tiles (of 32) per workgroup.  Measured at B = 32: 1 / 2 / 3 / 4 -> 1.735 / 1.692 / 1.726 / 1.767 ms per pass.
+#define PWR_NT 2
+// A 16-byte global load that stays where it is written and is waited for where the source says.  hipcc orders an ordinary
+// load of read-only memory by its use alone: it sinks it to the block that consumes it, across a sched_barrier too, and a
+// staging sequence "request everything, then store piece by piece" comes out as load / s_waitcnt vmcnt(0) / ds_write per
+// piece -- one dependent round trip each.  The compiler does not count these loads in its own waits (which only makes
+// those stricter: loads return in order); ld16_wait<N> is the wait -- at most N younger vector-memory requests still
+// outstanding -- and the registers pass through it, so no use of them can be scheduled in front of it.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4 ld16_issue(const void *p) {
+    u32x4 v;
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+    return v;
+}
+template <int N>
+__device__ __forceinline__ void ld16_wait(u32x4 &a) {
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void ld16_wait(u32x4 &a, u32x4 &b, u32x4 &c, u32x4 &d) {
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
+}
+// f(integral_constant 0) .. f(integral_constant N - 1): a loop whose index is a constant expression (the wait counts above)
+template <int... I, class F>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F &&f) { (f(std::integral_constant<int, I>{}), ...); }
 // MX (round 5): the split-bf16 form (x3_split above).  Wt is then the X3_ROWS copy of the weight slice (rows of Q * 6 uint4), the
 // chunk in LDS keeps that form (row stride Q * 6 + 1 uint4: an odd number of 16-B slots, conflict-free b128 reads), the wave's
 // activations are split once, in the prologue, and a tile is Q * X3_NP MFMAs of 32 cycles instead of 4 KS of 64.
@@ -582,69 +611,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
     constexpr int NB = KS / 4;                              // blocks of 32 input channels (K is 64, 96, 128 or 160)
     static_assert(KS % 4 == 0, "K must be a multiple of 32");
     const int lrow = lane >> 3, lc4 = (lane & 7) * 4;
-    float4 G[NB][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float *xr = X + (size_t)min(m0 + lrow + 8 * j, M - 1) * ldx + lc4;
-#pragma unroll
-        for (int b = 0; b < NB; ++b) G[b][j] = *(const float4 *)(xr + 32 * b);
-    }
-    // weight chunk and bias chunk -> LDS (coalesced float4 rows)
-    constexpr int K4 = K / 4;
+    // Staging: EVERY global request of the prologue -- the bias, the thread's pieces of the weight chunk, the wave's activations --
+    // is issued before the first wait on any of them, so a workgroup pays one round trip in front of its first MFMA.  (Written as
+    // a loop of "load a piece, store it to LDS", the chunk compiled to one 16-byte load per iteration with an s_waitcnt vmcnt(0)
+    // on it, 6 - 15 dependent round trips, and the activation loads were sunk behind that loop, four at a time in front of
+    // each block's slab writes.)  The requests are ld16_issue, the waits ld16_wait with the count of what was requested later.
+    // The pieces are unconditional -- one past the chunk's end reads piece 0 again and lands in a row's pad slot, which no tile
+    // reads -- and their number is a compile-time bound, NW, from PWR_NT.  The weights are requested FIRST: loads return in
+    // order, so their registers (up to 15 x 4) are free again, written to LDS, before the activations are split into their planes
+    // -- the other order holds both through the split, and the instances with the up-sampled term have no registers to spare.
+    constexpr int C = MX ? Q * 6 : K / 4;                   // 16-byte pieces per weight row (MX: the split row; else floats / 4)
+    constexpr int RSP = MX ? RS : WS / 4;                   // LDS row stride in pieces: C + 1, the last one padding
+    constexpr int NW = (PWR_NT * 32 * C + 255) / 256;       // pieces per thread at most (launch_pw_ex: ntw <= PWR_NT)
+    constexpr int NG = 4 * NB;                              // activation requests per lane
+    static_assert(RSP == C + 1, "a weight row in LDS ends in one pad piece");
     uint4 *wq = (uint4 *)wch;
-    if constexpr (MX) {
-        const uint4 *W3 = (const uint4 *)Wt;
-        for (int i = tid; i < ncols * (Q * 6); i += 256) {
-            const int row = i / (Q * 6), c = i - row * (Q * 6);
-            wq[row * RS + c] = W3[(size_t)(n0 + row) * (Q * 6) + c];
-        }
-    } else {
-        for (int i = tid; i < ncols * K4; i += 256) {
-            const int row = i / K4, c4 = i - row * K4;
-            *(float4 *)(wch + row * WS + c4 * 4) = *(const float4 *)(Wt + (size_t)(n0 + row) * ldw + c4 * 4);
-        }
+    float bv = 0.f;
+    if (bias) bv = bias[min(n0 + tid, N - 1)];              // (an ordinary load: the compiler waits for it where bch is written)
+    const uint32_t wstride = MX ? C * 4 : (uint32_t)ldw;    // floats from one weight row to the next
+    const int npieces = ncols * C;
+    // piece i = tid + 256 k is (row, c) = (i / C, i % C): divided once (by a constant), then stepped
+    const int wrow0 = tid / C, wc0 = tid - wrow0 * C;
+    u32x4 Wr[NW];
+    {
+        int row = wrow0, c = wc0;
+        static_for(std::make_integer_sequence<int, NW>{}, [&](auto k) {
+            const bool in = tid + 256 * k < npieces;
+            Wr[k] = ld16_issue(Wt + (uint32_t)(n0 + (in ? row : 0)) * wstride + (uint32_t)(in ? c : 0) * 4);
+            c += 256 % C; row += 256 / C;
+            if (c >= C) { c -= C; ++row; }
+        });
     }
-    if (tid < ncols) bch[tid] = (bias && n0 + tid < N) ? bias[n0 + tid] : 0.f;
-    float4 A[MX ? 1 : KS];
-    X3 A3[MX ? Q : 1];
+    u32x4 G[NB][4];
 #pragma unroll
-    for (int b = 0; b < NB; ++b) {
+    for (int b = 0; b < NB; ++b)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) *(float4 *)(slab + (lrow + 8 * j) * PWR_SLAB + lc4) = G[b][j];
-        __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): the slab is private to the wave
-        __builtin_amdgcn_wave_barrier();
-        if constexpr (MX) {
-            float4 a[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a[q] = *(const float4 *)(slab + r * PWR_SLAB + 8 * q + 4 * hh);
-            A3[MX ? 2 * b : 0] = x3_split(a[0], a[1]);
-            A3[MX ? 2 * b + 1 : 0] = x3_split(a[2], a[3]);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) A[MX ? 0 : 4 * b + q] = *(const float4 *)(slab + r * PWR_SLAB + 8 * q + 4 * hh);
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();                    // the next block overwrites the slab
-    }
-    __syncthreads();
-    if (m0 >= M) return;
-    // Every load of this wave has landed (the barrier above waited for the weight chunk, requested after the
-    // activations).  Saying so explicitly empties the compiler's vector-memory scoreboard in front of the tile loop, and
-    // the loop itself issues no global load (the bias comes from LDS): otherwise hipcc puts an s_waitcnt vmcnt(0) at the
-    // loop head -- the activation registers count as "possibly pending" on the back edge -- or in front of the first use
-    // of a bias value, and because loads and stores retire in order every tile then waits for the STORES of the tile
-    // before it: the chip alternates between an MFMA phase and a store phase (tools/micro/pw_phases.hip).
-    __builtin_amdgcn_s_waitcnt(0x0f70);                    // vmcnt(0)
-    // store role of the lane: rows (lane >> 3) + 8 it, channels 4 (lane & 7) .. + 3 of the tile
-    const int srow = lane >> 3, sc = (lane & 7) * 4;
-    const int nt = ncols >> 5;
-    // up-sample-add: the four taps and weights of each of the lane's four rows do not depend on the tile
+        for (int j = 0; j < 4; ++j) G[b][j] = ld16_issue(X + (size_t)min(m0 + lrow + 8 * j, M - 1) * ldx + lc4 + 32 * b);
+    __builtin_amdgcn_sched_barrier(0);                      // nothing below is scheduled in between the requests above
+    // up-sample-add: the four taps and weights of each of the lane's four store rows (rows (lane >> 3) + 8 it) do not depend on
+    // the tile.  Integer and float arithmetic only: it runs while the requests above are in flight.
     uint32_t uo[UPS ? 4 : 1][4];
     float uw[UPS ? 4 : 1][4];
     if (UPS) {
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            const int rr = min(m0 + srow + 8 * it, M - 1);
+            const int rr = min(m0 + lrow + 8 * it, M - 1);
             uint32_t ox, oy;
             const uint32_t f = fdivmod(fdivmod((uint32_t)rr, ups.dOW, ox), ups.dOH, oy);
             const float sy = fmaxf(0.5f * (oy + 0.5f) - 0.5f, 0.f), sx = fmaxf(0.5f * (ox + 0.5f) - 0.5f, 0.f);
@@ -655,8 +666,61 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
             uo[UPS ? it : 0][0] = (fb + y0 * ups.UW + x0) * (uint32_t)ups.ldu; uo[UPS ? it : 0][1] = (fb + y0 * ups.UW + x1) * (uint32_t)ups.ldu;
             uo[UPS ? it : 0][2] = (fb + y1 * ups.UW + x0) * (uint32_t)ups.ldu; uo[UPS ? it : 0][3] = (fb + y1 * ups.UW + x1) * (uint32_t)ups.ldu;
             uw[UPS ? it : 0][0] = 1.f - lx1; uw[UPS ? it : 0][1] = lx1; uw[UPS ? it : 0][2] = 1.f - ly1; uw[UPS ? it : 0][3] = ly1;
+            // (computed HERE: left alone, the compiler sinks all of it behind the barrier, in front of the tile loop)
+            asm volatile("" : "+v"(uo[UPS ? it : 0][0]), "+v"(uo[UPS ? it : 0][1]), "+v"(uo[UPS ? it : 0][2]), "+v"(uo[UPS ? it : 0][3]),
+                              "+v"(uw[UPS ? it : 0][0]), "+v"(uw[UPS ? it : 0][1]), "+v"(uw[UPS ? it : 0][2]), "+v"(uw[UPS ? it : 0][3]));
         }
     }
+    __builtin_amdgcn_sched_barrier(0);                      // (and the arithmetic above is not scheduled behind the first wait)
+    // weight chunk and bias chunk -> LDS: the pieces land in the order requested, each store behind its counted wait
+    {
+        int row = wrow0, c = wc0;
+        static_for(std::make_integer_sequence<int, NW>{}, [&](auto k) {
+            ld16_wait<NW - 1 - k + NG>(Wr[k]);
+            *(u32x4 *)(wq + (tid + 256 * k < npieces ? row * RSP + c : (tid & 31) * RSP + C)) = Wr[k];
+            c += 256 % C; row += 256 / C;
+            if (c >= C) { c -= C; ++row; }
+        });
+    }
+    float4 A[MX ? 1 : KS];
+    X3 A3[MX ? Q : 1];
+    static_for(std::make_integer_sequence<int, NB>{}, [&](auto b) {
+        ld16_wait<4 * (NB - 1 - b)>(G[b][0], G[b][1], G[b][2], G[b][3]);        // the blocks behind this one stay in flight
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *(u32x4 *)(slab + (lrow + 8 * j) * PWR_SLAB + lc4) = G[b][j];
+        __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): the slab is private to the wave
+        __builtin_amdgcn_wave_barrier();
+        if constexpr (MX) {
+            float4 a[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[q] = *(const float4 *)(slab + r * PWR_SLAB + 8 * q + 4 * hh);
+            A3[MX ? 2 * b : 0] = x3_split(a[0], a[1]);
+            A3[MX ? 2 * b + 1 : 0] = x3_split(a[2], a[3]);
+            if constexpr (UPS) {                            // split HERE: sunk behind the barrier, the block's 16 floats stay live beside the planes
+                asm volatile("" : "+v"(A3[MX ? 2 * b : 0].h), "+v"(A3[MX ? 2 * b : 0].m), "+v"(A3[MX ? 2 * b : 0].l));
+                asm volatile("" : "+v"(A3[MX ? 2 * b + 1 : 0].h), "+v"(A3[MX ? 2 * b + 1 : 0].m), "+v"(A3[MX ? 2 * b + 1 : 0].l));
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) A[MX ? 0 : 4 * b + q] = *(const float4 *)(slab + r * PWR_SLAB + 8 * q + 4 * hh);
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();                    // the next block overwrites the slab
+    });
+    // (the bias last: the compiler's own wait for it, vmcnt(0), is free here and would drain the activations anywhere above)
+    if (tid < ncols) bch[tid] = n0 + tid < N ? bv : 0.f;
+    __syncthreads();
+    if (m0 >= M) return;
+    // Every load of this wave has landed (the activations, requested last, have been split into their planes above, and
+    // loads return in order).  Saying so explicitly empties the compiler's vector-memory scoreboard in front of the tile loop, and
+    // the loop itself issues no global load (the bias comes from LDS): otherwise hipcc puts an s_waitcnt vmcnt(0) at the
+    // loop head -- the activation registers count as "possibly pending" on the back edge -- or in front of the first use
+    // of a bias value, and because loads and stores retire in order every tile then waits for the STORES of the tile
+    // before it: the chip alternates between an MFMA phase and a store phase (tools/micro/pw_phases.hip).
+    __builtin_amdgcn_s_waitcnt(0x0f70);                    // vmcnt(0)
+    // store role of the lane: rows (lane >> 3) + 8 it, channels 4 (lane & 7) .. + 3 of the tile
+    const int srow = lane >> 3, sc = (lane & 7) * 4;
+    const int nt = ncols >> 5;
     for (int t = 0; t < nt; ++t) {
         const int col = n0 + t * 32 + sc;
         float4 tap[UPS ? 4 : 1][4];
@@ -1072,10 +1136,37 @@ __global__ __launch_bounds__(256) SD_NO_PK void k_smooth_down_mfma(const float *
     const int ylo = (int)fmaxf(scy * (oy0 + 0.5f) - 0.5f, 0.f);
     const int yhi = min((int)fmaxf(scy * ((oy1 - 1) + 0.5f) - 0.5f, 0.f) + 1, NH - 1);
     const int nrows = min(yhi - ylo + 1, tile_cap);
-    for (int i = tid; i < LH * LW; i += 256) L[i] = logit[(size_t)f * LH * LW + i];
-    for (int i = tid; i < 64 * SD_KP; i += 256) {
-        const int p = i / SD_KP, k = i - p * SD_KP;
-        ph[i] = k < 49 ? phase[p * 49 + k] : 0.f;
+    // The frame's logits and the phase table -> LDS as 16-byte pieces, a batch of eight per thread requested before the first is
+    // waited for (ld16_issue / ld16_wait, see k_pwr).  `phase` is the handle's padded [64][SD_KP] copy: the LDS image itself.
+    // (One dword per thread and iteration, each waited for before the next, these were 7 + 14 dependent round trips at 256x416,
+    // the table's behind a divide and a branch -- and the kernel is one round of workgroups: its time is one workgroup's latency.)
+    // LW is a multiple of 4 (net_geometry), so is a frame's offset; a piece past the end reads the last one and is not stored.
+    {
+        constexpr int P4 = 64 * SD_KP / 4;                      // pieces of the table: 3.5 per thread
+        const int n4 = (LH * LW) >> 2;
+        const u32x4 *lg = (const u32x4 *)(logit + (size_t)f * LH * LW), *pt = (const u32x4 *)phase;
+        u32x4 *L4 = (u32x4 *)L, *ph4 = (u32x4 *)ph;
+        u32x4 lr[4], pr[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lr[k] = ld16_issue(lg + min(tid + 256 * k, n4 - 1));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pr[k] = ld16_issue(pt + min(tid + 256 * k, P4 - 1));
+        static_for(std::make_integer_sequence<int, 4>{}, [&](auto k) {
+            ld16_wait<7 - k>(lr[k]);
+            if (tid + 256 * k < n4) L4[tid + 256 * k] = lr[k];
+        });
+        static_for(std::make_integer_sequence<int, 4>{}, [&](auto k) {
+            ld16_wait<3 - k>(pr[k]);
+            if (tid + 256 * k < P4) ph4[tid + 256 * k] = pr[k];
+        });
+        for (int base = 1024; base < n4; base += 1024) {        // (a map of more than 4 096 cells: none of the plan's geometries)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) lr[k] = ld16_issue(lg + min(base + tid + 256 * k, n4 - 1));
+            static_for(std::make_integer_sequence<int, 4>{}, [&](auto k) {
+                ld16_wait<3 - k>(lr[k]);
+                if (base + tid + 256 * k < n4) L4[base + tid + 256 * k] = lr[k];
+            });
+        }
     }
     __syncthreads();
     const int cy_lo = ylo >> 3, cy_hi = (ylo + nrows - 1) >> 3;
@@ -1405,6 +1496,8 @@ static void net_geometry(int height, int width, int sd_rows_max, NetGeom &g, LzT
     // whose LDS fits.  A wide strip (h x 250 with h < 64) spreads few output rows over many network rows; one output row
     // needs two of them, about 24 KB with the logits and the phase table, so every shape has a band that fits.  A pixel is
     // computed from its own cell's MFMA chain and its own four tile values: the map does not depend on the band.
+    // (It stages a frame's logits as 16-byte pieces: NW / 8 is a multiple of 4, the network sizes being multiples of 32.)
+    assert(NH % 32 == 0 && NW % 32 == 0);
     for (g.sd_rows = sd_rows_max > 0 ? std::min(sd_rows_max, SD_ROWS) : SD_ROWS;; --g.sd_rows) {
         g.sd_tile_cap = sd_band_rows(height, NH, g.sd_rows);
         g.sd_lds = ((size_t)(NH / 8) * (NW / 8) + 64 * SD_KP + (size_t)g.sd_tile_cap * NW) * sizeof(float);
@@ -1601,8 +1694,7 @@ static WForm lane_form(const SvcHandle *h, int K) {
     return h->mx && (K & 15) == 0 ? X3_LANES : h->sk_lane && (K & 7) == 0 ? F32_LANES : W_MATRIX;
 }
 
-// k_pwr: column tiles (of 32) per workgroup.  Measured at B = 32: 1 / 2 / 3 / 4 -> 1.735 / 1.692 / 1.726 / 1.767 ms per pass.
-#define PWR_NT 2
+// (PWR_NT, k_pwr's column tiles per workgroup, is defined in front of the kernel: it bounds the registers of its weight staging)
 // k_pw_sk serves a long-K layer (K >= 256) when its row blocks x column tiles, at the nominal batch, do not exceed this.
 #define PW_SK_MAX_WG 2048
 
@@ -2845,7 +2937,7 @@ static int tail_smooth(SvcHandle *h, hipStream_t s, int n, int H3, int W3) {
     const int NH = p->NH, NW = p->NW;
     dim3 grid(ceil_div(p->h, p->sd_rows), n);
     RC(raise_lds_limit(h, (const void *)k_smooth_down_mfma, SD_LDS_MAX));       // (for uniformity, as in net_front: the plan keeps the request within the default)
-    k_smooth_down_mfma<<<grid, 256, p->sd_lds, s>>>(p->buf(B_LOGIT), h->net.smooth.w.dev, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3,
+    k_smooth_down_mfma<<<grid, 256, p->sd_lds, s>>>(p->buf(B_LOGIT), (const float *)h->smooth_pad.p, p->buf(B_PRE), (unsigned *)p->fmax.p, H3, W3,
                                                     NH, NW, p->h, p->w, p->sd_rows, p->sd_tile_cap, make_fdiv(p->w));
     SVC_CHECK_LAUNCH();
     return SVC_OK;
@@ -3321,6 +3413,17 @@ extern "C" int svc_create(const void *blob_host, size_t n_bytes, int device, Svc
     if ((rc = h->stem_wt.ensure(wt.size() * 4))) return rc;
     if (hipMemcpy(h->stem_wt.p, wt.data(), wt.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         svc_set_error("svc_create: stem weight upload failed");
+        return SVC_E_HIP;
+    }
+    // the smoothing phase table [64][49] -> [64][SD_KP], zeros in 49 .. SD_KP - 1: the image k_smooth_down_mfma keeps in LDS, so
+    // that it stages it with whole 16-byte loads
+    const float *ph_host = host + (h->net.smooth.w.dev - dev);
+    std::vector<float> pt(64 * SD_KP, 0.f);
+    for (int p = 0; p < 64; ++p)
+        for (int k = 0; k < 49; ++k) pt[p * SD_KP + k] = ph_host[p * 49 + k];
+    if ((rc = h->smooth_pad.ensure(pt.size() * 4))) return rc;
+    if (hipMemcpy(h->smooth_pad.p, pt.data(), pt.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        svc_set_error("svc_create: smoothing phase table upload failed");
         return SVC_E_HIP;
     }
     *out = h.release();
