@@ -89,7 +89,8 @@ const char *svc_last_error(void);
  *     svc_render_crops_to_layout (pitched output): one new entry that takes the existing SvcFrameLayout, unchanged, for the output; and
  *     svc_render_windows_q8 (sub-pixel windows): one new entry, no struct; and svc_debug_tail_plan (SVC_TAILPLAN_*): one new test door; and
  *     SVC_NODE_MAP / SVC_NODE_MAP_PROFILE: two new node ids of svc_debug_run_node, which an older library refuses as unknown; and
- *     svc_debug_sort_plan (SVC_SORTPLAN_*): one new test door that takes no handle, no struct.
+ *     svc_debug_sort_plan (SVC_SORTPLAN_*): one new test door that takes no handle, no struct; and
+ *     svc_focus_jumps_u8 and svc_host_focus_hold (focus stability from resident maps): two new entries, no handle, no struct.
  * 13 = svc_debug_scratch_fill exists. */
 #define SVC_ABI_VERSION 13
 int svc_abi_version(void);
@@ -450,6 +451,25 @@ int svc_debug_round_plan(const uint8_t *flags_host, int n, int32_t *round_out, i
 /* a[n][4], b[n][4] int32 boxes (x1,y1,x2,y2) -> out[n] float64 IoU, inclusive +1 pixel convention.  Writes out[0 .. n) and nothing else. */
 int svc_iou_i32(const int32_t *a, const int32_t *b, size_t n, double *out, void *stream);
 
+/* The jump statistics of the focus stability (get_points_on_line and the sums of sc_check_for_extra_cuts, smartVidCrop.py:1337-1455)
+ * from maps that stay on the device.  maps_nhw[n][height][width] u8: the FILTERED maps of the n selected frames; xy[n][2] float64
+ * (x, y): their centres BEFORE the hold, none of them empty.  sum_cnt[n][2] int32, 8-byte aligned (else SVC_E_INVALID): row i >= 1 =
+ * { sum of map i's values at the in-image samples of the move xy[i-1] -> xy[i], number of such samples }; a count of 0 says "no
+ * statistic" (the move is below min_d, NumPy would raise on the sample count, or no sample falls inside the image) and comes with
+ * sum 0; row 0 = { 0, 0 }.  The caller forms jumps[i] = cnt ? (double)sum / cnt : 255 -- the mean svc_host_focus_stability forms
+ * from a float64 accumulator that holds the same integer, so the two agree to the bit (one line walk for both: csrc/svc_jump.h) --
+ * and hands the list to svc_host_focus_hold.
+ * Domain: both centres of a move finite and no coordinate beyond SVC_FOCUS_MAX_COORD in magnitude; otherwise the row is { 0, -1 }
+ * and nothing of the map is read.  That bounds a line at 131 072 samples, so no input makes the kernel run long, and keeps every
+ * integer conversion of the walk defined.
+ * No handle (like svc_iou_i32): no weights, no scratch, nothing kept between calls; safe to call concurrently from several threads.
+ * One launch, one wavefront per map, on the CURRENT device.  Written: all 2 n words of sum_cnt and nothing else.  Read: xy, and of
+ * the maps only bytes of [maps_nhw, maps_nhw + n * height * width); the maps need no alignment.  n == 0: a successful no-op.
+ * SVC_E_INVALID: n < 0, height or width < 1, min_d NaN, a NULL pointer with n > 0. */
+#define SVC_FOCUS_MAX_COORD 65536
+int svc_focus_jumps_u8(const uint8_t *maps_nhw, int n, int height, int width, const double *xy, double min_d,
+                       int32_t *sum_cnt, void *stream);
+
 /* ---- host stages between the per-frame centres and the crop windows (csrc/svc_host.cpp) ----
  * north_star keeps them on the host; they are native so that a multi-video job runs them off the interpreter lock.
  * No GPU, no handle, no stream: every pointer is HOST memory, float64 unless stated.  Reference: smartVidCrop.py
@@ -477,7 +497,10 @@ int svc_iou_i32(const int32_t *a, const int32_t *b, size_t n, double *out, void 
  *                                sc_check_for_extra_cuts :1337-1455, the hold loop :2425-2473): centres of the n selected frames (in
  *                                place), the FILTERED maps frame-major uint8 [n][h][w] (host) -> jumps[n] (mean map value along the
  *                                move from centre i-1 to centre i, 255 = none), inds[] = frames with a jump below stab_t (returned
- *                                count); float32 buffer / slope arithmetic as in the reference */
+ *                                count); float32 buffer / slope arithmetic as in the reference
+ *   svc_host_focus_hold          its second half alone (:2448-2473), for jump statistics that come from svc_focus_jumps_u8: inds[] =
+ *                                frames i >= 1 with jumps[i] < stab_t (returned count; room for n), then the hold on the centres, in
+ *                                place.  svc_host_focus_stability is its jump loop followed by this call */
 typedef struct SvcTemporalParams {
     uint32_t struct_size;       /* = sizeof(SvcTemporalParams) as the caller compiled it */
     int32_t lp_filt;            /* CP['lp_filt'] */
@@ -490,6 +513,8 @@ typedef struct SvcTemporalParams {
 } SvcTemporalParams;
 int svc_host_focus_stability(double *cx, double *cy, int n, const uint8_t *maps_nhw, int h, int w, double fr, int skip,
                              double min_d_jump, double stab_t, double stab_s, double *jumps, int32_t *inds);
+int svc_host_focus_hold(double *cx, double *cy, int n, const double *jumps, double fr, int skip, double stab_t, double stab_s,
+                        int32_t *inds);
 int svc_host_fill_empty_centres(double *cx, double *cy, int n_sel, const int32_t *seg_sel, int n_seg);
 int svc_host_interp_segment(const double *sampled_t, const double *d1, const double *d2, int n, int n_out, double *out1, double *out2);
 int svc_host_lowpass(const double *b, const double *a, const double *zi, int taps, const double *x, int n, double *out);

@@ -22,7 +22,8 @@ EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'sv
            'svc_resize_frames_nv12', 'svc_render_crops_nv12', 'svc_render_crops_u8_to_nv12', 'svc_render_crops_nv12_to_nv12', 'svc_debug_run_node',
            'svc_resize_frames_layout', 'svc_render_crops_layout', 'svc_render_crops_filter', 'svc_debug_net_plan',
            'svc_resize_frames_colour', 'svc_render_crops_colour', 'svc_render_crops_to_layout',
-           'svc_render_windows_q8', 'svc_debug_tail_plan', 'svc_debug_scratch_fill', 'svc_debug_sort_plan')
+           'svc_render_windows_q8', 'svc_debug_tail_plan', 'svc_debug_scratch_fill', 'svc_debug_sort_plan',
+           'svc_focus_jumps_u8', 'svc_host_focus_hold')
 
 
 class SvcParams(ctypes.Structure):
@@ -51,7 +52,8 @@ RANGE_LIMITED, RANGE_FULL = 0, 1        # include/svc.h: SVC_RANGE_*
 
 
 COLOUR_ENTRIES = ('svc_resize_frames_colour', 'svc_render_crops_colour')
-LATER_ENTRIES = COLOUR_ENTRIES + ('svc_render_crops_to_layout', 'svc_render_windows_q8', 'svc_debug_tail_plan', 'svc_debug_sort_plan')        # entries that came without an ABI bump: bound where the build has them
+LATER_ENTRIES = COLOUR_ENTRIES + ('svc_render_crops_to_layout', 'svc_render_windows_q8', 'svc_debug_tail_plan', 'svc_debug_sort_plan',
+                                  'svc_focus_jumps_u8', 'svc_host_focus_hold')        # entries that came without an ABI bump: bound where the build has them
 
 
 class SvcColour(ctypes.Structure):
@@ -167,6 +169,12 @@ def load():
     lib.svc_host_boxes.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
     f64 = ctypes.c_double
     lib.svc_host_focus_stability.argtypes = [vp, vp, i32, vp, i32, i32, f64, i32, f64, f64, f64, vp, vp]
+    # (the two entries of the device focus stability likewise: on an older build ops.focus_jumps / temporal.focus_hold_native fail by
+    # the symbol's name, and SVC_FOCUS=host runs)
+    if hasattr(lib, 'svc_focus_jumps_u8'):
+        lib.svc_focus_jumps_u8.argtypes = [vp, i32, i32, i32, vp, f64, vp, vp]
+    if hasattr(lib, 'svc_host_focus_hold'):
+        lib.svc_host_focus_hold.argtypes = [vp, vp, i32, vp, f64, i32, f64, f64, vp]
     for name in EXPORTS:
         if name not in ('svc_last_error', 'svc_abi_version') and (name not in LATER_ENTRIES or hasattr(lib, name)):
             getattr(lib, name).restype = i32

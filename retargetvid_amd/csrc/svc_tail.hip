@@ -19,6 +19,7 @@
 //                 centroid (:1163-1219); k_centre_argmax: com_km = False (:1165-1178)
 //   k_tail_front / k_tail_back  the stages of a round fused into two launches
 //   k_iou         bb_intersection_over_union         smartVidCrop.py:927-944
+//   k_focus_jumps get_points_on_line + the sums of sc_check_for_extra_cuts   smartVidCrop.py:1337-1455 (svc_jump.h)
 #include <math.h>
 
 #include <algorithm>
@@ -28,6 +29,7 @@
 #include "hdb_tree.h"
 #include "svc_cvlinear.h"
 #include "svc_internal.h"
+#include "svc_jump.h"
 
 #ifndef TB
 #define TB 1024                 // threads per frame workgroup
@@ -203,6 +205,46 @@ __global__ __launch_bounds__(256) void k_iou(const int4 *__restrict__ a, const i
     long long inter = max(0LL, xb - xa + 1) * max(0LL, yb - ya + 1);
     long long aa = (long long)(A.z - A.x + 1) * (A.w - A.y + 1), ab = (long long)(B.z - B.x + 1) * (B.w - B.y + 1);
     out[i] = (double)inter / (double)(aa + ab - inter);
+}
+
+// The jump statistics of the focus stability (svc_jump.h: the line walk, one statement for this kernel and svc_host.cpp).  One
+// wavefront per map, FOCUS_WAVES maps per workgroup; wavefront i >= 1 walks the move xy[i-1] -> xy[i] over map i.  The set-up is
+// uniform and computed in every lane; lane l takes samples l, l + 64, ...; sum and count are integers reduced across the lanes
+// (wave_sum_i32: DPP), so there is no LDS, no atomic and no order to depend on.  A sum is at most 131 072 * 255 < 2^25.
+// Loads: only map bytes at jump_index of samples that passed jump_inside, i.e. inside [maps + i h w, maps + (i + 1) h w) -- in the
+// domain every coordinate is below 2^24, so the float32 comparisons against (float)w, (float)h are exact whatever w and h.
+// Stores: one 8-byte store per row from lane 0, rows 0 .. n-1.
+#define FOCUS_WAVES 4
+static_assert(SVC_JUMP_MAX_COORD == SVC_FOCUS_MAX_COORD, "svc_jump.h and include/svc.h state one domain");
+__global__ __launch_bounds__(64 * FOCUS_WAVES) void k_focus_jumps(const uint8_t *__restrict__ maps, int n, int h, int w,
+                                                                  const double *__restrict__ xy, double min_d,
+                                                                  int2 *__restrict__ sum_cnt) {
+    const int i = (int)blockIdx.x * FOCUS_WAVES + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (i >= n) return;                                                        // (wave-uniform)
+    int sum = 0, cnt = 0;
+    if (i >= 1) {
+        const double p1x = xy[2 * i - 2], p1y = xy[2 * i - 1], p2x = xy[2 * i], p2y = xy[2 * i + 1];
+        JumpLine L;
+        if (!jump_in_domain(p1x, p1y, p2x, p2y)) cnt = -1;
+        else if (jump_setup(p1x, p1y, p2x, p2y, min_d, &L)) {
+            const uint8_t *map = maps + (size_t)i * h * w;
+            const int m = (int)L.m;                                            // <= 131 072 in the domain
+            uint32_t s = 0;
+            int c = 0;
+            for (int k = lane; k < m; k += 64) {
+                float bx, by;
+                jump_sample(L, k, &bx, &by);
+                if (jump_inside(bx, by, w, h)) {
+                    s += map[jump_index(bx, by, w)];
+                    ++c;
+                }
+            }
+            sum = wave_sum_i32((int)s);
+            cnt = wave_sum_i32(c);
+            if (cnt == 0) sum = 0;
+        }
+    }
+    if (lane == 0) sum_cnt[i] = make_int2(sum, cnt);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2823,6 +2865,20 @@ extern "C" int svc_iou_i32(const int32_t *a, const int32_t *b, size_t n, double 
     if (!a || !b || !out) { svc_set_error("svc_iou_i32: invalid argument"); return SVC_E_INVALID; }
     if (n == 0) return SVC_OK;
     k_iou<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>((const int4 *)a, (const int4 *)b, n, out);
+    SVC_CHECK_LAUNCH();
+    return SVC_OK;
+}
+
+// No handle: no weights, no scratch, no state -- callable from any thread on any stream of the current device.
+extern "C" int svc_focus_jumps_u8(const uint8_t *maps_nhw, int n, int height, int width, const double *xy, double min_d,
+                                  int32_t *sum_cnt, void *stream) {
+    if (n < 0 || height < 1 || width < 1 || !(min_d == min_d) || (n > 0 && (!maps_nhw || !xy || !sum_cnt)) || ((uintptr_t)sum_cnt & 7)) {
+        svc_set_error("svc_focus_jumps_u8: invalid argument");
+        return SVC_E_INVALID;
+    }
+    if (n == 0) return SVC_OK;
+    k_focus_jumps<<<(unsigned)((n + FOCUS_WAVES - 1) / FOCUS_WAVES), 64 * FOCUS_WAVES, 0, (hipStream_t)stream>>>(
+        maps_nhw, n, height, width, xy, min_d, (int2 *)sum_cnt);
     SVC_CHECK_LAUNCH();
     return SVC_OK;
 }

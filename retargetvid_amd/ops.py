@@ -760,3 +760,27 @@ def iou_boxes(a, b):
     out = torch.empty(m, dtype=torch.float64, device=ta.device)
     _lib.check(lib.svc_iou_i32(_ptr(ta), _ptr(tb), m, _ptr(out), _stream()))
     return out.cpu().numpy()
+
+
+def focus_jumps(maps, xy, min_d):
+    """The jump statistics of the focus stability from maps that stay on the device (svc_focus_jumps_u8, include/svc.h): maps =
+    the FILTERED maps, a contiguous CUDA uint8 [n, h, w] tensor; xy = the centres before the hold, a CUDA float64 [n, 2] tensor on
+    the maps' device, or a NumPy array / list that is uploaded there.  -> CUDA int32 [n, 2]: row i >= 1 = (sum, count) of map i's
+    values along the move xy[i-1] -> xy[i]; count 0 = no statistic (jump 255), count -1 = a centre outside the entry's domain
+    (not finite, or beyond 65 536); row 0 = (0, 0).  Runs on the maps' device and the current stream; no handle, no scratch."""
+    lib = _lib.load()
+    if not hasattr(lib, 'svc_focus_jumps_u8'):
+        raise _lib.SvcError('%s lacks svc_focus_jumps_u8: the device focus stability needs a build that has it' % _lib.LIB_PATH)
+    _need_cuda(maps, torch.uint8, 'maps')
+    if maps.dim() != 3:
+        raise ValueError('maps must be [n, h, w], not %s' % (tuple(maps.shape),))
+    n, h, w = (int(v) for v in maps.shape)
+    if not torch.is_tensor(xy):
+        xy = torch.from_numpy(np.ascontiguousarray(xy, np.float64).reshape(-1, 2)).to(maps.device)
+    _need_cuda(xy, torch.float64, 'xy')
+    if tuple(xy.shape) != (n, 2) or xy.device != maps.device:
+        raise ValueError('xy must be [%d, 2] on %s, not %s on %s' % (n, maps.device, tuple(xy.shape), xy.device))
+    with torch.cuda.device(maps.device):
+        out = torch.empty((n, 2), dtype=torch.int32, device=maps.device)
+        _lib.check(lib.svc_focus_jumps_u8(_ptr(maps), n, h, w, _ptr(xy), float(min_d), _ptr(out), _stream()))
+    return out

@@ -731,8 +731,8 @@ def feature_cache_key(video, CP, engine):
 def after_ingest(VD, CP, engine, verbose=False):
     """Everything of smart_vid_crop behind the ingest (smartVidCrop.py:2293-2614 without the rendering): destination
     size, threshold + cluster filter + centres on the device (skipped when the ingest or the multi-video scheduler has
-    run them already: VD['xy_stream']), then the host stages -- empty-centre fill, focus stability, interpolation,
-    low-pass, LOESS, boxes.  One function for the one-video call and for retargetvid_amd/scheduler.py, so that both give
+    run them already: VD['xy_stream']), then the host stages -- empty-centre fill, focus stability (its jump statistics from
+    the maps on the device unless SVC_FOCUS=host), interpolation, low-pass, LOESS, boxes.  One function for the one-video call and for retargetvid_amd/scheduler.py, so that both give
     the same windows by construction.  -> (VD, smart_crop_results)."""
     results = {}
     VD['segm_backup'] = VD['segmentation'].copy()
@@ -791,9 +791,17 @@ def after_ingest(VD, CP, engine, verbose=False):
     VD['jumps_inds'] = []
     VD['dxnf'], VD['dynf'] = list(VD['dx']), list(VD['dy'])
     t = time.perf_counter()
-    if CP['focus_stability']:            # best settings: hold the focus across short low-saliency jumps (host)
-        maps_host = VD['smaps_dev'].cpu().numpy()        # frame-major [n,h,w]: no [H,W,n] transposition (VD['smaps'] stays lazy)
-        xy, VD['jumps'], VD['jumps_inds'] = temporal.focus_stability_native(xy, maps_host, VD['fr'], CP)
+    if CP['focus_stability']:            # best settings: hold the focus across short low-saliency jumps
+        # SVC_FOCUS (read per call): 'device' (the default) = the jump statistics from the resident maps, one launch, n x 2 doubles up
+        # and n x 2 int32 down (svc_focus_jumps_u8); 'host' = every filtered map copied to the host and walked there, the former route
+        route = os.environ.get('SVC_FOCUS') or 'device'
+        if route == 'device':
+            xy, VD['jumps'], VD['jumps_inds'] = temporal.focus_stability_device(xy, VD['smaps_dev'], VD['fr'], CP)
+        elif route == 'host':
+            maps_host = VD['smaps_dev'].cpu().numpy()        # frame-major [n,h,w]: no [H,W,n] transposition (VD['smaps'] stays lazy)
+            xy, VD['jumps'], VD['jumps_inds'] = temporal.focus_stability_native(xy, maps_host, VD['fr'], CP)
+        else:
+            raise ValueError("SVC_FOCUS=%r: 'device' or 'host'" % route)
         VD['dx'], VD['dy'] = xy[:, 0].tolist(), xy[:, 1].tolist()
     sc_register_time(t, '_focus_stability')
 

@@ -14,7 +14,8 @@ Reference (smartVidCrop.py unless noted):
   butter_lowpass         sc_butter_lowpass_filter           :1599-1627
   loess / loess_handler  loess_handler :1629-1646 and 3rd_party_libs/loess/pyloess.py:13-95
   smoothing              sc_smoothing                       :1648-1734
-  focus_stability        sc_check_for_extra_cuts + focus hold :1337-1455, :2425-2473
+  focus_stability        sc_check_for_extra_cuts + focus hold :1337-1455, :2425-2473  (focus_stability_device: the jump
+                         statistics from the maps on the device, ops.focus_jumps; only the hold runs here)
   shift_time             sc_shift_time                      :1740-1746
 """
 import ctypes
@@ -193,10 +194,50 @@ def focus_stability_native(xy, maps_nhw, fr, CP):
     return np.stack([cx, cy], 1), jl, [int(v) for v in inds[:ni]]
 
 
+def focus_hold_native(xy, jumps, fr, CP):
+    """The second half of focus_stability, native (svc_host_focus_hold): xy float64 [n, 2] and the n jump statistics (255 = none)
+    -> (xy with the focus held between low-saliency jumps close in time, jumps_inds list)."""
+    lib = _lib.load()
+    if not hasattr(lib, 'svc_host_focus_hold'):
+        raise _lib.SvcError('%s lacks svc_host_focus_hold: the device focus stability needs a build that has it' % _lib.LIB_PATH)
+    xy = np.asarray(xy, np.float64).reshape(-1, 2)
+    cx, cy = _f64(xy[:, 0]).copy(), _f64(xy[:, 1]).copy()
+    n = len(cx)
+    jv = _f64(jumps)
+    if jv.shape != (n,):
+        raise ValueError('%d jump statistics for %d centres' % (jv.size, n))
+    inds = np.empty(max(n, 1), np.int32)
+    ni = _lib.check(lib.svc_host_focus_hold(_p(cx), _p(cy), n, _p(jv), float(fr), int(CP['skip']), float(CP['foces_stab_t']),
+                                            float(CP['foces_stab_s']), _p(inds)))
+    return np.stack([cx, cy], 1), [int(v) for v in inds[:ni]]
+
+
+def focus_stability_device(xy, maps_dev, fr, CP):
+    """focus_stability_native with the maps left where they are: maps_dev = the FILTERED maps, a contiguous CUDA uint8 [n, h, w]
+    tensor.  The n - 1 jump statistics are one launch (ops.focus_jumps: svc_focus_jumps_u8, the same line walk as the host's,
+    csrc/svc_jump.h); n x 2 doubles go up, n x 2 int32 (sum, count) come back, and the mean sum / count is the host's float64 mean
+    to the bit.  Then the hold (focus_hold_native).  -> (xy, jumps list, jumps_inds list), the types and values of
+    focus_stability_native.  ValueError for a centre that is not finite or lies beyond 65 536 (the entry's domain), naming the
+    first such move."""
+    from . import ops
+    xy = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+    sc = ops.focus_jumps(maps_dev, xy, CP['min_d_jump']).cpu().numpy()
+    s, c = sc[:, 0].astype(np.float64), sc[:, 1]
+    bad = np.flatnonzero(c < 0)
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError('focus stability: the move %d -> %d, %s -> %s, has a centre that is not finite or lies beyond %d'
+                         % (i - 1, i, xy[i - 1].tolist(), xy[i].tolist(), 65536))
+    jumps = np.full(len(c), 255.0)
+    np.divide(s, c, out=jumps, where=c > 0)
+    xy, inds = focus_hold_native(xy, jumps, fr, CP)
+    return xy, [255 if v == 255.0 else float(v) for v in jumps], inds
+
+
 def focus_stability(dx, dy, smaps_hwn, fr, CP):
     """Jump statistics + focus hold (smartVidCrop.py:1337-1455, :2425-2473) with the reference's argument layout: smaps_hwn =
-    the filtered maps as [H,W,n].  -> (dx, dy, jumps, jumps_inds).  (after_ingest calls focus_stability_native on the
-    frame-major maps directly.)"""
+    the filtered maps as [H,W,n].  -> (dx, dy, jumps, jumps_inds).  (after_ingest calls focus_stability_device on the resident
+    frame-major maps, or -- SVC_FOCUS=host -- focus_stability_native on their host copy.)"""
     xy, jumps, inds = focus_stability_native(np.stack([_f64(dx), _f64(dy)], 1), np.transpose(np.asarray(smaps_hwn), (2, 0, 1)), fr, CP)
     return xy[:, 0].tolist(), xy[:, 1].tolist(), jumps, inds
 
