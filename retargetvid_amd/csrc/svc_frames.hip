@@ -17,6 +17,11 @@
 //   SrcNv12          YUV -> RGB conversion fused into both (no counterpart: the reference is handed RGB)
 //   DstNv12          the same crops written as NV12, the forward transform fused in (no counterpart: the reference hands RGB to its writer)
 //   Nv12Dec, Nv12Enc the colour (matrix x range: SvcColour) of those two, run-time kernel arguments
+//
+// The host layer under the render entries is written once as well: an entry fills a RenderCall and makes one call; render_pair
+// states the source x sink pairings (2 x 3) once; the launchers -- render_crops, render_windows, render_crops_lanczos -- are
+// launcher<Src, Dst>(call, source layout, output layout) and share their checks and device prologue (render_run); the layout
+// entries share render_crops_any and name their launcher by a RenderMode.  The down-scale is one kernel behind resize_frames.
 #include <algorithm>
 #include <type_traits>
 
@@ -900,102 +905,121 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_re
     Dst::rows_out(KO, lds, dst, ow);
 }
 
-// the argument checks of the render launchers (render_crops, render_crops_lanczos, render_windows): plain comparisons, before any device work
-template <class Src, class Dst>
-static int render_args_check(const char *name, SvcHandle *h, const uint8_t *frames, int n, int height, int width,
-                             const int32_t *boxes, int bw, int bh, uint8_t *out, int oh, int ow, int flags) {
-    if (!h || n < 0 || (n > 0 && (!frames || !boxes || !out)) || !Src::size_ok(height, width) || bw < 1 || bh < 1 ||
-        bw > width || bh > height) {                                                       // n = 0: a no-op, null buffers allowed
-        svc_set_error("%s: invalid argument%s", name, Src::size_rule());
+// --------------------------------------------------------------------------------------
+// The renderer's host layer (the file's header names its parts)
+// --------------------------------------------------------------------------------------
+struct RenderCall {                         // what a render call is, whichever entry it came through; the layouts are types and travel beside it
+    const char *name;                       // the entry the errors are reported under
+    SvcHandle *h;
+    const uint8_t *frames;
+    int n, height, width;
+    const int32_t *win;                     // the frames' windows: int32 [n][4] boxes; render_windows: [n][2] origins in 1/256 pixel
+    int bw, bh;
+    uint8_t *out;
+    int oh, ow, flags;
+    void *stream;
+    Colours C;                              // of both sides, checked
+};
+
+// What the launchers share, around the two parts each keeps.  The argument checks: plain comparisons, before any device work.
+// Then `rule`, the launcher's host half (its LDS rule, the host side of its tables), which may refuse the call; n = 0 is a no-op
+// from there on.  Then the device, and `launch` with what guards the kernels' 16-byte loads -- the end of the last frame's last
+// plane row (Packed: frames + n * frame_bytes) and whether they may run at all -- and the stream.
+template <class Src, class Dst, class Rule, class Launch>
+static int render_run(const RenderCall &c, const typename Src::lay &L, Rule rule, Launch launch) {
+    if (!c.h || c.n < 0 || (c.n > 0 && (!c.frames || !c.win || !c.out)) || !Src::size_ok(c.height, c.width) || c.bw < 1 || c.bh < 1 ||
+        c.bw > c.width || c.bh > c.height) {                                               // n = 0: a no-op, null buffers allowed
+        svc_set_error("%s: invalid argument%s", c.name, Src::size_rule());
         return SVC_E_INVALID;
     }
-    if (!Dst::size_ok(oh, ow)) {
-        svc_set_error("%s: an output of %dx%d (%s)", name, ow, oh, Dst::size_rule());
+    if (!Dst::size_ok(c.oh, c.ow)) {
+        svc_set_error("%s: an output of %dx%d (%s)", c.name, c.ow, c.oh, Dst::size_rule());
         return SVC_E_INVALID;
     }
-    if (!Dst::flags_ok(flags)) {
-        svc_set_error("%s: %s", name, Dst::flags_rule());
+    if (!Dst::flags_ok(c.flags)) {
+        svc_set_error("%s: %s", c.name, Dst::flags_rule());
         return SVC_E_INVALID;
     }
-    return SVC_OK;
+    const int rc = rule();
+    if (rc || c.n == 0) return rc;
+    SVC_HIP(hipSetDevice(c.h->device));
+    const uint8_t *in_end = c.frames + (size_t)(c.n - 1) * L.template frame<Src>(c.height, c.width) + Src::extent(L, c.height, c.width);
+    const bool vec = ((uintptr_t)c.frames & 15) == 0 && Src::vec_ok(L);
+    return launch(in_end, vec, (hipStream_t)c.stream);
 }
 
-template <class Src, class Dst>
-static int render_crops(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, const Colours &C, int n,
-                        int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, const typename Dst::olay &O, int oh, int ow,
-                        int flags, void *stream) {
-    int rc = render_args_check<Src, Dst>(name, h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags);
-    if (rc) return rc;
-    const int span_cap = (bw * 3 + 32 + 15) / 16 * 16;
-    const size_t lds = 2 * (size_t)span_cap + Dst::lds_bytes(ow);
-    const bool copy = oh == bh && ow == bw;
-    if (!copy && lds > 65536) {
-        svc_set_error("%s: window %dx%d -> %dx%d needs %zu bytes of LDS per %s (> 64 KiB)", name, bw, bh, ow, oh, lds,
-                      Dst::rows == 1 ? "output row" : "pair of output rows");
-        return SVC_E_INVALID;
-    }
-    if (n == 0) return SVC_OK;
-    SVC_HIP(hipSetDevice(h->device));
-    // the end of the last frame's last plane row: what the 16-byte loads are guarded by (Packed: frames + n * frame_bytes)
-    const uint8_t *in_end = frames + (size_t)(n - 1) * L.template frame<Src>(height, width) + Src::extent(L, height, width);
-    const bool aligned_in = ((uintptr_t)frames & 15) == 0 && Src::vec_ok(L);
-    hipStream_t s = (hipStream_t)stream;
-    const int *tab = nullptr;
-    if (!copy) {
-        rc = cv_tab(h, bh, bw, oh, ow, &tab);
-        if (rc) return rc;
-    }
-    ProfScope ps(h, SVC_K_RENDER, s);
-    if (copy) {
-        if (aligned_in && Dst::vec_ok(O, out, bw)) {               // (the layout decides which path runs, never whether the call is legal)
-            const unsigned grid = (unsigned)((Dst::vec_threads(n, bh, bw) + 255) / 256);
-            Dst::template vec_copy<Src>()<<<grid, 256, 0, s>>>(frames, out, boxes, n, height, width, bh, bw, in_end, L, Src::col(C), Dst::col(C), O);
-        } else {
-            const long long total = (long long)n * (bh / Dst::rows) * (bw / Dst::rows);
-            k_render_copy_px<Src, Dst><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(frames, out, boxes, height, width, bh, bw, total, L, Src::col(C), Dst::col(C), O);
-        }
-        SVC_CHECK_LAUNCH();
-        return SVC_OK;
-    }
-    for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
-        const dim3 grid((unsigned)(oh / Dst::rows), (unsigned)std::min(n - f0, 65535));
-        k_render_resize<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * O.template frame<Dst>(oh, ow), tab, boxes, f0, height, width,
-                                                         bh, bw, oh, ow, span_cap, in_end, aligned_in, L, Src::col(C), Dst::col(C), O);
-        SVC_CHECK_LAUNCH();
-    }
-    return SVC_OK;
+template <class Dst>
+static int lds_refused(const RenderCall &c, const char *filter, size_t lds) {
+    svc_set_error("%s: window %dx%d -> %dx%d%s needs %zu bytes of LDS per %s (> 64 KiB)", c.name, c.bw, c.bh, c.ow, c.oh, filter, lds,
+                  Dst::rows == 1 ? "output row" : "pair of output rows");
+    return SVC_E_INVALID;
 }
 
-// render_crops for windows whose origins are given in 1/256 pixel (svc_render_windows_q8): always the resampling kernel, also at
+// The linear launcher: the copy kernels at oh == bh && ow == bw (no LDS rule there), else k_render_resize.
+template <class Src, class Dst>
+static int render_crops(const RenderCall &c, const typename Src::lay &L, const typename Dst::olay &O) {
+    const bool copy = c.oh == c.bh && c.ow == c.bw;
+    int span_cap = 0;           // (set by the rule, read by the launch)
+    size_t lds = 0;
+    return render_run<Src, Dst>(c, L,
+        [&] {
+            span_cap = (c.bw * 3 + 32 + 15) / 16 * 16;
+            lds = 2 * (size_t)span_cap + Dst::lds_bytes(c.ow);
+            return !copy && lds > 65536 ? lds_refused<Dst>(c, "", lds) : SVC_OK;
+        },
+        [&](const uint8_t *in_end, bool vec, hipStream_t s) {
+            const int *tab = nullptr;
+            if (int rc = copy ? SVC_OK : cv_tab(c.h, c.bh, c.bw, c.oh, c.ow, &tab)) return rc;
+            ProfScope ps(c.h, SVC_K_RENDER, s);
+            if (copy) {
+                if (vec && Dst::vec_ok(O, c.out, c.bw)) {          // (the layout decides which path runs, never whether the call is legal)
+                    const unsigned grid = (unsigned)((Dst::vec_threads(c.n, c.bh, c.bw) + 255) / 256);
+                    Dst::template vec_copy<Src>()<<<grid, 256, 0, s>>>(c.frames, c.out, c.win, c.n, c.height, c.width, c.bh, c.bw, in_end, L,
+                                                                       Src::col(c.C), Dst::col(c.C), O);
+                } else {
+                    const long long total = (long long)c.n * (c.bh / Dst::rows) * (c.bw / Dst::rows);
+                    k_render_copy_px<Src, Dst><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(c.frames, c.out, c.win, c.height, c.width, c.bh, c.bw,
+                                                                                               total, L, Src::col(c.C), Dst::col(c.C), O);
+                }
+                SVC_CHECK_LAUNCH();
+                return SVC_OK;
+            }
+            for (int f0 = 0; f0 < c.n; f0 += 65535) {            // grid y <= 65535 frames per launch
+                const dim3 grid((unsigned)(c.oh / Dst::rows), (unsigned)std::min(c.n - f0, 65535));
+                k_render_resize<Src, Dst><<<grid, 256, lds, s>>>(c.frames, c.out + f0 * O.template frame<Dst>(c.oh, c.ow), tab, c.win, f0, c.height,
+                                                                 c.width, c.bh, c.bw, c.oh, c.ow, span_cap, in_end, vec, L, Src::col(c.C),
+                                                                 Dst::col(c.C), O);
+                SVC_CHECK_LAUNCH();
+            }
+            return SVC_OK;
+        });
+}
+
+// The launcher for windows whose origins are given in 1/256 pixel (svc_render_windows_q8): always the resampling kernel, also at
 // oh == bh && ow == bw (the identity table: a pure fractional shift), with one more staged column in the LDS rule.
 template <class Src, class Dst>
-static int render_windows(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, const Colours &C, int n,
-                          int height, int width, const int32_t *origins_q8, int bw, int bh, uint8_t *out, const typename Dst::olay &O, int oh,
-                          int ow, int flags, void *stream) {
-    int rc = render_args_check<Src, Dst>(name, h, frames, n, height, width, origins_q8, bw, bh, out, oh, ow, flags);
-    if (rc) return rc;
-    const int span_cap = ((bw + 1) * 3 + 32 + 15) / 16 * 16;
-    const size_t lds = 2 * (size_t)span_cap + Dst::lds_bytes(ow);
-    if (lds > 65536) {
-        svc_set_error("%s: window %dx%d -> %dx%d needs %zu bytes of LDS per %s (> 64 KiB)", name, bw, bh, ow, oh, lds,
-                      Dst::rows == 1 ? "output row" : "pair of output rows");
-        return SVC_E_INVALID;
-    }
-    if (n == 0) return SVC_OK;
-    SVC_HIP(hipSetDevice(h->device));
-    const uint8_t *in_end = frames + (size_t)(n - 1) * L.template frame<Src>(height, width) + Src::extent(L, height, width);
-    const int vec = ((uintptr_t)frames & 15) == 0 && Src::vec_ok(L);
-    hipStream_t s = (hipStream_t)stream;
-    const int *tab = nullptr;
-    if ((rc = cv_tab(h, bh, bw, oh, ow, &tab))) return rc;
-    ProfScope ps(h, SVC_K_RENDER, s);
-    for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
-        const dim3 grid((unsigned)(oh / Dst::rows), (unsigned)std::min(n - f0, 65535));
-        k_render_resize_q8<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * O.template frame<Dst>(oh, ow), tab, origins_q8, f0, height, width,
-                                                            bh, bw, oh, ow, span_cap, in_end, vec, L, Src::col(C), Dst::col(C), O);
-        SVC_CHECK_LAUNCH();
-    }
-    return SVC_OK;
+static int render_windows(const RenderCall &c, const typename Src::lay &L, const typename Dst::olay &O) {
+    int span_cap = 0;           // (set by the rule, read by the launch)
+    size_t lds = 0;
+    return render_run<Src, Dst>(c, L,
+        [&] {
+            span_cap = ((c.bw + 1) * 3 + 32 + 15) / 16 * 16;
+            lds = 2 * (size_t)span_cap + Dst::lds_bytes(c.ow);
+            return lds > 65536 ? lds_refused<Dst>(c, "", lds) : SVC_OK;
+        },
+        [&](const uint8_t *in_end, bool vec, hipStream_t s) {
+            const int *tab = nullptr;
+            if (int rc = cv_tab(c.h, c.bh, c.bw, c.oh, c.ow, &tab)) return rc;
+            ProfScope ps(c.h, SVC_K_RENDER, s);
+            for (int f0 = 0; f0 < c.n; f0 += 65535) {            // grid y <= 65535 frames per launch
+                const dim3 grid((unsigned)(c.oh / Dst::rows), (unsigned)std::min(c.n - f0, 65535));
+                k_render_resize_q8<Src, Dst><<<grid, 256, lds, s>>>(c.frames, c.out + f0 * O.template frame<Dst>(c.oh, c.ow), tab, c.win, f0,
+                                                                    c.height, c.width, c.bh, c.bw, c.oh, c.ow, span_cap, in_end, vec, L,
+                                                                    Src::col(c.C), Dst::col(c.C), O);
+                SVC_CHECK_LAUNCH();
+            }
+            return SVC_OK;
+        });
 }
 
 // --------------------------------------------------------------------------------------
@@ -1162,110 +1186,80 @@ static int lz_tile_rows(const std::vector<int> &vb, int oh, int B) {
     return cap;
 }
 
-// render_crops with the Lanczos filter.  The band: the largest B <= 32 (a multiple of Dst::rows) whose LDS fits in 64 KiB
-// (include/svc.h states the formula).
+// The Lanczos launcher.  oh == bh && ow == bw skips both passes: the linear launcher's exact copy (whose argument checks are
+// these).  The band: the largest B <= 32 (a multiple of Dst::rows) whose LDS fits in 64 KiB (include/svc.h states the formula).
 template <class Src, class Dst>
-static int render_crops_lanczos(const char *name, SvcHandle *h, const uint8_t *frames, const typename Src::lay &L, const Colours &C,
-                                int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, const typename Dst::olay &O,
-                                int oh, int ow, int flags, void *stream) {
-    int rc = render_args_check<Src, Dst>(name, h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags);
-    if (rc) return rc;
-    if (oh == bh && ow == bw)                               // both passes skipped: the exact copy
-        return render_crops<Src, Dst>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+static int render_crops_lanczos(const RenderCall &c, const typename Src::lay &L, const typename Dst::olay &O) {
+    if (c.oh == c.bh && c.ow == c.bw) return render_crops<Src, Dst>(c, L, O);
     ResampleTab *ht = nullptr, *vt = nullptr;
-    if ((rc = lz_tab(name, h, bw, ow, &ht)) || (rc = lz_tab(name, h, bh, oh, &vt))) return rc;
-    const int span_cap = (bw * 3 + 32 + 15) / 16 * 16, tw = (ow * 3 + 15) / 16 * 16;
-    const size_t fixed = (size_t)LZ_STAGE * span_cap + Dst::lds_bytes(ow);
-    int B = std::min(32, (oh + Dst::rows - 1) / Dst::rows * Dst::rows) / Dst::rows * Dst::rows, tile_cap = 0;
+    int span_cap = 0, B = 0, tile_cap = 0;
     size_t lds = 0;
-    for (;; B -= Dst::rows) {
-        tile_cap = lz_tile_rows(vt->bounds_host, oh, B);
-        lds = fixed + (size_t)tile_cap * tw;
-        if (lds <= 65536) break;
-        if (B == Dst::rows) {
-            svc_set_error("%s: window %dx%d -> %dx%d (lanczos) needs %zu bytes of LDS per %s (> 64 KiB)", name, bw, bh, ow, oh, lds,
-                          Dst::rows == 1 ? "output row" : "pair of output rows");
-            return SVC_E_INVALID;
-        }
-    }
-    if (n == 0) return SVC_OK;
-    SVC_HIP(hipSetDevice(h->device));
-    if ((rc = lz_upload(*ht)) || (rc = lz_upload(*vt))) return rc;
-    const uint8_t *in_end = frames + (size_t)(n - 1) * L.template frame<Src>(height, width) + Src::extent(L, height, width);
-    const int vec = ((uintptr_t)frames & 15) == 0 && Src::vec_ok(L);
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(h, SVC_K_RENDER, s);
-    for (int f0 = 0; f0 < n; f0 += 65535) {                  // grid y <= 65535 frames per launch
-        const dim3 grid((unsigned)((oh + B - 1) / B), (unsigned)std::min(n - f0, 65535));
-        k_render_lanczos<Src, Dst><<<grid, 256, lds, s>>>(frames, out + f0 * O.template frame<Dst>(oh, ow), (const int *)ht->bounds.p,
-                                                          (const int *)ht->coeff.p, ht->ksize, (const int *)vt->bounds.p,
-                                                          (const int *)vt->coeff.p, vt->ksize, boxes, f0, height, width, bh, bw, oh, ow,
-                                                          B, span_cap, tile_cap, in_end, vec, L, Src::col(C), Dst::col(C), O);
-        SVC_CHECK_LAUNCH();
-    }
-    return SVC_OK;
+    return render_run<Src, Dst>(c, L,
+        [&] {
+            int rc;
+            if ((rc = lz_tab(c.name, c.h, c.bw, c.ow, &ht)) || (rc = lz_tab(c.name, c.h, c.bh, c.oh, &vt))) return rc;
+            span_cap = (c.bw * 3 + 32 + 15) / 16 * 16;
+            const int tw = (c.ow * 3 + 15) / 16 * 16;
+            const size_t fixed = (size_t)LZ_STAGE * span_cap + Dst::lds_bytes(c.ow);
+            for (B = std::min(32, (c.oh + Dst::rows - 1) / Dst::rows * Dst::rows) / Dst::rows * Dst::rows;; B -= Dst::rows) {
+                tile_cap = lz_tile_rows(vt->bounds_host, c.oh, B);
+                lds = fixed + (size_t)tile_cap * tw;
+                if (lds <= 65536) return SVC_OK;
+                if (B == Dst::rows) return lds_refused<Dst>(c, " (lanczos)", lds);
+            }
+        },
+        [&](const uint8_t *in_end, bool vec, hipStream_t s) {
+            for (ResampleTab *t : {ht, vt}) if (int rc = lz_upload(*t)) return rc;
+            ProfScope ps(c.h, SVC_K_RENDER, s);
+            for (int f0 = 0; f0 < c.n; f0 += 65535) {            // grid y <= 65535 frames per launch
+                const dim3 grid((unsigned)((c.oh + B - 1) / B), (unsigned)std::min(c.n - f0, 65535));
+                k_render_lanczos<Src, Dst><<<grid, 256, lds, s>>>(c.frames, c.out + f0 * O.template frame<Dst>(c.oh, c.ow), (const int *)ht->bounds.p,
+                                                                  (const int *)ht->coeff.p, ht->ksize, (const int *)vt->bounds.p,
+                                                                  (const int *)vt->coeff.p, vt->ksize, c.win, f0, c.height, c.width, c.bh, c.bw,
+                                                                  c.oh, c.ow, B, span_cap, tile_cap, in_end, vec, L, Src::col(c.C), Dst::col(c.C), O);
+                SVC_CHECK_LAUNCH();
+            }
+            return SVC_OK;
+        });
 }
 
-// the source x sink pairings of one source layout and one output layout (flags picks the RGB sink's channel order), per filter
-template <class Lay, class OLay>
-static int render_crops_fmt(const char *name, int pix_fmt, bool to_nv12, SvcHandle *h, const uint8_t *frames, const Lay &L, const Colours &C, int n,
-                            int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, const OLay &O, int oh, int ow, int flags,
-                            void *stream) {
-    if (pix_fmt == SVC_FMT_NV12) {
-        if (to_nv12) return render_crops<SrcNv12<Lay>, DstNv12<OLay>>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
-        return (flags & SVC_RENDER_BGR ? render_crops<SrcNv12<Lay>, DstRgb<true, OLay>> : render_crops<SrcNv12<Lay>, DstRgb<false, OLay>>)(
-            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
-    }
-    if (to_nv12) return render_crops<SrcRgb<Lay>, DstNv12<OLay>>(name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
-    return (flags & SVC_RENDER_BGR ? render_crops<SrcRgb<Lay>, DstRgb<true, OLay>> : render_crops<SrcRgb<Lay>, DstRgb<false, OLay>>)(
-        name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
-}
-template <class Lay, class OLay>
-static int render_crops_lanczos_fmt(const char *name, int pix_fmt, bool to_nv12, SvcHandle *h, const uint8_t *frames, const Lay &L, const Colours &C,
-                                    int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, const OLay &O, int oh, int ow,
-                                    int flags, void *stream) {
+// The source x sink pairings of one source layout and one output layout, stated once: f is called with a Pair of the kernels'
+// Src and Dst for the frames' format, the output's format and (flags) the RGB sink's channel order.
+template <class S, class D> struct Pair { typedef S Src; typedef D Dst; };
+template <class Lay, class OLay, class F>
+static int render_pair(int pix_fmt, bool to_nv12, int flags, F f) {
     const bool nv12 = pix_fmt == SVC_FMT_NV12;
-    if (to_nv12)
-        return (nv12 ? render_crops_lanczos<SrcNv12<Lay>, DstNv12<OLay>> : render_crops_lanczos<SrcRgb<Lay>, DstNv12<OLay>>)(
-            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
-    if (flags & SVC_RENDER_BGR)
-        return (nv12 ? render_crops_lanczos<SrcNv12<Lay>, DstRgb<true, OLay>> : render_crops_lanczos<SrcRgb<Lay>, DstRgb<true, OLay>>)(
-            name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
-    return (nv12 ? render_crops_lanczos<SrcNv12<Lay>, DstRgb<false, OLay>> : render_crops_lanczos<SrcRgb<Lay>, DstRgb<false, OLay>>)(
-        name, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+    if (to_nv12) return nv12 ? f(Pair<SrcNv12<Lay>, DstNv12<OLay>>()) : f(Pair<SrcRgb<Lay>, DstNv12<OLay>>());
+    if (flags & SVC_RENDER_BGR) return nv12 ? f(Pair<SrcNv12<Lay>, DstRgb<true, OLay>>()) : f(Pair<SrcRgb<Lay>, DstRgb<true, OLay>>());
+    return nv12 ? f(Pair<SrcNv12<Lay>, DstRgb<false, OLay>>()) : f(Pair<SrcRgb<Lay>, DstRgb<false, OLay>>());
 }
 
-// (the sub-pixel kernels exist for the Pitched source policy only, as the Lanczos ones: 2 sources x 3 sinks per output layout)
-template <class OLay>
-static int render_windows_fmt(const char *name, int pix_fmt, bool to_nv12, SvcHandle *h, const uint8_t *frames, const Pitched &L, const Colours &C,
-                              int n, int height, int width, const int32_t *origins_q8, int bw, int bh, uint8_t *out, const OLay &O, int oh, int ow,
-                              int flags, void *stream) {
-    const bool nv12 = pix_fmt == SVC_FMT_NV12;
-    if (to_nv12)
-        return (nv12 ? render_windows<SrcNv12<Pitched>, DstNv12<OLay>> : render_windows<SrcRgb<Pitched>, DstNv12<OLay>>)(
-            name, h, frames, L, C, n, height, width, origins_q8, bw, bh, out, O, oh, ow, flags, stream);
-    if (flags & SVC_RENDER_BGR)
-        return (nv12 ? render_windows<SrcNv12<Pitched>, DstRgb<true, OLay>> : render_windows<SrcRgb<Pitched>, DstRgb<true, OLay>>)(
-            name, h, frames, L, C, n, height, width, origins_q8, bw, bh, out, O, oh, ow, flags, stream);
-    return (nv12 ? render_windows<SrcNv12<Pitched>, DstRgb<false, OLay>> : render_windows<SrcRgb<Pitched>, DstRgb<false, OLay>>)(
-        name, h, frames, L, C, n, height, width, origins_q8, bw, bh, out, O, oh, ow, flags, stream);
+// The four packed entries: the linear launcher on the Packed policies of both sides (the measured default path), BT.601 limited.
+static int render_crops_packed(const RenderCall &c, int pix_fmt, bool to_nv12) {
+    return render_pair<Packed, Packed>(pix_fmt, to_nv12, c.flags, [&](auto p) {
+        return render_crops<typename decltype(p)::Src, typename decltype(p)::Dst>(c, Packed(), Packed());
+    });
 }
 
 extern "C" int svc_render_crops_u8(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                    int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_u8", SVC_FMT_RGB24, false, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
+    const RenderCall c = {"svc_render_crops_u8", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream, COLOURS_DEFAULT};
+    return render_crops_packed(c, SVC_FMT_RGB24, false);
 }
 extern "C" int svc_render_crops_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                      int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_nv12", SVC_FMT_NV12, false, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
+    const RenderCall c = {"svc_render_crops_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream, COLOURS_DEFAULT};
+    return render_crops_packed(c, SVC_FMT_NV12, false);
 }
 extern "C" int svc_render_crops_u8_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                            int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_u8_to_nv12", SVC_FMT_RGB24, true, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
+    const RenderCall c = {"svc_render_crops_u8_to_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream, COLOURS_DEFAULT};
+    return render_crops_packed(c, SVC_FMT_RGB24, true);
 }
 extern "C" int svc_render_crops_nv12_to_nv12(SvcHandle *h, const uint8_t *frames, int n, int height, int width, const int32_t *boxes,
                                              int bw, int bh, uint8_t *out, int oh, int ow, int flags, void *stream) {
-    return render_crops_fmt("svc_render_crops_nv12_to_nv12", SVC_FMT_NV12, true, h, frames, Packed(), COLOURS_DEFAULT, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
+    const RenderCall c = {"svc_render_crops_nv12_to_nv12", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream, COLOURS_DEFAULT};
+    return render_crops_packed(c, SVC_FMT_NV12, true);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1347,52 +1341,64 @@ static int resize_frames_any(const char *name, SvcHandle *h, const uint8_t *fram
     return resize_frames<SrcRgb<Pitched>>(name, h, frames, L, C, n, height, width, out, sh, sw, stream);
 }
 
-// The Lanczos kernels exist for the Pitched layouts only, 2 sources x 3 sinks: packed frames arrive as the packed layout's
-// values.  profiles/pitched_frames.json measured that policy within 4 % of the compile-time packed one on the linear kernels; six
-// more instances would buy nothing that has been measured.  linear_name: the name the SVC_FILTER_LINEAR path reports under
-// (svc_render_crops_filter forwards to svc_render_crops_layout: its bytes, its errors).
-// out_layout (svc_render_crops_to_layout; NULL for every other entry, whose output is packed and whose format is out_fmt): where
-// the bytes of the oh x ow output frames lie.  The pitched sinks are instantiated for this launcher only -- i.e. for the Pitched
-// source policy, all four kernels, 2 sources x 3 sinks -- and an out_layout that holds the packed values runs the packed sinks.
-// q8 (svc_render_windows_q8): `boxes` holds window origins [n][2] in 1/256 pixel, not boxes; every check above the launcher is shared.
-static int render_crops_any(const char *name, const char *linear_name, SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout,
-                            const SvcColour *in_colour, int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out,
-                            int out_fmt, const SvcFrameLayout *out_layout, const SvcColour *out_colour, int oh, int ow, int filter, int flags,
-                            void *stream, bool q8 = false) {
-    if (filter == SVC_FILTER_LINEAR) name = linear_name;
-    else if (filter != SVC_FILTER_LANCZOS) {
-        svc_set_error("%s: unknown filter %d (SVC_FILTER_LINEAR or SVC_FILTER_LANCZOS)", name, filter);
-        return SVC_E_INVALID;
-    }
+// What a layout entry renders with: one of the three launchers (MODE_WINDOWS: the call's `win` holds origins, not boxes), here on
+// the pairing of the call's formats, for one output layout policy.  The Lanczos and the sub-pixel kernels exist here only, i.e.
+// for the Pitched source policy, 2 sources x 3 sinks per output policy: packed frames arrive as the packed layout's values.
+// profiles/pitched_frames.json measured that policy within 4 % of the compile-time packed one on the linear kernels; six more
+// instances would buy nothing that has been measured.
+enum RenderMode { MODE_LINEAR, MODE_LANCZOS, MODE_WINDOWS };
+template <class OLay>
+static int render_mode(const RenderCall &c, RenderMode mode, int pix_fmt, bool to_nv12, const Pitched &L, const OLay &O) {
+    return render_pair<Pitched, OLay>(pix_fmt, to_nv12, c.flags, [&](auto p) {
+        typedef typename decltype(p)::Src Src;
+        typedef typename decltype(p)::Dst Dst;
+        switch (mode) {
+        case MODE_LANCZOS: return render_crops_lanczos<Src, Dst>(c, L, O);
+        case MODE_WINDOWS: return render_windows<Src, Dst>(c, L, O);
+        default: return render_crops<Src, Dst>(c, L, O);
+        }
+    });
+}
+
+// Behind every layout entry: the checks of the layouts and colours (which fill c.C), then render_mode.
+// out_layout (svc_render_crops_to_layout, svc_render_windows_q8; NULL for every other entry, whose output is packed and whose format
+// is out_fmt): where the bytes of the oh x ow output frames lie.  The pitched sinks are instantiated here only -- i.e. for the
+// Pitched source policy, every kernel, 2 sources x 3 sinks -- and an out_layout that holds the packed values runs the packed sinks.
+static int render_crops_any(RenderCall &c, RenderMode mode, const SvcFrameLayout *layout, const SvcColour *in_colour, int out_fmt,
+                            const SvcFrameLayout *out_layout, const SvcColour *out_colour) {
     Pitched L, O = {0, 0, 0, 0};
-    int rc = layout_check(name, "", layout, n, height, width, L), mi, ri, mo, ro;
+    int rc = layout_check(c.name, "", layout, c.n, c.height, c.width, L), mi, ri, mo, ro;
     if (rc) return rc;
     bool packed_out = true;
     if (out_layout) {
-        if ((rc = layout_check(name, "out_layout: ", out_layout, n, oh, ow, O))) return rc;
+        if ((rc = layout_check(c.name, "out_layout: ", out_layout, c.n, c.oh, c.ow, O))) return rc;
         out_fmt = out_layout->pix_fmt;
         packed_out = out_fmt == SVC_FMT_NV12
-            ? O.pitch == ow && O.chroma_pitch == ow && O.chroma_offset == (long long)oh * ow && (size_t)O.frame_stride == DstNv12<>::frame_bytes(oh, ow)
-            : O.pitch == 3ll * ow && (size_t)O.frame_stride == DstRgb<false>::frame_bytes(oh, ow);
+            ? O.pitch == c.ow && O.chroma_pitch == c.ow && O.chroma_offset == (long long)c.oh * c.ow &&
+                  (size_t)O.frame_stride == DstNv12<>::frame_bytes(c.oh, c.ow)
+            : O.pitch == 3ll * c.ow && (size_t)O.frame_stride == DstRgb<false>::frame_bytes(c.oh, c.ow);
     } else if (out_fmt != SVC_FMT_RGB24 && out_fmt != SVC_FMT_NV12) {
-        svc_set_error("%s: unknown out_fmt %d (SVC_FMT_RGB24 or SVC_FMT_NV12)", name, out_fmt);
+        svc_set_error("%s: unknown out_fmt %d (SVC_FMT_RGB24 or SVC_FMT_NV12)", c.name, out_fmt);
         return SVC_E_INVALID;
     }
     const bool to_nv12 = out_fmt == SVC_FMT_NV12;
-    if ((rc = colour_check(name, "in_colour", in_colour, layout->pix_fmt == SVC_FMT_NV12, mi, ri)) ||
-        (rc = colour_check(name, "out_colour", out_colour, to_nv12, mo, ro)))
+    if ((rc = colour_check(c.name, "in_colour", in_colour, layout->pix_fmt == SVC_FMT_NV12, mi, ri)) ||
+        (rc = colour_check(c.name, "out_colour", out_colour, to_nv12, mo, ro)))
         return rc;
-    const Colours C = {COLOUR_DEC[mi][ri], COLOUR_ENC[mo][ro]};
-    if (q8) {                               // svc_render_windows_q8: `boxes` holds the origins [n][2] in 1/256 pixel, the filter is LINEAR
-        if (packed_out) return render_windows_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
-        return render_windows_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+    c.C = {COLOUR_DEC[mi][ri], COLOUR_ENC[mo][ro]};
+    return packed_out ? render_mode(c, mode, layout->pix_fmt, to_nv12, L, Packed()) : render_mode(c, mode, layout->pix_fmt, to_nv12, L, O);
+}
+
+// The same for the entries that take a filter (SVC_FILTER_*).  linear_name: the name SVC_FILTER_LINEAR reports under
+// (svc_render_crops_filter forwards to svc_render_crops_layout: its bytes, its errors).
+static int render_crops_filtered(RenderCall &c, const char *linear_name, int filter, const SvcFrameLayout *layout, const SvcColour *in_colour,
+                                 int out_fmt, const SvcFrameLayout *out_layout, const SvcColour *out_colour) {
+    if (filter == SVC_FILTER_LINEAR) c.name = linear_name;
+    else if (filter != SVC_FILTER_LANCZOS) {
+        svc_set_error("%s: unknown filter %d (SVC_FILTER_LINEAR or SVC_FILTER_LANCZOS)", c.name, filter);
+        return SVC_E_INVALID;
     }
-    if (filter == SVC_FILTER_LINEAR) {
-        if (packed_out) return render_crops_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
-        return render_crops_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
-    }
-    if (packed_out) return render_crops_lanczos_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, Packed(), oh, ow, flags, stream);
-    return render_crops_lanczos_fmt(name, layout->pix_fmt, to_nv12, h, frames, L, C, n, height, width, boxes, bw, bh, out, O, oh, ow, flags, stream);
+    return render_crops_any(c, filter == SVC_FILTER_LINEAR ? MODE_LINEAR : MODE_LANCZOS, layout, in_colour, out_fmt, out_layout, out_colour);
 }
 
 extern "C" int svc_resize_frames_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height,
@@ -1402,16 +1408,15 @@ extern "C" int svc_resize_frames_layout(SvcHandle *h, const uint8_t *frames, con
 extern "C" int svc_render_crops_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height,
                                        int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
                                        int flags, void *stream) {
-    const char *name = "svc_render_crops_layout";
-    return render_crops_any(name, name, h, frames, layout, nullptr, n, height, width, boxes, bw, bh, out, out_fmt, nullptr, nullptr, oh, ow,
-                            SVC_FILTER_LINEAR, flags, stream);
+    RenderCall c = {"svc_render_crops_layout", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream, COLOURS_DEFAULT};
+    return render_crops_any(c, MODE_LINEAR, layout, nullptr, out_fmt, nullptr, nullptr);
 }
 // svc_render_crops_layout with a choice of filter (include/svc.h)
 extern "C" int svc_render_crops_filter(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, int n, int height, int width,
                                        const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt, int oh, int ow,
                                        int filter, int flags, void *stream) {
-    return render_crops_any("svc_render_crops_filter", "svc_render_crops_layout", h, frames, layout, nullptr, n, height, width, boxes, bw, bh,
-                            out, out_fmt, nullptr, nullptr, oh, ow, filter, flags, stream);
+    RenderCall c = {"svc_render_crops_filter", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream, COLOURS_DEFAULT};
+    return render_crops_filtered(c, "svc_render_crops_layout", filter, layout, nullptr, out_fmt, nullptr, nullptr);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1424,25 +1429,24 @@ extern "C" int svc_resize_frames_colour(SvcHandle *h, const uint8_t *frames, con
 extern "C" int svc_render_crops_colour(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *in_colour, int n,
                                        int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out, int out_fmt,
                                        const SvcColour *out_colour, int oh, int ow, int filter, int flags, void *stream) {
-    const char *name = "svc_render_crops_colour";
-    return render_crops_any(name, name, h, frames, layout, in_colour, n, height, width, boxes, bw, bh, out, out_fmt, nullptr, out_colour, oh, ow,
-                            filter, flags, stream);
+    RenderCall c = {"svc_render_crops_colour", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream, COLOURS_DEFAULT};
+    return render_crops_filtered(c, c.name, filter, layout, in_colour, out_fmt, nullptr, out_colour);
 }
 
 // --------------------------------------------------------------------------------------
 // the same into the caller's output layout: an encoder's surfaces (include/svc.h states the write contract)
 // --------------------------------------------------------------------------------------
+static int out_layout_null(const char *name) {
+    svc_set_error("%s: out_layout: layout is NULL", name);
+    return SVC_E_INVALID;
+}
+
 extern "C" int svc_render_crops_to_layout(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *in_colour,
                                           int n, int height, int width, const int32_t *boxes, int bw, int bh, uint8_t *out,
                                           const SvcFrameLayout *out_layout, const SvcColour *out_colour, int oh, int ow, int filter, int flags,
                                           void *stream) {
-    const char *name = "svc_render_crops_to_layout";
-    if (!out_layout) {
-        svc_set_error("%s: out_layout: layout is NULL", name);
-        return SVC_E_INVALID;
-    }
-    return render_crops_any(name, name, h, frames, layout, in_colour, n, height, width, boxes, bw, bh, out, 0, out_layout, out_colour, oh, ow,
-                            filter, flags, stream);
+    RenderCall c = {"svc_render_crops_to_layout", h, frames, n, height, width, boxes, bw, bh, out, oh, ow, flags, stream, COLOURS_DEFAULT};
+    return out_layout ? render_crops_filtered(c, c.name, filter, layout, in_colour, 0, out_layout, out_colour) : out_layout_null(c.name);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1451,11 +1455,6 @@ extern "C" int svc_render_crops_to_layout(SvcHandle *h, const uint8_t *frames, c
 extern "C" int svc_render_windows_q8(SvcHandle *h, const uint8_t *frames, const SvcFrameLayout *layout, const SvcColour *in_colour,
                                      int n, int height, int width, const int32_t *origins_q8, int bw, int bh, uint8_t *out,
                                      const SvcFrameLayout *out_layout, const SvcColour *out_colour, int oh, int ow, int flags, void *stream) {
-    const char *name = "svc_render_windows_q8";
-    if (!out_layout) {
-        svc_set_error("%s: out_layout: layout is NULL", name);
-        return SVC_E_INVALID;
-    }
-    return render_crops_any(name, name, h, frames, layout, in_colour, n, height, width, origins_q8, bw, bh, out, 0, out_layout, out_colour, oh, ow,
-                            SVC_FILTER_LINEAR, flags, stream, true);
+    RenderCall c = {"svc_render_windows_q8", h, frames, n, height, width, origins_q8, bw, bh, out, oh, ow, flags, stream, COLOURS_DEFAULT};
+    return out_layout ? render_crops_any(c, MODE_WINDOWS, layout, in_colour, 0, out_layout, out_colour) : out_layout_null(c.name);
 }

@@ -312,6 +312,33 @@ def out_layout_of(out_layout, out_fmt, oh, ow, frame_stride=None):
         raise ValueError('out_layout: %s' % e) from None
 
 
+def _pictures(frames, layout, pix_fmt):
+    """(n, h, w) of the pictures in `frames`, checked: a contiguous CUDA tensor of picture_size's shapes, or, with a layout, what
+    _pitched takes."""
+    if layout is None:
+        _need_cuda(frames, torch.uint8, 'frames')
+        return picture_size(frames, pix_fmt)
+    return _pitched(frames, layout, pix_fmt), layout.h, layout.w
+
+
+def _src_args(handle, frames, layout, pix_fmt, n, h, w, *in_colour):
+    """The leading arguments of the C entries that take the frames' SvcFrameLayout (and, behind it, in_colour): packed frames
+    go as the packed layout's values."""
+    lay = (layout or frame_layout(pix_fmt, h, w)).struct()
+    return (handle, _ptr(frames), ctypes.byref(lay)) + in_colour + (n, h, w)
+
+
+def _out_shape(n, out_fmt, oh, ow, bgr, out_layout):
+    """Shape of the renderer's output of n frames of oh x ow in `out_fmt`: (n,) + out_frame_shape's, or (n, frame_stride) with an
+    out_layout, which must be an ops.FrameLayout (TypeError) of that format and picture size (out_layout_of's ValueErrors)."""
+    shape = (n,) + out_frame_shape(out_fmt, oh, ow, bgr)
+    if out_layout is not None:
+        if not isinstance(out_layout, FrameLayout):
+            raise TypeError('out_layout must be an ops.FrameLayout (ops.frame_layout(out_fmt, oh, ow, dict(pitch=...), frame_stride))')
+        shape = (n, out_layout_of(out_layout, out_fmt, oh, ow).frame_stride)
+    return shape
+
+
 BLEND_NEXT, MAP_HELD = 1, 2          # bits of cluster_center_'s per-map flags (include/svc.h: SVC_BLEND_NEXT, SVC_MAP_HELD)
 
 
@@ -367,29 +394,17 @@ class Engine:
         colour (what ops.frame_colour takes; nv12 only, else ValueError): the matrix and range the frames are decoded with
         (svc_resize_frames_colour); None, or BT.601 limited spelled out, is the call without it."""
         colour = _side_colour(colour, pix_fmt, 'colour')
-        if colour is not None:              # one entry for every layout: packed frames as the packed layout's values
-            if layout is None:
-                _need_cuda(frames, torch.uint8, 'frames')
-                n, h, w = picture_size(frames, pix_fmt)
-            else:
-                n, h, w = _pitched(frames, layout, pix_fmt), layout.h, layout.w
-            out = torch.empty((n, sh, sw, 3), dtype=torch.uint8, device=frames.device)
-            lay = (layout or frame_layout(pix_fmt, h, w)).struct()
-            _lib.check(self.lib.svc_resize_frames_colour(self._h, _ptr(frames), ctypes.byref(lay), _colour_struct(colour), n, h, w,
-                                                         _ptr(out), sh, sw, _stream()))
-            return out
-        if layout is not None:
-            n = _pitched(frames, layout, pix_fmt)
-            out = torch.empty((n, sh, sw, 3), dtype=torch.uint8, device=frames.device)
-            lay = layout.struct()
-            _lib.check(self.lib.svc_resize_frames_layout(self._h, _ptr(frames), ctypes.byref(lay), n, layout.h, layout.w, _ptr(out),
-                                                         sh, sw, _stream()))
-            return out
-        _need_cuda(frames, torch.uint8, 'frames')
-        n, h, w = picture_size(frames, pix_fmt)
+        n, h, w = _pictures(frames, layout, pix_fmt)
         out = torch.empty((n, sh, sw, 3), dtype=torch.uint8, device=frames.device)
-        fn = self.lib.svc_resize_frames_nv12 if pix_fmt == 'nv12' else self.lib.svc_resize_frames_u8
-        _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(out), sh, sw, _stream()))
+        if colour is not None:              # one entry for every layout: packed frames as the packed layout's values
+            lay = (layout or frame_layout(pix_fmt, h, w)).struct()
+            entry, src = 'svc_resize_frames_colour', (ctypes.byref(lay), _colour_struct(colour))
+        elif layout is not None:
+            lay = layout.struct()
+            entry, src = 'svc_resize_frames_layout', (ctypes.byref(lay),)
+        else:
+            entry, src = 'svc_resize_frames_nv12' if pix_fmt == 'nv12' else 'svc_resize_frames_u8', ()
+        _lib.check(getattr(self.lib, entry)(self._h, _ptr(frames), *src, n, h, w, _ptr(out), sh, sw, _stream()))
         return out
 
     # -- rendering ------------------------------------------------------------------------
@@ -427,11 +442,7 @@ class Engine:
             b0 = [0, 0, 2, 2] if out_fmt == 'nv12' else [0, 0, 1, 1]
         bw, bh = int(b0[2] - b0[0]), int(b0[3] - b0[1])
         oh, ow = (bh, bw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
-        shape = (n,) + out_frame_shape(out_fmt, oh, ow, bgr)      # (the ValueErrors come before anything touches the device)
-        if out_layout is not None:
-            if not isinstance(out_layout, FrameLayout):
-                raise TypeError('out_layout must be an ops.FrameLayout (ops.frame_layout(out_fmt, oh, ow, dict(pitch=...), frame_stride))')
-            shape = (n, out_layout_of(out_layout, out_fmt, oh, ow).frame_stride)
+        shape = _out_shape(n, out_fmt, oh, ow, bgr, out_layout)   # (the ValueErrors come before anything touches the device)
         if layout is None:
             _need_cuda(frames, torch.uint8, 'frames')
         else:
@@ -447,59 +458,45 @@ class Engine:
         check_interp(interp)
         colour, out_colour = _side_colour(colour, pix_fmt, 'colour'), _side_colour(out_colour, out_fmt, 'out_colour')
         _need_cuda(boxes, torch.int32, 'boxes')
-        if out_layout is not None:          # one entry for every format, layout, filter and colour; out: [n, frame_stride] or a view like it
-            out_frame_shape(out_fmt, out_layout.h, out_layout.w, bgr)
+        if out_layout is not None:          # out: [n, frame_stride] or a view like it
+            oh, ow = out_layout.h, out_layout.w
+            out_frame_shape(out_fmt, oh, ow, bgr)
             on = _pitched(out, out_layout, out_fmt, 'out')
-            if layout is None:
-                _need_cuda(frames, torch.uint8, 'frames')
-                n, h, w = picture_size(frames, pix_fmt)
-            else:
-                n, h, w = _pitched(frames, layout, pix_fmt), layout.h, layout.w
+            n, h, w = _pictures(frames, layout, pix_fmt)
             if on != n:
                 raise ValueError('out holds %d frames, frames holds %d' % (on, n))
             if tuple(boxes.shape) != (n, 4):
                 raise ValueError('boxes of shape %s for %d frames (int32 [n, 4])' % (tuple(boxes.shape), n))
-            if not hasattr(self.lib, 'svc_render_crops_to_layout'):
+        else:
+            _need_cuda(out, torch.uint8, 'out')
+            n, h, w = _pictures(frames, layout, pix_fmt)
+            if out_fmt == 'nv12':
+                on, oh, ow = picture_size(out, 'nv12')
+                out_frame_shape(out_fmt, oh, ow, bgr)
+            else:
+                out_frame_shape(out_fmt, 1, 1)
+                assert out.shape[3] == 3
+                on, oh, ow = (int(v) for v in out.shape[:3])
+            assert tuple(boxes.shape) == (n, 4) and on == n
+
+        src, window, flags = (self._h, frames, layout, pix_fmt, n, h, w), (_ptr(boxes), bw, bh, _ptr(out)), RENDER_BGR if bgr else 0
+        # the entry: the first rung that holds, each one entry for everything below it (format, layout, filter, colour)
+        if out_layout is not None:
+            entry = 'svc_render_crops_to_layout'
+            if not hasattr(self.lib, entry):
                 raise _lib.SvcError('%s lacks svc_render_crops_to_layout: an out_layout needs a build that has it' % _lib.LIB_PATH)
-            lay, olay = (layout or frame_layout(pix_fmt, h, w)).struct(), out_layout.struct()
-            _lib.check(self.lib.svc_render_crops_to_layout(self._h, _ptr(frames), ctypes.byref(lay), _colour_struct(colour), n, h, w,
-                                                           _ptr(boxes), bw, bh, _ptr(out), ctypes.byref(olay), _colour_struct(out_colour),
-                                                           out_layout.h, out_layout.w, INTERPS.index(interp), RENDER_BGR if bgr else 0,
-                                                           _stream()))
-            return out
-        _need_cuda(out, torch.uint8, 'out')
-        if layout is None:
-            _need_cuda(frames, torch.uint8, 'frames')
-            n, h, w = picture_size(frames, pix_fmt)
+            olay = out_layout.struct()
+            args = _src_args(*src, _colour_struct(colour)) + window + (ctypes.byref(olay), _colour_struct(out_colour), oh, ow, INTERPS.index(interp), flags)
+        elif colour is not None or out_colour is not None:
+            entry = 'svc_render_crops_colour'
+            args = _src_args(*src, _colour_struct(colour)) + window + (OUT_FMTS.index(out_fmt), _colour_struct(out_colour), oh, ow, INTERPS.index(interp), flags)
+        elif interp != 'linear':
+            entry, args = 'svc_render_crops_filter', _src_args(*src) + window + (OUT_FMTS.index(out_fmt), oh, ow, INTERPS.index(interp), flags)
+        elif layout is not None:
+            entry, args = 'svc_render_crops_layout', _src_args(*src) + window + (OUT_FMTS.index(out_fmt), oh, ow, flags)
         else:
-            n, h, w = _pitched(frames, layout, pix_fmt), layout.h, layout.w
-        if out_fmt == 'nv12':
-            on, oh, ow = picture_size(out, 'nv12')
-            out_frame_shape(out_fmt, oh, ow, bgr)
-        else:
-            out_frame_shape(out_fmt, 1, 1)
-            assert out.shape[3] == 3
-            on, oh, ow = (int(v) for v in out.shape[:3])
-        assert tuple(boxes.shape) == (n, 4) and on == n
-        if colour is not None or out_colour is not None:        # one entry for every format, layout and filter
-            lay = (layout or frame_layout(pix_fmt, h, w)).struct()
-            _lib.check(self.lib.svc_render_crops_colour(self._h, _ptr(frames), ctypes.byref(lay), _colour_struct(colour), n, h, w,
-                                                        _ptr(boxes), bw, bh, _ptr(out), OUT_FMTS.index(out_fmt), _colour_struct(out_colour),
-                                                        oh, ow, INTERPS.index(interp), RENDER_BGR if bgr else 0, _stream()))
-            return out
-        if interp != 'linear':              # one entry for every format and layout: packed frames as the packed layout's values
-            lay = (layout or frame_layout(pix_fmt, h, w)).struct()
-            _lib.check(self.lib.svc_render_crops_filter(self._h, _ptr(frames), ctypes.byref(lay), n, h, w, _ptr(boxes), bw, bh, _ptr(out),
-                                                        OUT_FMTS.index(out_fmt), oh, ow, INTERPS.index(interp),
-                                                        RENDER_BGR if bgr else 0, _stream()))
-            return out
-        if layout is not None:
-            lay = layout.struct()
-            _lib.check(self.lib.svc_render_crops_layout(self._h, _ptr(frames), ctypes.byref(lay), n, h, w, _ptr(boxes), bw, bh, _ptr(out),
-                                                        OUT_FMTS.index(out_fmt), oh, ow, RENDER_BGR if bgr else 0, _stream()))
-            return out
-        fn = getattr(self.lib, RENDER_ENTRIES[pix_fmt, out_fmt])
-        _lib.check(fn(self._h, _ptr(frames), n, h, w, _ptr(boxes), bw, bh, _ptr(out), oh, ow, RENDER_BGR if bgr else 0, _stream()))
+            entry, args = RENDER_ENTRIES[pix_fmt, out_fmt], (self._h, _ptr(frames), n, h, w) + window + (oh, ow, flags)
+        _lib.check(getattr(self.lib, entry)(*args, _stream()))
         return out
 
     def render_windows(self, frames, origins_q8, win_wh, out_hw=None, bgr=False, out=None, pix_fmt='rgb24', out_fmt='rgb24', layout=None,
@@ -517,21 +514,12 @@ class Engine:
         if bw < 1 or bh < 1:
             raise ValueError('empty window %d x %d' % (bw, bh))
         oh, ow = (bh, bw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
-        shape = (n,) + out_frame_shape(out_fmt, oh, ow, bgr)
-        if out_layout is not None:
-            if not isinstance(out_layout, FrameLayout):
-                raise TypeError('out_layout must be an ops.FrameLayout (ops.frame_layout(out_fmt, oh, ow, dict(pitch=...), frame_stride))')
-            shape = (n, out_layout_of(out_layout, out_fmt, oh, ow).frame_stride)
+        shape = _out_shape(n, out_fmt, oh, ow, bgr, out_layout)
         if not (torch.is_tensor(origins_q8) and origins_q8.dtype == torch.int32):
             raise TypeError('origins_q8 must be a CUDA tensor of dtype torch.int32 (window origins in 1/256 pixel)')
         if tuple(origins_q8.shape) != (n, 2):
             raise ValueError('origins_q8 of shape %s for %d frames (int32 [n, 2]: x, y)' % (tuple(origins_q8.shape), n))
-        if layout is None:
-            _need_cuda(frames, torch.uint8, 'frames')
-            _, h, w = picture_size(frames, pix_fmt)
-        else:
-            _pitched(frames, layout, pix_fmt)
-            h, w = layout.h, layout.w
+        _, h, w = _pictures(frames, layout, pix_fmt)
         if bw > w or bh > h:
             raise ValueError('a window of %d x %d does not fit the %d x %d picture' % (bw, bh, w, h))
         _need_cuda(origins_q8, torch.int32, 'origins_q8')
@@ -549,9 +537,8 @@ class Engine:
         if not hasattr(self.lib, 'svc_render_windows_q8'):
             raise _lib.SvcError('%s lacks svc_render_windows_q8: sub-pixel windows need a build that has it' % _lib.LIB_PATH)
         colour, out_colour = _side_colour(colour, pix_fmt, 'colour'), _side_colour(out_colour, out_fmt, 'out_colour')
-        lay = (layout or frame_layout(pix_fmt, h, w)).struct()
         olay = (out_layout or frame_layout(out_fmt, oh, ow)).struct()       # (the packed values run the packed sinks)
-        _lib.check(self.lib.svc_render_windows_q8(self._h, _ptr(frames), ctypes.byref(lay), _colour_struct(colour), n, h, w, _ptr(origins_q8),
+        _lib.check(self.lib.svc_render_windows_q8(*_src_args(self._h, frames, layout, pix_fmt, n, h, w, _colour_struct(colour)), _ptr(origins_q8),
                                                   bw, bh, _ptr(out), ctypes.byref(olay), _colour_struct(out_colour), oh, ow,
                                                   RENDER_BGR if bgr else 0, _stream()))
         return out
