@@ -91,7 +91,8 @@ const char *svc_last_error(void);
  *     SVC_NODE_MAP / SVC_NODE_MAP_PROFILE: two new node ids of svc_debug_run_node, which an older library refuses as unknown; and
  *     svc_debug_sort_plan (SVC_SORTPLAN_*): one new test door that takes no handle, no struct; and
  *     svc_focus_jumps_u8 and svc_host_focus_hold (focus stability from resident maps): two new entries, no handle, no struct.
- * 13 = svc_debug_scratch_fill exists. */
+ * 13 = svc_debug_scratch_fill exists.
+ * (13, no bump) svc_demo_frames_u8 (SVC_MARK_*: the five-panel demo frames): one new entry, no handle, no struct. */
 #define SVC_ABI_VERSION 13
 int svc_abi_version(void);
 
@@ -369,6 +370,63 @@ int svc_render_windows_q8(SvcHandle *h, const uint8_t *frames, const SvcFrameLay
                           int n, int height, int width, const int32_t *origins_q8 /* [n][2]: x, y */, int bw, int bh,
                           uint8_t *out, const SvcFrameLayout *out_layout, const SvcColour *out_colour,
                           int oh, int ow, int flags, void *stream);
+
+/* The five-panel demo frames of sc_renderer (smartVidCrop.py:1924-2126), composed on the device: per frame the picture, the raw
+ * saliency map, the filtered map, the overlay of the two and the picture again, side by side, with integer-defined marks drawn on
+ * top.  small[n][ph][pw][3] u8 RGB: the frames ALREADY at the process size (svc_resize_frames_* makes them: the compositor knows
+ * nothing of pixel formats, layouts or colours); raw and filt [n_maps][ph][pw] u8 each; map_of[n] int32: the map of frame f; out
+ * [n][ph][5 * pw][3] u8.  All pointers are DEVICE pointers.
+ * Panels.  Pixel (y, x) of panel k of frame f is out[f][y][k * pw + x].  With S = small[f][y][x], m = map_of[f] (an m outside
+ * [0, n_maps) reads as an all-zero map), r = raw[m][y][x], g = filt[m][y][x]:
+ *   panel 0: S      panel 1: (r, r, r)      panel 2: (g, g, g)      panel 4: S
+ *   panel 3, per channel: the mean of S and g with ties to even,  s = S + g;  v = s >> 1;  v += (s & v & 1)
+ * -- what cv2.addWeighted(a, 0.5, b, 0.5, 0) gives through its float path (cvRound of an exact half); OpenCV is not available
+ * where this library is built and tested, so that equality is UNPINNED here: the rule above is the definition.
+ * Marks.  marks[n_marks][SVC_MARK_WORDS] int32; the marks of frame f are rows first[f] .. first[f + 1] (first[n + 1] int32): both
+ * bounds are clamped into [0, n_marks], a negative count is 0, and only the first SVC_DEMO_MAX_MARKS rows of the range are looked at
+ * (ignored rows among them count).  They apply in list order, after the panels.  Words of a mark:
+ *   { kind | panel << 8,  x0,  y0,  x1,  y1,  p,  q,  r | g << 8 | b << 16 }        coordinates in PANEL pixels
+ * A mark is confined to its own panel: it covers only pixels 0 <= x < pw, 0 <= y < ph of that panel, so one that reaches over a
+ * panel's edge is cut there and never shows in the neighbour.  It covers pixel P = (x, y) when
+ *   SVC_MARK_DISC   (x - x0)^2 + (y - y0)^2 <= p^2
+ *   SVC_MARK_LINE   P is within p / 2 of the segment P0 P1 (thickness p), in exact integers: d = P1 - P0, L = d.d, e = P - P0,
+ *                   u = e.d;  L == 0 || u <= 0: 4 |e|^2 <= p^2;  else u >= L: 4 |P - P1|^2 <= p^2;  else 4 (e x d)^2 <= p^2 L
+ *                   (the kernel forms every product in int64 and the last test as (e x d)^2 <= (p^2 L) >> 2 where |e x d| < 2^31,
+ *                   false otherwise: p^2 L < 2^50, so the two are the same statement and nothing overflows)
+ *   SVC_MARK_RECT   x0 <= x <= x1 && y0 <= y <= y1 and x == x0 || x == x1 || y == y0 || y == y1 (the 1-pixel outline)
+ *   SVC_MARK_TEXT   0 <= x - x0 < w, 0 <= y - y0 < h, with w = q & 0xffff, h = q >> 16: a sprite of coverages, a =
+ *                   atlas[p + (y - y0) * w + (x - x0)] (the offset formed in int64); a byte outside [0, atlas_bytes) is not
+ *                   read and leaves the pixel alone
+ * DISC, LINE and RECT replace the pixel with the mark's colour (the reference writes its "fading" alpha into a BGRA channel that
+ * COLOR_BGRA2BGR then drops, :2054: its marks are opaque, and so are these); TEXT blends per channel, c the mark's and d the
+ * pixel's value:  (c * a + d * (255 - a) + 127) / 255.
+ * A mark is IGNORED -- never a fault, never a read outside the arrays -- when its word 0 is negative, its kind is none of the
+ * four or its panel is above 4; when one of x0, y0, x1, y1 is beyond +-32767 (all four are checked for every kind); when p is
+ * outside 0 .. 255 for DISC or LINE; when q is negative or a sprite side is above 4096 for TEXT.  Colour bits above 24 are not read.
+ * The marks are our own rules, not OpenCV's rasterisers (cv2.circle / cv2.line with LINE_AA, cv2.putText's Hershey glyphs): no
+ * anti-aliasing, and the glyphs are whatever the caller puts into the atlas.
+ * flags: SVC_RENDER_BGR stores every pixel -- panels and marks -- as (b, g, r): the RGB result with the channels reversed.
+ * Contract.  Writes all n * ph * 5 pw * 3 bytes of out and no other byte, wherever out begins (16-byte stores where a row's
+ * address allows them, the head and tail of every row bytewise); reads only inside the given arrays, which need no alignment and
+ * are left unchanged; out must not overlap them.  n == 0 is a successful no-op.  SVC_E_INVALID with a message, before any launch:
+ * a negative n, n_maps or n_marks; ph or pw < 1 (or 15 pw, or the number of workgroups, beyond 2^31 - 1); flags with bits other than
+ * SVC_RENDER_BGR; with n > 0 a NULL small, map_of, first or out, NULL raw or filt with n_maps > 0, NULL marks with n_marks > 0,
+ * NULL atlas with atlas_bytes > 0.  atlas may be NULL with atlas_bytes == 0 and marks NULL with n_marks == 0.
+ * No handle (like svc_focus_jumps_u8): no weights, no scratch, nothing kept between calls; one launch on the caller's stream, on
+ * the CURRENT device.  Not counted by the profile classes (they belong to a handle). */
+#define SVC_MARK_WORDS 8
+#define SVC_DEMO_MAX_MARKS 64
+#define SVC_DEMO_PANELS 5
+#define SVC_MARK_DISC 0
+#define SVC_MARK_LINE 1
+#define SVC_MARK_RECT 2
+#define SVC_MARK_TEXT 3
+int svc_demo_frames_u8(const uint8_t *small /* [n][ph][pw][3] RGB, frames already at process size */, int n, int ph, int pw,
+                       const uint8_t *raw, const uint8_t *filt /* [n_maps][ph][pw] each */, int n_maps,
+                       const int32_t *map_of /* [n] */,
+                       const int32_t *marks /* [n_marks][SVC_MARK_WORDS] */, int n_marks, const int32_t *first /* [n + 1] */,
+                       const uint8_t *atlas, size_t atlas_bytes,
+                       uint8_t *out /* [n][ph][5 * pw][3] */, int flags /* SVC_RENDER_BGR */, void *stream);
 
 /* frames_nhwc[n][h][w][3] u8 RGB (saliency size, e.g. 140x250) -> maps_nhw[n][h][w] u8.
  * Frame-major output; the reference's [h][w][n] view is a transpose done by the

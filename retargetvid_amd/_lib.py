@@ -23,7 +23,7 @@ EXPORTS = ('svc_last_error', 'svc_abi_version', 'svc_create', 'svc_destroy', 'sv
            'svc_resize_frames_layout', 'svc_render_crops_layout', 'svc_render_crops_filter', 'svc_debug_net_plan',
            'svc_resize_frames_colour', 'svc_render_crops_colour', 'svc_render_crops_to_layout',
            'svc_render_windows_q8', 'svc_debug_tail_plan', 'svc_debug_scratch_fill', 'svc_debug_sort_plan',
-           'svc_focus_jumps_u8', 'svc_host_focus_hold')
+           'svc_focus_jumps_u8', 'svc_host_focus_hold', 'svc_demo_frames_u8')
 
 
 class SvcParams(ctypes.Structure):
@@ -49,11 +49,13 @@ class SvcFrameLayout(ctypes.Structure):
 
 MATRIX_BT601, MATRIX_BT709 = 0, 1       # include/svc.h: SVC_MATRIX_*
 RANGE_LIMITED, RANGE_FULL = 0, 1        # include/svc.h: SVC_RANGE_*
+MARK_WORDS, DEMO_MAX_MARKS = 8, 64      # include/svc.h: SVC_MARK_WORDS, SVC_DEMO_MAX_MARKS
+MARK_DISC, MARK_LINE, MARK_RECT, MARK_TEXT = 0, 1, 2, 3     # include/svc.h: SVC_MARK_*
 
 
 COLOUR_ENTRIES = ('svc_resize_frames_colour', 'svc_render_crops_colour')
 LATER_ENTRIES = COLOUR_ENTRIES + ('svc_render_crops_to_layout', 'svc_render_windows_q8', 'svc_debug_tail_plan', 'svc_debug_sort_plan',
-                                  'svc_focus_jumps_u8', 'svc_host_focus_hold')        # entries that came without an ABI bump: bound where the build has them
+                                  'svc_focus_jumps_u8', 'svc_host_focus_hold', 'svc_demo_frames_u8')        # entries that came without an ABI bump: bound where the build has them
 
 
 class SvcColour(ctypes.Structure):
@@ -175,6 +177,9 @@ def load():
         lib.svc_focus_jumps_u8.argtypes = [vp, i32, i32, i32, vp, f64, vp, vp]
     if hasattr(lib, 'svc_host_focus_hold'):
         lib.svc_host_focus_hold.argtypes = [vp, vp, i32, vp, f64, i32, f64, f64, vp]
+    # (svc_demo_frames_u8 likewise: ops.demo_frames on an older build fails by the symbol's name)
+    if hasattr(lib, 'svc_demo_frames_u8'):
+        lib.svc_demo_frames_u8.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, sz, vp, i32, vp]
     for name in EXPORTS:
         if name not in ('svc_last_error', 'svc_abi_version') and (name not in LATER_ENTRIES or hasattr(lib, name)):
             getattr(lib, name).restype = i32

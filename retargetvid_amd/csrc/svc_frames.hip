@@ -17,6 +17,8 @@
 //   SrcNv12          YUV -> RGB conversion fused into both (no counterpart: the reference is handed RGB)
 //   DstNv12          the same crops written as NV12, the forward transform fused in (no counterpart: the reference hands RGB to its writer)
 //   Nv12Dec, Nv12Enc the colour (matrix x range: SvcColour) of those two, run-time kernel arguments
+//   k_demo_frames    the five panels of the demo video and the marks on them     smartVidCrop.py:1924-2126 (at the end of this file;
+//                    a consumer of the down-scale's output beside the renderer: no source, no sink, no handle)
 //
 // The host layer under the render entries is written once as well: an entry fills a RenderCall and makes one call; render_pair
 // states the source x sink pairings (2 x 3) once; the launchers -- render_crops, render_windows, render_crops_lanczos -- are
@@ -1457,4 +1459,188 @@ extern "C" int svc_render_windows_q8(SvcHandle *h, const uint8_t *frames, const 
                                      const SvcFrameLayout *out_layout, const SvcColour *out_colour, int oh, int ow, int flags, void *stream) {
     RenderCall c = {"svc_render_windows_q8", h, frames, n, height, width, origins_q8, bw, bh, out, oh, ow, flags, stream, COLOURS_DEFAULT};
     return out_layout ? render_crops_any(c, MODE_WINDOWS, layout, in_colour, 0, out_layout, out_colour) : out_layout_null(c.name);
+}
+
+// --------------------------------------------------------------------------------------
+// the five-panel demo frames: a consumer beside the renderer, not inside it (include/svc.h states every rule: svc_demo_frames_u8)
+//   k_demo_frames    framex | smaps_orig | smaps | addWeighted | framex side by side, marks on top    smartVidCrop.py:1924-2126
+// A workgroup composes DEMO_ROWS output rows of one frame.  Its first wavefront looks at the frame's marks once -- at most
+// SVC_DEMO_MAX_MARKS = one lane each --, drops the ignored ones and those whose bounding box misses the workgroup's rows or their
+// own panel, and leaves the rest in LDS in list order (ballot + prefix count) with the box in row coordinates; a pixel then walks
+// that list with one box test per mark.  Rows are stored like the render kernels': 16-byte groups where the row's address
+// allows them, its head and tail bytewise, so that no byte outside out is written whatever its phase (a row is 15 pw bytes).
+// --------------------------------------------------------------------------------------
+constexpr int DEMO_TB = 256, DEMO_ROWS = 4;
+constexpr int DEMO_COORD = 32767, DEMO_SPRITE = 4096;
+// a kept mark: its 8 words, then its box in row pixels [panel * pw + x] and rows, inclusive
+enum { DM_BX0 = SVC_MARK_WORDS, DM_BX1, DM_BY0, DM_BY1, DM_WORDS };
+struct DemoArgs {
+    const uint8_t *small, *raw, *filt, *atlas;
+    const int32_t *map_of, *marks, *first;
+    uint8_t *out;
+    long long atlas_bytes;
+    int n, ph, pw, n_maps, n_marks, bands, bgr;
+};
+
+__device__ __forceinline__ int demo_mean_even(int a, int b) {          // (a + b) / 2, ties to even
+    const int s = a + b;
+    int v = s >> 1;
+    v += s & v & 1;
+    return v;
+}
+__device__ __forceinline__ int demo_blend(int c, int d, int a) { return (c * a + d * (255 - a) + 127) / 255; }
+
+// whether mark M covers pixel (x, y) of its panel (already inside M's box), and with which coverage
+__device__ __forceinline__ bool demo_covers(const DemoArgs &A, const int *M, int x, int y, int &a) {
+    const int kind = M[0] & 0xff, x0 = M[1], y0 = M[2], x1 = M[3], y1 = M[4], p = M[5];
+    a = 255;
+    if (kind == SVC_MARK_DISC) {
+        const int dx = x - x0, dy = y - y0;                               // (inside the box: |dx|, |dy| <= p <= 255)
+        return dx * dx + dy * dy <= p * p;
+    }
+    if (kind == SVC_MARK_LINE) {
+        const long long dx = x1 - x0, dy = y1 - y0, ex = x - x0, ey = y - y0, p2 = (long long)p * p;
+        const long long L = dx * dx + dy * dy, u = ex * dx + ey * dy;
+        if (L == 0 || u <= 0) return 4 * (ex * ex + ey * ey) <= p2;
+        if (u >= L) {
+            const long long fx = x - x1, fy = y - y1;
+            return 4 * (fx * fx + fy * fy) <= p2;
+        }
+        const long long c = ex * dy - ey * dx, ac = c < 0 ? -c : c;
+        return ac < (1ll << 31) && ac * ac <= ((p2 * L) >> 2);           // 4 c^2 <= p^2 L, p^2 L < 2^50
+    }
+    if (kind == SVC_MARK_RECT) return x == x0 || x == x1 || y == y0 || y == y1;
+    const long long at = (long long)p + (long long)(y - y0) * (M[6] & 0xffff) + (x - x0);      // SVC_MARK_TEXT
+    if (at < 0 || at >= A.atlas_bytes) return false;
+    a = A.atlas[at];
+    return true;
+}
+
+// pixel px (0 .. 5 pw - 1) of row y of frame f, marks applied -> c0 | c1 << 8 | c2 << 16 in output channel order
+__device__ __forceinline__ uint32_t demo_pixel(const DemoArgs &A, const int (*marks)[DM_WORDS], int n_kept, int f, long long m, int y, int px) {
+    const int pw = A.pw;
+    const int k = (px >= pw) + (px >= 2 * pw) + (px >= 3 * pw) + (px >= 4 * pw), x = px - k * pw;
+    int r, g, b;
+    if (k == 1 || k == 2) {
+        r = g = b = m >= 0 ? (k == 1 ? A.raw : A.filt)[((size_t)m * A.ph + y) * pw + x] : 0;
+    } else {
+        const uint8_t *S = A.small + (((size_t)f * A.ph + y) * pw + x) * 3;
+        r = S[0], g = S[1], b = S[2];
+        if (k == 3) {
+            const int v = m >= 0 ? A.filt[((size_t)m * A.ph + y) * pw + x] : 0;
+            r = demo_mean_even(r, v), g = demo_mean_even(g, v), b = demo_mean_even(b, v);
+        }
+    }
+    for (int i = 0; i < n_kept; ++i) {
+        const int *M = marks[i];                                          // (a uniform address: one LDS broadcast)
+        if (px < M[DM_BX0] || px > M[DM_BX1] || y < M[DM_BY0] || y > M[DM_BY1]) continue;
+        int a;
+        if (!demo_covers(A, M, x, y, a)) continue;
+        const int col = M[7];
+        r = demo_blend(col & 255, r, a), g = demo_blend((col >> 8) & 255, g, a), b = demo_blend((col >> 16) & 255, b, a);
+    }
+    return A.bgr ? (uint32_t)b | (uint32_t)g << 8 | (uint32_t)r << 16 : (uint32_t)r | (uint32_t)g << 8 | (uint32_t)b << 16;
+}
+
+__global__ __launch_bounds__(DEMO_TB) void k_demo_frames(DemoArgs A) {
+    __shared__ int s_marks[SVC_DEMO_MAX_MARKS][DM_WORDS];
+    __shared__ int s_kept;
+    const int tid = threadIdx.x, f = (int)blockIdx.x / A.bands, band = (int)blockIdx.x - f * A.bands;
+    const int yb0 = band * DEMO_ROWS, yb1 = min(A.ph, yb0 + DEMO_ROWS) - 1;
+    if (tid < 64) {                                                       // the first wavefront, whole: one lane per mark
+        const int lo = min(max(A.first[f], 0), A.n_marks), hi = min(max(A.first[f + 1], 0), A.n_marks);
+        const int cnt = min(max(hi - lo, 0), SVC_DEMO_MAX_MARKS);
+        int w[DM_WORDS];
+        bool keep = false;
+        if (tid < cnt) {
+            const int32_t *mp = A.marks + (size_t)(lo + tid) * SVC_MARK_WORDS;
+#pragma unroll
+            for (int i = 0; i < SVC_MARK_WORDS; ++i) w[i] = mp[i];
+            const int kind = w[0] & 0xff, panel = w[0] >> 8, p = w[5], q = w[6];
+            bool ok = w[0] >= 0 && kind <= SVC_MARK_TEXT && panel < SVC_DEMO_PANELS;
+#pragma unroll
+            for (int i = 1; i <= 4; ++i) ok = ok && w[i] >= -DEMO_COORD && w[i] <= DEMO_COORD;
+            int bx0 = 0, bx1 = -1, by0 = 0, by1 = -1;
+            if (ok) {
+                if (kind == SVC_MARK_DISC || kind == SVC_MARK_LINE) {
+                    ok = p >= 0 && p <= 255;
+                    const int rad = kind == SVC_MARK_DISC ? p : (p + 1) >> 1;
+                    const int ex = kind == SVC_MARK_DISC ? w[1] : w[3], ey = kind == SVC_MARK_DISC ? w[2] : w[4];
+                    bx0 = min(w[1], ex) - rad, bx1 = max(w[1], ex) + rad, by0 = min(w[2], ey) - rad, by1 = max(w[2], ey) + rad;
+                } else if (kind == SVC_MARK_RECT) {
+                    bx0 = w[1], bx1 = w[3], by0 = w[2], by1 = w[4];
+                } else {
+                    const int sw = q & 0xffff, sh = q >> 16;
+                    ok = q >= 0 && sw <= DEMO_SPRITE && sh <= DEMO_SPRITE;
+                    bx0 = w[1], bx1 = w[1] + sw - 1, by0 = w[2], by1 = w[2] + sh - 1;
+                }
+            }
+            bx0 = max(bx0, 0), bx1 = min(bx1, A.pw - 1), by0 = max(by0, yb0), by1 = min(by1, yb1);       // its own panel, this workgroup's rows
+            keep = ok && bx0 <= bx1 && by0 <= by1;
+            w[DM_BX0] = panel * A.pw + bx0, w[DM_BX1] = panel * A.pw + bx1, w[DM_BY0] = by0, w[DM_BY1] = by1;
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (keep) {
+            const int slot = __popcll(mask & ((1ull << tid) - 1ull));
+#pragma unroll
+            for (int i = 0; i < DM_WORDS; ++i) s_marks[slot][i] = w[i];
+        }
+        if (tid == 0) s_kept = __popcll(mask);
+    }
+    __syncthreads();
+    const int n_kept = s_kept;
+    const long long mm = A.map_of[f], m = mm >= 0 && mm < A.n_maps ? mm : -1;
+    const int rowb = 15 * A.pw;
+    for (int y = yb0; y <= yb1; ++y) {
+        uint8_t *row = A.out + ((size_t)f * A.ph + y) * (size_t)rowb;
+        const int head = min(rowb, (int)((16 - ((uintptr_t)row & 15)) & 15)), nvec = (rowb - head) >> 4, tail = rowb - head - 16 * nvec;
+        for (int i = tid; i < nvec + 2; i += DEMO_TB) {                  // item 0: the head; 1 .. nvec: the 16-byte groups; nvec + 1: the tail
+            const int b0 = i == 0 ? 0 : head + 16 * (min(i, nvec + 1) - 1), cnt = i == 0 ? head : i <= nvec ? 16 : tail;
+            if (cnt == 0) continue;
+            uint64_t lo = 0, hi = 0;                                      // bytes b0 .. b0 + 15 of the row
+            const int p0 = b0 / 3, p1 = (b0 + cnt - 1) / 3;
+            for (int p = p0; p <= p1; ++p) {
+                const uint32_t v = demo_pixel(A, s_marks, n_kept, f, m, y, p);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int q = 3 * p + c - b0;
+                    const uint64_t byte = (v >> (8 * c)) & 255u;
+                    if (q >= 0 && q < 8) lo |= byte << (8 * q);
+                    else if (q >= 8 && q < 16) hi |= byte << (8 * (q - 8));
+                }
+            }
+            if (cnt == 16) {
+                *(uint4 *)(row + b0) = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+            } else {
+                for (int q = 0; q < cnt; ++q) row[b0 + q] = (uint8_t)(q < 8 ? lo >> (8 * q) : hi >> (8 * (q - 8)));
+            }
+        }
+    }
+}
+
+// No handle: no weights, no scratch, no state -- callable from any thread on any stream of the current device.
+extern "C" int svc_demo_frames_u8(const uint8_t *small, int n, int ph, int pw, const uint8_t *raw, const uint8_t *filt, int n_maps,
+                                  const int32_t *map_of, const int32_t *marks, int n_marks, const int32_t *first,
+                                  const uint8_t *atlas, size_t atlas_bytes, uint8_t *out, int flags, void *stream) {
+    const char *rule = nullptr;
+    if (n < 0 || n_maps < 0 || n_marks < 0) rule = "a count (n, n_maps, n_marks) is negative";
+    else if (ph < 1 || pw < 1) rule = "ph or pw is below 1";
+    else if (pw > 0x7fffffff / 15) rule = "a row of 15 pw bytes is beyond 2^31 - 1";
+    else if (flags & ~SVC_RENDER_BGR) rule = "flags has bits other than SVC_RENDER_BGR";
+    else if (n > 0 && (!small || !map_of || !first || !out)) rule = "small, map_of, first or out is NULL with n > 0";
+    else if (n > 0 && n_maps > 0 && (!raw || !filt)) rule = "raw or filt is NULL with n_maps > 0";
+    else if (n > 0 && n_marks > 0 && !marks) rule = "marks is NULL with n_marks > 0";
+    else if (n > 0 && atlas_bytes > 0 && !atlas) rule = "atlas is NULL with atlas_bytes > 0";
+    const int bands = rule ? 0 : (ph - 1) / DEMO_ROWS + 1;
+    if (!rule && (long long)n * bands > 0x7fffffffll) rule = "n * ceil(ph / 4) workgroups are beyond 2^31 - 1";
+    if (rule) {
+        svc_set_error("svc_demo_frames_u8: %s (n %d, ph %d, pw %d, n_maps %d, n_marks %d, flags %d)", rule, n, ph, pw, n_maps, n_marks, flags);
+        return SVC_E_INVALID;
+    }
+    if (n == 0) return SVC_OK;
+    const long long ab = atlas_bytes > (size_t)0x7fffffffffffffffll ? 0x7fffffffffffffffll : (long long)atlas_bytes;
+    const DemoArgs A = {small, raw, filt, atlas, map_of, marks, first, out, ab, n, ph, pw, n_maps, n_marks, bands, flags & SVC_RENDER_BGR};
+    k_demo_frames<<<(unsigned)(n * bands), DEMO_TB, 0, (hipStream_t)stream>>>(A);
+    SVC_CHECK_LAUNCH();
+    return SVC_OK;
 }

@@ -771,3 +771,70 @@ def focus_jumps(maps, xy, min_d):
         out = torch.empty((n, 2), dtype=torch.int32, device=maps.device)
         _lib.check(lib.svc_focus_jumps_u8(_ptr(maps), n, h, w, _ptr(xy), float(min_d), _ptr(out), _stream()))
     return out
+
+
+def _demo_i32(v, shape, name, dev):
+    """A host array / list -> contiguous int32 CUDA tensor of `shape` on dev (a tensor is checked, not copied)."""
+    if not torch.is_tensor(v):
+        a = np.ascontiguousarray(v, np.int32)
+        if a.shape != shape:
+            raise ValueError('%s must be int32 %s, not %s' % (name, list(shape), a.shape))
+        return torch.from_numpy(a).to(dev)
+    if v.dtype != torch.int32 or tuple(v.shape) != shape or not v.is_contiguous() or v.device != dev:
+        raise ValueError('%s must be a contiguous int32 %s tensor on %s, not %s %s on %s' % (name, list(shape), dev, v.dtype, tuple(v.shape), v.device))
+    return v
+
+
+def demo_frames(small, raw, filt, map_of, marks, first, atlas, bgr=False, out=None):
+    """The five-panel demo frames (svc_demo_frames_u8; include/svc.h states the panels and the marks): small = the frames at the
+    process size, a contiguous CUDA uint8 [n, ph, pw, 3] RGB tensor (Engine.resize_frames makes it); raw, filt = the raw and the
+    filtered maps, contiguous CUDA uint8 [n_maps, ph, pw] each; map_of int32 [n] = the map of every frame (outside [0, n_maps): an
+    all-zero map); marks int32 [k, 8] and first int32 [n + 1] = the marks of frame f are rows first[f] .. first[f + 1] (render.demo_marks
+    makes the three); atlas = the uint8 coverage sprites the TEXT marks point into (render.demo_atlas), or None.  map_of, marks,
+    first and atlas are CUDA tensors on small's device, or host arrays that are uploaded there.  bgr: every pixel stored (b, g, r).
+    -> out, a contiguous CUDA uint8 [n, ph, 5 * pw, 3] tensor (allocated unless given).  Every shape, dtype and device is checked
+    first: ValueError before any device work.  Runs on small's device and the current stream; no handle, no scratch."""
+    lib = _lib.load()
+    if not hasattr(lib, 'svc_demo_frames_u8'):
+        raise _lib.SvcError('%s lacks svc_demo_frames_u8: the demo frames need a build that has it' % _lib.LIB_PATH)
+
+    def u8(t, name, dims):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == dims):
+            raise ValueError('%s must be a contiguous CUDA uint8 tensor of %d dimensions' % (name, dims))
+    u8(small, 'small', 4)
+    n, ph, pw, ch = (int(v) for v in small.shape)
+    dev = small.device
+    if ch != 3 or ph < 1 or pw < 1:
+        raise ValueError('small must be [n, ph, pw, 3] with ph, pw >= 1, not %s' % (tuple(small.shape),))
+    u8(raw, 'raw', 3)
+    u8(filt, 'filt', 3)
+    n_maps = int(raw.shape[0])
+    for t, name in ((raw, 'raw'), (filt, 'filt')):
+        if tuple(t.shape) != (n_maps, ph, pw) or t.device != dev:
+            raise ValueError('%s must be [%d, %d, %d] on %s, not %s on %s' % (name, n_maps, ph, pw, dev, tuple(t.shape), t.device))
+    k = int(marks.shape[0]) if hasattr(marks, 'shape') and len(marks.shape) == 2 else len(marks)
+    map_of = _demo_i32(map_of, (n,), 'map_of', dev)
+    marks = _demo_i32(marks if k else np.zeros((0, _lib.MARK_WORDS), np.int32), (k, _lib.MARK_WORDS), 'marks', dev)
+    first = _demo_i32(first, (n + 1,), 'first', dev)
+    if atlas is not None:
+        if not torch.is_tensor(atlas):
+            a = np.ascontiguousarray(atlas)
+            if a.dtype != np.uint8 or a.ndim != 1:
+                raise ValueError('atlas must be uint8 [bytes], not %s %s' % (a.dtype, a.shape))
+            atlas = torch.from_numpy(a).to(dev)
+        u8(atlas, 'atlas', 1)
+        if atlas.device != dev:
+            raise ValueError('atlas must be on %s, not %s' % (dev, atlas.device))
+    shape = (n, ph, 5 * pw, 3)
+    if out is not None:
+        u8(out, 'out', 4)
+        if tuple(out.shape) != shape or out.device != dev:
+            raise ValueError('out must be %s on %s, not %s on %s' % (list(shape), dev, tuple(out.shape), out.device))
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        n_atlas = int(atlas.numel()) if atlas is not None else 0
+        _lib.check(lib.svc_demo_frames_u8(_ptr(small), n, ph, pw, _ptr(raw) if n_maps else None, _ptr(filt) if n_maps else None, n_maps,
+                                          _ptr(map_of), _ptr(marks) if k else None, k, _ptr(first), _ptr(atlas) if n_atlas else None, n_atlas,
+                                          _ptr(out), RENDER_BGR if bgr else 0, _stream()))
+    return out

@@ -154,20 +154,25 @@ class _OutRing:
             self._one(staged[s:s + cap], boxes[s:s + cap], bw, bh, bgr)
 
     def _one(self, staged, boxes, bw, bh, bgr):
+        if self.subpixel:
+            self.put(int(staged.shape[0]), lambda dst: self.engine.render_windows(
+                staged, boxes, (bw, bh), (int(self.ring['key'][1]), int(self.ring['key'][2])), bgr, dst, self.pix_fmt, self.out_fmt, self.layout,
+                self.colour, self.out_colour, self.out_layout))
+        else:
+            self.put(int(staged.shape[0]), lambda dst: self.engine._render(
+                staged, boxes, bw, bh, dst, bgr, self.pix_fmt, self.out_fmt, self.layout, self.interp, self.colour, self.out_colour, self.out_layout))
+
+    def put(self, m, fill):
+        """One chunk of m <= cap frames: fill(dst) enqueues on the current stream whatever writes them into dst, the device slot's
+        first m frames; the ring copies them back and delivers them in order.  (What push() does per chunk; render_demo's door.)"""
         import torch
-        m = int(staged.shape[0])
         slot = self.c & 1
         compute = torch.cuda.current_stream(self.dev)
         side = self.ring['stream']
         if self.used[slot]:
             compute.wait_event(self.copied[slot])           # the device slot's previous D2H has read it
         dst = self.ring['dev'][slot][:m]
-        if self.subpixel:
-            self.engine.render_windows(staged, boxes, (bw, bh), (int(self.ring['key'][1]), int(self.ring['key'][2])), bgr, dst, self.pix_fmt,
-                                       self.out_fmt, self.layout, self.colour, self.out_colour, self.out_layout)
-        else:
-            self.engine._render(staged, boxes, bw, bh, dst, bgr, self.pix_fmt, self.out_fmt, self.layout, self.interp, self.colour, self.out_colour,
-                                self.out_layout)
+        fill(dst)
         self.rendered[slot].record(compute)
         with torch.cuda.stream(side):
             side.wait_event(self.rendered[slot])
@@ -188,3 +193,177 @@ class _OutRing:
         if self.pending is not None:
             self._deliver(self.pending)
             self.pending = None
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# The five-panel demo video (sc_renderer, smartVidCrop.py:1924-2126): frame | raw saliency | filtered map with the centre's
+# trail, the jump score and the cut labels | overlay | frame with the final window.  The host states WHAT is drawn, per frame, as
+# a list of integer marks (demo_marks); the device composes the panels and draws the marks (ops.demo_frames:
+# svc_demo_frames_u8, include/svc.h states the pixel rules).  The marks are this package's own rasterising rules, not
+# OpenCV's: no anti-aliased circles and lines, and the labels are Pillow's default font, not the Hershey glyphs.
+# --------------------------------------------------------------------------------------------------------------------------
+DEMO_FONT_POS, DEMO_FONT_POS2, DEMO_FONT_POS3, DEMO_FONT_POS4 = (2, 15), (2, 30), (2, 45), (2, 60)      # smartVidCrop.py:1858-1862
+DEMO_TITLES = ((1, 'saliency'), (2, 'filtered'), (3, 'overlayed'), (4, 'final'))                        # (panel, title), :2086-2117
+DEMO_STRINGS = tuple(t for _, t in DEMO_TITLES) + ('jump:', 'jump', 'orig. cut') + tuple('0123456789')
+_DEMO_ATLAS = None
+
+
+def demo_atlas():
+    """The label sprites, built once per process with Pillow's default font -> (atlas uint8 [bytes], {string: (offset, w, h)}) for
+    every string of DEMO_STRINGS.  A sprite is w x h coverages (0 .. 255), row-major at atlas[offset:]: the string drawn at (2, 1)
+    in a box of its advance width + 4 and the font's line height + 2 (a margin that keeps an empty pixel all around the glyphs'
+    anti-aliased edges, for the outline), so every sprite has the same height and baseline and strings are composed by placing
+    them w - 4 apart ('jump:%d' from 'jump:' and the digits).  Directly behind it, at offset + w * h
+    and of the same size, lies its 3 x 3 dilation (the maximum over the neighbourhood): the black outline drawn under the label."""
+    global _DEMO_ATLAS
+    if _DEMO_ATLAS is None:
+        from PIL import Image, ImageDraw, ImageFont
+        font = ImageFont.load_default()
+        box = font.getbbox('Mgjy|0123456789')
+        line = int(box[3]) + 1
+        parts, where, pos = [], {}, 0
+        for s in DEMO_STRINGS:
+            w, h = int(np.ceil(font.getlength(s))) + 4, line + 2
+            img = Image.new('L', (w, h), 0)
+            ImageDraw.Draw(img).text((2, 1), s, fill=255, font=font)
+            a = np.asarray(img, np.uint8)
+            pad = np.pad(a, 1)
+            d = np.max([pad[1 + dy:1 + dy + h, 1 + dx:1 + dx + w] for dy in (-1, 0, 1) for dx in (-1, 0, 1)], axis=0).astype(np.uint8)
+            where[s] = (pos, w, h)
+            parts += [a.reshape(-1), d.reshape(-1)]
+            pos += 2 * w * h
+        _DEMO_ATLAS = (np.ascontiguousarray(np.concatenate(parts)), where)
+    return _DEMO_ATLAS
+
+
+def _demo_label(rows, where, panel, pos, strings):
+    """The label made of `strings` side by side, its bottom-left corner at pos (cv2.putText's org): every string's dilated
+    sprite in black, then every string in white."""
+    from ._lib import MARK_TEXT
+    for dilated, colour in ((1, 0), (0, 0xffffff)):
+        x = int(pos[0]) - 2
+        for s in strings:
+            off, w, h = where[s]
+            rows.append((MARK_TEXT | panel << 8, x, int(pos[1]) - (h - 2), 0, 0, off + dilated * w * h, w | h << 16, colour))
+            x += w - 4
+
+
+def demo_marks(VD, CP):
+    """What sc_renderer draws on the demo frames (smartVidCrop.py:1941-2117), in its draw order, as the marks ops.demo_frames
+    takes -> (marks int32 [k, 8], first int32 [fc + 1], map_of int32 [fc]): the marks of frame i are rows first[i] .. first[i + 1],
+    its maps are those of index map_of[i] = VD['inds_to_orig'][i].  int() truncation everywhere, as there.  With m = map_of[i],
+    T = past_steps - j, past_steps = int(fr / 5) and the colour level max(0, 255 - 20 j - 20) of trail step j = 1 .. past_steps - 1:
+      panel 2   where (dxnf, dynf)[m] != (dx, dy)[m]: the non-fixed centre in red -- a disc of radius 5, trail discs of radius
+                2 + T // 2 at m - j (when i - j >= 0), trail lines of thickness T from m - j to m - j - 1 (when i - j > 0); then the
+                centre (dx, dy) the same in green; 'jump:%d' % jumps[m] at DEMO_FONT_POS2; 'jump' at DEMO_FONT_POS3 while its counter
+                runs (set to fade_len = fr by a jump below CP['foces_stab_t'], one less per frame) and 'orig. cut' at DEMO_FONT_POS4
+                likewise (set by a frame index found in VD['segm_backup'])
+      panel 3   a green disc of radius 3 at the centre
+      panel 4   a green disc of radius 3 at (int(dxs * scale_w), int(dys * scale_h)) and the rectangle (int(bx1 * scale_w) + 1,
+                int(by1 * scale_h) + 1, int(bx2 * scale_w) - 1, int(by2 * scale_h) - 1)
+      panels 1 - 4   their titles at DEMO_FONT_POS
+    Every label is its black 3 x 3-dilated sprite, then the white one (demo_atlas).  The marks are opaque: the reference's fading
+    alpha lands in a channel that COLOR_BGRA2BGR drops (:2054).  A frame takes at most 64 marks (svc_demo_frames_u8): at fr >= 45
+    the two trails alone reach that, and what comes later in the order -- the titles last -- is not drawn.
+    Deviations from the reference, on purpose:
+      * where it indexes before the start of a list (m - j < 0, m - j - 1 < 0: Python wraps around to the video's END), nothing is drawn;
+      * 'jump' is drawn at DEMO_FONT_POS3 in both colours (the reference puts its white copy at DEMO_FONT_POS6, 45 rows lower)."""
+    from ._lib import MARK_DISC, MARK_LINE, MARK_RECT, MARK_WORDS
+    _, where = demo_atlas()
+    fr, fc = VD['fr'], int(VD['fc'])
+    m = [int(v) for v in VD['inds_to_orig'][:fc]]
+    scale_h, scale_w = float(VD['h_process']) / float(VD['h_orig']), float(VD['w_process']) / float(VD['w_orig'])
+    fade_len, past_steps = fr, int(fr / 5.0)
+    cuts = set(int(v) for v in np.asarray(VD['segm_backup']).reshape(-1))
+    bbs = VD['bbs_np'] if 'bbs_np' in VD else VD['bbs']
+    green = 255 << 8
+    fade_jump = fade_cut = 0
+    rows, first = [], [0]
+
+    def trail(xs, ys, i, mi, shift):
+        rows.append((MARK_DISC | 2 << 8, int(xs[mi]), int(ys[mi]), 0, 0, 5, 0, 255 << shift))
+        for j in range(1, past_steps):
+            if i - j >= 0 and mi - j >= 0:
+                rows.append((MARK_DISC | 2 << 8, int(xs[mi - j]), int(ys[mi - j]), 0, 0, 2 + (past_steps - j) // 2, 0, max(0, 255 - 20 * j - 20) << shift))
+        for j in range(1, past_steps):
+            if i - j > 0 and mi - j - 1 >= 0:
+                rows.append((MARK_LINE | 2 << 8, int(xs[mi - j]), int(ys[mi - j]), int(xs[mi - j - 1]), int(ys[mi - j - 1]), past_steps - j, 0,
+                             max(0, 255 - 20 * j - 20) << shift))
+    for i in range(fc):
+        mi = m[i]
+        if VD['dxnf'][mi] != VD['dx'][mi] or VD['dynf'][mi] != VD['dy'][mi]:
+            trail(VD['dxnf'], VD['dynf'], i, mi, 0)
+        trail(VD['dx'], VD['dy'], i, mi, 8)
+        _demo_label(rows, where, 2, DEMO_FONT_POS2, ['jump:'] + list('%d' % VD['jumps'][mi]))
+        if VD['jumps'][mi] < CP['foces_stab_t']:
+            fade_jump = fade_len
+        if fade_jump > 0:
+            _demo_label(rows, where, 2, DEMO_FONT_POS3, ['jump'])
+            fade_jump -= 1
+        if i in cuts:
+            fade_cut = fade_len
+        if fade_cut > 0:
+            _demo_label(rows, where, 2, DEMO_FONT_POS4, ['orig. cut'])
+            fade_cut -= 1
+        rows.append((MARK_DISC | 3 << 8, int(VD['dx'][mi]), int(VD['dy'][mi]), 0, 0, 3, 0, green))
+        bx1, by1, bx2, by2 = (int(v) for v in bbs[i])
+        rows.append((MARK_DISC | 4 << 8, int(VD['dxs'][i] * scale_w), int(VD['dys'][i] * scale_h), 0, 0, 3, 0, green))
+        rows.append((MARK_RECT | 4 << 8, int(bx1 * scale_w) + 1, int(by1 * scale_h) + 1, int(bx2 * scale_w) - 1, int(by2 * scale_h) - 1, 0, 0, green))
+        for panel, title in DEMO_TITLES:
+            _demo_label(rows, where, panel, DEMO_FONT_POS, [title])
+        first.append(len(rows))
+    marks = np.clip(np.asarray(rows, np.int64).reshape(-1, MARK_WORDS), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
+    return marks, np.asarray(first, np.int32), np.asarray(m, np.int32)
+
+
+def render_demo(video, VD, CP, engine=None, sink=None, chunk=32, bgr=False):
+    """The demo frames of VD['fc'] frames of `video` (what render_video takes: any container, format, layout and colour) ->
+    numpy uint8 [fc, h_process, 5 * w_process, 3] without a sink, else None: sink(chunk uint8 [m, h_process, 5 * w_process, 3]) is
+    called in frame order with views of a pinned buffer, as render_video's.  Per chunk: the frames are staged as for render_video,
+    brought to the process size by the ingest's own resize (engine.resize_frames: panel 0 is bit for bit the ingest's small frame),
+    composed with VD['smaps_orig_dev'] (the raw maps), VD['smaps_dev'] (the filtered ones) and the marks of demo_marks(VD, CP) by one
+    launch (ops.demo_frames), and copied back through the renderer's pinned double buffers.  bgr: (b, g, r) pixels.
+    VD['smaps_orig_dev'] is kept by after_ingest(keep_raw=True) -- smart_vid_crop(demo_fn=) asks for it; a VD without it, or with
+    maps of another shape than (h_process, w_process), raises ValueError before any device work."""
+    from .frames import FrameSource
+    if not dict.__contains__(VD, 'smaps_orig_dev') or VD['smaps_orig_dev'] is None:
+        raise ValueError("render_demo needs the raw maps VD['smaps_orig_dev'] (after_ingest(keep_raw=True) keeps them; "
+                         "the threshold overwrites VD['smaps_dev'] in place)")
+    src = FrameSource.of(video).whole()
+    fc, ph, pw = int(VD['fc']), int(VD['h_process']), int(VD['w_process'])
+    if src.n < fc:
+        raise ValueError('the container holds %d frames, the video has %d' % (src.n, fc))
+    raw, filt = VD['smaps_orig_dev'], VD['smaps_dev']
+    if tuple(raw.shape) != tuple(filt.shape) or tuple(filt.shape[1:]) != (ph, pw):
+        raise ValueError('maps of shape %s / %s for a process size of %d x %d' % (tuple(raw.shape), tuple(filt.shape), pw, ph))
+    marks, first, map_of = demo_marks(VD, CP)
+    atlas, _ = demo_atlas()
+    shape = (ph, 5 * pw, 3)
+    chunk = max(1, min(int(chunk), _MAX_CHUNK, _RING_BYTES // int(np.prod(shape))))
+    result = None
+    if sink is None:
+        result = np.empty((fc,) + shape, np.uint8)
+
+        def sink(c, _pos=[0]):
+            result[_pos[0]:_pos[0] + c.shape[0]] = c
+            _pos[0] += c.shape[0]
+    if fc == 0:
+        return result
+    import torch
+    from . import ops, smartVidCrop as S
+    engine = engine or S.get_engine()
+    dev = engine.device
+    marks_d, first_d, map_d, atlas_d = (torch.from_numpy(a).to(dev) for a in (marks, first, map_of, atlas))    # (once per video)
+    out = _OutRing(engine, chunk, ph, 5 * pw, sink)
+    cap = out.ring['key'][0]
+
+    def consume(staged, s):
+        for a in range(s, s + int(staged.shape[0]), cap):      # (a host feed stages at most 32 frames, the ring holds `chunk`)
+            part = staged[a - s:a - s + cap]
+            k = int(part.shape[0])
+            small = engine.resize_frames(part, ph, pw, src.pix_fmt, src.layout, src.colour)
+            # (a chunk's frames name their rows of the video's one mark list: first[a .. a + k])
+            out.put(k, lambda dst: ops.demo_frames(small, raw, filt, map_d[a:a + k], marks_d, first_d[a:a + k + 1], atlas_d, bgr, dst))
+    src.chunks(engine, fc, chunk, consume)
+    out.flush()
+    return result

@@ -61,6 +61,7 @@ _tls = threading.local()       # per-thread stage timers (the reference keeps on
 
 _video_reader = None
 _video_writer = None
+_demo_writer = None
 
 
 def set_video_reader(fn):
@@ -78,6 +79,15 @@ def set_video_writer(fn):
     ``fn(path, fr, (w, h), pix_fmt='nv12')`` and the frames are NV12 [h*3/2,w] u8 (ingest.write_frames_raw).  None removes it."""
     global _video_writer
     _video_writer = fn
+
+
+def set_demo_writer(fn):
+    """Install the encode hand-off of smart_vid_crop(..., save_vid=True, demo_fn=...), set_video_writer's sibling for the five-panel
+    demo video: ``fn(demo_fn, fr, (5 * w_process, h_process))`` returns an object with ``write(frame_rgb_u8)`` and ``release()``;
+    it receives every frame of render.render_demo, RGB [h_process, 5 * w_process, 3] u8, in order (ingest.write_frames_pillow takes
+    them).  None (the default) removes it: demo_fn then raises NotImplementedError."""
+    global _demo_writer
+    _demo_writer = fn
 
 
 def sc_init_time():
@@ -588,7 +598,14 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
         out_subpixel: both modes render the windows at their sub-pixel origins VD['bbs_q8'] (render.render_video(subpixel=True)):
         a crop written at an out_size follows the smoothed pan without the steps of whole-pixel windows.  With
         out_interp='lanczos' it raises ValueError before any work.  VD and the results are the same either way.
-    demo_fn (the five-panel demo) and copy_sound (ffmpeg) with a render raise NotImplementedError."""
+    demo_fn (with save_vid; independent of final_vid_fn, as in the reference): the five-panel demo video -- frame, raw saliency
+    map, filtered map with the centre's trail and the jump score, overlay, final window -- composed on the device
+    (render.render_demo; include/svc.h: svc_demo_frames_u8) and handed, every frame RGB [h_process, 5 * w_process, 3] u8, to the
+    writer installed with set_demo_writer(): fn(demo_fn, VD['fr'], (5 * w_process, h_process)); results['t_demo'] is its time.  The
+    raw maps are then kept on the device as VD['smaps_orig_dev'].  No demo writer installed: NotImplementedError; with
+    stream_batch (that ingest thresholds the maps): ValueError; both before any work.  A ``.pkl`` input renders no demo, as in
+    the reference (:1840).  VD['bbs'] and the results are the same with and without it.
+    copy_sound (ffmpeg) with a render raises NotImplementedError."""
     import torch
     sc_init_time()
     results = {}
@@ -597,8 +614,15 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
     if CP['exit_on_spread_sal'] or CP['exit_on_low_cvrg']:
         raise NotImplementedError(GATES_REFUSED)
     if save_vid and demo_fn:
-        raise NotImplementedError('the five-panel demo video (cv2 drawing and text) is not rendered by this package; '
-                                  'pass demo_fn=\'\'')
+        if _demo_writer is None:
+            raise NotImplementedError('the five-panel demo video (cv2 drawing and text) is not rendered by this package; '
+                                      'pass demo_fn=\'\' -- or, for the demo frames this package composes itself '
+                                      '(render.render_demo), install one with set_demo_writer()')
+        if stream_batch:
+            raise ValueError('demo_fn shows the raw saliency maps, and the streaming ingest (stream_batch=%r) thresholds them '
+                             'as they are made: pass stream_batch=0' % (stream_batch,))
+    # (a .pkl input opens no demo writer in the reference, :1840: no demo is rendered for one, silently)
+    render_demo = bool(save_vid and demo_fn) and not (isinstance(video_path, str) and video_path.endswith('.pkl'))
     render_pkl = render_writer = False
     from .ops import DEFAULT_COLOUR, FrameLayout, check_interp, frame_colour, out_frame_shape, out_layout_of
     out_frame_shape(out_pix_fmt, *((2, 2) if out_size is None else (out_size[1], out_size[0])))     # unknown format, odd out_size: ValueError
@@ -684,7 +708,7 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
                 pickle.dump(out, fp)
     if callback_status is not None and callback_session is not None:
         callback_status(callback_session, 'sc', 'SC PROCESSING', 'smart-cropping main process')
-    VD, results = after_ingest(VD, CP, engine, verbose=verbose)
+    VD, results = after_ingest(VD, CP, engine, verbose=verbose, **(dict(keep_raw=True) if render_demo else {}))
     if callback_status is not None and callback_session is not None:
         callback_status(callback_session, 'sc', 'SC RENDERING', 'smart-cropping rendering')
     if render_pkl or render_writer:
@@ -714,6 +738,16 @@ def smart_vid_crop(video_path, CP=None, demo_fn='', final_vid_fn='', plots_fn=''
                 writer.release()
         sc_register_time(t, 'render')
         results['t_render'] = sc_all_times(VD['fc'] / VD['fr'])['render']
+    if render_demo:                         # independent of final_vid_fn, as in the reference (:1840-1849)
+        from . import render
+        t = time.perf_counter()
+        writer = _demo_writer(demo_fn, VD['fr'], (5 * int(VD['w_process']), int(VD['h_process'])))
+        try:
+            render.render_demo(video, VD, CP, engine=engine, sink=lambda chunk: [writer.write(f) for f in chunk])
+        finally:
+            writer.release()
+        sc_register_time(t, 'demo')
+        results['t_demo'] = sc_all_times(VD['fc'] / VD['fr'])['demo']
     return VD, results
 
 
@@ -728,13 +762,18 @@ def feature_cache_key(video, CP, engine):
     return key
 
 
-def after_ingest(VD, CP, engine, verbose=False):
+def after_ingest(VD, CP, engine, verbose=False, keep_raw=False):
     """Everything of smart_vid_crop behind the ingest (smartVidCrop.py:2293-2614 without the rendering): destination
     size, threshold + cluster filter + centres on the device (skipped when the ingest or the multi-video scheduler has
     run them already: VD['xy_stream']), then the host stages -- empty-centre fill, focus stability (its jump statistics from
     the maps on the device unless SVC_FOCUS=host), interpolation, low-pass, LOESS, boxes.  One function for the one-video call and for retargetvid_amd/scheduler.py, so that both give
-    the same windows by construction.  -> (VD, smart_crop_results)."""
+    the same windows by construction.  -> (VD, smart_crop_results).
+    keep_raw: a device copy of the raw maps stays in VD['smaps_orig_dev'] (the reference's smaps_orig, sc_threshold(copy=True),
+    :2335), taken before the threshold overwrites VD['smaps_dev'] in place -- what render.render_demo shows in its second panel.
+    With maps that arrive thresholded (VD['xy_stream']: the streaming ingest, the scheduler) it raises ValueError."""
     results = {}
+    if keep_raw and 'xy_stream' in VD:
+        raise ValueError("keep_raw: the maps of this VD arrive thresholded (VD['xy_stream']); there are no raw maps to keep")
     VD['segm_backup'] = VD['segmentation'].copy()
 
     t = time.perf_counter()
@@ -757,6 +796,8 @@ def after_ingest(VD, CP, engine, verbose=False):
         tt = int(CP['t_threshold'])
         if maps.numel() and 2 <= tt <= 254:             # (t = 1: level 0 is also the value of the all-zero rows the off-by-one leaves)
             near = (maps - (tt - 1)).le_(2).sum()
+        if keep_raw:
+            VD['smaps_orig_dev'] = maps.clone()
         engine.threshold_(maps, CP['t_threshold'])
     sc_register_time(t, '_thresh')                     # (enqueue time; the stream is synchronised by the D2H below)
 
